@@ -6,12 +6,15 @@ kmer_extract -> hit_count -> prob_lookup -> taxon_prefix + lineage walk -> resul
 of synthetic queries per GPU, with the queries and the index already resident in HBM when the timed region starts
 (`--host-exact-match`: the lookup on the host instead, once, untimed -- rounds 1 and 2).
 
-The line verifies itself (SURVEY.md 8d, rank 0 at N = 1): after the timed region `parity_sample` holds the LAST TIMED STEP, as the device
+A plain run sets up, warms up, times `--steps` steps and prints the line; everything below that is not the headline runs only with
+`--full`, after the timed region.  `--dump-outputs DIR` writes the results of the last timed step as .npy files (dump_outputs).
+
+With `--full` the line verifies itself (SURVEY.md 8d, rank 0 at N = 1): after the timed region `parity_sample` holds the LAST TIMED STEP, as the device
 left it, against the CPU oracle -- the size-independent properties of all its results, and a seeded 2 000-query sample of its last
 sub-batch: hit counts of every visited tile bit-exact, no unvisited tile above the query's threshold, histogram, probabilities, result
 rows (raxtax_amd/checks.py).  A violation is printed in the line and the process exits with status 4.
 
-Beside `value` the line carries its own caveats (rank 0 at N = 1, `--no-extras` leaves them out): `value_incl_h2d` (the
+Beside `value` a `--full` line carries its own caveats (rank 0 at N = 1, `--no-extras` leaves them out): `value_incl_h2d` (the
 queries cross PCIe every step: staged beside the running step, and not overlapped), `value_end_to_end` (host buffers -> rtx_raxtax ->
 formatted result strings, no disk; busy time of every pipeline stage), `value_unpruned` (RTX_OPT_TILE_PRUNE = 0: every tile counted), a
 sweep over the divergence of the queries from their source reference (`divergence_sweep`: the tile pruning depends on how far a query's
@@ -29,8 +32,8 @@ queries, histograms are all-reduced and boundary prefix sums all-gathered per su
 already running under a launcher; the parent never touches the GPU.
 
 One JSON line on rank 0: metric/value (whole-job queries/s), ms_per_step, `roofline` of the dominant kernel
-(hit_count) and `cpu_baseline` (the CPU oracle, a C port of the reference algorithm, timed on this host's cores on a
-bounded sample).  How every number of `roofline` is derived: DESIGN.md section 5.
+(hit_count) and, with `--full`, `cpu_baseline` (the CPU oracle, a C port of the reference algorithm, timed on this host's cores on a
+bounded sample; null in a plain line).  How every number of `roofline` is derived: DESIGN.md section 5.
 """
 from __future__ import annotations
 
@@ -101,7 +104,7 @@ def parse():
                     help="restrict this process (and every thread it starts: HIP runtime, library pools) to its first C CPUs with sched_setaffinity before "
                          "anything is loaded -- the stricter rehearsal of a rank's CPU share (0 = leave the affinity mask alone)")
     ap.add_argument("--no-parity", action="store_true", help="N > 1: skip the self-check of the line (rank 0 holds a seeded sample of every rank's gathered records against the oracle)")
-    ap.add_argument("--no-extras", action="store_true", help="only the headline: no H2D / end-to-end / unpruned legs, no divergence sweep")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no H2D / end-to-end / unpruned legs, no divergence sweep")
     ap.add_argument("--host-exact-match", action="store_true",
                     help="Tree.sequences.get on the host, once, untimed (rounds 1-2); default: on the device inside the timed step")
     ap.add_argument("--e2e-chunk", type=int, default=131072, help="queries per device batch of the end-to-end leg (rtx_raxtax chunk_size)")
@@ -118,6 +121,15 @@ def parse():
                     help="with --shard-db: refs = contiguous reference ranges per GPU, all-reduce of histograms + all-gather of "
                          "prefix sums (SURVEY.md 8e mode B, default); kmers = k-mer ranges per GPU, all-reduce of the u16 "
                          "per-reference hit counts (mode A, the literal wording of BASELINE.json configs[4])")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline, after the timed region: parity_sample against the oracle, cpu_baseline and the "
+                         "caveat legs (value_incl_h2d, value_end_to_end, value_unpruned, divergence_sweep, value_mixed_lengths, "
+                         "value_real_composition, value_long_reads); --no-parity, --no-cpu-baseline and --no-extras leave parts of it out. "
+                         "Default: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0's results) to DIR/<name>.npy in "
+                         "float32 / float64: per-query arrays of every query (a seeded sample beyond 1 048 576), the result rows of a "
+                         "seeded sample of 16 384 queries; at most 64 MB (see dump_outputs)")
     args = ap.parse_args()
     refs, queries, name = CONFIGS[args.config]
     args.config_name = name if not (args.refs or args.queries) else "custom size"
@@ -145,6 +157,54 @@ def emit_fasta(args) -> int:
                       "sha256_of_the_encoded_arrays": sha.hexdigest(),
                       "reference_command": f"raxtax -d {out / 'db.fasta'} -i {out / 'queries.fasta'} -t 0 --redo"}))
     return 0
+
+
+DUMP_MAX_BYTES = 64 << 20
+DUMP_QUERIES = 1 << 20      # per-query arrays: every query up to this many, else a seeded sample of this size
+DUMP_ROW_QUERIES = 16384    # result rows: those of a seeded sample of this many queries
+
+
+def dump_outputs(out_dir, rx, view) -> dict:
+    """--dump-outputs DIR: the results of the last timed step as a caller of the step receives them (rx.Result of the view, rows in query
+    order), as .npy files in float32 (integers below 2^24) and float64, so that two builds can be compared output for output:
+      query_ids, t, status, global_signal, n_rows      per query: every query, or a seeded sample of DUMP_QUERIES (seed 20265)
+      row_query_ids, row_lineage, row_node, row_depth,  the rows of a seeded sample of DUMP_ROW_QUERIES queries (seed 20266), in query
+      row_local_signal, row_conf                        order; row_conf (rows x deepest lineage) is zero beyond a row's depth
+    The samples depend on the number of queries alone; the row sample is halved until everything fits in DUMP_MAX_BYTES."""
+    res = rx.Result(view)
+    nq = int(res.n_queries)
+
+    def sample(k, seed):
+        if nq <= k:
+            return np.arange(nq, dtype=np.int64)
+        return np.sort(np.random.default_rng(seed).choice(nq, k, replace=False)).astype(np.int64)
+
+    row_off = res.row_off.astype(np.int64)
+    n_rows = np.diff(row_off)
+    q = sample(DUMP_QUERIES, 20265)
+    arrays = {"query_ids": q.astype(np.float64), "t": res.t[q].astype(np.float32), "status": res.status[q].astype(np.float32),
+              "global_signal": res.global_signal[q].astype(np.float64), "n_rows": n_rows[q].astype(np.float32)}
+    fixed = sum(a.nbytes for a in arrays.values())
+    k = DUMP_ROW_QUERIES
+    while True:
+        rq = sample(k, 20266)
+        rows = (np.concatenate([np.arange(row_off[i], row_off[i + 1]) for i in rq]) if len(rq) else np.zeros(0, np.int64)).astype(np.int64)
+        depth = res.row_depth[rows].astype(np.int64)
+        conf = np.array(res.row_conf[rows], dtype=np.float64)
+        conf[np.arange(conf.shape[1])[None, :] >= depth[:, None]] = 0.0
+        row_arrays = {"row_query_ids": np.repeat(rq, n_rows[rq]).astype(np.float64), "row_lineage": res.row_lineage[rows].astype(np.float64),
+                      "row_node": res.row_node[rows].astype(np.float64), "row_depth": depth.astype(np.float32),
+                      "row_local_signal": res.row_local_signal[rows].astype(np.float64), "row_conf": conf}
+        if fixed + sum(a.nbytes for a in row_arrays.values()) + 128 * 16 <= DUMP_MAX_BYTES or k <= 1:   # (+ the .npy headers)
+            break
+        k //= 2
+    arrays.update(row_arrays)
+    out = Path(out_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {"dir": str(out), "files": sorted(f"{n}.npy" for n in arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "queries": int(len(q)), "row_queries": int(len(rq)), "rows": int(len(rows))}
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -1121,6 +1181,7 @@ def main():
     prob_work = index.prob_work()
     prune_stats = index.debug_prune_stats() if hasattr(index, "debug_prune_stats") else None   # of the last step (all zero: not pruned)
     ok = int((np.ctypeslib.as_array(view.status, shape=(args.queries,)) == 0).sum())
+    dumped = dump_outputs(args.dump_outputs, rx, view) if (rank == 0 and args.dump_outputs) else None   # before --full runs anything again
     parity_failed = False
     if rank == 0:
         line = {
@@ -1161,14 +1222,17 @@ def main():
             # gaps, the host's finalisation of the last sub-batch and the D2H of the records
             "stage_ms_sum_per_step": sum(stage_ms.values()) / args.steps,
             "unstaged_ms_per_step": elapsed / args.steps * 1e3 - sum(stage_ms.values()) / args.steps,
+            "full": bool(args.full),
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if not args.shard_db:
             line["step_bounds"] = step_bounds(args, line["stage_ms_per_step"], line["ms_per_step"], args.queries, L,
                                               pruned=bool(prune_stats and prune_stats.get("pairs")))
             line["stage_note"] = ("with RTX_OPT_OVERLAP (default) the back half of a sub-batch runs beside the front half of the next: the stage times "
                                   "overlap and their sum exceeds ms_per_step (unstaged_ms_per_step is then negative)")
         ctx = None
-        if world > 1 and not args.no_parity:             # N > 1: the line verifies itself too (rank 0, untimed; the other ranks wait at the barrier)
+        if args.full and world > 1 and not args.no_parity:   # N > 1: the line verifies itself too (rank 0, untimed; the other ranks wait at the barrier)
             try:
                 ctx_m = oracle_context(db)
                 if args.shard_db:
@@ -1179,7 +1243,7 @@ def main():
             except Exception as e:
                 line["parity_sample"] = {"ok": False, "error": f"{type(e).__name__}: {str(e)[:300]}"}
             parity_failed = not line["parity_sample"]["ok"]
-        if args.shard_db and world == 1 and not args.no_cpu_baseline:
+        if args.full and args.shard_db and world == 1 and not args.no_cpu_baseline:
             try:
                 line["parity_sample"] = sharded_parity_block(args, rx, index, view, oracle_context(db), db, qs, flags,
                                                              (cuts[rank], cuts[rank + 1]) if args.shard_mode == "refs" else None)
@@ -1187,7 +1251,7 @@ def main():
             except Exception as e:
                 line["parity_sample"] = {"ok": False, "error": f"{type(e).__name__}: {str(e)[:300]}"}
                 parity_failed = True
-        if not args.no_cpu_baseline and world == 1:      # the oracle: rank 0 at N = 1 only, never inside the timed region
+        if args.full and not args.no_cpu_baseline and world == 1:   # the oracle: rank 0 at N = 1 only, never inside the timed region
             try:
                 ctx = oracle_context(db)
             except Exception as e:                       # (no C compiler on the bench host, ...): the measured line is still printed
@@ -1196,7 +1260,7 @@ def main():
             if ctx is not None and not args.shard_db:    # first of all: the last timed step is still on the device
                 line["parity_sample"] = parity_block(args, rx, index, view, ctx, db, qs, flags)
                 parity_failed = not line["parity_sample"]["ok"]
-        if not args.no_extras and world == 1 and not args.shard_db:
+        if args.full and not args.no_extras and world == 1 and not args.shard_db:
             line.update(extras_block(args, rx, lib, index, tree, db, qs, flags))
             line["value_mixed_lengths"] = mixed_lengths_block(args, rx, lib, index, db, flags)
             index.upload(qs.bases, qs.base_off)     # (the headline's batch again)

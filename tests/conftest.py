@@ -2,7 +2,10 @@ import os
 import sys
 from pathlib import Path
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")  # (raxtax_amd/__init__.py: before anything initialises HIP)
+# (raxtax_amd/__init__.py: before anything initialises HIP.)  The package leaves a value the process came with alone; the suite pins eight,
+# whatever the caller's environment says: rtx_raxtax runs chunks ahead only with six hardware queues or more (csrc/host_threads.cpp), and
+# tests/test_gpu_run_ahead.py asserts that it does.
+os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 import pytest
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # headline + divergence sweep of bench.py (configs[2]) in one line each: sweep_check.sh
-timeout 900 python bench.py --no-cpu-baseline 2>gpurun_out/sweep_check.err | python -c "
+timeout 900 python bench.py --full --no-cpu-baseline | python -c "
 import sys, json
 b = json.loads(sys.stdin.read().strip().splitlines()[-1])
 print(round(b['value']), round(b['ms_per_step'], 2), {k: round(v, 2) for k, v in b['stage_ms_per_step'].items()})
