@@ -61,6 +61,7 @@ extern "C" {
 /* flags of rtx_classify_batch / rtx_batch_run (src/io.rs:119-121,131-133) */
 #define RTX_SKIP_EXACT_MATCHES 1u /* zero the hit counts of exact matches, raxtax.rs:65-68 */
 #define RTX_RAW_CONFIDENCE 2u     /* host mirror only: suppress the single-exact-match override, raxtax.rs:73-84 */
+#define RTX_TEXT_TSV 4u           /* rtx_index_text_setup only: the `.tsv` lines as well (lineage.rs:31-48) */
 
 /* per-query status in rtx_result_view.status */
 #define RTX_Q_OK 0
@@ -275,6 +276,9 @@ int rtx_index_set_batch(rtx_index *index, uint32_t sub_batch);
                                       * call that needs it (rtx_batch_sync, a download, the next run, switching the option off).  rtx_raxtax sets
                                       * it for the duration of a call with more than one chunk.  Results are those of the plain sequence.  (2: a test aid -- every
                                       * second run-ahead is abandoned as if the batch had overflowed.) */
+#define RTX_OPT_DEVICE_TEXT 24       /* 0 (default).  1: rtx_raxtax / rtx_raxtax_multi take the `.out` / `.tsv` text of their chunks from the device
+                                      * (rtx_batch_text: the call sets the text up for its tree and flags and stages the labels with every chunk);
+                                      * the format stage keeps only the lineage check of raxtax.rs:43-53.  The messages are the same either way. */
 /* RTX_OPT_SUB_BATCH, _PACKED_COUNTS, _HIT_PAIR, _TILE_PRUNE and _PROB_MODE shape the workspace that rtx_batch_upload sizes:
  * setting one of them drops the uploaded batch (rtx_batch_run then fails with RTX_ERR_STATE until the batch is uploaded again). */
 int rtx_index_set_option(rtx_index *index, int option, uint64_t value);
@@ -376,6 +380,30 @@ int rtx_batch_download(rtx_index *index, rtx_result_view *out);
  * finalisation between them).  Nothing staged: plain rtx_batch_download.  Under RTX_OPT_RUN_AHEAD the staged batch is enqueued before the
  * current one has finished, and the call may return RTX_RETRY_CHUNK (> 0). */
 int rtx_batch_download_then_run(rtx_index *index, rtx_result_view *out, uint32_t flags);
+
+/* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
+ * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte
+ * for byte what rtx_format_query prints for the view, the label, the bases and the exact matches of the query (the override of
+ * raxtax.rs:73-84 unless RTX_SKIP_EXACT_MATCHES or RTX_RAW_CONFIDENCE is set in `flags`; the exact matches are those of the batch: the ids
+ * passed at upload, or the device lookup's).  Off until a caller asks:
+ *   rtx_index_text_setup       uploads the lineage strings of `tree` (whose tips must be the handle's database) and switches the text on with
+ *                              `flags` (RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE | RTX_TEXT_TSV); tree == NULL switches it off and frees the table.
+ *   rtx_batch_prefetch_labels  stages the labels of the batch that the NEXT rtx_batch_prefetch / rtx_batch_upload stages (call it first),
+ *                              into the same input set, asynchronously.  A batch without labels has no text.
+ *   rtx_batch_text             the text of the last download: per query (input order) its lines joined by '\n', NUL-terminated, at
+ *                              out + out_off[q] (out_off[n_queries] = the bytes of all); a query with status != RTX_Q_OK has the empty
+ *                              text.  tsv / tsv_off likewise, NULL without RTX_TEXT_TSV.  Valid as long as the rtx_result_view of that
+ *                              download (until the second-next download).  RTX_ERR_STATE: that download has no text. */
+typedef struct {
+    uint64_t n_queries;
+    const char *out;
+    const uint64_t *out_off; /* [n_queries + 1] */
+    const char *tsv;
+    const uint64_t *tsv_off; /* [n_queries + 1] */
+} rtx_text_view;
+int rtx_index_text_setup(rtx_index *index, const rtx_tree *tree, uint32_t flags);
+int rtx_batch_prefetch_labels(rtx_index *index, uint64_t n_queries, const char *const *labels);
+int rtx_batch_text(rtx_index *index, rtx_text_view *out);
 
 /* ---- staged execution of a reference-sharded handle (one sub-batch at a time) --------------------
  * Between the stages the caller exchanges two device buffers with the other shards (RCCL):

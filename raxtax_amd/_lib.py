@@ -19,6 +19,7 @@ RTX_ERR_INVALID, RTX_ERR_HIP, RTX_ERR_NO_DEVICE, RTX_ERR_OOM = -1, -2, -3, -4
 RTX_ERR_PARSE, RTX_ERR_DEPTH, RTX_ERR_STATE, RTX_ERR_TOO_LONG = -5, -6, -7, -8
 RTX_SKIP_EXACT_MATCHES = 1
 RTX_RAW_CONFIDENCE = 2
+RTX_TEXT_TSV = 4
 RTX_Q_OK, RTX_Q_NO_KMERS, RTX_Q_ALL_KMERS = 0, 1, 2
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 
@@ -40,6 +41,10 @@ class ResultView(C.Structure):
                 ("global_signal", f64p), ("row_begin", u64p), ("row_count", u32p), ("row_lineage", u32p), ("row_node", u32p),
                 ("row_depth", u32p), ("row_conf", f64p), ("row_local_signal", f64p),
                 ("row_conf_stride", C.c_uint32), ("row_depth_u8", u8p), ("row_conf_hundredths", u8p)]   # ABI 5 (0 / NULL in a hand-made view)
+
+
+class TextView(C.Structure):
+    _fields_ = [("n_queries", C.c_uint64), ("out", C.c_void_p), ("out_off", u64p), ("tsv", C.c_void_p), ("tsv_off", u64p)]
 
 
 class RtxError(RuntimeError):
@@ -115,6 +120,9 @@ _SIGNATURES = {
     "rtx_batch_sync": (C.c_int, [C.c_void_p]),
     "rtx_batch_download": (C.c_int, [C.c_void_p, C.POINTER(ResultView)]),
     "rtx_batch_download_then_run": (C.c_int, [C.c_void_p, C.POINTER(ResultView), C.c_uint32]),
+    "rtx_index_text_setup": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
+    "rtx_batch_prefetch_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p)]),
+    "rtx_batch_text": (C.c_int, [C.c_void_p, C.POINTER(TextView)]),
     "rtx_batch_stage_times": (C.c_int, [C.c_void_p, f32p, u32p]),
     "rtx_batch_work": (C.c_int, [C.c_void_p, u64p, u64p, u64p]),
     "rtx_batch_prob_work": (C.c_int, [C.c_void_p, u64p, u64p]),

@@ -222,7 +222,7 @@ class Index:
                  tile_skip: Optional[bool] = None, hit_pair=None, locator: Optional[bool] = None, tile_prune: Optional[bool] = None,
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
-                 prune_self_sample: Optional[bool] = None):
+                 prune_self_sample: Optional[bool] = None, device_text: bool = False):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -258,6 +258,8 @@ class Index:
             check(self._lib.rtx_index_set_option(self._h, 14, 1))
         if device_exact is not None:
             check(self._lib.rtx_index_set_option(self._h, 15, int(device_exact)))
+        if device_text:   # RTX_OPT_DEVICE_TEXT: raxtax() takes the lines of its chunks from the device (rtx_text.hip)
+            check(self._lib.rtx_index_set_option(self._h, 24, 1))
         if fine_bounds is not None:
             check(self._lib.rtx_index_set_option(self._h, 17, int(fine_bounds)))
         if records is not None:   # RTX_OPT_RECORDS: pruned queries with at most this many live tiles write records instead of counts (0: off)
@@ -389,6 +391,37 @@ class Index:
         self.upload(bases, base_off, exact_ids, exact_off)
         self.run(RTX_SKIP_EXACT_MATCHES if skip_exact_matches else 0)
         return self.download()
+
+    def classify_text(self, bases: np.ndarray, base_off: np.ndarray, labels: Sequence, exact_ids=None, exact_off=None,
+                      skip_exact_matches: bool = False, raw_confidence: bool = False, tsv: bool = False):
+        """classify() with the result text formatted on the device (rtx_text.hip) -> (out_texts, tsv_texts or None), one str per query in
+        input order: the lines rtx_format_query prints for it ('\\n'-joined; '' for a query with status != 0).  The view of the download
+        stays available (format_query, rows)."""
+        flags = (RTX_SKIP_EXACT_MATCHES if skip_exact_matches else 0) | (_lib.RTX_RAW_CONFIDENCE if raw_confidence else 0) | (_lib.RTX_TEXT_TSV if tsv else 0)
+        check(self._lib.rtx_index_text_setup(self._h, self.tree._h, flags))
+        n_q = len(base_off) - 1
+        if len(labels) != n_q:
+            raise ValueError(f"{len(labels)} labels for {n_q} queries")
+        labs = (C.c_char_p * max(n_q, 1))(*[l.encode() if isinstance(l, str) else bytes(l) for l in labels])
+        check(self._lib.rtx_batch_prefetch_labels(self._h, n_q, labs))
+        self.prefetch(bases, base_off, exact_ids, exact_off)
+        self.activate()
+        self.run(RTX_SKIP_EXACT_MATCHES if skip_exact_matches else 0)
+        self.download(copy=False)
+        return self.last_text()
+
+    def last_text(self):
+        """The device text of the last download (rtx_batch_text) -> (out_texts, tsv_texts or None)."""
+        tv = _lib.TextView()
+        check(self._lib.rtx_batch_text(self._h, C.byref(tv)))
+        n = tv.n_queries
+
+        def split(base, off_p):
+            off = np.ctypeslib.as_array(off_p, shape=(n + 1,)).astype(np.int64)
+            raw = C.string_at(base, int(off[-1])) if off[-1] else b""
+            return [raw[off[q]:off[q + 1] - 1].decode() for q in range(n)]
+
+        return split(tv.out, tv.out_off), (split(tv.tsv, tv.tsv_off) if tv.tsv else None)
 
     # ---- parity taps ----------------------------------------------------------------------
     def debug_kmers(self, q: int) -> np.ndarray:

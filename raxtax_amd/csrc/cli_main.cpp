@@ -162,6 +162,7 @@ int main(int argc, char **argv) {
         t_prev = now;
     };
     std::vector<int> devices{0};
+    bool device_format = false;
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
     for (int i = 1; i < argc; i++) {
@@ -178,6 +179,7 @@ int main(int argc, char **argv) {
         else if (a == "-c" || a == "--clean") clean = true;
         else if (a == "--redo") redo = true;
         else if (a == "--timing") timing = true;
+        else if (a == "--device-format") device_format = true;  // RTX_OPT_DEVICE_TEXT on every handle: the lines are formatted on the GPU
         // CPU tuning flags of the reference (io.rs:139-153): accepted so that existing command lines keep working,
         // without effect on the device path.  -t takes a value; clap also accepts -tN, --threads=N, -vv, -qq.
         else if (a == "-t" || a == "--threads") (void)val();
@@ -201,7 +203,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -361,6 +363,7 @@ int main(int argc, char **argv) {
         for (size_t k = 0; k < devices.size(); k++)
             th.emplace_back([&, k] {
                 rcs[k] = rtx_index_create_from_tree(devices[k], tree, &indices[k]);
+                if (rcs[k] == RTX_OK && device_format) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEVICE_TEXT, 1);
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
             });
         for (auto &t : th) t.join();

@@ -117,6 +117,7 @@ struct Chunk {
     std::vector<Arena> out_arena, tsv_arena;   // one per formatting thread
     std::vector<uint64_t> msg_off, tsv_off;    // [nq] offset of the query's text in its thread's arena
     std::vector<uint32_t> msg_arena;           // [nq] which arena
+    rtx_text_view text{};              // RTX_OPT_DEVICE_TEXT: the messages as the device formatted them (valid as long as `res`)
     rtx_result_view res{};
     int stage = 0;                     // 1: exact matches looked up (or left to the device), 2: classified, 3: formatted, 4: sent
 };
@@ -146,11 +147,17 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     const uint64_t n_chunks = (n_queries + chunk_size - 1) / chunk_size;
     // thread budget: this process's share of the host's CPUs (rtx::host_threads), split over the handles driven here
     const unsigned nt_lookup = rtx::host_threads(4u), nt_format = rtx::host_threads(16u, n_dev);
-    std::vector<uint8_t> dev_lookup(n_dev);
+    std::vector<uint8_t> dev_lookup(n_dev), dev_text(n_dev);
     bool any_host_lookup = false;
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
+        // RTX_OPT_DEVICE_TEXT: the messages come from the device (rtx_text.hip), set up for this tree and these flags
+        dev_text[d] = rtx::index_device_text(indices[d]);
+        if (dev_text[d]) {
+            const int rc = rtx_index_text_setup(indices[d], tree, flags | (tsv ? RTX_TEXT_TSV : 0u));
+            if (rc) return rc;
+        }
     }
 
     // chunks follow one another through rtx_batch_download_then_run (the last sub-batch of a chunk is finalised beside the next chunk): two
@@ -243,6 +250,10 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     // (rtx_batch_prefetch / rtx_batch_activate): the reference's workers pick up their next chunk without a pause either (raxtax.rs:35-36).
     auto stage_chunk = [&](uint32_t d, uint64_t c) -> int {
         Chunk &ch = chunks[c];
+        if (dev_text[d]) {  // the labels travel with the chunk (the same input set)
+            const int rc = rtx_batch_prefetch_labels(indices[d], ch.nq, labels + ch.q0);
+            if (rc) return rc;
+        }
         if (dev_lookup[d]) return rtx_batch_prefetch(indices[d], ch.nq, bases, base_off + ch.q0, nullptr, nullptr);
         return rtx_batch_prefetch(indices[d], ch.nq, bases, base_off + ch.q0, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
     };
@@ -250,7 +261,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         bool running = false;  // the kernels of chunk c have been enqueued already (behind the download of the chunk before it)
         for (uint64_t c = d; c < n_chunks; c += n_dev) {
             if (!wait_stage(c, 1)) return;
-            if (c >= ahead && !wait_stage(c - ahead, 3)) return;  // the result set of this handle's second-last chunk is reused now
+            // the result set of this handle's second-last chunk is reused now (device text: the sender reads the text of that set itself)
+            if (c >= ahead && !wait_stage(c - ahead, dev_text[d] ? 4 : 3)) return;
             Chunk &ch = chunks[c];
             const double t_d0 = now();
             int rc = RTX_OK;
@@ -271,13 +283,15 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             // the last sub-batch (and this thread's bookkeeping) no longer stand between two chunks (rtx_batch_download_then_run)
             if (!rc) rc = staged ? rtx_batch_download_then_run(indices[d], &ch.res, flags) : rtx_batch_download(indices[d], &ch.res);
             if (rc == RTX_RETRY_CHUNK) {  // the run-ahead was abandoned (this chunk outgrew a buffer with the next one enqueued already): this chunk on its own
-                rc = dev_lookup[d] ? rtx_batch_upload(indices[d], ch.nq, bases, base_off + ch.q0, nullptr, nullptr)
+                rc = dev_text[d] ? rtx_batch_prefetch_labels(indices[d], ch.nq, labels + ch.q0) : RTX_OK;
+                if (!rc) rc = dev_lookup[d] ? rtx_batch_upload(indices[d], ch.nq, bases, base_off + ch.q0, nullptr, nullptr)
                                    : rtx_batch_upload(indices[d], ch.nq, bases, base_off + ch.q0, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
                 if (!rc) rc = rtx_batch_run(indices[d], flags);
                 if (!rc) rc = rtx_batch_download(indices[d], &ch.res);
                 staged = false;  // (the next chunk is staged, activated and run at the head of the loop)
             }
             if (!rc && staged) running = true;
+            if (!rc && dev_text[d]) rc = rtx_batch_text(indices[d], &ch.text);
             if (!rc && dev_lookup[d]) {
                 const uint64_t *xo = nullptr;
                 const uint32_t *xi = nullptr;
@@ -354,13 +368,18 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     __builtin_prefetch(l.data());
                     __builtin_prefetch(l.data() + 64);
                 };
-                for (uint64_t j = a; j < std::min<uint64_t>(b, a + 24); j++) stage1(j);
-                for (uint64_t j = a; j < std::min<uint64_t>(b, a + 16); j++) stage2(j);
-                for (uint64_t j = a; j < std::min<uint64_t>(b, a + 8); j++) stage3(j);
+                const bool pre = !dev_text[d];  // (the prefetches serve the host formatter)
+                if (pre) {
+                    for (uint64_t j = a; j < std::min<uint64_t>(b, a + 24); j++) stage1(j);
+                    for (uint64_t j = a; j < std::min<uint64_t>(b, a + 16); j++) stage2(j);
+                    for (uint64_t j = a; j < std::min<uint64_t>(b, a + 8); j++) stage3(j);
+                }
                 for (uint64_t i = a; i < b; i++) {
-                    stage1(i + 24);
-                    stage2(i + 16);
-                    stage3(i + 8);
+                    if (pre) {
+                        stage1(i + 24);
+                        stage2(i + 16);
+                        stage3(i + 8);
+                    }
                     const uint64_t q = ch.q0 + i;
                     const uint64_t ne = ch.exact_off[i + 1] - ch.exact_off[i];
                     if (!skip_exact_matches && ne > 1) {  // raxtax.rs:43-53 (the info! lines go to the log in the CLI)
@@ -373,7 +392,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                         for (uint64_t j = 1; j < ne; j++)
                             if (parent(ids[j]) != parent(ids[0])) { ch.differ[i] = 1; break; }
                     }
-                    if (ch.res.status[i] != RTX_Q_OK) continue;
+                    if (dev_text[d] || ch.res.status[i] != RTX_Q_OK) continue;  // (device text: the lines are formatted already)
                     const uint64_t len = base_off[q + 1] - base_off[q];
                     const uint64_t rows = ch.res.row_count[i];
                     const size_t need = (rows + 1) * (strlen(labels[q]) + 4096 + 8 * RTX_MAX_DEPTH) + len + 64;
@@ -421,8 +440,14 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 else fprintf(stderr, "[ERROR] query %s has too few valid 8-mers (%u) to be classified\n", labels[q], ch.t[i]);
                 continue;
             }
-            const uint32_t r = ch.msg_arena[i];
-            if (!sender(labels[q], ch.out_arena[r].p + ch.msg_off[i], tsv ? ch.tsv_arena[r].p + ch.tsv_off[i] : nullptr)) closed = true;
+            bool ok;
+            if (dev_text[c % n_dev]) {
+                ok = sender(labels[q], ch.text.out + ch.text.out_off[i], tsv ? ch.text.tsv + ch.text.tsv_off[i] : nullptr);
+            } else {
+                const uint32_t r = ch.msg_arena[i];
+                ok = sender(labels[q], ch.out_arena[r].p + ch.msg_off[i], tsv ? ch.tsv_arena[r].p + ch.tsv_off[i] : nullptr);
+            }
+            if (!ok) closed = true;
         }
         if (closed) { fail(RTX_ERR_SENDER, "result sink closed"); break; }  // sender.send(..)?, raxtax.rs:87
         std::vector<uint32_t>().swap(ch.exact_ids);

@@ -1242,11 +1242,14 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
                        const uint32_t *exact_ids, const uint64_t *exact_off) {
     int rc = bind(ix);
     if (rc) return rc;
+    rtx_index::Inputs &in = ix->in[ix->cur_in ^ 1u];
+    // labels staged for this batch (rtx_batch_prefetch_labels) belong to it alone: taken or dropped here, whatever becomes of the call
+    const bool with_labels = in.labels_pending && in.n_labels == n_queries;
+    in.labels_pending = in.has_labels = false;
     if (n_queries == 0 || !base_off || (!bases && base_off[n_queries])) {
         set_error("rtx_batch_upload: invalid argument");
         return RTX_ERR_INVALID;
     }
-    rtx_index::Inputs &in = ix->in[ix->cur_in ^ 1u];
     if (!ix->h2d_stream) RTX_HIP(hipStreamCreateWithFlags(&ix->h2d_stream, hipStreamNonBlocking));
     if (!in.ready) RTX_HIP(hipEventCreateWithFlags(&in.ready, hipEventDisableTiming));
     if (in.recorded) RTX_HIP(hipEventSynchronize(in.ready));  // the last transfer out of this set's pinned buffers (long done, as a rule)
@@ -1303,6 +1306,7 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
     for (int c = 0; c < 5; c++) { in.cls_n[c] = cls_n[c]; in.cls_max[c] = cls_max[c]; }
     in.n_exact = n_exact;
     in.has_exact = exact_off != nullptr;
+    in.has_labels = with_labels;
     in.staged = true;
     return RTX_OK;
 }

@@ -205,6 +205,8 @@ static int download_streamed(rtx_index *ix, rtx_index::HostRes &hr, bool *done, 
             if (flags & 12u) { redo = flags & 13u; break; }  // the rows of the counts buffer ran out, or a record segment was too short (whatever else such a run flagged)
             if (flags & 2u) { set_error("lineage walk exceeded its row/depth bounds (internal error)"); return RTX_ERR_HIP; }
             if (flags & 1u) { redo = 1u; break; }  // arena overflow
+            // the text (rtx_text.hip) while the rows and the input set are this batch's (ahead: the next batch has been activated -- its set is the current one)
+            if ((rc = enqueue_text(ix, ix->in[ahead ? ix->cur_in ^ 1u : ix->cur_in], nq, ix->host_exact[ix->res_set].valid))) return rc;
             if (!ahead && then_run && (rc = run_staged(ix, next_flags, ran_next))) return rc;  // the device is free for the next batch
         }
     }
@@ -247,6 +249,7 @@ static int download_impl(rtx_index *ix, rtx_result_view *out, bool then_run, uin
     const uint64_t nq = ix->n_q;
     ix->res_set ^= 1u;
     rtx_index::HostRes &hr = ix->host_res[ix->res_set];
+    ix->host_text[ix->res_set].valid = false;
     bool streamed = false, ran_next = false;
     uint64_t nrows = 0;
     if ((rc = download_streamed(ix, hr, &streamed, &nrows, then_run, next_flags, &ran_next))) return rc;
@@ -285,6 +288,7 @@ static int download_impl(rtx_index *ix, rtx_result_view *out, bool then_run, uin
         if ((rc = size_host_results(ix, hr, nq, fin, 0)) || (rc = copy_rows(ix, hr, 0, fin, ix->stream)) || (rc = copy_queries(ix, hr, nq, ix->stream))) return rc;
         RTX_HIP(hipStreamSynchronize(ix->stream));
         nrows = fin;
+        if ((rc = enqueue_text(ix, ix->in[ix->cur_in], nq, ix->dev_exact_used))) return rc;  // (before run_staged: the next batch writes these rows)
     }
     {   // the first download of a handle: the other result set (the two alternate, a view stays valid until the second-next
         // download) is allocated now, so that the second batch does not pay for its page-locked allocations

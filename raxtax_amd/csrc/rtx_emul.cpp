@@ -590,4 +590,42 @@ uint32_t emul_finalise_rows(uint32_t n, uint32_t D, const uint8_t *k, const uint
     return disagree;
 }
 
+// "{:.5}" of n values by rtx_math.hpp's text_put_fix5 (what rtx_text.hip prints), each followed by '\n'; "{:.2}" of the hundredths
+// 0 .. n_hund - 1 behind them, the same way.  Returns the bytes written (cap too small: -1).
+int64_t emul_text_numbers(const double *v, uint64_t n, uint32_t n_hund, char *out, uint64_t cap) {
+    TextWindow w{out, 0, 0, cap};
+    for (uint64_t i = 0; i < n; i++) { text_put_fix5(w, v[i]); w.put('\n'); }
+    for (uint32_t k = 0; k < n_hund; k++) { text_put_hund(w, k); w.put('\n'); }
+    return w.pos > cap ? -1 : (int64_t)w.pos;
+}
+
+// The text of a batch as the kernels of rtx_text.hip lay it out, from host arrays of the same shape: per query (input order) its lines
+// joined by '\n' and a NUL, at out_off[q]; a query with status != 0 (or without rows) has the empty text.  one[q]: the id of the query's
+// only exact match where the override applies, else kTextNoOverride.  seq/seq_off: base codes (tsv only).  Returns the bytes (-1: cap).
+int64_t emul_text_batch(const char *lin_bytes, const uint64_t *lin_off, const uint8_t *lin_depth, const uint32_t *row_lineage,
+                        const uint8_t *row_depth, const uint8_t *row_hund, const double *row_local, uint32_t D, uint64_t nq,
+                        const char *labels, const uint64_t *label_off, const uint8_t *status, const uint64_t *row_begin,
+                        const uint32_t *row_count, const double *gs, const uint32_t *one, const uint8_t *seq, const uint64_t *seq_off,
+                        int tsv, char *out, uint64_t cap, uint64_t *out_off) {
+    const TextSrc t{lin_bytes, lin_off, lin_depth, row_lineage, row_depth, row_hund, row_local, D};
+    TextWindow w{out, 0, 0, cap};
+    for (uint64_t q = 0; q < nq; q++) {
+        out_off[q] = w.pos;
+        const uint64_t n_out = status[q] != 0 || row_count[q] == 0 ? 0 : (one[q] != kTextNoOverride ? 1 : row_count[q]);
+        for (uint64_t i = 0; i < n_out; i++) {
+            if (i) w.put('\n');
+            const TextRow r = text_row(t, labels + label_off[q], label_off[q + 1] - label_off[q], row_begin[q], i, one[q], gs[q]);
+            if (tsv) {
+                const uint8_t *sq = seq + seq_off[q];
+                text_tsv_row(w, r, seq_off[q + 1] - seq_off[q], [&](uint64_t j) { return sq[j]; });
+            } else {
+                text_out_row(w, r);
+            }
+        }
+        w.put('\0');
+    }
+    out_off[nq] = w.pos;
+    return w.pos > cap ? -1 : (int64_t)w.pos;
+}
+
 }  // extern "C"

@@ -268,6 +268,13 @@ struct rtx_index {
         uint64_t n_q = 0, total = 0, max_len = 0, n_exact = 0;
         uint64_t cls_n[5] = {0, 0, 0, 0, 0}, cls_max[5] = {0, 0, 0, 0, 0};  // queries and longest query per length class (length_class)
         bool packed = true, has_exact = false, staged = false, recorded = false;
+        // the labels of the batch (rtx_batch_prefetch_labels, staged before the bases: labels_pending becomes has_labels at the prefetch)
+        DevBuf<char> d_labels;
+        DevBuf<uint64_t> d_label_off;
+        PinBuf<char> h_labels;
+        PinBuf<uint64_t> h_label_off;
+        uint64_t n_labels = 0;
+        bool labels_pending = false, has_labels = false;
         hipEvent_t ready = nullptr;        // its transfer has arrived
     } in[2];
     uint32_t cur_in = 0;               // the set of the current (activated) batch
@@ -375,6 +382,22 @@ struct rtx_index {
     } host_res[2];
     uint32_t res_set = 0;
     PinBuf<uint32_t> h_nrows_all;
+    // ---- device text (rtx_text.hip): the lineage table of rtx_index_text_setup, the passes' scratch, the text of the downloads (one per host
+    // result set, valid as long as its view)
+    bool text_on = false;
+    uint32_t text_flags = 0;
+    uint64_t text_tree_uid = 0;      // rtx_tree::uid of the tree the lineage table was uploaded from
+    uint32_t device_text_opt = 0;    // RTX_OPT_DEVICE_TEXT
+    DevBuf<char> d_lin_bytes, d_text;
+    DevBuf<uint64_t> d_lin_off;
+    DevBuf<uint8_t> d_lin_depth, d_text_tmp;
+    DevBuf<unsigned long long> d_text_len, d_text_off;
+    struct HostText {
+        PinBuf<char> out, tsv;
+        PinBuf<uint64_t> out_off, tsv_off;
+        uint64_t nq = 0;
+        bool valid = false, tsv_on = false;
+    } host_text[2];
     // streamed download: per sub-batch a snapshot of the arena cursor + an event; rtx_batch_download copies and
     // finalises finished sub-batches on `copy_stream` while later ones are still running
     std::vector<hipEvent_t> ev_sub;
@@ -489,5 +512,7 @@ int alloc_result_set(rtx_index *ix, uint64_t n_queries);  // (rtx_api_batch.hip)
 int settle_join(rtx_index *ix);        // (rtx_api_batch.hip) the handle's stream waits for the back halves of the last run, if that run left the join out
 int alloc_final(rtx_index *ix, uint64_t n_queries);  // (rtx_api_batch.hip) the final result arrays: n_queries per-query fields, arena_cap rows
 int enqueue_finalise(rtx_index *ix, const SubBatch &b, hipStream_t s);  // (rtx_api_batch.hip) behind the walks of a sub-batch
+// ---- rtx_text.hip
+int enqueue_text(rtx_index *ix, rtx_index::Inputs &in, uint64_t nq, bool dev_exact);  // the text of the batch being downloaded (synchronous)
 
 }  // namespace rtxi

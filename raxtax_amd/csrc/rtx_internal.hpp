@@ -2,6 +2,7 @@
 // libraxtax_hip.so.  Not part of the ABI (include/raxtax_hip.h is).
 #pragma once
 
+#include <atomic>
 #include <cstdint>
 #include <string>
 #include <string_view>
@@ -28,7 +29,8 @@ unsigned host_threads(unsigned want, unsigned sharers = 1);
 int index_device(const rtx_index *index);
 void index_set_shared_device(rtx_index *index, bool shared);
 uint32_t index_swap_min_subs(rtx_index *index, uint32_t v);  // returns the previous value
-uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v);  // RTX_OPT_RUN_AHEAD, returns the previous value
+uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v);
+bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value
 bool hw_queues_for_run_ahead();  // (host_threads.cpp) GPU_MAX_HW_QUEUES reads six or more: transfers do not share a hardware queue with kernels
 
 #ifndef RTX_NODE_TYPES_DEFINED
@@ -63,8 +65,16 @@ bool derive_flat_nodes(uint64_t n_refs, uint32_t n_nodes, const uint32_t *begin,
 
 }  // namespace rtx
 
+namespace rtx {
+inline uint64_t next_tree_uid() {
+    static std::atomic<uint64_t> next{1};
+    return next.fetch_add(1);
+}
+}  // namespace rtx
+
 // Host mirror of `Tree` (src/tree.rs:36-43).
 struct rtx_tree {
+    const uint64_t uid = rtx::next_tree_uid();  // distinct for every tree of the process (a freed tree's address may come back)
     uint64_t n = 0;         // input sequences
     uint64_t num_tips = 0;  // Tree.num_tips
     std::vector<std::string> lineages;  // sorted (tree.rs:53-54,128-129)

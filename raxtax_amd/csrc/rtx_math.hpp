@@ -552,4 +552,207 @@ RTX_HD double fin_local_signal(K k, const double *eb, uint32_t s0, uint32_t dept
     return sqrt(s);
 }
 
+// ---------------------------------------------------------------------------
+// Result text (rtx_text.hip), byte for byte what rtx_format_query (host_format.cpp) prints: lineage.rs:17-48, utils.rs:62-89.
+// The generators below write through a sink S with put(char) and put_gen(n, f) (n bytes, byte i = f(i)): TextCount only counts
+// (the measure pass), TextWindow keeps the bytes that fall into a window of the text (the write pass: a wave fills a window in LDS and
+// stores it with wide stores; the host emulation takes one window as large as the text).
+// ---------------------------------------------------------------------------
+struct TextCount {
+    uint64_t pos = 0;
+    RTX_HD void put(char) { pos++; }
+    template <class F>
+    RTX_HD void put_gen(uint64_t n, F) { pos += n; }
+};
+struct TextWindow {
+    char *buf;            // buf[i] holds byte w0 + i of the text
+    uint64_t pos, w0, w1;  // bytes [w0, w1) of the text are kept
+    RTX_HD void put(char c) {
+        if (pos >= w0 && pos < w1) buf[pos - w0] = c;
+        pos++;
+    }
+    template <class F>
+    RTX_HD void put_gen(uint64_t n, F f) {
+        const uint64_t lo = pos > w0 ? pos : w0, hi = pos + n < w1 ? pos + n : w1;
+        for (uint64_t i = lo; i < hi; i++) buf[i - w0] = f(i - pos);
+        pos += n;
+    }
+};
+
+// decimal digits of v (v > 0), most significant first
+template <class S>
+RTX_HD void text_put_u64(S &s, uint64_t v) {
+    uint32_t nd = 1;
+    for (uint64_t p = 10; nd < 20 && v >= p; p *= 10) nd++;
+    uint64_t div = 1;
+    for (uint32_t i = 1; i < nd; i++) div *= 10;
+    for (uint32_t i = 0; i < nd; i++) {
+        s.put((char)('0' + v / div % 10));
+        div /= 10;
+    }
+}
+
+// the integer part of a double of 2^64 or more: m * 2^e exactly, in 32-bit limbs, nine digits at a time (what printf prints for it)
+template <class S>
+RTX_HD void text_put_big_int(S &s, double v) {
+    int e2 = 0;
+    const double fr = frexp(v, &e2);                      // v = fr * 2^e2, fr in [0.5, 1)
+    uint64_t m = (uint64_t)ldexp(fr, 53);                 // v = m * 2^(e2 - 53), exactly
+    const int sh = e2 - 53;                               // >= 11 here
+    uint32_t limb[34] = {0};                              // 1088 bits
+    const int w = sh / 32, b = sh % 32;
+    limb[w] = (uint32_t)(m << b);
+    limb[w + 1] = (uint32_t)(m >> (32 - b));
+    limb[w + 2] = b ? (uint32_t)(m >> (64 - b)) : 0u;
+    uint32_t chunk[40];
+    int nc = 0, top = 33;
+    while (top >= 0) {
+        while (top >= 0 && limb[top] == 0) top--;
+        if (top < 0) break;
+        uint64_t rem = 0;
+        for (int i = top; i >= 0; i--) {
+            const uint64_t cur = rem << 32 | limb[i];
+            limb[i] = (uint32_t)(cur / 1000000000u);
+            rem = cur % 1000000000u;
+        }
+        chunk[nc++] = (uint32_t)rem;
+    }
+    text_put_u64(s, chunk[nc - 1]);
+    for (int i = nc - 2; i >= 0; i--)
+        for (uint32_t d = 100000000u; d; d /= 10) s.put((char)('0' + chunk[i] / d % 10));
+}
+
+// "{:.5}" (Rust) = "%.5f" (printf) of any double: the exact binary value rounded half to even at five decimals.  The integer part I = floor|v|
+// and the fraction F = |v| - I are exact; p = F * 1e5 is rounded, and fma(F, 1e5, -p) is its exact residual: the distance of F * 1e5 to
+// the half-way point between two integers is decided on exact values (no case is too close to call).  Non-finite: printf's "inf", "nan".
+template <class S>
+RTX_HD void text_put_fix5(S &s, double v) {
+    const bool neg = std::signbit(v);
+    if (std::isnan(v)) { if (neg) s.put('-'); s.put('n'); s.put('a'); s.put('n'); return; }
+    if (neg) s.put('-');
+    if (std::isinf(v)) { s.put('i'); s.put('n'); s.put('f'); return; }
+    const double a = fabs(v);
+    double I = floor(a);
+    const double F = a - I;
+    const double p = F * 1e5, e = fma(F, 1e5, -p);  // F * 1e5 = p + e exactly
+    const double n = floor(p), f = p - n;           // F * 1e5 = n + f + e, f in [0, 1)
+    bool up = false;
+    if (f >= 0.25) {  // f - 0.5 is exact from here on (Sterbenz); |e| <= 2^-37
+        const double d = f - 0.5;
+        up = d > -e || (d == -e && fmod(n, 2.0) != 0.0);
+    }
+    uint32_t r = (uint32_t)n + (up ? 1u : 0u);
+    if (r >= 100000u) { r -= 100000u; I += 1.0; }  // (F < 1 - 2^-53: only below 2^53, where I + 1 is exact)
+    if (I < 18446744073709551616.0) text_put_u64(s, (uint64_t)I);
+    else text_put_big_int(s, I);
+    s.put('.');
+    for (uint32_t d = 10000u; d; d /= 10u) s.put((char)('0' + r / d % 10u));
+}
+
+// "{:.2}" of a confidence given as hundredths (k / 100.0 of lineage.rs:128-129: the value k/100 rounded at two decimals is k)
+template <class S>
+RTX_HD void text_put_hund(S &s, uint32_t k) {
+    text_put_u64(s, k / 100u);
+    s.put('.');
+    s.put((char)('0' + k / 10u % 10u));
+    s.put((char)('0' + k % 10u));
+}
+
+// One result row.  ones: the single-exact-match override (raxtax.rs:73-84): every level 1.00.
+struct TextRow {
+    const char *label;
+    uint64_t label_len;
+    const char *lin;
+    uint64_t lin_len;
+    const uint8_t *hund;  // hundredths per level
+    uint32_t depth;
+    bool ones;
+    double local, global;
+};
+
+// `.out` line (lineage.rs:17-29): label \t lineage \t c,c,...,c \t local \t global
+template <class S>
+RTX_HD void text_out_row(S &s, const TextRow &r) {
+    s.put_gen(r.label_len, [&](uint64_t i) { return r.label[i]; });
+    s.put('\t');
+    s.put_gen(r.lin_len, [&](uint64_t i) { return r.lin[i]; });
+    s.put('\t');
+    for (uint32_t d = 0; d < r.depth; d++) {
+        if (d) s.put(',');
+        text_put_hund(s, r.ones ? 100u : r.hund[d]);
+    }
+    s.put('\t');
+    text_put_fix5(s, r.local);
+    s.put('\t');
+    text_put_fix5(s, r.global);
+}
+
+// base code -> letter (utils.rs:70-81)
+RTX_HD char text_base(uint8_t b) { return b == 1 ? 'A' : (b == 2 ? 'C' : (b == 4 ? 'G' : (b == 8 ? 'T' : '-'))); }
+
+// `.tsv` line (lineage.rs:31-48): label, then the levels of the lineage interleaved with the confidences (the longer side drained),
+// local, global, the decoded sequence; tab-separated.  base(i): code of base i of the query.
+template <class S, class B>
+RTX_HD void text_tsv_row(S &s, const TextRow &r, uint64_t seq_len, B base) {
+    s.put_gen(r.label_len, [&](uint64_t i) { return r.label[i]; });
+    s.put('\t');
+    uint64_t pos = 0;
+    uint32_t d = 0;
+    bool lin_done = false, first = true;
+    while (!lin_done || d < r.depth) {
+        if (!lin_done) {
+            uint64_t c = pos;
+            while (c < r.lin_len && r.lin[c] != ',') c++;
+            if (!first) s.put('\t');
+            const char *lv = r.lin + pos;
+            s.put_gen(c - pos, [&](uint64_t i) { return lv[i]; });
+            first = false;
+            if (c >= r.lin_len) lin_done = true;
+            else pos = c + 1;
+        }
+        if (d < r.depth) {
+            if (!first) s.put('\t');
+            text_put_hund(s, r.ones ? 100u : r.hund[d]);
+            first = false;
+            d++;
+        }
+    }
+    s.put('\t');
+    text_put_fix5(s, r.local);
+    s.put('\t');
+    text_put_fix5(s, r.global);
+    s.put('\t');
+    s.put_gen(seq_len, [&](uint64_t i) { return text_base(base(i)); });
+}
+
+// Where the rows of a query's text come from: the lineage table (bytes of tree.lineages back to back, offsets, levels = commas + 1) and the
+// final rows of a download (rtx_result_view: lineage, depth, hundredths [row][D], local signal).
+struct TextSrc {
+    const char *lin_bytes;
+    const uint64_t *lin_off;
+    const uint8_t *lin_depth;
+    const uint32_t *row_lineage;
+    const uint8_t *row_depth, *row_hund;
+    const double *row_local;
+    uint32_t D;
+};
+constexpr uint32_t kTextNoOverride = 0xFFFFFFFFu;
+
+// Row i of a query whose rows start at r0.  one != kTextNoOverride: the id of the query's only exact match, which replaces the rows
+// (raxtax.rs:73-84): its lineage, 1.00 on each of its levels, the local signal of the first row.
+RTX_HD TextRow text_row(const TextSrc &t, const char *label, uint64_t label_len, uint64_t r0, uint64_t i, uint32_t one, double global) {
+    TextRow r;
+    r.label = label;
+    r.label_len = label_len;
+    r.ones = one != kTextNoOverride;
+    const uint32_t li = r.ones ? one : t.row_lineage[r0 + i];
+    r.lin = t.lin_bytes + t.lin_off[li];
+    r.lin_len = t.lin_off[li + 1] - t.lin_off[li];
+    r.depth = r.ones ? t.lin_depth[li] : t.row_depth[r0 + i];
+    r.hund = t.row_hund + (r0 + i) * t.D;
+    r.local = t.row_local[r0 + (r.ones ? 0 : i)];
+    r.global = global;
+    return r;
+}
+
 }  // namespace rtx
