@@ -101,10 +101,7 @@ uint8_t *counts_lo(rtx_index *ix, rtx_index::Scratch &sc) { return reinterpret_c
 uint16_t *counts_hi(rtx_index *ix, rtx_index::Scratch &sc) {
     return reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(sc.d_counts.p) + (size_t)counts_rows_layout(ix) * ix->npad);
 }
-size_t counts_elems(const rtx_index *ix, uint64_t B) {  // u16 elements of d_counts
-    return ix->packed() ? (size_t)B * ix->npad * 5 / 8 : (size_t)B * ix->npad;
-}
-int ensure_full_counts(rtx_index *ix, rtx_index::Scratch &sc) { return sc.d_counts.alloc(counts_elems(ix, ix->sub_batch)); }
+int ensure_full_counts(rtx_index *ix, rtx_index::Scratch &sc) { return sc.d_counts.alloc(counts_elems(ix, ix->planes, ix->sub_batch)); }
 
 hipEvent_t stage_event(rtx_index *ix, const SubBatch &b, int stage, int which) {
     return ix->events[((size_t)b.sb * RTX_NUM_STAGES + stage) * 2 + which];
@@ -149,23 +146,33 @@ static KmerParams kmer_params(rtx_index *ix, const SubBatch &b) {
     return kp;
 }
 
+// What a sub-batch being enqueued goes through, decided once.  The run prunes (the recount of the debug taps leaves the pruning out):
+static bool run_prunes(const rtx_index *ix) { return ix->prune_used && !ix->dbg_full_run; }
+// ... its queries may take the records path (whole-database handles whose walk rides in the prefix launch: enqueue_prob_prefix starts
+// records_tail_kernel there).  rec_used implies a whole-database handle driven by enqueue_batch, which enqueues part 0 and fuses the walk;
+// the two callers still ask for that themselves, so that an rtx_shard_* call on such a handle stays off the path.
+static bool on_records_path(const rtx_index *ix, const rtx_index::Scratch &sc) { return run_prunes(ix) && ix->rec_used && sc.d_rec.p != nullptr; }
+// ... and the rows of its counts buffer are handed out with the decision about the records path (the diet)
+static bool on_diet(const rtx_index *ix, const rtx_index::Scratch &sc) { return on_records_path(ix, sc) && ix->diet_used && sc.d_cnt_row.p != nullptr; }
+
+static RecordRef record_ref(const rtx_index *ix, const rtx_index::Scratch &sc, const rtx_index::ResultSet &r) { return RecordRef{sc.d_rec_nslots.p, sc.d_rec_slots.p, sc.d_rec_cnt.p, sc.d_rec.p, ix->rec_slots(), ix->rec_seg_len, r.d_flags.p}; }
+static ProbTables prob_tables(const rtx_index *ix) { return ProbTables{ix->d_tab_cmf.p, ix->d_tab_ratio.p, ix->d_tab_off.p, ix->d_tab_moff.p, ix->d_tab_ilo.p, ix->d_tab_sat.p, ix->tab_tmax}; }
+
 int enqueue_kmer(rtx_index *ix, const SubBatch &b, hipStream_t s) {
     KmerParams kp = kmer_params(ix, b);
     // with tile pruning the per-tile lists wait until the live tiles are known (enqueue_hit); databases of few tiles build
     // their lists in one pass per tile whatever is live
-    kp.mode = ix->prune_used && !ix->dbg_full_run && ix->seg_blocks ? 1u : 0u;
+    kp.mode = run_prunes(ix) && ix->seg_blocks ? 1u : 0u;
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_KMER_EXTRACT, 0), s));
     launch_kmer_extract(s, kp, b.nq);
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_KMER_EXTRACT, 1), s));
     return RTX_OK;
 }
 
-// part 0: everything.  A reference shard that prunes stops in the middle for the exchange of the best blocks: part 1 = up to the
-// candidates (bounds pass, prune_kernel phase 1), part 2 = the rest (prune_kernel phase 2, lists of the live tiles, counting).
-int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s, int part, hipStream_t s_mid) {
+// the counting pass proper; what tile pruning adds (live masks, items, thresholds, records, rows of the diet) is filled in by enqueue_hit
+static HitParams hit_params(rtx_index *ix, const SubBatch &b, uint32_t flags) {
     rtx_index::Scratch &sc = ix->sc[b.set];
     rtx_index::ResultSet &r = ix->res();
-    ix->last_set = b.set;
     HitParams hp{};
     hp.bitmap = ix->d_bitmap.p;
     hp.stride_bytes = ix->stride_bytes;
@@ -199,12 +206,132 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
     hp.pair_urec = sc.d_urec.p;
     hp.pair_nu = sc.d_nu.p;
     hp.pair_ustride = 2u * ix->rstride;
-    hp.live = nullptr;
-    hp.live_words = 0;
-    hp.items = nullptr;
-    hp.n_items = nullptr;
-    hp.prune_thr = nullptr;
-    const bool prune = ix->prune_used && !ix->dbg_full_run;
+    return hp;
+}
+
+// (1) the queries against the union bitmap: every row dense, no lists, packed counts (bounds per block of references)
+static HitParams bounds_params(const rtx_index *ix, const rtx_index::Scratch &sc, const HitParams &hp) {
+    HitParams up = hp;
+    up.bitmap = ix->d_ubitmap.p;
+    up.stride_bytes = ix->u_stride_bytes;
+    up.n_refs = ix->u_nblocks;
+    up.dmask = nullptr;    // (a union bitmap is read densely: the kernel takes every row of the query, no masks, no sparse lists)
+    up.nsparse = nullptr;
+    up.ntiles = ix->u_ntiles;
+    up.counts = nullptr;  // nothing is stored per block: the epilogue keeps the largest bound per tile and the best block
+    up.counts_lo = nullptr;
+    up.counts_hi = nullptr;
+    up.hist = nullptr;
+    up.tile_max = nullptr;
+    up.bounds_tile_ub = sc.d_tile_ub.p;
+    up.bounds_tile_stride = ix->ntiles;
+    up.bounds_ntiles = ix->ntiles;
+    up.bounds_best = sc.d_best_key.p;
+    up.flags = 0;
+    up.group_base = hp.group_base + ix->n_groups_run;  // work accounting apart from the counting proper
+    return up;
+}
+
+// ... in two levels (rtx_bounds2.hip); heavy: the set has room for the queries and items left to the one-level pass
+static Bounds2Params bounds2_params(const rtx_index *ix, const rtx_index::Scratch &sc, const HitParams &up, bool heavy) {
+    Bounds2Params bp{};
+    bp.abitmap = ix->d_abitmap.p;
+    bp.bbitmap = ix->d_bbitmap.p;
+    bp.n_rows1 = ix->n_rows + 1;
+    bp.n_atiles = ix->n_atiles;
+    bp.ntiles = ix->ntiles;
+    bp.zero_row = ix->n_rows;
+    bp.pair_urec = sc.d_urec.p;
+    bp.pair_nu = sc.d_nu.p;
+    bp.pair_ustride = 2u * ix->rstride;
+    bp.nq = up.nq;
+    bp.t = sc.d_t.p;
+    bp.tile_ub = sc.d_tile_ub.p;
+    bp.tile_ub_stride = ix->ntiles;
+    bp.best_key = sc.d_best_key.p;
+    bp.delta_ct = ix->b2_delta[0];
+    bp.delta_cm = ix->b2_delta[1];
+    bp.delta_lo = ix->b2_delta[2];
+    bp.delta_hi = ix->b2_delta[3];
+    bp.group_rows = up.group_rows;
+    bp.group_base = up.group_base;
+    // queries whose rule asks for more than five B-tiles per A-tile go to the one-level pass (5 folds of level B ~ half of it)
+    bp.heavy = heavy ? sc.d_heavy.p : nullptr;
+    bp.heavy_max = std::max<uint32_t>(1u, std::min<uint32_t>(RTX_B2_HEAVY_PER_ATILE * ix->n_atiles, ix->n_btiles / 2u));
+    return bp;
+}
+
+// (2) bounds per tile, a lower bound of the best hit, the threshold, the live tiles of every pair
+static PruneParams prune_params(rtx_index *ix, const SubBatch &b, uint32_t flags, int part, const ExactRef &exact) {
+    rtx_index::Scratch &sc = ix->sc[b.set];
+    PruneParams pr{};
+    pr.tile_ub = sc.d_tile_ub.p;
+    pr.best_key = sc.d_best_key.p;
+    pr.tile_ub_stride = ix->ntiles;
+    pr.ntiles = ix->ntiles;
+    pr.nq = b.nq;
+    pr.n_refs = ix->n_refs;
+    pr.n_total = ix->n_total;
+    pr.ref_base = ix->ref_lo;
+    pr.phase = (uint32_t)part;
+    pr.best = part ? sc.d_best.p : nullptr;
+    pr.bitmap = ix->d_bitmap.p;
+    pr.cbitmap = part == 0 && (ix->two_level_used || (ix->planes > kBounds2MaxPlanes && ix->two_level_opt && ix->n_refs == ix->n_total)) ? reinterpret_cast<const uint2 *>(ix->d_cbitmap.p) : nullptr;  // (with the two-level pass: RTX_OPT_TWO_LEVEL_BOUNDS = 0 is the round-4 path whole)
+    pr.n_rows1 = ix->n_rows + 1;
+    pr.stride_bytes = ix->stride_bytes;
+    pr.rows = sc.d_rows.p;
+    pr.rstride = ix->rstride;
+    pr.nrows = sc.d_nrows.p;
+    pr.t = sc.d_t.p;
+    pr.flags = flags;
+    pr.q0 = b.q0;
+    pr.perm = ix->res().d_perm.p;
+    pr.exact = exact;
+    pr.lnfact = ix->d_lnfact.p;
+    pr.inv = ix->d_inv.p;
+    pr.nlf = std::min<uint32_t>(kLnFactLen, ix->tmax + ix->tmax / 2 + 2);  // (pruning runs with tmax <= 2047: 12 KB at t <= 1023, 25 KB at most)
+    pr.hist = sc.d_hist.p;
+    pr.hstride = ix->hstride;
+    pr.live = sc.d_live.p;
+    pr.live_words = LiveLayout{ix->ntiles}.words();
+    pr.pair_live = ItemsLayout(b.nq, ix->ntiles).pair_live(sc.d_items.p);
+    pr.thr_out = sc.d_prune_thr.p;
+    pr.i1_out = sc.d_prune_i1.p;
+    pr.stats = ix->d_prune_stats.p;
+    pr.detail = ix->debug_taps && ix->d_prune_detail.n >= (size_t)b.nq * kPruneDetailWords ? ix->d_prune_detail.p : nullptr;
+    return pr;
+}
+
+// (2b) the pairs that are left many live tiles against the fine union bitmap (blocks of 8 references)
+static HitParams fine_params(const rtx_index *ix, const rtx_index::Scratch &sc, const HitParams &hp) {
+    HitParams fp = hp;
+    fp.bitmap = ix->d_fbitmap.p;
+    fp.stride_bytes = ix->f_stride_bytes;
+    fp.n_refs = ix->f_nblocks;
+    fp.ntiles = ix->f_ntiles;
+    fp.counts = nullptr;
+    fp.counts_lo = nullptr;
+    fp.counts_hi = nullptr;
+    fp.tile_max = nullptr;
+    fp.flags = 0;
+    fp.group_rows = nullptr;  // (its rows are not part of the work accounting of the roofline: reported through its own counters)
+    fp.live = sc.d_live.p;
+    fp.live_words = LiveLayout{ix->ntiles}.words();
+    fp.prune_thr = sc.d_prune_thr.p;
+    fp.fine_n_refs = ix->n_refs;
+    fp.fine_ref_ntiles = ix->ntiles;
+    fp.fine_stats = ix->d_prune_stats.p + 2 * kPruneStatCopies * 8;
+    return fp;
+}
+
+// part 0: everything.  A reference shard that prunes stops in the middle for the exchange of the best blocks: part 1 = up to the
+// candidates (bounds pass, prune_kernel phase 1), part 2 = the rest (prune_kernel phase 2, lists of the live tiles, counting).
+int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s, int part, hipStream_t s_mid) {
+    rtx_index::Scratch &sc = ix->sc[b.set];
+    rtx_index::ResultSet &r = ix->res();
+    ix->last_set = b.set;
+    HitParams hp = hit_params(ix, b, flags);
+    const bool prune = run_prunes(ix);
     if (ix->pair_used && part != 2) {
         if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_PAIR_UNION, 0), s));
         launch_pair_union(s, sc.d_rows.p, sc.d_nrows.p, ix->rstride, b.nq, sc.d_urec.p, sc.d_nu.p, 2u * ix->rstride);
@@ -213,56 +340,14 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
     if (b.timed && !prune) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_HIT_COUNT, 0), s));
     if (part != 0 && !prune) { set_error("internal: a split run without tile pruning"); return RTX_ERR_STATE; }
     if (prune) {
-        // (1) the queries against the union bitmap: every row dense, no lists, packed counts (bounds per block of references)
-        HitParams up = hp;
-        up.bitmap = ix->d_ubitmap.p;
-        up.stride_bytes = ix->u_stride_bytes;
-        up.n_refs = ix->u_nblocks;
-        up.dmask = nullptr;    // (a union bitmap is read densely: the kernel takes every row of the query, no masks, no sparse lists)
-        up.nsparse = nullptr;
-        up.ntiles = ix->u_ntiles;
-        up.counts = nullptr;  // nothing is stored per block: the epilogue keeps the largest bound per tile and the best block
-        up.counts_lo = nullptr;
-        up.counts_hi = nullptr;
-        up.hist = nullptr;
-        up.tile_max = nullptr;
-        up.bounds_tile_ub = sc.d_tile_ub.p;
-        up.bounds_tile_stride = ix->ntiles;
-        up.bounds_ntiles = ix->ntiles;
-        up.bounds_best = sc.d_best_key.p;
-        up.flags = 0;
-        up.group_base = hp.group_base + ix->n_groups_run;  // work accounting apart from the counting proper
-        if (part != 2) {
+        if (part != 2) {  // (1) bounds
+            const HitParams up = bounds_params(ix, sc, hp);
             if (b.timed) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_TILE_BOUNDS, 0), s));
             // whole-database handles: the two-level pass (rtx_bounds2.hip); reference shards and RTX_OPT_TWO_LEVEL_BOUNDS = 0: blocks of 64 throughout
             ix->two_level_used = part == 0 && ix->two_level_opt && ix->d_abitmap.p && ix->d_bbitmap.p && ix->n_refs == ix->n_total && ix->planes <= kBounds2MaxPlanes;
             if (ix->two_level_used) {
-                Bounds2Params bp{};
-                bp.abitmap = ix->d_abitmap.p;
-                bp.bbitmap = ix->d_bbitmap.p;
-                bp.n_rows1 = ix->n_rows + 1;
-                bp.n_atiles = ix->n_atiles;
-                bp.ntiles = ix->ntiles;
-                bp.zero_row = ix->n_rows;
-                bp.pair_urec = sc.d_urec.p;
-                bp.pair_nu = sc.d_nu.p;
-                bp.pair_ustride = 2u * ix->rstride;
-                bp.nq = b.nq;
-                bp.t = sc.d_t.p;
-                bp.tile_ub = sc.d_tile_ub.p;
-                bp.tile_ub_stride = ix->ntiles;
-                bp.best_key = sc.d_best_key.p;
-                bp.delta_ct = ix->b2_delta[0];
-                bp.delta_cm = ix->b2_delta[1];
-                bp.delta_lo = ix->b2_delta[2];
-                bp.delta_hi = ix->b2_delta[3];
-                bp.group_rows = up.group_rows;
-                bp.group_base = up.group_base;
-                // queries whose rule asks for more than five B-tiles per A-tile go to the one-level pass (5 folds of level B ~ half of it)
-                const bool heavy_ok = sc.d_heavy.p && sc.d_heavy_items.p && sc.d_heavy_items.n >= (size_t)((b.nq + 1u) / 2u) * ix->u_ntiles + 9u;
-                bp.heavy = heavy_ok ? sc.d_heavy.p : nullptr;
-                bp.heavy_max = std::max<uint32_t>(1u, std::min<uint32_t>(RTX_B2_HEAVY_PER_ATILE * ix->n_atiles, ix->n_btiles / 2u));
-                launch_bounds2(s, bp, b.nq, ix->planes, up, ix->u_ntiles, heavy_ok ? sc.d_heavy_items.p : nullptr);
+                const bool heavy_ok = sc.d_heavy.p && sc.d_heavy_items.p && sc.d_heavy_items.n >= HeavyItemsLayout(b.nq, ix->u_ntiles).total();
+                launch_bounds2(s, bounds2_params(ix, sc, up, heavy_ok), b.nq, ix->planes, up, ix->u_ntiles, heavy_ok ? sc.d_heavy_items.p : nullptr);
             } else {
                 RTX_HIP(hipMemsetAsync(sc.d_best_key.p, 0, (size_t)b.nq * 4, s));  // the waves of a query's union tiles meet in an atomicMax
                 launch_hit_count_pair_bounds(s, up, b.nq, ix->u_ntiles, ix->planes);  // the union of the pair's rows serves both passes
@@ -275,48 +360,13 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
             s = s_mid;
         }
         if (b.timed && part != 1) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_TILE_PRUNE, 0), s));
-        // (2) bounds per tile, a lower bound of the best hit, the threshold, the live tiles of every pair
-        PruneParams pr{};
-        pr.tile_ub = sc.d_tile_ub.p;
-        pr.best_key = sc.d_best_key.p;
-        pr.tile_ub_stride = ix->ntiles;
-        pr.ntiles = ix->ntiles;
-        pr.nq = b.nq;
-        pr.n_refs = ix->n_refs;
-        pr.n_total = ix->n_total;
-        pr.ref_base = ix->ref_lo;
-        pr.phase = (uint32_t)part;
-        pr.best = part ? sc.d_best.p : nullptr;
-        pr.bitmap = ix->d_bitmap.p;
-        pr.cbitmap = part == 0 && (ix->two_level_used || (ix->planes > kBounds2MaxPlanes && ix->two_level_opt && ix->n_refs == ix->n_total)) ? reinterpret_cast<const uint2 *>(ix->d_cbitmap.p) : nullptr;  // (with the two-level pass: RTX_OPT_TWO_LEVEL_BOUNDS = 0 is the round-4 path whole)
-        pr.n_rows1 = ix->n_rows + 1;
-        pr.stride_bytes = ix->stride_bytes;
-        pr.rows = sc.d_rows.p;
-        pr.rstride = ix->rstride;
-        pr.nrows = sc.d_nrows.p;
-        pr.t = sc.d_t.p;
-        pr.flags = flags;
-        pr.q0 = b.q0;
-        pr.perm = r.d_perm.p;
-        pr.exact = hp.exact;
-        pr.lnfact = ix->d_lnfact.p;
-        pr.inv = ix->d_inv.p;
-        pr.nlf = std::min<uint32_t>(kLnFactLen, ix->tmax + ix->tmax / 2 + 2);  // (pruning runs with tmax <= 2047: 12 KB at t <= 1023, 25 KB at most)
-        pr.hist = sc.d_hist.p;
-        pr.hstride = ix->hstride;
-        pr.live = sc.d_live.p;
-        pr.live_words = (ix->ntiles + 31u) / 32u + 1u;
-        pr.pair_live = sc.d_items.p + (size_t)((b.nq + 1u) / 2u) * ix->ntiles + 9u;
-        pr.thr_out = sc.d_prune_thr.p;
-        pr.i1_out = sc.d_prune_i1.p;
-        pr.stats = ix->d_prune_stats.p;
-        pr.detail = ix->debug_taps && ix->d_prune_detail.n >= (size_t)b.nq * kPruneDetailWords ? ix->d_prune_detail.p : nullptr;
-        // the records path: whole-database handles whose walk rides in the prefix launch (enqueue_prob_prefix starts records_tail_kernel there)
-        const bool records = part == 0 && ix->rec_used && sc.d_rec.p != nullptr;
-        const RecordRef rr{sc.d_rec_nslots.p, sc.d_rec_slots.p, sc.d_rec_cnt.p, sc.d_rec.p, std::min<uint32_t>(ix->rec_opt, kRecMaxSlots), ix->rec_seg_len, r.d_flags.p};
+        // (2) threshold
+        PruneParams pr = prune_params(ix, b, flags, part, hp.exact);
+        const bool records = part == 0 && on_records_path(ix, sc), diet = part == 0 && on_diet(ix, sc);
+        const RecordRef rr = record_ref(ix, sc, r);
         if (records) { pr.rec = rr; pr.rec_max_slots = rr.stride; }
-        if (ix->diet_used && !(records && sc.d_cnt_row.p)) { set_error("internal: the counts buffer is on its diet without the records path"); return RTX_ERR_STATE; }
-        if (records && ix->diet_used && sc.d_cnt_row.p) {  // the rows of the counts buffer are handed out with the decision about the records path
+        if (ix->diet_used && !diet) { set_error("internal: the counts buffer is on its diet without the records path"); return RTX_ERR_STATE; }
+        if (diet) {
             RTX_HIP(hipMemsetAsync(sc.d_cnt_cursor.p, 0, 4, s));
             pr.cnt_row = sc.d_cnt_row.p;
             pr.cnt_cursor = sc.d_cnt_cursor.p;
@@ -324,32 +374,15 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
             pr.flags_out = r.d_flags.p;
             hp.cnt_row = sc.d_cnt_row.p;
         }
-        ProbTables tb{ix->d_tab_cmf.p, ix->d_tab_ratio.p, ix->d_tab_off.p, ix->d_tab_moff.p, ix->d_tab_ilo.p, ix->d_tab_sat.p, ix->tab_tmax};
-        launch_prune(s, pr, tb, b.nq);
+        launch_prune(s, pr, prob_tables(ix), b.nq);
         if (part == 1) { RTX_HIP(hipGetLastError()); return RTX_OK; }  // the caller exchanges RTX_BUF_BEST, then part 2
         // (2b) second stage of the bounds (whole-database handles with a fine union bitmap): the pairs that are left many live tiles are
         // counted against the union bitmap over blocks of 8 references, which takes the tiles without a block above the threshold off
         // their lists (fine_epilogue); prune_kernel's number of live tiles per pair is brought up to date for the list below
         if (part == 0 && ix->fine_opt && ix->d_fbitmap.p && ix->pair_used && sc.d_fine_items.p) {
-            HitParams fp = hp;
-            fp.bitmap = ix->d_fbitmap.p;
-            fp.stride_bytes = ix->f_stride_bytes;
-            fp.n_refs = ix->f_nblocks;
-            fp.ntiles = ix->f_ntiles;
-            fp.counts = nullptr;
-            fp.counts_lo = nullptr;
-            fp.counts_hi = nullptr;
-            fp.tile_max = nullptr;
-            fp.flags = 0;
-            fp.group_rows = nullptr;  // (its rows are not part of the work accounting of the roofline: reported through its own counters)
-            fp.live = sc.d_live.p;
-            fp.live_words = pr.live_words;
-            fp.prune_thr = sc.d_prune_thr.p;
-            fp.fine_n_refs = ix->n_refs;
-            fp.fine_ref_ntiles = ix->ntiles;
-            fp.fine_stats = ix->d_prune_stats.p + 2 * kPruneStatCopies * 8;
-            const size_t cap_f = (size_t)((b.nq + 1u) / 2u) * ix->f_ntiles;
-            launch_fine_bounds(s, fp, b.nq, ix->ntiles, ix->f_ntiles, pr.pair_live, sc.d_fine_items.p + cap_f + 9u, sc.d_fine_items.p, sc.d_fine_items.p + cap_f, ix->planes);
+            const FineItemsLayout fine(b.nq, ix->f_ntiles);
+            uint32_t *const fi = sc.d_fine_items.p;
+            launch_fine_bounds(s, fine_params(ix, sc, hp), b.nq, ix->ntiles, ix->f_ntiles, pr.pair_live, fine.cursors(fi), fine.items(fi), fine.count(fi), ix->planes);
         }
         // (3) tiles that are not counted keep a largest count of 0: taxon_prefix leaves them out
         RTX_HIP(hipMemsetAsync(sc.d_tilemax.p, 0, (size_t)b.nq * ix->ntiles * 2, s));
@@ -358,10 +391,10 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         hp.prune_thr = sc.d_prune_thr.p;
         if (records) hp.rec = rr;
         if (ix->pair_used) {  // the grid of the counting pass walks the live (pair, tile) blocks instead of all of them
-            const size_t np = (b.nq + 1u) / 2u, cap = np * ix->ntiles;
-            launch_live_items(s, sc.d_live.p, pr.live_words, pr.pair_live, b.nq, ix->ntiles, sc.d_items.p + cap + 9u + np, sc.d_items.p, sc.d_items.p + cap);
-            hp.items = sc.d_items.p;
-            hp.n_items = sc.d_items.p + cap;
+            const ItemsLayout items(b.nq, ix->ntiles);
+            launch_live_items(s, sc.d_live.p, pr.live_words, pr.pair_live, b.nq, ix->ntiles, items.offsets(sc.d_items.p), items.items(sc.d_items.p), items.count(sc.d_items.p));
+            hp.items = items.items(sc.d_items.p);
+            hp.n_items = items.count(sc.d_items.p);
         }
         if (ix->seg_blocks) {  // (4) the row lists of the live tiles (kmer_extract left them out)
             KmerParams kp = kmer_params(ix, b);
@@ -410,15 +443,13 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     pp.gs = r.d_gs.p;
     pp.status = r.d_status.p;
     pp.ndist = r.d_ndist.p;
-    pp.prune_thr = ix->prune_used && !ix->dbg_full_run ? sc.d_prune_thr.p : nullptr;
+    pp.prune_thr = run_prunes(ix) ? sc.d_prune_thr.p : nullptr;
     pp.prune_i1 = pp.prune_thr ? sc.d_prune_i1.p : nullptr;
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_PROB_TABLE, 0), s));
     if (ix->use_tables) {
-        ProbTables tb{ix->d_tab_cmf.p, ix->d_tab_ratio.p, ix->d_tab_off.p, ix->d_tab_moff.p,
-                      ix->d_tab_ilo.p, ix->d_tab_sat.p, ix->tab_tmax};
         launch_prob_order(s, sc.d_t.p, b.nq, sc.d_order.p);
         pp.order = sc.d_order.p;
-        launch_prob_lookup(s, pp, tb, b.nq);
+        launch_prob_lookup(s, pp, prob_tables(ix), b.nq);
     } else {
         if (ix->cur_cls >= 0 && ix->cls[ix->cur_cls].huge) {  // its arrays do not fit LDS: a stretch of global memory per query
             pp.gstride = (uint32_t)((prob_table_lds_bytes(ix->tmax) + 7) / 8);
@@ -449,12 +480,12 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     fp.n_bnd = ix->n_bnd_local;
     fp.tile_max = ix->tile_skip ? sc.d_tilemax.p : nullptr;
     fp.ntiles = ix->ntiles;
-    fp.prune_thr = ix->prune_used && !ix->dbg_full_run ? sc.d_prune_thr.p : nullptr;
+    fp.prune_thr = pp.prune_thr;
     fp.prune_stats = fp.prune_thr ? ix->d_prune_stats.p + kPruneStatCopies * 8 : nullptr;
     fp.fuse_walk = fuse_walk ? 1u : 0u;
-    const bool records = fuse_walk && fp.prune_thr && ix->rec_used && sc.d_rec.p != nullptr;
+    const bool records = fuse_walk && on_records_path(ix, sc);
     fp.rec_nslots = records ? sc.d_rec_nslots.p : nullptr;
-    fp.cnt_row = records && ix->diet_used && sc.d_cnt_row.p ? sc.d_cnt_row.p : nullptr;
+    fp.cnt_row = fuse_walk && on_diet(ix, sc) ? sc.d_cnt_row.p : nullptr;
     if (fuse_walk) {
         fp.walk = walk_params(ix, b, sc.d_prefix.p);
         int rc_r = fp.walk.sub_alloc ? reset_sub_alloc(ix, s) : RTX_OK;
@@ -464,7 +495,7 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     launch_taxon_prefix(s, fp, b.nq);
     if (records) {  // the queries on the records path: prefix sums from their records, the walk from LDS (rtx_records.hip)
         TailParams tp{};
-        tp.rec = RecordRef{sc.d_rec_nslots.p, sc.d_rec_slots.p, sc.d_rec_cnt.p, sc.d_rec.p, std::min<uint32_t>(ix->rec_opt, kRecMaxSlots), ix->rec_seg_len, r.d_flags.p};
+        tp.rec = record_ref(ix, sc, r);
         tp.t = sc.d_t.p;
         tp.table_z = sc.d_table_z.p;
         tp.hstride = ix->hstride;
@@ -695,9 +726,9 @@ int begin_run(rtx_index *ix, uint32_t *n_sub_out, bool *timed_out, bool cluster)
     const bool whole = ix->n_refs == ix->n_total && !ix->staged;
     const bool shard = ix->staged && ix->shard_prune_opt && ix->n_refs != ix->n_total;
     auto scratch_ok = [&](const rtx_index::Scratch &sc, uint32_t B) {  // sized at the upload / rtx_shard_begin (alloc_scratch_set) for this sub-batch size
-        return sc.d_tile_ub.p != nullptr && sc.d_tile_ub.n >= (size_t)B * ix->ntiles && sc.d_best_key.n >= B && sc.d_prune_thr.n >= B &&
-               sc.d_live.n >= (size_t)(B + 1u) * ((ix->ntiles + 31u) / 32u + 1u) && sc.d_best.n >= (size_t)B * kPruneBestWords &&
-               sc.d_items.n >= (size_t)((B + 1u) / 2u) * (ix->ntiles + 2u) + 9u;
+        const ScratchNeed n = ScratchNeed().set_queries(ix, B);
+        return sc.d_tile_ub.p != nullptr && sc.d_tile_ub.n >= n.tile_ub && sc.d_best_key.n >= n.best_key && sc.d_prune_thr.n >= n.prune_thr &&
+               sc.d_live.n >= n.live && sc.d_best.n >= n.best && sc.d_items.n >= n.items;
     };
     bool any_pair = false, any_prune = false;
     uint32_t b_max = 1;
@@ -706,34 +737,32 @@ int begin_run(rtx_index *ix, uint32_t *n_sub_out, bool *timed_out, bool cluster)
         // two neighbours per wave only pays when neighbours are related: with the processing order on
         k.pair = ix->pair_opt && cluster && k.planes <= 11 && ix->n_q > 1 && k.rstride <= 4096;
         const rtx_index::Scratch &s0 = ix->sc[k.side ? kSideSet : 0u];  // (a side class runs through the set of its own)
+        ScratchNeed need = ScratchNeed().set_queries(ix, k.sub_batch);  // of a sub-batch of the class
         if (whole && ix->rec_opt != 0u && ix->pruning())  // (segments that have grown since the workspace was sized: RecordRef::seg_len)
             for (uint32_t j = 0; j < 4u; j++) {
                 rtx_index::Scratch &sc = ix->sc[j];
-                const size_t need_r = (size_t)k.sub_batch * std::min<uint32_t>(ix->rec_opt, kRecMaxSlots) * ix->rec_seg_len;
-                if ((j == kSideSet) != k.side || sc.d_kmers.p == nullptr || sc.d_rec.p == nullptr || sc.d_rec.n >= need_r) continue;
+                if ((j == kSideSet) != k.side || sc.d_kmers.p == nullptr || sc.d_rec.p == nullptr || sc.d_rec.n >= need.rec) continue;
                 RTX_HIP(hipStreamSynchronize(ix->stream));
-                if (sc.d_rec.alloc(need_r)) sc.d_rec.release();
+                if (sc.d_rec.alloc(need.rec)) sc.d_rec.release();
             }
         k.prune = ix->pruning() && k.pair && k.use_tables && ix->tile_skip && ix->d_ubitmap.p && (whole || shard) &&
                   scratch_ok(s0, k.sub_batch) && (!ix->staged || scratch_ok(ix->sc[1], k.sub_batch));
-        k.rec = k.prune && whole && ix->rec_opt != 0u && ix->n_bnd_local == ix->n_bnd && s0.d_rec.p != nullptr &&
-                s0.d_rec.n >= (size_t)k.sub_batch * std::min<uint32_t>(ix->rec_opt, kRecMaxSlots) * ix->rec_seg_len;
+        k.rec = k.prune && whole && ix->rec_opt != 0u && ix->n_bnd_local == ix->n_bnd && s0.d_rec.p != nullptr && s0.d_rec.n >= need.rec;
         // the diet of the counts buffer: only with the records path (the queries without rows are exactly those on it), in every set the class may run through
-        auto diet_ok = [&](const rtx_index::Scratch &sc) { return sc.d_rec.p != nullptr && sc.d_cnt_row.p != nullptr && sc.d_cnt_cursor.p != nullptr && sc.d_cnt_row.n >= k.sub_batch; };
+        auto diet_ok = [&](const rtx_index::Scratch &sc) { return sc.d_rec.p != nullptr && sc.d_cnt_row.p != nullptr && sc.d_cnt_cursor.p != nullptr && sc.d_cnt_row.n >= need.cnt_row; };
         k.diet = k.rec && diet_rows(ix, k.sub_batch) < k.sub_batch && diet_ok(s0);
         if (k.diet && !k.side)
             for (uint32_t j = 1; j <= 2u; j++)
                 if (ix->sc[j].d_kmers.p != nullptr && !diet_ok(ix->sc[j])) k.diet = false;
         k.cnt_rows = k.diet ? diet_rows(ix, k.sub_batch) : k.sub_batch;
         {   // room for that many rows in the sets the class runs through (a class that was sized for the diet and runs without it, a diet that has grown)
-            const size_t need = ix->packed_opt && k.planes <= 10 ? (size_t)k.cnt_rows * ix->npad * 5 / 8 : (size_t)k.cnt_rows * ix->npad;
-            const size_t need_p = (size_t)k.cnt_rows * ix->n_bnd_local;  // (the rows of the boundary prefix sums go with those of the counts)
+            need.add_class(ix, k, k.sub_batch, k.cnt_rows);  // (the rows of the boundary prefix sums go with those of the counts)
             for (uint32_t j = 0; j < 4u; j++) {
                 rtx_index::Scratch &sc = ix->sc[j];
-                if ((j == kSideSet) != k.side || sc.d_kmers.p == nullptr || (sc.d_counts.n >= need && sc.d_prefix.n >= need_p)) continue;
+                if ((j == kSideSet) != k.side || sc.d_kmers.p == nullptr || (sc.d_counts.n >= need.counts && sc.d_prefix.n >= need.prefix)) continue;
                 RTX_HIP(hipStreamSynchronize(ix->stream));  // (nothing of an earlier run may still read the old buffers)
-                int rc_c = sc.d_counts.alloc(need);
-                if (!rc_c) rc_c = sc.d_prefix.alloc(need_p);
+                int rc_c = sc.d_counts.alloc(need.counts);
+                if (!rc_c) rc_c = sc.d_prefix.alloc(need.prefix);
                 if (rc_c) return rc_c;
             }
         }
@@ -942,7 +971,8 @@ int ensure_prob_tables(rtx_index *ix, uint32_t tmax, bool *usable) {
         return rc;
     RTX_HIP(hipMemcpy(ix->d_tab_off.p, off.data(), (T + 1) * 8, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(ix->d_tab_moff.p, moff.data(), (T + 1) * 4, hipMemcpyHostToDevice));
-    ProbTables tb{ix->d_tab_cmf.p, ix->d_tab_ratio.p, ix->d_tab_off.p, ix->d_tab_moff.p, ix->d_tab_ilo.p, ix->d_tab_sat.p, T};
+    ProbTables tb = prob_tables(ix);
+    tb.tmax = T;  // (tab_tmax follows once they are built)
     launch_prob_tables_build(ix->stream, tb, ix->d_lnfact.p, ix->d_inv.p);
     RTX_HIP(hipGetLastError());
     RTX_HIP(hipStreamSynchronize(ix->stream));
@@ -1079,19 +1109,6 @@ int prepare_workspace_single(rtx_index *ix, uint64_t n_queries, uint64_t tmax, u
     return size_workspace(ix, n_queries);
 }
 
-// per-query scratch bytes of a class (what a sub-batch of it costs per query)
-static uint64_t class_per_q(const rtx_index *ix, const rtx_index::BatchClass &k) {
-    const bool packed = ix->packed_opt && k.planes <= 10;
-    return (uint64_t)k.kstride * 2 + (uint64_t)k.rstride * 12 + 4 + (uint64_t)ix->ntiles * (k.rstride / 8 + ((kSegMaxSparseRows + 1) * 4 + 10)) + (packed ? ix->npad * 5 / 4 : ix->npad * 2) +
-           (uint64_t)k.hstride * 12 + (uint64_t)ix->n_bnd_local * 8 + 64 + (k.huge ? prob_table_lds_bytes(k.tmax) : 0) +
-           // + the scratch of the tile pruning: tile bounds, thresholds, live masks, best blocks, the lists of live blocks
-           (k.will_prune ? (uint64_t)ix->ntiles * 2 + 12 + (ix->ntiles + 31u) / 32u * 2u + 2u + kPruneBestWords * 4 +
-                               ((uint64_t)ix->ntiles + 2u) * 2u  /* the list of live (pair, tile) blocks: 4 bytes per pair and tile */ +
-                               (ix->d_fbitmap.p ? (uint64_t)ix->f_ntiles * 2u + 1u : 0u) /* the items of the fine bounds pass */ +
-                               (ix->rec_opt && ix->n_refs == ix->n_total ? (uint64_t)std::min<uint32_t>(ix->rec_opt, kRecMaxSlots) * 32768u + kRecMaxSlots * 6u + 2u : 0u) /* record segments */
-                           : 0);
-}
-
 static int size_workspace(rtx_index *ix, uint64_t n_queries) {
     int rc;
     // the memoised probability tables serve every class with t <= 1023: built for the longest of them
@@ -1182,49 +1199,27 @@ static int size_workspace(rtx_index *ix, uint64_t n_queries) {
     return RTX_OK;
 }
 
-// One set of sub-batch scratch, every buffer sized for the class that needs most of it.
+// One set of sub-batch scratch (scratch_set_need).  The buffers every run needs are mandatory; a group that only a faster path needs is given
+// up whole when one of its allocations fails (begin_run and enqueue_hit then leave that path out).
 int alloc_scratch_set(rtx_index *ix, uint32_t k) {
     int rc;
     rtx_index::Scratch &sc = ix->sc[k];
-    size_t n_kmers = 0, n_rows = 0, n_dmask = 0, n_counts = 0, n_hist = 0, n_urec = 0, b_max = 1, n_probscr = 0, r_max = 1;
-    for (uint32_t c = 0; c < ix->n_cls; c++) {
-        const rtx_index::BatchClass &kc = ix->cls[c];
-        if (kc.side != (k == kSideSet)) continue;  // set 3 serves the side classes, the others the bulk
-        const size_t B = kc.sub_batch;
-        b_max = std::max(b_max, B);
-        n_kmers = std::max(n_kmers, B * kc.kstride);
-        n_rows = std::max(n_rows, B * kc.rstride);
-        n_dmask = std::max(n_dmask, B * ix->ntiles * (kc.rstride / 64));
-        // (a class that will prune with the records path starts with a fraction of the rows: begin_run enlarges the buffer if the run turns out otherwise)
-        const bool diet = kc.will_prune && ix->rec_opt != 0u && ix->n_refs == ix->n_total && ix->n_bnd_local == ix->n_bnd;
-        const size_t R = diet ? diet_rows(ix, (uint32_t)B) : B;
-        n_counts = std::max(n_counts, ix->packed_opt && kc.planes <= 10 ? R * ix->npad * 5 / 8 : R * ix->npad);
-        r_max = std::max(r_max, R);
-        n_hist = std::max(n_hist, B * kc.hstride);
-        n_urec = std::max(n_urec, ((B + 1u) / 2u) * 2u * kc.rstride);
-        if (kc.huge) n_probscr = std::max(n_probscr, B * ((prob_table_lds_bytes(kc.tmax) + 7) / 8));
-    }
-    const size_t B = b_max;
-    if ((rc = sc.d_kmers.alloc(n_kmers)) || (rc = sc.d_rows.alloc(n_rows)) || (rc = sc.d_dmask.alloc(n_dmask)) ||
-        (rc = sc.d_nsparse.alloc(B * ix->ntiles)) || (rc = sc.d_srows.alloc(B * ix->ntiles * (kSegMaxSparseRows + 1))) ||
-        (rc = sc.d_t.alloc(B)) || (rc = sc.d_nrows.alloc(B)) || (rc = sc.d_counts.alloc(n_counts)) ||
-        (rc = sc.d_hist.alloc(n_hist)) || (rc = sc.d_table_z.alloc(n_hist)) ||
-        (rc = sc.d_prefix.alloc(r_max * ix->n_bnd_local)) || (rc = sc.d_order.alloc(B)) ||
-        (rc = sc.d_tilemax.alloc(B * ix->ntiles)) ||
-        (rc = sc.d_urec.alloc(n_urec)) || (rc = sc.d_nu.alloc((B + 1u) / 2u)))
+    const ScratchNeed n = scratch_set_need(ix, k);
+    if ((rc = sc.d_kmers.alloc(n.kmers)) || (rc = sc.d_rows.alloc(n.rows)) || (rc = sc.d_dmask.alloc(n.dmask)) || (rc = sc.d_nsparse.alloc(n.nsparse)) || (rc = sc.d_srows.alloc(n.srows)) ||
+        (rc = sc.d_t.alloc(n.t)) || (rc = sc.d_nrows.alloc(n.nrows)) || (rc = sc.d_counts.alloc(n.counts)) || (rc = sc.d_hist.alloc(n.hist)) || (rc = sc.d_table_z.alloc(n.hist)) ||
+        (rc = sc.d_prefix.alloc(n.prefix)) || (rc = sc.d_order.alloc(n.order)) || (rc = sc.d_tilemax.alloc(n.tilemax)) || (rc = sc.d_urec.alloc(n.urec)) || (rc = sc.d_nu.alloc(n.nu)))
         return rc;
-    if (n_probscr && (rc = ix->d_prob_scratch.alloc(std::max(n_probscr, ix->d_prob_scratch.n)))) return rc;
+    if (n.prob_scratch && (rc = ix->d_prob_scratch.alloc(std::max(n.prob_scratch, ix->d_prob_scratch.n)))) return rc;
     if (ix->pruning() && ix->d_ubitmap.p && (ix->n_refs == ix->n_total || ix->shard_prune_opt)) {
-        if ((rc = sc.d_tile_ub.alloc(B * ix->ntiles)) || (rc = sc.d_best_key.alloc(B)) || (rc = sc.d_prune_thr.alloc(B)) || (rc = sc.d_prune_i1.alloc(B)) || (rc = sc.d_best.alloc(B * kPruneBestWords)) || (rc = sc.d_live.alloc((B + 1u) * ((ix->ntiles + 31u) / 32u + 1u))) ||
-            (rc = sc.d_items.alloc(((B + 1u) / 2u) * (ix->ntiles + 2u) + 9u)))
+        if ((rc = sc.d_tile_ub.alloc(n.tile_ub)) || (rc = sc.d_best_key.alloc(n.best_key)) || (rc = sc.d_prune_thr.alloc(n.prune_thr)) || (rc = sc.d_prune_i1.alloc(n.prune_i1)) ||
+            (rc = sc.d_best.alloc(n.best)) || (rc = sc.d_live.alloc(n.live)) || (rc = sc.d_items.alloc(n.items)))
             return rc;
-        if (ix->d_abitmap.p && (sc.d_heavy.alloc(B + 1u) || sc.d_heavy_items.alloc(((B + 1u) / 2u) * ix->u_ntiles + 9u))) { sc.d_heavy.release(); sc.d_heavy_items.release(); }
+        if (ix->d_abitmap.p && (sc.d_heavy.alloc(n.heavy) || sc.d_heavy_items.alloc(n.heavy_items))) { sc.d_heavy.release(); sc.d_heavy_items.release(); }
         // (a failed allocation of the fine pass's lists only switches the pass off: enqueue_hit tolerates a null pointer)
-        if (ix->d_fbitmap.p && sc.d_fine_items.alloc(((B + 1u) / 2u) * ix->f_ntiles + 9u + ix->f_ntiles)) sc.d_fine_items.release();
+        if (ix->d_fbitmap.p && sc.d_fine_items.alloc(n.fine_items)) sc.d_fine_items.release();
         if (ix->rec_opt && ix->n_refs == ix->n_total) {  // the records path; without its buffers the run takes the dense epilogues
-            const size_t slots = std::min<uint32_t>(ix->rec_opt, kRecMaxSlots);
-            if (sc.d_rec_nslots.alloc(B) || sc.d_rec_slots.alloc(B * kRecMaxSlots) || sc.d_rec_cnt.alloc(B * kRecMaxSlots) ||
-                sc.d_rec.alloc(B * slots * ix->rec_seg_len) || sc.d_cnt_row.alloc(B) || sc.d_cnt_cursor.alloc(4))
+            if (sc.d_rec_nslots.alloc(n.rec_nslots) || sc.d_rec_slots.alloc(n.rec_slots) || sc.d_rec_cnt.alloc(n.rec_cnt) ||
+                sc.d_rec.alloc(n.rec) || sc.d_cnt_row.alloc(n.cnt_row) || sc.d_cnt_cursor.alloc(n.cnt_cursor))
                 sc.d_rec.release();
         }
     }

@@ -250,7 +250,7 @@ int rtx_debug_run_counts(rtx_index *ix, uint64_t query, uint16_t *counts, uint8_
     std::vector<uint8_t> live(nt, 1);
     uint16_t thr = 0, i1v = 0;
     if (ix->prune_used) {
-        const uint32_t lw = (nt + 31u) / 32u + 1u;
+        const uint32_t lw = LiveLayout{nt}.words();
         std::vector<uint32_t> words(lw);
         RTX_HIP(hipMemcpy(words.data(), sc.d_live.p + (size_t)slot * lw, lw * 4, hipMemcpyDeviceToHost));
         for (uint32_t T = 0; T < nt; T++) live[T] = (uint8_t)((words[T >> 5] >> (T & 31u)) & 1u);
@@ -261,7 +261,7 @@ int rtx_debug_run_counts(rtx_index *ix, uint64_t query, uint16_t *counts, uint8_
     if (ix->prune_used && ix->rec_used && sc.d_rec_nslots.p) RTX_HIP(hipMemcpy(&n_seg, sc.d_rec_nslots.p + slot, 2, hipMemcpyDeviceToHost));
     if (counts && n_seg) {
         // visited tiles: the count of every reference above the threshold, 0 for the others (the run never wrote those); unvisited: 0xFFFF
-        const uint32_t stride = std::min<uint32_t>(ix->rec_opt, kRecMaxSlots);
+        const uint32_t stride = ix->rec_slots();
         uint16_t tiles[kRecMaxSlots];
         uint32_t cnts[kRecMaxSlots];
         RTX_HIP(hipMemcpy(tiles, sc.d_rec_slots.p + (size_t)slot * kRecMaxSlots, sizeof tiles, hipMemcpyDeviceToHost));

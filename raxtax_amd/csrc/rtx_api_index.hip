@@ -720,11 +720,7 @@ uint64_t rtx_index_device_bytes(const rtx_index *index) {
 uint64_t rtx_index_workspace_bytes(const rtx_index *ix) {
     if (!ix) return 0;
     uint64_t b = (ix->d_tab_cmf.n + ix->d_tab_ratio.n) * 8 + ix->d_tab_off.n * 8 + ix->d_tab_moff.n * 4 + (ix->d_tab_ilo.n + ix->d_tab_sat.n) * 2 + ix->d_node_depth.n + ix->d_node_sig0.n + ix->d_node_begin.n * 4 + ix->d_node_eb.n * 8;
-    for (const auto &sc : ix->sc)
-        b += (sc.d_kmers.n + sc.d_counts.n + sc.d_tilemax.n + sc.d_tile_ub.n + sc.d_prune_thr.n + sc.d_prune_i1.n + sc.d_rec_nslots.n + sc.d_rec_slots.n) * 2 +
-             (sc.d_rows.n + sc.d_t.n + sc.d_nrows.n + sc.d_hist.n + sc.d_order.n + sc.d_srows.n + sc.d_nsparse.n + sc.d_nu.n + sc.d_live.n + sc.d_best_key.n + sc.d_items.n + sc.d_best.n +
-              sc.d_heavy_items.n + sc.d_fine_items.n + sc.d_rec_cnt.n + sc.d_rec.n) * 4 +
-             (sc.d_dmask.n + sc.d_table_z.n + sc.d_prefix.n + sc.d_urec.n) * 8 + sc.d_heavy.n;
+    for (const auto &sc : ix->sc) b += sc.bytes();
     for (const auto &in : ix->in) b += in.d_packed.n + (in.d_base_off.n + in.d_exact_off.n) * 8 + in.d_exact_ids.n * 4;
     b += ix->d_bases.n + ix->d_prob_scratch.n * 8 + (ix->d_skey_in.n + ix->d_skey_out.n) * 8 + ix->d_sidx.n * 4 + ix->d_sort_tmp.n + ix->d_group_rows.n * 4;
     for (const auto &r : ix->rs) {
@@ -742,10 +738,10 @@ int rtx_index_workspace_parts(const rtx_index *ix, uint64_t out[9]) {
     for (const auto &sc : ix->sc) {
         if (!sc.d_kmers.p) continue;
         out[8]++;
-        out[1] += sc.d_counts.n * 2;
-        out[2] += sc.d_rec.n * 4 + sc.d_rec_cnt.n * 4 + (sc.d_rec_nslots.n + sc.d_rec_slots.n) * 2;
-        out[3] += sc.d_prefix.n * 8;
-        out[4] += sc.d_dmask.n * 8 + (sc.d_srows.n + sc.d_nsparse.n) * 4;
+        out[1] += sc.d_counts.bytes();
+        out[2] += sc.d_rec.bytes() + sc.d_rec_cnt.bytes() + sc.d_rec_nslots.bytes() + sc.d_rec_slots.bytes();
+        out[3] += sc.d_prefix.bytes();
+        out[4] += sc.d_dmask.bytes() + sc.d_srows.bytes() + sc.d_nsparse.bytes();
     }
     out[6] = ix->d_bases.n + (ix->d_skey_in.n + ix->d_skey_out.n) * 8 + ix->d_sidx.n * 4 + ix->d_sort_tmp.n;
     for (const auto &in : ix->in) out[6] += in.d_packed.n + (in.d_base_off.n + in.d_exact_off.n) * 8 + in.d_exact_ids.n * 4;

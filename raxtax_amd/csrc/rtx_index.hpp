@@ -59,6 +59,7 @@ struct DevBuf {
         p = nullptr;
         n = 0;
     }
+    uint64_t bytes() const { return (uint64_t)n * sizeof(T); }
     ~DevBuf() { release(); }
 };
 
@@ -220,6 +221,7 @@ struct rtx_index {
     bool diet_used = false;      // the class being enqueued lays its counts out in cnt_rows_cur rows
     uint32_t cnt_rows_cur = 0;
     uint32_t rec_opt = 4;   // RTX_OPT_RECORDS: pruned queries with at most this many live tiles take the records path (0: off; at most kRecMaxSlots)
+    uint32_t rec_slots() const { return std::min<uint32_t>(rec_opt, kRecMaxSlots); }  // record segments per query (RecordRef::stride)
     uint32_t overlap_opt = 1;  // RTX_OPT_OVERLAP: 1 = back half of sub-batch k on a second stream beside the front half of k + 1 (2: three stages)
     uint32_t overlap_used = 0;  // scratch sets the last run used beside each other (0: one stream)
     hipStream_t stream2 = nullptr, stream3 = nullptr, hit_stream = nullptr;  // (hit_stream: where enqueue_hit launched the counting pass)
@@ -235,7 +237,8 @@ struct rtx_index {
     DevBuf<uint32_t> d_group_rows;
     uint32_t n_groups_run = 0;  // groups of the whole batch (n_sub * groups_per_sub): the second half of d_group_rows starts there
     uint32_t groups_per_sub = 0;
-    bool packed() const { return packed_opt && planes <= 10; }  // (11 planes -- reads of 1 031 .. 2 054 bases on the pair kernel -- leave u16 counts)
+    bool packs(int pl) const { return packed_opt && pl <= 10; }  // counts of a class of `pl` bit planes travel packed (11 planes -- reads of 1 031 .. 2 054 bases on the pair kernel -- leave u16 counts)
+    bool packed() const { return packs(planes); }
     DevBuf<uint64_t> d_skey_in, d_skey_out;
     DevBuf<uint32_t> d_sidx;
     DevBuf<uint8_t> d_sort_tmp;
@@ -309,23 +312,32 @@ struct rtx_index {
         DevBuf<uint32_t> d_nu;
         // tile pruning: the queries counted against the union bitmap (every row dense) leave the largest bound of
         // every tile and the best block (bounds_epilogue); thresholds and the live tiles per pair (prune_kernel)
-        DevBuf<uint32_t> d_live, d_best_key;
-        DevBuf<uint32_t> d_items;  // [pairs x tiles] the (pair, tile) blocks with a live query | [1] their number | [8] queue per XCD | [pairs] live tiles per pair | [pairs] offsets
+        DevBuf<uint32_t> d_live, d_best_key;  // (d_live: LiveLayout)
+        DevBuf<uint32_t> d_items;  // the (pair, tile) blocks with a live query, live tiles per pair, offsets (ItemsLayout)
         DevBuf<uint16_t> d_tile_ub, d_prune_thr, d_prune_i1;
         DevBuf<uint32_t> d_best;  // [B][kPruneBestWords] reference shards: the candidate for the best block of the database
         DevBuf<uint8_t> d_heavy;        // two-level bounds pass: [B] queries left to the one-level pass (Bounds2Params::heavy)
-        DevBuf<uint32_t> d_heavy_items; // ... and the (pair, union tile) items of that pass: [pairs x u_ntiles] | [9]
-        DevBuf<uint32_t> d_fine_items;  // fine bounds pass: [pairs x f_ntiles] items | [9] number + XCD queues | [f_ntiles] cursors
+        DevBuf<uint32_t> d_heavy_items; // ... and the (pair, union tile) items of that pass (HeavyItemsLayout)
+        DevBuf<uint32_t> d_fine_items;  // fine bounds pass: its items and cursors (FineItemsLayout)
         // the records path (RecordRef, rtx_kernels.hpp): per query the live tiles at prune time, the records of each, their number
         DevBuf<uint16_t> d_rec_nslots, d_rec_slots;
         DevBuf<uint32_t> d_rec_cnt, d_rec;
         DevBuf<uint32_t> d_cnt_row, d_cnt_cursor;  // [B] row of the counts buffer per query | [1] rows handed out (HitParams::cnt_row)
-        void release_all() {
-            d_kmers.release(); d_counts.release(); d_tilemax.release(); d_rows.release(); d_t.release(); d_nrows.release(); d_hist.release();
-            d_order.release(); d_srows.release(); d_nsparse.release(); d_dmask.release(); d_table_z.release(); d_prefix.release(); d_urec.release();
-            d_nu.release(); d_live.release(); d_best_key.release(); d_items.release(); d_tile_ub.release(); d_prune_thr.release(); d_prune_i1.release();
-            d_best.release(); d_fine_items.release(); d_heavy.release(); d_heavy_items.release(); d_rec_nslots.release(); d_rec_slots.release(); d_rec_cnt.release(); d_rec.release();
-            d_cnt_row.release(); d_cnt_cursor.release();
+        // every buffer of a set, once: what release_all and bytes() (and whoever else wants all of them) walk
+        template <class S, class F>
+        static void each(S &s, F &&f) {
+            f(s.d_kmers); f(s.d_counts); f(s.d_tilemax); f(s.d_rows); f(s.d_t); f(s.d_nrows); f(s.d_hist); f(s.d_order); f(s.d_srows); f(s.d_nsparse);
+            f(s.d_dmask); f(s.d_table_z); f(s.d_prefix); f(s.d_urec); f(s.d_nu); f(s.d_live); f(s.d_best_key); f(s.d_items); f(s.d_tile_ub); f(s.d_prune_thr);
+            f(s.d_prune_i1); f(s.d_best); f(s.d_heavy); f(s.d_heavy_items); f(s.d_fine_items); f(s.d_rec_nslots); f(s.d_rec_slots); f(s.d_rec_cnt); f(s.d_rec);
+            f(s.d_cnt_row); f(s.d_cnt_cursor);
+        }
+        void release_all() { each(*this, [](auto &b) { b.release(); }); }
+        // HBM of the set as rtx_index_workspace_bytes reports it.  d_cnt_row and d_cnt_cursor are left out: the reported figure never held them
+        // (hbm_bytes of the bench line is compared to the byte); counting them changes that figure and is a change of its own.
+        uint64_t bytes() const {
+            uint64_t b = 0;
+            each(*this, [&](const auto &buf) { b += buf.bytes(); });
+            return b - d_cnt_row.bytes() - d_cnt_cursor.bytes();
         }
     } sc[4];  // 0 .. 2: the sets that alternate (RTX_OPT_OVERLAP, rtx_shard_*); 3: the set of the side classes (a few long reads among barcodes)
     bool staged = false;  // driven with rtx_shard_*: sub-batch sb works in scratch set sb & 1, so that the exchange of one
@@ -470,11 +482,9 @@ struct SubBatch {
 SubBatch sub_batch_of(rtx_index *ix, uint32_t sb, bool timed);
 uint8_t *counts_lo(rtx_index *ix, rtx_index::Scratch &sc);
 uint16_t *counts_hi(rtx_index *ix, rtx_index::Scratch &sc);
-size_t counts_elems(const rtx_index *ix, uint64_t B);
 uint32_t counts_rows_layout(const rtx_index *ix);  // rows the counts buffer is laid out for right now (the diet's, or one per query of the sub-batch)
 uint32_t diet_rows(const rtx_index *ix, uint32_t B);
 int ensure_full_counts(rtx_index *ix, rtx_index::Scratch &sc);  // a row per query of the current class's sub-batch (the recounting taps)
-int grow_diet(rtx_index *ix);  // after a run whose rows ran out
 hipEvent_t stage_event(rtx_index *ix, const SubBatch &b, int stage, int which);
 int enqueue_kmer(rtx_index *ix, const SubBatch &b, hipStream_t s);
 int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s, int part = 0, hipStream_t s_mid = nullptr);
@@ -502,5 +512,112 @@ int alloc_final(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries);  //
 int enqueue_finalise(rtx_index *ix, const SubBatch &b, hipStream_t s);  // (rtx_api_batch.hip) behind the walks of a sub-batch
 // ---- rtx_text.hip
 int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of the batch being downloaded (synchronous)
+
+// ---- The scratch sets described once: the layouts of the buffers that hold several arrays, the elements a set wants of every buffer
+// (ScratchNeed) and the estimate that sizes a sub-batch against free HBM (class_per_q).  Whoever allocates, checks or reads a scratch
+// buffer takes its numbers from here.  SIZES are computed from the sub-batch size B a set is allocated for, OFFSETS from the queries nq
+// of the sub-batch being enqueued: the kernels index by nq.
+
+// A list of (pair, tile) items as the kernels that fill it and walk it lay it out: [pairs x tiles] items | [1] their number | [8] queue per XCD
+struct ItemList {
+    size_t np, ntiles;  // pairs of queries; tiles per pair
+    ItemList(size_t nq, size_t tiles) : np((nq + 1u) / 2u), ntiles(tiles) {}
+    size_t cap() const { return np * ntiles; }
+    size_t end() const { return cap() + 9u; }
+    uint32_t *items(uint32_t *p) const { return p; }
+    uint32_t *count(uint32_t *p) const { return p + cap(); }
+};
+struct ItemsLayout : ItemList {  // d_items (tiles of the database): the list | [pairs] live tiles per pair | [pairs] offsets (launch_live_items)
+    using ItemList::ItemList;
+    size_t total() const { return end() + 2u * np; }
+    uint32_t *pair_live(uint32_t *p) const { return p + end(); }
+    uint32_t *offsets(uint32_t *p) const { return p + end() + np; }
+};
+struct FineItemsLayout : ItemList {  // d_fine_items (tiles of the fine union bitmap): the list | [tiles] cursors (launch_fine_bounds)
+    using ItemList::ItemList;
+    size_t total() const { return end() + ntiles; }
+    uint32_t *cursors(uint32_t *p) const { return p + end(); }
+};
+struct HeavyItemsLayout : ItemList {  // d_heavy_items (tiles of the union bitmap): the list alone (launch_bounds2)
+    using ItemList::ItemList;
+    size_t total() const { return end(); }
+};
+struct LiveLayout {  // d_live: [B + 1] masks of live tiles, (tiles + 31) / 32 + 1 words each
+    uint32_t ntiles;
+    uint32_t words() const { return (ntiles + 31u) / 32u + 1u; }
+    size_t total(size_t B) const { return (B + 1u) * words(); }
+};
+
+// u16 elements of d_counts for `rows` rows: 10 bits per reference where the class packs its counts, a u16 otherwise
+inline size_t counts_elems(const rtx_index *ix, int planes, size_t rows) { return ix->packs(planes) ? rows * ix->npad * 5 / 8 : rows * ix->npad; }
+
+// Elements wanted of every buffer of a scratch set (named as the member of rtx_index::Scratch without its d_).  The numbers alone: which
+// groups a handle allocates at all, and which of them it can do without, is alloc_scratch_set's business.
+struct ScratchNeed {
+    size_t kmers = 0, rows = 0, dmask = 0, counts = 0, hist = 0 /* d_hist and d_table_z */, prefix = 0, urec = 0;  // by the shape of a class (add_class)
+    size_t prob_scratch = 0;                                                                                        // ... (rtx_index::d_prob_scratch, shared by the sets)
+    size_t nsparse = 0, srows = 0, t = 0, nrows = 0, order = 0, tilemax = 0, nu = 0;                                // by the number of queries (set_queries)
+    size_t tile_ub = 0, best_key = 0, prune_thr = 0, prune_i1 = 0, best = 0, live = 0, items = 0;                   // ... tile pruning
+    size_t heavy = 0, heavy_items = 0, fine_items = 0;                                                              // ... two-level bounds, fine bounds
+    size_t rec_nslots = 0, rec_slots = 0, rec_cnt = 0, rec = 0, cnt_row = 0, cnt_cursor = 0;                        // ... the records path and the diet
+    ScratchNeed &set_queries(const rtx_index *ix, size_t B) {  // a sub-batch of B queries, whatever their class
+        const size_t nt = ix->ntiles;
+        t = nrows = order = best_key = prune_thr = prune_i1 = rec_nslots = cnt_row = B;
+        nsparse = tilemax = tile_ub = B * nt;
+        srows = B * nt * (kSegMaxSparseRows + 1);
+        nu = (B + 1u) / 2u;
+        best = B * kPruneBestWords;
+        live = LiveLayout{ix->ntiles}.total(B);
+        items = ItemsLayout(B, nt).total();
+        heavy = B + 1u;
+        heavy_items = HeavyItemsLayout(B, ix->u_ntiles).total();
+        fine_items = FineItemsLayout(B, ix->f_ntiles).total();
+        rec_slots = rec_cnt = B * kRecMaxSlots;
+        rec = B * ix->rec_slots() * ix->rec_seg_len;
+        cnt_cursor = 4;
+        return *this;
+    }
+    // ... of class kc, with cnt_rows rows of counts and of boundary prefix sums (the diet's, or B); raises what an earlier class left
+    void add_class(const rtx_index *ix, const rtx_index::BatchClass &kc, size_t B, size_t cnt_rows) {
+        auto up = [](size_t &a, size_t v) { a = std::max(a, v); };
+        up(kmers, B * kc.kstride);
+        up(rows, B * kc.rstride);
+        up(dmask, B * ix->ntiles * (kc.rstride / 64));
+        up(counts, counts_elems(ix, kc.planes, cnt_rows));
+        up(prefix, cnt_rows * ix->n_bnd_local);
+        up(hist, B * kc.hstride);
+        up(urec, ((B + 1u) / 2u) * 2u * kc.rstride);
+        if (kc.huge) up(prob_scratch, B * ((prob_table_lds_bytes(kc.tmax) + 7) / 8));
+    }
+};
+
+// What scratch set k wants: every buffer sized for the class that needs most of it (set 3 serves the side classes, the others the bulk).
+inline ScratchNeed scratch_set_need(const rtx_index *ix, uint32_t k) {
+    ScratchNeed n;
+    size_t b_max = 1;
+    for (uint32_t c = 0; c < ix->n_cls; c++) {
+        const rtx_index::BatchClass &kc = ix->cls[c];
+        if (kc.side != (k == kSideSet)) continue;
+        const size_t B = kc.sub_batch;
+        b_max = std::max(b_max, B);
+        // (a class that will prune with the records path starts with a fraction of the rows: begin_run enlarges the buffer if the run turns out otherwise)
+        const bool diet = kc.will_prune && ix->rec_opt != 0u && ix->n_refs == ix->n_total && ix->n_bnd_local == ix->n_bnd;
+        n.add_class(ix, kc, B, diet ? diet_rows(ix, (uint32_t)B) : B);
+    }
+    return n.set_queries(ix, b_max);
+}
+
+// Scratch bytes a sub-batch of class k costs per query: what size_workspace divides free HBM by.  An ESTIMATE, not the sum of ScratchNeed:
+// the sub-batch size, and through it every result of the bench, follows from its value.
+inline uint64_t class_per_q(const rtx_index *ix, const rtx_index::BatchClass &k) {
+    return (uint64_t)k.kstride * 2 + (uint64_t)k.rstride * 12 + 4 + (uint64_t)ix->ntiles * (k.rstride / 8 + ((kSegMaxSparseRows + 1) * 4 + 10)) + (ix->packs(k.planes) ? ix->npad * 5 / 4 : ix->npad * 2) +
+           (uint64_t)k.hstride * 12 + (uint64_t)ix->n_bnd_local * 8 + 64 + (k.huge ? prob_table_lds_bytes(k.tmax) : 0) +
+           // + the scratch of the tile pruning: tile bounds, thresholds, live masks, best blocks, the lists of live blocks
+           (k.will_prune ? (uint64_t)ix->ntiles * 2 + 12 + (ix->ntiles + 31u) / 32u * 2u + 2u + kPruneBestWords * 4 +
+                               ((uint64_t)ix->ntiles + 2u) * 2u  /* the list of live (pair, tile) blocks: 4 bytes per pair and tile */ +
+                               (ix->d_fbitmap.p ? (uint64_t)ix->f_ntiles * 2u + 1u : 0u) /* the items of the fine bounds pass */ +
+                               (ix->rec_opt && ix->n_refs == ix->n_total ? (uint64_t)std::min<uint32_t>(ix->rec_opt, kRecMaxSlots) * 32768u + kRecMaxSlots * 6u + 2u : 0u) /* record segments */
+                           : 0);
+}
 
 }  // namespace rtxi
