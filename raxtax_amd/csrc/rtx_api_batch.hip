@@ -25,15 +25,12 @@ int ensure_events(rtx_index *ix, size_t count) {
 
 
 SubBatch sub_batch_of(rtx_index *ix, uint32_t sb, bool timed) {
+    const rtx_index::SubPlan &p = ix->plan[sb];  // the plan of the run (plan_sub_batches): classes of different sub-batch sizes follow one another
     SubBatch b;
     b.sb = sb;
-    if (sb < ix->sub_q0.size()) {  // the plan of the run (plan_sub_batches): classes of different sub-batch sizes follow one another
-        b.q0 = ix->sub_q0[sb];
-        b.nq = ix->sub_nq[sb];
-    } else {
-        b.q0 = (uint64_t)sb * ix->sub_batch;
-        b.nq = (uint32_t)std::min<uint64_t>(ix->sub_batch, ix->n_q - b.q0);
-    }
+    b.q0 = p.q0;
+    b.nq = p.nq;
+    b.cls = &ix->cls[p.cls];
     b.set = ix->staged ? (sb & 1u) : 0u;
     b.s = ix->stream;
     b.timed = timed;
@@ -41,29 +38,9 @@ SubBatch sub_batch_of(rtx_index *ix, uint32_t sb, bool timed) {
     return b;
 }
 
-// The class whose sub-batches are enqueued next: its shape becomes the handle's (the kernel parameters are filled from these fields).
-void apply_class(rtx_index *ix, uint32_t c) {
-    const rtx_index::BatchClass &k = ix->cls[c];
-    ix->diet_used = k.diet;
-    ix->cnt_rows_cur = k.diet ? k.cnt_rows : k.sub_batch;
-    ix->tmax = k.tmax;
-    ix->kstride = k.kstride;
-    ix->rstride = k.rstride;
-    ix->hstride = k.hstride;
-    ix->planes = k.planes;
-    ix->sub_batch = k.sub_batch;
-    ix->use_tables = k.use_tables;
-    ix->pair_used = k.pair;
-    ix->prune_used = k.prune;
-    ix->rec_used = k.rec;
-    ix->cur_cls = (int)c;
-}
-
 // The sub-batches of the run, class after class (positions of the processing order: the class leads the sort key, order_batch).
 int plan_sub_batches(rtx_index *ix) {
-    ix->sub_q0.clear();
-    ix->sub_nq.clear();
-    ix->sub_cls.clear();
+    ix->plan.clear();
     uint64_t pos = 0;
     for (uint32_t c = 0; c < ix->n_cls; c++) {  // positions: the classes in the order of their sort rank
         ix->cls[c].pos0 = pos;
@@ -76,15 +53,10 @@ int plan_sub_batches(rtx_index *ix) {
         for (uint32_t c = 0; c < ix->n_cls; c++) {
             rtx_index::BatchClass &k = ix->cls[c];
             if (k.side != (pass == 0)) continue;
-            k.sb0 = (uint32_t)ix->sub_q0.size();
-            for (uint64_t a = 0; a < k.n; a += k.sub_batch) {
-                ix->sub_q0.push_back(k.pos0 + a);
-                ix->sub_nq.push_back((uint32_t)std::min<uint64_t>(k.sub_batch, k.n - a));
-                ix->sub_cls.push_back((uint8_t)c);
-            }
-            k.n_sub = (uint32_t)ix->sub_q0.size() - k.sb0;
+            k.sb0 = ix->n_sub_total();
+            for (uint64_t a = 0; a < k.n; a += k.sub_batch) ix->plan.push_back({k.pos0 + a, (uint32_t)std::min<uint64_t>(k.sub_batch, k.n - a), c});
+            k.n_sub = ix->n_sub_total() - k.sb0;
         }
-    ix->n_sub_total = (uint32_t)ix->sub_q0.size();
     return RTX_OK;
 }
 
@@ -96,12 +68,12 @@ int plan_sub_batches(rtx_index *ix) {
 // counts that 99 % of the queries never wrote.  The recounting taps (rtx_api_debug.hip) count a sub-batch in full: a row per query again.
 constexpr uint32_t kDietMinRows = 1024;
 uint32_t diet_rows(const rtx_index *ix, uint32_t B) { return std::min<uint32_t>(B, std::max<uint32_t>(kDietMinRows, B >> ix->diet_shift)); }
-uint32_t counts_rows_layout(const rtx_index *ix) { return ix->diet_used && !ix->dbg_full_run && !ix->dbg_full ? ix->cnt_rows_cur : ix->sub_batch; }
+uint32_t counts_rows_layout(const rtx_index *ix, const rtx_index::BatchClass &k) { return k.diet && !ix->dbg_full_run && !ix->dbg_full ? k.cnt_rows : k.sub_batch; }
 uint8_t *counts_lo(rtx_index *ix, rtx_index::Scratch &sc) { return reinterpret_cast<uint8_t *>(sc.d_counts.p); }
-uint16_t *counts_hi(rtx_index *ix, rtx_index::Scratch &sc) {
-    return reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(sc.d_counts.p) + (size_t)counts_rows_layout(ix) * ix->npad);
+uint16_t *counts_hi(rtx_index *ix, const rtx_index::BatchClass &k, rtx_index::Scratch &sc) {
+    return reinterpret_cast<uint16_t *>(reinterpret_cast<uint8_t *>(sc.d_counts.p) + (size_t)counts_rows_layout(ix, k) * ix->npad);
 }
-int ensure_full_counts(rtx_index *ix, rtx_index::Scratch &sc) { return sc.d_counts.alloc(counts_elems(ix, ix->planes, ix->sub_batch)); }
+int ensure_full_counts(rtx_index *ix, const rtx_index::BatchClass &k, rtx_index::Scratch &sc) { return sc.d_counts.alloc(counts_elems(ix, k.planes, k.sub_batch)); }
 
 hipEvent_t stage_event(rtx_index *ix, const SubBatch &b, int stage, int which) {
     return ix->events[((size_t)b.sb * RTX_NUM_STAGES + stage) * 2 + which];
@@ -111,6 +83,7 @@ hipEvent_t stage_event(rtx_index *ix, const SubBatch &b, int stage, int which) {
 static KmerParams kmer_params(rtx_index *ix, const SubBatch &b) {
     rtx_index::Scratch &sc = ix->sc[b.set];
     rtx_index::ResultSet &r = ix->res();
+    const rtx_index::BatchClass &k = *b.cls;
     KmerParams kp{};
     kp.bases = ix->d_bases.p;
     kp.base_off = ix->in[ix->cur_in].d_base_off.p;
@@ -121,7 +94,7 @@ static KmerParams kmer_params(rtx_index *ix, const SubBatch &b) {
     kp.row_len = ix->d_row_len.p;
     kp.zero_row = ix->n_rows;
     kp.kmers = sc.d_kmers.p;
-    kp.kstride = ix->kstride;
+    kp.kstride = k.kstride;
     kp.seginfo = ix->d_seginfo.p;
     kp.seg_stride = ix->seg_stride;
     kp.segcls = ix->d_segcls.p;
@@ -132,7 +105,7 @@ static KmerParams kmer_params(rtx_index *ix, const SubBatch &b) {
     kp.seg_sbase = ix->d_seg_sbase.p;
     kp.seg_blocks = ix->seg_blocks;
     kp.rows = sc.d_rows.p;
-    kp.rstride = ix->rstride;
+    kp.rstride = k.rstride;
     kp.dmask = sc.d_dmask.p;
     kp.srows = sc.d_srows.p;
     kp.nsparse = sc.d_nsparse.p;
@@ -142,18 +115,18 @@ static KmerParams kmer_params(rtx_index *ix, const SubBatch &b) {
     kp.t_all = r.d_t_all.p;
     kp.nrows_all = r.d_nrows_all.p;
     kp.hist = sc.d_hist.p;  // zeroed by kmer_extract for hit_count's global atomics
-    kp.hstride = ix->hstride;
+    kp.hstride = k.hstride;
     return kp;
 }
 
-// What a sub-batch being enqueued goes through, decided once.  The run prunes (the recount of the debug taps leaves the pruning out):
-static bool run_prunes(const rtx_index *ix) { return ix->prune_used && !ix->dbg_full_run; }
+// What a sub-batch of class k being enqueued goes through, decided once.  It prunes (the recount of the debug taps leaves the pruning out):
+static bool run_prunes(const rtx_index *ix, const rtx_index::BatchClass &k) { return k.prune && !ix->dbg_full_run; }
 // ... its queries may take the records path (whole-database handles whose walk rides in the prefix launch: enqueue_prob_prefix starts
-// records_tail_kernel there).  rec_used implies a whole-database handle driven by enqueue_batch, which enqueues part 0 and fuses the walk;
+// records_tail_kernel there).  BatchClass::rec implies a whole-database handle driven by enqueue_batch, which enqueues part 0 and fuses the walk;
 // the two callers still ask for that themselves, so that an rtx_shard_* call on such a handle stays off the path.
-static bool on_records_path(const rtx_index *ix, const rtx_index::Scratch &sc) { return run_prunes(ix) && ix->rec_used && sc.d_rec.p != nullptr; }
+static bool on_records_path(const rtx_index *ix, const rtx_index::BatchClass &k, const rtx_index::Scratch &sc) { return run_prunes(ix, k) && k.rec && sc.d_rec.p != nullptr; }
 // ... and the rows of its counts buffer are handed out with the decision about the records path (the diet)
-static bool on_diet(const rtx_index *ix, const rtx_index::Scratch &sc) { return on_records_path(ix, sc) && ix->diet_used && sc.d_cnt_row.p != nullptr; }
+static bool on_diet(const rtx_index *ix, const rtx_index::BatchClass &k, const rtx_index::Scratch &sc) { return on_records_path(ix, k, sc) && k.diet && sc.d_cnt_row.p != nullptr; }
 
 static RecordRef record_ref(const rtx_index *ix, const rtx_index::Scratch &sc, const rtx_index::ResultSet &r) { return RecordRef{sc.d_rec_nslots.p, sc.d_rec_slots.p, sc.d_rec_cnt.p, sc.d_rec.p, ix->rec_slots(), ix->rec_seg_len, r.d_flags.p}; }
 static ProbTables prob_tables(const rtx_index *ix) { return ProbTables{ix->d_tab_cmf.p, ix->d_tab_ratio.p, ix->d_tab_off.p, ix->d_tab_moff.p, ix->d_tab_ilo.p, ix->d_tab_sat.p, ix->tab_tmax}; }
@@ -162,7 +135,7 @@ int enqueue_kmer(rtx_index *ix, const SubBatch &b, hipStream_t s) {
     KmerParams kp = kmer_params(ix, b);
     // with tile pruning the per-tile lists wait until the live tiles are known (enqueue_hit); databases of few tiles build
     // their lists in one pass per tile whatever is live
-    kp.mode = run_prunes(ix) && ix->seg_blocks ? 1u : 0u;
+    kp.mode = run_prunes(ix, *b.cls) && ix->seg_blocks ? 1u : 0u;
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_KMER_EXTRACT, 0), s));
     launch_kmer_extract(s, kp, b.nq);
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_KMER_EXTRACT, 1), s));
@@ -173,6 +146,7 @@ int enqueue_kmer(rtx_index *ix, const SubBatch &b, hipStream_t s) {
 static HitParams hit_params(rtx_index *ix, const SubBatch &b, uint32_t flags) {
     rtx_index::Scratch &sc = ix->sc[b.set];
     rtx_index::ResultSet &r = ix->res();
+    const rtx_index::BatchClass &k = *b.cls;
     HitParams hp{};
     hp.bitmap = ix->d_bitmap.p;
     hp.stride_bytes = ix->stride_bytes;
@@ -180,7 +154,7 @@ static HitParams hit_params(rtx_index *ix, const SubBatch &b, uint32_t flags) {
     hp.n_refs = ix->n_refs;
     hp.ref_base = ix->ref_lo;
     hp.rows = sc.d_rows.p;
-    hp.rstride = ix->rstride;
+    hp.rstride = k.rstride;
     hp.dmask = sc.d_dmask.p;
     hp.nrows = sc.d_nrows.p;
     hp.zero_row = ix->n_rows;
@@ -190,22 +164,22 @@ static HitParams hit_params(rtx_index *ix, const SubBatch &b, uint32_t flags) {
     hp.ntiles = ix->ntiles;
     hp.t = sc.d_t.p;
     hp.counts = sc.d_counts.p;
-    hp.counts_lo = ix->packed() ? counts_lo(ix, sc) : nullptr;  // null: u16 counts
-    hp.counts_hi = ix->packed() ? counts_hi(ix, sc) : nullptr;
+    hp.counts_lo = ix->packs(k.planes) ? counts_lo(ix, sc) : nullptr;  // null: u16 counts
+    hp.counts_hi = ix->packs(k.planes) ? counts_hi(ix, k, sc) : nullptr;
     hp.npad = ix->npad;
     hp.hist = sc.d_hist.p;
-    hp.hstride = ix->hstride;
+    hp.hstride = k.hstride;
     hp.tile_max = sc.d_tilemax.p;
     hp.flags = flags;
     hp.q0 = b.q0;
     hp.perm = r.d_perm.p;
     hp.exact = ExactRef{ix->in[ix->cur_in].d_exact_ids.p, ix->in[ix->cur_in].d_exact_off.p, r.dev_exact ? r.d_exact_grp.p : nullptr, ix->d_em_goff.p, ix->d_em_gids.p};
     hp.nq = b.nq;
-    hp.group_rows = ix->pair_used ? ix->d_group_rows.p : nullptr;
+    hp.group_rows = k.pair ? ix->d_group_rows.p : nullptr;
     hp.group_base = b.sb * ix->groups_per_sub;
     hp.pair_urec = sc.d_urec.p;
     hp.pair_nu = sc.d_nu.p;
-    hp.pair_ustride = 2u * ix->rstride;
+    hp.pair_ustride = 2u * k.rstride;
     return hp;
 }
 
@@ -243,7 +217,7 @@ static Bounds2Params bounds2_params(const rtx_index *ix, const rtx_index::Scratc
     bp.zero_row = ix->n_rows;
     bp.pair_urec = sc.d_urec.p;
     bp.pair_nu = sc.d_nu.p;
-    bp.pair_ustride = 2u * ix->rstride;
+    bp.pair_ustride = up.pair_ustride;
     bp.nq = up.nq;
     bp.t = sc.d_t.p;
     bp.tile_ub = sc.d_tile_ub.p;
@@ -264,6 +238,7 @@ static Bounds2Params bounds2_params(const rtx_index *ix, const rtx_index::Scratc
 // (2) bounds per tile, a lower bound of the best hit, the threshold, the live tiles of every pair
 static PruneParams prune_params(rtx_index *ix, const SubBatch &b, uint32_t flags, int part, const ExactRef &exact) {
     rtx_index::Scratch &sc = ix->sc[b.set];
+    const rtx_index::BatchClass &k = *b.cls;
     PruneParams pr{};
     pr.tile_ub = sc.d_tile_ub.p;
     pr.best_key = sc.d_best_key.p;
@@ -276,11 +251,11 @@ static PruneParams prune_params(rtx_index *ix, const SubBatch &b, uint32_t flags
     pr.phase = (uint32_t)part;
     pr.best = part ? sc.d_best.p : nullptr;
     pr.bitmap = ix->d_bitmap.p;
-    pr.cbitmap = part == 0 && (ix->two_level_used || (ix->planes > kBounds2MaxPlanes && ix->two_level_opt && ix->n_refs == ix->n_total)) ? reinterpret_cast<const uint2 *>(ix->d_cbitmap.p) : nullptr;  // (with the two-level pass: RTX_OPT_TWO_LEVEL_BOUNDS = 0 is the round-4 path whole)
+    pr.cbitmap = part == 0 && (ix->two_level_used || (k.planes > kBounds2MaxPlanes && ix->two_level_opt && ix->n_refs == ix->n_total)) ? reinterpret_cast<const uint2 *>(ix->d_cbitmap.p) : nullptr;  // (with the two-level pass: RTX_OPT_TWO_LEVEL_BOUNDS = 0 is the round-4 path whole)
     pr.n_rows1 = ix->n_rows + 1;
     pr.stride_bytes = ix->stride_bytes;
     pr.rows = sc.d_rows.p;
-    pr.rstride = ix->rstride;
+    pr.rstride = k.rstride;
     pr.nrows = sc.d_nrows.p;
     pr.t = sc.d_t.p;
     pr.flags = flags;
@@ -289,9 +264,9 @@ static PruneParams prune_params(rtx_index *ix, const SubBatch &b, uint32_t flags
     pr.exact = exact;
     pr.lnfact = ix->d_lnfact.p;
     pr.inv = ix->d_inv.p;
-    pr.nlf = std::min<uint32_t>(kLnFactLen, ix->tmax + ix->tmax / 2 + 2);  // (pruning runs with tmax <= 2047: 12 KB at t <= 1023, 25 KB at most)
+    pr.nlf = std::min<uint32_t>(kLnFactLen, k.tmax + k.tmax / 2 + 2);  // (pruning runs with tmax <= 2047: 12 KB at t <= 1023, 25 KB at most)
     pr.hist = sc.d_hist.p;
-    pr.hstride = ix->hstride;
+    pr.hstride = k.hstride;
     pr.live = sc.d_live.p;
     pr.live_words = LiveLayout{ix->ntiles}.words();
     pr.pair_live = ItemsLayout(b.nq, ix->ntiles).pair_live(sc.d_items.p);
@@ -329,12 +304,13 @@ static HitParams fine_params(const rtx_index *ix, const rtx_index::Scratch &sc, 
 int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s, int part, hipStream_t s_mid) {
     rtx_index::Scratch &sc = ix->sc[b.set];
     rtx_index::ResultSet &r = ix->res();
+    const rtx_index::BatchClass &k = *b.cls;
     ix->last_set = b.set;
     HitParams hp = hit_params(ix, b, flags);
-    const bool prune = run_prunes(ix);
-    if (ix->pair_used && part != 2) {
+    const bool prune = run_prunes(ix, k);
+    if (k.pair && part != 2) {
         if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_PAIR_UNION, 0), s));
-        launch_pair_union(s, sc.d_rows.p, sc.d_nrows.p, ix->rstride, b.nq, sc.d_urec.p, sc.d_nu.p, 2u * ix->rstride);
+        launch_pair_union(s, sc.d_rows.p, sc.d_nrows.p, k.rstride, b.nq, sc.d_urec.p, sc.d_nu.p, 2u * k.rstride);
         if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_PAIR_UNION, 1), s));
     }
     if (b.timed && !prune) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_HIT_COUNT, 0), s));
@@ -344,13 +320,13 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
             const HitParams up = bounds_params(ix, sc, hp);
             if (b.timed) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_TILE_BOUNDS, 0), s));
             // whole-database handles: the two-level pass (rtx_bounds2.hip); reference shards and RTX_OPT_TWO_LEVEL_BOUNDS = 0: blocks of 64 throughout
-            ix->two_level_used = part == 0 && ix->two_level_opt && ix->d_abitmap.p && ix->d_bbitmap.p && ix->n_refs == ix->n_total && ix->planes <= kBounds2MaxPlanes;
+            ix->two_level_used = part == 0 && ix->two_level_opt && ix->d_abitmap.p && ix->d_bbitmap.p && ix->n_refs == ix->n_total && k.planes <= kBounds2MaxPlanes;
             if (ix->two_level_used) {
                 const bool heavy_ok = sc.d_heavy.p && sc.d_heavy_items.p && sc.d_heavy_items.n >= HeavyItemsLayout(b.nq, ix->u_ntiles).total();
-                launch_bounds2(s, bounds2_params(ix, sc, up, heavy_ok), b.nq, ix->planes, up, ix->u_ntiles, heavy_ok ? sc.d_heavy_items.p : nullptr);
+                launch_bounds2(s, bounds2_params(ix, sc, up, heavy_ok), b.nq, k.planes, up, ix->u_ntiles, heavy_ok ? sc.d_heavy_items.p : nullptr);
             } else {
                 RTX_HIP(hipMemsetAsync(sc.d_best_key.p, 0, (size_t)b.nq * 4, s));  // the waves of a query's union tiles meet in an atomicMax
-                launch_hit_count_pair_bounds(s, up, b.nq, ix->u_ntiles, ix->planes);  // the union of the pair's rows serves both passes
+                launch_hit_count_pair_bounds(s, up, b.nq, ix->u_ntiles, k.planes);  // the union of the pair's rows serves both passes
             }
             if (b.timed) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_TILE_BOUNDS, 1), s));
         }
@@ -362,15 +338,15 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         if (b.timed && part != 1) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_TILE_PRUNE, 0), s));
         // (2) threshold
         PruneParams pr = prune_params(ix, b, flags, part, hp.exact);
-        const bool records = part == 0 && on_records_path(ix, sc), diet = part == 0 && on_diet(ix, sc);
+        const bool records = part == 0 && on_records_path(ix, k, sc), diet = part == 0 && on_diet(ix, k, sc);
         const RecordRef rr = record_ref(ix, sc, r);
         if (records) { pr.rec = rr; pr.rec_max_slots = rr.stride; }
-        if (ix->diet_used && !diet) { set_error("internal: the counts buffer is on its diet without the records path"); return RTX_ERR_STATE; }
+        if (k.diet && !diet) { set_error("internal: the counts buffer is on its diet without the records path"); return RTX_ERR_STATE; }
         if (diet) {
             RTX_HIP(hipMemsetAsync(sc.d_cnt_cursor.p, 0, 4, s));
             pr.cnt_row = sc.d_cnt_row.p;
             pr.cnt_cursor = sc.d_cnt_cursor.p;
-            pr.cnt_cap = ix->cnt_rows_cur;
+            pr.cnt_cap = k.cnt_rows;
             pr.flags_out = r.d_flags.p;
             hp.cnt_row = sc.d_cnt_row.p;
         }
@@ -379,10 +355,10 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         // (2b) second stage of the bounds (whole-database handles with a fine union bitmap): the pairs that are left many live tiles are
         // counted against the union bitmap over blocks of 8 references, which takes the tiles without a block above the threshold off
         // their lists (fine_epilogue); prune_kernel's number of live tiles per pair is brought up to date for the list below
-        if (part == 0 && ix->fine_opt && ix->d_fbitmap.p && ix->pair_used && sc.d_fine_items.p) {
+        if (part == 0 && ix->fine_opt && ix->d_fbitmap.p && k.pair && sc.d_fine_items.p) {
             const FineItemsLayout fine(b.nq, ix->f_ntiles);
             uint32_t *const fi = sc.d_fine_items.p;
-            launch_fine_bounds(s, fine_params(ix, sc, hp), b.nq, ix->ntiles, ix->f_ntiles, pr.pair_live, fine.cursors(fi), fine.items(fi), fine.count(fi), ix->planes);
+            launch_fine_bounds(s, fine_params(ix, sc, hp), b.nq, ix->ntiles, ix->f_ntiles, pr.pair_live, fine.cursors(fi), fine.items(fi), fine.count(fi), k.planes);
         }
         // (3) tiles that are not counted keep a largest count of 0: taxon_prefix leaves them out
         RTX_HIP(hipMemsetAsync(sc.d_tilemax.p, 0, (size_t)b.nq * ix->ntiles * 2, s));
@@ -390,7 +366,7 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         hp.live_words = pr.live_words;
         hp.prune_thr = sc.d_prune_thr.p;
         if (records) hp.rec = rr;
-        if (ix->pair_used) {  // the grid of the counting pass walks the live (pair, tile) blocks instead of all of them
+        if (k.pair) {  // the grid of the counting pass walks the live (pair, tile) blocks instead of all of them
             const ItemsLayout items(b.nq, ix->ntiles);
             launch_live_items(s, sc.d_live.p, pr.live_words, pr.pair_live, b.nq, ix->ntiles, items.offsets(sc.d_items.p), items.items(sc.d_items.p), items.count(sc.d_items.p));
             hp.items = items.items(sc.d_items.p);
@@ -408,8 +384,8 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
             RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_HIT_COUNT, 0), s));
         }
     }
-    if (ix->pair_used) launch_hit_count_pair(s, hp, b.nq, ix->ntiles, ix->planes);
-    else launch_hit_count(s, hp, b.nq, ix->ntiles, ix->planes);
+    if (k.pair) launch_hit_count_pair(s, hp, b.nq, ix->ntiles, k.planes);
+    else launch_hit_count(s, hp, b.nq, ix->ntiles, k.planes);
     if (b.timed) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_HIT_COUNT, 1), s));
     ix->hit_stream = s;
     return RTX_OK;
@@ -427,13 +403,14 @@ static int reset_sub_alloc(rtx_index *ix, hipStream_t s);
 // fuse_walk (whole database on this handle) the taxonomy walk of group 3 runs inside the prefix kernel
 int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool prob_only) {
     rtx_index::Scratch &sc = ix->sc[b.set];
+    const rtx_index::BatchClass &k = *b.cls;
     hipStream_t s = b.s;
     ProbParams pp{};
     pp.t = sc.d_t.p;
     pp.hist = sc.d_hist.p;
-    pp.hstride = ix->hstride;
-    pp.tmax = ix->tmax;
-    pp.n1max = ix->tmax / 2 + 1;
+    pp.hstride = k.hstride;
+    pp.tmax = k.tmax;
+    pp.n1max = k.tmax / 2 + 1;
     pp.lnfact = ix->d_lnfact.p;
     pp.n_refs = ix->n_total;
     pp.q0 = b.q0;
@@ -443,16 +420,16 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     pp.gs = r.d_gs.p;
     pp.status = r.d_status.p;
     pp.ndist = r.d_ndist.p;
-    pp.prune_thr = run_prunes(ix) ? sc.d_prune_thr.p : nullptr;
+    pp.prune_thr = run_prunes(ix, k) ? sc.d_prune_thr.p : nullptr;
     pp.prune_i1 = pp.prune_thr ? sc.d_prune_i1.p : nullptr;
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_PROB_TABLE, 0), s));
-    if (ix->use_tables) {
+    if (k.use_tables) {
         launch_prob_order(s, sc.d_t.p, b.nq, sc.d_order.p);
         pp.order = sc.d_order.p;
         launch_prob_lookup(s, pp, prob_tables(ix), b.nq);
     } else {
-        if (ix->cur_cls >= 0 && ix->cls[ix->cur_cls].huge) {  // its arrays do not fit LDS: a stretch of global memory per query
-            pp.gstride = (uint32_t)((prob_table_lds_bytes(ix->tmax) + 7) / 8);
+        if (k.huge) {  // its arrays do not fit LDS: a stretch of global memory per query
+            pp.gstride = (uint32_t)((prob_table_lds_bytes(k.tmax) + 7) / 8);
             if (ix->d_prob_scratch.n < (size_t)b.nq * pp.gstride) { set_error("internal: scratch of prob_table too small"); return RTX_ERR_STATE; }
             pp.gscratch = ix->d_prob_scratch.p;
         }
@@ -464,15 +441,15 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     PrefixParams fp{};
     fp.status = r.d_status.p;
     fp.t = sc.d_t.p;
-    fp.tz_in_lds = (size_t)ix->hstride * 8 <= 16 * 1024 ? 1u : 0u;
+    fp.tz_in_lds = (size_t)k.hstride * 8 <= 16 * 1024 ? 1u : 0u;
     fp.q0 = b.q0;
     fp.counts = sc.d_counts.p;
     fp.counts_lo = counts_lo(ix, sc);
-    fp.counts_hi = counts_hi(ix, sc);
-    fp.packed = ix->packed() ? 1u : 0u;
+    fp.counts_hi = counts_hi(ix, k, sc);
+    fp.packed = ix->packs(k.planes) ? 1u : 0u;
     fp.npad = ix->npad;
     fp.table_z = sc.d_table_z.p;
-    fp.hstride = ix->hstride;
+    fp.hstride = k.hstride;
     fp.n_refs = ix->n_refs;
     fp.bnd_bits = ix->d_bnd_bits.p;
     fp.bnd_rank = ix->d_bnd_rank.p;
@@ -483,9 +460,9 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     fp.prune_thr = pp.prune_thr;
     fp.prune_stats = fp.prune_thr ? ix->d_prune_stats.p + kPruneStatCopies * 8 : nullptr;
     fp.fuse_walk = fuse_walk ? 1u : 0u;
-    const bool records = fuse_walk && on_records_path(ix, sc);
+    const bool records = fuse_walk && on_records_path(ix, k, sc);
     fp.rec_nslots = records ? sc.d_rec_nslots.p : nullptr;
-    fp.cnt_row = fuse_walk && on_diet(ix, sc) ? sc.d_cnt_row.p : nullptr;
+    fp.cnt_row = fuse_walk && on_diet(ix, k, sc) ? sc.d_cnt_row.p : nullptr;
     if (fuse_walk) {
         fp.walk = walk_params(ix, b, sc.d_prefix.p);
         int rc_r = fp.walk.sub_alloc ? reset_sub_alloc(ix, s) : RTX_OK;
@@ -498,11 +475,11 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
         tp.rec = record_ref(ix, sc, r);
         tp.t = sc.d_t.p;
         tp.table_z = sc.d_table_z.p;
-        tp.hstride = ix->hstride;
+        tp.hstride = k.hstride;
         tp.bnd_bits = ix->d_bnd_bits.p;
         tp.bnd_rank = ix->d_bnd_rank.p;
         tp.prefix = sc.d_prefix.p;
-        if (fp.cnt_row) { tp.cnt_cursor = sc.d_cnt_cursor.p; tp.cnt_cap = ix->cnt_rows_cur; tp.flags_out = r.d_flags.p; }
+        if (fp.cnt_row) { tp.cnt_cursor = sc.d_cnt_cursor.p; tp.cnt_cap = k.cnt_rows; tp.flags_out = r.d_flags.p; }
         tp.n_bnd = ix->n_bnd_local;
         tp.nq = b.nq;
         tp.walk = fp.walk;
@@ -605,7 +582,7 @@ static WalkParams walk_params(rtx_index *ix, const SubBatch &b, const double *pr
     wp.n_bnd = ix->n_bnd;
     wp.rec = ix->d_noderec.p;
     wp.arena = r.d_arena.p;
-    const bool side = ix->cur_cls >= 0 && ix->cls[ix->cur_cls].side;  // its rows go to the top of the arena through a cursor of their own
+    const bool side = b.cls->side;  // its rows go to the top of the arena through a cursor of their own
     wp.arena_cap = side ? r.arena_cap : r.side_base;
     wp.arena_cursor = r.d_cursor.p + (side ? 1 : 0);
     // (launches of a few thousand walks do not contend, and the rows the sub-allocators leave unused must stay within the arena's
@@ -671,7 +648,7 @@ int order_batch(rtx_index *ix, bool cluster) {
 void record_batch(rtx_index *ix) {
     rtx_index::ResultSet &r = ix->res();
     r.n_q = ix->n_q;
-    r.n_sub = ix->n_sub_total;
+    r.n_sub = ix->n_sub_total();
     r.n_side = 0;
     for (uint32_t c = 0; c < ix->n_cls; c++)
         if (ix->cls[c].side) r.n_side += ix->cls[c].n_sub;  // (plan_sub_batches: their sub-batches come first)
@@ -683,7 +660,7 @@ void record_batch(rtx_index *ix) {
 int begin_run(rtx_index *ix, uint32_t *n_sub_out, bool *timed_out, bool cluster) {
     int rc_p = plan_sub_batches(ix);
     if (rc_p) return rc_p;
-    const uint32_t n_sub = ix->n_sub_total;
+    const uint32_t n_sub = ix->n_sub_total();
     record_batch(ix);
     rtx_index::ResultSet &r = ix->res();
     const bool timed = n_sub <= 4096;
@@ -794,7 +771,6 @@ int begin_run(rtx_index *ix, uint32_t *n_sub_out, bool *timed_out, bool cluster)
         ix->overlap_used = 2;
         if (ix->overlap_opt >= 2u && n_sub >= 3 && ix->sc[2].d_kmers.p != nullptr && scratch_ok(ix->sc[2], b_max) == scratch_ok(ix->sc[0], b_max)) ix->overlap_used = 3;
     }
-    if (ix->n_cls) apply_class(ix, 0);
     if (r.dev_exact) {  // Tree.sequences.get for every query of the batch (raxtax.rs:42), part of the run
         ExactParams xp{ix->d_bases.p, ix->in[ix->cur_in].d_base_off.p, (uint32_t)ix->n_q, ix->d_em_table.p, ix->em_bits, ix->d_em_rep_off.p,
                        ix->d_em_rep_bytes.p, r.d_exact_grp.p, ix->em_hash_mask};
@@ -870,9 +846,8 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
         for (uint32_t k = 0; k < 2u; k++)
             if (!ix->ev_set_free[k]) RTX_HIP(hipEventCreateWithFlags(&ix->ev_set_free[k], hipEventDisableTiming));
     for (uint32_t sb = 0; sb < n_sub; sb++) {
-        if ((int)ix->sub_cls[sb] != ix->cur_cls) apply_class(ix, ix->sub_cls[sb]);  // the next length class: its planes, strides, kernels
-        SubBatch b = sub_batch_of(ix, sb, timed);
-        const bool side = ix->cls[ix->sub_cls[sb]].side;
+        SubBatch b = sub_batch_of(ix, sb, timed);  // (with its length class: planes, strides, kernels)
+        const bool side = b.cls->side;
         if (side) {  // (the side classes come first: sub-batches 0 .. n_side - 1, one after the other through their own set)
             b.set = kSideSet;
             if (overlap) {
@@ -1052,7 +1027,8 @@ static int size_workspace(rtx_index *ix, uint64_t n_queries);
 int prepare_workspace(rtx_index *ix, uint64_t n_queries, const uint64_t cls_n_in[5], const uint64_t cls_max_in[5]) {
     uint64_t cn[5], cm[5];
     for (int c = 0; c < 5; c++) { cn[c] = cls_n_in[c]; cm[c] = cls_max_in[c]; }
-    if (ix->n_refs != ix->n_total) {  // a reference / k-mer shard: the exchange buffers of rtx_shard_* have one row stride -- one class
+    if (ix->n_refs != ix->n_total) {  // a reference shard: the exchange buffers of rtx_shard_* have one row stride -- one class (a k-mer shard holds every reference and is not
+                                      // caught here: its staged run is launched in the shape of cls[0] whatever its classes, shard_sb)
         uint64_t mx = 0;
         for (int c = 0; c < 5; c++) mx = std::max(mx, cm[c]);
         return prepare_workspace_single(ix, n_queries, mx >= 8 ? mx - 7 : 1, mx);
@@ -1181,7 +1157,6 @@ static int size_workspace(rtx_index *ix, uint64_t n_queries) {
     while (n_sets > 1u && (uint64_t)n_sets * worst > budget) n_sets--;
     ix->staged = false;
     if ((rc = plan_sub_batches(ix))) return rc;
-    apply_class(ix, ix->n_cls - 1u);
     if ((rc = alloc_scratch_set(ix, 0))) return rc;
     {
         bool any_side = false;
@@ -1190,7 +1165,7 @@ static int size_workspace(rtx_index *ix, uint64_t n_queries) {
         else ix->sc[kSideSet].release_all();
     }
     for (uint32_t k = 1; k <= 2u; k++) {  // (without the further sets the run stays on one stream)
-        if (k < n_sets && ix->n_sub_total > 1) {
+        if (k < n_sets && ix->n_sub_total() > 1) {
             if (alloc_scratch_set(ix, k)) ix->sc[k].d_kmers.release();
         } else if (ix->n_refs == ix->n_total) {
             ix->sc[k].release_all();  // none wanted on a whole-database handle: given back (a shard keeps its second set for rtx_shard_begin)

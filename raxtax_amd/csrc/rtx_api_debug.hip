@@ -9,7 +9,7 @@ int rtx_batch_stage_times(rtx_index *ix, float ms[RTX_NUM_STAGES], uint32_t laun
     if (!ix->synced) { set_error("rtx_batch_stage_times: batch not synchronised"); return RTX_ERR_STATE; }
     for (int s = 0; s < RTX_NUM_STAGES; s++) { ms[s] = 0.f; launches[s] = 0; }
     for (uint32_t sb = 0; sb < ix->n_sub_last; sb++) {
-        const rtx_index::BatchClass &kc = ix->cls[sb < ix->sub_cls.size() ? ix->sub_cls[sb] : 0u];  // which events its class recorded
+        const rtx_index::BatchClass &kc = ix->cls[ix->plan[sb].cls];  // which events its class recorded
         for (int s = 0; s < RTX_NUM_STAGES; s++) {
             if (s == RTX_STAGE_EXACT_MATCH) {
                 if (sb != 0 || !ix->dev_exact_used || !ix->stage_timing) continue;  // one launch per run
@@ -42,7 +42,7 @@ int rtx_batch_work(rtx_index *ix, uint64_t *sum_hits, uint64_t *sum_query_bytes,
     for (uint64_t q = 0; q < ix->n_q; q++) h += ix->h_hq[q];
     // per sub-batch: a class on the pair kernel loaded its rows once per pair of queries (the union rows every wave counted: d_group_rows),
     // the others once per query (kmer_extract's number of dense segments)
-    const uint32_t n_sub = ix->n_sub_total;
+    const uint32_t n_sub = ix->n_sub_total();
     const size_t ng = (size_t)n_sub * ix->groups_per_sub;
     std::vector<uint32_t> gr;
     bool any_pair = false, any_prune = false;
@@ -54,14 +54,14 @@ int rtx_batch_work(rtx_index *ix, uint64_t *sum_hits, uint64_t *sum_query_bytes,
     // (the two-level pass counts load instructions: a KiB each, several short rows)
     const uint64_t urow_bytes = ix->two_level_used ? 1024u : (ix->u_ntiles ? ((ix->u_nblocks + 7) / 8 + ix->u_ntiles - 1) / ix->u_ntiles : 0);
     for (uint32_t sb = 0; sb < n_sub; sb++) {
-        const rtx_index::BatchClass &kc = ix->cls[ix->sub_cls[sb]];
+        const rtx_index::BatchClass &kc = ix->cls[ix->plan[sb].cls];
         if (kc.pair) {
             for (size_t g = (size_t)sb * ix->groups_per_sub; g < (size_t)(sb + 1) * ix->groups_per_sub; g++) {
                 b += (uint64_t)gr[g] * row_bytes;
                 if (kc.prune) b += (uint64_t)gr[ng + g] * urow_bytes;  // + the rows of the union bitmap the bounds pass loaded (the same kernel)
             }
         } else {
-            for (uint64_t pos = ix->sub_q0[sb]; pos < ix->sub_q0[sb] + ix->sub_nq[sb]; pos++) b += (uint64_t)ix->h_nrows_all[pos] * row_bytes;
+            for (uint64_t pos = ix->plan[sb].q0; pos < ix->plan[sb].q0 + ix->plan[sb].nq; pos++) b += (uint64_t)ix->h_nrows_all[pos] * row_bytes;
         }
     }
     (void)any_prune;
@@ -79,7 +79,7 @@ int rtx_batch_work_split(rtx_index *ix, uint64_t *live_bytes, uint64_t *bounds_b
     if (rc) return rc;
     uint64_t bounds = 0;
     {
-        const uint32_t n_sub = ix->n_sub_total;
+        const uint32_t n_sub = ix->n_sub_total();
         const size_t ng = (size_t)n_sub * ix->groups_per_sub;
         bool any = false;
         for (uint32_t c = 0; c < ix->n_cls; c++) any = any || (ix->cls[c].pair && ix->cls[c].prune);
@@ -88,7 +88,7 @@ int rtx_batch_work_split(rtx_index *ix, uint64_t *live_bytes, uint64_t *bounds_b
             RTX_HIP(hipMemcpy(gr.data(), ix->d_group_rows.p + ng, ng * 4, hipMemcpyDeviceToHost));
             const uint64_t urow_bytes = ix->two_level_used ? 1024u : ((ix->u_nblocks + 7) / 8 + ix->u_ntiles - 1) / ix->u_ntiles;
             for (uint32_t sb = 0; sb < n_sub; sb++)
-                if (ix->cls[ix->sub_cls[sb]].prune)
+                if (ix->cls[ix->plan[sb].cls].prune)
                     for (size_t g = (size_t)sb * ix->groups_per_sub; g < (size_t)(sb + 1) * ix->groups_per_sub; g++) bounds += (uint64_t)gr[g] * urow_bytes;
         }
     }
@@ -123,7 +123,7 @@ static int debug_slot_as_run(rtx_index *ix, uint64_t query, uint32_t *slot, uint
     int rc = bind(ix);
     if (rc) return rc;
     if (!ix->synced) { set_error("debug tap: batch not synchronised"); return RTX_ERR_STATE; }
-    const uint64_t last0 = ix->n_sub_total && ix->sub_q0.size() == ix->n_sub_total ? ix->sub_q0[ix->n_sub_total - 1] : 0;  // the last sub-batch of the run (of its last length class)
+    const uint64_t last0 = ix->plan.back().q0;  // the last sub-batch of the run (of its last length class)
     if (query >= ix->n_q) { set_error("debug tap: query %llu out of range", (unsigned long long)query); return RTX_ERR_INVALID; }
     uint32_t p = 0;
     RTX_HIP(hipMemcpy(&p, ix->res().d_iperm.p + query, 4, hipMemcpyDeviceToHost));  // (the batch is synchronised: the order is in place)
@@ -141,12 +141,12 @@ static int debug_slot(rtx_index *ix, uint64_t query, uint32_t *slot, uint32_t *p
 // uncounted references lumped into bin 0: the taps promise the full vectors, so the sub-batch is counted again in full
 // (k-mers, hit counts, histogram, probability table; the result rows of the run are not touched).
 static int debug_recount_full(rtx_index *ix) {
-    if (!ix->prune_used || ix->dbg_full) return RTX_OK;
-    const uint32_t n_sub = ix->n_sub_total;
-    SubBatch b = sub_batch_of(ix, n_sub - 1, false);
+    if (!ix->last_cls().prune || ix->dbg_full) return RTX_OK;
+    SubBatch b = sub_batch_of(ix, ix->n_sub_total() - 1, false);
     b.set = ix->last_set;
+    b.cls = &ix->last_cls();  // (a staged run: cls[0])
     RTX_HIP(hipStreamSynchronize(ix->stream));
-    int rc = ensure_full_counts(ix, ix->sc[b.set]);  // the recount writes the counts of EVERY query of the sub-batch (the run's buffer may be on its diet)
+    int rc = ensure_full_counts(ix, *b.cls, ix->sc[b.set]);  // the recount writes the counts of EVERY query of the sub-batch (the run's buffer may be on its diet)
     if (rc) return rc;
     ix->dbg_full_run = true;
     rc = enqueue_kmer(ix, b, ix->stream);
@@ -162,16 +162,17 @@ static int debug_recount_full(rtx_index *ix) {
 // u16 counts of one slot of the last sub-batch on the device (unpacked into a scratch row if they are packed)
 static int debug_counts_u16(rtx_index *ix, uint32_t slot, const uint16_t **out) {
     rtx_index::Scratch &sc = ix->sc[ix->last_set];
-    if (ix->diet_used && !ix->dbg_full && sc.d_cnt_row.p) {  // as the run left them: the query's row of the counts buffer (HitParams::cnt_row)
+    const rtx_index::BatchClass &k = ix->last_cls();
+    if (k.diet && !ix->dbg_full && sc.d_cnt_row.p) {  // as the run left them: the query's row of the counts buffer (HitParams::cnt_row)
         uint32_t row = 0;
         RTX_HIP(hipMemcpy(&row, sc.d_cnt_row.p + slot, 4, hipMemcpyDeviceToHost));
         if (row == 0xFFFFFFFFu) { set_error("debug tap: the query holds no row of the counts buffer (records path)"); return RTX_ERR_STATE; }
         slot = row;
     }
-    if (!ix->packed()) { *out = sc.d_counts.p + (size_t)slot * ix->npad; return RTX_OK; }
+    if (!ix->packs(k.planes)) { *out = sc.d_counts.p + (size_t)slot * ix->npad; return RTX_OK; }
     int rc = ix->d_counts_dbg.alloc(ix->npad);
     if (rc) return rc;
-    launch_counts_unpack(ix->stream, counts_lo(ix, sc) + (size_t)slot * ix->npad, counts_hi(ix, sc) + (size_t)slot * (ix->npad >> 3), ix->npad,
+    launch_counts_unpack(ix->stream, counts_lo(ix, sc) + (size_t)slot * ix->npad, counts_hi(ix, k, sc) + (size_t)slot * (ix->npad >> 3), ix->npad,
                          ix->d_counts_dbg.p);
     RTX_HIP(hipStreamSynchronize(ix->stream));
     *out = ix->d_counts_dbg.p;
@@ -185,7 +186,7 @@ int rtx_debug_kmers(rtx_index *ix, uint64_t query, uint16_t *kmers, uint32_t *t)
     uint32_t tt = 0;
     RTX_HIP(hipMemcpy(&tt, ix->sc[ix->last_set].d_t.p + slot, 4, hipMemcpyDeviceToHost));
     if (t) *t = tt;
-    if (kmers && tt) RTX_HIP(hipMemcpy(kmers, ix->sc[ix->last_set].d_kmers.p + (size_t)slot * ix->kstride, std::min(tt, ix->kstride) * 2, hipMemcpyDeviceToHost));
+    if (kmers && tt) RTX_HIP(hipMemcpy(kmers, ix->sc[ix->last_set].d_kmers.p + (size_t)slot * ix->last_cls().kstride, std::min(tt, ix->last_cls().kstride) * 2, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
 
@@ -206,8 +207,9 @@ int rtx_debug_prob_table(rtx_index *ix, uint64_t query, double *table_over_z, do
     uint32_t tt = 0;
     RTX_HIP(hipMemcpy(&tt, ix->sc[ix->last_set].d_t.p + slot, 4, hipMemcpyDeviceToHost));
     std::vector<uint32_t> hist(tt + 1);
-    RTX_HIP(hipMemcpy(hist.data(), ix->sc[ix->last_set].d_hist.p + (size_t)slot * ix->hstride, (tt + 1) * 4, hipMemcpyDeviceToHost));
-    RTX_HIP(hipMemcpy(table_over_z, ix->sc[ix->last_set].d_table_z.p + (size_t)slot * ix->hstride, (tt + 1) * 8, hipMemcpyDeviceToHost));
+    const uint32_t hstride = ix->last_cls().hstride;
+    RTX_HIP(hipMemcpy(hist.data(), ix->sc[ix->last_set].d_hist.p + (size_t)slot * hstride, (tt + 1) * 4, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(table_over_z, ix->sc[ix->last_set].d_table_z.p + (size_t)slot * hstride, (tt + 1) * 8, hipMemcpyDeviceToHost));
     for (uint32_t m = 0; m <= tt; m++)
         if (!hist[m]) table_over_z[m] = 0.0;  // entries of absent counts are never written
     if (z) RTX_HIP(hipMemcpy(z, ix->res().d_z.p + pos, 8, hipMemcpyDeviceToHost));
@@ -219,7 +221,8 @@ int rtx_debug_pruned_prob_table(rtx_index *ix, uint64_t query, double *table_ove
     uint32_t slot, pos;
     int rc = debug_slot_as_run(ix, query, &slot, &pos);
     if (rc) return rc;
-    if (!ix->prune_used) { set_error("rtx_debug_pruned_prob_table: the last run did not prune"); return RTX_ERR_STATE; }
+    const rtx_index::BatchClass &k = ix->last_cls();
+    if (!k.prune) { set_error("rtx_debug_pruned_prob_table: the last run did not prune"); return RTX_ERR_STATE; }
     if (ix->dbg_full) { set_error("rtx_debug_pruned_prob_table: another tap has recounted the sub-batch in full"); return RTX_ERR_STATE; }
     rtx_index::Scratch &sc = ix->sc[ix->last_set];
     uint32_t tt = 0;
@@ -227,8 +230,8 @@ int rtx_debug_pruned_prob_table(rtx_index *ix, uint64_t query, double *table_ove
     RTX_HIP(hipMemcpy(&tt, sc.d_t.p + slot, 4, hipMemcpyDeviceToHost));
     RTX_HIP(hipMemcpy(&thr, sc.d_prune_thr.p + slot, 2, hipMemcpyDeviceToHost));
     std::vector<uint32_t> hist(tt + 1);
-    RTX_HIP(hipMemcpy(hist.data(), sc.d_hist.p + (size_t)slot * ix->hstride, (tt + 1) * 4, hipMemcpyDeviceToHost));
-    RTX_HIP(hipMemcpy(table_over_z, sc.d_table_z.p + (size_t)slot * ix->hstride, (tt + 1) * 8, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(hist.data(), sc.d_hist.p + (size_t)slot * k.hstride, (tt + 1) * 4, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(table_over_z, sc.d_table_z.p + (size_t)slot * k.hstride, (tt + 1) * 8, hipMemcpyDeviceToHost));
     for (uint32_t m = 0; m <= tt; m++)
         if (!hist[m] || m <= thr) table_over_z[m] = 0.0;  // entries of absent counts are never written; up to the threshold: 0 by construction
     if (z) RTX_HIP(hipMemcpy(z, ix->res().d_z.p + pos, 8, hipMemcpyDeviceToHost));
@@ -246,10 +249,11 @@ int rtx_debug_run_counts(rtx_index *ix, uint64_t query, uint16_t *counts, uint8_
     if (rc) return rc;
     if (ix->dbg_full) { set_error("rtx_debug_run_counts: another tap has recounted the sub-batch in full"); return RTX_ERR_STATE; }
     rtx_index::Scratch &sc = ix->sc[ix->last_set];
+    const rtx_index::BatchClass &k = ix->last_cls();
     const uint32_t nt = ix->ntiles;
     std::vector<uint8_t> live(nt, 1);
     uint16_t thr = 0, i1v = 0;
-    if (ix->prune_used) {
+    if (k.prune) {
         const uint32_t lw = LiveLayout{nt}.words();
         std::vector<uint32_t> words(lw);
         RTX_HIP(hipMemcpy(words.data(), sc.d_live.p + (size_t)slot * lw, lw * 4, hipMemcpyDeviceToHost));
@@ -258,7 +262,7 @@ int rtx_debug_run_counts(rtx_index *ix, uint64_t query, uint16_t *counts, uint8_
         RTX_HIP(hipMemcpy(&i1v, sc.d_prune_i1.p + slot, 2, hipMemcpyDeviceToHost));
     }
     uint16_t n_seg = 0;  // > 0: the query took the records path -- its counts are the records of its segments
-    if (ix->prune_used && ix->rec_used && sc.d_rec_nslots.p) RTX_HIP(hipMemcpy(&n_seg, sc.d_rec_nslots.p + slot, 2, hipMemcpyDeviceToHost));
+    if (k.prune && k.rec && sc.d_rec_nslots.p) RTX_HIP(hipMemcpy(&n_seg, sc.d_rec_nslots.p + slot, 2, hipMemcpyDeviceToHost));
     if (counts && n_seg) {
         // visited tiles: the count of every reference above the threshold, 0 for the others (the run never wrote those); unvisited: 0xFFFF
         const uint32_t stride = ix->rec_slots();
@@ -268,15 +272,15 @@ int rtx_debug_run_counts(rtx_index *ix, uint64_t query, uint16_t *counts, uint8_
         RTX_HIP(hipMemcpy(cnts, sc.d_rec_cnt.p + (size_t)slot * kRecMaxSlots, sizeof cnts, hipMemcpyDeviceToHost));
         for (uint64_t r = 0; r < ix->n_refs; r++) counts[r] = live[r >> 13] ? 0u : 0xFFFFu;
         std::vector<uint32_t> seg(ix->rec_seg_len);
-        for (uint32_t k = 0; k < n_seg && k < stride; k++) {
-            const uint32_t c = std::min<uint32_t>(cnts[k], ix->rec_seg_len);
+        for (uint32_t j = 0; j < n_seg && j < stride; j++) {
+            const uint32_t c = std::min<uint32_t>(cnts[j], ix->rec_seg_len);
             if (!c) continue;
-            RTX_HIP(hipMemcpy(seg.data(), sc.d_rec.p + ((size_t)slot * stride + k) * ix->rec_seg_len, (size_t)c * 4, hipMemcpyDeviceToHost));
+            RTX_HIP(hipMemcpy(seg.data(), sc.d_rec.p + ((size_t)slot * stride + j) * ix->rec_seg_len, (size_t)c * 4, hipMemcpyDeviceToHost));
             uint32_t prev = 0;
             for (uint32_t i = 0; i < c; i++) {
                 const uint32_t rl = seg[i] & 8191u;
-                const uint64_t r = (uint64_t)tiles[k] * 8192u + rl;
-                if (r >= ix->n_refs || (i && rl <= prev) || !live[tiles[k]]) { set_error("rtx_debug_run_counts: malformed record %u of segment %u of query %llu", i, k, (unsigned long long)query); return RTX_ERR_STATE; }
+                const uint64_t r = (uint64_t)tiles[j] * 8192u + rl;
+                if (r >= ix->n_refs || (i && rl <= prev) || !live[tiles[j]]) { set_error("rtx_debug_run_counts: malformed record %u of segment %u of query %llu", i, j, (unsigned long long)query); return RTX_ERR_STATE; }
                 counts[r] = (uint16_t)(seg[i] >> 13);
                 prev = rl;
             }
@@ -295,7 +299,7 @@ int rtx_debug_run_counts(rtx_index *ix, uint64_t query, uint16_t *counts, uint8_
     if (hist) {
         uint32_t tt = 0;
         RTX_HIP(hipMemcpy(&tt, sc.d_t.p + slot, 4, hipMemcpyDeviceToHost));
-        RTX_HIP(hipMemcpy(hist, sc.d_hist.p + (size_t)slot * ix->hstride, (size_t)(tt + 1) * 4, hipMemcpyDeviceToHost));
+        RTX_HIP(hipMemcpy(hist, sc.d_hist.p + (size_t)slot * k.hstride, (size_t)(tt + 1) * 4, hipMemcpyDeviceToHost));
     }
     if (threshold) *threshold = thr;
     if (i1) *i1 = i1v;
@@ -310,7 +314,7 @@ int rtx_debug_run_mode(rtx_index *ix, uint64_t query, uint32_t *n_segments) {
     if (!n_segments) { set_error("null argument"); return RTX_ERR_INVALID; }
     uint16_t n_seg = 0;
     rtx_index::Scratch &sc = ix->sc[ix->last_set];
-    if (ix->prune_used && ix->rec_used && sc.d_rec_nslots.p) RTX_HIP(hipMemcpy(&n_seg, sc.d_rec_nslots.p + slot, 2, hipMemcpyDeviceToHost));
+    if (ix->last_cls().prune && ix->last_cls().rec && sc.d_rec_nslots.p) RTX_HIP(hipMemcpy(&n_seg, sc.d_rec_nslots.p + slot, 2, hipMemcpyDeviceToHost));
     *n_segments = n_seg;
     return RTX_OK;
 }
@@ -322,7 +326,7 @@ int rtx_debug_prune_detail(rtx_index *ix, uint64_t query, uint32_t *out) {
     int rc = debug_slot_as_run(ix, query, &slot);
     if (rc) return rc;
     if (!out) { set_error("null argument"); return RTX_ERR_INVALID; }
-    if (!ix->prune_used || !ix->debug_taps || ix->d_prune_detail.n < (size_t)(slot + 1) * kPruneDetailWords) {
+    if (!ix->last_cls().prune || !ix->debug_taps || ix->d_prune_detail.n < (size_t)(slot + 1) * kPruneDetailWords) {
         set_error("rtx_debug_prune_detail: the last run did not prune, or RTX_OPT_DEBUG_TAPS was off");
         return RTX_ERR_STATE;
     }
@@ -336,7 +340,7 @@ int rtx_debug_tile_bounds(rtx_index *ix, uint64_t query, uint16_t *tile_ub) {
     if (rc) return rc;
     if (!tile_ub) { set_error("null argument"); return RTX_ERR_INVALID; }
     rtx_index::Scratch &sc = ix->sc[ix->last_set];
-    if (!ix->prune_used || sc.d_tile_ub.n < (size_t)(slot + 1) * ix->ntiles) { set_error("rtx_debug_tile_bounds: the last run did not prune"); return RTX_ERR_STATE; }
+    if (!ix->last_cls().prune || sc.d_tile_ub.n < (size_t)(slot + 1) * ix->ntiles) { set_error("rtx_debug_tile_bounds: the last run did not prune"); return RTX_ERR_STATE; }
     RTX_HIP(hipMemcpy(tile_ub, sc.d_tile_ub.p + (size_t)slot * ix->ntiles, (size_t)ix->ntiles * 2, hipMemcpyDeviceToHost));
     return RTX_OK;
 }
@@ -361,18 +365,18 @@ int rtx_debug_prune_stats(rtx_index *ix, uint64_t *out) {
 
 int rtx_batch_sub_batch(const rtx_index *ix, uint32_t *sub_batch, uint32_t *n_sub) {
     if (!ix) { set_error("null index handle"); return RTX_ERR_INVALID; }
-    if (!ix->uploaded || ix->sub_batch == 0 || ix->n_cls == 0) { set_error("rtx_batch_sub_batch: no batch has been uploaded"); return RTX_ERR_STATE; }
+    if (!ix->uploaded || ix->n_cls == 0 || ix->cls[ix->n_cls - 1].sub_batch == 0) { set_error("rtx_batch_sub_batch: no batch has been uploaded"); return RTX_ERR_STATE; }
     if (sub_batch) *sub_batch = ix->cls[ix->n_cls - 1].sub_batch;
-    if (n_sub) *n_sub = ix->n_sub_total;
+    if (n_sub) *n_sub = ix->n_sub_total();
     return RTX_OK;
 }
 
 // the last sub-batch of the uploaded batch (the one the taps can read): positions [first, first + n) of the processing order
 int rtx_batch_last_sub_batch(const rtx_index *ix, uint64_t *first, uint32_t *n) {
     if (!ix) { set_error("null index handle"); return RTX_ERR_INVALID; }
-    if (!ix->uploaded || ix->n_sub_total == 0 || ix->sub_q0.size() != ix->n_sub_total) { set_error("rtx_batch_last_sub_batch: no batch has been uploaded"); return RTX_ERR_STATE; }
-    if (first) *first = ix->sub_q0[ix->n_sub_total - 1];
-    if (n) *n = ix->sub_nq[ix->n_sub_total - 1];
+    if (!ix->uploaded) { set_error("rtx_batch_last_sub_batch: no batch has been uploaded"); return RTX_ERR_STATE; }
+    if (first) *first = ix->plan.back().q0;
+    if (n) *n = ix->plan.back().nq;
     return RTX_OK;
 }
 
@@ -408,7 +412,7 @@ int rtx_debug_probs(rtx_index *ix, uint64_t query, double *probs) {
     if ((rc = ix->d_probs_dbg.alloc(ix->n_refs))) return rc;
     const uint16_t *src = nullptr;
     if ((rc = debug_counts_u16(ix, slot, &src))) return rc;
-    launch_probs_expand(ix->stream, src, ix->sc[ix->last_set].d_table_z.p + (size_t)slot * ix->hstride, ix->n_refs, ix->d_probs_dbg.p);
+    launch_probs_expand(ix->stream, src, ix->sc[ix->last_set].d_table_z.p + (size_t)slot * ix->last_cls().hstride, ix->n_refs, ix->d_probs_dbg.p);
     RTX_HIP(hipStreamSynchronize(ix->stream));
     RTX_HIP(hipMemcpy(probs, ix->d_probs_dbg.p, ix->n_refs * 8, hipMemcpyDeviceToHost));
     return RTX_OK;
@@ -425,7 +429,8 @@ int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out)
     if (N > 65535) { set_error("rtx_debug_evaluate supports at most 65535 references"); return RTX_ERR_INVALID; }
     ix->uploaded = ix->ran = ix->synced = false;
     if ((rc = prepare_workspace_single(ix, 1, std::max<uint64_t>(N, 8), 0))) return rc;
-    ix->last_set = 0;
+    const SubBatch b = sub_batch_of(ix, 0, false);  // the one pseudo-query, in the one class
+    ix->last_set = b.set;
     ix->sum_query_bytes = 0;
     record_batch(ix);
     rtx_index::ResultSet &res = ix->res();
@@ -462,7 +467,7 @@ int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out)
     fp.counts = ix->sc[ix->last_set].d_counts.p;
     fp.npad = ix->npad;
     fp.table_z = ix->sc[ix->last_set].d_table_z.p;
-    fp.hstride = ix->hstride;
+    fp.hstride = b.cls->hstride;
     fp.n_refs = N;
     fp.bnd_bits = ix->d_bnd_bits.p;
     fp.bnd_rank = ix->d_bnd_rank.p;
@@ -482,11 +487,7 @@ int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out)
     wp.row_start = res.d_row_start.p;
     wp.flags_out = res.d_flags.p;
     launch_lineage_walk(s, wp, 1);
-    {
-        SubBatch b{};
-        b.sb = 0; b.nq = 1; b.set = 0; b.q0 = 0; b.s = s;
-        if ((rc = enqueue_finalise(ix, b, s))) return rc;
-    }
+    if ((rc = enqueue_finalise(ix, b, s))) return rc;
     RTX_HIP(hipGetLastError());
     ix->n_sub_last = 0;
     ix->ran = true;

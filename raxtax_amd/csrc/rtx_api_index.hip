@@ -556,7 +556,9 @@ int rtx_index_create_from_sequences(int device, uint64_t n_refs, const uint8_t *
     for (uint64_t i = 0; i <= n_refs; i++) off0[i] = seq_off[i] - seq_off[0];
     hipError_t e = hipMemcpy(d_seq.p, seq_bytes + seq_off[0], total, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_off.p, off0.data(), (n_refs + 1) * 8, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemset(d_present.p, 0, 2048 * 4);
+    // (on the handle's stream: it does not wait for the null stream, and a fill of device memory may still be under way when hipMemset returns --
+    // a fill that lands behind the kernel's marks leaves k-mers without a row, and ref_bitmap_set_kernel an address far outside the bitmap)
+    if (e == hipSuccess) e = hipMemsetAsync(d_present.p, 0, 2048 * 4, ix->stream);
     if (e == hipSuccess) {
         launch_ref_kmer_mark(ix->stream, d_seq.p, d_off.p, n_refs, d_present.p);
         e = hipStreamSynchronize(ix->stream);

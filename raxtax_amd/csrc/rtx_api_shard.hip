@@ -11,6 +11,8 @@ extern "C" {
 //   rtx_shard_prob   -> all-gather of the local prefix sums (RTX_BUF_PREFIX, [nq][n_bnd_local] f64), offset
 //                       by the running shard totals and concatenated into [nq][n_bnd]
 //   rtx_shard_walk(prefix_global)
+// The exchange buffers have ONE row stride, so every sub-batch of a staged run is launched in the shape of cls[0] (shard_sb), and cls[0] is
+// what the entry points that are handed no sub-batch report.  A reference shard has no other class (prepare_workspace); a k-mer shard may.
 int rtx_shard_begin(rtx_index *ix, uint32_t *n_sub_batches, uint32_t *sub_batch) {
     int rc = bind(ix);
     if (rc) return rc;
@@ -28,7 +30,7 @@ int rtx_shard_begin(rtx_index *ix, uint32_t *n_sub_batches, uint32_t *sub_batch)
     ix->synced = false;
     ix->last_flags = 0;
     if (n_sub_batches) *n_sub_batches = n_sub;
-    if (sub_batch) *sub_batch = ix->sub_batch;
+    if (sub_batch) *sub_batch = ix->cls[0].sub_batch;
     return RTX_OK;
 }
 
@@ -36,14 +38,15 @@ static int shard_sb(rtx_index *ix, uint32_t sb, SubBatch *b) {
     int rc = bind(ix);
     if (rc) return rc;
     if (!ix->ran) { set_error("rtx_shard_* before rtx_shard_begin"); return RTX_ERR_STATE; }
-    const uint32_t n_sub = ix->n_sub_total;
+    const uint32_t n_sub = ix->n_sub_total();
     if (sb >= n_sub) { set_error("sub-batch %u out of range (%u)", sb, n_sub); return RTX_ERR_INVALID; }
     *b = sub_batch_of(ix, sb, ix->n_sub_last != 0);
+    b->cls = &ix->cls[0];  // (whatever class the plan names: above)
     ix->synced = false;
     return RTX_OK;
 }
 
-int rtx_shard_prunes(const rtx_index *ix) { return ix && ix->ran && ix->staged && ix->prune_used ? 1 : 0; }
+int rtx_shard_prunes(const rtx_index *ix) { return ix && ix->ran && ix->staged && ix->cls[0].prune ? 1 : 0; }
 
 // A pruning shard, first half of the counting of a sub-batch: k-mers, bounds against the union bitmap of this shard, its candidate for
 // the best block of the database (RTX_BUF_BEST).  The caller keeps per query the candidate with the largest bound over all shards
@@ -52,7 +55,7 @@ int rtx_shard_bounds(rtx_index *ix, uint32_t sb, uint32_t flags) {
     SubBatch b;
     int rc = shard_sb(ix, sb, &b);
     if (rc) return rc;
-    if (!ix->prune_used) { set_error("rtx_shard_bounds: this run does not prune (rtx_shard_prunes)"); return RTX_ERR_STATE; }
+    if (!b.cls->prune) { set_error("rtx_shard_bounds: this run does not prune (rtx_shard_prunes)"); return RTX_ERR_STATE; }
     ix->last_flags = flags;
     if ((rc = enqueue_kmer(ix, b, b.s))) return rc;
     return enqueue_hit(ix, b, flags, b.s, 1);
@@ -63,7 +66,7 @@ int rtx_shard_count(rtx_index *ix, uint32_t sb, uint32_t flags) {
     int rc = shard_sb(ix, sb, &b);
     if (rc) return rc;
     ix->last_flags = flags;
-    if (ix->prune_used) return enqueue_hit(ix, b, flags, b.s, 2);  // after rtx_shard_bounds and the exchange of RTX_BUF_BEST
+    if (b.cls->prune) return enqueue_hit(ix, b, flags, b.s, 2);  // after rtx_shard_bounds and the exchange of RTX_BUF_BEST
     return enqueue_count(ix, b, flags);
 }
 
@@ -99,7 +102,7 @@ int rtx_device_buffer(rtx_index *ix, int which, void **ptr, uint64_t *row_stride
     if (!ix->uploaded) { set_error("rtx_device_buffer before rtx_batch_upload"); return RTX_ERR_STATE; }
     rtx_index::Scratch &sc = ix->sc[0];
     switch (which) {
-        case RTX_BUF_HIST: *ptr = sc.d_hist.p; if (row_stride_elems) *row_stride_elems = ix->hstride; return RTX_OK;
+        case RTX_BUF_HIST: *ptr = sc.d_hist.p; if (row_stride_elems) *row_stride_elems = ix->cls[0].hstride; return RTX_OK;
         case RTX_BUF_PREFIX: *ptr = sc.d_prefix.p; if (row_stride_elems) *row_stride_elems = ix->n_bnd_local; return RTX_OK;
         default: break;
     }
@@ -112,7 +115,7 @@ int rtx_shard_buffer(rtx_index *ix, uint32_t sb, int which, void **ptr, uint64_t
     if (!ix->uploaded) { set_error("rtx_shard_buffer before rtx_batch_upload"); return RTX_ERR_STATE; }
     rtx_index::Scratch &sc = ix->sc[ix->staged ? (sb & 1u) : 0u];
     switch (which) {
-        case RTX_BUF_HIST: *ptr = sc.d_hist.p; if (row_stride_elems) *row_stride_elems = ix->hstride; return RTX_OK;
+        case RTX_BUF_HIST: *ptr = sc.d_hist.p; if (row_stride_elems) *row_stride_elems = ix->cls[0].hstride; return RTX_OK;
         case RTX_BUF_PREFIX: *ptr = sc.d_prefix.p; if (row_stride_elems) *row_stride_elems = ix->n_bnd_local; return RTX_OK;
         case RTX_BUF_BEST:
             if (!sc.d_best.p) { set_error("RTX_BUF_BEST: the handle does not prune"); return RTX_ERR_STATE; }
@@ -120,7 +123,7 @@ int rtx_shard_buffer(rtx_index *ix, uint32_t sb, int which, void **ptr, uint64_t
             if (row_stride_elems) *row_stride_elems = kPruneBestWords;
             return RTX_OK;
         case RTX_BUF_COUNTS:
-            if (ix->packed()) { set_error("RTX_BUF_COUNTS needs u16 counts (RTX_OPT_PACKED_COUNTS = 0)"); return RTX_ERR_STATE; }
+            if (ix->packs(ix->cls[0].planes)) { set_error("RTX_BUF_COUNTS needs u16 counts (RTX_OPT_PACKED_COUNTS = 0)"); return RTX_ERR_STATE; }
             *ptr = sc.d_counts.p;
             if (row_stride_elems) *row_stride_elems = ix->npad;
             return RTX_OK;
@@ -142,9 +145,9 @@ int rtx_shard_rehist(rtx_index *ix, uint32_t sb) {
     SubBatch b;
     int rc = shard_sb(ix, sb, &b);
     if (rc) return rc;
-    if (ix->packed()) { set_error("rtx_shard_rehist needs u16 counts (RTX_OPT_PACKED_COUNTS = 0)"); return RTX_ERR_STATE; }
+    if (ix->packs(b.cls->planes)) { set_error("rtx_shard_rehist needs u16 counts (RTX_OPT_PACKED_COUNTS = 0)"); return RTX_ERR_STATE; }
     rtx_index::Scratch &sc = ix->sc[b.set];
-    launch_rehist(b.s, sc.d_counts.p, ix->npad, ix->n_refs, sc.d_t.p, sc.d_hist.p, ix->hstride, sc.d_tilemax.p, ix->ntiles, b.nq);
+    launch_rehist(b.s, sc.d_counts.p, ix->npad, ix->n_refs, sc.d_t.p, sc.d_hist.p, b.cls->hstride, sc.d_tilemax.p, ix->ntiles, b.nq);
     RTX_HIP(hipGetLastError());
     return RTX_OK;
 }

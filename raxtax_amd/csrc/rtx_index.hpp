@@ -149,7 +149,6 @@ struct rtx_index {
     DevBuf<uint64_t> d_tab_off;
     DevBuf<uint32_t> d_tab_moff;
     DevBuf<uint16_t> d_tab_ilo, d_tab_sat;
-    bool use_tables = false;
     // ---- taxonomy
     FlatNodes nodes;
     std::vector<uint32_t> bnd;  // sorted unique range endpoints
@@ -193,8 +192,7 @@ struct rtx_index {
     bool prune_pays = true;        // ... which is: a sample of the database's own references keeps fewer than kSelfSampleOff of its tiles live
     double self_live = -1.0;       // the share of (query, tile) combinations the sample kept live (-1: no sample was taken)
     bool pruning() const { return prune_opt != 0u && (prune_pays || self_sample_opt == 0u); }  // tile pruning is on for this handle (where the batch allows it)
-    bool prune_used = false;  // the last run pruned
-    bool dbg_full = false;    // ... and the debug taps have recounted the last sub-batch in full since
+    bool dbg_full = false;    // the last sub-batch of the run was pruned (last_cls().prune) and the debug taps have recounted it in full since
     bool dbg_full_run = false;  // (the recount in progress: enqueue_hit leaves the pruning out)
     DevBuf<uint32_t> d_ubitmap;  // union bitmap: one column per block of 2^kPruneShift references, tile-major like d_bitmap
     uint32_t u_stride_bytes = 0, u_ntiles = 0;
@@ -218,27 +216,22 @@ struct rtx_index {
     // least kDietMinRows); a run in which prune_kernel runs out of rows raises bit 2 of d_flags, the download lowers diet_shift and repeats it.
     uint32_t rec_seg_len = 1024;  // records per segment of the records path (RecordRef::seg_len): doubled, up to 8192, when a run's segment overflows
     uint32_t diet_shift = 3;
-    bool diet_used = false;      // the class being enqueued lays its counts out in cnt_rows_cur rows
-    uint32_t cnt_rows_cur = 0;
     uint32_t rec_opt = 4;   // RTX_OPT_RECORDS: pruned queries with at most this many live tiles take the records path (0: off; at most kRecMaxSlots)
     uint32_t rec_slots() const { return std::min<uint32_t>(rec_opt, kRecMaxSlots); }  // record segments per query (RecordRef::stride)
     uint32_t overlap_opt = 1;  // RTX_OPT_OVERLAP: 1 = back half of sub-batch k on a second stream beside the front half of k + 1 (2: three stages)
     uint32_t overlap_used = 0;  // scratch sets the last run used beside each other (0: one stream)
     hipStream_t stream2 = nullptr, stream3 = nullptr, hit_stream = nullptr;  // (hit_stream: where enqueue_hit launched the counting pass)
     std::vector<hipEvent_t> ev_front, ev_back, ev_mid;  // per sub-batch: front half enqueued (on stream), back half done (on stream2)
-    bool rec_used = false;  // the last run offered the records path (whole-database handle that prunes, walk fused)
     DevBuf<unsigned long long> d_prune_stats;
     uint32_t shard_prune_opt = 0;  // RTX_OPT_SHARD_PRUNE: a reference shard prunes with the threshold of the whole database (rtx_shard_bounds)
     uint32_t debug_taps = 0;     // RTX_OPT_DEBUG_TAPS: prune_kernel leaves its view of every query (rtx_debug_prune_detail)
     DevBuf<uint32_t> d_prune_detail;  // [sub_batch][kPruneDetailWords]
     uint32_t locator_opt = 1; // RTX_OPT_LOCATOR: the sort key of the processing order is led by the query's position in the database
     DevBuf<uint32_t> d_loc_table;  // 12-mer -> lowest reference position (rtx_cluster.hip); only when built from sequences
-    bool pair_used = false;   // the last run went through hit_count_pair_kernel
     DevBuf<uint32_t> d_group_rows;
     uint32_t n_groups_run = 0;  // groups of the whole batch (n_sub * groups_per_sub): the second half of d_group_rows starts there
     uint32_t groups_per_sub = 0;
     bool packs(int pl) const { return packed_opt && pl <= 10; }  // counts of a class of `pl` bit planes travel packed (11 planes -- reads of 1 031 .. 2 054 bases on the pair kernel -- leave u16 counts)
-    bool packed() const { return packs(planes); }
     DevBuf<uint64_t> d_skey_in, d_skey_out;
     DevBuf<uint32_t> d_sidx;
     DevBuf<uint8_t> d_sort_tmp;
@@ -270,11 +263,9 @@ struct rtx_index {
     hipEvent_t ev_activated = nullptr; // on the handle's stream, behind everything that was enqueued before the current batch was activated:
                                        // the kernels that read the OTHER input set have run when it fires (a transfer into that set waits for it)
     uint64_t sum_query_bytes = 0;
-    uint32_t kstride = 0, rstride = 0, hstride = 0, tmax = 0;
-    int planes = 10;
     // ---- sub-batch scratch: two sets -- a staged (reference-sharded) run alternates between them, so that the exchange of
     // one sub-batch can overlap with the counting of the next; a whole-database handle uses set 0 only
-    uint32_t sub_batch_req = 0, sub_batch = 0;
+    uint32_t sub_batch_req = 0;  // rtx_index_set_batch (0: sized against free HBM)
     uint32_t min_subs = 4;  // RTX_OPT_MIN_SUB_BATCHES: a pruned batch is cut into at least this many sub-batches (the host finalises one while the next run)
     uint64_t ws_key[14] = {0};  // shape and options the workspace was last prepared for (prepare_workspace)
     bool ws_valid = false;
@@ -282,25 +273,31 @@ struct rtx_index {
     // kernel, tile pruning), how its probabilities are computed (memoised tables up to t = 2047, the recurrence kernel in LDS, the same
     // from global memory for reads of tens of kilobases) and how much scratch it needs.  A batch used to take ALL of that from its longest
     // query: one 1 100-base read in a file of COI barcodes moved every query off the fast path.  Now the class leads the sort key of the
-    // processing order, every class is cut into sub-batches of its own shape, and the fields above (tmax, strides, planes, sub_batch,
-    // use_tables, pair_used, prune_used, rec_used) are those of the class being enqueued (apply_class) -- after a run: of the last one,
-    // which is what the taps of the last sub-batch read.  A reference shard and rtx_debug_evaluate run one class.
+    // processing order and every class is cut into sub-batches of its own shape (plan).  The shape of a class (tmax, strides, planes,
+    // sub_batch, cnt_rows) and what it runs through (use_tables, pair, prune, rec, diet) are held HERE and nowhere else: a SubBatch names its
+    // class (sub_batch_of), whoever fills kernel parameters reads it there, and the handle holds no "current class".  The taps read the class
+    // of the last sub-batch (last_cls).  A reference shard and rtx_debug_evaluate have one class (prepare_workspace_single).  A STAGED run
+    // (rtx_shard_*) has one row stride for its exchange buffers: every sub-batch of it is launched in the shape of cls[0] (shard_sb) -- which is
+    // all there is on a reference shard; a k-mer shard holds every reference, so a batch of mixed lengths is cut into several classes there,
+    // and its longer reads are clipped to class 0's strides as they always were.
     struct BatchClass {
         uint64_t pos0 = 0, n = 0, max_len = 0;  // positions [pos0, pos0 + n) of the processing order
         uint32_t tmax = 0, kstride = 0, rstride = 0, hstride = 0, sub_batch = 0, sb0 = 0, n_sub = 0;
         int planes = 10;
+        // what its sub-batches run through: the memoised tables, hit_count_pair_kernel, tile pruning, the records path on offer (whole-database handle
+        // that prunes, walk fused) -- decided by begin_run; huge: prob_table's arrays in global memory; will_prune: size_workspace's forecast of prune
         bool use_tables = false, pair = false, prune = false, rec = false, huge = false, will_prune = false;
         bool side = false;  // a handful of queries beside the bulk of the batch: they run FIRST, through a small scratch set of their own (kSideSet)
         bool diet = false;      // rows of the counts buffer are handed out by prune_kernel (behind tile pruning with the records path: HitParams::cnt_row)
         uint32_t cnt_rows = 0;  // rows of counts a sub-batch of the class lays out (diet: a fraction of sub_batch)
     } cls[5];
     uint32_t n_cls = 0;
-    int cur_cls = -1;
     uint64_t key_lim[4] = {~0ull, ~0ull, ~0ull, ~0ull};  // sort rank of a query = the number of these lengths it exceeds
-    std::vector<uint64_t> sub_q0;   // per sub-batch of the run: first position,
-    std::vector<uint32_t> sub_nq;   // queries,
-    std::vector<uint8_t> sub_cls;   // class
-    uint32_t n_sub_total = 0, sub_batch_max = 0;
+    struct SubPlan { uint64_t q0; uint32_t nq, cls; };  // a sub-batch of the run: first position of the processing order, queries, index of its class
+    std::vector<SubPlan> plan;      // plan_sub_batches: whenever the workspace is sized and at the start of every run (an upload of the shape of the last one keeps
+                                    // the plan it finds: ws_valid).  `uploaded` implies a workspace sized for at least one query: never empty behind an upload
+    uint32_t n_sub_total() const { return (uint32_t)plan.size(); }
+    uint32_t sub_batch_max = 0;
     bool any_prune = false;  // some class of the last run pruned (rtx_debug_prune_stats sums over the run)
     DevBuf<double> d_prob_scratch;  // prob_table_kernel's arrays of a class of very long reads (they do not fit LDS)
     struct Scratch {
@@ -343,6 +340,7 @@ struct rtx_index {
     bool staged = false;  // driven with rtx_shard_*: sub-batch sb works in scratch set sb & 1, so that the exchange of one
                           // sub-batch (RCCL, on the caller's stream) can overlap with the counting of the next
     uint32_t last_set = 0;  // scratch set of the last sub-batch (debug taps)
+    const BatchClass &last_cls() const { return cls[staged ? 0u : plan.back().cls]; }  // ... and the class it ran in the shape of (the last of the bulk: plan_sub_batches; staged: cls[0])
     DevBuf<double> d_probs_dbg;
     DevBuf<uint16_t> d_counts_dbg;
     DevBuf<unsigned long long> d_sub_alloc;  // WalkParams::sub_alloc
@@ -475,16 +473,17 @@ int ensure_events(rtx_index *ix, size_t count);
 struct SubBatch {
     uint32_t sb, nq, set;
     uint64_t q0;
+    const rtx_index::BatchClass *cls;  // the length class its kernels are launched in the shape of
     hipStream_t s;   // main stream
     bool timed;      // HIP events around hit_count (the roofline kernel)
     bool timed_all;  // ... and around every other kernel (RTX_OPT_STAGE_TIMING)
 };
 SubBatch sub_batch_of(rtx_index *ix, uint32_t sb, bool timed);
 uint8_t *counts_lo(rtx_index *ix, rtx_index::Scratch &sc);
-uint16_t *counts_hi(rtx_index *ix, rtx_index::Scratch &sc);
-uint32_t counts_rows_layout(const rtx_index *ix);  // rows the counts buffer is laid out for right now (the diet's, or one per query of the sub-batch)
+uint16_t *counts_hi(rtx_index *ix, const rtx_index::BatchClass &k, rtx_index::Scratch &sc);
+uint32_t counts_rows_layout(const rtx_index *ix, const rtx_index::BatchClass &k);  // rows the counts buffer of a sub-batch of class k is laid out for right now (the diet's, or one per query)
 uint32_t diet_rows(const rtx_index *ix, uint32_t B);
-int ensure_full_counts(rtx_index *ix, rtx_index::Scratch &sc);  // a row per query of the current class's sub-batch (the recounting taps)
+int ensure_full_counts(rtx_index *ix, const rtx_index::BatchClass &k, rtx_index::Scratch &sc);  // a row per query of a sub-batch of class k (the recounting taps)
 hipEvent_t stage_event(rtx_index *ix, const SubBatch &b, int stage, int which);
 int enqueue_kmer(rtx_index *ix, const SubBatch &b, hipStream_t s);
 int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s, int part = 0, hipStream_t s_mid = nullptr);
@@ -500,7 +499,6 @@ uint32_t length_class(uint64_t len);
 uint64_t class3_max_len();  // 0: t <= 255, 1: t <= 1023, 2: t <= 2047, 3: longer, prob_table in LDS, 4: longer still
 int prepare_workspace(rtx_index *ix, uint64_t n_queries, const uint64_t cls_n[5], const uint64_t cls_max[5]);
 int prepare_workspace_single(rtx_index *ix, uint64_t n_queries, uint64_t tmax, uint64_t max_len);  // one class whatever the lengths
-void apply_class(rtx_index *ix, uint32_t c);
 int plan_sub_batches(rtx_index *ix);
 int alloc_scratch_set(rtx_index *ix, uint32_t k);
 constexpr uint32_t kSideSet = 3;
