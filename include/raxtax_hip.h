@@ -279,6 +279,18 @@ int rtx_index_set_batch(rtx_index *index, uint32_t sub_batch);
 #define RTX_OPT_DEVICE_TEXT 24       /* 0 (default).  1: rtx_raxtax / rtx_raxtax_multi take the `.out` / `.tsv` text of their chunks from the device
                                       * (rtx_batch_text: the call sets the text up for its tree and flags and stages the labels with every chunk);
                                       * the format stage keeps only the lineage check of raxtax.rs:43-53.  The messages are the same either way. */
+#define RTX_OPT_STRAND 25            /* 0 (default): every query is classified in the orientation it is given, as the reference does.  1: BOTH STRANDS -- when a
+                                      * batch becomes the current one the handle appends the reverse complement of every query on the device (the sequence
+                                      * reversed, the four bits of every one-hot code reversed: A <-> T, C <-> G, ambiguity codes to their complements, a byte
+                                      * above 15 stays), classifies both and keeps, per query, the orientation with the larger PEAK -- the largest hit count
+                                      * over the references, after RTX_SKIP_EXACT_MATCHES has zeroed the exact matches of that orientation; an orientation
+                                      * whose status is not RTX_Q_OK has peak 0.  The reverse complement wins only with a strictly larger peak.  Everything
+                                      * a download returns for a query (t, status, global signal, rows, exact matches) is what the chosen orientation gives
+                                      * as an input of its own; rtx_batch_strands tells which one it was.  Needs the exact-match lookup of the device
+                                      * (rtx_index_has_exact_lookup; a batch with ids passed in is refused: RTX_ERR_INVALID, a handle without the lookup:
+                                      * RTX_ERR_STATE), not available on a reference shard (RTX_ERR_INVALID) and without device text (rtx_batch_text:
+                                      * RTX_ERR_STATE; rtx_raxtax formats on the host whatever RTX_OPT_DEVICE_TEXT says).  Costs at least twice the step
+                                      * time.  Shapes the workspace like the options below. */
 /* RTX_OPT_SUB_BATCH, _PACKED_COUNTS, _HIT_PAIR, _TILE_PRUNE and _PROB_MODE shape the workspace that rtx_batch_upload sizes:
  * setting one of them drops the uploaded batch (rtx_batch_run then fails with RTX_ERR_STATE until the batch is uploaded again). */
 int rtx_index_set_option(rtx_index *index, int option, uint64_t value);
@@ -316,7 +328,7 @@ int rtx_set_default_option(int option, uint64_t value);
  * host mirror, since it needs `raw_confidence` and the lineage strings). */
 typedef struct {
     uint32_t n_queries;
-    uint64_t n_rows;
+    uint64_t n_rows;               /* the length of the row arrays (under RTX_OPT_STRAND they also hold the rows of the orientations that lost: no query refers to them) */
     const uint32_t *t;             /* [n_queries] distinct valid 8-mers (k_mers.len(), raxtax.rs:55) */
     const uint8_t *status;         /* [n_queries] RTX_Q_*                                            */
     const double *global_signal;   /* [n_queries] lineage.rs:86-90                                   */
@@ -365,6 +377,15 @@ int rtx_index_has_exact_lookup(const rtx_index *index);
 /* The exact matches of the last download as the device found them (the batch was uploaded with exact_off == NULL): CSR over the
  * queries, ids ascending as Tree.sequences holds them (tree.rs:109-112).  Valid as long as the view of that download. */
 int rtx_batch_exact_matches(rtx_index *index, const uint64_t **exact_off /*n_queries + 1*/, const uint32_t **exact_ids);
+
+/* Strand and peak of every query of the last download, [n_queries], valid as long as that download's view.  strand: 0 = plus (as given),
+ * 1 = minus (the reverse complement was classified; RTX_OPT_STRAND) -- all 0 with the option off.  peak: the largest hit count over the
+ * references for the classified orientation (see RTX_OPT_STRAND), filled with the option off as well: peak / t tells how near the nearest
+ * reference is.  Either pointer may be NULL.  (A staged run of rtx_shard_* takes no peaks: all 0.) */
+int rtx_batch_strands(rtx_index *index, const uint8_t **strand, const uint32_t **peak);
+/* The reverse complement as the device builds it, on the host: out[i] = complement(in[n - 1 - i]) (in and out must not overlap).  The formatter
+ * uses it for the `.tsv` sequence column of a minus-strand query, which prints the classified orientation. */
+int rtx_revcomp(const uint8_t *in, uint64_t n, uint8_t *out);
 
 /* The same in stages, so that a caller (bench.py) can keep inputs resident in HBM and
  * time the device part alone, or overlap stages of different batches. */
@@ -585,6 +606,16 @@ int rtx_raxtax(rtx_index *index, const rtx_tree *tree, uint64_t n_queries, const
 int rtx_raxtax_multi(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
                      const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                      int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv);
+/* The same with a second callback: `info` (may be NULL) is called directly before the sender, once for every query that has a message, in
+ * input order, with the query's label, its strand (0 plus, 1 minus: RTX_OPT_STRAND), its peak (rtx_batch_strands) and t.  A non-zero return
+ * ends the call like a closed channel (RTX_ERR_SENDER).  rtx_raxtax and rtx_raxtax_multi are this call with info = NULL.  All three honour
+ * RTX_OPT_STRAND of their handles, which must agree on it (RTX_ERR_INVALID otherwise): the messages are those of the chosen orientation,
+ * formatted on the host whatever RTX_OPT_DEVICE_TEXT says; the `.tsv` sequence column prints the orientation that was classified. */
+typedef int (*rtx_query_info_fn)(void *ctx, const char *label, int strand, uint32_t peak, uint32_t t);
+int rtx_raxtax_multi_ex(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                        const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                        int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                        rtx_query_info_fn info, void *info_ctx);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

@@ -148,6 +148,9 @@ _SIGNATURES = {
                                      C.POINTER(C.c_int64)]),
     "rtx_raxtax": (C.c_int, None),  # argtypes set in api.py (callback type)
     "rtx_raxtax_multi": (C.c_int, None),
+    "rtx_raxtax_multi_ex": (C.c_int, None),
+    "rtx_batch_strands": (C.c_int, [C.c_void_p, C.POINTER(u8p), C.POINTER(u32p)]),
+    "rtx_revcomp": (C.c_int, [u8p, C.c_uint64, u8p]),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

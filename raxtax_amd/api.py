@@ -176,10 +176,13 @@ class EvaluationResult:
 
 class Result:
     """Arrays of one classified batch, copied out of the library-owned rtx_result_view and put into query
-    order (the library stores the rows in processing order): rows of query q = row_off[q] .. row_off[q+1]."""
+    order (the library stores the rows in processing order): rows of query q = row_off[q] .. row_off[q+1].
+    strand (0 plus, 1 minus: Index(strand="both")) and peak (the largest hit count over the references for the classified orientation)
+    per query, when the view came from a download (rtx_batch_strands), else None."""
 
-    def __init__(self, view: ResultView):
+    def __init__(self, view: ResultView, strand: Optional[np.ndarray] = None, peak: Optional[np.ndarray] = None):
         nq, nr = view.n_queries, view.n_rows
+        self.strand, self.peak = strand, peak
         arr = lambda p, n: (np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0))
         self.n_queries = nq
         self.t = arr(view.t, nq)
@@ -191,7 +194,7 @@ class Result:
         self.row_off[1:] = np.cumsum(count)
         # source row of every canonical row
         src = (np.repeat(begin - self.row_off[:-1].astype(np.int64), count) + np.arange(int(count.sum()))) if nq else np.zeros(0, np.int64)
-        assert len(src) == nr
+        assert len(src) <= nr   # (under both strands the row arrays also hold the rows of the orientations that lost)
         self.row_lineage = arr(view.row_lineage, nr)[src]
         self.row_node = arr(view.row_node, nr)[src]
         self.row_depth = arr(view.row_depth, nr)[src]
@@ -222,7 +225,7 @@ class Index:
                  tile_skip: Optional[bool] = None, hit_pair=None, locator: Optional[bool] = None, tile_prune: Optional[bool] = None,
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
-                 prune_self_sample: Optional[bool] = None, device_text: bool = False):
+                 prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus"):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -270,6 +273,11 @@ class Index:
             check(self._lib.rtx_index_set_option(self._h, 21, int(two_level)))
         if prune_self_sample is not None:  # RTX_OPT_PRUNE_SELF_SAMPLE: False = RTX_OPT_TILE_PRUNE alone decides (tests of the pruned path on real barcodes)
             check(self._lib.rtx_index_set_option(self._h, 22, int(prune_self_sample)))
+        if strand not in ("plus", "both"):
+            raise ValueError(f"strand must be 'plus' or 'both', not {strand!r}")
+        self.strand = strand
+        if strand == "both":   # RTX_OPT_STRAND: every query is classified in both orientations, the one with the larger peak is reported
+            check(self._lib.rtx_index_set_option(self._h, 25, 1))
         self._view = ResultView()
         self._keep = None
 
@@ -344,7 +352,16 @@ class Index:
 
     def download(self, copy: bool = True):
         check(self._lib.rtx_batch_download(self._h, C.byref(self._view)))
-        return Result(self._view) if copy else self._view
+        return Result(self._view, *self.strands()) if copy else self._view
+
+    def strands(self):
+        """(strand, peak) of every query of the last download: rtx_batch_strands."""
+        ps, pk = u8p(), u32p()
+        check(self._lib.rtx_batch_strands(self._h, C.byref(ps), C.byref(pk)))
+        n = self._view.n_queries
+        if not n:
+            return np.zeros(0, np.uint8), np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(ps, shape=(n,)).copy(), np.ctypeslib.as_array(pk, shape=(n,)).copy()
 
     def stage_times(self):
         ms = (C.c_float * len(_lib.STAGES))()
@@ -546,18 +563,30 @@ class Index:
 
 
 _SENDER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p)
+_INFO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32)
+
+
+def revcomp(seq: np.ndarray) -> np.ndarray:
+    """rtx_revcomp: the reverse complement of an encoded sequence as the library builds it."""
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    out = np.zeros(len(seq), dtype=np.uint8)
+    check(_lib.load().rtx_revcomp(ptr(seq, u8p), len(seq), ptr(out, u8p)))
+    return out
 
 
 def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: bool, raw_confidence: bool,
-           chunk_size: int, sender: Callable[[str, str, Optional[str]], None], tsv: bool) -> None:
+           chunk_size: int, sender: Callable[[str, str, Optional[str]], None], tsv: bool,
+           info: Optional[Callable[[str, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
-    plays the role of a closed channel."""
+    plays the role of a closed channel.  `info(label, strand, peak, t)`, if given, is called directly before the sender of the same query
+    (rtx_raxtax_multi_ex); handles built with strand="both" report the orientation with the larger peak."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
     lib.rtx_raxtax_multi.argtypes = [C.POINTER(C.c_void_p), C.c_uint32] + lib.rtx_raxtax.argtypes[1:]
+    lib.rtx_raxtax_multi_ex.argtypes = lib.rtx_raxtax_multi.argtypes + [_INFO, C.c_void_p]
     handles = list(tree) if isinstance(tree, (list, tuple)) else [tree]
     labels = (C.c_char_p * max(len(queries), 1))(*[q[0].encode() for q in queries])
     flat, off = _flatten([q[1] for q in queries])
@@ -571,7 +600,19 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if len(handles) == 1:
+    def cb_info(_ctx, label, strand, peak, t):
+        try:
+            info(label.decode(), int(strand), int(peak), int(t))
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if info is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                     int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _INFO(cb_info), None)
+    elif len(handles) == 1:
         rc = lib.rtx_raxtax(handles[0]._h, handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                             int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv))
     else:

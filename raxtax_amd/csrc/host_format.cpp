@@ -175,6 +175,17 @@ extern "C" int64_t rtx_format_query(const rtx_tree *tree, const rtx_result_view 
     return (int64_t)o.len;
 }
 
+// The reverse complement of a query as revcomp_kernel builds it (rtx_strand.hip): reversed, the four bits of every one-hot code reversed
+// (A=1 <-> T=8, C=2 <-> G=4, ambiguity codes to their complements, N stays), a byte above 15 as it is.
+extern "C" int rtx_revcomp(const uint8_t *in, uint64_t n, uint8_t *out) {
+    if ((!in || !out) && n) { rtx::set_error("rtx_revcomp: null argument"); return RTX_ERR_INVALID; }
+    for (uint64_t i = 0; i < n; i++) {
+        const uint8_t b = in[n - 1 - i];
+        out[i] = b > 15u ? b : (uint8_t)(((b & 1u) << 3) | ((b & 2u) << 1) | ((b & 4u) >> 1) | ((b & 8u) >> 3));
+    }
+    return RTX_OK;
+}
+
 // ---- compact byte record of a result view (the unit the multi-GPU gather ships, raxtax_amd/dist_util.py) ----
 //   int64[4] n_queries, n_rows, L (confidence levels per row = deepest row of the view), version (2)
 //   | int64 begin[nq] | f64 global[nq] | u32 count[nq] | u32 t[nq] | u8 status[nq]

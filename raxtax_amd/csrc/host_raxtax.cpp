@@ -78,6 +78,8 @@ LastTiming g_timing{{0, 0, 0, 0}, 0};
 
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
+// (label, strand, peak, t) of the query whose message follows (rtx_query_info_fn); empty: nobody asked
+using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t)>;
 
 // One chunk of queries travelling through the stages of run().
 struct Chunk {
@@ -87,6 +89,8 @@ struct Chunk {
     std::vector<uint8_t> differ;       // raxtax.rs:43-53: exact matches with different parents
     std::vector<uint8_t> status;       // res.status / res.t copied by the format stage: the sender must not read `res`, whose host set the
     std::vector<uint32_t> t;           // handle reuses once this chunk is formatted
+    std::vector<uint8_t> strand;       // rtx_batch_strands, copied by the device stage (both strands, or an info callback)
+    std::vector<uint32_t> peak;
     // The messages of the chunk: every formatting thread appends the NUL-terminated `.out` (and `.tsv`) text of its queries to an arena
     // of its own; msg_off[i] locates query i's text in the arena of the thread that took it (a std::string per message was a malloc in
     // the format thread and a free in the sender's, per query: half of the format stage)
@@ -134,7 +138,7 @@ struct Chunk {
 // A handle keeps two result sets, so the view of its k-th chunk stays valid until its (k + 2)-th is classified.
 int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_t n_queries, const char *const *labels,
         const uint8_t *bases, const uint64_t *base_off, bool skip_exact_matches, bool raw_confidence, uint64_t chunk_size,
-        const RawSender &sender, bool tsv) {
+        const RawSender &sender, bool tsv, const RawInfo &info = RawInfo()) {
     if (!indices || n_dev == 0 || !tree || !base_off || !labels) { rtx::set_error("rtx_raxtax: null argument"); return RTX_ERR_INVALID; }
     for (uint32_t d = 0; d < n_dev; d++) {
         if (!indices[d]) { rtx::set_error("rtx_raxtax: null index handle"); return RTX_ERR_INVALID; }
@@ -149,11 +153,19 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     const unsigned nt_lookup = rtx::host_threads(4u), nt_format = rtx::host_threads(16u, n_dev);
     std::vector<uint8_t> dev_lookup(n_dev), dev_text(n_dev);
     bool any_host_lookup = false;
+    // RTX_OPT_STRAND: every handle classifies both orientations, or none does; the exact matches then come from the device (those of a
+    // reverse complement belong to the same lookup) and the text from the host (the device formats the given orientation only)
+    const bool both = rtx::index_strand(indices[0]);
+    for (uint32_t d = 0; d < n_dev; d++) {
+        if (rtx::index_strand(indices[d]) != both) { rtx::set_error("rtx_raxtax_multi: the handles disagree on RTX_OPT_STRAND"); return RTX_ERR_INVALID; }
+        if (both && !rtx_index_has_exact_lookup(indices[d])) { rtx::set_error("RTX_OPT_STRAND needs the exact-match lookup of the device (a handle built from the reference sequences)"); return RTX_ERR_STATE; }
+    }
+    const bool want_strands = both || (bool)info;
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
         // RTX_OPT_DEVICE_TEXT: the messages come from the device (rtx_text.hip), set up for this tree and these flags
-        dev_text[d] = rtx::index_device_text(indices[d]);
+        dev_text[d] = rtx::index_device_text(indices[d]) && !both;
         if (dev_text[d]) {
             const int rc = rtx_index_text_setup(indices[d], tree, flags | (tsv ? RTX_TEXT_TSV : 0u));
             if (rc) return rc;
@@ -301,6 +313,15 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     ch.exact_ids.assign(xi, xi + xo[ch.nq]);
                 }
             }
+            if (!rc && want_strands) {
+                const uint8_t *st = nullptr;
+                const uint32_t *pk = nullptr;
+                rc = rtx_batch_strands(indices[d], &st, &pk);
+                if (!rc) {
+                    ch.strand.assign(st, st + ch.nq);
+                    ch.peak.assign(pk, pk + ch.nq);
+                }
+            }
             if (rc) { fail(rc, rtx_last_error()); return; }
             busy_device[d] += now() - t_d0;
             set_stage(c, 2);
@@ -343,6 +364,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     Chunk &c; unsigned r; Chunk::Arena &o, *t;
                     ~Back() { c.out_arena[r] = std::move(o); if (t) c.tsv_arena[r] = std::move(*t); }
                 } back{ch, r, oa, ta};
+                std::vector<uint8_t> rc_seq;  // a minus-strand query prints the orientation that was classified (the `.tsv` sequence column)
                 // The rows of a view lie in the PROCESSING order of the batch and the queries are formatted in input order: every row array
                 // (confidences: 256 bytes per row, lineage, depth, local signal) and the lineage string are cache misses per query -- what
                 // the stage waited for (0.6 us per query on sixteen threads where the arithmetic needs 0.2).  Three prefetch stages ahead of
@@ -400,7 +422,13 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     char *tb = ta ? ta->room(need + rows * len) : nullptr;
                     if (!ob || (ta && !tb)) { rc_fmt = RTX_ERR_OOM; return; }
                     int64_t tsv_len = 0;
-                    const int64_t n = rtx_format_query(tree, &ch.res, i, labels[q], bases + base_off[q], len,
+                    const uint8_t *seq = bases + base_off[q];
+                    if (tb && both && ch.strand[i]) {
+                        rc_seq.resize(len + 1);
+                        (void)rtx_revcomp(seq, len, rc_seq.data());
+                        seq = rc_seq.data();
+                    }
+                    const int64_t n = rtx_format_query(tree, &ch.res, i, labels[q], seq, len,
                                                        ch.exact_ids.data() + ch.exact_off[i], ne, flags, ob, need,
                                                        tb, tb ? need + rows * len : 0, &tsv_len);
                     if (n < 0) { rc_fmt = (int)n; return; }
@@ -441,6 +469,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 continue;
             }
             bool ok;
+            if (info && !info(labels[q], ch.strand[i], ch.peak[i], ch.t[i])) { closed = true; break; }
             if (dev_text[c % n_dev]) {
                 ok = sender(labels[q], ch.text.out + ch.text.out_off[i], tsv ? ch.text.tsv + ch.text.tsv_off[i] : nullptr);
             } else {
@@ -455,6 +484,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint8_t>().swap(ch.differ);
         std::vector<uint8_t>().swap(ch.status);
         std::vector<uint32_t>().swap(ch.t);
+        std::vector<uint8_t>().swap(ch.strand);
+        std::vector<uint32_t>().swap(ch.peak);
         {
             std::lock_guard<std::mutex> g(pool_mu);
             for (auto &a : ch.out_arena) arena_pool.push_back(std::move(a));
@@ -511,9 +542,8 @@ extern "C" int rtx_raxtax(rtx_index *index, const rtx_tree *tree, uint64_t n_que
                           const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches, int raw_confidence,
                           uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv) {
     if (!sender) { rtx::set_error("rtx_raxtax: null sender"); return RTX_ERR_INVALID; }
-    RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
-    return run(&index, 1, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
-               tsv != 0);
+    return rtx_raxtax_multi_ex(&index, 1, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender, sender_ctx,
+                               tsv, nullptr, nullptr);
 }
 
 // The same over several device handles (one per GPU, or several on one): the reference's parallel driver is one call inside the
@@ -522,10 +552,21 @@ extern "C" int rtx_raxtax(rtx_index *index, const rtx_tree *tree, uint64_t n_que
 extern "C" int rtx_raxtax_multi(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
                                 const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                                 int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv) {
+    return rtx_raxtax_multi_ex(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender,
+                               sender_ctx, tsv, nullptr, nullptr);
+}
+
+// ... with `info` called directly before the sender for every query that has a message: its label, strand, peak and t
+extern "C" int rtx_raxtax_multi_ex(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                   const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                   int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                   rtx_query_info_fn info, void *info_ctx) {
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
+    RawInfo fi;
+    if (info) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t) { return info(info_ctx, label, strand, peak, t) == 0; };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
-               tsv != 0);
+               tsv != 0, fi);
 }
 
 extern "C" int rtx_raxtax_last_timing(double busy[4], uint64_t *n_chunks) {

@@ -522,6 +522,10 @@ int alloc_final(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries) {
     if ((rc = r.d_fin_t.alloc(n_queries)) || (rc = r.d_fin_status.alloc(n_queries)) || (rc = r.d_fin_gs.alloc(n_queries)) ||
         (rc = r.d_fin_row_begin.alloc(n_queries)) || (rc = r.d_fin_row_count.alloc(n_queries)) || (rc = r.d_fin_cursor.alloc(2)))
         return rc;
+    if ((rc = r.d_peak2.alloc(n_queries)) || (rc = r.d_peak.alloc(n_queries)) || (rc = r.d_strand.alloc(n_queries))) return rc;  // (rtx_strand.hip)
+    if (ix->strand_opt && ((rc = r.d_sel_t.alloc(n_queries)) || (rc = r.d_sel_status.alloc(n_queries)) || (rc = r.d_sel_gs.alloc(n_queries)) ||
+                           (rc = r.d_sel_row_begin.alloc(n_queries)) || (rc = r.d_sel_row_count.alloc(n_queries))))
+        return rc;
     const uint64_t rows = r.arena_cap, D = ix->fin_D;
     if ((rc = r.d_fin_lineage.alloc(rows)) || (rc = r.d_fin_node.alloc(rows)) || (rc = r.d_fin_depth.alloc(rows)) || (rc = r.d_fin_depth8.alloc(rows)) ||
         (rc = r.d_fin_local.alloc(rows)) || (rc = r.d_fin_conf.alloc(rows * D)) || (rc = r.d_fin_hund.alloc(rows * D)))
@@ -648,6 +652,8 @@ int order_batch(rtx_index *ix, bool cluster) {
 void record_batch(rtx_index *ix) {
     rtx_index::ResultSet &r = ix->res();
     r.n_q = ix->n_q;
+    r.n_user = ix->strand_used ? ix->n_user : ix->n_q;
+    r.has_peak = false;
     r.n_sub = ix->n_sub_total();
     r.n_side = 0;
     for (uint32_t c = 0; c < ix->n_cls; c++)
@@ -875,6 +881,10 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
             b.s = ix->stream2;
             RTX_HIP(hipStreamWaitEvent(b.s, ix->ev_front[sb], 0));
         }
+        {   // the peak of every query of the sub-batch, from the histogram the probability stage is about to read (rtx_strand.hip)
+            const rtx_index::Scratch &sc = ix->sc[b.set];
+            launch_peak(b.s, PeakParams{sc.d_hist.p, b.cls->hstride, sc.d_t.p, b.q0, r.d_perm.p, b.nq, r.d_peak2.p});
+        }
         if ((rc = enqueue_prob_prefix(ix, b, fuse))) return rc;
         if (!fuse && (rc = enqueue_walk(ix, b, ix->sc[b.set].d_prefix.p, b.s))) return rc;
         if (fuse && b.timed_all) {  // keeps rtx_batch_stage_times whole: an empty interval
@@ -905,6 +915,16 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
         int rc_f = r.h_flags.resize(1);
         if (rc_f) return rc_f;
         const hipStream_t fs = ra ? ix->stream2 : ix->stream;  // (run-ahead: behind the last back half -- every front half lies before it)
+        {   // strand and peak of the caller's queries; under RTX_OPT_STRAND the final fields of the chosen orientation (rtx_strand.hip)
+            const bool both = r.n_user != r.n_q;
+            if (both && (r.n_q != 2u * r.n_user || !r.d_sel_t.p || r.d_sel_t.n < r.n_user)) { set_error("internal: a batch of both strands without its twins"); return RTX_ERR_STATE; }
+            launch_strand_select(fs, StrandParams{(uint32_t)r.n_user, both ? 1u : 0u, r.d_peak2.p, r.d_fin_status.p, r.d_fin_t.p, r.d_fin_gs.p, r.d_fin_row_begin.p,
+                                                  r.d_fin_row_count.p, r.d_strand.p, r.d_peak.p, r.d_sel_status.p, r.d_sel_t.p, r.d_sel_gs.p, r.d_sel_row_begin.p,
+                                                  r.d_sel_row_count.p});
+            if (!r.ev_select) RTX_HIP(hipEventCreateWithFlags(&r.ev_select, hipEventDisableTiming));
+            RTX_HIP(hipEventRecord(r.ev_select, fs));
+            r.has_peak = true;
+        }
         RTX_HIP(hipMemcpyAsync(r.h_flags.data(), r.d_flags.p, 4, hipMemcpyDeviceToHost, fs));
         if (!r.ev_flags) RTX_HIP(hipEventCreateWithFlags(&r.ev_flags, hipEventDisableTiming));
         RTX_HIP(hipEventRecord(r.ev_flags, fs));
@@ -1043,7 +1063,7 @@ int prepare_workspace(rtx_index *ix, uint64_t n_queries, const uint64_t cls_n_in
     const uint64_t key[14] = {n_queries, cn[0], cn[1], cn[2] << 32 | cn[3], cn[4], cm[0], cm[1], cm[2] << 32 | cm[3], cm[4], ix->sub_batch_req,
                               (uint64_t)ix->packed_opt | (uint64_t)ix->pair_opt << 1 | (uint64_t)ix->pruning() << 2 | (uint64_t)ix->shard_prune_opt << 3 | (uint64_t)ix->fine_opt << 4 |
                                   (uint64_t)(ix->prob_mode & 3) << 5 | (uint64_t)ix->rec_opt << 8 | (uint64_t)ix->overlap_opt << 16 | (uint64_t)ix->min_subs << 20,
-                              (uint64_t)ix->n_bnd_local, ix->shared_device ? 1u : 0u, 0};
+                              (uint64_t)ix->n_bnd_local, ix->shared_device ? 1u : 0u, ix->strand_opt};
     // A batch of the shape of the last one under the same options (the chunks of rtx_raxtax): everything below would come out the same --
     // and hipMemGetInfo alone costs a good part of a millisecond between two chunks, with the device idle
     if (ix->ws_valid && std::memcmp(key, ix->ws_key, sizeof key) == 0 && !ix->staged) {
@@ -1076,6 +1096,7 @@ int prepare_workspace(rtx_index *ix, uint64_t n_queries, const uint64_t cls_n_in
 // One class whatever the lengths: reference shards (rtx_shard_*: one row stride for the exchange buffers), rtx_debug_evaluate.
 int prepare_workspace_single(rtx_index *ix, uint64_t n_queries, uint64_t tmax, uint64_t max_len) {
     ix->ws_valid = false;
+    ix->strand_used = false;
     tmax = std::min<uint64_t>(tmax, 65535);  // (shape_class)
     ix->n_cls = 1;
     for (int c = 0; c < 4; c++) ix->key_lim[c] = ~0ull;
@@ -1220,6 +1241,14 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
         set_error("rtx_batch_upload: invalid argument");
         return RTX_ERR_INVALID;
     }
+    // RTX_OPT_STRAND: the activation appends the reverse complement of every query (rtx_strand.hip); room for the twins is made here
+    const bool both = ix->strand_opt != 0u;
+    if (both) {
+        if (exact_off || exact_ids) { set_error("RTX_OPT_STRAND: exact-match ids cannot be passed in (those of the reverse complements must come from the same lookup: pass NULL)"); return RTX_ERR_INVALID; }
+        if (!rtx_index_has_exact_lookup(ix) || ix->n_refs != ix->n_total) { set_error("RTX_OPT_STRAND needs the exact-match lookup of the device (a handle built from the reference sequences, RTX_OPT_DEVICE_EXACT on)"); return RTX_ERR_STATE; }
+        if (n_queries > 0x7FFFFFFFull) { set_error("RTX_OPT_STRAND: too many queries in one batch"); return RTX_ERR_INVALID; }
+    }
+    const uint64_t n_dev = both ? 2 * n_queries : n_queries;  // queries of the batch on the device
     if (!ix->h2d_stream) RTX_HIP(hipStreamCreateWithFlags(&ix->h2d_stream, hipStreamNonBlocking));
     if (!in.ready) RTX_HIP(hipEventCreateWithFlags(&in.ready, hipEventDisableTiming));
     if (in.recorded) RTX_HIP(hipEventSynchronize(in.ready));  // the last transfer out of this set's pinned buffers (long done, as a rule)
@@ -1251,7 +1280,7 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
     }
     const uint64_t n_packed = (total + 1) / 2;
     if ((rc = in.h_packed.resize(total + 64)) || (rc = in.h_base_off.resize(n_queries + 1)) || (rc = in.d_packed.alloc(total + 64)) ||
-        (rc = in.d_base_off.alloc(n_queries + 1)) || (rc = in.d_exact_off.alloc(n_queries + 1)) || (rc = in.d_exact_ids.alloc(n_exact + 1)))
+        (rc = in.d_base_off.alloc(n_dev + 1)) || (rc = in.d_exact_off.alloc(n_dev + 1)) || (rc = in.d_exact_ids.alloc(n_exact + 1)))
         return rc;
     for (uint64_t q = 0; q <= n_queries; q++) in.h_base_off[q] = base_off[q] - base_off[0];
     // two bases per byte; a byte above 15 is no code of parser.rs:11-34 -- such a batch travels as it is (the kernels see the caller's bytes)
@@ -1266,14 +1295,15 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
         RTX_HIP(hipMemcpyAsync(in.d_exact_off.p, in.h_exact_off.data(), (n_queries + 1) * 8, hipMemcpyHostToDevice, ix->h2d_stream));
         if (n_exact) RTX_HIP(hipMemcpyAsync(in.d_exact_ids.p, in.h_exact_ids.data(), n_exact * 4, hipMemcpyHostToDevice, ix->h2d_stream));
     } else {
-        RTX_HIP(hipMemsetAsync(in.d_exact_off.p, 0, (n_queries + 1) * 8, ix->h2d_stream));
+        RTX_HIP(hipMemsetAsync(in.d_exact_off.p, 0, (n_dev + 1) * 8, ix->h2d_stream));
     }
     RTX_HIP(hipEventRecord(in.ready, ix->h2d_stream));
     in.recorded = true;
-    in.n_q = n_queries;
+    in.n_q = n_dev;
+    in.n_user = n_queries;
     in.total = total;
     in.max_len = max_len;
-    for (int c = 0; c < 5; c++) { in.cls_n[c] = cls_n[c]; in.cls_max[c] = cls_max[c]; }
+    for (int c = 0; c < 5; c++) { in.cls_n[c] = both ? 2 * cls_n[c] : cls_n[c]; in.cls_max[c] = cls_max[c]; }  // (a twin has the length of its query)
     in.n_exact = n_exact;
     in.has_exact = exact_off != nullptr;
     in.has_labels = with_labels;
@@ -1290,8 +1320,10 @@ int rtx_batch_activate(rtx_index *ix) {
     if (!in.staged) { set_error("rtx_batch_activate without a staged batch (rtx_batch_prefetch)"); return RTX_ERR_STATE; }
     ix->uploaded = ix->ran = ix->synced = false;
     if ((rc = prepare_workspace(ix, in.n_q, in.cls_n, in.cls_max))) return rc;
-    ix->sum_query_bytes = in.total;
-    if ((rc = ix->d_bases.alloc(in.total + 64))) return rc;
+    const bool both = in.n_q != in.n_user;  // staged under RTX_OPT_STRAND (setting the option drops what was staged)
+    const uint64_t total_dev = both ? 2 * in.total : in.total;
+    ix->sum_query_bytes = total_dev;
+    if ((rc = ix->d_bases.alloc(total_dev + 64))) return rc;
     RTX_HIP(hipStreamWaitEvent(ix->stream, in.ready, 0));
     if (in.packed) {
         rtx::launch_unpack_nibbles(ix->stream, in.d_packed.p, ix->d_bases.p, in.total, in.total + 64);
@@ -1299,6 +1331,12 @@ int rtx_batch_activate(rtx_index *ix) {
         RTX_HIP(hipMemcpyAsync(ix->d_bases.p, in.d_packed.p, in.total, hipMemcpyDeviceToDevice, ix->stream));
         RTX_HIP(hipMemsetAsync(ix->d_bases.p + in.total, 0, 64, ix->stream));
     }
+    if (both) {  // query n + q = the reverse complement of query q; from here on the batch is 2 n queries for every stage
+        rtx::launch_revcomp(ix->stream, ix->d_bases.p, in.d_base_off.p, (uint32_t)in.n_user, in.total);
+        RTX_HIP(hipMemsetAsync(ix->d_bases.p + total_dev, 0, 64, ix->stream));
+    }
+    ix->strand_used = both;
+    ix->n_user = in.n_user;
     ix->dev_exact_used = !in.has_exact && ix->dev_exact_opt && ix->d_em_table.p && ix->n_refs == ix->n_total;
     if (ix->dev_exact_used && (rc = ix->res().d_exact_grp.alloc(in.n_q))) return rc;
     if (!ix->ev_activated) RTX_HIP(hipEventCreateWithFlags(&ix->ev_activated, hipEventDisableTiming));

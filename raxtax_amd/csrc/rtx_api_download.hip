@@ -39,7 +39,7 @@ int node_tables(rtx_index *ix) {
 static int size_host_results(rtx_index *ix, rtx_index::HostRes &hr, uint64_t nq, uint64_t rows, uint64_t keep) {
     int rc;
     if ((rc = hr.h_t.resize(nq)) || (rc = hr.h_status.resize(nq)) || (rc = hr.h_gs.resize(nq)) || (rc = hr.v_row_begin.resize(nq)) ||
-        (rc = hr.v_row_count.resize(nq)))
+        (rc = hr.v_row_count.resize(nq)) || (rc = hr.h_strand.resize(nq)) || (rc = hr.h_peak.resize(nq)))
         return rc;
     const uint64_t D = ix->fin_D;
     if ((rc = hr.v_row_lineage.grow_keep(rows, keep)) || (rc = hr.v_row_node.grow_keep(rows, keep)) || (rc = hr.v_row_depth.grow_keep(rows, keep)) ||
@@ -63,13 +63,27 @@ static int copy_rows(rtx_index *ix, const rtx_index::ResultSet &r, rtx_index::Ho
     return RTX_OK;
 }
 // ... and of the per-query fields (input order: complete when the last sub-batch has been finalised)
+// Under RTX_OPT_STRAND (r.n_user queries, r.n_q = twice as many on the device) they are those of the chosen orientation, gathered by
+// strand_select_kernel; strand and peak come with them either way (rtx_batch_strands).
 static int copy_queries(const rtx_index::ResultSet &r, rtx_index::HostRes &hr, hipStream_t cs) {
-    const uint64_t nq = r.n_q;
-    RTX_HIP(hipMemcpyAsync(hr.h_t.data(), r.d_fin_t.p, nq * 4, hipMemcpyDeviceToHost, cs));
-    RTX_HIP(hipMemcpyAsync(hr.h_status.data(), r.d_fin_status.p, nq, hipMemcpyDeviceToHost, cs));
-    RTX_HIP(hipMemcpyAsync(hr.h_gs.data(), r.d_fin_gs.p, nq * 8, hipMemcpyDeviceToHost, cs));
-    RTX_HIP(hipMemcpyAsync(hr.v_row_begin.data(), r.d_fin_row_begin.p, nq * 8, hipMemcpyDeviceToHost, cs));
-    RTX_HIP(hipMemcpyAsync(hr.v_row_count.data(), r.d_fin_row_count.p, nq * 4, hipMemcpyDeviceToHost, cs));
+    const uint64_t nq = r.n_user;
+    const bool both = r.n_user != r.n_q;
+    hr.n_user = nq;
+    hr.both = both;
+    if (r.has_peak) RTX_HIP(hipStreamWaitEvent(cs, r.ev_select, 0));
+    else if (both) { set_error("internal: a batch of both strands without its selection"); return RTX_ERR_STATE; }
+    RTX_HIP(hipMemcpyAsync(hr.h_t.data(), both ? r.d_sel_t.p : r.d_fin_t.p, nq * 4, hipMemcpyDeviceToHost, cs));
+    RTX_HIP(hipMemcpyAsync(hr.h_status.data(), both ? r.d_sel_status.p : r.d_fin_status.p, nq, hipMemcpyDeviceToHost, cs));
+    RTX_HIP(hipMemcpyAsync(hr.h_gs.data(), both ? r.d_sel_gs.p : r.d_fin_gs.p, nq * 8, hipMemcpyDeviceToHost, cs));
+    RTX_HIP(hipMemcpyAsync(hr.v_row_begin.data(), both ? r.d_sel_row_begin.p : r.d_fin_row_begin.p, nq * 8, hipMemcpyDeviceToHost, cs));
+    RTX_HIP(hipMemcpyAsync(hr.v_row_count.data(), both ? r.d_sel_row_count.p : r.d_fin_row_count.p, nq * 4, hipMemcpyDeviceToHost, cs));
+    if (r.has_peak) {
+        RTX_HIP(hipMemcpyAsync(hr.h_strand.data(), r.d_strand.p, nq, hipMemcpyDeviceToHost, cs));
+        RTX_HIP(hipMemcpyAsync(hr.h_peak.data(), r.d_peak.p, nq * 4, hipMemcpyDeviceToHost, cs));
+    } else {  // (a staged run, rtx_debug_evaluate: no peak was taken)
+        std::memset(hr.h_strand.data(), 0, nq);
+        std::memset(hr.h_peak.data(), 0, nq * 4);
+    }
     return RTX_OK;
 }
 // The flags of a run and the arena cursor of its bulk, once its streams have drained
@@ -240,7 +254,7 @@ static int download_impl(rtx_index *ix, rtx_result_view *out, bool then_run, uin
     if (rc) return rc;
     if (!ix->ran || !out) { set_error("rtx_batch_download before rtx_batch_run"); return RTX_ERR_STATE; }
     rtx_index::ResultSet &r = ix->res();  // the batch that ran last (a run-ahead below moves the handle on to the other set)
-    const uint64_t nq = r.n_q;
+    const uint64_t nq = r.n_q, n_user = r.n_user;  // (read now: a batch that this call enqueues behind the download records itself in the same set)
     ix->res_set ^= 1u;
     rtx_index::HostRes &hr = ix->host_res[ix->res_set];
     ix->host_text[ix->res_set].valid = false;
@@ -288,8 +302,8 @@ static int download_impl(rtx_index *ix, rtx_result_view *out, bool then_run, uin
         if ((rc = fetch_exact_groups(ix, r))) return rc;
         if (then_run && (rc = run_staged(ix, next_flags, &ran_next))) return rc;
     }
-    out->n_queries = (uint32_t)nq;
-    out->n_rows = nrows;
+    out->n_queries = (uint32_t)n_user;  // (under RTX_OPT_STRAND: the caller's queries, each with the fields of its chosen orientation)
+    out->n_rows = nrows;               // the length of the row arrays: the rows of the orientation that lost stay in them, unreferenced
     out->t = hr.h_t.data();
     out->status = hr.h_status.data();
     out->global_signal = hr.h_gs.data();
@@ -319,23 +333,37 @@ int rtx_index_has_exact_lookup(const rtx_index *index) { return index && index->
 int rtx_batch_exact_matches(rtx_index *ix, const uint64_t **exact_off, const uint32_t **exact_ids) {
     if (!ix || !exact_off || !exact_ids) { set_error("null argument"); return RTX_ERR_INVALID; }
     rtx_index::HostExact &hx = ix->host_exact[ix->res_set];
+    const rtx_index::HostRes &hres = ix->host_res[ix->res_set];
     if (!hx.valid) { set_error("rtx_batch_exact_matches: the last download has no device lookup (ids were passed in, or no table)"); return RTX_ERR_STATE; }
     if (!hx.csr_valid) {
-        const size_t nq = hx.grp.size();
+        // under RTX_OPT_STRAND the groups hold the twins' as well: a query reports those of its chosen orientation
+        const bool both = hres.both && hx.grp.size() == 2 * hres.n_user;
+        const size_t nq = both ? hres.n_user : hx.grp.size();
+        auto group = [&](size_t q) { return hx.grp[both && hres.h_strand[q] ? q + nq : q]; };
         hx.off.assign(nq + 1, 0);
         for (size_t q = 0; q < nq; q++) {
-            const uint32_t g = hx.grp[q];
+            const uint32_t g = group(q);
             hx.off[q + 1] = hx.off[q] + (g == 0xFFFFFFFFu ? 0u : ix->h_em_goff[g + 1] - ix->h_em_goff[g]);
         }
         hx.ids.resize(hx.off[nq] + 1);
         for (size_t q = 0; q < nq; q++) {
-            const uint32_t g = hx.grp[q];
+            const uint32_t g = group(q);
             if (g != 0xFFFFFFFFu) std::copy(ix->h_em_gids.begin() + ix->h_em_goff[g], ix->h_em_gids.begin() + ix->h_em_goff[g + 1], hx.ids.begin() + hx.off[q]);
         }
         hx.csr_valid = true;
     }
     *exact_off = hx.off.data();
     *exact_ids = hx.ids.data();
+    return RTX_OK;
+}
+
+// Strand (0 plus, 1 minus) and peak of every query of the last download (rtx_strand.hip)
+int rtx_batch_strands(rtx_index *ix, const uint8_t **strand, const uint32_t **peak) {
+    if (!ix || (!strand && !peak)) { set_error("rtx_batch_strands: null argument"); return RTX_ERR_INVALID; }
+    const rtx_index::HostRes &hr = ix->host_res[ix->res_set];
+    if (hr.h_strand.empty() || hr.h_peak.empty() || hr.h_strand.size() < hr.n_user) { set_error("rtx_batch_strands before a download"); return RTX_ERR_STATE; }
+    if (strand) *strand = hr.h_strand.data();
+    if (peak) *peak = hr.h_peak.data();
     return RTX_OK;
 }
 

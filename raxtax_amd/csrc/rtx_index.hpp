@@ -164,6 +164,9 @@ struct rtx_index {
     DevBuf<uint8_t> d_bnd_bits;
     // ---- exact-match lookup on the device (rtx_exact.hip): the distinct reference sequences ("groups") in a hash table
     uint32_t dev_exact_opt = 1;       // RTX_OPT_DEVICE_EXACT
+    uint32_t strand_opt = 0;          // RTX_OPT_STRAND: 1 = every query is classified in both orientations (rtx_strand.hip)
+    bool strand_used = false;         // ... the activated batch holds the twins (queries n_user .. n_q - 1)
+    uint64_t n_user = 0;              // queries of the activated batch as the caller passed them
     uint32_t em_groups = 0, em_bits = 0;
     uint64_t em_hash_mask = ~0ull;    // RTX_DEFAULT_EXACT_HASH_MASK at creation (tests: a weak hash, so that probes collide)
     DevBuf<uint2> d_em_table;         // [2^em_bits] {tag, group + 1}
@@ -247,6 +250,7 @@ struct rtx_index {
         PinBuf<uint64_t> h_base_off, h_exact_off;
         PinBuf<uint32_t> h_exact_ids;
         uint64_t n_q = 0, total = 0, max_len = 0, n_exact = 0;
+        uint64_t n_user = 0;  // queries as the caller passed them: n_q, or half of it under RTX_OPT_STRAND (n_q counts the twins the activation appends; total does not)
         uint64_t cls_n[5] = {0, 0, 0, 0, 0}, cls_max[5] = {0, 0, 0, 0, 0};  // queries and longest query per length class (length_class)
         bool packed = true, has_exact = false, staged = false, recorded = false;
         // the labels of the batch (rtx_batch_prefetch_labels, staged before the bases: labels_pending becomes has_labels at the prefetch)
@@ -366,6 +370,16 @@ struct rtx_index {
         uint64_t fin_cap = 0;
         DevBuf<uint32_t> d_perm, d_iperm;  // the processing order (rtx_cluster.hip): perm[position] = query, iperm[query] = position
         DevBuf<uint32_t> d_exact_grp;      // [n_q] group of every query of the batch (0xFFFFFFFF: none)
+        // rtx_strand.hip: the peak of every query of the batch (peak_kernel, per sub-batch), and behind the last sub-batch the strand and the peak of
+        // the caller's queries (strand_select_kernel) -- under RTX_OPT_STRAND with the final per-query fields of the chosen orientation, which the
+        // download copies in the place of d_fin_*.  (Not part of bytes(): a few bytes per query that the reported figure never held.)
+        DevBuf<uint32_t> d_peak2, d_peak, d_sel_t, d_sel_row_count;
+        DevBuf<uint8_t> d_strand, d_sel_status;
+        DevBuf<double> d_sel_gs;
+        DevBuf<unsigned long long> d_sel_row_begin;
+        hipEvent_t ev_select = nullptr;    // behind strand_select_kernel
+        uint64_t n_user = 0;               // queries as the caller passed them (n_q counts the twins as well)
+        bool has_peak = false;             // the run filled d_peak2 (enqueue_batch; not a staged run or rtx_debug_evaluate)
         hipEvent_t ev_exact = nullptr;     // behind exact_match_kernel of the run: the download fetches the groups at its START, beside the kernels, not at its tail
         PinBuf<uint32_t> h_flags;          // the run's flags (d_flags), copied behind its last kernel: the download reads them without a round trip of its own
         hipEvent_t ev_flags = nullptr;     // ... behind that copy
@@ -391,6 +405,7 @@ struct rtx_index {
             for (auto e : ev_sub) (void)hipEventDestroy(e);
             if (ev_exact) (void)hipEventDestroy(ev_exact);
             if (ev_flags) (void)hipEventDestroy(ev_flags);
+            if (ev_select) (void)hipEventDestroy(ev_select);
         }
     } rs[2];
     uint32_t rs_w = 0;  // the set the batch being enqueued writes (after a run: that run's)
@@ -410,6 +425,10 @@ struct rtx_index {
         PinBuf<double> h_gs;
         PinBuf<unsigned long long> v_row_begin;  // by query; the rows themselves are in processing order
         PinBuf<uint32_t> v_row_count;
+        PinBuf<uint8_t> h_strand;  // rtx_batch_strands
+        PinBuf<uint32_t> h_peak;
+        uint64_t n_user = 0;       // queries of the view
+        bool both = false;         // the download ran under RTX_OPT_STRAND: the exact matches are those of the chosen orientation
     } host_res[2];
     uint32_t res_set = 0;
     PinBuf<uint32_t> h_nrows_all;

@@ -72,6 +72,44 @@ void launch_exact_match(hipStream_t s, const ExactParams &p);
 void launch_unpack_nibbles(hipStream_t s, const uint8_t *packed, uint8_t *bases, uint64_t n_bases, uint64_t n_out);
 bool pack_nibbles_mt(const uint8_t *in, uint64_t n, uint8_t *out, unsigned nt);
 
+// rtx_strand.hip: both-strand mode (RTX_OPT_STRAND) and the peak of every query
+// complement of a one-hot code: the four bits reversed (A=1 <-> T=8, C=2 <-> G=4, ambiguity codes to their complements, N = 15 stays);
+// a byte above 15 is no code of parser.rs:11-34 and stays as it is
+__host__ __device__ inline uint8_t complement_code(uint8_t b) {
+    return b > 15u ? b : (uint8_t)(((b & 1u) << 3) | ((b & 2u) << 1) | ((b & 4u) >> 1) | ((b & 8u) >> 3));
+}
+// the reverse complement of every query of the batch appended behind it: query n + q is the twin of q.  bases holds total bytes and has room
+// for 2 total + 64; base_off holds n + 1 entries (base_off[n] = total) and has room for 2 n + 1
+void launch_revcomp(hipStream_t s, uint8_t *bases, uint64_t *base_off, uint32_t n, uint64_t total);
+struct PeakParams {
+    const uint32_t *hist;  // [nq][hstride] the histogram of prob.rs:13-19 as hit_count left it (behind RTX_SKIP_EXACT_MATCHES, bin 0 = every count up to the threshold)
+    uint32_t hstride;
+    const uint32_t *t;     // [nq]
+    uint64_t q0;
+    const uint32_t *perm;
+    uint32_t nq;
+    uint32_t *peak;        // [n_q] by query: the highest non-empty bin above 0 (0: no reference shares a k-mer)
+};
+void launch_peak(hipStream_t s, const PeakParams &p);
+struct StrandParams {
+    uint32_t n;            // queries as the caller passed them
+    uint32_t both;         // 1: queries n .. 2 n - 1 are the twins
+    const uint32_t *peak2; // [n or 2 n] launch_peak
+    const uint8_t *status; // the final per-query fields (finalise_kernel), [n or 2 n]
+    const uint32_t *t;
+    const double *gs;
+    const unsigned long long *row_begin;
+    const uint32_t *row_count;
+    uint8_t *strand;       // [n] 0 plus, 1 minus: minus if the twin's peak is strictly larger
+    uint32_t *peak;        // [n] of the chosen orientation; an orientation whose status is not RTX_Q_OK has peak 0
+    uint8_t *o_status;     // [n] the fields of the chosen orientation (both only)
+    uint32_t *o_t;
+    double *o_gs;
+    unsigned long long *o_row_begin;
+    uint32_t *o_row_count;
+};
+void launch_strand_select(hipStream_t s, const StrandParams &p);
+
 struct KmerParams {
     const uint8_t *bases;
     const uint64_t *base_off;

@@ -185,6 +185,7 @@ int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r) {
     rtx_index::HostText &ht = ix->host_text[ix->res_set];
     ht.valid = false;
     if (!ix->text_on || !in.has_labels || in.n_labels != nq) return RTX_OK;
+    if (r.n_user != r.n_q) return RTX_OK;  // RTX_OPT_STRAND: no device text (the host formats the chosen orientation)
     TextParams p{};
     p.src = TextSrc{ix->d_lin_bytes.p, ix->d_lin_off.p, ix->d_lin_depth.p, r.d_fin_lineage.p, r.d_fin_depth8.p, r.d_fin_hund.p,
                     r.d_fin_local.p, ix->fin_D};
@@ -288,6 +289,7 @@ int rtx_batch_prefetch_labels(rtx_index *ix, uint64_t n_queries, const char *con
 int rtx_batch_text(rtx_index *ix, rtx_text_view *out) {
     if (!ix || !out) { set_error("rtx_batch_text: null argument"); return RTX_ERR_INVALID; }
     const rtx_index::HostText &ht = ix->host_text[ix->res_set];
+    if (!ht.valid && ix->host_res[ix->res_set].both) { set_error("rtx_batch_text: no device text under RTX_OPT_STRAND (format the view on the host: rtx_format_query)"); return RTX_ERR_STATE; }
     if (!ht.valid) { set_error("rtx_batch_text: the last download has no text (rtx_index_text_setup, then labels with the batch: rtx_batch_prefetch_labels)"); return RTX_ERR_STATE; }
     out->n_queries = ht.nq;
     out->out = ht.out.data();

@@ -88,7 +88,7 @@ def unpack_records(buf: np.ndarray) -> dict:
     # into query order
     row_off = np.zeros(n_q + 1, dtype=np.int64)
     row_off[1:] = np.cumsum(count)
-    src = np.repeat(begin - row_off[:-1], count) + np.arange(n_rows)
+    src = np.repeat(begin - row_off[:-1], count) + np.arange(int(count.sum()))   # (a view of both strands holds rows that no query refers to)
     lineage, depth, conf, local = lineage[src], depth[src], conf[src], local[src]
     return dict(n_queries=n_q, n_rows=n_rows, row_off=row_off, global_signal=gs, t=t, status=status, row_lineage=lineage,
                 row_depth=depth, row_conf=conf, row_local_signal=local)
