@@ -37,7 +37,9 @@ extern "C" {
                              5: rtx_result_view grows row_conf_stride, row_depth_u8, row_conf_hundredths (the rows are finalised on the device and
                                 arrive in their final layout: row_conf is [n_rows][row_conf_stride], no longer [n_rows][RTX_MAX_DEPTH]); the exports
                                 and options of round 5 (rtx_index_self_sample, rtx_records_format, options 18-22);
-                             6: RTX_OPT_RUN_AHEAD (23), RTX_RETRY_CHUNK from rtx_batch_download_then_run under it, rtx_index_run_ahead_stats */
+                             6: RTX_OPT_RUN_AHEAD (23), RTX_RETRY_CHUNK from rtx_batch_download_then_run under it, rtx_index_run_ahead_stats
+                                (still 6 with RTX_OPT_NEAREST (26), RTX_NO_REF, rtx_batch_nearest and rtx_raxtax_multi_ex2: exports and an option
+                                that is off by default, nothing that exists changes shape) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -291,6 +293,14 @@ int rtx_index_set_batch(rtx_index *index, uint32_t sub_batch);
                                       * RTX_ERR_STATE), not available on a reference shard (RTX_ERR_INVALID) and without device text (rtx_batch_text:
                                       * RTX_ERR_STATE; rtx_raxtax formats on the host whatever RTX_OPT_DEVICE_TEXT says).  Costs at least twice the step
                                       * time.  Shapes the workspace like the options below. */
+#define RTX_OPT_NEAREST 26           /* 0 (default): nothing is launched or allocated, every output is what it is without the option.  1: every run also finds,
+                                      * per query, the NEAREST reference -- the lowest reference id (the order of the tree's lineages) whose hit count is the
+                                      * query's peak (rtx_batch_strands; the counts as the probability stage sees them, after RTX_SKIP_EXACT_MATCHES) -- and
+                                      * the number of references that share that count (ties): rtx_batch_nearest.  A query whose status is not RTX_Q_OK or
+                                      * whose peak is 0 has RTX_NO_REF and 0 ties.  Under RTX_OPT_STRAND the values are those of the chosen orientation.
+                                      * Exact on the pruned path as well.  Not available on a reference shard (RTX_ERR_INVALID); staged rtx_shard_* runs and
+                                      * rtx_debug_evaluate fill nothing.  Setting it drops the uploaded batch like the options below. */
+#define RTX_NO_REF 0xFFFFFFFFu       /* no reference (rtx_batch_nearest, rtx_query_hit_fn) */
 /* RTX_OPT_SUB_BATCH, _PACKED_COUNTS, _HIT_PAIR, _TILE_PRUNE and _PROB_MODE shape the workspace that rtx_batch_upload sizes:
  * setting one of them drops the uploaded batch (rtx_batch_run then fails with RTX_ERR_STATE until the batch is uploaded again). */
 int rtx_index_set_option(rtx_index *index, int option, uint64_t value);
@@ -386,6 +396,13 @@ int rtx_batch_strands(rtx_index *index, const uint8_t **strand, const uint32_t *
 /* The reverse complement as the device builds it, on the host: out[i] = complement(in[n - 1 - i]) (in and out must not overlap).  The formatter
  * uses it for the `.tsv` sequence column of a minus-strand query, which prints the classified orientation. */
 int rtx_revcomp(const uint8_t *in, uint64_t n, uint8_t *out);
+/* Nearest reference and ties of every query of the last download (RTX_OPT_NEAREST), [n_queries], valid as long as that download's view (each of
+ * the two host result sets keeps its own, also under RTX_OPT_RUN_AHEAD).  Either pointer may be NULL.  RTX_ERR_STATE if the run of that
+ * download had the option off. */
+int rtx_batch_nearest(rtx_index *index, const uint32_t **nearest, const uint32_t **ties);
+/* Milliseconds the kernel behind it took over the sub-batches of the last run, and its launches (RTX_OPT_STAGE_TIMING on; else 0 and 0).  Not one
+ * of the stages of rtx_batch_stage_times: RTX_NUM_STAGES is part of the ABI.  After rtx_batch_sync. */
+int rtx_batch_nearest_time(rtx_index *index, float *ms, uint32_t *launches);
 
 /* The same in stages, so that a caller (bench.py) can keep inputs resident in HBM and
  * time the device part alone, or overlap stages of different batches. */
@@ -616,6 +633,13 @@ int rtx_raxtax_multi_ex(rtx_index *const *indices, uint32_t n_indices, const rtx
                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                         rtx_query_info_fn info, void *info_ctx);
+/* rtx_raxtax_multi_ex with a callback that also receives the nearest reference of the query and its ties (RTX_OPT_NEAREST on the handles,
+ * which must agree on it: RTX_ERR_INVALID otherwise; with the option off it receives RTX_NO_REF and 0).  `hit` may be NULL. */
+typedef int (*rtx_query_hit_fn)(void *ctx, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties);
+int rtx_raxtax_multi_ex2(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_hit_fn hit, void *hit_ctx);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

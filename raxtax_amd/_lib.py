@@ -151,6 +151,9 @@ _SIGNATURES = {
     "rtx_raxtax_multi_ex": (C.c_int, None),
     "rtx_batch_strands": (C.c_int, [C.c_void_p, C.POINTER(u8p), C.POINTER(u32p)]),
     "rtx_revcomp": (C.c_int, [u8p, C.c_uint64, u8p]),
+    "rtx_raxtax_multi_ex2": (C.c_int, None),
+    "rtx_batch_nearest": (C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p)]),
+    "rtx_batch_nearest_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

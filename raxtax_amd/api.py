@@ -178,11 +178,14 @@ class Result:
     """Arrays of one classified batch, copied out of the library-owned rtx_result_view and put into query
     order (the library stores the rows in processing order): rows of query q = row_off[q] .. row_off[q+1].
     strand (0 plus, 1 minus: Index(strand="both")) and peak (the largest hit count over the references for the classified orientation)
-    per query, when the view came from a download (rtx_batch_strands), else None."""
+    per query, when the view came from a download (rtx_batch_strands), else None.  nearest (the lowest reference id whose hit count is the
+    peak, NO_REF where the peak is 0) and nearest_ties (references with that count) per query under Index(nearest=True), else None."""
 
-    def __init__(self, view: ResultView, strand: Optional[np.ndarray] = None, peak: Optional[np.ndarray] = None):
+    def __init__(self, view: ResultView, strand: Optional[np.ndarray] = None, peak: Optional[np.ndarray] = None,
+                 nearest: Optional[np.ndarray] = None, nearest_ties: Optional[np.ndarray] = None):
         nq, nr = view.n_queries, view.n_rows
         self.strand, self.peak = strand, peak
+        self.nearest, self.nearest_ties = nearest, nearest_ties
         arr = lambda p, n: (np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0))
         self.n_queries = nq
         self.t = arr(view.t, nq)
@@ -219,13 +222,16 @@ DEFAULT_SEGMENT_CLASSES = 1   # RTX_DEFAULT_SEGMENT_CLASSES of the library (rtx_
 class Index:
     """Device-resident index + batch workspace of one GPU (rtx_index)."""
 
+    nearest_on = False   # Index(nearest=True): downloads also fetch rtx_batch_nearest (the staged subclasses never set the option)
+
     def __init__(self, tree: Tree, device: int = 0, sub_batch: int = 0, prob_mode: int = 0,
                  stage_timing: bool = False, cluster: Optional[bool] = None, segment_classes=None,
                  packed_counts: Optional[bool] = None,
                  tile_skip: Optional[bool] = None, hit_pair=None, locator: Optional[bool] = None, tile_prune: Optional[bool] = None,
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
-                 prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus"):
+                 prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
+                 nearest: bool = False):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -278,6 +284,9 @@ class Index:
         self.strand = strand
         if strand == "both":   # RTX_OPT_STRAND: every query is classified in both orientations, the one with the larger peak is reported
             check(self._lib.rtx_index_set_option(self._h, 25, 1))
+        self.nearest_on = bool(nearest)
+        if nearest:   # RTX_OPT_NEAREST: every run also names the reference that holds each query's peak
+            check(self._lib.rtx_index_set_option(self._h, 26, 1))
         self._view = ResultView()
         self._keep = None
 
@@ -352,7 +361,22 @@ class Index:
 
     def download(self, copy: bool = True):
         check(self._lib.rtx_batch_download(self._h, C.byref(self._view)))
-        return Result(self._view, *self.strands()) if copy else self._view
+        return Result(self._view, *self.strands(), *(self.nearest() if self.nearest_on else (None, None))) if copy else self._view
+
+    def nearest(self):
+        """(nearest, ties) of every query of the last download: rtx_batch_nearest (Index(nearest=True))."""
+        pn, pt = u32p(), u32p()
+        check(self._lib.rtx_batch_nearest(self._h, C.byref(pn), C.byref(pt)))
+        n = self._view.n_queries
+        if not n:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(pn, shape=(n,)).copy(), np.ctypeslib.as_array(pt, shape=(n,)).copy()
+
+    def nearest_time(self):
+        """(milliseconds, launches) of the kernel behind nearest() in the last run (stage_timing=True): rtx_batch_nearest_time."""
+        ms, n = C.c_float(), C.c_uint32()
+        check(self._lib.rtx_batch_nearest_time(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def strands(self):
         """(strand, peak) of every query of the last download: rtx_batch_strands."""
@@ -564,6 +588,8 @@ class Index:
 
 _SENDER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p)
 _INFO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32)
+_HIT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
+NO_REF = 0xFFFFFFFF   # RTX_NO_REF
 
 
 def revcomp(seq: np.ndarray) -> np.ndarray:
@@ -576,17 +602,23 @@ def revcomp(seq: np.ndarray) -> np.ndarray:
 
 def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: bool, raw_confidence: bool,
            chunk_size: int, sender: Callable[[str, str, Optional[str]], None], tsv: bool,
-           info: Optional[Callable[[str, int, int, int], None]] = None) -> None:
+           info: Optional[Callable[[str, int, int, int], None]] = None,
+           hit: Optional[Callable[[str, int, int, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
     plays the role of a closed channel.  `info(label, strand, peak, t)`, if given, is called directly before the sender of the same query
-    (rtx_raxtax_multi_ex); handles built with strand="both" report the orientation with the larger peak."""
+    (rtx_raxtax_multi_ex); handles built with strand="both" report the orientation with the larger peak.
+    `hit(label, strand, peak, t, nearest, ties)` is the same with the nearest reference and its ties (rtx_raxtax_multi_ex2; handles built with
+    nearest=True, else NO_REF and 0); give one of the two."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
     lib.rtx_raxtax_multi.argtypes = [C.POINTER(C.c_void_p), C.c_uint32] + lib.rtx_raxtax.argtypes[1:]
     lib.rtx_raxtax_multi_ex.argtypes = lib.rtx_raxtax_multi.argtypes + [_INFO, C.c_void_p]
+    lib.rtx_raxtax_multi_ex2.argtypes = lib.rtx_raxtax_multi.argtypes + [_HIT, C.c_void_p]
+    if info is not None and hit is not None:
+        raise ValueError("raxtax: give info or hit, not both")
     handles = list(tree) if isinstance(tree, (list, tuple)) else [tree]
     labels = (C.c_char_p * max(len(queries), 1))(*[q[0].encode() for q in queries])
     flat, off = _flatten([q[1] for q in queries])
@@ -608,7 +640,19 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if info is not None:
+    def cb_hit(_ctx, label, strand, peak, t, nearest, ties):
+        try:
+            hit(label.decode(), int(strand), int(peak), int(t), int(nearest), int(ties))
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if hit is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex2(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _HIT(cb_hit), None)
+    elif info is not None:
         arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         rc = lib.rtx_raxtax_multi_ex(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _INFO(cb_info), None)

@@ -7,6 +7,7 @@
 //   PREFIX/raxtax.ckp   one finished query label per line  PREFIX/raxtax.json checkpoint (flags + DB fingerprint)
 //   PREFIX/<db>.bin     bincode database cache (unless --skip-db)
 //   PREFIX/raxtax.strand  (--strand both) label, + or -, peak, t per query, in the order of raxtax.out
+//   PREFIX/raxtax.hits    (--hits) label, + or -, peak, t, ties, id and lineage of the nearest reference per query, in the order of raxtax.out
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
@@ -115,11 +116,12 @@ std::string fingerprint(const std::string &path) {
 }
 
 // (--strand both is part of the checkpoint like the three flags: a rerun with the other setting starts over; a default run writes the file it always wrote)
-std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both) {
+// (... and so is --hits)
+std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
-       << (both ? ",\n  \"strand\": \"both\"" : "") << "\n}\n";
+       << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "") << "\n}\n";
     return ss.str();
 }
 
@@ -146,8 +148,9 @@ void purge_incomplete(const std::string &path, const std::set<std::string> &done
 }
 
 struct Sink {
-    std::ofstream out, tsv, ckp, strand;
-    bool want_tsv = false;
+    std::ofstream out, tsv, ckp, strand, hits;
+    bool want_tsv = false, want_strand = false, want_hits = false;
+    const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
 };
 
 }  // namespace
@@ -167,6 +170,7 @@ int main(int argc, char **argv) {
     std::vector<int> devices{0};
     bool device_format = false;
     bool both_strands = false;  // --strand both: RTX_OPT_STRAND on every handle
+    bool want_hits = false;     // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
     for (int i = 1; i < argc; i++) {
@@ -208,11 +212,12 @@ int main(int argc, char **argv) {
             if (v != "plus" && v != "both") { fprintf(stderr, "raxtax-hip: --strand takes plus or both\n"); return 64; }
             both_strands = v == "both";
         }
+        else if (a == "--hits") want_hits = true;
         else if (a == "--batch") chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -223,14 +228,14 @@ int main(int argc, char **argv) {
         return 64;
     }
     const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp";
-    const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand";
+    const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits";
     if (device_format && both_strands) {
         fprintf(stderr, "[INFO ] --strand both: the result lines are formatted on the host (--device-format has no effect)\n");
         device_format = false;
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -242,6 +247,7 @@ int main(int argc, char **argv) {
             purge_incomplete(out_path, done);
             if (tsv) purge_incomplete(tsv_path, done);
             if (both_strands) purge_incomplete(strand_path, done);
+            if (want_hits) purge_incomplete(hits_path, done);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -295,7 +301,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -379,6 +385,7 @@ int main(int argc, char **argv) {
                 rcs[k] = rtx_index_create_from_tree(devices[k], tree, &indices[k]);
                 if (rcs[k] == RTX_OK && device_format) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEVICE_TEXT, 1);
                 if (rcs[k] == RTX_OK && both_strands) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_STRAND, 1);
+                if (rcs[k] == RTX_OK && want_hits) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_NEAREST, 1);
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
             });
         for (auto &t : th) t.join();
@@ -405,6 +412,11 @@ int main(int argc, char **argv) {
     if (tsv) sink.tsv.open(tsv_path, mode);
     if (both_strands) sink.strand.open(strand_path, mode);
     else if (mode == std::ios::trunc) remove(strand_path.c_str());  // (a run that starts over in a folder of a --strand both run: its file would describe other lines)
+    if (want_hits) sink.hits.open(hits_path, mode);
+    else if (mode == std::ios::trunc) remove(hits_path.c_str());  // (likewise)
+    sink.want_strand = both_strands;
+    sink.want_hits = want_hits;
+    sink.tree = tree;
     // the writer of main.rs:127-135: result lines, then the label into the progress file
     auto sender = [](void *c, const char *label, const char *lines, const char *tsv_lines) -> int {
         Sink *s = static_cast<Sink *>(c);
@@ -414,10 +426,16 @@ int main(int argc, char **argv) {
         return s->out.good() && s->ckp.good() ? 0 : 1;
     };
     // ... and in front of them, under --strand both, which orientation the lines are of
-    auto info = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t) -> int {
+    // ... and, under --hits, which reference they look like: peak, t, ties, id and lineage of the nearest reference ('-' twice where no reference shares a k-mer)
+    auto info = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties) -> int {
         Sink *s = static_cast<Sink *>(c);
-        s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
-        return s->strand.good() ? 0 : 1;
+        if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
+        if (s->want_hits) {
+            s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
+            if (nearest == RTX_NO_REF) s->hits << "-\t-\n";
+            else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest) << '\n';
+        }
+        return (!s->want_strand || s->strand.good()) && (!s->want_hits || s->hits.good()) ? 0 : 1;
     };
     int rc = RTX_OK;
     uint64_t n = 0;
@@ -448,8 +466,8 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            rc = rtx_raxtax_multi_ex(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                     both_strands ? +info : nullptr, &sink);
+            rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                      both_strands || want_hits ? +info : nullptr, &sink);
             n += nb;
             if (timing) {  // busy seconds of the pipeline stages of this block (which stage bounds the run)
                 double busy[4];
@@ -471,6 +489,7 @@ int main(int argc, char **argv) {
     sink.ckp.flush();
     if (tsv) sink.tsv.flush();
     if (both_strands) sink.strand.flush();
+    if (want_hits) sink.hits.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
     if (!join_bin_writer()) return 74;

@@ -79,7 +79,8 @@ LastTiming g_timing{{0, 0, 0, 0}, 0};
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
 // (label, strand, peak, t) of the query whose message follows (rtx_query_info_fn); empty: nobody asked
-using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t)>;
+// ... with the nearest reference and its ties behind them (rtx_query_hit_fn; RTX_NO_REF and 0 with RTX_OPT_NEAREST off)
+using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32_t, uint32_t)>;
 
 // One chunk of queries travelling through the stages of run().
 struct Chunk {
@@ -91,6 +92,7 @@ struct Chunk {
     std::vector<uint32_t> t;           // handle reuses once this chunk is formatted
     std::vector<uint8_t> strand;       // rtx_batch_strands, copied by the device stage (both strands, or an info callback)
     std::vector<uint32_t> peak;
+    std::vector<uint32_t> nearest, ties;  // rtx_batch_nearest, copied with them (RTX_OPT_NEAREST and an info callback)
     // The messages of the chunk: every formatting thread appends the NUL-terminated `.out` (and `.tsv`) text of its queries to an arena
     // of its own; msg_off[i] locates query i's text in the arena of the thread that took it (a std::string per message was a malloc in
     // the format thread and a free in the sender's, per query: half of the format stage)
@@ -161,6 +163,9 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         if (both && !rtx_index_has_exact_lookup(indices[d])) { rtx::set_error("RTX_OPT_STRAND needs the exact-match lookup of the device (a handle built from the reference sequences)"); return RTX_ERR_STATE; }
     }
     const bool want_strands = both || (bool)info;
+    const bool near = rtx::index_nearest(indices[0]);  // RTX_OPT_NEAREST: on every handle, or on none
+    for (uint32_t d = 0; d < n_dev; d++)
+        if (rtx::index_nearest(indices[d]) != near) { rtx::set_error("rtx_raxtax_multi: the handles disagree on RTX_OPT_NEAREST"); return RTX_ERR_INVALID; }
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
@@ -322,6 +327,14 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     ch.peak.assign(pk, pk + ch.nq);
                 }
             }
+            if (!rc && near && info) {
+                const uint32_t *nr = nullptr, *ti = nullptr;
+                rc = rtx_batch_nearest(indices[d], &nr, &ti);
+                if (!rc) {
+                    ch.nearest.assign(nr, nr + ch.nq);
+                    ch.ties.assign(ti, ti + ch.nq);
+                }
+            }
             if (rc) { fail(rc, rtx_last_error()); return; }
             busy_device[d] += now() - t_d0;
             set_stage(c, 2);
@@ -469,7 +482,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 continue;
             }
             bool ok;
-            if (info && !info(labels[q], ch.strand[i], ch.peak[i], ch.t[i])) { closed = true; break; }
+            if (info && !info(labels[q], ch.strand[i], ch.peak[i], ch.t[i], near ? ch.nearest[i] : RTX_NO_REF, near ? ch.ties[i] : 0u)) { closed = true; break; }
             if (dev_text[c % n_dev]) {
                 ok = sender(labels[q], ch.text.out + ch.text.out_off[i], tsv ? ch.text.tsv + ch.text.tsv_off[i] : nullptr);
             } else {
@@ -486,6 +499,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint32_t>().swap(ch.t);
         std::vector<uint8_t>().swap(ch.strand);
         std::vector<uint32_t>().swap(ch.peak);
+        std::vector<uint32_t>().swap(ch.nearest);
+        std::vector<uint32_t>().swap(ch.ties);
         {
             std::lock_guard<std::mutex> g(pool_mu);
             for (auto &a : ch.out_arena) arena_pool.push_back(std::move(a));
@@ -564,7 +579,20 @@ extern "C" int rtx_raxtax_multi_ex(rtx_index *const *indices, uint32_t n_indices
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
-    if (info) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t) { return info(info_ctx, label, strand, peak, t) == 0; };
+    if (info) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t, uint32_t) { return info(info_ctx, label, strand, peak, t) == 0; };
+    return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
+               tsv != 0, fi);
+}
+
+// ... with the nearest reference and its ties as well (RTX_OPT_NEAREST)
+extern "C" int rtx_raxtax_multi_ex2(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_hit_fn hit, void *hit_ctx) {
+    if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
+    RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
+    RawInfo fi;
+    if (hit) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties) { return hit(hit_ctx, label, strand, peak, t, nearest, ties) == 0; };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
                tsv != 0, fi);
 }

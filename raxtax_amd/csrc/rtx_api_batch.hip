@@ -523,6 +523,8 @@ int alloc_final(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries) {
         (rc = r.d_fin_row_begin.alloc(n_queries)) || (rc = r.d_fin_row_count.alloc(n_queries)) || (rc = r.d_fin_cursor.alloc(2)))
         return rc;
     if ((rc = r.d_peak2.alloc(n_queries)) || (rc = r.d_peak.alloc(n_queries)) || (rc = r.d_strand.alloc(n_queries))) return rc;  // (rtx_strand.hip)
+    if (ix->nearest_opt && ((rc = r.d_nearest2.alloc(n_queries)) || (rc = r.d_ties2.alloc(n_queries)) || (rc = r.d_nearest.alloc(n_queries)) || (rc = r.d_ties.alloc(n_queries))))  // (rtx_nearest.hip)
+        return rc;
     if (ix->strand_opt && ((rc = r.d_sel_t.alloc(n_queries)) || (rc = r.d_sel_status.alloc(n_queries)) || (rc = r.d_sel_gs.alloc(n_queries)) ||
                            (rc = r.d_sel_row_begin.alloc(n_queries)) || (rc = r.d_sel_row_count.alloc(n_queries))))
         return rc;
@@ -654,6 +656,7 @@ void record_batch(rtx_index *ix) {
     r.n_q = ix->n_q;
     r.n_user = ix->strand_used ? ix->n_user : ix->n_q;
     r.has_peak = false;
+    r.has_nearest = false;
     r.n_sub = ix->n_sub_total();
     r.n_side = 0;
     for (uint32_t c = 0; c < ix->n_cls; c++)
@@ -809,6 +812,9 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
     rc = begin_run(ix, &n_sub, &timed, ix->cluster != 0);
     if (rc) return rc;
     rtx_index::ResultSet &r = ix->res();
+    ix->n_near_last = 0;
+    r.has_nearest = ix->nearest_opt != 0u && r.d_nearest2.p != nullptr && r.d_nearest2.n >= r.n_q && r.d_nearest.n >= r.n_user;
+    if (ix->nearest_opt != 0u && !r.has_nearest) { set_error("internal: RTX_OPT_NEAREST without its arrays"); return RTX_ERR_STATE; }
     if (n_sub <= 4096) {  // per sub-batch: completion event (+ cursor snapshots) for the streamed download
         if (!ix->copy_stream) RTX_HIP(hipStreamCreateWithFlags(&ix->copy_stream, hipStreamNonBlocking));
         while (r.ev_sub.size() < n_sub) {
@@ -885,6 +891,50 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
             const rtx_index::Scratch &sc = ix->sc[b.set];
             launch_peak(b.s, PeakParams{sc.d_hist.p, b.cls->hstride, sc.d_t.p, b.q0, r.d_perm.p, b.nq, r.d_peak2.p});
         }
+        if (r.has_nearest) {  // RTX_OPT_NEAREST: which reference holds it, from what the counting epilogues left (rtx_nearest.hip)
+            rtx_index::Scratch &sc = ix->sc[b.set];
+            const rtx_index::BatchClass &k = *b.cls;
+            NearestParams np{};
+            np.hist = sc.d_hist.p;
+            np.hstride = k.hstride;
+            np.t = sc.d_t.p;
+            np.q0 = b.q0;
+            np.perm = r.d_perm.p;
+            np.nq = b.nq;
+            np.tile_max = sc.d_tilemax.p;
+            np.ntiles = ix->ntiles;
+            np.n_refs = ix->n_refs;
+            np.counts = sc.d_counts.p;
+            np.counts_lo = ix->packs(k.planes) ? counts_lo(ix, sc) : nullptr;
+            np.counts_hi = ix->packs(k.planes) ? counts_hi(ix, k, sc) : nullptr;
+            np.npad = ix->npad;
+            np.cnt_rows = counts_rows_layout(ix, k);
+            np.cnt_row = on_diet(ix, k, sc) ? sc.d_cnt_row.p : nullptr;
+            if (on_records_path(ix, k, sc)) {
+                const RecordRef rr = record_ref(ix, sc, r);
+                np.rec_nslots = rr.nslots;
+                np.rec_slots = rr.slots;
+                np.rec_cnt = rr.cnt;
+                np.rec = rr.rec;
+                np.rec_stride = rr.stride;
+                np.rec_seg_len = rr.seg_len;
+            }
+            np.nearest = r.d_nearest2.p;
+            np.ties = r.d_ties2.p;
+            if (b.timed_all) {  // (not one of the stages of rtx_batch_stage_times, whose number is part of the ABI: rtx_batch_nearest_time)
+                while (ix->ev_near.size() < 2u * ((size_t)sb + 1u)) {
+                    hipEvent_t e;
+                    RTX_HIP(hipEventCreate(&e));
+                    ix->ev_near.push_back(e);
+                }
+                RTX_HIP(hipEventRecord(ix->ev_near[2u * sb], b.s));
+            }
+            launch_nearest(b.s, np);
+            if (b.timed_all) {
+                RTX_HIP(hipEventRecord(ix->ev_near[2u * sb + 1u], b.s));
+                ix->n_near_last = sb + 1u;
+            }
+        }
         if ((rc = enqueue_prob_prefix(ix, b, fuse))) return rc;
         if (!fuse && (rc = enqueue_walk(ix, b, ix->sc[b.set].d_prefix.p, b.s))) return rc;
         if (fuse && b.timed_all) {  // keeps rtx_batch_stage_times whole: an empty interval
@@ -920,7 +970,8 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
             if (both && (r.n_q != 2u * r.n_user || !r.d_sel_t.p || r.d_sel_t.n < r.n_user)) { set_error("internal: a batch of both strands without its twins"); return RTX_ERR_STATE; }
             launch_strand_select(fs, StrandParams{(uint32_t)r.n_user, both ? 1u : 0u, r.d_peak2.p, r.d_fin_status.p, r.d_fin_t.p, r.d_fin_gs.p, r.d_fin_row_begin.p,
                                                   r.d_fin_row_count.p, r.d_strand.p, r.d_peak.p, r.d_sel_status.p, r.d_sel_t.p, r.d_sel_gs.p, r.d_sel_row_begin.p,
-                                                  r.d_sel_row_count.p});
+                                                  r.d_sel_row_count.p, r.has_nearest ? r.d_nearest2.p : nullptr, r.has_nearest ? r.d_ties2.p : nullptr,
+                                                  r.has_nearest ? r.d_nearest.p : nullptr, r.has_nearest ? r.d_ties.p : nullptr});
             if (!r.ev_select) RTX_HIP(hipEventCreateWithFlags(&r.ev_select, hipEventDisableTiming));
             RTX_HIP(hipEventRecord(r.ev_select, fs));
             r.has_peak = true;
@@ -1063,7 +1114,7 @@ int prepare_workspace(rtx_index *ix, uint64_t n_queries, const uint64_t cls_n_in
     const uint64_t key[14] = {n_queries, cn[0], cn[1], cn[2] << 32 | cn[3], cn[4], cm[0], cm[1], cm[2] << 32 | cm[3], cm[4], ix->sub_batch_req,
                               (uint64_t)ix->packed_opt | (uint64_t)ix->pair_opt << 1 | (uint64_t)ix->pruning() << 2 | (uint64_t)ix->shard_prune_opt << 3 | (uint64_t)ix->fine_opt << 4 |
                                   (uint64_t)(ix->prob_mode & 3) << 5 | (uint64_t)ix->rec_opt << 8 | (uint64_t)ix->overlap_opt << 16 | (uint64_t)ix->min_subs << 20,
-                              (uint64_t)ix->n_bnd_local, ix->shared_device ? 1u : 0u, ix->strand_opt};
+                              (uint64_t)ix->n_bnd_local, ix->shared_device ? 1u : 0u, ix->strand_opt | ix->nearest_opt << 1};
     // A batch of the shape of the last one under the same options (the chunks of rtx_raxtax): everything below would come out the same --
     // and hipMemGetInfo alone costs a good part of a millisecond between two chunks, with the device idle
     if (ix->ws_valid && std::memcmp(key, ix->ws_key, sizeof key) == 0 && !ix->staged) {

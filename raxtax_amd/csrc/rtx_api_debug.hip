@@ -28,6 +28,23 @@ int rtx_batch_stage_times(rtx_index *ix, float ms[RTX_NUM_STAGES], uint32_t laun
     return RTX_OK;
 }
 
+// Time of nearest_kernel over the sub-batches of the last run (RTX_OPT_NEAREST with RTX_OPT_STAGE_TIMING on, else 0 launches)
+int rtx_batch_nearest_time(rtx_index *ix, float *ms, uint32_t *launches) {
+    if (!ix || !ms || !launches) { set_error("null argument"); return RTX_ERR_INVALID; }
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (!ix->synced) { set_error("rtx_batch_nearest_time: batch not synchronised"); return RTX_ERR_STATE; }
+    *ms = 0.f;
+    *launches = 0;
+    for (uint32_t sb = 0; sb < ix->n_near_last && 2u * sb + 1u < ix->ev_near.size(); sb++) {
+        float t = 0.f;
+        RTX_HIP(hipEventElapsedTime(&t, ix->ev_near[2u * sb], ix->ev_near[2u * sb + 1u]));
+        *ms += t;
+        (*launches)++;
+    }
+    return RTX_OK;
+}
+
 int rtx_batch_work(rtx_index *ix, uint64_t *sum_hits, uint64_t *sum_query_bytes, uint64_t *bitmap_bytes_read) {
     if (!ix) { set_error("null index handle"); return RTX_ERR_INVALID; }
     int rc = bind(ix);

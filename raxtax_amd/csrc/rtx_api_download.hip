@@ -41,6 +41,7 @@ static int size_host_results(rtx_index *ix, rtx_index::HostRes &hr, uint64_t nq,
     if ((rc = hr.h_t.resize(nq)) || (rc = hr.h_status.resize(nq)) || (rc = hr.h_gs.resize(nq)) || (rc = hr.v_row_begin.resize(nq)) ||
         (rc = hr.v_row_count.resize(nq)) || (rc = hr.h_strand.resize(nq)) || (rc = hr.h_peak.resize(nq)))
         return rc;
+    if (ix->nearest_opt && ((rc = hr.h_nearest.resize(nq)) || (rc = hr.h_ties.resize(nq)))) return rc;  // (rtx_batch_nearest)
     const uint64_t D = ix->fin_D;
     if ((rc = hr.v_row_lineage.grow_keep(rows, keep)) || (rc = hr.v_row_node.grow_keep(rows, keep)) || (rc = hr.v_row_depth.grow_keep(rows, keep)) ||
         (rc = hr.v_row_depth8.grow_keep(rows, keep)) || (rc = hr.v_row_local.grow_keep(rows, keep)) || (rc = hr.v_row_conf.grow_keep(rows * D, keep * D)) ||
@@ -83,6 +84,12 @@ static int copy_queries(const rtx_index::ResultSet &r, rtx_index::HostRes &hr, h
     } else {  // (a staged run, rtx_debug_evaluate: no peak was taken)
         std::memset(hr.h_strand.data(), 0, nq);
         std::memset(hr.h_peak.data(), 0, nq * 4);
+    }
+    hr.has_nearest = r.has_peak && r.has_nearest;  // RTX_OPT_NEAREST (rtx_nearest.hip)
+    if (hr.has_nearest) {
+        if (hr.h_nearest.size() < nq || hr.h_ties.size() < nq) { set_error("internal: RTX_OPT_NEAREST without its host arrays"); return RTX_ERR_STATE; }
+        RTX_HIP(hipMemcpyAsync(hr.h_nearest.data(), r.d_nearest.p, nq * 4, hipMemcpyDeviceToHost, cs));
+        RTX_HIP(hipMemcpyAsync(hr.h_ties.data(), r.d_ties.p, nq * 4, hipMemcpyDeviceToHost, cs));
     }
     return RTX_OK;
 }
@@ -364,6 +371,16 @@ int rtx_batch_strands(rtx_index *ix, const uint8_t **strand, const uint32_t **pe
     if (hr.h_strand.empty() || hr.h_peak.empty() || hr.h_strand.size() < hr.n_user) { set_error("rtx_batch_strands before a download"); return RTX_ERR_STATE; }
     if (strand) *strand = hr.h_strand.data();
     if (peak) *peak = hr.h_peak.data();
+    return RTX_OK;
+}
+
+// Nearest reference and ties of every query of the last download (rtx_nearest.hip)
+int rtx_batch_nearest(rtx_index *ix, const uint32_t **nearest, const uint32_t **ties) {
+    if (!ix || (!nearest && !ties)) { set_error("rtx_batch_nearest: null argument"); return RTX_ERR_INVALID; }
+    const rtx_index::HostRes &hr = ix->host_res[ix->res_set];
+    if (!hr.has_nearest || hr.h_nearest.size() < hr.n_user || hr.h_ties.size() < hr.n_user) { set_error("rtx_batch_nearest: the last download's run had RTX_OPT_NEAREST off (or there was no download)"); return RTX_ERR_STATE; }
+    if (nearest) *nearest = hr.h_nearest.data();
+    if (ties) *ties = hr.h_ties.data();
     return RTX_OK;
 }
 

@@ -12,6 +12,7 @@ void index_set_shared_device(rtx_index *index, bool shared) { if (index) index->
 uint32_t index_swap_min_subs(rtx_index *index, uint32_t v) { if (!index) return 0; const uint32_t old = index->min_subs; index->min_subs = v; return old; }
 // RTX_OPT_RUN_AHEAD for the duration of a call of the host mirror (rtx_raxtax over several chunks); switched off: the last run's join is enqueued
 bool index_strand(const rtx_index *index) { return index && index->strand_opt != 0u; }
+bool index_nearest(const rtx_index *index) { return index && index->nearest_opt != 0u; }
 bool index_device_text(const rtx_index *index) { return index && index->device_text_opt != 0u; }
 uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v) {
     if (!index) return 0;
@@ -843,6 +844,14 @@ int rtx_index_set_option(rtx_index *index, int option, uint64_t value) {
             index->in[0].staged = index->in[1].staged = false;
             index->ws_valid = false;
             index->strand_opt = (uint32_t)value;
+            return RTX_OK;
+        case RTX_OPT_NEAREST:
+            if (value > 1) break;
+            if (value && index->n_refs != index->n_total) { set_error("RTX_OPT_NEAREST: not on a reference-shard handle (the peak of a query is spread over the shards)"); return RTX_ERR_INVALID; }
+            index->uploaded = index->ran = index->synced = false;  // shapes the result sets: the batch is uploaded again
+            index->in[0].staged = index->in[1].staged = false;
+            index->ws_valid = false;
+            index->nearest_opt = (uint32_t)value;
             return RTX_OK;
         case RTX_OPT_TWO_LEVEL_BOUNDS:
             index->two_level_opt = value ? 1u : 0u;

@@ -628,4 +628,35 @@ int64_t emul_text_batch(const char *lin_bytes, const uint64_t *lin_off, const ui
     return w.pos > cap ? -1 : (int64_t)w.pos;
 }
 
+// The scan of one tile by nearest_kernel (rtx_nearest.hip), step by step and lane by lane with the functions the kernel calls: the lowest
+// local reference of the tile whose count is `peak`, or 0xFFFFFFFF.  in_tile: references the tile holds (8192, fewer in the last tile).
+// packed != 0: lo = the tile's low bytes, hi = its high-bit words (u16 per chunk of eight references); else lo = its u16 counts.
+// Every step's lanes are all evaluated before the lowest lane with a match is taken, as the ballot does.
+uint32_t emul_nearest_scan(const void *lo, const uint16_t *hi, uint32_t in_tile, uint32_t peak, int packed) {
+    const uint32_t per = packed ? 16u : 8u;
+    for (uint32_t step = 0; nearest_lane_base(step, 0u, per) < in_tile; step++) {
+        uint32_t mask[64];
+        for (uint32_t lane = 0; lane < 64u; lane++) {
+            const uint32_t b0 = nearest_lane_base(step, lane, per);
+            mask[lane] = 0;
+            if (b0 >= in_tile) continue;
+            uint32_t w[4];
+            if (packed) {
+                std::memcpy(w, static_cast<const uint8_t *>(lo) + b0, 16);
+                uint32_t h2;
+                std::memcpy(&h2, hi + (b0 >> 3), 4);
+                mask[lane] = nearest_match16(w, h2, peak, b0, in_tile);
+            } else {
+                std::memcpy(w, static_cast<const uint16_t *>(lo) + b0, 16);
+                mask[lane] = nearest_match8(w, peak, b0, in_tile);
+            }
+        }
+        for (uint32_t lane = 0; lane < 64u; lane++)
+            if (mask[lane]) return nearest_lane_base(step, lane, per) + (uint32_t)__builtin_ctz(mask[lane]);
+    }
+    return 0xFFFFFFFFu;
+}
+// byte, high-bit word and shift of local reference rl in the packed counts of its tile (packed_count_pos)
+void emul_packed_count_pos(uint32_t rl, uint32_t *byte, uint32_t *hi_word, uint32_t *hi_shift) { packed_count_pos(rl, *byte, *hi_word, *hi_shift); }
+
 }  // extern "C"

@@ -31,6 +31,7 @@ void index_set_shared_device(rtx_index *index, bool shared);
 uint32_t index_swap_min_subs(rtx_index *index, uint32_t v);  // returns the previous value
 uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v);
 bool index_strand(const rtx_index *index);  // RTX_OPT_STRAND
+bool index_nearest(const rtx_index *index);  // RTX_OPT_NEAREST
 bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value
 bool hw_queues_for_run_ahead();  // (host_threads.cpp) GPU_MAX_HW_QUEUES reads six or more: transfers do not share a hardware queue with kernels
 

@@ -107,8 +107,36 @@ struct StrandParams {
     double *o_gs;
     unsigned long long *o_row_begin;
     uint32_t *o_row_count;
+    const uint32_t *nearest2, *ties2;  // [n or 2 n] launch_nearest (RTX_OPT_NEAREST) or null
+    uint32_t *nearest, *ties;          // [n] of the chosen orientation; RTX_NO_REF and 0 where its peak is 0
 };
 void launch_strand_select(hipStream_t s, const StrandParams &p);
+
+// rtx_nearest.hip: which reference holds the peak (RTX_OPT_NEAREST), one wave per query of a sub-batch, from what its counting epilogue left
+struct NearestParams {
+    const uint32_t *hist;  // as PeakParams
+    uint32_t hstride;
+    const uint32_t *t;
+    uint64_t q0;
+    const uint32_t *perm;
+    uint32_t nq;
+    const uint16_t *tile_max;  // [nq][ntiles] HitParams::tile_max
+    uint32_t ntiles;
+    uint64_t n_refs;
+    const uint16_t *counts;       // u16 counts (counts_lo == null) ...
+    const uint8_t *counts_lo;     // ... or the packed form (HitParams)
+    const uint16_t *counts_hi;
+    uint64_t npad;
+    uint32_t cnt_rows;            // rows of the counts buffer
+    const uint32_t *cnt_row;      // [nq] the query's row (HitParams::cnt_row) or null: row q
+    const uint16_t *rec_nslots;   // the records path (RecordRef) or null: every query has a row of counts
+    const uint16_t *rec_slots;
+    const uint32_t *rec_cnt, *rec;
+    uint32_t rec_stride, rec_seg_len;
+    uint32_t *nearest;  // [n_q] by query: the lowest reference with the peak as its count; RTX_NO_REF: peak 0, or the run left the query neither a row nor records (it is repeated)
+    uint32_t *ties;     // [n_q] references with that count: the histogram bin of the peak
+};
+void launch_nearest(hipStream_t s, const NearestParams &p);
 
 struct KmerParams {
     const uint8_t *bases;

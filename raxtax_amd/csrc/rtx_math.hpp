@@ -51,6 +51,46 @@ RTX_HD void ref_slot(uint32_t r, uint32_t stride_bytes, uint32_t &word, uint32_t
 }
 
 // ---------------------------------------------------------------------------
+// Where the count of local reference rl of a tile sits in what the dense epilogues of hit_count store (nearest_kernel, rtx_nearest.hip;
+// taxon_prefix reads the same places chunk by chunk).  Group g of lane l goes to offset (g*L + l)*8 of the tile's stretch of the row, which
+// is where its references are: the stored counts are in REFERENCE order, in a full tile and in the short last one alike, whatever lane
+// held them.  u16 counts: element rl.  Packed counts (10 bits): the low byte at byte rl, the two high bits at bits 2 (rl & 7) of the u16
+// of chunk rl >> 3 (the tile's high-bit words begin at u16 tile * 1024 of the row's high part).
+// ---------------------------------------------------------------------------
+RTX_HD void packed_count_pos(uint32_t rl, uint32_t &byte, uint32_t &hi_word, uint32_t &hi_shift) {
+    byte = rl;
+    hi_word = rl >> 3;
+    hi_shift = (rl & 7u) * 2u;
+}
+// nearest_kernel scans a tile in steps of 64 lanes, every lane `per_lane` consecutive references (16 packed: 16 bytes of low bytes and
+// two high-bit words; 8 as u16: 16 bytes): the first local reference of a lane.  Ascending in (step, lane), so the lowest lane of the
+// first step with a match holds the lowest reference.
+RTX_HD uint32_t nearest_lane_base(uint32_t step, uint32_t lane, uint32_t per_lane) { return (step * 64u + lane) * per_lane; }
+// bit j: reference base + j (base a multiple of 16, below in_tile = the references the tile holds) has the count `peak`.
+// lo: its 16 low bytes, hi2: the high-bit words of chunks base >> 3 (low half) and (base >> 3) + 1 (high half)
+RTX_HD uint32_t nearest_match16(const uint32_t (&lo)[4], uint32_t hi2, uint32_t peak, uint32_t base, uint32_t in_tile) {
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < 16u; j++) {
+        uint32_t byte, hw, hs;
+        packed_count_pos(base + j, byte, hw, hs);
+        byte -= base;
+        hw -= base >> 3;
+        const uint32_t c = ((lo[byte >> 2] >> ((byte & 3u) * 8u)) & 0xFFu) | (((hi2 >> (hw * 16u + hs)) & 3u) << 8);
+        if (c == peak && base + j < in_tile) m |= 1u << j;
+    }
+    return m;
+}
+// the same over 8 u16 counts (w: four words, base a multiple of 8)
+RTX_HD uint32_t nearest_match8(const uint32_t (&w)[4], uint32_t peak, uint32_t base, uint32_t in_tile) {
+    uint32_t m = 0;
+    for (uint32_t j = 0; j < 8u; j++) {
+        const uint32_t c = (w[j >> 1] >> ((j & 1u) * 16u)) & 0xFFFFu;
+        if (c == peak && base + j < in_tile) m |= 1u << j;
+    }
+    return m;
+}
+
+// ---------------------------------------------------------------------------
 // Hash of an encoded sequence for the exact-match lookup (Tree.sequences.get, raxtax.rs:42) on the device.  The bytes are taken
 // as 8-byte little-endian words (the last one zero-padded); every word is mixed with its position and the mixes are ADDED, so
 // that the lanes of a wave can hash their words independently and meet in one sum.  Equal sequences hash equal; a collision only

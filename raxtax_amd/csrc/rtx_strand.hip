@@ -62,6 +62,10 @@ __global__ __launch_bounds__(256) void strand_select_kernel(StrandParams p) {
     }
     p.strand[q] = c == q ? 0u : 1u;
     p.peak[q] = peak;
+    if (p.nearest2) {  // RTX_OPT_NEAREST (rtx_nearest.hip): of the chosen orientation; a peak of 0 (or a status that is not RTX_Q_OK) names no reference
+        p.nearest[q] = peak ? p.nearest2[c] : RTX_NO_REF;
+        p.ties[q] = peak ? p.ties2[c] : 0u;
+    }
 }
 
 void launch_strand_select(hipStream_t s, const StrandParams &p) {
