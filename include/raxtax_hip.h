@@ -39,7 +39,8 @@ extern "C" {
                                 and options of round 5 (rtx_index_self_sample, rtx_records_format, options 18-22);
                              6: RTX_OPT_RUN_AHEAD (23), RTX_RETRY_CHUNK from rtx_batch_download_then_run under it, rtx_index_run_ahead_stats
                                 (still 6 with RTX_OPT_NEAREST (26), RTX_NO_REF, rtx_batch_nearest and rtx_raxtax_multi_ex2: exports and an option
-                                that is off by default, nothing that exists changes shape) */
+                                that is off by default, nothing that exists changes shape; and with the taxon profile, rtx_index_profile_* /
+                                rtx_profile_merge / rtx_profile_format: exports only) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -403,6 +404,54 @@ int rtx_batch_nearest(rtx_index *index, const uint32_t **nearest, const uint32_t
 /* Milliseconds the kernel behind it took over the sub-batches of the last run, and its launches (RTX_OPT_STAGE_TIMING on; else 0 and 0).  Not one
  * of the stages of rtx_batch_stage_times: RTX_NUM_STAGES is part of the ABI.  After rtx_batch_sync. */
 int rtx_batch_nearest_time(rtx_index *index, float *ms, uint32_t *launches);
+
+/* ---- taxon profile of a run, accumulated on the device (rtx_profile.hip) --------------------------------------------------------------
+ * What is in the sample: per node of the taxonomy (rtx_nodes_view numbering) the queries under it, the queries assigned to it and the sum
+ * of their confidences, from the BEST LINEAGE of every query -- the one `.out` prints first: the first row of the query, or, where it has
+ * exactly one exact match and neither RTX_SKIP_EXACT_MATCHES nor RTX_RAW_CONFIDENCE is in the profile's flags, the Taxon node of that
+ * reference with 100 on every level (raxtax.rs:73-84).  Its path a_0 .. a_{depth-1} runs from the child of the root to its node; L = the
+ * number of leading levels whose confidence in hundredths reaches the cutoff.  L == 0: the query is `unclassified`; else clade[a_d] += 1 and
+ * conf_sum[a_d] += hundredths[d] for d < L, direct[a_{L-1}] += 1, and the query is `classified`.  A query whose status is not RTX_Q_OK or
+ * that has no row is `unclassifiable`.  totals = {queries, classified, unclassified, unclassifiable}.  Node 0, the root, stays 0;
+ * clade[n] == direct[n] + the clade of n's children, and the sum of direct is totals[1].  Integers throughout: the result is exact and
+ * does not depend on the order of the queries.
+ * Off unless begun: no allocation, no launch, every other output what it is without it.  While a profile is open every batch is added ONCE,
+ * when its download accepts it (rtx_batch_download / _download_then_run / rtx_classify_batch, rtx_raxtax*): a run that is repeated for buffer
+ * space, a batch that ends in RTX_RETRY_CHUNK and a second download of one run add nothing; neither do rtx_debug_evaluate and staged
+ * rtx_shard_* runs.  Under RTX_OPT_STRAND a query counts with the orientation that was chosen.
+ *   rtx_index_profile_begin  cutoff_hundredths 1 .. 100, flags RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE (either one: no override); allocates
+ *                            and zeroes the counters.  RTX_ERR_INVALID: cutoff out of range, unknown flags, a reference shard; RTX_ERR_STATE:
+ *                            a profile is open already.
+ *   rtx_index_profile_read   the counters of everything downloaded so far, copied to host arrays that stay valid until the next read, reset
+ *                            or end.  RTX_ERR_STATE (also reset, end, time): no profile is open.
+ *   rtx_index_profile_reset  zeroes the counters, the profile stays open.
+ *   rtx_index_profile_end    switches the accumulation off and frees everything.
+ *   rtx_index_profile_time   milliseconds and launches of the kernel since begin or reset, for downloads under RTX_OPT_STAGE_TIMING (else 0, 0).
+ *   rtx_profile_merge        sums n profiles (one handle per GPU) into caller arrays of n_nodes entries; RTX_ERR_INVALID when the views differ
+ *                            in n_nodes, cutoff or flags.
+ *   rtx_profile_format       the report: "# cutoff=0.80<TAB>queries=N<TAB>classified=A<TAB>unclassified=B<TAB>unclassifiable=C", then
+ *                            "clade<TAB>direct<TAB>percent<TAB>mean_conf<TAB>depth<TAB>taxon<TAB>lineage", then one line per node with clade > 0 in
+ *                            pre-order (node_begin ascending, then depth ascending); percent = (clade * 10000 + N / 2) / N printed with two
+ *                            decimals, mean_conf = (conf_sum + clade / 2) / clade hundredths likewise, lineage = the first `depth` levels of
+ *                            lineages[node_begin], taxon = the last of them.  Every line ends in '\n', no NUL.  Returns the bytes written,
+ *                            with out == NULL the bytes needed; a buffer that is too small: -(bytes needed) - RTX_NEED_BASE.
+ * rtx_raxtax and rtx_raxtax_multi* honour open profiles: all handles of a call have one open, with one cutoff, or none has, and its flags
+ * are the call's skip_exact_matches / raw_confidence (RTX_ERR_INVALID otherwise). */
+typedef struct {
+    uint32_t n_nodes;
+    uint32_t cutoff_hundredths;
+    uint32_t flags;
+    const uint64_t *clade, *direct, *conf_sum; /* [n_nodes] */
+    uint64_t totals[4];
+} rtx_profile_view;
+int rtx_index_profile_begin(rtx_index *index, uint32_t cutoff_hundredths, uint32_t flags);
+int rtx_index_profile_read(rtx_index *index, rtx_profile_view *out);
+int rtx_index_profile_reset(rtx_index *index);
+int rtx_index_profile_end(rtx_index *index);
+int rtx_index_profile_time(rtx_index *index, float *ms, uint32_t *launches);
+int rtx_profile_merge(rtx_profile_view *const *views, uint32_t n, uint64_t *clade, uint64_t *direct, uint64_t *conf_sum, uint64_t totals[4]);
+int64_t rtx_profile_format(const rtx_tree *tree, const uint64_t *clade, const uint64_t *direct, const uint64_t *conf_sum,
+                           const uint64_t totals[4], uint32_t cutoff_hundredths, char *out, uint64_t cap);
 
 /* The same in stages, so that a caller (bench.py) can keep inputs resident in HBM and
  * time the device part alone, or overlap stages of different batches. */

@@ -47,6 +47,11 @@ class TextView(C.Structure):
     _fields_ = [("n_queries", C.c_uint64), ("out", C.c_void_p), ("out_off", u64p), ("tsv", C.c_void_p), ("tsv_off", u64p)]
 
 
+class ProfileView(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("cutoff_hundredths", C.c_uint32), ("flags", C.c_uint32), ("clade", u64p), ("direct", u64p),
+                ("conf_sum", u64p), ("totals", C.c_uint64 * 4)]
+
+
 class RtxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"libraxtax_hip error {code}: {msg}")
@@ -154,6 +159,13 @@ _SIGNATURES = {
     "rtx_raxtax_multi_ex2": (C.c_int, None),
     "rtx_batch_nearest": (C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p)]),
     "rtx_batch_nearest_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtx_index_profile_begin": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
+    "rtx_index_profile_read": (C.c_int, [C.c_void_p, C.POINTER(ProfileView)]),
+    "rtx_index_profile_reset": (C.c_int, [C.c_void_p]),
+    "rtx_index_profile_end": (C.c_int, [C.c_void_p]),
+    "rtx_index_profile_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtx_profile_merge": (C.c_int, [C.POINTER(C.POINTER(ProfileView)), C.c_uint32, u64p, u64p, u64p, u64p]),
+    "rtx_profile_format": (C.c_int64, [C.c_void_p, u64p, u64p, u64p, u64p, C.c_uint32, C.c_char_p, C.c_uint64]),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

@@ -205,6 +205,9 @@ class Result:
         self.row_conf = (np.ctypeslib.as_array(view.row_conf, shape=(nr, stride))[src] if nr
                          else np.zeros((0, stride)))
         self.row_local_signal = arr(view.row_local_signal, nr)[src]
+        # the confidences as integer hundredths, [rows][stride] (what the taxon profile counts; a hand-made view has none: rounded from row_conf)
+        self.row_conf_hundredths = (np.ctypeslib.as_array(view.row_conf_hundredths, shape=(nr, stride))[src].copy() if nr and view.row_conf_hundredths
+                                    else np.rint(self.row_conf * 100.0).astype(np.uint8))
 
     def rows(self, q: int) -> List[EvaluationResult]:
         out = []
@@ -214,6 +217,51 @@ class Result:
                                         [float(x) for x in self.row_conf[r, :d]],
                                         float(self.row_local_signal[r]), float(self.global_signal[q])))
         return out
+
+
+@dataclass
+class Profile:
+    """The taxon profile of a handle (rtx_index_profile_read), or a sum of several (profile_merge): per node of Tree.nodes() the queries under it
+    (clade), assigned to it (direct) and the sum of their confidences in hundredths (conf_sum); totals = queries, classified, unclassified,
+    unclassifiable.  cutoff in hundredths, flags = RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE as the profile was begun."""
+    cutoff: int
+    flags: int
+    clade: np.ndarray
+    direct: np.ndarray
+    conf_sum: np.ndarray
+    totals: np.ndarray
+
+    def _view(self) -> "_lib.ProfileView":
+        v = _lib.ProfileView()
+        v.n_nodes, v.cutoff_hundredths, v.flags = len(self.clade), self.cutoff, self.flags
+        v.clade, v.direct, v.conf_sum = ptr(self.clade, u64p), ptr(self.direct, u64p), ptr(self.conf_sum, u64p)
+        for i in range(4):
+            v.totals[i] = int(self.totals[i])
+        return v
+
+
+def profile_merge(profiles: Sequence[Profile]) -> Profile:
+    """rtx_profile_merge: the sum of the profiles of several handles (one per GPU); they must agree on the nodes, the cutoff and the flags."""
+    if not profiles:
+        raise ValueError("profile_merge: no profiles")
+    views = [p._view() for p in profiles]
+    arr = (C.POINTER(_lib.ProfileView) * len(views))(*[C.pointer(v) for v in views])
+    n = len(profiles[0].clade)
+    clade, direct, conf = (np.zeros(n, np.uint64) for _ in range(3))
+    totals = np.zeros(4, np.uint64)
+    check(_lib.load().rtx_profile_merge(arr, len(views), ptr(clade, u64p), ptr(direct, u64p), ptr(conf, u64p), ptr(totals, u64p)))
+    return Profile(profiles[0].cutoff, profiles[0].flags, clade, direct, conf, totals)
+
+
+def profile_text(tree: Tree, profile: Profile) -> str:
+    """rtx_profile_format: the report of a profile over `tree` (what raxtax-hip --profile writes to PREFIX/raxtax.profile)."""
+    lib = _lib.load()
+    a = [np.ascontiguousarray(x, dtype=np.uint64) for x in (profile.clade, profile.direct, profile.conf_sum, profile.totals)]
+    args = [tree._h] + [ptr(x, u64p) for x in a] + [int(profile.cutoff)]
+    n = check(lib.rtx_profile_format(*args, None, 0))
+    buf = C.create_string_buffer(max(n, 1))
+    check(lib.rtx_profile_format(*args, buf, n))
+    return buf.raw[:n].decode()
 
 
 DEFAULT_SEGMENT_CLASSES = 1   # RTX_DEFAULT_SEGMENT_CLASSES of the library (rtx_api_index.hip: g_seg_classes)
@@ -376,6 +424,32 @@ class Index:
         """(milliseconds, launches) of the kernel behind nearest() in the last run (stage_timing=True): rtx_batch_nearest_time."""
         ms, n = C.c_float(), C.c_uint32()
         check(self._lib.rtx_batch_nearest_time(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
+
+    # ---- taxon profile (rtx_profile.hip) ----------------------------------------------------
+    def profile_begin(self, cutoff: float = 0.8, skip_exact_matches: bool = False, raw_confidence: bool = False):
+        """Opens the taxon profile of the handle: every batch downloaded from now on is added once (rtx_index_profile_begin).  cutoff: the
+        confidence a level needs to count, in (0, 1]; either flag switches the single-exact-match override off, as in the `.out` text."""
+        flags = (RTX_SKIP_EXACT_MATCHES if skip_exact_matches else 0) | (RTX_RAW_CONFIDENCE if raw_confidence else 0)
+        check(self._lib.rtx_index_profile_begin(self._h, int(round(cutoff * 100)), flags))
+
+    def profile_read(self) -> Profile:
+        v = _lib.ProfileView()
+        check(self._lib.rtx_index_profile_read(self._h, C.byref(v)))
+        n = v.n_nodes
+        g = lambda p: np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+        return Profile(int(v.cutoff_hundredths), int(v.flags), g(v.clade), g(v.direct), g(v.conf_sum), np.array(list(v.totals), dtype=np.uint64))
+
+    def profile_reset(self):
+        check(self._lib.rtx_index_profile_reset(self._h))
+
+    def profile_end(self):
+        check(self._lib.rtx_index_profile_end(self._h))
+
+    def profile_time(self):
+        """(milliseconds, launches) of the profile kernel since profile_begin / profile_reset (stage_timing=True): rtx_index_profile_time."""
+        ms, n = C.c_float(), C.c_uint32()
+        check(self._lib.rtx_index_profile_time(self._h, C.byref(ms), C.byref(n)))
         return float(ms.value), int(n.value)
 
     def strands(self):

@@ -7,6 +7,7 @@ package stays free of the oracle while `tests/` and the `cpu_baseline` leg of `b
   check_run_as_left     one query of the last sub-batch exactly as the pruned, timed run left it, against the oracle's full computation
   assert_rows_equivalent  result rows identical, or an exact tie between sibling taxa verified from the oracle's probabilities
   as_run_oracle_sample  a seeded sample of the queries of the LAST sub-batch of a run through the three checks above
+  profile_expected      the taxon profile (rtx_index_profile_*) of a downloaded Result, restated in numpy
 """
 from __future__ import annotations
 
@@ -254,3 +255,60 @@ def as_run_oracle_sample(index, res, oracle, otree, bases, base_off, n_sample: i
                 seen["ties"] += 1
             seen["n"] += 1
     return seen
+
+
+def profile_expected(nodes_view, result, exact_off, exact_ids, cutoff, override_ok):
+    """The taxon profile of one downloaded batch as include/raxtax_hip.h defines it, from the Result of the download -- a plain restatement
+    that shares nothing with the kernel.  nodes_view: Tree.nodes(); exact_off / exact_ids: the exact matches of the batch as the download
+    reports them (of the chosen orientation under both strands); cutoff in hundredths.  Returns (clade, direct, conf_sum, totals, seen): uint64
+    arrays by node, totals = queries, classified, unclassified, unclassifiable, and seen = how many queries took which way (override,
+    several exact matches, L == 0, 0 < L < depth, L == depth, status not OK) so that a test can tell what it covered."""
+    parent = np.asarray(nodes_view["parent"]).astype(np.int64)
+    begin, end, typ = (np.asarray(nodes_view[k]) for k in ("begin", "end", "type"))
+    nn = len(parent)
+    depth = np.zeros(nn, np.int64)
+    for v in range(1, nn):          # breadth first: a parent comes before its children
+        depth[v] = depth[parent[v]] + 1
+    leaf = np.full(int(end[0]) if nn else 0, -1, np.int64)
+    for v in range(1, nn):          # the deepest Taxon node over a reference is the last one written
+        if typ[v] == 1:
+            leaf[int(begin[v]):int(end[v])] = v
+    clade, direct, conf_sum = (np.zeros(nn, np.uint64) for _ in range(3))
+    totals = np.zeros(4, np.uint64)
+    seen = dict(override=0, several_exact=0, l_zero=0, l_partial=0, l_full=0, not_ok=0)
+    hund = result.row_conf_hundredths
+    for q in range(result.n_queries):
+        totals[0] += 1
+        a, b = int(result.row_off[q]), int(result.row_off[q + 1])
+        if int(result.status[q]) != 0 or b == a:
+            totals[3] += 1
+            seen["not_ok"] += 1
+            continue
+        ne = int(exact_off[q + 1]) - int(exact_off[q])
+        seen["several_exact"] += ne >= 2
+        if override_ok and ne == 1:
+            node = int(leaf[int(exact_ids[int(exact_off[q])])])
+            d = int(depth[node])
+            h = [100] * d
+            seen["override"] += 1
+        else:
+            node, d = int(result.row_node[a]), int(result.row_depth[a])
+            h = [int(x) for x in hund[a, :d]]
+        L = 0
+        while L < d and h[L] >= cutoff:
+            L += 1
+        if L == 0:
+            totals[2] += 1
+            seen["l_zero"] += 1
+            continue
+        seen["l_full" if L == d else "l_partial"] += 1
+        totals[1] += 1
+        path = [0] * d
+        for k in range(d - 1, -1, -1):
+            path[k] = node
+            node = int(parent[node])
+        for k in range(L):
+            clade[path[k]] += 1
+            conf_sum[path[k]] += h[k]
+        direct[path[L - 1]] += 1
+    return clade, direct, conf_sum, totals, seen

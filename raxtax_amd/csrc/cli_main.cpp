@@ -7,6 +7,7 @@
 //   PREFIX/raxtax.ckp   one finished query label per line  PREFIX/raxtax.json checkpoint (flags + DB fingerprint)
 //   PREFIX/<db>.bin     bincode database cache (unless --skip-db)
 //   PREFIX/raxtax.strand  (--strand both) label, + or -, peak, t per query, in the order of raxtax.out
+//   PREFIX/raxtax.profile (--profile CUTOFF) the taxon profile of the whole run: reads under and at every taxon whose confidence reaches CUTOFF (rtx_profile_format)
 //   PREFIX/raxtax.hits    (--hits) label, + or -, peak, t, ties, id and lineage of the nearest reference per query, in the order of raxtax.out
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
@@ -17,6 +18,7 @@
 
 #include <cctype>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <deque>
 #include <mutex>
@@ -116,12 +118,14 @@ std::string fingerprint(const std::string &path) {
 }
 
 // (--strand both is part of the checkpoint like the three flags: a rerun with the other setting starts over; a default run writes the file it always wrote)
-// (... and so is --hits)
-std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits) {
+// (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
+std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
-       << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "") << "\n}\n";
+       << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "");
+    if (profile) ss << ",\n  \"profile\": " << profile;
+    ss << "\n}\n";
     return ss.str();
 }
 
@@ -171,6 +175,7 @@ int main(int argc, char **argv) {
     bool device_format = false;
     bool both_strands = false;  // --strand both: RTX_OPT_STRAND on every handle
     bool want_hits = false;     // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
+    uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
     for (int i = 1; i < argc; i++) {
@@ -213,11 +218,19 @@ int main(int argc, char **argv) {
             both_strands = v == "both";
         }
         else if (a == "--hits") want_hits = true;
+        else if (a == "--profile") {
+            char *end = nullptr;
+            const char *v = val();
+            const double x = strtod(v, &end);
+            const long c = end != v && *end == '\0' && x > 0.0 && x <= 1.0 ? lround(x * 100.0) : 0;
+            if (c < 1 || c > 100) { fprintf(stderr, "raxtax-hip: --profile takes a confidence cutoff in (0, 1], such as 0.8\n"); return 64; }
+            profile_cutoff = (uint32_t)c;
+        }
         else if (a == "--batch") chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--profile CUTOFF]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -228,14 +241,14 @@ int main(int argc, char **argv) {
         return 64;
     }
     const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp";
-    const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits";
+    const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && both_strands) {
         fprintf(stderr, "[INFO ] --strand both: the result lines are formatted on the host (--device-format has no effect)\n");
         device_format = false;
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -244,6 +257,11 @@ int main(int argc, char **argv) {
             std::ifstream p(ckp_path);
             std::string l;
             while (std::getline(p, l)) done.insert(l);
+            if (profile_cutoff && !done.empty()) {  // the queries of the earlier run are not classified again: their share of the sample is gone
+                fprintf(stderr, "raxtax-hip: --profile cannot resume a checkpoint with processed queries (%zu in %s): the profile would miss them; "
+                                "run with --redo to classify the whole sample again\n", done.size(), ckp_path.c_str());
+                return 64;
+            }
             purge_incomplete(out_path, done);
             if (tsv) purge_incomplete(tsv_path, done);
             if (both_strands) purge_incomplete(strand_path, done);
@@ -301,7 +319,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -386,6 +404,8 @@ int main(int argc, char **argv) {
                 if (rcs[k] == RTX_OK && device_format) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEVICE_TEXT, 1);
                 if (rcs[k] == RTX_OK && both_strands) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_STRAND, 1);
                 if (rcs[k] == RTX_OK && want_hits) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_NEAREST, 1);
+                if (rcs[k] == RTX_OK && profile_cutoff)
+                    rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
             });
         for (auto &t : th) t.join();
@@ -414,6 +434,7 @@ int main(int argc, char **argv) {
     else if (mode == std::ios::trunc) remove(strand_path.c_str());  // (a run that starts over in a folder of a --strand both run: its file would describe other lines)
     if (want_hits) sink.hits.open(hits_path, mode);
     else if (mode == std::ios::trunc) remove(hits_path.c_str());  // (likewise)
+    if (mode == std::ios::trunc) remove(profile_path.c_str());  // (written at the end of a run with --profile)
     sink.want_strand = both_strands;
     sink.want_hits = want_hits;
     sink.tree = tree;
@@ -498,6 +519,34 @@ int main(int argc, char **argv) {
     if (rc != RTX_OK) {
         fprintf(stderr, "[ERROR] %s\nRerun raxtax-hip to continue from the last checkpoint.\n", rtx_last_error());
         return rc == RTX_ERR_SENDER ? 75 : 70;  // exitcode::TEMPFAIL / SOFTWARE
+    }
+    if (profile_cutoff) {  // the taxon profile of the whole run: the sum over the handles, written once
+        std::vector<rtx_profile_view> views(indices.size());
+        std::vector<rtx_profile_view *> ptrs(indices.size());
+        int prc = RTX_OK;
+        for (size_t k = 0; k < indices.size() && prc == RTX_OK; k++) {
+            prc = rtx_index_profile_read(indices[k], &views[k]);
+            ptrs[k] = &views[k];
+        }
+        std::vector<uint64_t> acc(prc == RTX_OK ? 3 * (size_t)views[0].n_nodes : 0);
+        uint64_t totals[4] = {0, 0, 0, 0};
+        const size_t nn = prc == RTX_OK ? views[0].n_nodes : 0;
+        if (prc == RTX_OK) prc = rtx_profile_merge(ptrs.data(), (uint32_t)ptrs.size(), acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals);
+        std::string text;
+        if (prc == RTX_OK) {
+            const int64_t need = rtx_profile_format(tree, acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals, profile_cutoff, nullptr, 0);
+            if (need < 0) prc = (int)need;
+            else {
+                text.resize((size_t)need);
+                const int64_t got = rtx_profile_format(tree, acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals, profile_cutoff, &text[0], text.size());
+                if (got != need) prc = got < 0 ? (int)got : RTX_ERR_STATE;
+            }
+        }
+        if (prc != RTX_OK) { fprintf(stderr, "[ERROR] taxon profile: %s\n", rtx_last_error()); return 70; }
+        std::ofstream pf(profile_path, std::ios::trunc);
+        pf << text;
+        pf.close();
+        if (!pf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", profile_path.c_str()); return 74; }
     }
     if (clean) {  // Checkpoint::cleanup (io.rs:80-89)
         remove(ckp_json.c_str());

@@ -4,6 +4,7 @@
 //   utils::get_results / get_results_tsv src/utils.rs:62-68,83-89
 //   utils::decompress_sequence           src/utils.rs:70-81
 //   exact-match override                 src/raxtax.rs:73-84
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -364,4 +365,76 @@ extern "C" int64_t rtx_records_format(const rtx_tree *tree, const uint8_t *recor
     }
     if (line_off) line_off[nq] = total;
     return (int64_t)total;
+}
+
+// ---- the taxon profile (rtx_index_profile_*, rtx_profile.hip) on the host: the sum over handles and the report
+
+extern "C" int rtx_profile_merge(rtx_profile_view *const *views, uint32_t n, uint64_t *clade, uint64_t *direct, uint64_t *conf_sum, uint64_t totals[4]) {
+    if (!views || n == 0 || !clade || !direct || !conf_sum || !totals) { rtx::set_error("rtx_profile_merge: null argument"); return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {
+        if (!views[i] || !views[i]->clade || !views[i]->direct || !views[i]->conf_sum) { rtx::set_error("rtx_profile_merge: view %u is null or empty", i); return RTX_ERR_INVALID; }
+        if (views[i]->n_nodes != views[0]->n_nodes || views[i]->cutoff_hundredths != views[0]->cutoff_hundredths || views[i]->flags != views[0]->flags) {
+            rtx::set_error("rtx_profile_merge: view %u differs from view 0 in its nodes, cutoff or flags (%u / %u / %#x against %u / %u / %#x)", i, views[i]->n_nodes,
+                           views[i]->cutoff_hundredths, views[i]->flags, views[0]->n_nodes, views[0]->cutoff_hundredths, views[0]->flags);
+            return RTX_ERR_INVALID;
+        }
+    }
+    const uint32_t nn = views[0]->n_nodes;
+    for (uint32_t v = 0; v < nn; v++) {  // (an output may be the array of one of the views: every entry is read before it is written)
+        uint64_t c = 0, d = 0, s = 0;
+        for (uint32_t i = 0; i < n; i++) { c += views[i]->clade[v]; d += views[i]->direct[v]; s += views[i]->conf_sum[v]; }
+        clade[v] = c; direct[v] = d; conf_sum[v] = s;
+    }
+    uint64_t t[4] = {0, 0, 0, 0};
+    for (uint32_t i = 0; i < n; i++)
+        for (int k = 0; k < 4; k++) t[k] += views[i]->totals[k];
+    for (int k = 0; k < 4; k++) totals[k] = t[k];
+    return RTX_OK;
+}
+
+// The report: a line of totals, a line of column names, and one line per node with clade > 0 in pre-order (node_begin ascending, then depth
+// ascending).  Integer arithmetic throughout: percent = (clade * 10000 + N / 2) / N hundredths of a percent, mean_conf = (conf_sum + clade / 2)
+// / clade hundredths.  Every line ends in '\n'; no NUL.
+extern "C" int64_t rtx_profile_format(const rtx_tree *tree, const uint64_t *clade, const uint64_t *direct, const uint64_t *conf_sum, const uint64_t totals[4],
+                                      uint32_t cutoff_hundredths, char *out, uint64_t cap) {
+    if (!tree || !clade || !direct || !conf_sum || !totals) { rtx::set_error("rtx_profile_format: null argument"); return RTX_ERR_INVALID; }
+    const rtx::FlatNodes &f = tree->flat;
+    const uint32_t nn = f.size();
+    std::vector<uint32_t> order;
+    for (uint32_t v = 1; v < nn; v++)
+        if (clade[v]) order.push_back(v);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return f.begin[a] != f.begin[b] ? f.begin[a] < f.begin[b] : f.depth[a] < f.depth[b]; });
+    char num[160];
+    std::string text;
+    snprintf(num, sizeof num, "# cutoff=%u.%02u\tqueries=%llu\tclassified=%llu\tunclassified=%llu\tunclassifiable=%llu\n", cutoff_hundredths / 100u, cutoff_hundredths % 100u,
+             (unsigned long long)totals[0], (unsigned long long)totals[1], (unsigned long long)totals[2], (unsigned long long)totals[3]);
+    text += num;
+    text += "clade\tdirect\tpercent\tmean_conf\tdepth\ttaxon\tlineage\n";
+    const uint64_t N = totals[0];
+    for (uint32_t v : order) {
+        if (f.begin[v] >= tree->lineages.size()) { rtx::set_error("rtx_profile_format: node %u begins behind the tree's lineages", v); return RTX_ERR_INVALID; }
+        const uint64_t pct = N ? (clade[v] * 10000u + N / 2u) / N : 0u, mean = (conf_sum[v] + clade[v] / 2u) / clade[v];
+        snprintf(num, sizeof num, "%llu\t%llu\t%llu.%02llu\t%u.%02u\t%u\t", (unsigned long long)clade[v], (unsigned long long)direct[v], (unsigned long long)(pct / 100u),
+                 (unsigned long long)(pct % 100u), (unsigned)(mean / 100u), (unsigned)(mean % 100u), f.depth[v]);
+        text += num;
+        const std::string &lin = tree->lineages[f.begin[v]];
+        size_t end = 0, start = 0;  // the first depth levels: [0, end), the last of them [start, end)
+        for (uint32_t d = 0; d < f.depth[v]; d++) {
+            start = d ? end + 1 : 0;
+            const size_t c = start <= lin.size() ? lin.find(',', start) : std::string::npos;
+            end = c == std::string::npos ? lin.size() : c;
+        }
+        start = std::min(start, lin.size());
+        text.append(lin, start, end - start);
+        text += '\t';
+        text.append(lin, 0, end);
+        text += '\n';
+    }
+    if (!out) return (int64_t)text.size();
+    if (cap < text.size()) {  // (as rtx_records_format answers it)
+        rtx::set_error("rtx_profile_format: buffer of %llu bytes, need %llu", (unsigned long long)cap, (unsigned long long)text.size());
+        return -(int64_t)text.size() - (int64_t)RTX_NEED_BASE;
+    }
+    memcpy(out, text.data(), text.size());
+    return (int64_t)text.size();
 }

@@ -166,6 +166,20 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     const bool near = rtx::index_nearest(indices[0]);  // RTX_OPT_NEAREST: on every handle, or on none
     for (uint32_t d = 0; d < n_dev; d++)
         if (rtx::index_nearest(indices[d]) != near) { rtx::set_error("rtx_raxtax_multi: the handles disagree on RTX_OPT_NEAREST"); return RTX_ERR_INVALID; }
+    // an open taxon profile (rtx_index_profile_begin): on every handle or on none, with one cutoff, and with the flags of this call
+    uint32_t prof_cutoff = 0, prof_flags = 0;
+    const bool prof = rtx::index_profile(indices[0], &prof_cutoff, &prof_flags);
+    for (uint32_t d = 1; d < n_dev; d++) {
+        uint32_t c = 0, f = 0;
+        if (rtx::index_profile(indices[d], &c, &f) != prof || (prof && (c != prof_cutoff || f != prof_flags))) {
+            rtx::set_error("rtx_raxtax_multi: the handles disagree on their taxon profile (open on all or on none, one cutoff, one set of flags)");
+            return RTX_ERR_INVALID;
+        }
+    }
+    if (prof && prof_flags != flags) {
+        rtx::set_error("rtx_raxtax: the open taxon profile has flags %#x, the call %#x (skip_exact_matches / raw_confidence must match)", prof_flags, flags);
+        return RTX_ERR_INVALID;
+    }
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];

@@ -657,6 +657,7 @@ void record_batch(rtx_index *ix) {
     r.n_user = ix->strand_used ? ix->n_user : ix->n_q;
     r.has_peak = false;
     r.has_nearest = false;
+    r.profiled = false;
     r.n_sub = ix->n_sub_total();
     r.n_side = 0;
     for (uint32_t c = 0; c < ix->n_cls; c++)

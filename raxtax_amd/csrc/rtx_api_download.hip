@@ -100,6 +100,54 @@ static int read_flags(const rtx_index::ResultSet &r, uint32_t *flags, unsigned l
     return RTX_OK;
 }
 
+// The batch in result set r joins the open taxon profile (rtx_profile.hip), once: called where the text of a download is produced -- the run's
+// flags have been accepted, its final rows, its selection and its exact-match groups are complete on the device, and the next run has not
+// been let onto these rows.  A staged run and rtx_debug_evaluate (no peak, no selection) add nothing.  Synchronous like the text, and for
+// the same reason: the input set with the ids a caller passed in is free for the next rtx_batch_prefetch when the download returns.
+int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r) {
+    rtx_index::Profile &pf = ix->prof;
+    if (!pf.on || r.profiled || !r.has_peak) return RTX_OK;
+    const rtx_index::Inputs &in = ix->in[r.in_set];
+    const bool both = r.n_user != r.n_q;
+    ProfileParams p{};
+    p.src = ProfileSrc{both ? r.d_sel_status.p : r.d_fin_status.p, both ? r.d_sel_row_count.p : r.d_fin_row_count.p,
+                       both ? r.d_sel_row_begin.p : r.d_fin_row_begin.p, r.d_fin_node.p, r.d_fin_depth8.p, r.d_fin_hund.p, ix->fin_D,
+                       pf.d_parent.p, ix->d_node_depth.p, pf.d_ref_leaf.p, ix->nodes.size(), (uint32_t)ix->n_total};
+    p.n_pos = r.n_q;
+    p.n_user = (uint32_t)r.n_user;
+    p.perm = r.d_perm.p;
+    p.strand = both ? r.d_strand.p : nullptr;
+    p.exact = ExactRef{in.d_exact_ids.p, in.d_exact_off.p, r.dev_exact ? r.d_exact_grp.p : nullptr, ix->d_em_goff.p, ix->d_em_gids.p};
+    p.override_ok = !(pf.flags & (RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE));
+    p.cutoff = pf.cutoff;
+    p.n_nodes = ix->nodes.size();
+    p.clade = pf.d_acc.p;
+    p.direct = p.clade + p.n_nodes;
+    p.conf_sum = p.direct + p.n_nodes;
+    p.totals = p.conf_sum + p.n_nodes;
+    if (r.d_perm.n < r.n_q || !p.src.status || !p.src.row_begin) { set_error("internal: a profile over a batch without its arrays"); return RTX_ERR_STATE; }
+    hipStream_t s = ix->copy_stream ? ix->copy_stream : ix->stream;
+    if (both) RTX_HIP(hipStreamWaitEvent(s, r.ev_select, 0));
+    const bool timed = ix->stage_timing != 0u;
+    if (timed) {
+        for (auto &e : pf.ev)
+            if (!e) RTX_HIP(hipEventCreate(&e));
+        RTX_HIP(hipEventRecord(pf.ev[0], s));
+    }
+    launch_profile(s, p);
+    RTX_HIP(hipGetLastError());
+    if (timed) RTX_HIP(hipEventRecord(pf.ev[1], s));
+    RTX_HIP(hipStreamSynchronize(s));
+    if (timed) {
+        float ms = 0.f;
+        RTX_HIP(hipEventElapsedTime(&ms, pf.ev[0], pf.ev[1]));
+        pf.ms += ms;
+        pf.launches++;
+    }
+    r.profiled = true;
+    return RTX_OK;
+}
+
 // Streamed download: while later sub-batches are still running, the records of every finished one are copied
 // (copy_stream) and finalised on the calling thread, so that only the last sub-batch is left once the device is
 // done.  *done = false: not applicable (batch already complete: the bulk path with its threads is faster) or the
@@ -222,6 +270,7 @@ static int download_streamed(rtx_index *ix, rtx_index::ResultSet &r, rtx_index::
             if (flags & 2u) { set_error("lineage walk exceeded its row/depth bounds (internal error)"); return RTX_ERR_HIP; }
             if (flags & 1u) { redo = 1u; break; }  // arena overflow
             if ((rc = enqueue_text(ix, r))) return rc;  // the text (rtx_text.hip)
+            if ((rc = enqueue_profile(ix, r))) return rc;  // ... and the taxon profile (rtx_profile.hip)
             if (!ahead && then_run && (rc = run_staged(ix, next_flags, ran_next))) return rc;  // the device is free for the next batch
         }
     }
@@ -299,6 +348,7 @@ static int download_impl(rtx_index *ix, rtx_result_view *out, bool then_run, uin
         RTX_HIP(hipStreamSynchronize(ix->stream));
         nrows = fin;
         if ((rc = enqueue_text(ix, r))) return rc;  // (before run_staged: the next batch writes these rows)
+        if ((rc = enqueue_profile(ix, r))) return rc;
     }
     {   // the first download of a handle: the other result set (the two alternate, a view stays valid until the second-next
         // download) is allocated now, so that the second batch does not pay for its page-locked allocations
@@ -381,6 +431,91 @@ int rtx_batch_nearest(rtx_index *ix, const uint32_t **nearest, const uint32_t **
     if (!hr.has_nearest || hr.h_nearest.size() < hr.n_user || hr.h_ties.size() < hr.n_user) { set_error("rtx_batch_nearest: the last download's run had RTX_OPT_NEAREST off (or there was no download)"); return RTX_ERR_STATE; }
     if (nearest) *nearest = hr.h_nearest.data();
     if (ties) *ties = hr.h_ties.data();
+    return RTX_OK;
+}
+
+// ---- the taxon profile of the handle (rtx_profile.hip): open between begin and end; every accepted download adds its batch once
+int rtx_index_profile_begin(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t flags) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    rtx_index::Profile &pf = ix->prof;
+    if (cutoff_hundredths < 1u || cutoff_hundredths > 100u) { set_error("rtx_index_profile_begin: the cutoff is %u hundredths, not 1 .. 100", cutoff_hundredths); return RTX_ERR_INVALID; }
+    if (flags & ~(RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE)) { set_error("rtx_index_profile_begin: unknown flags %#x", flags); return RTX_ERR_INVALID; }
+    if (ix->n_refs != ix->n_total) { set_error("rtx_index_profile_begin: not on a reference-shard handle (its downloads hold no whole result)"); return RTX_ERR_INVALID; }
+    if (pf.on) { set_error("rtx_index_profile_begin: a profile is open already (rtx_index_profile_end)"); return RTX_ERR_STATE; }
+    const FlatNodes &f = ix->nodes;
+    const uint32_t nn = f.size();
+    // the Taxon node of every reference: the nodes come breadth first, so the deepest Taxon node over a reference is the last one written
+    std::vector<uint32_t> leaf(ix->n_total ? ix->n_total : 1u, kNoNode);
+    for (uint32_t v = 0; v < nn; v++)
+        if (f.type[v] == kTaxon) std::fill(leaf.begin() + f.begin[v], leaf.begin() + f.end[v], v);
+    if ((rc = pf.d_parent.alloc(nn)) || (rc = pf.d_ref_leaf.alloc(leaf.size())) || (rc = pf.d_acc.alloc(3u * (size_t)nn + 4u))) {
+        pf.d_parent.release(); pf.d_ref_leaf.release(); pf.d_acc.release();
+        return rc;
+    }
+    RTX_HIP(hipMemcpy(pf.d_parent.p, f.parent.data(), (size_t)nn * 4, hipMemcpyHostToDevice));
+    RTX_HIP(hipMemcpy(pf.d_ref_leaf.p, leaf.data(), leaf.size() * 4, hipMemcpyHostToDevice));
+    RTX_HIP(hipMemset(pf.d_acc.p, 0, (3u * (size_t)nn + 4u) * 8));
+    pf.cutoff = cutoff_hundredths;
+    pf.flags = flags;
+    pf.ms = 0.f;
+    pf.launches = 0;
+    pf.on = true;
+    return RTX_OK;
+}
+
+int rtx_index_profile_read(rtx_index *ix, rtx_profile_view *out) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (!out) { set_error("rtx_index_profile_read: null argument"); return RTX_ERR_INVALID; }
+    rtx_index::Profile &pf = ix->prof;
+    if (!pf.on) { set_error("rtx_index_profile_read: no profile is open (rtx_index_profile_begin)"); return RTX_ERR_STATE; }
+    const uint32_t nn = ix->nodes.size();
+    pf.h_acc.resize(3u * (size_t)nn + 4u);
+    // (every download has waited for its own kernel: what has been downloaded is in the counters)
+    RTX_HIP(hipMemcpy(pf.h_acc.data(), pf.d_acc.p, pf.h_acc.size() * 8, hipMemcpyDeviceToHost));
+    out->n_nodes = nn;
+    out->cutoff_hundredths = pf.cutoff;
+    out->flags = pf.flags;
+    out->clade = pf.h_acc.data();
+    out->direct = out->clade + nn;
+    out->conf_sum = out->direct + nn;
+    for (int i = 0; i < 4; i++) out->totals[i] = pf.h_acc[3u * (size_t)nn + i];
+    return RTX_OK;
+}
+
+int rtx_index_profile_reset(rtx_index *ix) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    rtx_index::Profile &pf = ix->prof;
+    if (!pf.on) { set_error("rtx_index_profile_reset: no profile is open"); return RTX_ERR_STATE; }
+    RTX_HIP(hipMemset(pf.d_acc.p, 0, (3u * (size_t)ix->nodes.size() + 4u) * 8));
+    pf.ms = 0.f;
+    pf.launches = 0;
+    return RTX_OK;
+}
+
+int rtx_index_profile_end(rtx_index *ix) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    rtx_index::Profile &pf = ix->prof;
+    if (!pf.on) { set_error("rtx_index_profile_end: no profile is open"); return RTX_ERR_STATE; }
+    pf.on = false;
+    pf.d_acc.release(); pf.d_parent.release(); pf.d_ref_leaf.release();
+    std::vector<uint64_t>().swap(pf.h_acc);
+    for (auto &e : pf.ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+    return RTX_OK;
+}
+
+// Milliseconds profile_kernel took and its launches since begin or reset (RTX_OPT_STAGE_TIMING on at the downloads; else 0 and 0)
+int rtx_index_profile_time(rtx_index *ix, float *ms, uint32_t *launches) {
+    if (!ix || (!ms && !launches)) { set_error("rtx_index_profile_time: null argument"); return RTX_ERR_INVALID; }
+    if (!ix->prof.on) { set_error("rtx_index_profile_time: no profile is open"); return RTX_ERR_STATE; }
+    if (ms) *ms = ix->prof.ms;
+    if (launches) *launches = ix->prof.launches;
     return RTX_OK;
 }
 

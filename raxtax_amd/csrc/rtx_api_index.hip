@@ -13,6 +13,12 @@ uint32_t index_swap_min_subs(rtx_index *index, uint32_t v) { if (!index) return 
 // RTX_OPT_RUN_AHEAD for the duration of a call of the host mirror (rtx_raxtax over several chunks); switched off: the last run's join is enqueued
 bool index_strand(const rtx_index *index) { return index && index->strand_opt != 0u; }
 bool index_nearest(const rtx_index *index) { return index && index->nearest_opt != 0u; }
+bool index_profile(const rtx_index *index, uint32_t *cutoff_hundredths, uint32_t *flags) {
+    if (!index || !index->prof.on) return false;
+    if (cutoff_hundredths) *cutoff_hundredths = index->prof.cutoff;
+    if (flags) *flags = index->prof.flags;
+    return true;
+}
 bool index_device_text(const rtx_index *index) { return index && index->device_text_opt != 0u; }
 uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v) {
     if (!index) return 0;

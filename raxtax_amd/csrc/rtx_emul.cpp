@@ -659,4 +659,28 @@ uint32_t emul_nearest_scan(const void *lo, const uint16_t *hi, uint32_t in_tile,
 // byte, high-bit word and shift of local reference rl in the packed counts of its tile (packed_count_pos)
 void emul_packed_count_pos(uint32_t rl, uint32_t *byte, uint32_t *hi_word, uint32_t *hi_shift) { packed_count_pos(rl, *byte, *hi_word, *hi_shift); }
 
+// The taxon profile of a batch as profile_kernel (rtx_profile.hip) accumulates it, query by query with the step the kernel calls
+// (profile_step): the path is walked from a_{L-1} up as the kernel's lanes walk it.  one[q]: the id of the query's only exact match where the
+// override applies, else kTextNoOverride.  The counters are added to (the caller zeroes them).
+void emul_profile(uint64_t nq, const uint8_t *status, const uint32_t *row_count, const uint64_t *row_begin, const uint32_t *row_node,
+                  const uint8_t *row_depth, const uint8_t *row_hund, uint32_t D, const uint32_t *parent, const uint8_t *node_depth,
+                  const uint32_t *ref_leaf, uint32_t n_nodes, uint32_t n_refs, const uint32_t *one, uint32_t cutoff, uint64_t *clade,
+                  uint64_t *direct, uint64_t *conf_sum, uint64_t *totals) {
+    const ProfileSrc src{status, row_count, reinterpret_cast<const unsigned long long *>(row_begin), row_node, row_depth, row_hund, D, parent, node_depth, ref_leaf, n_nodes, n_refs};
+    for (uint64_t q = 0; q < nq; q++) {
+        const ProfileStep st = profile_step(src, q, one[q], cutoff);
+        totals[0]++;
+        totals[st.kind == kProfClassified ? 1 : (st.kind == kProfUnclassified ? 2 : 3)]++;
+        if (st.kind != kProfClassified) continue;
+        uint32_t node = st.node;
+        for (uint32_t d = st.L; d-- > 0u;) {
+            if (node >= n_nodes) break;
+            clade[node]++;
+            conf_sum[node] += st.at(d);
+            if (d + 1u == st.L) direct[node]++;
+            node = parent[node];
+        }
+    }
+}
+
 }  // extern "C"

@@ -398,6 +398,7 @@ struct rtx_index {
         uint32_t in_set = 0;             // its input set (in[])
         bool dev_exact = false;          // the device looked its exact matches up (d_exact_grp)
         bool stream_dl = false;          // the streamed download applies (ev_sub, h_cursor_sub, h_fin_sub are recorded)
+        bool profiled = false;           // the run in the set has been added to the open profile (a second download of it adds nothing; record_batch clears it)
         // HBM as rtx_index_workspace_parts counts it: the processing order (part [6]), the exact-match groups ([5]), the rest ([7]; flags and cursors uncounted)
         struct Bytes { uint64_t order, groups, rest; };
         Bytes bytes() const {
@@ -470,9 +471,26 @@ struct rtx_index {
     bool set_busy[3] = {false, false, false};
     uint64_t n_run_ahead = 0, n_run_ahead_retry = 0;  // chunks enqueued ahead / run-aheads abandoned for an overflow of the chunk before (rtx_index_run_ahead_stats)
 
+    // ---- the taxon profile (rtx_index_profile_*, rtx_profile.hip): open between begin and end, nothing of it exists otherwise.  Every accepted
+    // download adds its batch once (enqueue_profile, where enqueue_text is called); a run that is repeated or abandoned has added nothing.
+    struct Profile {
+        bool on = false;
+        uint32_t cutoff = 0, flags = 0;        // hundredths; RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE (either one: no override)
+        DevBuf<unsigned long long> d_acc;      // clade | direct | conf_sum ([n_nodes] each) | totals [4]
+        // a parent per node rather than an [n_nodes][D] table of ancestors: 4 bytes per node against 128, and the climb of at most D dependent loads
+        // hits a table that stays in L2 (2 MB at 500 000 nodes); the Taxon node of every reference for the override
+        DevBuf<uint32_t> d_parent, d_ref_leaf;
+        std::vector<uint64_t> h_acc;           // rtx_index_profile_read: valid until the next read, reset or end
+        float ms = 0.f;                        // RTX_OPT_STAGE_TIMING: the kernel's time and launches since begin or reset
+        uint32_t launches = 0;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+    } prof;
+
     bool shared_device = false;  // rtx_raxtax_multi drives another handle on the same device beside this one: no second stream (begin_run)
     ~rtx_index() {
         for (auto e : events) (void)hipEventDestroy(e);
+        for (auto e : prof.ev)
+            if (e) (void)hipEventDestroy(e);
         for (auto e : ev_near) (void)hipEventDestroy(e);
         for (auto &r : rs) r.destroy_events();
         for (auto e : ev_set_free)
@@ -537,6 +555,7 @@ int alloc_result_set(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries,
 int settle_join(rtx_index *ix);        // (rtx_api_batch.hip) the handle's stream waits for the back halves of the last run, if that run left the join out
 int alloc_final(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries);  // (rtx_api_batch.hip) the final result arrays: n_queries per-query fields, arena_cap rows
 int enqueue_finalise(rtx_index *ix, const SubBatch &b, hipStream_t s);  // (rtx_api_batch.hip) behind the walks of a sub-batch
+int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r);  // the batch being downloaded joins the open profile, once (synchronous; nothing without one)
 // ---- rtx_text.hip
 int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of the batch being downloaded (synchronous)
 

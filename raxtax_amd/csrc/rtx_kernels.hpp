@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "raxtax_hip.h"
+#include "rtx_math.hpp"
 
 namespace rtx {
 
@@ -55,6 +56,13 @@ __device__ __forceinline__ void exact_range(const ExactRef &x, uint64_t qin, uin
         e0 = x.off[qin];
         e1 = x.off[qin + 1];
     }
+}
+// The query's ONLY exact match -- what the override of raxtax.rs:73-84 needs (rtx_text.hip, rtx_profile.hip) -- or kTextNoOverride
+__device__ __forceinline__ uint32_t exact_only(const ExactRef &x, uint64_t qin) {
+    uint64_t e0, e1;
+    const uint32_t *ids;
+    exact_range(x, qin, e0, e1, ids);
+    return e1 - e0 == 1u ? ids[e0] : kTextNoOverride;
 }
 struct ExactParams {  // rtx_exact.hip
     const uint8_t *bases;      // the batch (padded behind its end)
@@ -137,6 +145,23 @@ struct NearestParams {
     uint32_t *ties;     // [n_q] references with that count: the histogram bin of the peak
 };
 void launch_nearest(hipStream_t s, const NearestParams &p);
+
+// rtx_profile.hip: what the queries of a downloaded batch add to the taxon profile of the handle (rtx_index_profile_*), a lane per position
+// of the processing order
+struct ProfileParams {
+    ProfileSrc src;         // the per-query fields of the chosen orientation, the final rows, the node tables of the open profile
+    uint64_t n_pos;         // positions of the processing order (the twins' included under RTX_OPT_STRAND)
+    uint32_t n_user;        // queries as the caller passed them
+    const uint32_t *perm;   // [n_pos] query at every position
+    const uint8_t *strand;  // [n_user] under RTX_OPT_STRAND (a minus-strand query takes the exact matches of its twin, query n_user + q), else null
+    ExactRef exact;
+    bool override_ok;       // neither RTX_SKIP_EXACT_MATCHES nor RTX_RAW_CONFIDENCE
+    uint32_t cutoff;        // hundredths, 1 .. 100
+    uint32_t n_nodes;
+    unsigned long long *clade, *direct, *conf_sum;  // [n_nodes]
+    unsigned long long *totals;                     // [4] queries, classified, unclassified, unclassifiable
+};
+void launch_profile(hipStream_t s, const ProfileParams &p);
 
 struct KmerParams {
     const uint8_t *bases;

@@ -795,4 +795,51 @@ RTX_HD TextRow text_row(const TextSrc &t, const char *label, uint64_t label_len,
     return r;
 }
 
+// ---------------------------------------------------------------------------
+// Taxon profile (rtx_profile.hip): what one query adds.  Its BEST LINEAGE is the one `.out` prints first -- the Taxon leaf of its only
+// exact match with 1.00 on every level where the override of raxtax.rs:73-84 applies (one != kTextNoOverride), else its first row.  The path
+// a_0 .. a_{depth-1} runs from the child of the root down to that node; L = the leading levels whose hundredths reach the cutoff.  The
+// query counts under a_0 .. a_{L-1} (clade, conf_sum) and ends at a_{L-1} (direct).
+// ---------------------------------------------------------------------------
+struct ProfileSrc {
+    const uint8_t *status;                 // [queries] the per-query fields of the chosen orientation
+    const uint32_t *row_count;
+    const unsigned long long *row_begin;
+    const uint32_t *row_node;              // the final rows (rtx_result_view)
+    const uint8_t *row_depth, *row_hund;
+    uint32_t D;
+    const uint32_t *parent;                // [n_nodes] rtx_nodes_view numbering; the root has none
+    const uint8_t *node_depth;             // [n_nodes]
+    const uint32_t *ref_leaf;              // [n_refs] the Taxon node of a reference's own lineage
+    uint32_t n_nodes, n_refs;
+};
+constexpr uint32_t kProfUnclassifiable = 0u, kProfUnclassified = 1u, kProfClassified = 2u;
+struct ProfileStep {
+    uint32_t kind;        // kProf*
+    uint32_t node, L;     // a_{L-1} and L (classified only)
+    const uint8_t *hund;  // hundredths per level of the best lineage; null: 100 on every level (the override)
+    RTX_HD uint32_t at(uint32_t d) const { return hund ? hund[d] : 100u; }
+};
+RTX_HD ProfileStep profile_step(const ProfileSrc &s, uint64_t q, uint32_t one, uint32_t cutoff) {
+    ProfileStep r{kProfUnclassifiable, 0u, 0u, nullptr};
+    if (s.status[q] != 0 || s.row_count[q] == 0u) return r;  // (0: RTX_Q_OK)
+    uint32_t node, depth;
+    if (one != kTextNoOverride && one < s.n_refs) {
+        node = s.ref_leaf[one];
+        depth = node < s.n_nodes ? s.node_depth[node] : 0u;
+    } else {
+        const uint64_t row = s.row_begin[q];
+        node = s.row_node[row];
+        depth = s.row_depth[row];
+        r.hund = s.row_hund + row * s.D;
+    }
+    uint32_t L = 0;
+    while (L < depth && r.at(L) >= cutoff) L++;
+    r.kind = L ? kProfClassified : kProfUnclassified;
+    r.L = L;
+    for (uint32_t d = depth; d > L && L && node < s.n_nodes; d--) node = s.parent[node];  // a_{depth-1} -> a_{L-1}
+    r.node = node;
+    return r;
+}
+
 }  // namespace rtx

@@ -46,14 +46,7 @@ struct TextParams {
 
 __device__ __forceinline__ uint32_t text_one(const TextParams &p, uint64_t q) {  // the only exact match, or kTextNoOverride
     if (!p.override_ok) return kTextNoOverride;
-    if (p.grp) {
-        const uint32_t g = p.grp[q];
-        if (g == 0xFFFFFFFFu) return kTextNoOverride;
-        const uint32_t a = p.goff[g];
-        return p.goff[g + 1] - a == 1u ? p.gids[a] : kTextNoOverride;
-    }
-    const uint64_t a = p.ex_off[q];
-    return p.ex_off[q + 1] - a == 1u ? p.ex_ids[a] : kTextNoOverride;
+    return exact_only(ExactRef{p.ex_ids, p.ex_off, p.grp, p.goff, p.gids}, q);
 }
 
 __device__ __forceinline__ uint32_t text_rows(const TextParams &p, uint64_t q, uint32_t one) {
