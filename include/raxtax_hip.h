@@ -40,7 +40,8 @@ extern "C" {
                              6: RTX_OPT_RUN_AHEAD (23), RTX_RETRY_CHUNK from rtx_batch_download_then_run under it, rtx_index_run_ahead_stats
                                 (still 6 with RTX_OPT_NEAREST (26), RTX_NO_REF, rtx_batch_nearest and rtx_raxtax_multi_ex2: exports and an option
                                 that is off by default, nothing that exists changes shape; and with the taxon profile, rtx_index_profile_* /
-                                rtx_profile_merge / rtx_profile_format: exports only) */
+                                rtx_profile_merge / rtx_profile_format: exports only; and with RTX_OPT_DEREP (27), rtx_derep_*,
+                                rtx_batch_prefetch_weights and rtx_raxtax_last_derep: exports and an option that is off by default) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -302,6 +303,16 @@ int rtx_index_set_batch(rtx_index *index, uint32_t sub_batch);
                                       * Exact on the pruned path as well.  Not available on a reference shard (RTX_ERR_INVALID); staged rtx_shard_* runs and
                                       * rtx_debug_evaluate fill nothing.  Setting it drops the uploaded batch like the options below. */
 #define RTX_NO_REF 0xFFFFFFFFu       /* no reference (rtx_batch_nearest, rtx_query_hit_fn) */
+#define RTX_OPT_DEREP 27             /* 0 (default): no new code runs, nothing is allocated, every output is what it is without the option.  1: DEREPLICATION --
+                                      * rtx_raxtax / rtx_raxtax_multi* classify each distinct read of a chunk once: a device stage in front of the handle
+                                      * (rtx_derep_run, on a stream of its own, a chunk ahead of the handle) finds the byte-identical copies, the handle
+                                      * receives the distinct reads alone, and every query of the caller gets the result of its representative -- its own
+                                      * message, label and callbacks, in input order, byte for byte those of a run without the option (the result of a
+                                      * query never depends on the rest of its batch).  Per chunk: a copy in another chunk is classified again.  The text
+                                      * is formatted on the host whatever RTX_OPT_DEVICE_TEXT says (a device line carries one label); an open profile
+                                      * counts a distinct read with its number of copies (rtx_batch_prefetch_weights).  The handles of a call must agree
+                                      * on it (RTX_ERR_INVALID).  Only the mirror honours it, as RTX_OPT_DEVICE_TEXT: rtx_batch_* and rtx_classify_batch
+                                      * ignore it, it shapes no workspace and drops no uploaded batch. */
 /* RTX_OPT_SUB_BATCH, _PACKED_COUNTS, _HIT_PAIR, _TILE_PRUNE and _PROB_MODE shape the workspace that rtx_batch_upload sizes:
  * setting one of them drops the uploaded batch (rtx_batch_run then fails with RTX_ERR_STATE until the batch is uploaded again). */
 int rtx_index_set_option(rtx_index *index, int option, uint64_t value);
@@ -327,6 +338,9 @@ int rtx_index_run_ahead_stats(const rtx_index *index, uint64_t *enqueued_ahead, 
 /* RTX_DEFAULT_EXACT_HASH_MASK (default: all ones; 0 restores it): the hash of the device exact-match table is ANDed with this mask.
  * Tests pass a mask of a few bits so that most sequences collide in slot and tag and every probe ends in the byte compare. */
 #define RTX_DEFAULT_EXACT_HASH_MASK 2
+/* RTX_DEFAULT_DEREP_HASH_MASK (default: all ones; 0 restores it): the hash of rtx_derep_run is ANDed with this mask, read at every run.
+ * Tests pass a mask of two bits so that every probe of its table ends in the byte compare. */
+#define RTX_DEFAULT_DEREP_HASH_MASK 3
 int rtx_set_default_option(int option, uint64_t value);
 
 /* ------------------------------------------------------------------------- */
@@ -453,6 +467,13 @@ int rtx_profile_merge(rtx_profile_view *const *views, uint32_t n, uint64_t *clad
 int64_t rtx_profile_format(const rtx_tree *tree, const uint64_t *clade, const uint64_t *direct, const uint64_t *conf_sum,
                            const uint64_t totals[4], uint32_t cutoff_hundredths, char *out, uint64_t cap);
 
+/* One weight per query for the batch that the NEXT rtx_batch_prefetch / rtx_batch_upload stages (call it first): the number of reads the
+ * query stands for in the open profile -- every counter takes weight (conf_sum: weight x hundredths) where it takes 1 without; 0: the query
+ * does not count.  The path of rtx_batch_prefetch_labels: the same input set, asynchronous, taken or dropped at that prefetch; a count that
+ * does not match the batch is dropped (every query then counts once).  Indexed by the caller's query under RTX_OPT_STRAND.  rtx_raxtax*
+ * stage the copies of every distinct read this way under RTX_OPT_DEREP. */
+int rtx_batch_prefetch_weights(rtx_index *index, uint64_t n_queries, const uint32_t *weights);
+
 /* The same in stages, so that a caller (bench.py) can keep inputs resident in HBM and
  * time the device part alone, or overlap stages of different batches. */
 int rtx_batch_upload(rtx_index *index, uint64_t n_queries, const uint8_t *bases,
@@ -467,6 +488,28 @@ int rtx_batch_download(rtx_index *index, rtx_result_view *out);
  * finalisation between them).  Nothing staged: plain rtx_batch_download.  Under RTX_OPT_RUN_AHEAD the staged batch is enqueued before the
  * current one has finished, and the call may return RTX_RETRY_CHUNK (> 0). */
 int rtx_batch_download_then_run(rtx_index *index, rtx_result_view *out, uint32_t flags);
+
+/* ---- dereplication (rtx_derep.hip; RTX_OPT_DEREP is the host mirror's use of it) --------------------------------------------------------
+ * Which queries of a batch are copies of an earlier one -- what `vsearch --derep_fulllength` does in front of a classifier, on the device.
+ *   rtx_derep_create  an object of its own on GPU `device`: one stream, its own buffers (they only grow), no rtx_index.  It may run beside
+ *                     a handle on the same device; distinct objects may be driven from distinct threads, calls on one are serialised by
+ *                     the caller.  RTX_ERR_NO_DEVICE without a gfx950.
+ *   rtx_derep_run     rep[q] = the lowest q' <= q whose sequence is identical to that of q: the same length and the same bytes as given
+ *                     (ambiguity codes and bytes above 15 compared as they are; a read and its reverse complement are different reads).
+ *                     *n_unique = the number of q with rep[q] == q.  Exact -- a hash only picks the candidates, the bytes decide -- and
+ *                     the same whatever the scheduling.  bases / base_off as rtx_batch_prefetch takes them.  n == 0: RTX_OK, *n_unique = 0;
+ *                     n > 2^31 - 2 or a base_off that is not monotone: RTX_ERR_INVALID.  Synchronous.
+ *   rtx_derep_plan    the host side of the map (no device): uniq[u] = the queries with rep[q] == q, ascending (*n_unique of them);
+ *                     slot[q] = the position of rep[q] in uniq; size[u] = the queries whose representative is uniq[u].  All three hold n
+ *                     entries.  RTX_ERR_INVALID if rep is no such map (rep[q] > q, or rep[rep[q]] != rep[q]).
+ *   rtx_raxtax_last_derep  the last rtx_raxtax* call of the process: the queries of its dereplicated chunks, the distinct reads handed to
+ *                     the handles and the busy seconds of the stage (map, plan and the copy of the distinct reads); all 0 with the option off. */
+typedef struct rtx_derep rtx_derep;
+int rtx_derep_create(int device, rtx_derep **out);
+int rtx_derep_run(rtx_derep *d, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *rep /*[n]*/, uint64_t *n_unique);
+void rtx_derep_destroy(rtx_derep *d);
+int rtx_derep_plan(uint64_t n, const uint32_t *rep, uint32_t *uniq /*[n]*/, uint32_t *slot /*[n]*/, uint32_t *size /*[n]*/, uint64_t *n_unique);
+int rtx_raxtax_last_derep(uint64_t *queries, uint64_t *distinct, double *busy_seconds);
 
 /* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
  * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte

@@ -21,6 +21,8 @@ RTX_SKIP_EXACT_MATCHES = 1
 RTX_RAW_CONFIDENCE = 2
 RTX_TEXT_TSV = 4
 RTX_Q_OK, RTX_Q_NO_KMERS, RTX_Q_ALL_KMERS = 0, 1, 2
+RTX_OPT_DEREP = 27                 # rtx_index_set_option: raxtax() classifies each distinct read of a chunk once
+RTX_DEFAULT_DEREP_HASH_MASK = 3    # rtx_set_default_option: the hash of rtx_derep_run ANDed with a mask (tests)
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 
 u8p = C.POINTER(C.c_uint8)
@@ -166,6 +168,12 @@ _SIGNATURES = {
     "rtx_index_profile_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
     "rtx_profile_merge": (C.c_int, [C.POINTER(C.POINTER(ProfileView)), C.c_uint32, u64p, u64p, u64p, u64p]),
     "rtx_profile_format": (C.c_int64, [C.c_void_p, u64p, u64p, u64p, u64p, C.c_uint32, C.c_char_p, C.c_uint64]),
+    "rtx_batch_prefetch_weights": (C.c_int, [C.c_void_p, C.c_uint64, u32p]),
+    "rtx_derep_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
+    "rtx_derep_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, C.POINTER(C.c_uint64)]),
+    "rtx_derep_destroy": (None, [C.c_void_p]),
+    "rtx_derep_plan": (C.c_int, [C.c_uint64, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]),
+    "rtx_raxtax_last_derep": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

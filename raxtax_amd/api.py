@@ -279,7 +279,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False):
+                 nearest: bool = False, derep: bool = False):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -335,6 +335,8 @@ class Index:
         self.nearest_on = bool(nearest)
         if nearest:   # RTX_OPT_NEAREST: every run also names the reference that holds each query's peak
             check(self._lib.rtx_index_set_option(self._h, 26, 1))
+        if derep:   # RTX_OPT_DEREP: raxtax() classifies each distinct read of a chunk once (rtx_derep.hip); classify() ignores it
+            check(self._lib.rtx_index_set_option(self._h, _lib.RTX_OPT_DEREP, 1))
         self._view = ResultView()
         self._keep = None
 
@@ -397,6 +399,12 @@ class Index:
                                                ptr(exact_off, u64p)))
         else:
             check(self._lib.rtx_batch_prefetch(self._h, n_q, ptr(bases, u8p), ptr(base_off, u64p), None, None))
+
+    def prefetch_weights(self, weights: np.ndarray):
+        """One weight per query of the batch the NEXT prefetch() / upload() / classify() stages: the reads it stands for in the open profile
+        (rtx_batch_prefetch_weights).  A count that does not match that batch is dropped."""
+        w = np.ascontiguousarray(weights, dtype=np.uint32)
+        check(self._lib.rtx_batch_prefetch_weights(self._h, len(w), ptr(w if len(w) else np.zeros(1, np.uint32), u32p)))
 
     def activate(self):
         check(self._lib.rtx_batch_activate(self._h))
@@ -740,6 +748,56 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     if err:
         raise err[0]
     check(rc)
+
+
+class Derep:
+    """The dereplication stage on one GPU (rtx_derep): an object of its own beside any Index, one stream, buffers that only grow."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        self._h = None
+        h = C.c_void_p()
+        check(self._lib.rtx_derep_create(device, C.byref(h)))
+        self._h = h
+        self.n_unique = 0
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_derep_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, bases: np.ndarray, base_off: np.ndarray) -> np.ndarray:
+        """rep[q] = the lowest query whose sequence is byte for byte that of q (rtx_derep_run); n_unique = the queries with rep[q] == q."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        n = len(base_off) - 1
+        rep = np.zeros(max(n, 1), dtype=np.uint32)
+        nu = C.c_uint64()
+        check(self._lib.rtx_derep_run(self._h, n, ptr(bases if len(bases) else np.zeros(1, np.uint8), u8p), ptr(base_off, u64p), ptr(rep, u32p), C.byref(nu)))
+        self.n_unique = int(nu.value)
+        return rep[:n]
+
+
+def derep_plan(rep: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """rtx_derep_plan: (uniq, slot, size) of a dereplication map -- the queries with rep[q] == q in ascending order, the position of every
+    query's representative among them, and the number of queries every one of them stands for.  RtxError if `rep` is no such map."""
+    rep = np.ascontiguousarray(rep, dtype=np.uint32)
+    n = len(rep)
+    uniq, slot, size = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+    nu = C.c_uint64()
+    check(_lib.load().rtx_derep_plan(n, ptr(rep if n else np.zeros(1, np.uint32), u32p), ptr(uniq, u32p), ptr(slot, u32p), ptr(size, u32p), C.byref(nu)))
+    return uniq[:nu.value].copy(), slot[:n].copy(), size[:nu.value].copy()
+
+
+def raxtax_last_derep() -> Tuple[int, int, float]:
+    """rtx_raxtax_last_derep: (queries of the dereplicated chunks, distinct reads handed to the handles, busy seconds of the stage) of the
+    last raxtax() call of this process; all 0 when its handles had derep off."""
+    q, u, b = C.c_uint64(), C.c_uint64(), C.c_double()
+    check(_lib.load().rtx_raxtax_last_derep(C.byref(q), C.byref(u), C.byref(b)))
+    return int(q.value), int(u.value), float(b.value)
 
 
 def raxtax_last_timing() -> Tuple[List[float], int]:

@@ -9,6 +9,7 @@
 //   PREFIX/raxtax.strand  (--strand both) label, + or -, peak, t per query, in the order of raxtax.out
 //   PREFIX/raxtax.profile (--profile CUTOFF) the taxon profile of the whole run: reads under and at every taxon whose confidence reaches CUTOFF (rtx_profile_format)
 //   PREFIX/raxtax.hits    (--hits) label, + or -, peak, t, ties, id and lineage of the nearest reference per query, in the order of raxtax.out
+//   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
@@ -175,6 +176,7 @@ int main(int argc, char **argv) {
     bool device_format = false;
     bool both_strands = false;  // --strand both: RTX_OPT_STRAND on every handle
     bool want_hits = false;     // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
+    bool derep = false;         // --derep: RTX_OPT_DEREP on every handle (each distinct read of a chunk is classified once; the files are the same)
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -218,6 +220,7 @@ int main(int argc, char **argv) {
             both_strands = v == "both";
         }
         else if (a == "--hits") want_hits = true;
+        else if (a == "--derep") derep = true;
         else if (a == "--profile") {
             char *end = nullptr;
             const char *v = val();
@@ -230,7 +233,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--profile CUTOFF]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--profile CUTOFF] [--derep]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -242,6 +245,10 @@ int main(int argc, char **argv) {
     }
     const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
+    if (device_format && derep) {
+        fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
+        device_format = false;
+    }
     if (device_format && both_strands) {
         fprintf(stderr, "[INFO ] --strand both: the result lines are formatted on the host (--device-format has no effect)\n");
         device_format = false;
@@ -404,6 +411,7 @@ int main(int argc, char **argv) {
                 if (rcs[k] == RTX_OK && device_format) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEVICE_TEXT, 1);
                 if (rcs[k] == RTX_OK && both_strands) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_STRAND, 1);
                 if (rcs[k] == RTX_OK && want_hits) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_NEAREST, 1);
+                if (rcs[k] == RTX_OK && derep) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEREP, 1);
                 if (rcs[k] == RTX_OK && profile_cutoff)
                     rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
@@ -460,6 +468,8 @@ int main(int argc, char **argv) {
     };
     int rc = RTX_OK;
     uint64_t n = 0;
+    uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
+    double derep_busy = 0;
     bool parse_failed = false;
     for (;;) {
         Parsed pz;
@@ -490,6 +500,12 @@ int main(int argc, char **argv) {
             rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
                                       both_strands || want_hits ? +info : nullptr, &sink);
             n += nb;
+            if (derep) {
+                uint64_t dq = 0, du = 0;
+                double db_ = 0;
+                if (rtx_raxtax_last_derep(&dq, &du, &db_) == RTX_OK) { derep_queries += dq; derep_distinct += du; derep_busy += db_; }
+                if (timing) fprintf(stderr, "[TIMING] dereplication of this block: %llu queries, %llu distinct, busy %.3f s (ahead of the device stage)\n", (unsigned long long)dq, (unsigned long long)du, db_);
+            }
             if (timing) {  // busy seconds of the pipeline stages of this block (which stage bounds the run)
                 double busy[4];
                 uint64_t nch = 0;
@@ -513,6 +529,10 @@ int main(int argc, char **argv) {
     if (want_hits) sink.hits.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
+    if (derep) {  // (per chunk: a copy in another chunk counts as a distinct read of its own)
+        fprintf(stderr, "[INFO ] --derep: %llu queries, %llu distinct\n", (unsigned long long)derep_queries, (unsigned long long)derep_distinct);
+        if (timing) t_log << ", \"derep_busy\": " << derep_busy;
+    }
     if (!join_bin_writer()) return 74;
     lap("database_cache_wait");
     if (timing) fprintf(stderr, "{\"n_queries\": %llu, %s}\n", (unsigned long long)n, t_log.str().c_str());

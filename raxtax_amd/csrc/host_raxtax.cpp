@@ -75,12 +75,38 @@ private:
 struct LastTiming { double busy[4]; uint64_t n_chunks; };
 std::mutex g_timing_mu;
 LastTiming g_timing{{0, 0, 0, 0}, 0};
+struct LastDerep { uint64_t queries, distinct; double busy; };  // rtx_raxtax_last_derep (under g_timing_mu)
+LastDerep g_derep{0, 0, 0.0};
 
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
 // (label, strand, peak, t) of the query whose message follows (rtx_query_info_fn); empty: nobody asked
 // ... with the nearest reference and its ties behind them (rtx_query_hit_fn; RTX_NO_REF and 0 with RTX_OPT_NEAREST off)
 using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32_t, uint32_t)>;
+
+// Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the
+// one thread that dereplicates, which was most of the stage; the buffers travel between the chunks of a call through a pool, so that
+// only the first few of them fault their pages in.
+struct ByteBuf {
+    uint8_t *p = nullptr;
+    size_t cap = 0;
+    bool reserve(size_t n) {
+        if (n <= cap) return true;
+        free(p);
+        cap = n + n / 8 + 64;
+        p = static_cast<uint8_t *>(malloc(cap));
+        if (!p) cap = 0;
+        return p != nullptr;
+    }
+    ByteBuf() = default;
+    ByteBuf(const ByteBuf &) = delete;
+    ByteBuf(ByteBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    ByteBuf &operator=(ByteBuf &&o) noexcept {
+        if (this != &o) { free(p); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    ~ByteBuf() { free(p); }
+};
 
 // One chunk of queries travelling through the stages of run().
 struct Chunk {
@@ -123,6 +149,14 @@ struct Chunk {
     std::vector<Arena> out_arena, tsv_arena;   // one per formatting thread
     std::vector<uint64_t> msg_off, tsv_off;    // [nq] offset of the query's text in its thread's arena
     std::vector<uint32_t> msg_arena;           // [nq] which arena
+    // RTX_OPT_DEREP: the handle is given the distinct reads of the chunk alone, and whatever comes back per query is read through slot[]
+    uint64_t nu = 0;                   // queries handed to the handle: nq, or the distinct reads of a chunk that has copies
+    const uint8_t *dev_bases = nullptr;  // what every device call of the chunk (and the host lookup) is given: the caller's arrays,
+    const uint64_t *dev_off = nullptr;   // or u_bases / u_off ([nu + 1], from 0: rtx_batch_prefetch wants contiguous offsets)
+    std::vector<uint32_t> slot;        // [nq] position of query i's representative among the distinct reads; empty: i itself (no copies, or the option off)
+    std::vector<uint32_t> size;        // [nu] copies of every distinct read: its weight in an open profile
+    ByteBuf u_bases;
+    std::vector<uint64_t> u_off;
     rtx_text_view text{};              // RTX_OPT_DEVICE_TEXT: the messages as the device formatted them (valid as long as `res`)
     rtx_result_view res{};
     int stage = 0;                     // 1: exact matches looked up (or left to the device), 2: classified, 3: formatted, 4: sent
@@ -136,6 +170,9 @@ struct Chunk {
 // and for all of them
 //   lookup thread : exact-match ids (host hash map, raxtax.rs:42) -- only for handles without the device lookup
 //                   (rtx_index_has_exact_lookup): otherwise the ids come back with the results of the device stage
+//                   Under RTX_OPT_DEREP it first finds the copies of the chunk on the device (rtx_derep_run, a stream of its own beside
+//                   the handle's) and cuts the chunk down to its distinct reads: the handle classifies those, the format thread and
+//                   the sender go on per query of the caller (Chunk::slot)
 //   calling thread: the sender, one message per query in INPUT order (raxtax.rs:85-87): chunk 0, 1, 2 ... as they become ready.
 // A handle keeps two result sets, so the view of its k-th chunk stays valid until its (k + 2)-th is classified.
 int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_t n_queries, const char *const *labels,
@@ -180,11 +217,33 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         rtx::set_error("rtx_raxtax: the open taxon profile has flags %#x, the call %#x (skip_exact_matches / raw_confidence must match)", prof_flags, flags);
         return RTX_ERR_INVALID;
     }
+    // RTX_OPT_DEREP: on every handle, or on none.  One stage object (rtx_derep.hip) per distinct device for the duration of the call: the
+    // lookup thread runs chunk c through the object of handle c mod n_dev's device while that handle still classifies an earlier chunk.
+    const bool derep = rtx::index_derep(indices[0]);
+    for (uint32_t d = 0; d < n_dev; d++)
+        if (rtx::index_derep(indices[d]) != derep) { rtx::set_error("rtx_raxtax_multi: the handles disagree on RTX_OPT_DEREP"); return RTX_ERR_INVALID; }
+    struct Dereps {
+        std::vector<rtx_derep *> of;  // per handle; handles of one device share an object
+        std::vector<rtx_derep *> own;
+        ~Dereps() { for (auto *p : own) rtx_derep_destroy(p); }
+    } dereps;
+    if (derep) {
+        dereps.of.assign(n_dev, nullptr);
+        for (uint32_t d = 0; d < n_dev; d++) {
+            for (uint32_t e = 0; e < d && !dereps.of[d]; e++)
+                if (rtx::index_device(indices[e]) == rtx::index_device(indices[d])) dereps.of[d] = dereps.of[e];
+            if (dereps.of[d]) continue;
+            const int rc = rtx_derep_create(rtx::index_device(indices[d]), &dereps.of[d]);
+            if (rc) return rc;
+            dereps.own.push_back(dereps.of[d]);
+        }
+    }
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
         // RTX_OPT_DEVICE_TEXT: the messages come from the device (rtx_text.hip), set up for this tree and these flags
-        dev_text[d] = rtx::index_device_text(indices[d]) && !both;
+        // (not under RTX_OPT_DEREP: a device line carries one label, a distinct read has as many as it has copies)
+        dev_text[d] = rtx::index_device_text(indices[d]) && !both && !derep;
         if (dev_text[d]) {
             const int rc = rtx_index_text_setup(indices[d], tree, flags | (tsv ? RTX_TEXT_TSV : 0u));
             if (rc) return rc;
@@ -220,10 +279,13 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     std::vector<Chunk> chunks(n_chunks);
     for (uint64_t c = 0; c < n_chunks; c++) {
         chunks[c].q0 = c * chunk_size;
-        chunks[c].nq = std::min<uint64_t>(chunk_size, n_queries - chunks[c].q0);
+        chunks[c].nq = chunks[c].nu = std::min<uint64_t>(chunk_size, n_queries - chunks[c].q0);
+        chunks[c].dev_bases = bases;
+        chunks[c].dev_off = base_off + chunks[c].q0;
     }
     // busy seconds of the stages (rtx_raxtax_last_timing: which stage bounds an end-to-end run)
-    double busy_lookup = 0, busy_send = 0;
+    double busy_lookup = 0, busy_send = 0, busy_derep = 0;
+    uint64_t derep_queries = 0, derep_distinct = 0;
     std::vector<double> busy_device(n_dev, 0.0), busy_format(n_dev, 0.0);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     std::mutex mu;
@@ -250,27 +312,66 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     const uint64_t ahead = 2ull * n_dev;  // chunks a stage may run ahead of the next one
     std::mutex pool_mu;
     std::vector<Chunk::Arena> arena_pool;  // message arenas between the sender (done with a chunk) and the format threads (next chunk)
+    std::vector<ByteBuf> bases_pool;       // ... and the arrays of distinct reads between the sender and the lookup thread (RTX_OPT_DEREP)
 
     std::thread lookup([&] {
         for (uint64_t c = 0; c < n_chunks; c++) {
             Chunk &ch = chunks[c];
-            if (dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
+            if (!derep && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
             if (c >= ahead && !wait_stage(c - ahead, 2)) return;
+            if (derep) {  // the copies of the chunk, on the device (a stream of its own beside the handle's); then the map's host side
+                const double t_r0 = now();
+                std::vector<uint32_t> rep(ch.nq);
+                uint64_t nu = 0;
+                int rc = rtx_derep_run(dereps.of[c % n_dev], ch.nq, bases, base_off + ch.q0, rep.data(), &nu);
+                if (!rc && nu < ch.nq) {  // (a chunk without copies goes on as it came)
+                    std::vector<uint32_t> uniq(ch.nq);
+                    ch.slot.resize(ch.nq);
+                    ch.size.resize(ch.nq);
+                    rc = rtx_derep_plan(ch.nq, rep.data(), uniq.data(), ch.slot.data(), ch.size.data(), &nu);
+                    if (!rc) {
+                        ch.size.resize(nu);
+                        ch.u_off.assign(nu + 1, 0);
+                        for (uint64_t u = 0; u < nu; u++) ch.u_off[u + 1] = ch.u_off[u] + (base_off[ch.q0 + uniq[u] + 1] - base_off[ch.q0 + uniq[u]]);
+                        {
+                            std::lock_guard<std::mutex> g(pool_mu);
+                            if (!bases_pool.empty()) { ch.u_bases = std::move(bases_pool.back()); bases_pool.pop_back(); }
+                        }
+                        if (!ch.u_bases.reserve(ch.u_off[nu] + 1)) { fail(RTX_ERR_OOM, "no memory for the distinct reads of a chunk"); return; }
+                        // runs of neighbouring distinct reads that are neighbours in the input as well (most of a chunk with few copies) move in one memcpy
+                        parallel_ranges(nu, nt_lookup, [&](uint64_t a, uint64_t b) {
+                            for (uint64_t u = a; u < b;) {
+                                uint64_t v = u + 1;
+                                while (v < b && uniq[v] == uniq[v - 1] + 1u) v++;
+                                if (ch.u_off[v] > ch.u_off[u]) memcpy(ch.u_bases.p + ch.u_off[u], bases + base_off[ch.q0 + uniq[u]], ch.u_off[v] - ch.u_off[u]);
+                                u = v;
+                            }
+                        });
+                        ch.nu = nu;
+                        ch.dev_bases = ch.u_bases.p;
+                        ch.dev_off = ch.u_off.data();
+                    }
+                }
+                if (rc) { fail(rc, rtx_last_error()); return; }
+                derep_queries += ch.nq;
+                derep_distinct += ch.nu;
+                busy_derep += now() - t_r0;
+                if (dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
+            }
             const double t_l0 = now();
-            std::vector<const uint32_t *> ptr(ch.nq);
-            std::vector<uint32_t> cnt(ch.nq);
-            parallel_ranges(ch.nq, nt_lookup, [&](uint64_t a, uint64_t b) {
+            std::vector<const uint32_t *> ptr(ch.nu);
+            std::vector<uint32_t> cnt(ch.nu);
+            parallel_ranges(ch.nu, nt_lookup, [&](uint64_t a, uint64_t b) {
                 for (uint64_t i = a; i < b; i++) {
-                    const uint64_t q = ch.q0 + i;
                     const uint32_t *ids = nullptr;
-                    cnt[i] = (uint32_t)rtx_tree_exact_matches(tree, bases + base_off[q], base_off[q + 1] - base_off[q], &ids);
+                    cnt[i] = (uint32_t)rtx_tree_exact_matches(tree, ch.dev_bases + ch.dev_off[i], ch.dev_off[i + 1] - ch.dev_off[i], &ids);
                     ptr[i] = ids;
                 }
             });
-            ch.exact_off.assign(ch.nq + 1, 0);
-            for (uint64_t i = 0; i < ch.nq; i++) ch.exact_off[i + 1] = ch.exact_off[i] + cnt[i];
-            ch.exact_ids.resize(ch.exact_off[ch.nq]);
-            for (uint64_t i = 0; i < ch.nq; i++) std::copy(ptr[i], ptr[i] + cnt[i], ch.exact_ids.begin() + ch.exact_off[i]);
+            ch.exact_off.assign(ch.nu + 1, 0);
+            for (uint64_t i = 0; i < ch.nu; i++) ch.exact_off[i + 1] = ch.exact_off[i] + cnt[i];
+            ch.exact_ids.resize(ch.exact_off[ch.nu]);
+            for (uint64_t i = 0; i < ch.nu; i++) std::copy(ptr[i], ptr[i] + cnt[i], ch.exact_ids.begin() + ch.exact_off[i]);
             busy_lookup += now() - t_l0;
             set_stage(c, 1);
         }
@@ -285,8 +386,12 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             const int rc = rtx_batch_prefetch_labels(indices[d], ch.nq, labels + ch.q0);
             if (rc) return rc;
         }
-        if (dev_lookup[d]) return rtx_batch_prefetch(indices[d], ch.nq, bases, base_off + ch.q0, nullptr, nullptr);
-        return rtx_batch_prefetch(indices[d], ch.nq, bases, base_off + ch.q0, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
+        if (prof && !ch.size.empty()) {  // a distinct read counts with its copies in the open profile (the same input set as well)
+            const int rc = rtx_batch_prefetch_weights(indices[d], ch.nu, ch.size.data());
+            if (rc) return rc;
+        }
+        if (dev_lookup[d]) return rtx_batch_prefetch(indices[d], ch.nu, ch.dev_bases, ch.dev_off, nullptr, nullptr);
+        return rtx_batch_prefetch(indices[d], ch.nu, ch.dev_bases, ch.dev_off, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
     };
     auto device_loop = [&](uint32_t d) {
         bool running = false;  // the kernels of chunk c have been enqueued already (behind the download of the chunk before it)
@@ -315,8 +420,9 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             if (!rc) rc = staged ? rtx_batch_download_then_run(indices[d], &ch.res, flags) : rtx_batch_download(indices[d], &ch.res);
             if (rc == RTX_RETRY_CHUNK) {  // the run-ahead was abandoned (this chunk outgrew a buffer with the next one enqueued already): this chunk on its own
                 rc = dev_text[d] ? rtx_batch_prefetch_labels(indices[d], ch.nq, labels + ch.q0) : RTX_OK;
-                if (!rc) rc = dev_lookup[d] ? rtx_batch_upload(indices[d], ch.nq, bases, base_off + ch.q0, nullptr, nullptr)
-                                   : rtx_batch_upload(indices[d], ch.nq, bases, base_off + ch.q0, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
+                if (!rc && prof && !ch.size.empty()) rc = rtx_batch_prefetch_weights(indices[d], ch.nu, ch.size.data());
+                if (!rc) rc = dev_lookup[d] ? rtx_batch_upload(indices[d], ch.nu, ch.dev_bases, ch.dev_off, nullptr, nullptr)
+                                   : rtx_batch_upload(indices[d], ch.nu, ch.dev_bases, ch.dev_off, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
                 if (!rc) rc = rtx_batch_run(indices[d], flags);
                 if (!rc) rc = rtx_batch_download(indices[d], &ch.res);
                 staged = false;  // (the next chunk is staged, activated and run at the head of the loop)
@@ -328,25 +434,37 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 const uint32_t *xi = nullptr;
                 rc = rtx_batch_exact_matches(indices[d], &xo, &xi);
                 if (!rc) {  // copied: the format thread reads them while the next chunk is classified
-                    ch.exact_off.assign(xo, xo + ch.nq + 1);
-                    ch.exact_ids.assign(xi, xi + xo[ch.nq]);
+                    ch.exact_off.assign(xo, xo + ch.nu + 1);
+                    ch.exact_ids.assign(xi, xi + xo[ch.nu]);
                 }
             }
             if (!rc && want_strands) {
                 const uint8_t *st = nullptr;
                 const uint32_t *pk = nullptr;
                 rc = rtx_batch_strands(indices[d], &st, &pk);
-                if (!rc) {
-                    ch.strand.assign(st, st + ch.nq);
-                    ch.peak.assign(pk, pk + ch.nq);
+                if (!rc) {  // (per query of the caller, as everything the sender reads)
+                    if (ch.slot.empty()) {
+                        ch.strand.assign(st, st + ch.nq);
+                        ch.peak.assign(pk, pk + ch.nq);
+                    } else {
+                        ch.strand.resize(ch.nq);
+                        ch.peak.resize(ch.nq);
+                        for (uint64_t i = 0; i < ch.nq; i++) { ch.strand[i] = st[ch.slot[i]]; ch.peak[i] = pk[ch.slot[i]]; }
+                    }
                 }
             }
             if (!rc && near && info) {
                 const uint32_t *nr = nullptr, *ti = nullptr;
                 rc = rtx_batch_nearest(indices[d], &nr, &ti);
                 if (!rc) {
-                    ch.nearest.assign(nr, nr + ch.nq);
-                    ch.ties.assign(ti, ti + ch.nq);
+                    if (ch.slot.empty()) {
+                        ch.nearest.assign(nr, nr + ch.nq);
+                        ch.ties.assign(ti, ti + ch.nq);
+                    } else {
+                        ch.nearest.resize(ch.nq);
+                        ch.ties.resize(ch.nq);
+                        for (uint64_t i = 0; i < ch.nq; i++) { ch.nearest[i] = nr[ch.slot[i]]; ch.ties[i] = ti[ch.slot[i]]; }
+                    }
                 }
             }
             if (rc) { fail(rc, rtx_last_error()); return; }
@@ -363,8 +481,14 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             Chunk &ch = chunks[c];
             const double t_f0 = now();
             ch.differ.assign(ch.nq, 0);
-            ch.status.assign(ch.res.status, ch.res.status + ch.nq);
-            ch.t.assign(ch.res.t, ch.res.t + ch.nq);
+            if (ch.slot.empty()) {
+                ch.status.assign(ch.res.status, ch.res.status + ch.nq);
+                ch.t.assign(ch.res.t, ch.res.t + ch.nq);
+            } else {
+                ch.status.resize(ch.nq);
+                ch.t.resize(ch.nq);
+                for (uint64_t i = 0; i < ch.nq; i++) { ch.status[i] = ch.res.status[ch.slot[i]]; ch.t[i] = ch.res.t[ch.slot[i]]; }
+            }
             ch.msg_off.assign(ch.nq, 0);
             ch.msg_arena.assign(ch.nq, 0);
             if (tsv) ch.tsv_off.assign(ch.nq, 0);
@@ -396,9 +520,13 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 // (confidences: 256 bytes per row, lineage, depth, local signal) and the lineage string are cache misses per query -- what
                 // the stage waited for (0.6 us per query on sixteen threads where the arithmetic needs 0.2).  Three prefetch stages ahead of
                 // the formatting: the row arrays of query i + 24, the string object of i + 16 (its index has arrived), the characters of i + 8.
-                auto row_of = [&](uint64_t j) { return ch.res.row_begin[j]; };
+                // (j, i: queries of the caller; the view is read at their representative's position at(.), RTX_OPT_DEREP)
+                const uint32_t *const slot = ch.slot.empty() ? nullptr : ch.slot.data();
+                auto at = [slot](uint64_t j) -> uint64_t { return slot ? slot[j] : j; };
+                auto row_of = [&](uint64_t j) { return ch.res.row_begin[at(j)]; };
+                auto has_rows = [&](uint64_t j) { const uint64_t s = at(j); return ch.res.status[s] == RTX_Q_OK && ch.res.row_count[s] != 0; };
                 auto stage1 = [&](uint64_t j) {
-                    if (j >= b || ch.res.status[j] != RTX_Q_OK || ch.res.row_count[j] == 0) return;
+                    if (j >= b || !has_rows(j)) return;
                     const uint64_t r = row_of(j);
                     __builtin_prefetch(ch.res.row_conf + r * (ch.res.row_conf_stride ? ch.res.row_conf_stride : RTX_MAX_DEPTH));
                     __builtin_prefetch(ch.res.row_lineage + r);
@@ -408,11 +536,11 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 auto stage2 = [&](uint64_t j) {
                     if (j >= b) return;
                     __builtin_prefetch(labels[ch.q0 + j]);  // (the labels are the caller's strings, one allocation each)
-                    if (ch.res.status[j] != RTX_Q_OK || ch.res.row_count[j] == 0) return;
+                    if (!has_rows(j)) return;
                     __builtin_prefetch(&tree->lineages[ch.res.row_lineage[row_of(j)]]);
                 };
                 auto stage3 = [&](uint64_t j) {
-                    if (j >= b || ch.res.status[j] != RTX_Q_OK || ch.res.row_count[j] == 0) return;
+                    if (j >= b || !has_rows(j)) return;
                     const std::string &l = tree->lineages[ch.res.row_lineage[row_of(j)]];
                     __builtin_prefetch(l.data());
                     __builtin_prefetch(l.data() + 64);
@@ -429,10 +557,10 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                         stage2(i + 16);
                         stage3(i + 8);
                     }
-                    const uint64_t q = ch.q0 + i;
-                    const uint64_t ne = ch.exact_off[i + 1] - ch.exact_off[i];
+                    const uint64_t q = ch.q0 + i, s = at(i);
+                    const uint64_t ne = ch.exact_off[s + 1] - ch.exact_off[s];
                     if (!skip_exact_matches && ne > 1) {  // raxtax.rs:43-53 (the info! lines go to the log in the CLI)
-                        const uint32_t *ids = ch.exact_ids.data() + ch.exact_off[i];
+                        const uint32_t *ids = ch.exact_ids.data() + ch.exact_off[s];
                         auto parent = [&](uint32_t id) {
                             const std::string &l = tree->lineages[id];
                             const size_t k = l.rfind(',');
@@ -441,9 +569,9 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                         for (uint64_t j = 1; j < ne; j++)
                             if (parent(ids[j]) != parent(ids[0])) { ch.differ[i] = 1; break; }
                     }
-                    if (dev_text[d] || ch.res.status[i] != RTX_Q_OK) continue;  // (device text: the lines are formatted already)
+                    if (dev_text[d] || ch.res.status[s] != RTX_Q_OK) continue;  // (device text: the lines are formatted already)
                     const uint64_t len = base_off[q + 1] - base_off[q];
-                    const uint64_t rows = ch.res.row_count[i];
+                    const uint64_t rows = ch.res.row_count[s];
                     const size_t need = (rows + 1) * (strlen(labels[q]) + 4096 + 8 * RTX_MAX_DEPTH) + len + 64;
                     char *ob = oa.room(need);
                     char *tb = ta ? ta->room(need + rows * len) : nullptr;
@@ -455,8 +583,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                         (void)rtx_revcomp(seq, len, rc_seq.data());
                         seq = rc_seq.data();
                     }
-                    const int64_t n = rtx_format_query(tree, &ch.res, i, labels[q], seq, len,
-                                                       ch.exact_ids.data() + ch.exact_off[i], ne, flags, ob, need,
+                    const int64_t n = rtx_format_query(tree, &ch.res, s, labels[q], seq, len,
+                                                       ch.exact_ids.data() + ch.exact_off[s], ne, flags, ob, need,
                                                        tb, tb ? need + rows * len : 0, &tsv_len);
                     if (n < 0) { rc_fmt = (int)n; return; }
                     ch.msg_arena[i] = r;
@@ -515,8 +643,12 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint32_t>().swap(ch.peak);
         std::vector<uint32_t>().swap(ch.nearest);
         std::vector<uint32_t>().swap(ch.ties);
+        std::vector<uint32_t>().swap(ch.slot);
+        std::vector<uint32_t>().swap(ch.size);
+        std::vector<uint64_t>().swap(ch.u_off);
         {
             std::lock_guard<std::mutex> g(pool_mu);
+            if (ch.u_bases.p) bases_pool.push_back(std::move(ch.u_bases));
             for (auto &a : ch.out_arena) arena_pool.push_back(std::move(a));
             for (auto &a : ch.tsv_arena) arena_pool.push_back(std::move(a));
         }
@@ -535,6 +667,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         for (uint32_t d = 0; d < n_dev; d++) { bd = std::max(bd, busy_device[d]); bf = std::max(bf, busy_format[d]); }
         std::lock_guard<std::mutex> g(g_timing_mu);
         g_timing = {{any_host_lookup ? busy_lookup : 0.0, bd, bf, busy_send}, n_chunks};
+        g_derep = {derep_queries, derep_distinct, busy_derep};
     }
     if (failed != RTX_OK) { rtx::set_error("%s", failed_msg.c_str()); return failed; }
     if (warnings)  // raxtax.rs:93-95
@@ -616,6 +749,37 @@ extern "C" int rtx_raxtax_last_timing(double busy[4], uint64_t *n_chunks) {
     std::lock_guard<std::mutex> g(g_timing_mu);
     for (int i = 0; i < 4; i++) busy[i] = g_timing.busy[i];
     if (n_chunks) *n_chunks = g_timing.n_chunks;
+    return RTX_OK;
+}
+
+extern "C" int rtx_raxtax_last_derep(uint64_t *queries, uint64_t *distinct, double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_derep.queries;
+    if (distinct) *distinct = g_derep.distinct;
+    if (busy_seconds) *busy_seconds = g_derep.busy;
+    return RTX_OK;
+}
+
+// The host side of a dereplication map (rtx_derep_run): the distinct queries in ascending order, every query's position among them and the
+// size of every cluster.  Refuses a map that is none: a representative behind its query, or one that is not its own representative.
+extern "C" int rtx_derep_plan(uint64_t n, const uint32_t *rep, uint32_t *uniq, uint32_t *slot, uint32_t *size, uint64_t *n_unique) {
+    if (n_unique) *n_unique = 0;
+    if (n > 0xFFFFFFFFull || (n && (!rep || !uniq || !slot || !size))) { rtx::set_error("rtx_derep_plan: invalid argument"); return RTX_ERR_INVALID; }
+    uint64_t nu = 0;
+    for (uint64_t q = 0; q < n; q++) {
+        const uint32_t r = rep[q];
+        if (r > q || rep[r] != r) { rtx::set_error("rtx_derep_plan: rep[%llu] = %u is no representative (rep[q] <= q and rep[rep[q]] == rep[q])", (unsigned long long)q, r); return RTX_ERR_INVALID; }
+        if (r == q) {
+            uniq[nu] = (uint32_t)q;
+            size[nu] = 1;
+            slot[q] = (uint32_t)nu++;
+        } else {
+            slot[q] = slot[r];
+            size[slot[r]]++;
+        }
+    }
+    for (uint64_t u = nu; u < n; u++) uniq[u] = size[u] = 0;
+    if (n_unique) *n_unique = nu;
     return RTX_OK;
 }
 

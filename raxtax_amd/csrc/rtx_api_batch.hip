@@ -1289,6 +1289,8 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
     // labels staged for this batch (rtx_batch_prefetch_labels) belong to it alone: taken or dropped here, whatever becomes of the call
     const bool with_labels = in.labels_pending && in.n_labels == n_queries;
     in.labels_pending = in.has_labels = false;
+    const bool with_weights = in.weights_pending && in.n_weights == n_queries;  // ... and so do its weights (rtx_batch_prefetch_weights)
+    in.weights_pending = in.has_weights = false;
     if (n_queries == 0 || !base_off || (!bases && base_off[n_queries])) {
         set_error("rtx_batch_upload: invalid argument");
         return RTX_ERR_INVALID;
@@ -1359,6 +1361,7 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
     in.n_exact = n_exact;
     in.has_exact = exact_off != nullptr;
     in.has_labels = with_labels;
+    in.has_weights = with_weights;
     in.staged = true;
     return RTX_OK;
 }

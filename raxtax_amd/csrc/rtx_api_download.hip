@@ -120,6 +120,7 @@ int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r) {
     p.exact = ExactRef{in.d_exact_ids.p, in.d_exact_off.p, r.dev_exact ? r.d_exact_grp.p : nullptr, ix->d_em_goff.p, ix->d_em_gids.p};
     p.override_ok = !(pf.flags & (RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE));
     p.cutoff = pf.cutoff;
+    p.weight = in.has_weights && in.n_weights == r.n_user ? in.d_weights.p : nullptr;
     p.n_nodes = ix->nodes.size();
     p.clade = pf.d_acc.p;
     p.direct = p.clade + p.n_nodes;
@@ -516,6 +517,28 @@ int rtx_index_profile_time(rtx_index *ix, float *ms, uint32_t *launches) {
     if (!ix->prof.on) { set_error("rtx_index_profile_time: no profile is open"); return RTX_ERR_STATE; }
     if (ms) *ms = ix->prof.ms;
     if (launches) *launches = ix->prof.launches;
+    return RTX_OK;
+}
+
+// One weight per query for the batch that the NEXT rtx_batch_prefetch / rtx_batch_upload stages: how many reads the query stands for in the
+// open profile (the host mirror under RTX_OPT_DEREP: the copies of a distinct read).  The path of rtx_batch_prefetch_labels: the input set
+// beside the current one, asynchronous H2D on the transfer stream, taken or dropped at that prefetch (a count that does not match: dropped).
+int rtx_batch_prefetch_weights(rtx_index *ix, uint64_t n_queries, const uint32_t *weights) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (!weights && n_queries) { set_error("rtx_batch_prefetch_weights: null weights"); return RTX_ERR_INVALID; }
+    rtx_index::Inputs &in = ix->in[ix->cur_in ^ 1u];
+    if (!ix->h2d_stream) RTX_HIP(hipStreamCreateWithFlags(&ix->h2d_stream, hipStreamNonBlocking));
+    if (!in.ready) RTX_HIP(hipEventCreateWithFlags(&in.ready, hipEventDisableTiming));
+    if (in.recorded) RTX_HIP(hipEventSynchronize(in.ready));  // the last transfer out of this set's pinned buffers
+    if (ix->ev_activated) RTX_HIP(hipStreamWaitEvent(ix->h2d_stream, ix->ev_activated, 0));
+    if ((rc = in.h_weights.resize(n_queries + 1)) || (rc = in.d_weights.alloc(n_queries + 1))) return rc;
+    if (n_queries) std::memcpy(in.h_weights.data(), weights, n_queries * 4);
+    if (n_queries) RTX_HIP(hipMemcpyAsync(in.d_weights.p, in.h_weights.data(), n_queries * 4, hipMemcpyHostToDevice, ix->h2d_stream));
+    RTX_HIP(hipEventRecord(in.ready, ix->h2d_stream));
+    in.recorded = true;
+    in.weights_pending = true;
+    in.n_weights = n_queries;
     return RTX_OK;
 }
 

@@ -20,6 +20,7 @@ bool index_profile(const rtx_index *index, uint32_t *cutoff_hundredths, uint32_t
     return true;
 }
 bool index_device_text(const rtx_index *index) { return index && index->device_text_opt != 0u; }
+bool index_derep(const rtx_index *index) { return index && index->derep_opt != 0u; }
 uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v) {
     if (!index) return 0;
     const uint32_t old = index->run_ahead_opt;
@@ -776,6 +777,7 @@ int rtx_index_set_batch(rtx_index *index, uint32_t sub_batch) {
 int rtx_set_default_option(int option, uint64_t value) {
     if (option == RTX_DEFAULT_SEGMENT_CLASSES) { g_seg_classes = value ? 1 : 0; return RTX_OK; }
     if (option == RTX_DEFAULT_EXACT_HASH_MASK) { g_em_hash_mask = value ? value : ~0ull; return RTX_OK; }
+    if (option == RTX_DEFAULT_DEREP_HASH_MASK) { set_derep_hash_mask(value ? value : ~0ull); return RTX_OK; }
     set_error("rtx_set_default_option: unknown option %d", option);
     return RTX_ERR_INVALID;
 }
@@ -842,6 +844,10 @@ int rtx_index_set_option(rtx_index *index, int option, uint64_t value) {
             return RTX_OK;
         case RTX_OPT_DEVICE_TEXT:
             index->device_text_opt = value ? 1u : 0u;
+            return RTX_OK;
+        case RTX_OPT_DEREP:  // honoured by the host mirror alone (host_raxtax.cpp): nothing of the handle changes
+            if (value > 1) break;
+            index->derep_opt = (uint32_t)value;
             return RTX_OK;
         case RTX_OPT_STRAND:
             if (value > 1) break;

@@ -1,0 +1,217 @@
+// Dereplication on the device (rtx_derep_*): which queries of a batch are byte-for-byte copies of an earlier one.  Amplicon runs hold the
+// same read many times over (what `vsearch --derep_fulllength` is run for in front of a classifier); the result of a query never depends on
+// the rest of its batch, so a copy need not be classified at all.  The stage stands IN FRONT of a handle (host_raxtax.cpp: RTX_OPT_DEREP):
+// an object of its own with one stream and its own buffers, so that the lookup thread of rtx_raxtax can run it on chunk c + 1 while the
+// handle on that device classifies chunk c.
+//
+// The bases travel as a handle's do (rtx_ingest.hip: two per byte through pinned memory, unpacked to one byte per base on the device; a
+// batch with a byte above 15 as it is), then three kernels:
+//   hash     one wave per query: the 64-bit hash of rtx_exact.hip over the 8-byte words of the sequence (em_mix_word / em_finish)
+//   insert   one wave per query: linear probing in an open-addressing table of 2^bits >= 2 n slots that hold query + 1.  An empty slot is
+//            claimed with a compare-and-swap; an occupant with the same hash and length is compared word by word -- the hash is a
+//            pre-filter, the bytes decide, always.  An equal occupant becomes the query's OWNER; a query that claims a slot owns itself.
+//            Which copy owns a cluster depends on the scheduling, so every member also lowers cluster_min[owner] to its own index.
+//            No wave ever waits for another: a slot goes from empty to occupied once and never changes again, a lost compare-and-swap
+//            returns the occupant, the table is at most half full.
+//   resolve  rep[q] = cluster_min[owner[q]]: the lowest index with q's sequence, whatever the scheduling was; the queries with
+//            rep[q] == q are counted, a ballot and one atomic per wave.
+// Identical queries probe the same slots in the same order and slots are never vacated: the second one to arrive meets the first before
+// it can meet an empty slot, so a cluster has exactly one owner.
+#include <atomic>
+
+#include "rtx_index.hpp"
+
+namespace {
+
+std::atomic<uint64_t> g_derep_hash_mask{~0ull};  // RTX_DEFAULT_DEREP_HASH_MASK (tests: a hash of two bits, so that every probe ends in the byte compare)
+
+struct DerepParams {
+    const uint8_t *bases;      // one byte per base, padded behind the end (em_load_word)
+    const uint64_t *base_off;  // [n + 1]
+    uint32_t n;
+    uint64_t *hash;            // [n]
+    uint32_t *table;           // [2^bits] query + 1; 0: empty
+    uint32_t bits;
+    uint64_t hash_mask;
+    uint32_t *owner;           // [n] the query that holds the slot of q's sequence
+    uint32_t *cluster_min;     // [n] at an owner: the lowest query of its cluster (preset to all ones)
+    uint32_t *rep;             // [n] | [1] the number of q with rep[q] == q
+};
+
+__global__ __launch_bounds__(256) void derep_hash_kernel(DerepParams p) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q >= p.n) return;  // wave-uniform
+    const uint64_t b0 = p.base_off[q], len = p.base_off[q + 1] - b0;
+    const uint8_t *seq = p.bases + b0;
+    const uint64_t nw = (len + 7u) >> 3;
+    uint64_t sum = 0;
+    for (uint64_t j = lane; j < nw; j += 64) sum += em_mix_word(em_load_word(seq, len, j), j);
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
+    if (lane == 0) p.hash[q] = em_finish(sum, len) & p.hash_mask;
+}
+
+__global__ __launch_bounds__(256) void derep_insert_kernel(DerepParams p) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (q >= p.n) return;  // wave-uniform
+    const uint64_t b0 = p.base_off[q], len = p.base_off[q + 1] - b0;
+    const uint8_t *seq = p.bases + b0;
+    const uint64_t nw = (len + 7u) >> 3;
+    const uint64_t h = p.hash[q];
+    const uint32_t mask = (uint32_t)((1ull << p.bits) - 1ull);
+    uint32_t slot = em_slot(h, p.bits);
+    uint32_t own = q;
+    for (uint64_t probe = 0; probe <= mask; probe++) {  // wave-uniform; the table is at most half full: an empty slot comes
+        uint32_t e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(p.table + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (e == 0u) {
+            uint32_t old = 0u;
+            if (lane == 0) old = atomicCAS(p.table + slot, 0u, q + 1u);
+            e = __builtin_amdgcn_readfirstlane(old);
+            if (e == 0u) break;  // the slot is this query's: it owns itself
+        }
+        const uint32_t o = e - 1u;  // an occupant (found, or the winner of the compare-and-swap)
+        if (p.hash[o] == h) {
+            const uint64_t o0 = p.base_off[o], olen = p.base_off[o + 1] - o0;
+            if (olen == len) {
+                bool differ = false;
+                for (uint64_t j = lane; j < nw; j += 64) differ = differ || em_load_word(seq, len, j) != em_load_word(p.bases + o0, len, j);
+                if (__ballot(differ) == 0ull) { own = o; break; }
+            }
+        }
+        slot = (slot + 1u) & mask;
+    }
+    if (lane == 0) {
+        p.owner[q] = own;
+        atomicMin(p.cluster_min + own, q);
+    }
+}
+
+// (no lane leaves early: the ballot runs over whole waves)
+__global__ __launch_bounds__(256) void derep_resolve_kernel(DerepParams p) {
+    const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+    bool self = false;
+    if (q < p.n) {
+        const uint32_t r = p.cluster_min[p.owner[q]];
+        p.rep[q] = r;
+        self = r == q;
+    }
+    const unsigned long long m = __ballot(self);
+    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(p.rep + p.n, (uint32_t)__popcll(m));
+}
+
+}  // namespace
+
+namespace rtxi {
+void set_derep_hash_mask(uint64_t mask) { g_derep_hash_mask.store(mask); }
+}  // namespace rtxi
+
+// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
+// classifies beside the stage (a buffer that has to grow is replaced, with headroom, so that chunks of one size allocate once).
+struct rtx_derep {
+    int device = -1;
+    hipStream_t stream = nullptr;
+    DevBuf<uint8_t> d_packed, d_bases;
+    DevBuf<uint64_t> d_base_off, d_hash;
+    DevBuf<uint32_t> d_table, d_owner, d_cluster_min, d_rep;
+    PinBuf<uint8_t> h_packed;
+    PinBuf<uint64_t> h_base_off;
+    PinBuf<uint32_t> h_rep;
+    ~rtx_derep() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+template <class T>
+int grow(DevBuf<T> &b, size_t count) {
+    if (b.p && count <= b.n) return RTX_OK;
+    return b.alloc(count + count / 4 + 64);
+}
+}  // namespace
+
+extern "C" {
+
+int rtx_derep_create(int device, rtx_derep **out) {
+    if (!out) { set_error("rtx_derep_create: null argument"); return RTX_ERR_INVALID; }
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
+        return RTX_ERR_NO_DEVICE;
+    }
+    RTX_HIP(hipSetDevice(device));
+    hipDeviceProp_t prop;
+    RTX_HIP(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
+        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
+        return RTX_ERR_NO_DEVICE;
+    }
+    auto d = new rtx_derep();
+    d->device = device;
+    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
+        set_error("hipStreamCreate failed");
+        delete d;
+        return RTX_ERR_HIP;
+    }
+    *out = d;
+    return RTX_OK;
+}
+
+void rtx_derep_destroy(rtx_derep *d) {
+    if (!d) return;
+    (void)hipSetDevice(d->device);
+    delete d;
+}
+
+int rtx_derep_run(rtx_derep *d, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *rep, uint64_t *n_unique) {
+    if (!d || !n_unique) { set_error("rtx_derep_run: null argument"); return RTX_ERR_INVALID; }
+    *n_unique = 0;
+    if (n == 0) return RTX_OK;
+    if (n > 0x7FFFFFFEull) { set_error("rtx_derep_run: %llu queries in one batch (at most 2^31 - 2)", (unsigned long long)n); return RTX_ERR_INVALID; }
+    if (!base_off || !rep) { set_error("rtx_derep_run: null argument"); return RTX_ERR_INVALID; }
+    for (uint64_t q = 0; q < n; q++)
+        if (base_off[q + 1] < base_off[q]) { set_error("base_off not monotone at query %llu", (unsigned long long)q); return RTX_ERR_INVALID; }
+    const uint64_t total = base_off[n] - base_off[0];
+    if (total && !bases) { set_error("rtx_derep_run: null bases"); return RTX_ERR_INVALID; }
+    RTX_HIP(hipSetDevice(d->device));
+    uint32_t bits = 1;
+    while ((1ull << bits) < 2ull * n) bits++;
+    const size_t slots = (size_t)1 << bits;
+    int rc;
+    if ((rc = d->h_packed.resize(total + 64)) || (rc = d->h_base_off.resize(n + 1)) || (rc = d->h_rep.resize(n + 1)) || (rc = grow(d->d_packed, total + 64)) ||
+        (rc = grow(d->d_bases, total + 64)) || (rc = grow(d->d_base_off, n + 1)) || (rc = grow(d->d_hash, n)) || (rc = grow(d->d_owner, n)) ||
+        (rc = grow(d->d_cluster_min, n)) || (rc = grow(d->d_rep, n + 1)) || (rc = d->d_table.alloc(slots)))
+        return rc;
+    hipStream_t s = d->stream;
+    for (uint64_t q = 0; q <= n; q++) d->h_base_off[q] = base_off[q] - base_off[0];
+    // two bases per byte over PCIe; a byte above 15 is no code of parser.rs:11-34: such a batch travels as it is (rtx_batch_prefetch)
+    const bool packed = total == 0 || rtx::pack_nibbles_mt(bases + base_off[0], total, d->h_packed.data(), rtx::host_threads(4u));
+    if (!packed) std::memcpy(d->h_packed.data(), bases + base_off[0], total);
+    if (total) RTX_HIP(hipMemcpyAsync(d->d_packed.p, d->h_packed.data(), packed ? (total + 1) / 2 : total, hipMemcpyHostToDevice, s));
+    RTX_HIP(hipMemcpyAsync(d->d_base_off.p, d->h_base_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
+    if (packed) {
+        rtx::launch_unpack_nibbles(s, d->d_packed.p, d->d_bases.p, total, total + 64);  // ... and 64 zero bytes: em_load_word reads past an end
+    } else {
+        if (total) RTX_HIP(hipMemcpyAsync(d->d_bases.p, d->d_packed.p, total, hipMemcpyDeviceToDevice, s));
+        RTX_HIP(hipMemsetAsync(d->d_bases.p + total, 0, 64, s));
+    }
+    RTX_HIP(hipMemsetAsync(d->d_table.p, 0, slots * 4, s));
+    RTX_HIP(hipMemsetAsync(d->d_cluster_min.p, 0xFF, n * 4, s));
+    RTX_HIP(hipMemsetAsync(d->d_rep.p + n, 0, 4, s));
+    DerepParams p{d->d_bases.p, d->d_base_off.p, (uint32_t)n, d->d_hash.p, d->d_table.p, bits, g_derep_hash_mask.load(),
+                  d->d_owner.p, d->d_cluster_min.p, d->d_rep.p};
+    const dim3 waves((unsigned)((n + 3u) / 4u)), threads((unsigned)((n + 255u) / 256u));
+    hipLaunchKernelGGL(derep_hash_kernel, waves, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(derep_insert_kernel, waves, dim3(256), 0, s, p);
+    hipLaunchKernelGGL(derep_resolve_kernel, threads, dim3(256), 0, s, p);
+    RTX_HIP(hipGetLastError());
+    RTX_HIP(hipMemcpyAsync(d->h_rep.data(), d->d_rep.p, (n + 1) * 4, hipMemcpyDeviceToHost, s));
+    RTX_HIP(hipStreamSynchronize(s));
+    std::memcpy(rep, d->h_rep.data(), n * 4);
+    *n_unique = d->h_rep[n];
+    return RTX_OK;
+}
+
+}  // extern "C"

@@ -12,15 +12,6 @@
 
 namespace rtx {
 
-// 8 bytes at seq + 8 j, zero beyond len (the buffers are padded: reading up to 7 bytes past the end is safe)
-__device__ __forceinline__ uint64_t em_load_word(const uint8_t *seq, uint64_t len, uint64_t j) {
-    uint64_t w;
-    __builtin_memcpy(&w, seq + 8u * j, 8);
-    const uint64_t rest = len - 8u * j;  // > 0
-    if (rest < 8u) w &= (1ull << (8u * rest)) - 1ull;
-    return w;
-}
-
 __global__ __launch_bounds__(256) void exact_match_kernel(ExactParams p) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);

@@ -261,6 +261,11 @@ struct rtx_index {
         PinBuf<uint64_t> h_label_off;
         uint64_t n_labels = 0;
         bool labels_pending = false, has_labels = false;
+        // the weights of the batch for the taxon profile (rtx_batch_prefetch_weights: the path of the labels)
+        DevBuf<uint32_t> d_weights;
+        PinBuf<uint32_t> h_weights;
+        uint64_t n_weights = 0;
+        bool weights_pending = false, has_weights = false;
         hipEvent_t ready = nullptr;        // its transfer has arrived
     } in[2];
     uint32_t cur_in = 0;               // the set of the current (activated) batch
@@ -448,6 +453,7 @@ struct rtx_index {
     uint32_t text_flags = 0;
     uint64_t text_tree_uid = 0;      // rtx_tree::uid of the tree the lineage table was uploaded from
     uint32_t device_text_opt = 0;    // RTX_OPT_DEVICE_TEXT
+    uint32_t derep_opt = 0;          // RTX_OPT_DEREP: rtx_raxtax* classify each distinct read of a chunk once (rtx_derep.hip); the handle itself never reads it
     DevBuf<char> d_lin_bytes, d_text;
     DevBuf<uint64_t> d_lin_off;
     DevBuf<uint8_t> d_lin_depth, d_text_tmp;
@@ -556,6 +562,8 @@ int settle_join(rtx_index *ix);        // (rtx_api_batch.hip) the handle's strea
 int alloc_final(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries);  // (rtx_api_batch.hip) the final result arrays: n_queries per-query fields, arena_cap rows
 int enqueue_finalise(rtx_index *ix, const SubBatch &b, hipStream_t s);  // (rtx_api_batch.hip) behind the walks of a sub-batch
 int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r);  // the batch being downloaded joins the open profile, once (synchronous; nothing without one)
+// ---- rtx_derep.hip
+void set_derep_hash_mask(uint64_t mask);  // RTX_DEFAULT_DEREP_HASH_MASK (rtx_set_default_option)
 // ---- rtx_text.hip
 int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of the batch being downloaded (synchronous)
 

@@ -76,6 +76,14 @@ struct ExactParams {  // rtx_exact.hip
     uint64_t hash_mask;        // all ones; tests weaken the hash (RTX_DEFAULT_EXACT_HASH_MASK) so that chains and tags collide
 };
 void launch_exact_match(hipStream_t s, const ExactParams &p);
+// 8 bytes at seq + 8 j, zero beyond len (the buffers are padded: reading up to 7 bytes past the end is safe); rtx_exact.hip, rtx_derep.hip
+__device__ __forceinline__ uint64_t em_load_word(const uint8_t *seq, uint64_t len, uint64_t j) {
+    uint64_t w;
+    __builtin_memcpy(&w, seq + 8u * j, 8);
+    const uint64_t rest = len - 8u * j;  // > 0
+    if (rest < 8u) w &= (1ull << (8u * rest)) - 1ull;
+    return w;
+}
 // rtx_ingest.hip: bases two per byte over PCIe (host packer, device unpacker)
 void launch_unpack_nibbles(hipStream_t s, const uint8_t *packed, uint8_t *bases, uint64_t n_bases, uint64_t n_out);
 bool pack_nibbles_mt(const uint8_t *in, uint64_t n, uint8_t *out, unsigned nt);
@@ -160,6 +168,7 @@ struct ProfileParams {
     uint32_t n_nodes;
     unsigned long long *clade, *direct, *conf_sum;  // [n_nodes]
     unsigned long long *totals;                     // [4] queries, classified, unclassified, unclassifiable
+    const uint32_t *weight; // [n_user] how many reads query q stands for (rtx_batch_prefetch_weights); null: 1 each
 };
 void launch_profile(hipStream_t s, const ProfileParams &p);
 

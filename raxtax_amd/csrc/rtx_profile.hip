@@ -26,9 +26,19 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
            ((uint32_t)__builtin_amdgcn_readlane((int)v, 32) + (uint32_t)__builtin_amdgcn_readlane((int)v, 48));
 }
 
+// ... of 64-bit values (weighted queries: a weight times 64 lanes times 100 hundredths does not fit 32 bits); all 64 lanes active
+__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
+    return v;
+}
+
 constexpr uint32_t kProfileThreads = 256;
 
 // (no lane leaves early: the reductions run over whole waves)
+// W: every query counts with its weight (ProfileParams::weight: the reads it stands for; 0 = not at all) -- wave sums in the place of the
+// popcounts, 64-bit throughout; without weights the kernel is the one it was.
+template <bool W>
 __global__ __launch_bounds__(kProfileThreads) void profile_kernel(ProfileParams p) {
     const uint32_t lane = lane_id();
     const uint64_t pos = (uint64_t)blockIdx.x * kProfileThreads + threadIdx.x;
@@ -44,15 +54,28 @@ __global__ __launch_bounds__(kProfileThreads) void profile_kernel(ProfileParams 
         const uint64_t qx = p.strand && p.strand[q] ? q + p.n_user : q;
         st = profile_step(p.src, q, p.override_ok ? exact_only(p.exact, qx) : kTextNoOverride, p.cutoff);
     }
-    // totals: queries, classified, unclassified, unclassifiable
-    const uint32_t n_act = (uint32_t)__popcll(__ballot(active));
-    const uint32_t n_cls = (uint32_t)__popcll(__ballot(active && st.kind == kProfClassified));
-    const uint32_t n_unc = (uint32_t)__popcll(__ballot(active && st.kind == kProfUnclassified));
-    if (lane == 0 && n_act) {
-        atomicAdd(p.totals + 0, (unsigned long long)n_act);
-        if (n_cls) atomicAdd(p.totals + 1, (unsigned long long)n_cls);
-        if (n_unc) atomicAdd(p.totals + 2, (unsigned long long)n_unc);
-        if (n_act - n_cls - n_unc) atomicAdd(p.totals + 3, (unsigned long long)(n_act - n_cls - n_unc));
+    const unsigned long long w = W && active ? p.weight[q] : 0ull;
+    if constexpr (W) {
+        const unsigned long long n_act = wave_sum_u64(w);
+        const unsigned long long n_cls = wave_sum_u64(st.kind == kProfClassified ? w : 0ull);
+        const unsigned long long n_unc = wave_sum_u64(st.kind == kProfUnclassified ? w : 0ull);
+        if (lane == 0 && n_act) {
+            atomicAdd(p.totals + 0, n_act);
+            if (n_cls) atomicAdd(p.totals + 1, n_cls);
+            if (n_unc) atomicAdd(p.totals + 2, n_unc);
+            if (n_act - n_cls - n_unc) atomicAdd(p.totals + 3, n_act - n_cls - n_unc);
+        }
+    } else {
+        // totals: queries, classified, unclassified, unclassifiable
+        const uint32_t n_act = (uint32_t)__popcll(__ballot(active));
+        const uint32_t n_cls = (uint32_t)__popcll(__ballot(active && st.kind == kProfClassified));
+        const uint32_t n_unc = (uint32_t)__popcll(__ballot(active && st.kind == kProfUnclassified));
+        if (lane == 0 && n_act) {
+            atomicAdd(p.totals + 0, (unsigned long long)n_act);
+            if (n_cls) atomicAdd(p.totals + 1, (unsigned long long)n_cls);
+            if (n_unc) atomicAdd(p.totals + 2, (unsigned long long)n_unc);
+            if (n_act - n_cls - n_unc) atomicAdd(p.totals + 3, (unsigned long long)(n_act - n_cls - n_unc));
+        }
     }
     const uint32_t L = active ? st.L : 0u;
     const uint32_t max_l = wave_max_u32(L);
@@ -67,12 +90,23 @@ __global__ __launch_bounds__(kProfileThreads) void profile_kernel(ProfileParams 
             const uint32_t key = (uint32_t)__shfl((int)node, (int)lead, 64);
             const bool mine = part && node == key;
             const unsigned long long m = __ballot(mine);
-            const uint32_t n_dir = (uint32_t)__popcll(__ballot(mine && direct));
-            const uint32_t sum_h = wave_sum_u32(mine ? h : 0u);
-            if (lane == lead && key < p.n_nodes) {  // (a node id outside the table: never from a well-formed result)
-                atomicAdd(p.clade + key, (unsigned long long)__popcll(m));
-                atomicAdd(p.conf_sum + key, (unsigned long long)sum_h);
-                if (n_dir) atomicAdd(p.direct + key, (unsigned long long)n_dir);
+            if constexpr (W) {
+                const unsigned long long n_mine = wave_sum_u64(mine ? w : 0ull);
+                const unsigned long long n_dir = wave_sum_u64(mine && direct ? w : 0ull);
+                const unsigned long long sum_h = wave_sum_u64(mine ? w * h : 0ull);
+                if (lane == lead && key < p.n_nodes && n_mine) {
+                    atomicAdd(p.clade + key, n_mine);
+                    atomicAdd(p.conf_sum + key, sum_h);
+                    if (n_dir) atomicAdd(p.direct + key, n_dir);
+                }
+            } else {
+                const uint32_t n_dir = (uint32_t)__popcll(__ballot(mine && direct));
+                const uint32_t sum_h = wave_sum_u32(mine ? h : 0u);
+                if (lane == lead && key < p.n_nodes) {  // (a node id outside the table: never from a well-formed result)
+                    atomicAdd(p.clade + key, (unsigned long long)__popcll(m));
+                    atomicAdd(p.conf_sum + key, (unsigned long long)sum_h);
+                    if (n_dir) atomicAdd(p.direct + key, (unsigned long long)n_dir);
+                }
             }
             todo &= ~m;
         }
@@ -82,7 +116,9 @@ __global__ __launch_bounds__(kProfileThreads) void profile_kernel(ProfileParams 
 
 void launch_profile(hipStream_t s, const ProfileParams &p) {
     if (p.n_pos == 0) return;
-    hipLaunchKernelGGL(profile_kernel, dim3((unsigned)((p.n_pos + kProfileThreads - 1u) / kProfileThreads)), dim3(kProfileThreads), 0, s, p);
+    const dim3 grid((unsigned)((p.n_pos + kProfileThreads - 1u) / kProfileThreads));
+    if (p.weight) hipLaunchKernelGGL(profile_kernel<true>, grid, dim3(kProfileThreads), 0, s, p);
+    else hipLaunchKernelGGL(profile_kernel<false>, grid, dim3(kProfileThreads), 0, s, p);
 }
 
 }  // namespace rtx
