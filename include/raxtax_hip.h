@@ -41,7 +41,8 @@ extern "C" {
                                 (still 6 with RTX_OPT_NEAREST (26), RTX_NO_REF, rtx_batch_nearest and rtx_raxtax_multi_ex2: exports and an option
                                 that is off by default, nothing that exists changes shape; and with the taxon profile, rtx_index_profile_* /
                                 rtx_profile_merge / rtx_profile_format: exports only; and with RTX_OPT_DEREP (27), rtx_derep_*,
-                                rtx_batch_prefetch_weights and rtx_raxtax_last_derep: exports and an option that is off by default) */
+                                rtx_batch_prefetch_weights and rtx_raxtax_last_derep: exports and an option that is off by default; and with
+                                RTX_OPT_IDENTITY (28), RTX_NO_DIST, rtx_batch_identity, rtx_semiglobal_distance and rtx_raxtax_multi_ex3: the same) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -303,6 +304,15 @@ int rtx_index_set_batch(rtx_index *index, uint32_t sub_batch);
                                       * Exact on the pruned path as well.  Not available on a reference shard (RTX_ERR_INVALID); staged rtx_shard_* runs and
                                       * rtx_debug_evaluate fill nothing.  Setting it drops the uploaded batch like the options below. */
 #define RTX_NO_REF 0xFFFFFFFFu       /* no reference (rtx_batch_nearest, rtx_query_hit_fn) */
+#define RTX_OPT_IDENTITY 28          /* 0 (default): nothing is launched or allocated.  1: every run also aligns each query, in the orientation that was classified,
+                                      * to its nearest reference (RTX_OPT_NEAREST, which must be on: RTX_ERR_STATE otherwise, and switching it off while
+                                      * this option is on is refused with RTX_ERR_STATE) and reports the semi-global edit distance of
+                                      * rtx_semiglobal_distance: rtx_batch_identity.  A query without a nearest reference (RTX_NO_REF) or longer than
+                                      * RTX_IDENTITY_MAX_QUERY bases has RTX_NO_DIST.  Needs a handle that holds the reference sequences (built from a
+                                      * tree or from sequences: RTX_ERR_STATE otherwise); not available on a reference shard (RTX_ERR_INVALID); staged
+                                      * rtx_shard_* runs and rtx_debug_evaluate fill nothing.  Setting it drops the uploaded batch like RTX_OPT_NEAREST. */
+#define RTX_NO_DIST 0xFFFFFFFFu      /* no distance (rtx_batch_identity, rtx_query_align_fn) */
+#define RTX_IDENTITY_MAX_QUERY 4096u /* longest query that is aligned: 64 lanes of 64 bases (rtx_identity.hip) */
 #define RTX_OPT_DEREP 27             /* 0 (default): no new code runs, nothing is allocated, every output is what it is without the option.  1: DEREPLICATION --
                                       * rtx_raxtax / rtx_raxtax_multi* classify each distinct read of a chunk once: a device stage in front of the handle
                                       * (rtx_derep_run, on a stream of its own, a chunk ahead of the handle) finds the byte-identical copies, the handle
@@ -418,6 +428,19 @@ int rtx_batch_nearest(rtx_index *index, const uint32_t **nearest, const uint32_t
 /* Milliseconds the kernel behind it took over the sub-batches of the last run, and its launches (RTX_OPT_STAGE_TIMING on; else 0 and 0).  Not one
  * of the stages of rtx_batch_stage_times: RTX_NUM_STAGES is part of the ABI.  After rtx_batch_sync. */
 int rtx_batch_nearest_time(rtx_index *index, float *ms, uint32_t *launches);
+/* Alignment identity of every query of the last download (RTX_OPT_IDENTITY), [n_queries], under the lifetime rules of rtx_batch_nearest.
+ * dist: the semi-global edit distance (rtx_semiglobal_distance) of the query, in the orientation that was classified (rtx_batch_strands), to
+ * the reference rtx_batch_nearest names, or RTX_NO_DIST; qlen: the query's length in bases.  The identity in hundredths of a percent is
+ * ((qlen - dist) * 10000 + qlen / 2) / qlen.  Either pointer may be NULL.  RTX_ERR_STATE if the run of that download had the option off. */
+int rtx_batch_identity(rtx_index *index, const uint32_t **dist, const uint32_t **qlen);
+/* Milliseconds the alignment kernels took in the last run, and their launches (RTX_OPT_STAGE_TIMING on; else 0 and 0), like
+ * rtx_batch_nearest_time: not one of the stages of rtx_batch_stage_times.  After rtx_batch_sync. */
+int rtx_batch_identity_time(rtx_index *index, float *ms, uint32_t *launches);
+/* The distance of RTX_OPT_IDENTITY on the host, no device involved: the minimum, over all substrings s of r (the empty one included), of the
+ * Levenshtein distance between q and s -- substitution, insertion and deletion cost 1 each, the whole query is aligned, the reference's
+ * overhang at either end is free.  Bytes as everywhere (one per base, parser.rs:11-34): two match when both are codes (1 .. 15) and share a
+ * bit; a byte that is 0 or above 15 matches nothing.  0 <= *dist <= qlen; any lengths. */
+int rtx_semiglobal_distance(const uint8_t *q, uint64_t qlen, const uint8_t *r, uint64_t rlen, uint32_t *dist);
 
 /* ---- taxon profile of a run, accumulated on the device (rtx_profile.hip) --------------------------------------------------------------
  * What is in the sample: per node of the taxonomy (rtx_nodes_view numbering) the queries under it, the queries assigned to it and the sum
@@ -732,6 +755,14 @@ int rtx_raxtax_multi_ex2(rtx_index *const *indices, uint32_t n_indices, const rt
                          const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                          int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                          rtx_query_hit_fn hit, void *hit_ctx);
+/* rtx_raxtax_multi_ex2 with a callback that also receives the alignment identity of the query (RTX_OPT_IDENTITY on the handles, which must
+ * agree on it: RTX_ERR_INVALID otherwise; with the option off it receives RTX_NO_DIST and the query's length).  `align` may be NULL. */
+typedef int (*rtx_query_align_fn)(void *ctx, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties,
+                                  uint32_t dist, uint32_t qlen);
+int rtx_raxtax_multi_ex3(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_align_fn align, void *align_ctx);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

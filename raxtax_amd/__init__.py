@@ -7,9 +7,9 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from .api import (EvaluationResult, Index, Result, Tree, parse_query_fasta_str, parse_reference_fasta_str,  # noqa: F401
-                  raxtax, raxtax_last_timing, NO_REF, Profile, profile_merge, profile_text, Derep, derep_plan, raxtax_last_derep)
+                  raxtax, raxtax_last_timing, NO_REF, NO_DIST, semiglobal_distance, Profile, profile_merge, profile_text, Derep, derep_plan, raxtax_last_derep)
 from ._lib import (RTX_RAW_CONFIDENCE, RTX_SKIP_EXACT_MATCHES, RtxError)  # noqa: F401
 
 __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last_timing", "parse_reference_fasta_str",
-           "parse_query_fasta_str", "RtxError", "RTX_SKIP_EXACT_MATCHES", "RTX_RAW_CONFIDENCE", "NO_REF",
+           "parse_query_fasta_str", "RtxError", "RTX_SKIP_EXACT_MATCHES", "RTX_RAW_CONFIDENCE", "NO_REF", "NO_DIST", "semiglobal_distance",
            "Profile", "profile_merge", "profile_text", "Derep", "derep_plan", "raxtax_last_derep"]

@@ -161,6 +161,10 @@ _SIGNATURES = {
     "rtx_raxtax_multi_ex2": (C.c_int, None),
     "rtx_batch_nearest": (C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p)]),
     "rtx_batch_nearest_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtx_raxtax_multi_ex3": (C.c_int, None),
+    "rtx_batch_identity": (C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p)]),
+    "rtx_batch_identity_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "rtx_semiglobal_distance": (C.c_int, [u8p, C.c_uint64, u8p, C.c_uint64, C.POINTER(C.c_uint32)]),
     "rtx_index_profile_begin": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32]),
     "rtx_index_profile_read": (C.c_int, [C.c_void_p, C.POINTER(ProfileView)]),
     "rtx_index_profile_reset": (C.c_int, [C.c_void_p]),

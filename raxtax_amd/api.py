@@ -179,13 +179,17 @@ class Result:
     order (the library stores the rows in processing order): rows of query q = row_off[q] .. row_off[q+1].
     strand (0 plus, 1 minus: Index(strand="both")) and peak (the largest hit count over the references for the classified orientation)
     per query, when the view came from a download (rtx_batch_strands), else None.  nearest (the lowest reference id whose hit count is the
-    peak, NO_REF where the peak is 0) and nearest_ties (references with that count) per query under Index(nearest=True), else None."""
+    peak, NO_REF where the peak is 0) and nearest_ties (references with that count) per query under Index(nearest=True), else None.
+    nearest_dist (the semi-global edit distance of the query, as classified, to that reference: semiglobal_distance; NO_DIST where there is
+    none) and query_len (bases) per query under Index(identity=True), else None."""
 
     def __init__(self, view: ResultView, strand: Optional[np.ndarray] = None, peak: Optional[np.ndarray] = None,
-                 nearest: Optional[np.ndarray] = None, nearest_ties: Optional[np.ndarray] = None):
+                 nearest: Optional[np.ndarray] = None, nearest_ties: Optional[np.ndarray] = None,
+                 nearest_dist: Optional[np.ndarray] = None, query_len: Optional[np.ndarray] = None):
         nq, nr = view.n_queries, view.n_rows
         self.strand, self.peak = strand, peak
         self.nearest, self.nearest_ties = nearest, nearest_ties
+        self.nearest_dist, self.query_len = nearest_dist, query_len
         arr = lambda p, n: (np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0))
         self.n_queries = nq
         self.t = arr(view.t, nq)
@@ -270,6 +274,7 @@ DEFAULT_SEGMENT_CLASSES = 1   # RTX_DEFAULT_SEGMENT_CLASSES of the library (rtx_
 class Index:
     """Device-resident index + batch workspace of one GPU (rtx_index)."""
 
+    identity_on = False  # Index(identity=True): downloads also fetch rtx_batch_identity
     nearest_on = False   # Index(nearest=True): downloads also fetch rtx_batch_nearest (the staged subclasses never set the option)
 
     def __init__(self, tree: Tree, device: int = 0, sub_batch: int = 0, prob_mode: int = 0,
@@ -279,7 +284,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False):
+                 nearest: bool = False, derep: bool = False, identity: bool = False):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -332,9 +337,12 @@ class Index:
         self.strand = strand
         if strand == "both":   # RTX_OPT_STRAND: every query is classified in both orientations, the one with the larger peak is reported
             check(self._lib.rtx_index_set_option(self._h, 25, 1))
-        self.nearest_on = bool(nearest)
-        if nearest:   # RTX_OPT_NEAREST: every run also names the reference that holds each query's peak
+        self.nearest_on = bool(nearest) or bool(identity)
+        if self.nearest_on:   # RTX_OPT_NEAREST: every run also names the reference that holds each query's peak
             check(self._lib.rtx_index_set_option(self._h, 26, 1))
+        self.identity_on = bool(identity)
+        if identity:   # RTX_OPT_IDENTITY: ... and aligns the query to it (rtx_identity.hip); implies nearest
+            check(self._lib.rtx_index_set_option(self._h, 28, 1))
         if derep:   # RTX_OPT_DEREP: raxtax() classifies each distinct read of a chunk once (rtx_derep.hip); classify() ignores it
             check(self._lib.rtx_index_set_option(self._h, _lib.RTX_OPT_DEREP, 1))
         self._view = ResultView()
@@ -417,7 +425,25 @@ class Index:
 
     def download(self, copy: bool = True):
         check(self._lib.rtx_batch_download(self._h, C.byref(self._view)))
-        return Result(self._view, *self.strands(), *(self.nearest() if self.nearest_on else (None, None))) if copy else self._view
+        if not copy:
+            return self._view
+        return Result(self._view, *self.strands(), *(self.nearest() if self.nearest_on else (None, None)),
+                      *(self.identity() if self.identity_on else (None, None)))
+
+    def identity(self):
+        """(dist, qlen) of every query of the last download: rtx_batch_identity (Index(identity=True))."""
+        pd, pl = u32p(), u32p()
+        check(self._lib.rtx_batch_identity(self._h, C.byref(pd), C.byref(pl)))
+        n = self._view.n_queries
+        if not n:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        return np.ctypeslib.as_array(pd, shape=(n,)).copy(), np.ctypeslib.as_array(pl, shape=(n,)).copy()
+
+    def identity_time(self):
+        """(milliseconds, launches) of the kernels behind identity() in the last run (stage_timing=True): rtx_batch_identity_time."""
+        ms, n = C.c_float(), C.c_uint32()
+        check(self._lib.rtx_batch_identity_time(self._h, C.byref(ms), C.byref(n)))
+        return float(ms.value), int(n.value)
 
     def nearest(self):
         """(nearest, ties) of every query of the last download: rtx_batch_nearest (Index(nearest=True))."""
@@ -671,7 +697,20 @@ class Index:
 _SENDER = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p)
 _INFO = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32)
 _HIT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
+_ALIGN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
 NO_REF = 0xFFFFFFFF   # RTX_NO_REF
+NO_DIST = 0xFFFFFFFF  # RTX_NO_DIST
+
+
+def semiglobal_distance(q: np.ndarray, r: np.ndarray) -> int:
+    """rtx_semiglobal_distance: the least Levenshtein distance between the encoded sequence q and any substring of r (the empty one
+    included) -- what Result.nearest_dist holds for a query and its nearest reference, computed on the host."""
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    r = np.ascontiguousarray(r, dtype=np.uint8)
+    d = C.c_uint32()
+    one = np.zeros(1, np.uint8)
+    check(_lib.load().rtx_semiglobal_distance(ptr(q if len(q) else one, u8p), len(q), ptr(r if len(r) else one, u8p), len(r), C.byref(d)))
+    return int(d.value)
 
 
 def revcomp(seq: np.ndarray) -> np.ndarray:
@@ -685,22 +724,25 @@ def revcomp(seq: np.ndarray) -> np.ndarray:
 def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: bool, raw_confidence: bool,
            chunk_size: int, sender: Callable[[str, str, Optional[str]], None], tsv: bool,
            info: Optional[Callable[[str, int, int, int], None]] = None,
-           hit: Optional[Callable[[str, int, int, int, int, int], None]] = None) -> None:
+           hit: Optional[Callable[[str, int, int, int, int, int], None]] = None,
+           align: Optional[Callable[[str, int, int, int, int, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
     plays the role of a closed channel.  `info(label, strand, peak, t)`, if given, is called directly before the sender of the same query
     (rtx_raxtax_multi_ex); handles built with strand="both" report the orientation with the larger peak.
     `hit(label, strand, peak, t, nearest, ties)` is the same with the nearest reference and its ties (rtx_raxtax_multi_ex2; handles built with
-    nearest=True, else NO_REF and 0); give one of the two."""
+    nearest=True, else NO_REF and 0).  `align(label, strand, peak, t, nearest, ties, dist, qlen)` adds the alignment identity
+    (rtx_raxtax_multi_ex3; handles built with identity=True, else NO_DIST and the query's length).  Give one of the three."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
     lib.rtx_raxtax_multi.argtypes = [C.POINTER(C.c_void_p), C.c_uint32] + lib.rtx_raxtax.argtypes[1:]
     lib.rtx_raxtax_multi_ex.argtypes = lib.rtx_raxtax_multi.argtypes + [_INFO, C.c_void_p]
     lib.rtx_raxtax_multi_ex2.argtypes = lib.rtx_raxtax_multi.argtypes + [_HIT, C.c_void_p]
-    if info is not None and hit is not None:
-        raise ValueError("raxtax: give info or hit, not both")
+    lib.rtx_raxtax_multi_ex3.argtypes = lib.rtx_raxtax_multi.argtypes + [_ALIGN, C.c_void_p]
+    if (info is not None) + (hit is not None) + (align is not None) > 1:
+        raise ValueError("raxtax: give one of info, hit and align")
     handles = list(tree) if isinstance(tree, (list, tuple)) else [tree]
     labels = (C.c_char_p * max(len(queries), 1))(*[q[0].encode() for q in queries])
     flat, off = _flatten([q[1] for q in queries])
@@ -730,7 +772,19 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if hit is not None:
+    def cb_align(_ctx, label, strand, peak, t, nearest, ties, dist, qlen):
+        try:
+            align(label.decode(), int(strand), int(peak), int(t), int(nearest), int(ties), int(dist), int(qlen))
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if align is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex3(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _ALIGN(cb_align), None)
+    elif hit is not None:
         arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         rc = lib.rtx_raxtax_multi_ex2(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                       int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _HIT(cb_hit), None)

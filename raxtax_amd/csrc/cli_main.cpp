@@ -9,6 +9,8 @@
 //   PREFIX/raxtax.strand  (--strand both) label, + or -, peak, t per query, in the order of raxtax.out
 //   PREFIX/raxtax.profile (--profile CUTOFF) the taxon profile of the whole run: reads under and at every taxon whose confidence reaches CUTOFF (rtx_profile_format)
 //   PREFIX/raxtax.hits    (--hits) label, + or -, peak, t, ties, id and lineage of the nearest reference per query, in the order of raxtax.out
+//   (--identity, implies --hits: two more columns at the end of every line of raxtax.hits -- the semi-global edit distance of the query to that
+//    reference and the identity in percent, two decimals; '-' twice where there is no distance: RTX_OPT_IDENTITY)
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
@@ -120,11 +122,11 @@ std::string fingerprint(const std::string &path) {
 
 // (--strand both is part of the checkpoint like the three flags: a rerun with the other setting starts over; a default run writes the file it always wrote)
 // (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
-std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0) {
+std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
-       << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "");
+       << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "") << (identity ? ",\n  \"identity\": true" : "");
     if (profile) ss << ",\n  \"profile\": " << profile;
     ss << "\n}\n";
     return ss.str();
@@ -176,6 +178,7 @@ int main(int argc, char **argv) {
     bool device_format = false;
     bool both_strands = false;  // --strand both: RTX_OPT_STRAND on every handle
     bool want_hits = false;     // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
+    bool want_identity = false; // --identity: RTX_OPT_IDENTITY on every handle, dist and identity at the end of every line of raxtax.hits (implies --hits)
     bool derep = false;         // --derep: RTX_OPT_DEREP on every handle (each distinct read of a chunk is classified once; the files are the same)
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
@@ -220,6 +223,7 @@ int main(int argc, char **argv) {
             both_strands = v == "both";
         }
         else if (a == "--hits") want_hits = true;
+        else if (a == "--identity") want_identity = want_hits = true;
         else if (a == "--derep") derep = true;
         else if (a == "--profile") {
             char *end = nullptr;
@@ -233,7 +237,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--profile CUTOFF] [--derep]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -255,7 +259,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -326,7 +330,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -411,6 +415,7 @@ int main(int argc, char **argv) {
                 if (rcs[k] == RTX_OK && device_format) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEVICE_TEXT, 1);
                 if (rcs[k] == RTX_OK && both_strands) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_STRAND, 1);
                 if (rcs[k] == RTX_OK && want_hits) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_NEAREST, 1);
+                if (rcs[k] == RTX_OK && want_identity) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_IDENTITY, 1);
                 if (rcs[k] == RTX_OK && derep) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEREP, 1);
                 if (rcs[k] == RTX_OK && profile_cutoff)
                     rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
@@ -466,6 +471,23 @@ int main(int argc, char **argv) {
         }
         return (!s->want_strand || s->strand.good()) && (!s->want_hits || s->hits.good()) ? 0 : 1;
     };
+    // ... and, under --identity, how far the query is from it: the edit distance and the identity in percent behind the line of --hits
+    auto align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t dist, uint32_t qlen) -> int {
+        Sink *s = static_cast<Sink *>(c);
+        if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
+        s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
+        if (nearest == RTX_NO_REF) s->hits << "-\t-";
+        else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest);
+        if (dist == RTX_NO_DIST || qlen == 0u) {
+            s->hits << "\t-\t-\n";
+        } else {
+            const uint64_t h = ((uint64_t)(qlen - dist) * 10000u + qlen / 2u) / qlen;  // hundredths of a percent
+            char pct[32];
+            snprintf(pct, sizeof pct, "%llu.%02llu", (unsigned long long)(h / 100u), (unsigned long long)(h % 100u));
+            s->hits << '\t' << dist << '\t' << pct << '\n';
+        }
+        return (!s->want_strand || s->strand.good()) && s->hits.good() ? 0 : 1;
+    };
     int rc = RTX_OK;
     uint64_t n = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
@@ -497,8 +519,12 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                      both_strands || want_hits ? +info : nullptr, &sink);
+            if (want_identity)
+                rc = rtx_raxtax_multi_ex3(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                          +align, &sink);
+            else
+                rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                          both_strands || want_hits ? +info : nullptr, &sink);
             n += nb;
             if (derep) {
                 uint64_t dq = 0, du = 0;

@@ -82,7 +82,8 @@ LastDerep g_derep{0, 0, 0.0};
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
 // (label, strand, peak, t) of the query whose message follows (rtx_query_info_fn); empty: nobody asked
 // ... with the nearest reference and its ties behind them (rtx_query_hit_fn; RTX_NO_REF and 0 with RTX_OPT_NEAREST off)
-using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32_t, uint32_t)>;
+// ... and the alignment identity: distance and query length (rtx_query_align_fn; RTX_NO_DIST and the length with RTX_OPT_IDENTITY off)
+using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t)>;
 
 // Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the
 // one thread that dereplicates, which was most of the stage; the buffers travel between the chunks of a call through a pool, so that
@@ -119,6 +120,7 @@ struct Chunk {
     std::vector<uint8_t> strand;       // rtx_batch_strands, copied by the device stage (both strands, or an info callback)
     std::vector<uint32_t> peak;
     std::vector<uint32_t> nearest, ties;  // rtx_batch_nearest, copied with them (RTX_OPT_NEAREST and an info callback)
+    std::vector<uint32_t> dist;           // rtx_batch_identity, the same (RTX_OPT_IDENTITY)
     // The messages of the chunk: every formatting thread appends the NUL-terminated `.out` (and `.tsv`) text of its queries to an arena
     // of its own; msg_off[i] locates query i's text in the arena of the thread that took it (a std::string per message was a malloc in
     // the format thread and a free in the sender's, per query: half of the format stage)
@@ -203,6 +205,9 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     const bool near = rtx::index_nearest(indices[0]);  // RTX_OPT_NEAREST: on every handle, or on none
     for (uint32_t d = 0; d < n_dev; d++)
         if (rtx::index_nearest(indices[d]) != near) { rtx::set_error("rtx_raxtax_multi: the handles disagree on RTX_OPT_NEAREST"); return RTX_ERR_INVALID; }
+    const bool ident = rtx::index_identity(indices[0]);  // RTX_OPT_IDENTITY: the same
+    for (uint32_t d = 0; d < n_dev; d++)
+        if (rtx::index_identity(indices[d]) != ident) { rtx::set_error("rtx_raxtax_multi: the handles disagree on RTX_OPT_IDENTITY"); return RTX_ERR_INVALID; }
     // an open taxon profile (rtx_index_profile_begin): on every handle or on none, with one cutoff, and with the flags of this call
     uint32_t prof_cutoff = 0, prof_flags = 0;
     const bool prof = rtx::index_profile(indices[0], &prof_cutoff, &prof_flags);
@@ -467,6 +472,18 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     }
                 }
             }
+            if (!rc && ident && info) {
+                const uint32_t *di = nullptr;
+                rc = rtx_batch_identity(indices[d], &di, nullptr);
+                if (!rc) {
+                    if (ch.slot.empty()) {
+                        ch.dist.assign(di, di + ch.nq);
+                    } else {  // (a copy has its representative's bases, and so its distance)
+                        ch.dist.resize(ch.nq);
+                        for (uint64_t i = 0; i < ch.nq; i++) ch.dist[i] = di[ch.slot[i]];
+                    }
+                }
+            }
             if (rc) { fail(rc, rtx_last_error()); return; }
             busy_device[d] += now() - t_d0;
             set_stage(c, 2);
@@ -624,7 +641,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 continue;
             }
             bool ok;
-            if (info && !info(labels[q], ch.strand[i], ch.peak[i], ch.t[i], near ? ch.nearest[i] : RTX_NO_REF, near ? ch.ties[i] : 0u)) { closed = true; break; }
+            if (info && !info(labels[q], ch.strand[i], ch.peak[i], ch.t[i], near ? ch.nearest[i] : RTX_NO_REF, near ? ch.ties[i] : 0u,
+                              ident ? ch.dist[i] : RTX_NO_DIST, (uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull))) { closed = true; break; }
             if (dev_text[c % n_dev]) {
                 ok = sender(labels[q], ch.text.out + ch.text.out_off[i], tsv ? ch.text.tsv + ch.text.tsv_off[i] : nullptr);
             } else {
@@ -726,7 +744,7 @@ extern "C" int rtx_raxtax_multi_ex(rtx_index *const *indices, uint32_t n_indices
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
-    if (info) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t, uint32_t) { return info(info_ctx, label, strand, peak, t) == 0; };
+    if (info) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t, uint32_t, uint32_t, uint32_t) { return info(info_ctx, label, strand, peak, t) == 0; };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
                tsv != 0, fi);
 }
@@ -739,7 +757,23 @@ extern "C" int rtx_raxtax_multi_ex2(rtx_index *const *indices, uint32_t n_indice
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
-    if (hit) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties) { return hit(hit_ctx, label, strand, peak, t, nearest, ties) == 0; };
+    if (hit) fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) { return hit(hit_ctx, label, strand, peak, t, nearest, ties) == 0; };
+    return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
+               tsv != 0, fi);
+}
+
+// ... and the alignment identity (RTX_OPT_IDENTITY)
+extern "C" int rtx_raxtax_multi_ex3(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_align_fn align, void *align_ctx) {
+    if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
+    RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
+    RawInfo fi;
+    if (align)
+        fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t dist, uint32_t qlen) {
+            return align(align_ctx, label, strand, peak, t, nearest, ties, dist, qlen) == 0;
+        };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
                tsv != 0, fi);
 }

@@ -525,6 +525,7 @@ int alloc_final(rtx_index *ix, rtx_index::ResultSet &r, uint64_t n_queries) {
     if ((rc = r.d_peak2.alloc(n_queries)) || (rc = r.d_peak.alloc(n_queries)) || (rc = r.d_strand.alloc(n_queries))) return rc;  // (rtx_strand.hip)
     if (ix->nearest_opt && ((rc = r.d_nearest2.alloc(n_queries)) || (rc = r.d_ties2.alloc(n_queries)) || (rc = r.d_nearest.alloc(n_queries)) || (rc = r.d_ties.alloc(n_queries))))  // (rtx_nearest.hip)
         return rc;
+    if (ix->identity_opt && ((rc = r.d_dist.alloc(n_queries)) || (rc = r.d_qlen.alloc(n_queries)))) return rc;  // (rtx_identity.hip)
     if (ix->strand_opt && ((rc = r.d_sel_t.alloc(n_queries)) || (rc = r.d_sel_status.alloc(n_queries)) || (rc = r.d_sel_gs.alloc(n_queries)) ||
                            (rc = r.d_sel_row_begin.alloc(n_queries)) || (rc = r.d_sel_row_count.alloc(n_queries))))
         return rc;
@@ -657,6 +658,7 @@ void record_batch(rtx_index *ix) {
     r.n_user = ix->strand_used ? ix->n_user : ix->n_q;
     r.has_peak = false;
     r.has_nearest = false;
+    r.has_identity = false;
     r.profiled = false;
     r.n_sub = ix->n_sub_total();
     r.n_side = 0;
@@ -816,6 +818,9 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
     ix->n_near_last = 0;
     r.has_nearest = ix->nearest_opt != 0u && r.d_nearest2.p != nullptr && r.d_nearest2.n >= r.n_q && r.d_nearest.n >= r.n_user;
     if (ix->nearest_opt != 0u && !r.has_nearest) { set_error("internal: RTX_OPT_NEAREST without its arrays"); return RTX_ERR_STATE; }
+    ix->ident_timed = false;
+    r.has_identity = ix->identity_opt != 0u && r.has_nearest && r.d_dist.p != nullptr && r.d_dist.n >= r.n_user && r.d_qlen.n >= r.n_user && ix->d_em_ref_grp.p != nullptr;
+    if (ix->identity_opt != 0u && !r.has_identity) { set_error("internal: RTX_OPT_IDENTITY without its arrays"); return RTX_ERR_STATE; }
     if (n_sub <= 4096) {  // per sub-batch: completion event (+ cursor snapshots) for the streamed download
         if (!ix->copy_stream) RTX_HIP(hipStreamCreateWithFlags(&ix->copy_stream, hipStreamNonBlocking));
         while (r.ev_sub.size() < n_sub) {
@@ -973,6 +978,37 @@ int enqueue_batch(rtx_index *ix, uint32_t flags) {
                                                   r.d_fin_row_count.p, r.d_strand.p, r.d_peak.p, r.d_sel_status.p, r.d_sel_t.p, r.d_sel_gs.p, r.d_sel_row_begin.p,
                                                   r.d_sel_row_count.p, r.has_nearest ? r.d_nearest2.p : nullptr, r.has_nearest ? r.d_ties2.p : nullptr,
                                                   r.has_nearest ? r.d_nearest.p : nullptr, r.has_nearest ? r.d_ties.p : nullptr});
+            if (r.has_identity) {  // RTX_OPT_IDENTITY: every query of the caller against the reference just chosen for it (rtx_identity.hip)
+                // The query bytes are those of the batch's input set, which is not staged again before this run has been downloaded (a
+                // prefetch goes to the OTHER set until the next activation, and that follows this run's download, which waits for the
+                // event below): the guarantee the text kernel reads the same bytes under.
+                const rtx_index::Inputs &in = ix->in[r.in_set];
+                IdentityParams ip{};
+                ip.n = (uint32_t)r.n_user;
+                ip.max_len = (uint32_t)std::min<uint64_t>(in.max_len, 0xFFFFFFFFull);
+                ip.nearest = r.d_nearest.p;
+                ip.strand = r.d_strand.p;
+                ip.qbytes = in.d_packed.p;
+                ip.qoff = in.d_base_off.p;
+                ip.packed = in.packed;
+                ip.ref_grp = ix->d_em_ref_grp.p;
+                ip.rep_off = ix->d_em_rep_off.p;
+                ip.rep_bytes = ix->d_em_rep_bytes.p;
+                ip.n_refs = (uint32_t)ix->n_refs;
+                ip.dist = r.d_dist.p;
+                ip.qlen = r.d_qlen.p;
+                const bool timed_id = ix->stage_timing != 0u;  // (not one of the stages of rtx_batch_stage_times: rtx_batch_identity_time)
+                if (timed_id) {
+                    for (auto &e : ix->ev_ident)
+                        if (!e) RTX_HIP(hipEventCreate(&e));
+                    RTX_HIP(hipEventRecord(ix->ev_ident[0], fs));
+                }
+                launch_identity(fs, ip);
+                if (timed_id) {
+                    RTX_HIP(hipEventRecord(ix->ev_ident[1], fs));
+                    ix->ident_timed = true;
+                }
+            }
             if (!r.ev_select) RTX_HIP(hipEventCreateWithFlags(&r.ev_select, hipEventDisableTiming));
             RTX_HIP(hipEventRecord(r.ev_select, fs));
             r.has_peak = true;
@@ -1115,7 +1151,7 @@ int prepare_workspace(rtx_index *ix, uint64_t n_queries, const uint64_t cls_n_in
     const uint64_t key[14] = {n_queries, cn[0], cn[1], cn[2] << 32 | cn[3], cn[4], cm[0], cm[1], cm[2] << 32 | cm[3], cm[4], ix->sub_batch_req,
                               (uint64_t)ix->packed_opt | (uint64_t)ix->pair_opt << 1 | (uint64_t)ix->pruning() << 2 | (uint64_t)ix->shard_prune_opt << 3 | (uint64_t)ix->fine_opt << 4 |
                                   (uint64_t)(ix->prob_mode & 3) << 5 | (uint64_t)ix->rec_opt << 8 | (uint64_t)ix->overlap_opt << 16 | (uint64_t)ix->min_subs << 20,
-                              (uint64_t)ix->n_bnd_local, ix->shared_device ? 1u : 0u, ix->strand_opt | ix->nearest_opt << 1};
+                              (uint64_t)ix->n_bnd_local, ix->shared_device ? 1u : 0u, ix->strand_opt | ix->nearest_opt << 1 | ix->identity_opt << 2};
     // A batch of the shape of the last one under the same options (the chunks of rtx_raxtax): everything below would come out the same --
     // and hipMemGetInfo alone costs a good part of a millisecond between two chunks, with the device idle
     if (ix->ws_valid && std::memcmp(key, ix->ws_key, sizeof key) == 0 && !ix->staged) {

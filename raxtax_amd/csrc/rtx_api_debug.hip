@@ -45,6 +45,21 @@ int rtx_batch_nearest_time(rtx_index *ix, float *ms, uint32_t *launches) {
     return RTX_OK;
 }
 
+// Time of the kernels of rtx_identity.hip in the last run (RTX_OPT_IDENTITY with RTX_OPT_STAGE_TIMING on, else 0 launches)
+int rtx_batch_identity_time(rtx_index *ix, float *ms, uint32_t *launches) {
+    if (!ix || !ms || !launches) { set_error("null argument"); return RTX_ERR_INVALID; }
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (!ix->synced) { set_error("rtx_batch_identity_time: batch not synchronised"); return RTX_ERR_STATE; }
+    *ms = 0.f;
+    *launches = 0;
+    if (ix->ident_timed && ix->ev_ident[0] && ix->ev_ident[1]) {
+        RTX_HIP(hipEventElapsedTime(ms, ix->ev_ident[0], ix->ev_ident[1]));
+        *launches = 1;
+    }
+    return RTX_OK;
+}
+
 int rtx_batch_work(rtx_index *ix, uint64_t *sum_hits, uint64_t *sum_query_bytes, uint64_t *bitmap_bytes_read) {
     if (!ix) { set_error("null index handle"); return RTX_ERR_INVALID; }
     int rc = bind(ix);

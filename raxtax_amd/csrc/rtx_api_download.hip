@@ -42,6 +42,7 @@ static int size_host_results(rtx_index *ix, rtx_index::HostRes &hr, uint64_t nq,
         (rc = hr.v_row_count.resize(nq)) || (rc = hr.h_strand.resize(nq)) || (rc = hr.h_peak.resize(nq)))
         return rc;
     if (ix->nearest_opt && ((rc = hr.h_nearest.resize(nq)) || (rc = hr.h_ties.resize(nq)))) return rc;  // (rtx_batch_nearest)
+    if (ix->identity_opt && ((rc = hr.h_dist.resize(nq)) || (rc = hr.h_qlen.resize(nq)))) return rc;  // (rtx_batch_identity)
     const uint64_t D = ix->fin_D;
     if ((rc = hr.v_row_lineage.grow_keep(rows, keep)) || (rc = hr.v_row_node.grow_keep(rows, keep)) || (rc = hr.v_row_depth.grow_keep(rows, keep)) ||
         (rc = hr.v_row_depth8.grow_keep(rows, keep)) || (rc = hr.v_row_local.grow_keep(rows, keep)) || (rc = hr.v_row_conf.grow_keep(rows * D, keep * D)) ||
@@ -90,6 +91,12 @@ static int copy_queries(const rtx_index::ResultSet &r, rtx_index::HostRes &hr, h
         if (hr.h_nearest.size() < nq || hr.h_ties.size() < nq) { set_error("internal: RTX_OPT_NEAREST without its host arrays"); return RTX_ERR_STATE; }
         RTX_HIP(hipMemcpyAsync(hr.h_nearest.data(), r.d_nearest.p, nq * 4, hipMemcpyDeviceToHost, cs));
         RTX_HIP(hipMemcpyAsync(hr.h_ties.data(), r.d_ties.p, nq * 4, hipMemcpyDeviceToHost, cs));
+    }
+    hr.has_identity = hr.has_nearest && r.has_identity;  // RTX_OPT_IDENTITY (rtx_identity.hip, in front of ev_select)
+    if (hr.has_identity) {
+        if (hr.h_dist.size() < nq || hr.h_qlen.size() < nq) { set_error("internal: RTX_OPT_IDENTITY without its host arrays"); return RTX_ERR_STATE; }
+        RTX_HIP(hipMemcpyAsync(hr.h_dist.data(), r.d_dist.p, nq * 4, hipMemcpyDeviceToHost, cs));
+        RTX_HIP(hipMemcpyAsync(hr.h_qlen.data(), r.d_qlen.p, nq * 4, hipMemcpyDeviceToHost, cs));
     }
     return RTX_OK;
 }
@@ -539,6 +546,16 @@ int rtx_batch_prefetch_weights(rtx_index *ix, uint64_t n_queries, const uint32_t
     in.recorded = true;
     in.weights_pending = true;
     in.n_weights = n_queries;
+    return RTX_OK;
+}
+
+// Distance to the nearest reference and length of every query of the last download (rtx_identity.hip)
+int rtx_batch_identity(rtx_index *ix, const uint32_t **dist, const uint32_t **qlen) {
+    if (!ix || (!dist && !qlen)) { set_error("rtx_batch_identity: null argument"); return RTX_ERR_INVALID; }
+    const rtx_index::HostRes &hr = ix->host_res[ix->res_set];
+    if (!hr.has_identity || hr.h_dist.size() < hr.n_user || hr.h_qlen.size() < hr.n_user) { set_error("rtx_batch_identity: the last download's run had RTX_OPT_IDENTITY off (or there was no download)"); return RTX_ERR_STATE; }
+    if (dist) *dist = hr.h_dist.data();
+    if (qlen) *qlen = hr.h_qlen.data();
     return RTX_OK;
 }
 

@@ -13,6 +13,7 @@ uint32_t index_swap_min_subs(rtx_index *index, uint32_t v) { if (!index) return 
 // RTX_OPT_RUN_AHEAD for the duration of a call of the host mirror (rtx_raxtax over several chunks); switched off: the last run's join is enqueued
 bool index_strand(const rtx_index *index) { return index && index->strand_opt != 0u; }
 bool index_nearest(const rtx_index *index) { return index && index->nearest_opt != 0u; }
+bool index_identity(const rtx_index *index) { return index && index->identity_opt != 0u; }
 bool index_profile(const rtx_index *index, uint32_t *cutoff_hundredths, uint32_t *flags) {
     if (!index || !index->prof.on) return false;
     if (cutoff_hundredths) *cutoff_hundredths = index->prof.cutoff;
@@ -860,10 +861,30 @@ int rtx_index_set_option(rtx_index *index, int option, uint64_t value) {
         case RTX_OPT_NEAREST:
             if (value > 1) break;
             if (value && index->n_refs != index->n_total) { set_error("RTX_OPT_NEAREST: not on a reference-shard handle (the peak of a query is spread over the shards)"); return RTX_ERR_INVALID; }
+            if (!value && index->identity_opt) { set_error("RTX_OPT_NEAREST cannot be switched off while RTX_OPT_IDENTITY is on"); return RTX_ERR_STATE; }
             index->uploaded = index->ran = index->synced = false;  // shapes the result sets: the batch is uploaded again
             index->in[0].staged = index->in[1].staged = false;
             index->ws_valid = false;
             index->nearest_opt = (uint32_t)value;
+            return RTX_OK;
+        case RTX_OPT_IDENTITY:
+            if (value > 1) break;
+            if (value && index->n_refs != index->n_total) { set_error("RTX_OPT_IDENTITY: not on a reference-shard handle"); return RTX_ERR_INVALID; }
+            if (value && !index->nearest_opt) { set_error("RTX_OPT_IDENTITY needs RTX_OPT_NEAREST (the reference a query is aligned to)"); return RTX_ERR_STATE; }
+            if (value && (!index->d_em_rep_bytes.p || !index->d_em_goff.p || !index->em_groups)) { set_error("RTX_OPT_IDENTITY needs the reference sequences on the device (a handle built from a tree or from sequences)"); return RTX_ERR_STATE; }
+            if (value && !index->d_em_ref_grp.p) {  // reference -> its distinct sequence, once per handle
+                int rc = bind(index);
+                if (rc) return rc;
+                if ((rc = index->d_em_ref_grp.alloc(index->n_refs))) return rc;
+                RTX_HIP(hipMemsetAsync(index->d_em_ref_grp.p, 0, index->n_refs * 4, index->stream));
+                rtx::launch_ref_group(index->stream, index->d_em_goff.p, index->d_em_gids.p, index->em_groups, (uint32_t)index->n_refs, index->d_em_ref_grp.p);
+                RTX_HIP(hipGetLastError());
+                RTX_HIP(hipStreamSynchronize(index->stream));
+            }
+            index->uploaded = index->ran = index->synced = false;  // shapes the result sets: the batch is uploaded again
+            index->in[0].staged = index->in[1].staged = false;
+            index->ws_valid = false;
+            index->identity_opt = (uint32_t)value;
             return RTX_OK;
         case RTX_OPT_TWO_LEVEL_BOUNDS:
             index->two_level_opt = value ? 1u : 0u;

@@ -656,6 +656,31 @@ uint32_t emul_nearest_scan(const void *lo, const uint16_t *hi, uint32_t in_tile,
     }
     return 0xFFFFFFFFu;
 }
+// The alignment of identity_kernel (rtx_identity.hip) with the functions the kernel calls, the blocks of a column one after the other where the
+// kernel runs them skewed over the lanes of a group (the same carries between the same blocks): the semi-global edit distance of the query
+// against the text r.  q: the query's bytes as the input set holds them from base q_first on -- two per byte (packed != 0: base k in the low
+// nibble of byte k >> 1 when k is even) or raw; minus != 0: the reverse complement is aligned.  qlen 1 .. 4096.
+uint32_t emul_identity(const uint8_t *q, uint64_t q_first, uint32_t qlen, int packed, int minus, const uint8_t *r, uint32_t rlen) {
+    const uint32_t nb = (qlen + 63u) / 64u;
+    std::vector<IdentityBlock> blk(nb);
+    auto fetch_packed = [&](uint32_t j) { const uint64_t k = q_first + j; return (uint32_t)((q[k >> 1] >> ((k & 1u) * 4u)) & 15u); };
+    auto fetch_raw = [&](uint32_t j) { return (uint32_t)q[q_first + j]; };
+    for (uint32_t b = 0; b < nb; b++) {
+        if (packed) identity_block_init(blk[b], fetch_packed, qlen, b, minus != 0);
+        else identity_block_init(blk[b], fetch_raw, qlen, b, minus != 0);
+    }
+    uint32_t score = qlen, best = qlen;
+    for (uint32_t j = 0; j < rlen; j++) {
+        const uint32_t code = identity_code(r[j]);
+        int h = 0;
+        for (uint32_t b = 0; b < nb; b++) h = identity_step(blk[b], code, h, identity_out_mask(qlen, b));
+        score += (uint32_t)h;
+        best = std::min(best, score);
+    }
+    return best;
+}
+uint32_t emul_identity_hundredths(uint32_t dist, uint32_t qlen) { return identity_hundredths(dist, qlen); }
+
 // byte, high-bit word and shift of local reference rl in the packed counts of its tile (packed_count_pos)
 void emul_packed_count_pos(uint32_t rl, uint32_t *byte, uint32_t *hi_word, uint32_t *hi_shift) { packed_count_pos(rl, *byte, *hi_word, *hi_shift); }
 

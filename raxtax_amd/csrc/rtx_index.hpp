@@ -165,6 +165,8 @@ struct rtx_index {
     // ---- exact-match lookup on the device (rtx_exact.hip): the distinct reference sequences ("groups") in a hash table
     uint32_t dev_exact_opt = 1;       // RTX_OPT_DEVICE_EXACT
     uint32_t nearest_opt = 0;         // RTX_OPT_NEAREST: 1 = every run also names the reference that holds each query's peak (rtx_nearest.hip)
+    uint32_t identity_opt = 0;        // RTX_OPT_IDENTITY: 1 = every run also aligns each query to its nearest reference (rtx_identity.hip)
+    DevBuf<uint32_t> d_em_ref_grp;    // [n_refs] reference -> its distinct sequence (built when the option is first switched on)
     uint32_t strand_opt = 0;          // RTX_OPT_STRAND: 1 = every query is classified in both orientations (rtx_strand.hip)
     bool strand_used = false;         // ... the activated batch holds the twins (queries n_user .. n_q - 1)
     uint64_t n_user = 0;              // queries of the activated batch as the caller passed them
@@ -388,6 +390,9 @@ struct rtx_index {
         // sub-batch), and of the caller's queries (strand_select_kernel, beside d_peak)
         DevBuf<uint32_t> d_nearest2, d_ties2, d_nearest, d_ties;
         bool has_nearest = false;          // the run fills them
+        // rtx_identity.hip (RTX_OPT_IDENTITY; not allocated without it): distance to the nearest reference and length of the caller's queries
+        DevBuf<uint32_t> d_dist, d_qlen;
+        bool has_identity = false;         // the run fills them
         uint64_t n_user = 0;               // queries as the caller passed them (n_q counts the twins as well)
         bool has_peak = false;             // the run filled d_peak2 (enqueue_batch; not a staged run or rtx_debug_evaluate)
         hipEvent_t ev_exact = nullptr;     // behind exact_match_kernel of the run: the download fetches the groups at its START, beside the kernels, not at its tail
@@ -426,6 +431,8 @@ struct rtx_index {
     uint32_t n_sub_last = 0;
     std::vector<hipEvent_t> ev_near;  // 2 per sub-batch around nearest_kernel (RTX_OPT_NEAREST under RTX_OPT_STAGE_TIMING: rtx_batch_nearest_time)
     uint32_t n_near_last = 0;         // sub-batches of the last run that recorded them
+    hipEvent_t ev_ident[2] = {nullptr, nullptr};  // around the kernels of rtx_identity.hip (RTX_OPT_IDENTITY under RTX_OPT_STAGE_TIMING: rtx_batch_identity_time)
+    bool ident_timed = false;         // the last run recorded them
     // ---- host results
     // two alternating sets: the view of download c stays valid while batch c+1 runs and is downloaded
     // (page-locked: the device's final arrays are copied straight into them, rtx_api_download.hip)
@@ -442,6 +449,8 @@ struct rtx_index {
         PinBuf<uint32_t> h_peak;
         PinBuf<uint32_t> h_nearest, h_ties;  // rtx_batch_nearest (sized only under RTX_OPT_NEAREST)
         bool has_nearest = false;  // the download's run had RTX_OPT_NEAREST on
+        PinBuf<uint32_t> h_dist, h_qlen;  // rtx_batch_identity (sized only under RTX_OPT_IDENTITY)
+        bool has_identity = false; // the download's run had RTX_OPT_IDENTITY on
         uint64_t n_user = 0;       // queries of the view
         bool both = false;         // the download ran under RTX_OPT_STRAND: the exact matches are those of the chosen orientation
     } host_res[2];
@@ -498,6 +507,8 @@ struct rtx_index {
         for (auto e : prof.ev)
             if (e) (void)hipEventDestroy(e);
         for (auto e : ev_near) (void)hipEventDestroy(e);
+        for (auto e : ev_ident)
+            if (e) (void)hipEventDestroy(e);
         for (auto &r : rs) r.destroy_events();
         for (auto e : ev_set_free)
             if (e) (void)hipEventDestroy(e);

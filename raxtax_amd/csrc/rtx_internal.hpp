@@ -32,6 +32,7 @@ uint32_t index_swap_min_subs(rtx_index *index, uint32_t v);  // returns the prev
 uint32_t index_swap_run_ahead(rtx_index *index, uint32_t v);
 bool index_strand(const rtx_index *index);  // RTX_OPT_STRAND
 bool index_nearest(const rtx_index *index);  // RTX_OPT_NEAREST
+bool index_identity(const rtx_index *index);  // RTX_OPT_IDENTITY
 bool index_profile(const rtx_index *index, uint32_t *cutoff_hundredths, uint32_t *flags);  // a taxon profile is open (rtx_index_profile_begin), with what
 bool index_derep(const rtx_index *index);  // RTX_OPT_DEREP
 bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value

@@ -172,6 +172,26 @@ struct ProfileParams {
 };
 void launch_profile(hipStream_t s, const ProfileParams &p);
 
+// rtx_identity.hip: the semi-global edit distance of every query of the caller to its nearest reference (RTX_OPT_IDENTITY), once per run
+// behind strand_select_kernel
+struct IdentityParams {
+    uint32_t n;               // queries as the caller passed them
+    uint32_t max_len;         // the longest of them (no query beyond 1024 bases: no launch of the whole-wave kernel)
+    const uint32_t *nearest;  // [n] of the chosen orientation (StrandParams::nearest)
+    const uint8_t *strand;    // [n] 1: the reverse complement was classified, and is aligned
+    const uint8_t *qbytes;    // the batch's input set: two bases per byte (packed) or one
+    const uint64_t *qoff;     // [n + 1]
+    bool packed;
+    const uint32_t *ref_grp;  // [n_refs] the distinct sequence of every reference (launch_ref_group) ...
+    const uint64_t *rep_off;  // ... and where it lies (the exact-match lookup's, rtx_exact.hip)
+    const uint8_t *rep_bytes;
+    uint32_t n_refs;
+    uint32_t *dist;           // [n] RTX_NO_DIST: no nearest reference, or longer than RTX_IDENTITY_MAX_QUERY
+    uint32_t *qlen;           // [n]
+};
+void launch_identity(hipStream_t s, const IdentityParams &p);
+void launch_ref_group(hipStream_t s, const uint32_t *goff, const uint32_t *gids, uint32_t n_groups, uint32_t n_refs, uint32_t *ref_grp);
+
 struct KmerParams {
     const uint8_t *bases;
     const uint64_t *base_off;

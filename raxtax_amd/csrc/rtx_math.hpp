@@ -91,6 +91,70 @@ RTX_HD uint32_t nearest_match8(const uint32_t (&w)[4], uint32_t peak, uint32_t b
 }
 
 // ---------------------------------------------------------------------------
+// Alignment identity (identity_kernel, rtx_identity.hip; rtx_semiglobal_distance on the host; emul_identity on x86): the semi-global
+// edit distance of a query against its nearest reference by Myers' bit-vector algorithm in its block form (Myers 1999, in Hyyro's
+// formulation).  The pattern is the query in blocks of 64 bases, the text the reference; the horizontal delta that enters row 0 is 0 in
+// every column (the text's overhang is free), the score of the query's last row starts at qlen.
+// No per-symbol Peq: a block keeps the four one-hot bit PLANES of its 64 codes (bit j of plane x = code j has bit x), and Eq of a text
+// code c is the OR of the planes whose bit c holds -- two codes match when both are codes (1 .. 15) and intersect, a byte that is 0 or
+// above 15 has no bit in any plane and selects none.
+// ---------------------------------------------------------------------------
+struct IdentityBlock {
+    uint64_t pv, mv;        // vertical deltas +1 / -1 of the block's rows in the column last processed (column -1: all +1)
+    uint64_t plane[4];
+};
+// the code a text or pattern byte contributes: itself if it is one (1 .. 15), else 0
+RTX_HD uint32_t identity_code(uint32_t byte) { return byte > 15u ? 0u : byte; }
+// base i of the query in the orientation that was classified: fetch(j) = byte j as the caller gave it; minus = the reverse complement
+// (index reversed, the four bits of a code reversed, a byte above 15 unchanged: complement_code)
+template <class F>
+RTX_HD uint32_t identity_query_byte(const F &fetch, uint32_t qlen, uint32_t i, bool minus) {
+    if (!minus) return fetch(i);
+    const uint32_t b = fetch(qlen - 1u - i);
+    return b > 15u ? b : (((b & 1u) << 3) | ((b & 2u) << 1) | ((b & 4u) >> 1) | ((b & 8u) >> 3));
+}
+// block `blk` of a query of qlen bases (blk * 64 < qlen) before the first column
+template <class F>
+RTX_HD void identity_block_init(IdentityBlock &b, const F &fetch, uint32_t qlen, uint32_t blk, bool minus) {
+    b.pv = ~0ull;
+    b.mv = 0ull;
+    b.plane[0] = b.plane[1] = b.plane[2] = b.plane[3] = 0ull;
+    const uint32_t i0 = blk * 64u, n = qlen - i0 < 64u ? qlen - i0 : 64u;
+    for (uint32_t j = 0; j < n; j++) {
+        const uint64_t c = identity_code(identity_query_byte(fetch, qlen, i0 + j, minus));
+        b.plane[0] |= (c & 1u) << j;
+        b.plane[1] |= ((c >> 1) & 1u) << j;
+        b.plane[2] |= ((c >> 2) & 1u) << j;
+        b.plane[3] |= ((c >> 3) & 1u) << j;
+    }
+}
+// One column through one block.  code: identity_code of the text byte; hin: the horizontal delta at the block's top (-1, 0, +1: 0 for the
+// first block, the block above's result otherwise); out_mask: the one bit of the row of the block whose horizontal delta is returned -- row 63
+// hands it to the block below, row (qlen - 1) % 64 of the last block is the change of the score of the query's last row (identity_out_mask;
+// a mask and not a bit number: a 64-bit shift by a register is the slowest thing the step could hold).
+RTX_HD uint64_t identity_out_mask(uint32_t qlen, uint32_t blk) { return 1ull << ((blk + 1u) * 64u >= qlen ? (qlen - 1u) & 63u : 63u); }
+RTX_HD int identity_step(IdentityBlock &b, uint32_t code, int hin, uint64_t out_mask) {
+    uint64_t eq = ((code & 1u) ? b.plane[0] : 0ull) | ((code & 2u) ? b.plane[1] : 0ull) | ((code & 4u) ? b.plane[2] : 0ull) |
+                  ((code & 8u) ? b.plane[3] : 0ull);
+    const uint64_t pv = b.pv, mv = b.mv;
+    const uint64_t xv = eq | mv;
+    if (hin < 0) eq |= 1ull;
+    const uint64_t xh = (((eq & pv) + pv) ^ pv) | eq;  // (the only carry chain)
+    uint64_t ph = mv | ~(xh | pv);
+    uint64_t mh = pv & xh;
+    const int hout = ((ph & out_mask) != 0ull ? 1 : 0) - ((mh & out_mask) != 0ull ? 1 : 0);
+    ph = (ph << 1) | (hin > 0 ? 1ull : 0ull);
+    mh = (mh << 1) | (hin < 0 ? 1ull : 0ull);
+    b.pv = mh | ~(xv | ph);
+    b.mv = ph & xv;
+    return hout;
+}
+// hundredths of a percent of the query's bases that the alignment keeps (what the CLI prints): ((qlen - dist) 10000 + qlen / 2) / qlen
+RTX_HD uint32_t identity_hundredths(uint32_t dist, uint32_t qlen) {
+    return qlen ? (uint32_t)(((uint64_t)(qlen - dist) * 10000u + qlen / 2u) / qlen) : 0u;
+}
+
+// ---------------------------------------------------------------------------
 // Hash of an encoded sequence for the exact-match lookup (Tree.sequences.get, raxtax.rs:42) on the device.  The bytes are taken
 // as 8-byte little-endian words (the last one zero-padded); every word is mixed with its position and the mixes are ADDED, so
 // that the lanes of a wave can hash their words independently and meet in one sum.  Equal sequences hash equal; a collision only
