@@ -42,7 +42,9 @@ extern "C" {
                                 that is off by default, nothing that exists changes shape; and with the taxon profile, rtx_index_profile_* /
                                 rtx_profile_merge / rtx_profile_format: exports only; and with RTX_OPT_DEREP (27), rtx_derep_*,
                                 rtx_batch_prefetch_weights and rtx_raxtax_last_derep: exports and an option that is off by default; and with
-                                RTX_OPT_IDENTITY (28), RTX_NO_DIST, rtx_batch_identity, rtx_semiglobal_distance and rtx_raxtax_multi_ex3: the same) */
+                                RTX_OPT_IDENTITY (28), RTX_NO_DIST, rtx_batch_identity, rtx_semiglobal_distance and rtx_raxtax_multi_ex3: the same;
+                                and with primer trimming, rtx_trim_* / rtx_primer_search / rtx_index_set_primers / rtx_raxtax_last_trim /
+                                rtx_raxtax_multi_ex4: exports and a setting that is off by default) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -534,6 +536,62 @@ void rtx_derep_destroy(rtx_derep *d);
 int rtx_derep_plan(uint64_t n, const uint32_t *rep, uint32_t *uniq /*[n]*/, uint32_t *slot /*[n]*/, uint32_t *size /*[n]*/, uint64_t *n_unique);
 int rtx_raxtax_last_derep(uint64_t *queries, uint64_t *distinct, double *busy_seconds);
 
+/* ---- primer trimming (rtx_trim.hip; rtx_index_set_primers is the host mirror's use of it) ---------------------------------------------------
+ * Amplicon reads come with their PCR primers attached, the references without: what `cutadapt` is run for in front of a classifier, on the
+ * device.  Exact integers; the host function and the device agree bit for bit.
+ *   bytes        one per base, codes 1 .. 15.  Two bytes match when both are codes and share a bit (IUPAC degeneracy is an AND); a read
+ *                byte that is 0 or above 15 matches nothing; a pattern byte must be a code.
+ *   search(p, x, w, k)   p: m codes, 1 <= m <= RTX_TRIM_MAX_PATTERN; X = x[0 .. min(len(x), w)).  E[j], j = 0 .. len(X): the least
+ *                Levenshtein distance (substitution, insertion, deletion 1 each) of the WHOLE pattern to X[i .. j) over 0 <= i <= j -- the text
+ *                in front of the match is free, E[0] = m.  e = min E[j]; j* = the LARGEST j with E[j] == e; found iff e <= k (k < m).
+ *   5' pattern   (j*, e) = search(p, x, w, k): the read loses x[0 .. j*).
+ *   3' pattern   given as it reads on the read, 5'->3': (j*, e) = search(reverse(p), reverse(x), w, k), the read loses its last j* bases
+ *                (the tie rule cuts the most at either end).
+ *   several patterns of one end: among the found ones the least e wins, then the lowest index in the list.  The two ends are searched
+ *                independently on the untrimmed read.
+ *   per read     lo = the 5' cut or 0; hi = len - the 3' cut, or len; hi < lo: hi = lo (the read is left empty);
+ *                hit = pat5 | err5 << 8 | pat3 << 16 | err3 << 24, pattern RTX_TRIM_NO_PATTERN and errors 0 where nothing was found.
+ *                Never depends on the rest of the batch.
+ *   window       0: min(RTX_TRIM_MAX_WINDOW, m + max_errors + 32).
+ *   rtx_trim_create   an object of its own on GPU `device` like rtx_derep: one stream, its own buffers (they only grow), no rtx_index, a
+ *                copy of the patterns.  Checked in this order: null arguments, n == 0 or n > RTX_TRIM_MAX_PATTERNS, every pattern (a byte that
+ *                is no code, len 0 or above RTX_TRIM_MAX_PATTERN, max_errors >= len, window above RTX_TRIM_MAX_WINDOW, an unknown end):
+ *                RTX_ERR_INVALID; then the device: RTX_ERR_NO_DEVICE without a gfx950.
+ *   rtx_trim_run      lo / hi / hit of n reads, [n] each; bases / base_off as rtx_batch_prefetch takes them.  Only the ends of the reads
+ *                travel to the device.  n == 0: RTX_OK; a base_off that is not monotone or a read of 2^32 bases or more: RTX_ERR_INVALID.
+ *                Synchronous; calls on one object are serialised by the caller.
+ *   rtx_primer_search the search of ONE pattern in one read on the host (no device), with the function the kernel calls: *cut = j*,
+ *                *errors = e; *cut = 0 and *errors = RTX_NO_DIST when not found.  RTX_ERR_INVALID as rtx_trim_create refuses a pattern.
+ *   rtx_trim_apply    host: the kept ranges [lo, hi) of the reads back to back into out_bases (room for the sum of hi - lo, at most the
+ *                input's bytes) with out_off[n + 1] from 0.  RTX_ERR_INVALID unless lo <= hi <= the read's length.
+ *   rtx_index_set_primers  the patterns rtx_raxtax* trim every read with before anything else sees it (n == 0, the default: off -- no new
+ *                code runs, nothing is allocated, every output is what it is without).  Like RTX_OPT_DEREP honoured by the mirror alone
+ *                (rtx_batch_* and rtx_classify_batch ignore it), shapes no workspace, drops no uploaded batch; the handle keeps a copy.  The
+ *                handles of one call must hold the same list: RTX_ERR_INVALID otherwise.  The stage runs in front of dereplication; exact
+ *                matches, the `.tsv` sequence column and the identity's qlen are those of the trimmed read; an emptied read is classified
+ *                as the empty read.  rtx_index_primers: how many it holds.
+ *   rtx_raxtax_last_trim  the last rtx_raxtax* call of the process: its queries, those with a 5' primer, with a 3' primer, those left
+ *                empty (hi == lo of a read that had bases) and the busy seconds of the stage; all 0 with no primers set. */
+#define RTX_TRIM_5P 0u
+#define RTX_TRIM_3P 1u
+#define RTX_TRIM_MAX_PATTERNS 8
+#define RTX_TRIM_MAX_PATTERN 64
+#define RTX_TRIM_MAX_WINDOW 256
+#define RTX_TRIM_NO_PATTERN 0xFFu
+typedef struct { const uint8_t *codes; uint32_t len, end, max_errors, window; } rtx_trim_pattern;
+typedef struct rtx_trim rtx_trim;
+int rtx_trim_create(int device, const rtx_trim_pattern *pats, uint32_t n, rtx_trim **out);
+int rtx_trim_run(rtx_trim *t, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *lo /*[n]*/, uint32_t *hi /*[n]*/, uint32_t *hit /*[n]*/);
+void rtx_trim_destroy(rtx_trim *t);
+int rtx_trim_kernel_time(const rtx_trim *t, float *ms); /* milliseconds of the kernel of the last rtx_trim_run, from HIP events around it */
+int rtx_primer_search(const uint8_t *p, uint32_t m, const uint8_t *x, uint64_t n, uint32_t end, uint32_t window, uint32_t max_errors,
+                      uint32_t *cut, uint32_t *errors);
+int rtx_trim_apply(uint64_t n, const uint8_t *bases, const uint64_t *base_off, const uint32_t *lo, const uint32_t *hi, uint8_t *out_bases,
+                   uint64_t *out_off /*[n + 1]*/);
+int rtx_index_set_primers(rtx_index *index, const rtx_trim_pattern *pats, uint32_t n);
+int rtx_index_primers(const rtx_index *index, uint32_t *n);
+int rtx_raxtax_last_trim(uint64_t *queries, uint64_t *with5, uint64_t *with3, uint64_t *emptied, double *busy_seconds);
+
 /* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
  * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte
  * for byte what rtx_format_query prints for the view, the label, the bases and the exact matches of the query (the override of
@@ -763,6 +821,15 @@ int rtx_raxtax_multi_ex3(rtx_index *const *indices, uint32_t n_indices, const rt
                          const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                          int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                          rtx_query_align_fn align, void *align_ctx);
+/* rtx_raxtax_multi_ex3 with a callback for the primer trimming (rtx_index_set_primers): called for EVERY query of the caller, in input
+ * order, directly before the `align` callback of that query (a query without a message, such as an emptied read, has no `align` call and
+ * still has this one): the read's length as given, the kept range [lo, hi) and the hit word.  With no primers set: 0, raw_len and nothing
+ * found.  Per query of the caller also under RTX_OPT_DEREP: every read is trimmed itself.  Either callback may be NULL. */
+typedef int (*rtx_query_trim_fn)(void *ctx, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit);
+int rtx_raxtax_multi_ex4(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

@@ -25,6 +25,9 @@ RTX_OPT_DEREP = 27                 # rtx_index_set_option: raxtax() classifies e
 RTX_DEFAULT_DEREP_HASH_MASK = 3    # rtx_set_default_option: the hash of rtx_derep_run ANDed with a mask (tests)
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 
+RTX_TRIM_5P, RTX_TRIM_3P = 0, 1      # rtx_trim_pattern.end
+RTX_TRIM_MAX_PATTERNS, RTX_TRIM_MAX_PATTERN, RTX_TRIM_MAX_WINDOW, RTX_TRIM_NO_PATTERN = 8, 64, 256, 0xFF
+
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
 u32p = C.POINTER(C.c_uint32)
@@ -52,6 +55,10 @@ class TextView(C.Structure):
 class ProfileView(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("cutoff_hundredths", C.c_uint32), ("flags", C.c_uint32), ("clade", u64p), ("direct", u64p),
                 ("conf_sum", u64p), ("totals", C.c_uint64 * 4)]
+
+
+class TrimPattern(C.Structure):
+    _fields_ = [("codes", u8p), ("len", C.c_uint32), ("end", C.c_uint32), ("max_errors", C.c_uint32), ("window", C.c_uint32)]
 
 
 class RtxError(RuntimeError):
@@ -178,6 +185,16 @@ _SIGNATURES = {
     "rtx_derep_destroy": (None, [C.c_void_p]),
     "rtx_derep_plan": (C.c_int, [C.c_uint64, u32p, u32p, u32p, u32p, C.POINTER(C.c_uint64)]),
     "rtx_raxtax_last_derep": (C.c_int, [C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    "rtx_trim_create": (C.c_int, [C.c_int, C.POINTER(TrimPattern), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rtx_trim_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u32p, u32p]),
+    "rtx_trim_destroy": (None, [C.c_void_p]),
+    "rtx_trim_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_primer_search": (C.c_int, [u8p, C.c_uint32, u8p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, u32p, u32p]),
+    "rtx_trim_apply": (C.c_int, [C.c_uint64, u8p, u64p, u32p, u32p, u8p, u64p]),
+    "rtx_index_set_primers": (C.c_int, [C.c_void_p, C.POINTER(TrimPattern), C.c_uint32]),
+    "rtx_index_primers": (C.c_int, [C.c_void_p, u32p]),
+    "rtx_raxtax_last_trim": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
+    "rtx_raxtax_multi_ex4": (C.c_int, None),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

@@ -284,7 +284,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False, identity: bool = False):
+                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -345,8 +345,23 @@ class Index:
             check(self._lib.rtx_index_set_option(self._h, 28, 1))
         if derep:   # RTX_OPT_DEREP: raxtax() classifies each distinct read of a chunk once (rtx_derep.hip); classify() ignores it
             check(self._lib.rtx_index_set_option(self._h, _lib.RTX_OPT_DEREP, 1))
+        if primers:   # rtx_index_set_primers: raxtax() trims every read with them first (rtx_trim.hip); classify() ignores them
+            self.set_primers(primers)
         self._view = ResultView()
         self._keep = None
+
+    def set_primers(self, patterns) -> None:
+        """rtx_index_set_primers: the patterns (TrimPrimer, or (codes, end, max_errors[, window]) tuples; see primer_patterns) raxtax()
+        trims every read with; an empty list switches the stage off."""
+        arr, _keep = _trim_patterns(patterns)
+        check(self._lib.rtx_index_set_primers(self._h, arr, len(_keep)))
+
+    @property
+    def primers(self) -> int:
+        """How many patterns the handle holds (rtx_index_primers)."""
+        n = C.c_uint32()
+        check(self._lib.rtx_index_primers(self._h, C.byref(n)))
+        return int(n.value)
 
     @property
     def prune_verdict(self):
@@ -700,6 +715,137 @@ _HIT = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uin
 _ALIGN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
 NO_REF = 0xFFFFFFFF   # RTX_NO_REF
 NO_DIST = 0xFFFFFFFF  # RTX_NO_DIST
+_TRIM = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
+TRIM_5P, TRIM_3P, TRIM_NO_PATTERN = _lib.RTX_TRIM_5P, _lib.RTX_TRIM_3P, _lib.RTX_TRIM_NO_PATTERN
+IUPAC = {"A": 1, "C": 2, "G": 4, "T": 8, "W": 9, "S": 6, "M": 3, "K": 12, "R": 5, "Y": 10, "B": 14, "D": 13, "H": 11, "V": 7, "N": 15}
+
+
+@dataclass
+class TrimPrimer:
+    """One pattern of the primer trimming (rtx_trim_pattern): its codes (1 .. 15, at most 64), the end it is looked for at (TRIM_5P / TRIM_3P; a
+    3' pattern as it reads on the read, 5'->3'), the errors allowed (fewer than its codes) and the window (0: min(256, len + max_errors + 32))."""
+    codes: np.ndarray
+    end: int
+    max_errors: int
+    window: int = 0
+
+
+def encode_iupac(text: str) -> np.ndarray:
+    """The codes of an oligo given in IUPAC letters (either case); ValueError names a character that is none."""
+    try:
+        return np.array([IUPAC[ch] for ch in text.upper()], np.uint8)
+    except KeyError as e:
+        raise ValueError(f"primer {text!r}: {e.args[0]!r} is no IUPAC code") from None
+
+
+def primer_patterns(pair: Tuple[str, str], error_percent: int = 10, window: int = 0, both_strands: bool = False) -> List[TrimPrimer]:
+    """The pattern list of a (FWD, REV) pair of oligos as ordered, 5'->3' (what raxtax-hip --primers FWD:REV registers): FWD at the 5' end and
+    revcomp(REV) at the 3' end; both_strands=True adds REV at 5' and revcomp(FWD) at 3' (reads given in either orientation).  Either oligo may be
+    empty.  max_errors = len * error_percent // 100."""
+    fwd, rev = (encode_iupac(x) for x in pair)
+    out = []
+
+    def add(codes, end):
+        if len(codes):
+            out.append(TrimPrimer(codes, end, len(codes) * int(error_percent) // 100, window))
+
+    add(fwd, TRIM_5P)
+    add(revcomp(rev) if len(rev) else rev, TRIM_3P)
+    if both_strands:
+        add(rev, TRIM_5P)
+        add(revcomp(fwd) if len(fwd) else fwd, TRIM_3P)
+    return out
+
+
+def _trim_patterns(patterns):
+    """(rtx_trim_pattern array, the arrays it points into) of TrimPrimer objects or (codes, end, max_errors[, window]) tuples."""
+    ps = [p if isinstance(p, TrimPrimer) else TrimPrimer(*p) for p in patterns]
+    keep = [np.ascontiguousarray(p.codes, dtype=np.uint8) for p in ps]
+    arr = (_lib.TrimPattern * max(len(ps), 1))()
+    for i, (p, k) in enumerate(zip(ps, keep)):
+        arr[i].codes = ptr(k if len(k) else np.zeros(1, np.uint8), u8p)
+        arr[i].len, arr[i].end, arr[i].max_errors, arr[i].window = len(k), int(p.end), int(p.max_errors), int(p.window)
+    return arr, keep
+
+
+def trim_hit(hit: int) -> Tuple[Optional[int], int, Optional[int], int]:
+    """(pattern5 or None, errors5, pattern3 or None, errors3) of a hit word: pat5 | err5 << 8 | pat3 << 16 | err3 << 24."""
+    hit = int(hit)
+    p5, e5, p3, e3 = hit & 0xFF, (hit >> 8) & 0xFF, (hit >> 16) & 0xFF, (hit >> 24) & 0xFF
+    return (None if p5 == TRIM_NO_PATTERN else p5), e5, (None if p3 == TRIM_NO_PATTERN else p3), e3
+
+
+def primer_search(pattern: np.ndarray, read: np.ndarray, end: int = TRIM_5P, window: int = 0, max_errors: int = 0) -> Tuple[int, int]:
+    """rtx_primer_search: (cut, errors) of one pattern in one read on the host, with the function the device kernel calls; (0, NO_DIST) when
+    not found."""
+    p = np.ascontiguousarray(pattern, dtype=np.uint8)
+    x = np.ascontiguousarray(read, dtype=np.uint8)
+    one = np.zeros(1, np.uint8)
+    cut, err = C.c_uint32(), C.c_uint32()
+    check(_lib.load().rtx_primer_search(ptr(p if len(p) else one, u8p), len(p), ptr(x if len(x) else one, u8p), len(x), int(end), int(window),
+                                        int(max_errors), C.byref(cut), C.byref(err)))
+    return int(cut.value), int(err.value)
+
+
+def trim_apply(bases: np.ndarray, base_off: np.ndarray, lo: np.ndarray, hi: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """rtx_trim_apply: (bases, offsets) of the kept ranges [lo, hi) of the reads, back to back."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+    lo = np.ascontiguousarray(lo, dtype=np.uint32)
+    hi = np.ascontiguousarray(hi, dtype=np.uint32)
+    n = len(base_off) - 1
+    if len(lo) != n or len(hi) != n:
+        raise ValueError(f"{len(lo)} / {len(hi)} ranges for {n} reads")
+    out = np.zeros(max(len(bases), 1), np.uint8)
+    off = np.zeros(n + 1, np.uint64)
+    z8, z32 = np.zeros(1, np.uint8), np.zeros(1, np.uint32)
+    check(_lib.load().rtx_trim_apply(n, ptr(bases if len(bases) else z8, u8p), ptr(base_off, u64p), ptr(lo if n else z32, u32p),
+                                     ptr(hi if n else z32, u32p), ptr(out, u8p), ptr(off, u64p)))
+    return out[:int(off[-1])].copy(), off
+
+
+class Trim:
+    """The primer-trimming stage on one GPU (rtx_trim): an object of its own beside any Index, one stream, buffers that only grow."""
+
+    def __init__(self, device: int, patterns):
+        self._lib = _lib.load()
+        self._h = None
+        arr, keep = _trim_patterns(patterns)
+        h = C.c_void_p()
+        check(self._lib.rtx_trim_create(device, arr, len(keep), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_trim_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, bases: np.ndarray, base_off: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(lo, hi, hit) per read (rtx_trim_run): the read keeps [lo, hi); hit as trim_hit() takes it apart."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        n = len(base_off) - 1
+        lo, hi, hit = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(3))
+        check(self._lib.rtx_trim_run(self._h, n, ptr(bases if len(bases) else np.zeros(1, np.uint8), u8p), ptr(base_off, u64p), ptr(lo, u32p),
+                                     ptr(hi, u32p), ptr(hit, u32p)))
+        return lo[:n], hi[:n], hit[:n]
+
+    def kernel_ms(self) -> float:
+        """Milliseconds of the kernel of the last run(), from HIP events (rtx_trim_kernel_time)."""
+        ms = C.c_float()
+        check(self._lib.rtx_trim_kernel_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
+
+def raxtax_last_trim() -> Tuple[int, int, int, int, float]:
+    """rtx_raxtax_last_trim: (queries, with a 5' primer, with a 3' primer, left empty, busy seconds of the stage) of the last raxtax() call of
+    this process; all 0 when its handles had no primers set."""
+    a, b, c, d, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    check(_lib.load().rtx_raxtax_last_trim(C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(s)))
+    return int(a.value), int(b.value), int(c.value), int(d.value), float(s.value)
 
 
 def semiglobal_distance(q: np.ndarray, r: np.ndarray) -> int:
@@ -725,7 +871,8 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
            chunk_size: int, sender: Callable[[str, str, Optional[str]], None], tsv: bool,
            info: Optional[Callable[[str, int, int, int], None]] = None,
            hit: Optional[Callable[[str, int, int, int, int, int], None]] = None,
-           align: Optional[Callable[[str, int, int, int, int, int, int, int], None]] = None) -> None:
+           align: Optional[Callable[[str, int, int, int, int, int, int, int], None]] = None,
+           trim: Optional[Callable[[str, int, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
@@ -733,7 +880,9 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     (rtx_raxtax_multi_ex); handles built with strand="both" report the orientation with the larger peak.
     `hit(label, strand, peak, t, nearest, ties)` is the same with the nearest reference and its ties (rtx_raxtax_multi_ex2; handles built with
     nearest=True, else NO_REF and 0).  `align(label, strand, peak, t, nearest, ties, dist, qlen)` adds the alignment identity
-    (rtx_raxtax_multi_ex3; handles built with identity=True, else NO_DIST and the query's length).  Give one of the three."""
+    (rtx_raxtax_multi_ex3; handles built with identity=True, else NO_DIST and the query's length).  Give one of the three.
+    `trim(label, raw_len, lo, hi, hit)` is called for every query, in input order, directly before `align` (rtx_raxtax_multi_ex4; handles built
+    with primers=[...]: the read kept [lo, hi) of its raw_len bases, hit as trim_hit() takes it apart); it goes with `align` or alone."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
@@ -741,8 +890,11 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     lib.rtx_raxtax_multi_ex.argtypes = lib.rtx_raxtax_multi.argtypes + [_INFO, C.c_void_p]
     lib.rtx_raxtax_multi_ex2.argtypes = lib.rtx_raxtax_multi.argtypes + [_HIT, C.c_void_p]
     lib.rtx_raxtax_multi_ex3.argtypes = lib.rtx_raxtax_multi.argtypes + [_ALIGN, C.c_void_p]
+    lib.rtx_raxtax_multi_ex4.argtypes = lib.rtx_raxtax_multi_ex3.argtypes + [_TRIM, C.c_void_p]
     if (info is not None) + (hit is not None) + (align is not None) > 1:
         raise ValueError("raxtax: give one of info, hit and align")
+    if trim is not None and (info is not None or hit is not None):
+        raise ValueError("raxtax: trim goes with align or alone")
     handles = list(tree) if isinstance(tree, (list, tuple)) else [tree]
     labels = (C.c_char_p * max(len(queries), 1))(*[q[0].encode() for q in queries])
     flat, off = _flatten([q[1] for q in queries])
@@ -780,7 +932,20 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if align is not None:
+    def cb_trim(_ctx, label, raw_len, lo, hi, hit_word):
+        try:
+            trim(label.decode(), int(raw_len), int(lo), int(hi), int(hit_word))
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if trim is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex4(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
+                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None, _TRIM(cb_trim), None)
+    elif align is not None:
         arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         rc = lib.rtx_raxtax_multi_ex3(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                       int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _ALIGN(cb_align), None)

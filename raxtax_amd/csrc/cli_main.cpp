@@ -12,6 +12,13 @@
 //   (--identity, implies --hits: two more columns at the end of every line of raxtax.hits -- the semi-global edit distance of the query to that
 //    reference and the identity in percent, two decimals; '-' twice where there is no distance: RTX_OPT_IDENTITY)
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
+//   (--primers FWD:REV [--primer-errors PCT] [--primer-window N]: the PCR primers are trimmed off every read on the device before anything else
+//    sees it (rtx_index_set_primers, rtx_trim.hip).  The oligos as ordered, 5'->3', IUPAC codes allowed, either side may be empty, the option
+//    may be given twice: FWD is looked for at the 5' end and the reverse complement of REV at the 3' end -- under --strand both REV at the
+//    5' end and the reverse complement of FWD at the 3' end as well -- with at most len * PCT / 100 errors (default 10) in the first / last
+//    N bases (default: len + errors + 32).  PREFIX/raxtax.trim: a header, then label, length, start, end, primer5, errors5, primer3, errors3
+//    per query in input order -- the read kept [start, end) of its length bases, the primers by their place in the list above, '-' where
+//    none was found; "N queries, A with a 5' primer, B with a 3' primer, C left empty" goes to the log)
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
@@ -122,18 +129,21 @@ std::string fingerprint(const std::string &path) {
 
 // (--strand both is part of the checkpoint like the three flags: a rerun with the other setting starts over; a default run writes the file it always wrote)
 // (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
-std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false) {
+// (... and --primers with its two settings, as given: trimmed reads are other reads)
+std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
+                            const std::string &primers = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
        << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "") << (identity ? ",\n  \"identity\": true" : "");
     if (profile) ss << ",\n  \"profile\": " << profile;
+    if (!primers.empty()) ss << ",\n  \"primers\": \"" << primers << "\"";
     ss << "\n}\n";
     return ss.str();
 }
 
 // check_incomplete_output (io.rs:156-187): keep only the lines whose first field is a finished query
-void purge_incomplete(const std::string &path, const std::set<std::string> &done) {
+void purge_incomplete(const std::string &path, const std::set<std::string> &done, bool keep_header = false) {
     std::ifstream in(path);
     if (!in) return;
     std::vector<std::string> keep;
@@ -141,6 +151,7 @@ void purge_incomplete(const std::string &path, const std::set<std::string> &done
     std::string line;
     while (std::getline(in, line)) {
         const size_t tab = line.find('\t');
+        if (keep_header) { keep.push_back(line); keep_header = false; continue; }
         if (tab != std::string::npos && done.count(line.substr(0, tab))) keep.push_back(line);
         else rewrite = true;
     }
@@ -154,8 +165,18 @@ void purge_incomplete(const std::string &path, const std::set<std::string> &done
     rename(tmp.c_str(), path.c_str());
 }
 
+// parser.rs:11-34 for an oligo on the command line; 0 where the character is no IUPAC code
+uint8_t iupac_code(char ch) {
+    switch (toupper((unsigned char)ch)) {
+        case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8;
+        case 'W': return 9; case 'S': return 6; case 'M': return 3; case 'K': return 12; case 'R': return 5; case 'Y': return 10;
+        case 'B': return 14; case 'D': return 13; case 'H': return 11; case 'V': return 7; case 'N': return 15;
+        default: return 0;
+    }
+}
+
 struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits;
+    std::ofstream out, tsv, ckp, strand, hits, trim;
     bool want_tsv = false, want_strand = false, want_hits = false;
     const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
 };
@@ -180,6 +201,8 @@ int main(int argc, char **argv) {
     bool want_hits = false;     // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
     bool want_identity = false; // --identity: RTX_OPT_IDENTITY on every handle, dist and identity at the end of every line of raxtax.hits (implies --hits)
     bool derep = false;         // --derep: RTX_OPT_DEREP on every handle (each distinct read of a chunk is classified once; the files are the same)
+    std::vector<std::pair<std::string, std::string>> primer_pairs;  // --primers FWD:REV (once or twice): rtx_index_set_primers on every handle, PREFIX/raxtax.trim
+    uint32_t primer_pct = 10, primer_window = 0;                   // --primer-errors PCT, --primer-window N
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -225,6 +248,25 @@ int main(int argc, char **argv) {
         else if (a == "--hits") want_hits = true;
         else if (a == "--identity") want_identity = want_hits = true;
         else if (a == "--derep") derep = true;
+        else if (a == "--primers") {
+            const std::string v = val();
+            const size_t colon = v.find(':');
+            if (colon == std::string::npos || v.find(':', colon + 1) != std::string::npos || v.size() < 2) {
+                fprintf(stderr, "raxtax-hip: --primers takes FWD:REV (either side may be empty), not '%s'\n", v.c_str());
+                return 64;
+            }
+            primer_pairs.emplace_back(v.substr(0, colon), v.substr(colon + 1));
+        }
+        else if (a == "--primer-errors") {
+            const int x = atoi(val());
+            if (x < 0 || x > 99) { fprintf(stderr, "raxtax-hip: --primer-errors takes a percentage, 0 .. 99\n"); return 64; }
+            primer_pct = (uint32_t)x;
+        }
+        else if (a == "--primer-window") {
+            const int x = atoi(val());
+            if (x < 1 || x > RTX_TRIM_MAX_WINDOW) { fprintf(stderr, "raxtax-hip: --primer-window takes 1 .. %d bases\n", RTX_TRIM_MAX_WINDOW); return 64; }
+            primer_window = (uint32_t)x;
+        }
         else if (a == "--profile") {
             char *end = nullptr;
             const char *v = val();
@@ -237,7 +279,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -247,7 +289,40 @@ int main(int argc, char **argv) {
         fprintf(stderr, "raxtax-hip: -d is required, -i unless --only-db; --only-db conflicts with --skip-db\n");
         return 64;
     }
-    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp";
+    // --primers: the pattern list, checked here -- before the database is read and any device is touched
+    struct Primer { std::string name; std::vector<uint8_t> codes; uint32_t end; };
+    std::vector<Primer> primers;
+    std::string primer_spec;
+    for (const auto &pr : primer_pairs) {
+        std::vector<uint8_t> fwd, rev;
+        for (int side = 0; side < 2; side++) {
+            const std::string &oligo = side ? pr.second : pr.first;
+            for (char ch : oligo) {
+                const uint8_t c = iupac_code(ch);
+                if (!c) { fprintf(stderr, "raxtax-hip: --primers: '%c' in primer %s is no IUPAC code\n", ch, oligo.c_str()); return 64; }
+                (side ? rev : fwd).push_back(c);
+            }
+            if (oligo.size() > RTX_TRIM_MAX_PATTERN) { fprintf(stderr, "raxtax-hip: --primers: primer %s has %zu bases (at most %d)\n", oligo.c_str(), oligo.size(), RTX_TRIM_MAX_PATTERN); return 64; }
+        }
+        auto rc_of = [](const std::vector<uint8_t> &x) { std::vector<uint8_t> y(x.size() + 1); (void)rtx_revcomp(x.data(), x.size(), y.data()); y.resize(x.size()); return y; };
+        auto add = [&](const std::string &name, const std::vector<uint8_t> &codes, uint32_t end) {
+            if (!codes.empty()) primers.push_back({name, codes, end});
+        };
+        add(pr.first, fwd, RTX_TRIM_5P);
+        add("revcomp(" + pr.second + ")", rc_of(rev), RTX_TRIM_3P);
+        if (both_strands) {
+            add(pr.second, rev, RTX_TRIM_5P);
+            add("revcomp(" + pr.first + ")", rc_of(fwd), RTX_TRIM_3P);
+        }
+        if (primers.size() > RTX_TRIM_MAX_PATTERNS) {
+            fprintf(stderr, "raxtax-hip: --primers: %s:%s makes %zu patterns (at most %d%s)\n", pr.first.c_str(), pr.second.c_str(), primers.size(), RTX_TRIM_MAX_PATTERNS,
+                    both_strands ? "; --strand both registers every oligo at both ends" : "");
+            return 64;
+        }
+        primer_spec += (primer_spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
+    }
+    if (!primer_spec.empty()) primer_spec += ";errors=" + std::to_string(primer_pct) + ";window=" + std::to_string(primer_window);
+    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && derep) {
         fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
@@ -259,7 +334,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -277,6 +352,7 @@ int main(int argc, char **argv) {
             if (tsv) purge_incomplete(tsv_path, done);
             if (both_strands) purge_incomplete(strand_path, done);
             if (want_hits) purge_incomplete(hits_path, done);
+            if (!primers.empty()) purge_incomplete(trim_path, done, true);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -330,7 +406,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -417,6 +493,11 @@ int main(int argc, char **argv) {
                 if (rcs[k] == RTX_OK && want_hits) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_NEAREST, 1);
                 if (rcs[k] == RTX_OK && want_identity) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_IDENTITY, 1);
                 if (rcs[k] == RTX_OK && derep) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEREP, 1);
+                if (rcs[k] == RTX_OK && !primers.empty()) {
+                    std::vector<rtx_trim_pattern> pats;
+                    for (const Primer &p : primers) pats.push_back({p.codes.data(), (uint32_t)p.codes.size(), p.end, (uint32_t)(p.codes.size() * primer_pct / 100u), primer_window});
+                    rcs[k] = rtx_index_set_primers(indices[k], pats.data(), (uint32_t)pats.size());
+                }
                 if (rcs[k] == RTX_OK && profile_cutoff)
                     rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
@@ -448,6 +529,14 @@ int main(int argc, char **argv) {
     if (want_hits) sink.hits.open(hits_path, mode);
     else if (mode == std::ios::trunc) remove(hits_path.c_str());  // (likewise)
     if (mode == std::ios::trunc) remove(profile_path.c_str());  // (written at the end of a run with --profile)
+    if (!primers.empty()) {
+        const bool header = mode == std::ios::trunc || !is_file(trim_path);
+        sink.trim.open(trim_path, mode);
+        if (header) sink.trim << "label\tlength\tstart\tend\tprimer5\terrors5\tprimer3\terrors3\n";
+        for (size_t k = 0; k < primers.size(); k++)
+            fprintf(stderr, "[INFO ] --primers: pattern %zu at the %s end: %s, at most %zu error(s)\n", k, primers[k].end == RTX_TRIM_3P ? "3'" : "5'", primers[k].name.c_str(),
+                    primers[k].codes.size() * primer_pct / 100u);
+    } else if (mode == std::ios::trunc) remove(trim_path.c_str());  // (likewise)
     sink.want_strand = both_strands;
     sink.want_hits = want_hits;
     sink.tree = tree;
@@ -488,8 +577,32 @@ int main(int argc, char **argv) {
         }
         return (!s->want_strand || s->strand.good()) && s->hits.good() ? 0 : 1;
     };
+    // ... and, under --primers, what was cut off every query (also one that has no result lines: an emptied read)
+    auto trimmed = [](void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit) -> int {
+        Sink *s = static_cast<Sink *>(c);
+        const uint32_t p5 = hit & 0xFFu, e5 = (hit >> 8) & 0xFFu, p3 = (hit >> 16) & 0xFFu, e3 = hit >> 24;
+        s->trim << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t';
+        if (p5 == RTX_TRIM_NO_PATTERN) s->trim << "-\t-\t";
+        else s->trim << p5 << '\t' << e5 << '\t';
+        if (p3 == RTX_TRIM_NO_PATTERN) s->trim << "-\t-\n";
+        else s->trim << p3 << '\t' << e3 << '\n';
+        return s->trim.good() ? 0 : 1;
+    };
+    // (rtx_raxtax_multi_ex4 carries the callback of --identity: without that option the one of --strand both / --hits stands in its shape)
+    auto info_as_align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {
+        Sink *s = static_cast<Sink *>(c);
+        if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
+        if (s->want_hits) {
+            s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
+            if (nearest == RTX_NO_REF) s->hits << "-\t-\n";
+            else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest) << '\n';
+        }
+        return (!s->want_strand || s->strand.good()) && (!s->want_hits || s->hits.good()) ? 0 : 1;
+    };
     int rc = RTX_OK;
     uint64_t n = 0;
+    uint64_t trim_total[4] = {0, 0, 0, 0};  // --primers: over the blocks of the file (rtx_raxtax_last_trim)
+    double trim_busy = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
     double derep_busy = 0;
     bool parse_failed = false;
@@ -519,13 +632,22 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            if (want_identity)
+            if (!primers.empty())
+                rc = rtx_raxtax_multi_ex4(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                          want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, +trimmed, &sink);
+            else if (want_identity)
                 rc = rtx_raxtax_multi_ex3(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
                                           +align, &sink);
             else
                 rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
                                           both_strands || want_hits ? +info : nullptr, &sink);
             n += nb;
+            if (!primers.empty()) {
+                uint64_t tq[4] = {0, 0, 0, 0};
+                double tb = 0;
+                if (rtx_raxtax_last_trim(&tq[0], &tq[1], &tq[2], &tq[3], &tb) == RTX_OK) { for (int k = 0; k < 4; k++) trim_total[k] += tq[k]; trim_busy += tb; }
+                if (timing) fprintf(stderr, "[TIMING] primer trimming of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)tq[0], tb);
+            }
             if (derep) {
                 uint64_t dq = 0, du = 0;
                 double db_ = 0;
@@ -553,8 +675,14 @@ int main(int argc, char **argv) {
     if (tsv) sink.tsv.flush();
     if (both_strands) sink.strand.flush();
     if (want_hits) sink.hits.flush();
+    if (!primers.empty()) sink.trim.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
+    if (!primers.empty()) {
+        fprintf(stderr, "[INFO ] --primers: %llu queries, %llu with a 5' primer, %llu with a 3' primer, %llu left empty\n", (unsigned long long)trim_total[0],
+                (unsigned long long)trim_total[1], (unsigned long long)trim_total[2], (unsigned long long)trim_total[3]);
+        if (timing) t_log << ", \"trim_busy\": " << trim_busy;
+    }
     if (derep) {  // (per chunk: a copy in another chunk counts as a distinct read of its own)
         fprintf(stderr, "[INFO ] --derep: %llu queries, %llu distinct\n", (unsigned long long)derep_queries, (unsigned long long)derep_distinct);
         if (timing) t_log << ", \"derep_busy\": " << derep_busy;

@@ -77,6 +77,8 @@ std::mutex g_timing_mu;
 LastTiming g_timing{{0, 0, 0, 0}, 0};
 struct LastDerep { uint64_t queries, distinct; double busy; };  // rtx_raxtax_last_derep (under g_timing_mu)
 LastDerep g_derep{0, 0, 0.0};
+struct LastTrim { uint64_t queries, with5, with3, emptied; double busy; };  // rtx_raxtax_last_trim (under g_timing_mu)
+LastTrim g_trim{0, 0, 0, 0, 0.0};
 
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
@@ -84,6 +86,8 @@ using RawSender = std::function<bool(const char *, const char *, const char *)>;
 // ... with the nearest reference and its ties behind them (rtx_query_hit_fn; RTX_NO_REF and 0 with RTX_OPT_NEAREST off)
 // ... and the alignment identity: distance and query length (rtx_query_align_fn; RTX_NO_DIST and the length with RTX_OPT_IDENTITY off)
 using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t)>;
+// (label, length as given, lo, hi, hit) of every query, directly before its RawInfo call (rtx_query_trim_fn); empty: nobody asked
+using RawTrim = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint32_t)>;
 
 // Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the
 // one thread that dereplicates, which was most of the stage; the buffers travel between the chunks of a call through a pool, so that
@@ -159,6 +163,13 @@ struct Chunk {
     std::vector<uint32_t> size;        // [nu] copies of every distinct read: its weight in an open profile
     ByteBuf u_bases;
     std::vector<uint64_t> u_off;
+    // primer trimming (rtx_index_set_primers): the reads of the chunk as everything downstream sees them -- the caller's arrays, or, where a
+    // primer was found in the chunk, the kept ranges back to back (t_bases / t_off, [nq + 1] from 0).  Query i: src_bases + src_off[i].
+    const uint8_t *src_bases = nullptr;
+    const uint64_t *src_off = nullptr;
+    std::vector<uint32_t> lo, hi, hit;  // [nq] rtx_trim_run, per query of the caller (empty: the option is off)
+    ByteBuf t_bases;
+    std::vector<uint64_t> t_off;
     rtx_text_view text{};              // RTX_OPT_DEVICE_TEXT: the messages as the device formatted them (valid as long as `res`)
     rtx_result_view res{};
     int stage = 0;                     // 1: exact matches looked up (or left to the device), 2: classified, 3: formatted, 4: sent
@@ -175,11 +186,13 @@ struct Chunk {
 //                   Under RTX_OPT_DEREP it first finds the copies of the chunk on the device (rtx_derep_run, a stream of its own beside
 //                   the handle's) and cuts the chunk down to its distinct reads: the handle classifies those, the format thread and
 //                   the sender go on per query of the caller (Chunk::slot)
+//                   With primers set (rtx_index_set_primers) it trims the reads of the chunk before that (rtx_trim_run, the same kind of
+//                   stage): the copies are looked for among the trimmed reads, and everything downstream sees those (Chunk::src_bases)
 //   calling thread: the sender, one message per query in INPUT order (raxtax.rs:85-87): chunk 0, 1, 2 ... as they become ready.
 // A handle keeps two result sets, so the view of its k-th chunk stays valid until its (k + 2)-th is classified.
 int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_t n_queries, const char *const *labels,
         const uint8_t *bases, const uint64_t *base_off, bool skip_exact_matches, bool raw_confidence, uint64_t chunk_size,
-        const RawSender &sender, bool tsv, const RawInfo &info = RawInfo()) {
+        const RawSender &sender, bool tsv, const RawInfo &info = RawInfo(), const RawTrim &trim_cb = RawTrim()) {
     if (!indices || n_dev == 0 || !tree || !base_off || !labels) { rtx::set_error("rtx_raxtax: null argument"); return RTX_ERR_INVALID; }
     for (uint32_t d = 0; d < n_dev; d++) {
         if (!indices[d]) { rtx::set_error("rtx_raxtax: null index handle"); return RTX_ERR_INVALID; }
@@ -243,6 +256,29 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             dereps.own.push_back(dereps.of[d]);
         }
     }
+    // Primers (rtx_index_set_primers): the same list on every handle.  One stage object (rtx_trim.hip) per distinct device, as for derep.
+    const std::vector<rtx::TrimPrimer> &primers = rtx::index_primers(indices[0]);
+    const bool trim = !primers.empty();
+    for (uint32_t d = 1; d < n_dev; d++)
+        if (!(rtx::index_primers(indices[d]) == primers)) { rtx::set_error("rtx_raxtax_multi: the handles disagree on their primers (rtx_index_set_primers)"); return RTX_ERR_INVALID; }
+    struct Trims {
+        std::vector<rtx_trim *> of;  // per handle; handles of one device share an object
+        std::vector<rtx_trim *> own;
+        ~Trims() { for (auto *p : own) rtx_trim_destroy(p); }
+    } trims;
+    if (trim) {
+        std::vector<rtx_trim_pattern> pats(primers.size());
+        for (size_t i = 0; i < primers.size(); i++) pats[i] = {primers[i].codes.data(), (uint32_t)primers[i].codes.size(), primers[i].end, primers[i].max_errors, primers[i].window};
+        trims.of.assign(n_dev, nullptr);
+        for (uint32_t d = 0; d < n_dev; d++) {
+            for (uint32_t e = 0; e < d && !trims.of[d]; e++)
+                if (rtx::index_device(indices[e]) == rtx::index_device(indices[d])) trims.of[d] = trims.of[e];
+            if (trims.of[d]) continue;
+            const int rc = rtx_trim_create(rtx::index_device(indices[d]), pats.data(), (uint32_t)pats.size(), &trims.of[d]);
+            if (rc) return rc;
+            trims.own.push_back(trims.of[d]);
+        }
+    }
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
@@ -285,12 +321,13 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     for (uint64_t c = 0; c < n_chunks; c++) {
         chunks[c].q0 = c * chunk_size;
         chunks[c].nq = chunks[c].nu = std::min<uint64_t>(chunk_size, n_queries - chunks[c].q0);
-        chunks[c].dev_bases = bases;
-        chunks[c].dev_off = base_off + chunks[c].q0;
+        chunks[c].dev_bases = chunks[c].src_bases = bases;
+        chunks[c].dev_off = chunks[c].src_off = base_off + chunks[c].q0;
     }
     // busy seconds of the stages (rtx_raxtax_last_timing: which stage bounds an end-to-end run)
-    double busy_lookup = 0, busy_send = 0, busy_derep = 0;
+    double busy_lookup = 0, busy_send = 0, busy_derep = 0, busy_trim = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;
+    uint64_t trim_queries = 0, trim_with5 = 0, trim_with3 = 0, trim_emptied = 0;
     std::vector<double> busy_device(n_dev, 0.0), busy_format(n_dev, 0.0);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     std::mutex mu;
@@ -317,18 +354,54 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     const uint64_t ahead = 2ull * n_dev;  // chunks a stage may run ahead of the next one
     std::mutex pool_mu;
     std::vector<Chunk::Arena> arena_pool;  // message arenas between the sender (done with a chunk) and the format threads (next chunk)
-    std::vector<ByteBuf> bases_pool;       // ... and the arrays of distinct reads between the sender and the lookup thread (RTX_OPT_DEREP)
+    std::vector<ByteBuf> bases_pool;       // ... and the arrays of distinct reads (RTX_OPT_DEREP) and of trimmed reads (primers) between the sender and the lookup thread
 
     std::thread lookup([&] {
         for (uint64_t c = 0; c < n_chunks; c++) {
             Chunk &ch = chunks[c];
-            if (!derep && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
+            if (!derep && !trim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
             if (c >= ahead && !wait_stage(c - ahead, 2)) return;
+            if (trim) {  // the primers of the chunk's reads, on the device (a stream of its own beside the handle's); then the kept ranges
+                const double t_t0 = now();
+                ch.lo.resize(ch.nq);
+                ch.hi.resize(ch.nq);
+                ch.hit.resize(ch.nq);
+                int rc = rtx_trim_run(trims.of[c % n_dev], ch.nq, bases, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.hit.data());
+                bool any = false;
+                if (!rc)
+                    for (uint64_t i = 0; i < ch.nq; i++) {
+                        const uint64_t len = base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
+                        const bool f5 = (ch.hit[i] & 0xFFu) != RTX_TRIM_NO_PATTERN, f3 = ((ch.hit[i] >> 16) & 0xFFu) != RTX_TRIM_NO_PATTERN;
+                        trim_with5 += f5;
+                        trim_with3 += f3;
+                        trim_emptied += len != 0 && ch.hi[i] == ch.lo[i];
+                        any = any || ch.lo[i] != 0u || ch.hi[i] != len;
+                    }
+                if (!rc && any) {  // (a chunk in which nothing was found goes on as it came, without a copy)
+                    uint64_t kept = 0;
+                    for (uint64_t i = 0; i < ch.nq; i++) kept += ch.hi[i] - ch.lo[i];
+                    {
+                        std::lock_guard<std::mutex> g(pool_mu);
+                        if (!bases_pool.empty()) { ch.t_bases = std::move(bases_pool.back()); bases_pool.pop_back(); }
+                    }
+                    if (!ch.t_bases.reserve(kept + 1)) { fail(RTX_ERR_OOM, "no memory for the trimmed reads of a chunk"); return; }
+                    ch.t_off.resize(ch.nq + 1);
+                    rc = rtx_trim_apply(ch.nq, bases, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.t_bases.p, ch.t_off.data());
+                    if (!rc) {
+                        ch.dev_bases = ch.src_bases = ch.t_bases.p;
+                        ch.dev_off = ch.src_off = ch.t_off.data();
+                    }
+                }
+                if (rc) { fail(rc, rtx_last_error()); return; }
+                trim_queries += ch.nq;
+                busy_trim += now() - t_t0;
+                if (!derep && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
+            }
             if (derep) {  // the copies of the chunk, on the device (a stream of its own beside the handle's); then the map's host side
                 const double t_r0 = now();
                 std::vector<uint32_t> rep(ch.nq);
                 uint64_t nu = 0;
-                int rc = rtx_derep_run(dereps.of[c % n_dev], ch.nq, bases, base_off + ch.q0, rep.data(), &nu);
+                int rc = rtx_derep_run(dereps.of[c % n_dev], ch.nq, ch.src_bases, ch.src_off, rep.data(), &nu);
                 if (!rc && nu < ch.nq) {  // (a chunk without copies goes on as it came)
                     std::vector<uint32_t> uniq(ch.nq);
                     ch.slot.resize(ch.nq);
@@ -337,7 +410,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     if (!rc) {
                         ch.size.resize(nu);
                         ch.u_off.assign(nu + 1, 0);
-                        for (uint64_t u = 0; u < nu; u++) ch.u_off[u + 1] = ch.u_off[u] + (base_off[ch.q0 + uniq[u] + 1] - base_off[ch.q0 + uniq[u]]);
+                        for (uint64_t u = 0; u < nu; u++) ch.u_off[u + 1] = ch.u_off[u] + (ch.src_off[uniq[u] + 1] - ch.src_off[uniq[u]]);
                         {
                             std::lock_guard<std::mutex> g(pool_mu);
                             if (!bases_pool.empty()) { ch.u_bases = std::move(bases_pool.back()); bases_pool.pop_back(); }
@@ -348,7 +421,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                             for (uint64_t u = a; u < b;) {
                                 uint64_t v = u + 1;
                                 while (v < b && uniq[v] == uniq[v - 1] + 1u) v++;
-                                if (ch.u_off[v] > ch.u_off[u]) memcpy(ch.u_bases.p + ch.u_off[u], bases + base_off[ch.q0 + uniq[u]], ch.u_off[v] - ch.u_off[u]);
+                                if (ch.u_off[v] > ch.u_off[u]) memcpy(ch.u_bases.p + ch.u_off[u], ch.src_bases + ch.src_off[uniq[u]], ch.u_off[v] - ch.u_off[u]);
                                 u = v;
                             }
                         });
@@ -587,14 +660,14 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                             if (parent(ids[j]) != parent(ids[0])) { ch.differ[i] = 1; break; }
                     }
                     if (dev_text[d] || ch.res.status[s] != RTX_Q_OK) continue;  // (device text: the lines are formatted already)
-                    const uint64_t len = base_off[q + 1] - base_off[q];
+                    const uint64_t len = ch.src_off[i + 1] - ch.src_off[i];  // (the read as it was classified: trimmed, with primers set)
                     const uint64_t rows = ch.res.row_count[s];
                     const size_t need = (rows + 1) * (strlen(labels[q]) + 4096 + 8 * RTX_MAX_DEPTH) + len + 64;
                     char *ob = oa.room(need);
                     char *tb = ta ? ta->room(need + rows * len) : nullptr;
                     if (!ob || (ta && !tb)) { rc_fmt = RTX_ERR_OOM; return; }
                     int64_t tsv_len = 0;
-                    const uint8_t *seq = bases + base_off[q];
+                    const uint8_t *seq = ch.src_bases + ch.src_off[i];
                     if (tb && both && ch.strand[i]) {
                         rc_seq.resize(len + 1);
                         (void)rtx_revcomp(seq, len, rc_seq.data());
@@ -634,6 +707,11 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 fprintf(stderr, "[WARN ] Exact matches for %s differ above the leafs of the lineage tree!\n", labels[q]);
                 warnings = true;
             }
+            if (trim_cb) {  // every query, also one without a message (an emptied read)
+                const uint32_t raw = (uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull);
+                const bool on = !ch.lo.empty();
+                if (!trim_cb(labels[q], raw, on ? ch.lo[i] : 0u, on ? ch.hi[i] : raw, on ? ch.hit[i] : (RTX_TRIM_NO_PATTERN | RTX_TRIM_NO_PATTERN << 16))) { closed = true; break; }
+            }
             if (ch.status[i] != RTX_Q_OK) {
                 // the reference aborts here (prob.rs:21/162); report and skip the query instead
                 if (ch.status[i] == RTX_Q_ALL_KMERS) fprintf(stderr, "[ERROR] query %s holds every 8-mer (t = 65536): the reference asserts t < 65536 (raxtax.rs:56)\n", labels[q]);
@@ -642,7 +720,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             }
             bool ok;
             if (info && !info(labels[q], ch.strand[i], ch.peak[i], ch.t[i], near ? ch.nearest[i] : RTX_NO_REF, near ? ch.ties[i] : 0u,
-                              ident ? ch.dist[i] : RTX_NO_DIST, (uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull))) { closed = true; break; }
+                              ident ? ch.dist[i] : RTX_NO_DIST, (uint32_t)std::min<uint64_t>(ch.src_off[i + 1] - ch.src_off[i], 0xFFFFFFFFull))) { closed = true; break; }
             if (dev_text[c % n_dev]) {
                 ok = sender(labels[q], ch.text.out + ch.text.out_off[i], tsv ? ch.text.tsv + ch.text.tsv_off[i] : nullptr);
             } else {
@@ -664,9 +742,14 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint32_t>().swap(ch.slot);
         std::vector<uint32_t>().swap(ch.size);
         std::vector<uint64_t>().swap(ch.u_off);
+        std::vector<uint32_t>().swap(ch.lo);
+        std::vector<uint32_t>().swap(ch.hi);
+        std::vector<uint32_t>().swap(ch.hit);
+        std::vector<uint64_t>().swap(ch.t_off);
         {
             std::lock_guard<std::mutex> g(pool_mu);
             if (ch.u_bases.p) bases_pool.push_back(std::move(ch.u_bases));
+            if (ch.t_bases.p) bases_pool.push_back(std::move(ch.t_bases));
             for (auto &a : ch.out_arena) arena_pool.push_back(std::move(a));
             for (auto &a : ch.tsv_arena) arena_pool.push_back(std::move(a));
         }
@@ -686,6 +769,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::lock_guard<std::mutex> g(g_timing_mu);
         g_timing = {{any_host_lookup ? busy_lookup : 0.0, bd, bf, busy_send}, n_chunks};
         g_derep = {derep_queries, derep_distinct, busy_derep};
+        g_trim = {trim_queries, trim_with5, trim_with3, trim_emptied, busy_trim};
     }
     if (failed != RTX_OK) { rtx::set_error("%s", failed_msg.c_str()); return failed; }
     if (warnings)  // raxtax.rs:93-95
@@ -767,6 +851,15 @@ extern "C" int rtx_raxtax_multi_ex3(rtx_index *const *indices, uint32_t n_indice
                                     const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                                     int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                                     rtx_query_align_fn align, void *align_ctx) {
+    return rtx_raxtax_multi_ex4(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender,
+                                sender_ctx, tsv, align, align_ctx, nullptr, nullptr);
+}
+
+// ... and the primer trimming of every query (rtx_index_set_primers)
+extern "C" int rtx_raxtax_multi_ex4(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx) {
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
@@ -774,8 +867,10 @@ extern "C" int rtx_raxtax_multi_ex3(rtx_index *const *indices, uint32_t n_indice
         fi = [&](const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t dist, uint32_t qlen) {
             return align(align_ctx, label, strand, peak, t, nearest, ties, dist, qlen) == 0;
         };
+    RawTrim ft;
+    if (trim) ft = [&](const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit) { return trim(trim_ctx, label, raw_len, lo, hi, hit) == 0; };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
-               tsv != 0, fi);
+               tsv != 0, fi, ft);
 }
 
 extern "C" int rtx_raxtax_last_timing(double busy[4], uint64_t *n_chunks) {
@@ -791,6 +886,16 @@ extern "C" int rtx_raxtax_last_derep(uint64_t *queries, uint64_t *distinct, doub
     if (queries) *queries = g_derep.queries;
     if (distinct) *distinct = g_derep.distinct;
     if (busy_seconds) *busy_seconds = g_derep.busy;
+    return RTX_OK;
+}
+
+extern "C" int rtx_raxtax_last_trim(uint64_t *queries, uint64_t *with5, uint64_t *with3, uint64_t *emptied, double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_trim.queries;
+    if (with5) *with5 = g_trim.with5;
+    if (with3) *with3 = g_trim.with3;
+    if (emptied) *emptied = g_trim.emptied;
+    if (busy_seconds) *busy_seconds = g_trim.busy;
     return RTX_OK;
 }
 

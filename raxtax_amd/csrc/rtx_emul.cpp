@@ -681,6 +681,32 @@ uint32_t emul_identity(const uint8_t *q, uint64_t q_first, uint32_t qlen, int pa
 }
 uint32_t emul_identity_hundredths(uint32_t dist, uint32_t qlen) { return identity_hundredths(dist, qlen); }
 
+// Primer trimming as trim_kernel (rtx_trim.hip) runs it, with the functions the kernel calls: the read's ends staged into rows
+// (trim_stage_row), the patterns as planes (trim_pattern_init), one read against them (trim_read -> trim_search).  codes / code_off: the
+// patterns as given, [n_pat] each of end[] (0: 5', 1: 3'), max_errors[] and window[] (0: the default); x: one read of len bytes.
+void emul_trim_read(uint32_t n_pat, const uint8_t *codes, const uint32_t *code_off, const uint32_t *end, const uint32_t *max_errors,
+                    const uint32_t *window, const uint8_t *x, uint32_t len, uint32_t *lo, uint32_t *hi, uint32_t *hit) {
+    std::vector<TrimPattern> pat;
+    uint32_t n5 = 0, n3 = 0, w5 = 0, w3 = 0;
+    for (uint32_t e = 0; e < 2; e++)
+        for (uint32_t i = 0; i < n_pat; i++) {
+            if (end[i] != e) continue;
+            TrimPattern p;
+            trim_pattern_init(p, codes + code_off[i], code_off[i + 1] - code_off[i], max_errors[i], window[i], e == 1u, i);
+            pat.push_back(p);
+            (e ? n3 : n5)++;
+            uint32_t &w = e ? w3 : w5;
+            w = std::max(w, p.w);
+        }
+    std::vector<uint8_t> row5(trim_row_stride(w5) + 16), row3(trim_row_stride(w3) + 16);
+    if (n5) trim_stage_row(x, len, w5, false, row5.data());
+    if (n3) trim_stage_row(x, len, w3, true, row3.data());
+    auto loader = [](const std::vector<uint8_t> &row) {
+        return [&row](uint32_t c) { TrimWords t; memcpy(t.w, row.data() + 16u * c, 16); return t; };
+    };
+    trim_read(pat.data(), n5, n3, loader(row5), loader(row3), len, *lo, *hi, *hit);
+}
+
 // byte, high-bit word and shift of local reference rl in the packed counts of its tile (packed_count_pos)
 void emul_packed_count_pos(uint32_t rl, uint32_t *byte, uint32_t *hi_word, uint32_t *hi_shift) { packed_count_pos(rl, *byte, *hi_word, *hi_shift); }
 

@@ -35,6 +35,14 @@ bool index_nearest(const rtx_index *index);  // RTX_OPT_NEAREST
 bool index_identity(const rtx_index *index);  // RTX_OPT_IDENTITY
 bool index_profile(const rtx_index *index, uint32_t *cutoff_hundredths, uint32_t *flags);  // a taxon profile is open (rtx_index_profile_begin), with what
 bool index_derep(const rtx_index *index);  // RTX_OPT_DEREP
+// primer trimming (host_trim.cpp / rtx_trim.hip): a pattern with its codes owned; the list a handle holds (rtx_index_set_primers; empty: off)
+struct TrimPrimer {
+    std::vector<uint8_t> codes;
+    uint32_t end = 0, max_errors = 0, window = 0;
+    bool operator==(const TrimPrimer &o) const { return codes == o.codes && end == o.end && max_errors == o.max_errors && window == o.window; }
+};
+int trim_check_patterns(const char *who, const rtx_trim_pattern *pats, uint32_t n);  // RTX_OK, or RTX_ERR_INVALID with the pattern named
+const std::vector<TrimPrimer> &index_primers(const rtx_index *index);
 bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value
 bool hw_queues_for_run_ahead();  // (host_threads.cpp) GPU_MAX_HW_QUEUES reads six or more: transfers do not share a hardware queue with kernels
 

@@ -155,6 +155,101 @@ RTX_HD uint32_t identity_hundredths(uint32_t dist, uint32_t qlen) {
 }
 
 // ---------------------------------------------------------------------------
+// Primer trimming (trim_kernel, rtx_trim.hip; rtx_primer_search on the host; emul_trim_* on x86): Sellers' search of a pattern of at most
+// 64 codes in the first w bases of a text, by the block step above with the roles swapped -- the PATTERN is the block, the read the text.
+// E[j] = the least distance of the whole pattern to a substring that ends at j (the text in front is free: horizontal delta 0 into row 0,
+// E[0] = m); the answer is the least E and the LARGEST j that has it, found when it is at most k.
+// The text arrives as the stage packs it (trim_stage_row): two bases per byte, base j in nibble j, a byte above 15 as 0 (both match nothing),
+// a 3' window reversed, in chunks of 32 bases = 16 bytes (TrimWords: one load of the lane's own row).
+// ---------------------------------------------------------------------------
+struct TrimPattern {     // one pattern as the kernel argument carries it (uniform over a wave: scalar registers)
+    uint64_t plane[4];   // bit j of plane x: code j of the pattern AS IT IS SEARCHED (a 3' pattern reversed) has bit x
+    uint32_t m, k, w;    // codes, errors allowed (k < m), window (resolved by trim_window: 1 .. 256)
+    uint32_t index;      // its place in the caller's list (what the hit word names)
+};
+struct TrimWords { uint32_t w[4]; };
+constexpr uint32_t kTrimNone = 0xFFu;          // the hit word's pattern where nothing was found
+constexpr uint32_t kTrimNoDist = 0xFFFFFFFFu;  // (RTX_NO_DIST)
+RTX_HD uint32_t trim_window(uint32_t m, uint32_t k, uint32_t window) {
+    if (window) return window;
+    const uint32_t d = m + k + 32u;
+    return d < 256u ? d : 256u;
+}
+RTX_HD uint32_t trim_row_stride(uint32_t w) { return (w + 31u) / 32u * 16u; }  // bytes of a row that holds w bases: whole 16-byte loads
+// codes: the pattern as given (m of them, every one 1 .. 15); reversed: a 3' pattern (it is searched in the reversed read)
+RTX_HD void trim_pattern_init(TrimPattern &p, const uint8_t *codes, uint32_t m, uint32_t k, uint32_t window, bool reversed, uint32_t index) {
+    p.plane[0] = p.plane[1] = p.plane[2] = p.plane[3] = 0ull;
+    for (uint32_t j = 0; j < m; j++) {
+        const uint64_t c = identity_code(codes[reversed ? m - 1u - j : j]);
+        p.plane[0] |= (c & 1u) << j;
+        p.plane[1] |= ((c >> 1) & 1u) << j;
+        p.plane[2] |= ((c >> 2) & 1u) << j;
+        p.plane[3] |= ((c >> 3) & 1u) << j;
+    }
+    p.m = m;
+    p.k = k;
+    p.w = trim_window(m, k, window);
+    p.index = index;
+}
+// the first min(len, w) bases of x (reversed: the last ones, last base first) into a row of trim_row_stride(w) bytes; what lies behind them is zero
+RTX_HD void trim_stage_row(const uint8_t *x, uint64_t len, uint32_t w, bool reversed, uint8_t *row) {
+    const uint32_t n = len < w ? (uint32_t)len : w, stride = trim_row_stride(w);
+    for (uint32_t b = 0; b < stride; b++) {
+        const uint32_t j0 = 2u * b, j1 = j0 + 1u;
+        const uint32_t c0 = j0 < n ? identity_code(x[reversed ? len - 1u - j0 : j0]) : 0u;
+        const uint32_t c1 = j1 < n ? identity_code(x[reversed ? len - 1u - j1 : j1]) : 0u;
+        row[b] = (uint8_t)(c0 | (c1 << 4));
+    }
+}
+// load(c): bases 32 c .. 32 c + 31 of the text; len: the bases the read has (the text is its first min(len, p.w)).  The chunk loop is
+// uniform over a wave (p.w is), a lane whose text has ended sits the steps out.  cut = 0 and err = kTrimNoDist when not found.
+template <class L>
+RTX_HD void trim_search(const TrimPattern &p, const L &load, uint32_t len, uint32_t &cut, uint32_t &err) {
+    IdentityBlock b;
+    b.pv = ~0ull;
+    b.mv = 0ull;
+    b.plane[0] = p.plane[0]; b.plane[1] = p.plane[1]; b.plane[2] = p.plane[2]; b.plane[3] = p.plane[3];
+    const uint64_t out_mask = 1ull << (p.m - 1u);
+    const uint32_t n = len < p.w ? len : p.w;
+    uint32_t score = p.m, best = p.m, best_j = 0u;
+    for (uint32_t c = 0; c * 32u < p.w; c++) {
+        const TrimWords t = load(c);
+#pragma unroll
+        for (uint32_t i = 0; i < 32u; i++) {
+            const uint32_t j = c * 32u + i;
+            if (j < n) {
+                score += (uint32_t)identity_step(b, (t.w[i >> 3] >> ((i & 7u) * 4u)) & 15u, 0, out_mask);
+                if (score <= best) { best = score; best_j = j + 1u; }  // (<=: the latest j of the least E)
+            }
+        }
+    }
+    const bool found = best <= p.k;
+    cut = found ? best_j : 0u;
+    err = found ? best : kTrimNoDist;
+}
+// One read against the patterns of both ends (pat[0 .. n5): 5', pat[n5 .. n5 + n3): 3', each end in the order of the caller's list): the
+// least errors win, then the lowest index; the ends are searched independently on the untrimmed read.  load5 / load3: the read's rows.
+template <class L5, class L3>
+RTX_HD void trim_read(const TrimPattern *pat, uint32_t n5, uint32_t n3, const L5 &load5, const L3 &load3, uint32_t len, uint32_t &lo,
+                      uint32_t &hi, uint32_t &hit) {
+    uint32_t cut5 = 0u, err5 = kTrimNoDist, pat5 = kTrimNone, cut3 = 0u, err3 = kTrimNoDist, pat3 = kTrimNone;
+    for (uint32_t i = 0; i < n5; i++) {
+        uint32_t c, e;
+        trim_search(pat[i], load5, len, c, e);
+        if (e < err5) { err5 = e; cut5 = c; pat5 = pat[i].index; }
+    }
+    for (uint32_t i = n5; i < n5 + n3; i++) {
+        uint32_t c, e;
+        trim_search(pat[i], load3, len, c, e);
+        if (e < err3) { err3 = e; cut3 = c; pat3 = pat[i].index; }
+    }
+    lo = cut5;
+    hi = len - cut3;
+    if (hi < lo) hi = lo;  // the cuts overlap: the read is left empty
+    hit = pat5 | ((pat5 == kTrimNone ? 0u : err5) << 8) | (pat3 << 16) | ((pat3 == kTrimNone ? 0u : err3) << 24);
+}
+
+// ---------------------------------------------------------------------------
 // Hash of an encoded sequence for the exact-match lookup (Tree.sequences.get, raxtax.rs:42) on the device.  The bytes are taken
 // as 8-byte little-endian words (the last one zero-padded); every word is mixed with its position and the mixes are ADDED, so
 // that the lanes of a wave can hash their words independently and meet in one sum.  Equal sequences hash equal; a collision only
