@@ -44,7 +44,9 @@ extern "C" {
                                 rtx_batch_prefetch_weights and rtx_raxtax_last_derep: exports and an option that is off by default; and with
                                 RTX_OPT_IDENTITY (28), RTX_NO_DIST, rtx_batch_identity, rtx_semiglobal_distance and rtx_raxtax_multi_ex3: the same;
                                 and with primer trimming, rtx_trim_* / rtx_primer_search / rtx_index_set_primers / rtx_raxtax_last_trim /
-                                rtx_raxtax_multi_ex4: exports and a setting that is off by default) */
+                                rtx_raxtax_multi_ex4: exports and a setting that is off by default; and with FASTQ and the quality filter,
+                                rtx_queries_parse_fastq* / rtx_fastq_block_end / rtx_queries_quals / rtx_qual_* / rtx_index_set_quality /
+                                rtx_raxtax_last_qual / rtx_raxtax_multi_ex5: the same) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -163,6 +165,24 @@ uint64_t rtx_queries_len(const rtx_queries *q);
 const char *rtx_queries_label(const rtx_queries *q, uint64_t i);
 /* all sequences concatenated + n+1 offsets (the layout rtx_classify_batch takes) */
 int rtx_queries_data(const rtx_queries *q, const uint8_t **bases, const uint64_t **base_off);
+/* FASTQ (what a sequencer emits) in the four-line record form only: `@header`, the sequence, `+` followed by anything, the quality string of
+ * the sequence's length; `\r\n` line ends are tolerated, the last record may lack its final newline, blank lines may only follow the last
+ * record.  The label is derived from the header line and the bases are encoded as rtx_queries_parse_fasta does it (lower case and IUPAC
+ * included), `skip` labels are dropped likewise; a record without bases is kept (the empty read).  ascii_base (33 or 64) is only checked
+ * against: every quality byte must lie in 33 .. 126.  RTX_ERR_PARSE, with the number of the record (from 1, within the text given) in
+ * rtx_last_error: a first line that does not start with '@', a third line that does not start with '+', a quality string of another length
+ * than the sequence, a quality byte outside 33 .. 126, a character that is no base, and a record that is cut short.
+ * A quality line may itself start with '@', so a block of a file that is read piecewise cannot be cut at "\n@": rtx_fastq_block_end returns
+ * the offset behind the last complete group of four lines counted from the start of the text (0 if there is none) -- every block starts at
+ * a record; parse text[0, end) and carry text[end, len) over, flags as for FASTA (a record cut short is an error in every block).  The
+ * records of all blocks together are exactly those of the whole-file parse.
+ * rtx_queries_quals: the quality bytes as they stand in the file (ASCII, the base not taken off), concatenated and indexed by the base_off
+ * of rtx_queries_data; NULL for the handle of a FASTA parse. */
+int rtx_queries_parse_fastq(const char *text, uint64_t len, const char *const *skip, uint64_t n_skip, uint32_t ascii_base, rtx_queries **out);
+uint64_t rtx_fastq_block_end(const char *text, uint64_t len);
+int rtx_queries_parse_fastq_block(const char *text, uint64_t len, const char *const *skip, uint64_t n_skip, uint32_t ascii_base, uint32_t flags,
+                                  rtx_queries **out);
+int rtx_queries_quals(const rtx_queries *q, const uint8_t **quals);
 
 /* ------------------------------------------------------------------------- */
 /* Device index (replaces the read-only `&Tree` argument of raxtax())        */
@@ -592,6 +612,77 @@ int rtx_index_set_primers(rtx_index *index, const rtx_trim_pattern *pats, uint32
 int rtx_index_primers(const rtx_index *index, uint32_t *n);
 int rtx_raxtax_last_trim(uint64_t *queries, uint64_t *with5, uint64_t *with3, uint64_t *emptied, double *busy_seconds);
 
+/* ---- quality filter (rtx_qual.hip; rtx_index_set_quality is the host mirror's use of it) -----------------------------------------------------
+ * The step that starts an amplicon pipeline (`vsearch --fastq_filter`, DADA2 `filterAndTrim`) on the device: where a read is cut and whether
+ * it is discarded, from its FASTQ quality string.  Exact integers; the host function, the x86 emulator and the device agree bit for bit.
+ *   table        e[Q] = llround(10^(-Q/10) * 2^40), Q = 0 .. 93 (e[0] = 2^40, e[93] = 551): computed once on the host, the kernel receives
+ *                that array; rtx_qual_error_table hands it out.  A threshold given as a double x is floor(x * 2^40), at most 2^63: that
+ *                integer is compared.  A read has at most RTX_QUAL_MAX_READ bases, so no sum exceeds 2^60.
+ *   parameters   ascii_base 33 or 64; every other field has a value that switches it off, and a struct that is entirely off is no filter:
+ *                  trunc_len    0   a range shorter than this is discarded (and left as long as it is); otherwise it is cut to this length
+ *                  trunc_qual  <0   cut in front of the first base with Q <= this (at most 93)
+ *                  trunc_ee    <0   cut in front of the first base at which the sum of e from the start of the range, that base included,
+ *                                   is above this
+ *                  min_len      0   discard if fewer bases are kept
+ *                  max_len      0   discard if more bases are kept
+ *                  max_ns      <0   discard if the kept bases hold more bases that are none of A, C, G, T (codes 1, 2, 4, 8) than this
+ *                  max_ee      <0   discard if the expected errors of the kept bases -- the sum of their e -- are above this
+ *                  max_ee_rate <0   discard if they are above this times the number of kept bases
+ *                RTX_ERR_INVALID: a NaN, an ascii_base other than 33 or 64, a trunc_qual above 93.
+ *   per read     the input range [lo, hi_in) -- the whole read, or what the primer trimming kept; Q_i = qual_i - ascii_base.
+ *                1. a byte of the range with Q_i outside 0 .. 93: the verdict is RTX_QC_BAD_QUALITY alone, hi = lo, ee = 0.
+ *                2. trunc_len; 3. trunc_qual and trunc_ee, each within what trunc_len left: the shorter result wins.  hi: the end of what
+ *                is kept; ee: the sum of e over [lo, hi); 4. the verdict is the OR of EVERY reason that applies (RTX_QC_*), 0: the read
+ *                passes.  hi and ee are given for a discarded read as well.  Never depends on the rest of the batch.
+ *   rtx_qual_create   an object of its own on GPU `device` like rtx_trim: one stream, its own buffers (they only grow), no rtx_index.
+ *                Checked in this order: null arguments, the parameters (RTX_ERR_INVALID), the device (RTX_ERR_NO_DEVICE without a gfx950).
+ *   rtx_qual_run      hi / ee / verdict of n reads, [n] each; bases / base_off as rtx_batch_prefetch takes them, quals indexed like bases
+ *                (raw bytes: rtx_queries_quals); lo_in / hi_in [n] or both NULL (whole reads).  One byte per base of the ranges travels to
+ *                the device -- the quality byte, bit 7 set where the base is no A/C/G/T -- and an offset and a length per read.  n == 0:
+ *                RTX_OK; RTX_ERR_INVALID: a base_off that is not monotone, a range outside its read, a read of more than RTX_QUAL_MAX_READ
+ *                bases, a quality byte of 128 or more in a range.  Synchronous; calls on one object are serialised by the caller.
+ *   rtx_qual_stage_times  seconds of the last rtx_qual_run: the host's staging pass, the copies and the wait around the kernel, all of it.
+ *   rtx_qual_read     the same for ONE read on the host (no device), with the functions the kernel calls.
+ *   rtx_index_set_quality  the filter rtx_raxtax* run every read through (NULL or a struct that is entirely off, the default: off -- no
+ *                new code runs, nothing is allocated, every output is what it is without).  Like the primers honoured by the mirror alone,
+ *                shapes no workspace; the handles of one call must hold the same setting and the call must bring quals
+ *                (rtx_raxtax_multi_ex5): RTX_ERR_INVALID otherwise.  Primers are trimmed first, on the raw read; the filter runs on the
+ *                range they kept; dereplication comes last.  A discarded read is classified as the empty read: no message, no `align`
+ *                callback, not counted by an open profile.  rtx_index_quality: the setting and whether it is on.
+ *   rtx_raxtax_last_qual  the last rtx_raxtax* call of the process: its queries, those that passed, those that passed and were cut short
+ *                by the filter, how often each reason applied (reasons[b]: bit b of the verdict) and the busy seconds of the stage;
+ *                all 0 with the filter off. */
+#define RTX_QUAL_MAX_READ (1u << 20)
+#define RTX_QUAL_TABLE 94
+#define RTX_QC_BAD_QUALITY 1u
+#define RTX_QC_SHORT_FOR_TRUNC_LEN 2u
+#define RTX_QC_TOO_SHORT 4u
+#define RTX_QC_TOO_LONG 8u
+#define RTX_QC_TOO_MANY_N 16u
+#define RTX_QC_MAX_EE 32u
+#define RTX_QC_MAX_EE_RATE 64u
+typedef struct {
+    uint32_t ascii_base, trunc_len;
+    int32_t trunc_qual;
+    double trunc_ee;
+    uint32_t min_len, max_len;
+    int32_t max_ns;
+    double max_ee, max_ee_rate;
+} rtx_qual_params;
+typedef struct rtx_qual rtx_qual;
+int rtx_qual_error_table(uint64_t out[RTX_QUAL_TABLE]);
+int rtx_qual_create(int device, const rtx_qual_params *params, rtx_qual **out);
+int rtx_qual_run(rtx_qual *q, uint64_t n, const uint8_t *bases, const uint8_t *quals, const uint64_t *base_off, const uint32_t *lo_in /*[n] or NULL*/,
+                 const uint32_t *hi_in /*[n] or NULL*/, uint32_t *hi_out /*[n]*/, uint64_t *ee_out /*[n]*/, uint32_t *verdict_out /*[n]*/);
+void rtx_qual_destroy(rtx_qual *q);
+int rtx_qual_kernel_time(const rtx_qual *q, float *ms); /* milliseconds of the kernel of the last rtx_qual_run, from HIP events around it */
+int rtx_qual_stage_times(const rtx_qual *q, double seconds[3]);
+int rtx_qual_read(const rtx_qual_params *params, const uint8_t *bases, const uint8_t *quals, uint64_t len, uint32_t lo, uint32_t hi_in,
+                  uint32_t *hi_out, uint64_t *ee_out, uint32_t *verdict_out);
+int rtx_index_set_quality(rtx_index *index, const rtx_qual_params *params);
+int rtx_index_quality(const rtx_index *index, rtx_qual_params *params, int *on);
+int rtx_raxtax_last_qual(uint64_t *queries, uint64_t *passed, uint64_t *truncated, uint64_t reasons[7], double *busy_seconds);
+
 /* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
  * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte
  * for byte what rtx_format_query prints for the view, the label, the bases and the exact matches of the query (the override of
@@ -830,6 +921,17 @@ int rtx_raxtax_multi_ex4(rtx_index *const *indices, uint32_t n_indices, const rt
                          const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                          int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                          rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx);
+/* rtx_raxtax_multi_ex4 with the quality strings of the reads (quals, indexed by base_off: rtx_queries_quals) and a callback for the quality
+ * filter (rtx_index_set_quality): called for EVERY query of the caller, in input order, directly after its `trim` callback: the read's
+ * length as given, the kept range [lo, hi) -- of the raw read, the primers off -- the expected errors of the kept bases times 2^40 and the
+ * verdict (0: passed; a discarded read is classified as the empty read).  With no filter set: the range the primers left, 0 and 0, and
+ * quals is ignored; a filter without quals is RTX_ERR_INVALID.  Per query of the caller also under RTX_OPT_DEREP.  Any callback may be NULL. */
+typedef int (*rtx_query_qual_fn)(void *ctx, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict);
+int rtx_raxtax_multi_ex5(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                         rtx_query_qual_fn qual, void *qual_ctx);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

@@ -28,6 +28,9 @@ STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_wa
 RTX_TRIM_5P, RTX_TRIM_3P = 0, 1      # rtx_trim_pattern.end
 RTX_TRIM_MAX_PATTERNS, RTX_TRIM_MAX_PATTERN, RTX_TRIM_MAX_WINDOW, RTX_TRIM_NO_PATTERN = 8, 64, 256, 0xFF
 
+RTX_QUAL_MAX_READ, RTX_QUAL_TABLE = 1 << 20, 94
+RTX_QC_NAMES = ("bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate")   # bit b of a verdict: RTX_QC_*
+
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
 u32p = C.POINTER(C.c_uint32)
@@ -59,6 +62,11 @@ class ProfileView(C.Structure):
 
 class TrimPattern(C.Structure):
     _fields_ = [("codes", u8p), ("len", C.c_uint32), ("end", C.c_uint32), ("max_errors", C.c_uint32), ("window", C.c_uint32)]
+
+
+class QualParams(C.Structure):   # rtx_qual_params
+    _fields_ = [("ascii_base", C.c_uint32), ("trunc_len", C.c_uint32), ("trunc_qual", C.c_int32), ("trunc_ee", C.c_double), ("min_len", C.c_uint32),
+                ("max_len", C.c_uint32), ("max_ns", C.c_int32), ("max_ee", C.c_double), ("max_ee_rate", C.c_double)]
 
 
 class RtxError(RuntimeError):
@@ -195,6 +203,21 @@ _SIGNATURES = {
     "rtx_index_primers": (C.c_int, [C.c_void_p, u32p]),
     "rtx_raxtax_last_trim": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_raxtax_multi_ex4": (C.c_int, None),
+    "rtx_queries_parse_fastq": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rtx_fastq_block_end": (C.c_uint64, [C.c_char_p, C.c_uint64]),
+    "rtx_queries_parse_fastq_block": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rtx_queries_quals": (C.c_int, [C.c_void_p, C.POINTER(u8p)]),
+    "rtx_qual_error_table": (C.c_int, [u64p]),
+    "rtx_qual_create": (C.c_int, [C.c_int, C.POINTER(QualParams), C.POINTER(C.c_void_p)]),
+    "rtx_qual_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u8p, u64p, u32p, u32p, u32p, u64p, u32p]),
+    "rtx_qual_destroy": (None, [C.c_void_p]),
+    "rtx_qual_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_qual_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rtx_qual_read": (C.c_int, [C.POINTER(QualParams), u8p, u8p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u64p, u32p]),
+    "rtx_index_set_quality": (C.c_int, [C.c_void_p, C.POINTER(QualParams)]),
+    "rtx_index_quality": (C.c_int, [C.c_void_p, C.POINTER(QualParams), C.POINTER(C.c_int)]),
+    "rtx_raxtax_last_qual": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
+    "rtx_raxtax_multi_ex5": (C.c_int, None),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

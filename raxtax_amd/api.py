@@ -164,6 +164,35 @@ def parse_query_fasta_str(text: str, queries_to_skip: Sequence[str] = ()) -> Lis
         lib.rtx_queries_destroy(h)
 
 
+def parse_query_fastq_str(text: str, queries_to_skip: Sequence[str] = (), ascii_base: int = 33) -> List[Tuple[str, np.ndarray, np.ndarray]]:
+    """rtx_queries_parse_fastq: (label, bases, quals) of every record of a FASTQ text in the four-line form; the bases encoded as
+    parse_query_fasta_str encodes them, the quality bytes as they stand in the file (ASCII, ascii_base not taken off)."""
+    lib = _lib.load()
+    b = text.encode() if isinstance(text, str) else bytes(text)
+    skip = (C.c_char_p * max(len(queries_to_skip), 1))(*[s.encode() for s in queries_to_skip])
+    h = C.c_void_p()
+    check(lib.rtx_queries_parse_fastq(b, len(b), skip, len(queries_to_skip), int(ascii_base), C.byref(h)))
+    try:
+        return _queries_records(lib, h)
+    finally:
+        lib.rtx_queries_destroy(h)
+
+
+def _queries_records(lib, h):
+    """The records of an rtx_queries handle: (label, bases) pairs, or (label, bases, quals) triples when it holds qualities."""
+    n = lib.rtx_queries_len(h)
+    pb, po, pq = u8p(), u64p(), u8p()
+    check(lib.rtx_queries_data(h, C.byref(pb), C.byref(po)))
+    check(lib.rtx_queries_quals(h, C.byref(pq)))
+    off = np.ctypeslib.as_array(po, shape=(n + 1,)).copy()
+    tot = int(off[-1])
+    bases = np.ctypeslib.as_array(pb, shape=(tot,)).copy() if tot else np.zeros(0, np.uint8)
+    if not pq:
+        return [(lib.rtx_queries_label(h, i).decode(), bases[int(off[i]):int(off[i + 1])].copy()) for i in range(n)]
+    quals = np.ctypeslib.as_array(pq, shape=(tot,)).copy() if tot else np.zeros(0, np.uint8)
+    return [(lib.rtx_queries_label(h, i).decode(), bases[int(off[i]):int(off[i + 1])].copy(), quals[int(off[i]):int(off[i + 1])].copy()) for i in range(n)]
+
+
 @dataclass
 class EvaluationResult:
     """src/lineage.rs:8-14 (lineage given as index into tree.lineages)."""
@@ -284,7 +313,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None):
+                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -347,8 +376,22 @@ class Index:
             check(self._lib.rtx_index_set_option(self._h, _lib.RTX_OPT_DEREP, 1))
         if primers:   # rtx_index_set_primers: raxtax() trims every read with them first (rtx_trim.hip); classify() ignores them
             self.set_primers(primers)
+        if quality is not None:   # rtx_index_set_quality: raxtax() filters every read by its quality string (rtx_qual.hip); classify() ignores it
+            self.set_quality(quality)
         self._view = ResultView()
         self._keep = None
+
+    def set_quality(self, params) -> None:
+        """rtx_index_set_quality: the QualParams raxtax() filters every read with (its queries then come with quality strings); None, or
+        parameters that are entirely off, switch the stage off."""
+        check(self._lib.rtx_index_set_quality(self._h, C.byref(params._c()) if params is not None else None))
+
+    @property
+    def quality(self):
+        """The QualParams the handle holds, or None (rtx_index_quality)."""
+        c, on = _lib.QualParams(), C.c_int()
+        check(self._lib.rtx_index_quality(self._h, C.byref(c), C.byref(on)))
+        return QualParams._of(c) if on.value else None
 
     def set_primers(self, patterns) -> None:
         """rtx_index_set_primers: the patterns (TrimPrimer, or (codes, end, max_errors[, window]) tuples; see primer_patterns) raxtax()
@@ -848,6 +891,129 @@ def raxtax_last_trim() -> Tuple[int, int, int, int, float]:
     return int(a.value), int(b.value), int(c.value), int(d.value), float(s.value)
 
 
+_QUAL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32)
+QUAL_MAX_READ = _lib.RTX_QUAL_MAX_READ
+QC_BAD_QUALITY, QC_SHORT_FOR_TRUNC_LEN, QC_TOO_SHORT, QC_TOO_LONG, QC_TOO_MANY_N, QC_MAX_EE, QC_MAX_EE_RATE = (1 << b for b in range(7))
+
+
+@dataclass
+class QualParams:
+    """The quality filter's parameters (rtx_qual_params); every field but ascii_base (33 or 64) has a value that switches it off.
+    trunc_len: a range shorter than this is discarded, otherwise it is cut to this length; trunc_qual: cut in front of the first base with
+    Q <= this; trunc_ee: ... in front of the first base at which the running sum of error probabilities is above this; min_len / max_len:
+    discard by the kept length; max_ns: ... if the kept bases hold more non-A/C/G/T bases; max_ee: ... if their expected errors are above
+    this; max_ee_rate: ... above this times the kept length.  A threshold x is compared as floor(x * 2^40)."""
+    ascii_base: int = 33
+    trunc_len: int = 0
+    trunc_qual: int = -1
+    trunc_ee: float = -1.0
+    min_len: int = 0
+    max_len: int = 0
+    max_ns: int = -1
+    max_ee: float = -1.0
+    max_ee_rate: float = -1.0
+
+    def _c(self) -> "_lib.QualParams":
+        return _lib.QualParams(int(self.ascii_base), int(self.trunc_len), int(self.trunc_qual), float(self.trunc_ee), int(self.min_len), int(self.max_len),
+                               int(self.max_ns), float(self.max_ee), float(self.max_ee_rate))
+
+    @staticmethod
+    def _of(c) -> "QualParams":
+        return QualParams(c.ascii_base, c.trunc_len, c.trunc_qual, c.trunc_ee, c.min_len, c.max_len, c.max_ns, c.max_ee, c.max_ee_rate)
+
+
+def qual_error_table() -> List[int]:
+    """rtx_qual_error_table: e[Q] = llround(10^(-Q/10) * 2^40) for Q = 0 .. 93, the integers the device sums."""
+    t = np.zeros(_lib.RTX_QUAL_TABLE, np.uint64)
+    check(_lib.load().rtx_qual_error_table(ptr(t, u64p)))
+    return [int(x) for x in t]
+
+
+def qual_verdict_names(v: int) -> List[str]:
+    """The reasons of a verdict (RTX_QC_*), [] for a read that passes."""
+    return [name for b, name in enumerate(_lib.RTX_QC_NAMES) if (int(v) >> b) & 1]
+
+
+def qual_read(params: QualParams, bases: np.ndarray, quals: np.ndarray, lo: int = 0, hi: Optional[int] = None) -> Tuple[int, int, int]:
+    """rtx_qual_read: (hi, ee, verdict) of ONE read on the host, with the functions the device kernel calls; [lo, hi) is the input range
+    (the whole read by default), ee the expected errors of the kept bases times 2^40."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    quals = np.ascontiguousarray(quals, dtype=np.uint8)
+    if len(bases) != len(quals):
+        raise ValueError(f"{len(quals)} quality bytes for {len(bases)} bases")
+    one = np.zeros(1, np.uint8)
+    h, e, v = C.c_uint32(), C.c_uint64(), C.c_uint32()
+    check(_lib.load().rtx_qual_read(C.byref(params._c()), ptr(bases if len(bases) else one, u8p), ptr(quals if len(quals) else one, u8p), len(bases),
+                                    int(lo), len(bases) if hi is None else int(hi), C.byref(h), C.byref(e), C.byref(v)))
+    return int(h.value), int(e.value), int(v.value)
+
+
+class Qual:
+    """The quality-filter stage on one GPU (rtx_qual): an object of its own beside any Index, one stream, buffers that only grow."""
+
+    def __init__(self, device: int, params: QualParams):
+        self._lib = _lib.load()
+        self._h = None
+        h = C.c_void_p()
+        check(self._lib.rtx_qual_create(device, C.byref(params._c()), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_qual_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, bases: np.ndarray, quals: np.ndarray, base_off: np.ndarray, lo=None, hi=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(hi, ee, verdict) per read (rtx_qual_run): the read keeps [lo, hi) -- lo as given, 0 by default -- with ee expected errors
+        times 2^40; verdict 0: it passes (qual_verdict_names)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        quals = np.ascontiguousarray(quals, dtype=np.uint8)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        if len(bases) != len(quals):
+            raise ValueError(f"{len(quals)} quality bytes for {len(bases)} bases")
+        if (lo is None) != (hi is None):
+            raise ValueError("Qual.run: give both lo and hi, or neither")
+        n = len(base_off) - 1
+        one = np.zeros(1, np.uint8)
+        hi_out, verdict = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(2))
+        ee = np.zeros(max(n, 1), dtype=np.uint64)
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, dtype=np.uint32)
+            hi = np.ascontiguousarray(hi, dtype=np.uint32)
+            if len(lo) != n or len(hi) != n:
+                raise ValueError(f"{len(lo)} / {len(hi)} ranges for {n} reads")
+            if n == 0:
+                lo = hi = np.zeros(1, np.uint32)
+        check(self._lib.rtx_qual_run(self._h, n, ptr(bases if len(bases) else one, u8p), ptr(quals if len(quals) else one, u8p), ptr(base_off, u64p),
+                                     ptr(lo, u32p) if lo is not None else None, ptr(hi, u32p) if hi is not None else None, ptr(hi_out, u32p),
+                                     ptr(ee, u64p), ptr(verdict, u32p)))
+        return hi_out[:n], ee[:n], verdict[:n]
+
+    def kernel_ms(self) -> float:
+        """Milliseconds of the kernel of the last run(), from HIP events (rtx_qual_kernel_time)."""
+        ms = C.c_float()
+        check(self._lib.rtx_qual_kernel_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def stage_seconds(self) -> Tuple[float, float, float]:
+        """(host staging, copies and waiting around the kernel, the whole call) of the last run(), in seconds (rtx_qual_stage_times)."""
+        t = (C.c_double * 3)()
+        check(self._lib.rtx_qual_stage_times(self._h, t))
+        return float(t[0]), float(t[1]), float(t[2])
+
+
+def raxtax_last_qual() -> Tuple[int, int, int, List[int], float]:
+    """rtx_raxtax_last_qual: (queries, passed, passed and cut short, how often each reason applied -- in the order of qual_verdict_names --
+    busy seconds of the stage) of the last raxtax() call of this process; all 0 when its handles had no quality filter set."""
+    a, b, c, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    r = (C.c_uint64 * 7)()
+    check(_lib.load().rtx_raxtax_last_qual(C.byref(a), C.byref(b), C.byref(c), r, C.byref(s)))
+    return int(a.value), int(b.value), int(c.value), [int(x) for x in r], float(s.value)
+
+
 def semiglobal_distance(q: np.ndarray, r: np.ndarray) -> int:
     """rtx_semiglobal_distance: the least Levenshtein distance between the encoded sequence q and any substring of r (the empty one
     included) -- what Result.nearest_dist holds for a query and its nearest reference, computed on the host."""
@@ -872,7 +1038,9 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
            info: Optional[Callable[[str, int, int, int], None]] = None,
            hit: Optional[Callable[[str, int, int, int, int, int], None]] = None,
            align: Optional[Callable[[str, int, int, int, int, int, int, int], None]] = None,
-           trim: Optional[Callable[[str, int, int, int, int], None]] = None) -> None:
+           trim: Optional[Callable[[str, int, int, int, int], None]] = None,
+           quals: Optional[Sequence[np.ndarray]] = None,
+           qual: Optional[Callable[[str, int, int, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
@@ -882,7 +1050,11 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     nearest=True, else NO_REF and 0).  `align(label, strand, peak, t, nearest, ties, dist, qlen)` adds the alignment identity
     (rtx_raxtax_multi_ex3; handles built with identity=True, else NO_DIST and the query's length).  Give one of the three.
     `trim(label, raw_len, lo, hi, hit)` is called for every query, in input order, directly before `align` (rtx_raxtax_multi_ex4; handles built
-    with primers=[...]: the read kept [lo, hi) of its raw_len bases, hit as trim_hit() takes it apart); it goes with `align` or alone."""
+    with primers=[...]: the read kept [lo, hi) of its raw_len bases, hit as trim_hit() takes it apart); it goes with `align` or alone.
+    Handles built with quality=QualParams(...) need the quality strings of the reads: queries as (label, bases, quals) triples
+    (parse_query_fastq_str) or `quals`, one array per query.  `qual(label, raw_len, lo, hi, ee, verdict)` is called for every query directly
+    after `trim` (rtx_raxtax_multi_ex5): the range the primers and the filter kept, the expected errors times 2^40 and the verdict (0: passed;
+    qual_verdict_names); it goes with `align`, `trim` or alone."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
@@ -893,8 +1065,18 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     lib.rtx_raxtax_multi_ex4.argtypes = lib.rtx_raxtax_multi_ex3.argtypes + [_TRIM, C.c_void_p]
     if (info is not None) + (hit is not None) + (align is not None) > 1:
         raise ValueError("raxtax: give one of info, hit and align")
-    if trim is not None and (info is not None or hit is not None):
-        raise ValueError("raxtax: trim goes with align or alone")
+    lib.rtx_raxtax_multi_ex5.argtypes = lib.rtx_raxtax_multi_ex4.argtypes + [u8p, _QUAL, C.c_void_p]
+    if (trim is not None or qual is not None) and (info is not None or hit is not None):
+        raise ValueError("raxtax: trim and qual go with align or alone")
+    if quals is None and info is None and hit is None and len(queries) and all(len(q) == 3 for q in queries):
+        quals = [q[2] for q in queries]   # (info and hit go through calls that carry no quality strings: triples are then read as pairs)
+    if quals is not None and (info is not None or hit is not None):
+        raise ValueError("raxtax: quals go with align, trim and qual")
+    flat_q = None
+    if quals is not None:
+        if len(quals) != len(queries) or any(len(a) != len(q[1]) for a, q in zip(quals, queries)):
+            raise ValueError("raxtax: quals needs one array per query, as long as its bases")
+        flat_q = _flatten(list(quals))[0]
     handles = list(tree) if isinstance(tree, (list, tuple)) else [tree]
     labels = (C.c_char_p * max(len(queries), 1))(*[q[0].encode() for q in queries])
     flat, off = _flatten([q[1] for q in queries])
@@ -940,7 +1122,23 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if trim is not None:
+    def cb_qual(_ctx, label, raw_len, lo, hi, ee, verdict):
+        try:
+            qual(label.decode(), int(raw_len), int(lo), int(hi), int(ee), int(verdict))
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if flat_q is not None or qual is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex5(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
+                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None,
+                                      _TRIM(cb_trim) if trim is not None else C.cast(None, _TRIM), None,
+                                      ptr(flat_q, u8p) if flat_q is not None else None,
+                                      _QUAL(cb_qual) if qual is not None else C.cast(None, _QUAL), None)
+    elif trim is not None:
         arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         rc = lib.rtx_raxtax_multi_ex4(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                       int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),

@@ -19,6 +19,12 @@
 //    N bases (default: len + errors + 32).  PREFIX/raxtax.trim: a header, then label, length, start, end, primer5, errors5, primer3, errors3
 //    per query in input order -- the read kept [start, end) of its length bases, the primers by their place in the list above, '-' where
 //    none was found; "N queries, A with a 5' primer, B with a 3' primer, C left empty" goes to the log)
+//   (-i takes FASTQ as well -- the first non-blank byte of the file decides: '@' FASTQ, '>' FASTA; four-line records, --fastq-ascii 33|64 --
+//    and then the quality filter on the device, rtx_index_set_quality / rtx_qual.hip: --trunclen N, --truncq Q, --truncee E, --minlen N,
+//    --maxlen N, --maxns N, --maxee E, --maxee-rate R as `vsearch --fastq_filter` names them.  With a filter option PREFIX/raxtax.qc: a header,
+//    then label, length, start, end, expected errors, verdict per query in input order -- the read kept [start, end) of its length bases with
+//    that many expected errors (six decimals, truncated), verdict `pass` or the reasons it was discarded for joined by '+'; a discarded read has
+//    no result lines; the totals go to the log.  A filter option on FASTA input is refused.)
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
@@ -131,13 +137,14 @@ std::string fingerprint(const std::string &path) {
 // (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
 // (... and --primers with its two settings, as given: trimmed reads are other reads)
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
-                            const std::string &primers = std::string()) {
+                            const std::string &primers = std::string(), const std::string &quality = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
        << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "") << (identity ? ",\n  \"identity\": true" : "");
     if (profile) ss << ",\n  \"profile\": " << profile;
     if (!primers.empty()) ss << ",\n  \"primers\": \"" << primers << "\"";
+    if (!quality.empty()) ss << ",\n  \"quality\": \"" << quality << "\"";  // (... and the quality filter's settings, as given)
     ss << "\n}\n";
     return ss.str();
 }
@@ -176,7 +183,7 @@ uint8_t iupac_code(char ch) {
 }
 
 struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits, trim;
+    std::ofstream out, tsv, ckp, strand, hits, trim, qc;
     bool want_tsv = false, want_strand = false, want_hits = false;
     const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
 };
@@ -203,6 +210,8 @@ int main(int argc, char **argv) {
     bool derep = false;         // --derep: RTX_OPT_DEREP on every handle (each distinct read of a chunk is classified once; the files are the same)
     std::vector<std::pair<std::string, std::string>> primer_pairs;  // --primers FWD:REV (once or twice): rtx_index_set_primers on every handle, PREFIX/raxtax.trim
     uint32_t primer_pct = 10, primer_window = 0;                   // --primer-errors PCT, --primer-window N
+    rtx_qual_params qual{33u, 0u, -1, -1.0, 0u, 0u, -1, -1.0, -1.0};  // --fastq-ascii and the filter options: rtx_index_set_quality on every handle, PREFIX/raxtax.qc
+    std::string qual_spec;                                             // the filter options as given (empty: none) -- part of the checkpoint
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -267,6 +276,32 @@ int main(int argc, char **argv) {
             if (x < 1 || x > RTX_TRIM_MAX_WINDOW) { fprintf(stderr, "raxtax-hip: --primer-window takes 1 .. %d bases\n", RTX_TRIM_MAX_WINDOW); return 64; }
             primer_window = (uint32_t)x;
         }
+        else if (a == "--fastq-ascii") {
+            const std::string v = val();
+            if (v != "33" && v != "64") { fprintf(stderr, "raxtax-hip: --fastq-ascii takes 33 or 64, not '%s'\n", v.c_str()); return 64; }
+            qual.ascii_base = (uint32_t)atoi(v.c_str());
+        }
+        else if (a == "--trunclen" || a == "--minlen" || a == "--maxlen" || a == "--maxns" || a == "--truncq") {
+            char *end = nullptr;
+            const char *v = val();
+            const long x = strtol(v, &end, 10);
+            const long least = a == "--maxns" || a == "--truncq" ? 0 : 1, most = a == "--truncq" ? 93 : (long)RTX_QUAL_MAX_READ;
+            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
+            if (a == "--trunclen") qual.trunc_len = (uint32_t)x;
+            else if (a == "--minlen") qual.min_len = (uint32_t)x;
+            else if (a == "--maxlen") qual.max_len = (uint32_t)x;
+            else if (a == "--maxns") qual.max_ns = (int32_t)x;
+            else qual.trunc_qual = (int32_t)x;
+            qual_spec += (qual_spec.empty() ? "" : ";") + a.substr(2) + "=" + v;
+        }
+        else if (a == "--truncee" || a == "--maxee" || a == "--maxee-rate") {
+            char *end = nullptr;
+            const char *v = val();
+            const double x = strtod(v, &end);
+            if (end == v || *end != 0 || !(x >= 0.0)) { fprintf(stderr, "raxtax-hip: %s takes a number that is not negative, not '%s'\n", a.c_str(), v); return 64; }
+            (a == "--truncee" ? qual.trunc_ee : a == "--maxee" ? qual.max_ee : qual.max_ee_rate) = x;
+            qual_spec += (qual_spec.empty() ? "" : ";") + a.substr(2) + "=" + v;
+        }
         else if (a == "--profile") {
             char *end = nullptr;
             const char *v = val();
@@ -278,8 +313,8 @@ int main(int argc, char **argv) {
         else if (a == "--batch") chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
-            fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.fasta] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]]\n"
+            fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -289,6 +324,23 @@ int main(int argc, char **argv) {
         fprintf(stderr, "raxtax-hip: -d is required, -i unless --only-db; --only-db conflicts with --skip-db\n");
         return 64;
     }
+    // FASTQ or FASTA: the first non-blank byte of the query file.  A filter option needs quality strings: refused here, before the database is read
+    bool fastq = false;
+    if (!qf.empty()) {
+        Input f;
+        if (f.open(qf)) {
+            char c = 0;
+            while (f.read(&c, 1) == 1 && isspace((unsigned char)c)) c = 0;
+            fastq = c == '@';
+            f.close();
+        }
+    }
+    const bool qual_on = !qual_spec.empty();
+    if (qual_on && !fastq) {
+        fprintf(stderr, "raxtax-hip: the quality filter (%s) needs FASTQ input: %s does not start with '@'\n", qual_spec.c_str(), qf.empty() ? "-i" : qf.c_str());
+        return 64;
+    }
+    if (qual_on) qual_spec += ";ascii=" + std::to_string(qual.ascii_base);
     // --primers: the pattern list, checked here -- before the database is read and any device is touched
     struct Primer { std::string name; std::vector<uint8_t> codes; uint32_t end; };
     std::vector<Primer> primers;
@@ -322,7 +374,7 @@ int main(int argc, char **argv) {
         primer_spec += (primer_spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
     }
     if (!primer_spec.empty()) primer_spec += ";errors=" + std::to_string(primer_pct) + ";window=" + std::to_string(primer_window);
-    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim";
+    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && derep) {
         fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
@@ -334,7 +386,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -353,6 +405,7 @@ int main(int argc, char **argv) {
             if (both_strands) purge_incomplete(strand_path, done);
             if (want_hits) purge_incomplete(hits_path, done);
             if (!primers.empty()) purge_incomplete(trim_path, done, true);
+            if (qual_on) purge_incomplete(qc_path, done, true);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -406,7 +459,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -419,7 +472,7 @@ int main(int argc, char **argv) {
     }
 
     // ---- queries: the file is read and parsed block by block on a thread of its own (cut in front of header lines,
-    // rtx_fasta_block_end), so that ingest overlaps with classification and memory stays bounded for very large
+    // rtx_fasta_block_end; FASTQ: behind whole records, rtx_fastq_block_end), so that ingest overlaps with classification and memory stays bounded for very large
     // files (the reference reads the whole file, parser.rs:112-115).  Already finished labels are dropped
     // (parser.rs:150-153).
     std::vector<const char *> skip;
@@ -450,12 +503,13 @@ int main(int argc, char **argv) {
             uint64_t end = buf.size();
             uint32_t flags = first ? 0u : RTX_FASTA_NOT_FIRST;
             if (!eof) {
-                end = rtx_fasta_block_end(buf.data(), buf.size());
-                if (end == 0) continue;  // no header inside the block yet: read on
+                end = fastq ? rtx_fastq_block_end(buf.data(), buf.size()) : rtx_fasta_block_end(buf.data(), buf.size());
+                if (end == 0) continue;  // no header (FASTQ: no whole record) inside the block yet: read on
                 flags |= RTX_FASTA_MORE_FOLLOWS;
             }
             Parsed pz;
-            pz.rc = rtx_queries_parse_fasta_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), flags, &pz.qs);
+            pz.rc = fastq ? rtx_queries_parse_fastq_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), qual.ascii_base, flags, &pz.qs)
+                          : rtx_queries_parse_fasta_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), flags, &pz.qs);
             if (pz.rc != RTX_OK) pz.err = rtx_last_error();
             pz.end = eof || pz.rc != RTX_OK;
             const bool failed = pz.rc != RTX_OK;
@@ -498,6 +552,7 @@ int main(int argc, char **argv) {
                     for (const Primer &p : primers) pats.push_back({p.codes.data(), (uint32_t)p.codes.size(), p.end, (uint32_t)(p.codes.size() * primer_pct / 100u), primer_window});
                     rcs[k] = rtx_index_set_primers(indices[k], pats.data(), (uint32_t)pats.size());
                 }
+                if (rcs[k] == RTX_OK && qual_on) rcs[k] = rtx_index_set_quality(indices[k], &qual);
                 if (rcs[k] == RTX_OK && profile_cutoff)
                     rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
@@ -537,6 +592,11 @@ int main(int argc, char **argv) {
             fprintf(stderr, "[INFO ] --primers: pattern %zu at the %s end: %s, at most %zu error(s)\n", k, primers[k].end == RTX_TRIM_3P ? "3'" : "5'", primers[k].name.c_str(),
                     primers[k].codes.size() * primer_pct / 100u);
     } else if (mode == std::ios::trunc) remove(trim_path.c_str());  // (likewise)
+    if (qual_on) {
+        const bool header = mode == std::ios::trunc || !is_file(qc_path);
+        sink.qc.open(qc_path, mode);
+        if (header) sink.qc << "label\tlength\tstart\tend\texpected_errors\tverdict\n";
+    } else if (mode == std::ios::trunc) remove(qc_path.c_str());  // (likewise)
     sink.want_strand = both_strands;
     sink.want_hits = want_hits;
     sink.tree = tree;
@@ -588,6 +648,19 @@ int main(int argc, char **argv) {
         else s->trim << p3 << '\t' << e3 << '\n';
         return s->trim.good() ? 0 : 1;
     };
+    // ... and, with a quality filter, what it made of every query (also one without result lines: a discarded read)
+    auto filtered = [](void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) -> int {
+        static const char *const names[7] = {"bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate"};
+        Sink *s = static_cast<Sink *>(c);
+        char frac[8];  // six decimals of ee / 2^40, truncated: from the integer, no floating point
+        snprintf(frac, sizeof frac, "%06llu", (unsigned long long)(((ee & ((1ull << 40) - 1)) * 1000000ull) >> 40));
+        s->qc << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t' << (ee >> 40) << '.' << frac << '\t';
+        if (!verdict) s->qc << "pass";
+        for (uint32_t b = 0, first = 1; b < 7u; b++)
+            if ((verdict >> b) & 1u) { s->qc << (first ? "" : "+") << names[b]; first = 0; }
+        s->qc << '\n';
+        return s->qc.good() ? 0 : 1;
+    };
     // (rtx_raxtax_multi_ex4 carries the callback of --identity: without that option the one of --strand both / --hits stands in its shape)
     auto info_as_align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {
         Sink *s = static_cast<Sink *>(c);
@@ -603,6 +676,8 @@ int main(int argc, char **argv) {
     uint64_t n = 0;
     uint64_t trim_total[4] = {0, 0, 0, 0};  // --primers: over the blocks of the file (rtx_raxtax_last_trim)
     double trim_busy = 0;
+    uint64_t qual_total[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the quality filter: queries, passed, cut short, the seven reasons (rtx_raxtax_last_qual)
+    double qual_busy = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
     double derep_busy = 0;
     bool parse_failed = false;
@@ -632,7 +707,14 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            if (!primers.empty())
+            if (qual_on) {
+                const uint8_t *quals = nullptr;
+                rtx_queries_quals(pz.qs, &quals);
+                rc = rtx_raxtax_multi_ex5(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                          want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
+                                          quals, +filtered, &sink);
+            }
+            else if (!primers.empty())
                 rc = rtx_raxtax_multi_ex4(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
                                           want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, +trimmed, &sink);
             else if (want_identity)
@@ -647,6 +729,12 @@ int main(int argc, char **argv) {
                 double tb = 0;
                 if (rtx_raxtax_last_trim(&tq[0], &tq[1], &tq[2], &tq[3], &tb) == RTX_OK) { for (int k = 0; k < 4; k++) trim_total[k] += tq[k]; trim_busy += tb; }
                 if (timing) fprintf(stderr, "[TIMING] primer trimming of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)tq[0], tb);
+            }
+            if (qual_on) {
+                uint64_t qq[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                double qb = 0;
+                if (rtx_raxtax_last_qual(&qq[0], &qq[1], &qq[2], qq + 3, &qb) == RTX_OK) { for (int k = 0; k < 10; k++) qual_total[k] += qq[k]; qual_busy += qb; }
+                if (timing) fprintf(stderr, "[TIMING] quality filter of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)qq[0], qb);
             }
             if (derep) {
                 uint64_t dq = 0, du = 0;
@@ -676,12 +764,20 @@ int main(int argc, char **argv) {
     if (both_strands) sink.strand.flush();
     if (want_hits) sink.hits.flush();
     if (!primers.empty()) sink.trim.flush();
+    if (qual_on) sink.qc.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
     if (!primers.empty()) {
         fprintf(stderr, "[INFO ] --primers: %llu queries, %llu with a 5' primer, %llu with a 3' primer, %llu left empty\n", (unsigned long long)trim_total[0],
                 (unsigned long long)trim_total[1], (unsigned long long)trim_total[2], (unsigned long long)trim_total[3]);
         if (timing) t_log << ", \"trim_busy\": " << trim_busy;
+    }
+    if (qual_on) {
+        fprintf(stderr, "[INFO ] quality filter: %llu queries, %llu passed (%llu of them cut short); discarded for bad_quality %llu, short_for_trunc_len %llu, too_short %llu, "
+                        "too_long %llu, too_many_n %llu, max_ee %llu, max_ee_rate %llu\n", (unsigned long long)qual_total[0], (unsigned long long)qual_total[1],
+                (unsigned long long)qual_total[2], (unsigned long long)qual_total[3], (unsigned long long)qual_total[4], (unsigned long long)qual_total[5],
+                (unsigned long long)qual_total[6], (unsigned long long)qual_total[7], (unsigned long long)qual_total[8], (unsigned long long)qual_total[9]);
+        if (timing) t_log << ", \"qual_busy\": " << qual_busy;
     }
     if (derep) {  // (per chunk: a copy in another chunk counts as a distinct read of its own)
         fprintf(stderr, "[INFO ] --derep: %llu queries, %llu distinct\n", (unsigned long long)derep_queries, (unsigned long long)derep_distinct);

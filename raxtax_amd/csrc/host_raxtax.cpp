@@ -79,6 +79,8 @@ struct LastDerep { uint64_t queries, distinct; double busy; };  // rtx_raxtax_la
 LastDerep g_derep{0, 0, 0.0};
 struct LastTrim { uint64_t queries, with5, with3, emptied; double busy; };  // rtx_raxtax_last_trim (under g_timing_mu)
 LastTrim g_trim{0, 0, 0, 0, 0.0};
+struct LastQual { uint64_t queries, passed, truncated, reasons[7]; double busy; };  // rtx_raxtax_last_qual (under g_timing_mu)
+LastQual g_qual{0, 0, 0, {0, 0, 0, 0, 0, 0, 0}, 0.0};
 
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
@@ -88,6 +90,8 @@ using RawSender = std::function<bool(const char *, const char *, const char *)>;
 using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t)>;
 // (label, length as given, lo, hi, hit) of every query, directly before its RawInfo call (rtx_query_trim_fn); empty: nobody asked
 using RawTrim = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint32_t)>;
+// (label, length as given, lo, hi, expected errors, verdict) of every query, directly after its RawTrim call (rtx_query_qual_fn)
+using RawQual = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint64_t, uint32_t)>;
 
 // Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the
 // one thread that dereplicates, which was most of the stage; the buffers travel between the chunks of a call through a pool, so that
@@ -167,7 +171,11 @@ struct Chunk {
     // primer was found in the chunk, the kept ranges back to back (t_bases / t_off, [nq + 1] from 0).  Query i: src_bases + src_off[i].
     const uint8_t *src_bases = nullptr;
     const uint64_t *src_off = nullptr;
-    std::vector<uint32_t> lo, hi, hit;  // [nq] rtx_trim_run, per query of the caller (empty: the option is off)
+    std::vector<uint32_t> lo, hi, hit;  // [nq] rtx_trim_run, per query of the caller (empty: primers and quality filter are off)
+    // quality filter (rtx_index_set_quality): rtx_qual_run on [lo, hi), per query of the caller (empty: off); keep_hi: the end of what goes
+    // downstream -- q_hi, or lo for a discarded read (the empty read)
+    std::vector<uint32_t> q_hi, q_verdict, keep_hi;
+    std::vector<uint64_t> q_ee;
     ByteBuf t_bases;
     std::vector<uint64_t> t_off;
     rtx_text_view text{};              // RTX_OPT_DEVICE_TEXT: the messages as the device formatted them (valid as long as `res`)
@@ -188,11 +196,14 @@ struct Chunk {
 //                   the sender go on per query of the caller (Chunk::slot)
 //                   With primers set (rtx_index_set_primers) it trims the reads of the chunk before that (rtx_trim_run, the same kind of
 //                   stage): the copies are looked for among the trimmed reads, and everything downstream sees those (Chunk::src_bases)
+//                   With a quality filter set (rtx_index_set_quality) the ranges the primers left are filtered next (rtx_qual_run, again
+//                   such a stage); both ranges are applied in one rtx_trim_apply, a discarded read goes on as the empty read
 //   calling thread: the sender, one message per query in INPUT order (raxtax.rs:85-87): chunk 0, 1, 2 ... as they become ready.
 // A handle keeps two result sets, so the view of its k-th chunk stays valid until its (k + 2)-th is classified.
 int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_t n_queries, const char *const *labels,
         const uint8_t *bases, const uint64_t *base_off, bool skip_exact_matches, bool raw_confidence, uint64_t chunk_size,
-        const RawSender &sender, bool tsv, const RawInfo &info = RawInfo(), const RawTrim &trim_cb = RawTrim()) {
+        const RawSender &sender, bool tsv, const RawInfo &info = RawInfo(), const RawTrim &trim_cb = RawTrim(), const uint8_t *quals = nullptr,
+        const RawQual &qual_cb = RawQual()) {
     if (!indices || n_dev == 0 || !tree || !base_off || !labels) { rtx::set_error("rtx_raxtax: null argument"); return RTX_ERR_INVALID; }
     for (uint32_t d = 0; d < n_dev; d++) {
         if (!indices[d]) { rtx::set_error("rtx_raxtax: null index handle"); return RTX_ERR_INVALID; }
@@ -279,6 +290,34 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             trims.own.push_back(trims.of[d]);
         }
     }
+    // Quality filter (rtx_index_set_quality): the same setting on every handle, and the call brings the quality strings.  One stage object
+    // (rtx_qual.hip) per distinct device, as for the primers.
+    rtx_qual_params qparams{};
+    const bool qual = rtx::index_quality(indices[0], &qparams);
+    for (uint32_t d = 1; d < n_dev; d++) {
+        rtx_qual_params other{};
+        if (rtx::index_quality(indices[d], &other) != qual || (qual && !rtx::qual_params_equal(other, qparams))) {
+            rtx::set_error("rtx_raxtax_multi: the handles disagree on their quality filter (rtx_index_set_quality)");
+            return RTX_ERR_INVALID;
+        }
+    }
+    if (qual && !quals) { rtx::set_error("rtx_raxtax: a quality filter is set (rtx_index_set_quality) and the call brings no quality strings (rtx_raxtax_multi_ex5)"); return RTX_ERR_INVALID; }
+    struct Quals {
+        std::vector<rtx_qual *> of;  // per handle; handles of one device share an object
+        std::vector<rtx_qual *> own;
+        ~Quals() { for (auto *p : own) rtx_qual_destroy(p); }
+    } qualstages;
+    if (qual) {
+        qualstages.of.assign(n_dev, nullptr);
+        for (uint32_t d = 0; d < n_dev; d++) {
+            for (uint32_t e = 0; e < d && !qualstages.of[d]; e++)
+                if (rtx::index_device(indices[e]) == rtx::index_device(indices[d])) qualstages.of[d] = qualstages.of[e];
+            if (qualstages.of[d]) continue;
+            const int rc = rtx_qual_create(rtx::index_device(indices[d]), &qparams, &qualstages.of[d]);
+            if (rc) return rc;
+            qualstages.own.push_back(qualstages.of[d]);
+        }
+    }
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
@@ -325,7 +364,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         chunks[c].dev_off = chunks[c].src_off = base_off + chunks[c].q0;
     }
     // busy seconds of the stages (rtx_raxtax_last_timing: which stage bounds an end-to-end run)
-    double busy_lookup = 0, busy_send = 0, busy_derep = 0, busy_trim = 0;
+    double busy_lookup = 0, busy_send = 0, busy_derep = 0, busy_trim = 0, busy_qual = 0;
+    uint64_t qual_queries = 0, qual_passed = 0, qual_truncated = 0, qual_reasons[7] = {0, 0, 0, 0, 0, 0, 0};
     uint64_t derep_queries = 0, derep_distinct = 0;
     uint64_t trim_queries = 0, trim_with5 = 0, trim_with3 = 0, trim_emptied = 0;
     std::vector<double> busy_device(n_dev, 0.0), busy_format(n_dev, 0.0);
@@ -359,42 +399,70 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     std::thread lookup([&] {
         for (uint64_t c = 0; c < n_chunks; c++) {
             Chunk &ch = chunks[c];
-            if (!derep && !trim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
+            if (!derep && !trim && !qual && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
             if (c >= ahead && !wait_stage(c - ahead, 2)) return;
-            if (trim) {  // the primers of the chunk's reads, on the device (a stream of its own beside the handle's); then the kept ranges
+            if (trim || qual) {  // the primers of the chunk's reads, then their quality, on the device (streams of their own beside the handle's); then the kept ranges
                 const double t_t0 = now();
                 ch.lo.resize(ch.nq);
                 ch.hi.resize(ch.nq);
                 ch.hit.resize(ch.nq);
-                int rc = rtx_trim_run(trims.of[c % n_dev], ch.nq, bases, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.hit.data());
+                int rc = RTX_OK;
+                if (trim) {
+                    rc = rtx_trim_run(trims.of[c % n_dev], ch.nq, bases, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.hit.data());
+                    if (!rc)
+                        for (uint64_t i = 0; i < ch.nq; i++) {
+                            const uint64_t len = base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
+                            const bool f5 = (ch.hit[i] & 0xFFu) != RTX_TRIM_NO_PATTERN, f3 = ((ch.hit[i] >> 16) & 0xFFu) != RTX_TRIM_NO_PATTERN;
+                            trim_with5 += f5;
+                            trim_with3 += f3;
+                            trim_emptied += len != 0 && ch.hi[i] == ch.lo[i];
+                        }
+                } else {
+                    for (uint64_t i = 0; i < ch.nq; i++) {
+                        ch.lo[i] = 0u;
+                        ch.hi[i] = (uint32_t)std::min<uint64_t>(base_off[ch.q0 + i + 1] - base_off[ch.q0 + i], 0xFFFFFFFFull);
+                        ch.hit[i] = RTX_TRIM_NO_PATTERN | RTX_TRIM_NO_PATTERN << 16;
+                    }
+                }
+                const double t_q0 = now();
+                if (!rc && qual) {  // every read's range as the primers left it; a discarded read goes on empty
+                    ch.q_hi.resize(ch.nq);
+                    ch.q_verdict.resize(ch.nq);
+                    ch.q_ee.resize(ch.nq);
+                    ch.keep_hi.resize(ch.nq);
+                    rc = rtx_qual_run(qualstages.of[c % n_dev], ch.nq, bases, quals, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.q_hi.data(), ch.q_ee.data(),
+                                      ch.q_verdict.data());
+                    if (!rc)
+                        for (uint64_t i = 0; i < ch.nq; i++) {
+                            const uint32_t v = ch.q_verdict[i];
+                            ch.keep_hi[i] = v ? ch.lo[i] : ch.q_hi[i];
+                            qual_passed += v == 0u;
+                            qual_truncated += v == 0u && ch.q_hi[i] < ch.hi[i];
+                            for (uint32_t b = 0; b < 7u; b++) qual_reasons[b] += (v >> b) & 1u;
+                        }
+                }
+                const std::vector<uint32_t> &keep_hi = qual ? ch.keep_hi : ch.hi;
                 bool any = false;
                 if (!rc)
-                    for (uint64_t i = 0; i < ch.nq; i++) {
-                        const uint64_t len = base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
-                        const bool f5 = (ch.hit[i] & 0xFFu) != RTX_TRIM_NO_PATTERN, f3 = ((ch.hit[i] >> 16) & 0xFFu) != RTX_TRIM_NO_PATTERN;
-                        trim_with5 += f5;
-                        trim_with3 += f3;
-                        trim_emptied += len != 0 && ch.hi[i] == ch.lo[i];
-                        any = any || ch.lo[i] != 0u || ch.hi[i] != len;
-                    }
-                if (!rc && any) {  // (a chunk in which nothing was found goes on as it came, without a copy)
+                    for (uint64_t i = 0; i < ch.nq && !any; i++) any = ch.lo[i] != 0u || keep_hi[i] != base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
+                if (!rc && any) {  // (a chunk in which nothing was cut goes on as it came, without a copy)
                     uint64_t kept = 0;
-                    for (uint64_t i = 0; i < ch.nq; i++) kept += ch.hi[i] - ch.lo[i];
+                    for (uint64_t i = 0; i < ch.nq; i++) kept += keep_hi[i] - ch.lo[i];
                     {
                         std::lock_guard<std::mutex> g(pool_mu);
                         if (!bases_pool.empty()) { ch.t_bases = std::move(bases_pool.back()); bases_pool.pop_back(); }
                     }
                     if (!ch.t_bases.reserve(kept + 1)) { fail(RTX_ERR_OOM, "no memory for the trimmed reads of a chunk"); return; }
                     ch.t_off.resize(ch.nq + 1);
-                    rc = rtx_trim_apply(ch.nq, bases, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.t_bases.p, ch.t_off.data());
+                    rc = rtx_trim_apply(ch.nq, bases, base_off + ch.q0, ch.lo.data(), keep_hi.data(), ch.t_bases.p, ch.t_off.data());
                     if (!rc) {
                         ch.dev_bases = ch.src_bases = ch.t_bases.p;
                         ch.dev_off = ch.src_off = ch.t_off.data();
                     }
                 }
                 if (rc) { fail(rc, rtx_last_error()); return; }
-                trim_queries += ch.nq;
-                busy_trim += now() - t_t0;
+                if (trim) { trim_queries += ch.nq; busy_trim += (qual ? t_q0 : now()) - t_t0; }
+                if (qual) { qual_queries += ch.nq; busy_qual += now() - t_q0; }
                 if (!derep && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
             }
             if (derep) {  // the copies of the chunk, on the device (a stream of its own beside the handle's); then the map's host side
@@ -712,6 +780,11 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 const bool on = !ch.lo.empty();
                 if (!trim_cb(labels[q], raw, on ? ch.lo[i] : 0u, on ? ch.hi[i] : raw, on ? ch.hit[i] : (RTX_TRIM_NO_PATTERN | RTX_TRIM_NO_PATTERN << 16))) { closed = true; break; }
             }
+            if (qual_cb) {  // likewise
+                const uint32_t raw = (uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull);
+                const bool ranged = !ch.lo.empty(), on = !ch.q_hi.empty();
+                if (!qual_cb(labels[q], raw, ranged ? ch.lo[i] : 0u, on ? ch.q_hi[i] : (ranged ? ch.hi[i] : raw), on ? ch.q_ee[i] : 0ull, on ? ch.q_verdict[i] : 0u)) { closed = true; break; }
+            }
             if (ch.status[i] != RTX_Q_OK) {
                 // the reference aborts here (prob.rs:21/162); report and skip the query instead
                 if (ch.status[i] == RTX_Q_ALL_KMERS) fprintf(stderr, "[ERROR] query %s holds every 8-mer (t = 65536): the reference asserts t < 65536 (raxtax.rs:56)\n", labels[q]);
@@ -745,6 +818,10 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint32_t>().swap(ch.lo);
         std::vector<uint32_t>().swap(ch.hi);
         std::vector<uint32_t>().swap(ch.hit);
+        std::vector<uint32_t>().swap(ch.q_hi);
+        std::vector<uint32_t>().swap(ch.q_verdict);
+        std::vector<uint32_t>().swap(ch.keep_hi);
+        std::vector<uint64_t>().swap(ch.q_ee);
         std::vector<uint64_t>().swap(ch.t_off);
         {
             std::lock_guard<std::mutex> g(pool_mu);
@@ -770,6 +847,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         g_timing = {{any_host_lookup ? busy_lookup : 0.0, bd, bf, busy_send}, n_chunks};
         g_derep = {derep_queries, derep_distinct, busy_derep};
         g_trim = {trim_queries, trim_with5, trim_with3, trim_emptied, busy_trim};
+        g_qual = {qual_queries, qual_passed, qual_truncated, {qual_reasons[0], qual_reasons[1], qual_reasons[2], qual_reasons[3], qual_reasons[4], qual_reasons[5], qual_reasons[6]}, busy_qual};
     }
     if (failed != RTX_OK) { rtx::set_error("%s", failed_msg.c_str()); return failed; }
     if (warnings)  // raxtax.rs:93-95
@@ -860,6 +938,16 @@ extern "C" int rtx_raxtax_multi_ex4(rtx_index *const *indices, uint32_t n_indice
                                     const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                                     int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                                     rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx) {
+    return rtx_raxtax_multi_ex5(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender,
+                                sender_ctx, tsv, align, align_ctx, trim, trim_ctx, nullptr, nullptr, nullptr);
+}
+
+// ... and the quality strings of the reads with the quality filter of every query (rtx_index_set_quality)
+extern "C" int rtx_raxtax_multi_ex5(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                                    rtx_query_qual_fn qual, void *qual_ctx) {
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
@@ -869,8 +957,10 @@ extern "C" int rtx_raxtax_multi_ex4(rtx_index *const *indices, uint32_t n_indice
         };
     RawTrim ft;
     if (trim) ft = [&](const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit) { return trim(trim_ctx, label, raw_len, lo, hi, hit) == 0; };
+    RawQual fq;
+    if (qual) fq = [&](const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) { return qual(qual_ctx, label, raw_len, lo, hi, ee, verdict) == 0; };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
-               tsv != 0, fi, ft);
+               tsv != 0, fi, ft, quals, fq);
 }
 
 extern "C" int rtx_raxtax_last_timing(double busy[4], uint64_t *n_chunks) {
@@ -896,6 +986,16 @@ extern "C" int rtx_raxtax_last_trim(uint64_t *queries, uint64_t *with5, uint64_t
     if (with3) *with3 = g_trim.with3;
     if (emptied) *emptied = g_trim.emptied;
     if (busy_seconds) *busy_seconds = g_trim.busy;
+    return RTX_OK;
+}
+
+extern "C" int rtx_raxtax_last_qual(uint64_t *queries, uint64_t *passed, uint64_t *truncated, uint64_t reasons[7], double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_qual.queries;
+    if (passed) *passed = g_qual.passed;
+    if (truncated) *truncated = g_qual.truncated;
+    if (reasons) for (int b = 0; b < 7; b++) reasons[b] = g_qual.reasons[b];
+    if (busy_seconds) *busy_seconds = g_qual.busy;
     return RTX_OK;
 }
 

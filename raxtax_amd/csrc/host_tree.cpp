@@ -587,6 +587,118 @@ int rtx_queries_parse_fasta_block(const char *text, uint64_t len, const char *co
         return RTX_ERR_OOM;
     }
 }
+// ---- FASTQ: the four-line record form (include/raxtax_hip.h).  A quality line may start with '@' or '+', so nothing is decided by the first
+// byte of a line alone: the lines are counted from the start of the text, a record is lines 4 r .. 4 r + 3.
+uint64_t rtx_fastq_block_end(const char *text, uint64_t len) {
+    if (!text) return 0;
+    uint64_t lines = 0, end = 0, pos = 0;
+    const void *nl;
+    while (pos < len && (nl = memchr(text + pos, '\n', len - pos)) != nullptr) {
+        pos = (uint64_t)((const char *)nl - text) + 1;
+        if ((++lines & 3u) == 0) end = pos;
+    }
+    return end;
+}
+
+int rtx_queries_parse_fastq(const char *text, uint64_t len, const char *const *skip, uint64_t n_skip, uint32_t ascii_base, rtx_queries **out) {
+    return rtx_queries_parse_fastq_block(text, len, skip, n_skip, ascii_base, 0, out);
+}
+
+int rtx_queries_parse_fastq_block(const char *text, uint64_t len, const char *const *skip, uint64_t n_skip, uint32_t ascii_base, uint32_t flags,
+                                  rtx_queries **out) {
+    (void)flags;  // (every block starts at a record and holds whole records: the first and the last one are parsed like any other)
+    if (!out) { set_error("null argument"); return RTX_ERR_INVALID; }
+    if (ascii_base != 33u && ascii_base != 64u) { set_error("rtx_queries_parse_fastq: ascii_base %u (33 or 64)", ascii_base); return RTX_ERR_INVALID; }
+    if (!text || len == 0) { set_error("File is empty"); return RTX_ERR_PARSE; }
+    try {
+        std::unordered_map<std::string_view, int> skipset;
+        for (uint64_t i = 0; i < n_skip; i++) skipset.emplace(skip[i], 1);
+        auto is_ws = [](char c) { return c == ' ' || c == '\t' || c == '\r' || c == '\n' || c == '\v' || c == '\f'; };
+        std::vector<uint64_t> start{0};  // of every line; the last line may lack its newline
+        for (uint64_t pos = 0; pos < len;) {
+            const void *nl = memchr(text + pos, '\n', len - pos);
+            if (!nl) break;
+            pos = (uint64_t)((const char *)nl - text) + 1;
+            start.push_back(pos);
+        }
+        uint64_t n_lines = start.size();
+        start.push_back(len + 1);  // (as if a newline followed)
+        if (start[n_lines - 1] == len) n_lines--;  // the text ends in a newline: nothing follows it
+        auto blank = [&](uint64_t i) {
+            for (uint64_t k = start[i]; k < std::min(start[i + 1] - 1, len); k++)
+                if (!is_ws(text[k])) return false;
+            return true;
+        };
+        // blank lines behind the last record (a record without bases has two blank lines of its own: only what does not fill a record goes)
+        while (n_lines % 4 && blank(n_lines - 1)) n_lines--;
+        while (n_lines >= 4 && blank(n_lines - 1) && blank(n_lines - 2) && blank(n_lines - 3) && blank(n_lines - 4)) n_lines -= 4;
+        if (n_lines == 0) { set_error("File is empty"); return RTX_ERR_PARSE; }
+        const uint64_t n_rec = n_lines / 4;
+        auto line = [&](uint64_t i) {  // trimmed as the FASTA parser trims its lines
+            uint64_t b = start[i], e = std::min(start[i + 1] - 1, len);
+            while (b < e && is_ws(text[b])) b++;
+            while (e > b && is_ws(text[e - 1])) e--;
+            return std::string_view(text + b, e - b);
+        };
+        const size_t np = (size_t)std::max<uint64_t>(1, std::min<uint64_t>(parse_threads(len), n_rec));
+        struct Piece : FastaPiece { std::vector<uint8_t> quals; };
+        std::vector<Piece> pieces(np);
+        auto parse_piece = [&](size_t pi) {
+            Piece &P = pieces[pi];
+            P.off.push_back(0);
+            char msg[160];
+            for (uint64_t r = n_rec * pi / np; r < n_rec * (pi + 1) / np; r++) {
+                const std::string_view head = line(4 * r), seq = line(4 * r + 1), plus = line(4 * r + 2), qual = line(4 * r + 3);
+                const unsigned long long rec = (unsigned long long)r + 1;
+                if (head.empty() || head[0] != '@') { snprintf(msg, sizeof msg, "FASTQ record %llu: the first line does not start with '@'", rec); P.err = msg; return; }
+                if (plus.empty() || plus[0] != '+') { snprintf(msg, sizeof msg, "FASTQ record %llu: the third line does not start with '+'", rec); P.err = msg; return; }
+                if (qual.size() != seq.size()) { snprintf(msg, sizeof msg, "FASTQ record %llu: %zu quality bytes for %zu bases", rec, qual.size(), seq.size()); P.err = msg; return; }
+                const bool skipped = skipset.count(head.substr(1)) != 0;
+                const size_t at = P.bytes.size();
+                if (!skipped) { P.bytes.resize(at + seq.size()); P.quals.resize(at + seq.size()); }
+                for (size_t i = 0; i < seq.size(); i++) {
+                    const uint8_t c = map_dna_char((unsigned char)seq[i]);
+                    const unsigned char qb = (unsigned char)qual[i];
+                    if (c == 0xFF) { snprintf(msg, sizeof msg, "FASTQ record %llu: Unexpected character: %c", rec, seq[i]); P.err = msg; return; }
+                    if (qb < 33 || qb > 126) { snprintf(msg, sizeof msg, "FASTQ record %llu: quality byte %u (33 .. 126)", rec, (unsigned)qb); P.err = msg; return; }
+                    if (!skipped) { P.bytes[at + i] = c; P.quals[at + i] = qb; }
+                }
+                if (skipped) continue;
+                P.labels.emplace_back(head.substr(1));
+                P.off.push_back(P.bytes.size());
+            }
+        };
+        run_pieces(np, parse_piece);
+        auto q = new rtx_queries();
+        q->fastq = true;
+        q->quals.reserve(1);  // (rtx_queries_quals: never NULL for a FASTQ parse)
+        for (Piece &P : pieces) {
+            if (!P.err.empty()) { set_error("%s", P.err.c_str()); delete q; return RTX_ERR_PARSE; }
+            for (std::string &l : P.labels) q->labels.push_back(std::move(l));
+            const uint64_t base = q->bases.size();
+            q->bases.insert(q->bases.end(), P.bytes.begin(), P.bytes.end());
+            q->quals.insert(q->quals.end(), P.quals.begin(), P.quals.end());
+            for (size_t i = 1; i < P.off.size(); i++) q->base_off.push_back(base + P.off[i]);
+        }
+        if (n_lines % 4) {  // (reported behind the errors of the whole records in front of it)
+            set_error("FASTQ record %llu: cut short after %llu of its four lines", (unsigned long long)n_rec + 1, (unsigned long long)(n_lines % 4));
+            delete q;
+            return RTX_ERR_PARSE;
+        }
+        *out = q;
+        return RTX_OK;
+    } catch (const std::bad_alloc &) {
+        set_error("out of host memory");
+        return RTX_ERR_OOM;
+    }
+}
+
+int rtx_queries_quals(const rtx_queries *q, const uint8_t **quals) {
+    if (!q || !quals) { set_error("null argument"); return RTX_ERR_INVALID; }
+    *quals = q->fastq ? q->quals.data() : nullptr;
+    return RTX_OK;
+}
+
 void rtx_queries_destroy(rtx_queries *q) { delete q; }
 uint64_t rtx_queries_len(const rtx_queries *q) { return q ? q->labels.size() : 0; }
 const char *rtx_queries_label(const rtx_queries *q, uint64_t i) {

@@ -707,6 +707,67 @@ void emul_trim_read(uint32_t n_pat, const uint8_t *codes, const uint32_t *code_o
     trim_read(pat.data(), n5, n3, loader(row5), loader(row3), len, *lo, *hi, *hit);
 }
 
+// The quality filter as qual_kernel (rtx_qual.hip) runs it, with the functions the kernel calls, in the kernel's geometry: steps of 16 pieces
+// of 16 bytes, the piece sums of a step first, then the scan over them, then every piece's stop with what lies in front of it, the first of
+// the step, and the sums read from the piece that holds it.  cfg: the parameters as integers (base, trunc_len, trunc_qual, min_len,
+// max_len, max_ns as uint32 / int32 in cfg32[6]; trunc_ee, max_ee, max_ee_rate in cfg64[3], ~0: off); table: the 94 errors; x: the staged
+// bytes of one range (quality | 0x80 where the base is no A/C/G/T), len of them.
+void emul_qual_read(const int32_t *cfg32, const uint64_t *cfg64, const uint64_t *table, const uint8_t *x, uint32_t len, uint32_t *kept, uint64_t *ee,
+                    uint32_t *verdict) {
+    QualCfg cfg;
+    cfg.base = (uint32_t)cfg32[0];
+    cfg.trunc_len = (uint32_t)cfg32[1];
+    cfg.trunc_qual = cfg32[2];
+    cfg.min_len = (uint32_t)cfg32[3];
+    cfg.max_len = (uint32_t)cfg32[4];
+    cfg.max_ns = cfg32[5];
+    cfg.trunc_ee = cfg64[0];
+    cfg.max_ee = cfg64[1];
+    cfg.max_ee_rate = cfg64[2];
+    std::vector<uint8_t> row((size_t)(len + 15u) / 16u * 16u + 16u, 0xFF);  // (what lies behind the range is never taken as data)
+    if (len) memcpy(row.data(), x, len);
+    bool short_tl, bad = false, done = false;
+    const uint32_t end = qual_end(cfg, len, short_tl);
+    uint64_t carry_e = 0;
+    uint32_t carry_n = 0, hi = end;
+    for (uint32_t s = 0; s * 256u < len; s++) {
+        QualPiece pc[kQualGroup];
+        uint64_t before_e[kQualGroup], run_e = carry_e;
+        uint32_t before_n[kQualGroup], run_n = carry_n;
+        for (uint32_t gl = 0; gl < kQualGroup; gl++) {
+            const uint32_t pos = s * 256u + gl * 16u;
+            QualWords t{{0u, 0u, 0u, 0u}};
+            if (pos < len) memcpy(t.w, row.data() + pos, 16);
+            qual_piece_sum(cfg, table, t, pos, len, end, pc[gl]);
+            bad = bad || pc[gl].bad;
+            before_e[gl] = run_e;
+            before_n[gl] = run_n;
+            run_e += pc[gl].c[kQualPiece - 1u];
+            run_n += (uint32_t)__builtin_popcount(pc[gl].ns);
+        }
+        uint32_t first = 0xFFFFFFFFu, src = kQualGroup - 1u;
+        uint64_t at_e[kQualGroup];
+        uint32_t at_n[kQualGroup];
+        for (uint32_t gl = 0; gl < kQualGroup; gl++) {
+            const uint32_t pos = s * 256u + gl * 16u;
+            uint64_t e;
+            uint32_t nn;
+            const uint32_t stop = qual_piece_stop(cfg, pc[gl], before_e[gl], pos, end, e, nn);
+            at_e[gl] = before_e[gl] + e;
+            at_n[gl] = before_n[gl] + nn;
+            if (stop != kQualPiece && pos + stop < first) { first = pos + stop; src = gl; }
+        }
+        if (!done) {
+            carry_e = at_e[src];
+            carry_n = at_n[src];
+            if (first != 0xFFFFFFFFu) { hi = first; done = true; }
+        }
+    }
+    *kept = bad ? 0u : hi;
+    *ee = bad ? 0ull : carry_e;
+    *verdict = qual_verdict(cfg, bad, short_tl, hi, carry_e, carry_n);
+}
+
 // byte, high-bit word and shift of local reference rl in the packed counts of its tile (packed_count_pos)
 void emul_packed_count_pos(uint32_t rl, uint32_t *byte, uint32_t *hi_word, uint32_t *hi_shift) { packed_count_pos(rl, *byte, *hi_word, *hi_shift); }
 

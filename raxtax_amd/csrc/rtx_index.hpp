@@ -463,6 +463,8 @@ struct rtx_index {
     uint64_t text_tree_uid = 0;      // rtx_tree::uid of the tree the lineage table was uploaded from
     uint32_t device_text_opt = 0;    // RTX_OPT_DEVICE_TEXT
     uint32_t derep_opt = 0;          // RTX_OPT_DEREP: rtx_raxtax* classify each distinct read of a chunk once (rtx_derep.hip); the handle itself never reads it
+    rtx_qual_params quality{};       // rtx_index_set_quality: rtx_raxtax* filter every read by its quality string (rtx_qual.hip); the handle itself never reads it
+    bool quality_on = false;
     std::vector<rtx::TrimPrimer> primers;  // rtx_index_set_primers: rtx_raxtax* trim every read with them first (rtx_trim.hip); the handle itself never reads them
     DevBuf<char> d_lin_bytes, d_text;
     DevBuf<uint64_t> d_lin_off;

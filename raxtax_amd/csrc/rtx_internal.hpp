@@ -43,6 +43,13 @@ struct TrimPrimer {
 };
 int trim_check_patterns(const char *who, const rtx_trim_pattern *pats, uint32_t n);  // RTX_OK, or RTX_ERR_INVALID with the pattern named
 const std::vector<TrimPrimer> &index_primers(const rtx_index *index);
+// quality filter (host_qual.cpp / rtx_qual.hip): the checks of a parameter struct (RTX_OK, or RTX_ERR_INVALID with the field named), whether it
+// filters anything, the error table (computed once), and the setting a handle holds (rtx_index_set_quality; false: off)
+int qual_check_params(const char *who, const rtx_qual_params *p);
+bool qual_params_on(const rtx_qual_params &p);
+bool qual_params_equal(const rtx_qual_params &a, const rtx_qual_params &b);
+const uint64_t *qual_table();
+bool index_quality(const rtx_index *index, rtx_qual_params *params);
 bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value
 bool hw_queues_for_run_ahead();  // (host_threads.cpp) GPU_MAX_HW_QUEUES reads six or more: transfers do not share a hardware queue with kernels
 
@@ -105,4 +112,6 @@ struct rtx_queries {
     std::vector<std::string> labels;
     std::vector<uint8_t> bases;
     std::vector<uint64_t> base_off{0};
+    std::vector<uint8_t> quals;  // FASTQ: the quality bytes as they stand in the file, indexed like bases (rtx_queries_quals)
+    bool fastq = false;
 };

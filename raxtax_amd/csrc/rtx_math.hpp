@@ -250,6 +250,126 @@ RTX_HD void trim_read(const TrimPattern *pat, uint32_t n5, uint32_t n3, const L5
 }
 
 // ---------------------------------------------------------------------------
+// Quality filter (qual_kernel, rtx_qual.hip; rtx_qual_read on the host; emul_qual_read on x86): where a read is cut and why it is discarded,
+// from its FASTQ quality string -- include/raxtax_hip.h has the semantics.  Exact integers: the error probability of quality Q is
+// e[Q] = llround(10^(-Q/10) * 2^40), computed once on the host (qual_table), a threshold x is floor(x * 2^40); a read has at most 2^20 bases,
+// so no sum exceeds 2^60.
+// The read arrives as the stage packs it: one byte per base, the raw quality byte in bits 0-6, bit 7 set where the base is no A/C/G/T, in
+// pieces of 16 bytes (QualWords: one load).  A piece is worked in two halves, because the cut of trunc_ee needs the sum of everything in
+// front of the piece: qual_piece_sum (the piece's own prefix sums and totals), then -- after the scan over the pieces of a step, across the
+// lanes of a group on the device, a plain loop in qual_read_serial -- qual_piece_stop (the first position to cut in front of).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kQualMaxQ = 93u;                // Q = 0 .. 93: the printable ASCII range above base 33
+constexpr uint32_t kQualMaxRead = 1u << 20;        // RTX_QUAL_MAX_READ
+constexpr uint32_t kQualPiece = 16u;               // bytes of a piece
+constexpr uint32_t kQualGroup = 16u;               // pieces of a step: the lanes of a group
+constexpr uint64_t kQualOff = ~0ull;               // a threshold that is off (a given one is at most 2^63)
+constexpr uint32_t kQcBadQuality = 1u, kQcShortForTruncLen = 2u, kQcTooShort = 4u, kQcTooLong = 8u, kQcTooManyN = 16u, kQcMaxEe = 32u,
+                   kQcMaxEeRate = 64u;             // RTX_QC_*
+struct QualCfg {           // rtx_qual_params as integers (host_qual.cpp: qual_cfg_init); uniform over a wave
+    uint32_t base;         // 33 or 64
+    uint32_t trunc_len;    // 0: off
+    int32_t trunc_qual;    // < 0: off
+    uint64_t trunc_ee;     // kQualOff: off
+    uint32_t min_len, max_len;  // 0: off
+    int32_t max_ns;        // < 0: off
+    uint64_t max_ee;       // kQualOff: off
+    uint64_t max_ee_rate;  // kQualOff: off
+};
+struct QualWords { uint32_t w[4]; };
+struct QualPiece {
+    uint64_t c[kQualPiece];  // inclusive prefix sums of e over the piece's bytes (a byte at or behind `end` adds 0)
+    uint32_t ns;             // bit j: byte j is an N in front of `end`
+    uint32_t low;            // bit j: byte j lies in front of `end` and has Q <= trunc_qual
+    bool bad;                // a byte in front of `len` has Q outside 0 .. 93
+};
+// The piece at bytes pos .. pos + 15 of a range of len bytes, of which [0, end) stand for truncation (end <= len: trunc_len applied).
+RTX_HD void qual_piece_sum(const QualCfg &cfg, const uint64_t *table, const QualWords &t, uint32_t pos, uint32_t len, uint32_t end, QualPiece &p) {
+    uint64_t run = 0;
+    p.ns = p.low = 0u;
+    p.bad = false;
+#pragma unroll
+    for (uint32_t j = 0; j < kQualPiece; j++) {
+        const uint32_t b = (t.w[j >> 2] >> ((j & 3u) * 8u)) & 0xFFu;
+        const uint32_t q = (b & 0x7Fu) - cfg.base;  // (wraps below the base: above 93 as well)
+        const bool in_len = pos + j < len, in_end = pos + j < end;
+        p.bad = p.bad || (in_len && q > kQualMaxQ);
+        const uint64_t e = table[q > kQualMaxQ ? 0u : q];
+        run += in_end ? e : 0ull;
+        p.c[j] = run;
+        p.ns |= (uint32_t)(in_end && (b & 0x80u) != 0u) << j;
+        p.low |= (uint32_t)(in_end && cfg.trunc_qual >= 0 && q <= (uint32_t)cfg.trunc_qual) << j;
+    }
+}
+// before: the sum of e over everything of the range in front of the piece.  The first byte j of the piece to cut in front of -- Q <= trunc_qual,
+// or before + c[j] above trunc_ee -- or kQualPiece when it has none; ee / ns: what the piece adds in front of that byte.
+RTX_HD uint32_t qual_piece_stop(const QualCfg &cfg, const QualPiece &p, uint64_t before, uint32_t pos, uint32_t end, uint64_t &ee, uint32_t &ns) {
+    uint32_t stop = kQualPiece;
+#pragma unroll
+    for (uint32_t j = kQualPiece; j-- > 0u;) {
+        const bool over = cfg.trunc_ee != kQualOff && pos + j < end && before + p.c[j] > cfg.trunc_ee;
+        if (over || ((p.low >> j) & 1u)) stop = j;
+    }
+    ee = 0ull;
+#pragma unroll
+    for (uint32_t j = 0; j < kQualPiece; j++)
+        if (j + 1u == stop) ee = p.c[j];
+    const uint32_t m = p.ns & ((1u << stop) - 1u);
+#if defined(__HIP_DEVICE_COMPILE__)
+    ns = (uint32_t)__popc(m);
+#else
+    ns = (uint32_t)__builtin_popcount(m);
+#endif
+    return stop;
+}
+// is ee above rate * kept?  (rate up to 2^63, kept below 2^21: the product in 96 bits)
+RTX_HD bool qual_rate_exceeded(uint64_t ee, uint64_t rate, uint32_t kept) {
+    const uint64_t p0 = (rate & 0xFFFFFFFFull) * kept, p1 = (rate >> 32) * kept;  // the product is (p1 << 32) + p0
+    const uint64_t mid = p1 + (p0 >> 32);
+    if (mid >> 32) return false;  // 2^64 or more: no sum reaches it
+    return ee > ((mid << 32) | (p0 & 0xFFFFFFFFull));
+}
+// len: the bytes of the input range; short_tl: it was shorter than trunc_len; kept / ee / ns: of [0, kept)
+RTX_HD uint32_t qual_verdict(const QualCfg &cfg, bool bad, bool short_tl, uint32_t kept, uint64_t ee, uint32_t ns) {
+    if (bad) return kQcBadQuality;
+    uint32_t v = short_tl ? kQcShortForTruncLen : 0u;
+    if (cfg.min_len && kept < cfg.min_len) v |= kQcTooShort;
+    if (cfg.max_len && kept > cfg.max_len) v |= kQcTooLong;
+    if (cfg.max_ns >= 0 && ns > (uint32_t)cfg.max_ns) v |= kQcTooManyN;
+    if (cfg.max_ee != kQualOff && ee > cfg.max_ee) v |= kQcMaxEe;
+    if (cfg.max_ee_rate != kQualOff && qual_rate_exceeded(ee, cfg.max_ee_rate, kept)) v |= kQcMaxEeRate;
+    return v;
+}
+// [0, end) of a range of len bytes stands for truncation: trunc_len cuts it, a range shorter than trunc_len keeps its length (and is discarded)
+RTX_HD uint32_t qual_end(const QualCfg &cfg, uint32_t len, bool &short_tl) {
+    short_tl = cfg.trunc_len != 0u && len < cfg.trunc_len;
+    return cfg.trunc_len != 0u && !short_tl ? cfg.trunc_len : len;
+}
+// One range of len bytes, the steps and pieces of qual_kernel one after the other.  load(i): bytes 16 i .. 16 i + 15 of the range.
+template <class L>
+RTX_HD void qual_read_serial(const QualCfg &cfg, const uint64_t *table, const L &load, uint32_t len, uint32_t &kept, uint64_t &ee, uint32_t &verdict) {
+    bool short_tl, bad = false, done = false;
+    const uint32_t end = qual_end(cfg, len, short_tl);
+    uint64_t carry_e = 0;
+    uint32_t carry_n = 0, hi = end;
+    for (uint32_t pos = 0; pos < len; pos += kQualPiece) {
+        QualPiece p;
+        qual_piece_sum(cfg, table, load(pos / kQualPiece), pos, len, end, p);
+        bad = bad || p.bad;
+        if (done) continue;
+        uint64_t e;
+        uint32_t n;
+        const uint32_t stop = qual_piece_stop(cfg, p, carry_e, pos, end, e, n);
+        carry_e += e;
+        carry_n += n;
+        if (stop != kQualPiece) { hi = pos + stop; done = true; }
+    }
+    kept = bad ? 0u : hi;
+    ee = bad ? 0ull : carry_e;
+    verdict = qual_verdict(cfg, bad, short_tl, hi, carry_e, carry_n);
+}
+
+// ---------------------------------------------------------------------------
 // Hash of an encoded sequence for the exact-match lookup (Tree.sequences.get, raxtax.rs:42) on the device.  The bytes are taken
 // as 8-byte little-endian words (the last one zero-padded); every word is mixed with its position and the mixes are ADDED, so
 // that the lanes of a wave can hash their words independently and meet in one sum.  Equal sequences hash equal; a collision only
