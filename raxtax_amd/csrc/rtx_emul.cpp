@@ -14,7 +14,89 @@
 
 using namespace rtx;
 
+// Folds n_rows words (one 32-reference column; n_rows a multiple of 8) into NP planes by one of the kernels' schedules:
+//   sched 32: hit_count_kernel / fold_ring<NB = 4> -- 32 rows = four tree8 + two CSAs on plane 3 + one on plane 4 + ripple from plane 5,
+//             the rest eight at a time (planes_add8);
+//   sched 24: hit_count_pair_kernel (fold_seg<NB = 3>, rtx_hit_pair.hip) -- 24 rows = three tree8, a CSA on plane 3 for the first two
+//             carries, a half adder on plane 3 for the third, a CSA on plane 4, ripple from plane 5; the rows a list lacks for its last
+//             group are the zero row, as the kernel pads its lists.
+template <int NP>
+static void emul_fold(uint32_t (&pl)[NP], const uint32_t *rows, uint32_t n_rows, int sched) {
+    auto t8 = [&](const uint32_t *r) { return planes_tree8<NP>(pl, r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7]); };
+    uint32_t r = 0;
+    if (sched == 24) {
+        std::vector<uint32_t> padded(rows, rows + n_rows);
+        padded.resize((n_rows + 23u) / 24u * 24u, 0u);
+        for (; r + 24 <= padded.size(); r += 24) {
+            const uint32_t c3a = t8(&padded[r]), c3b = t8(&padded[r + 8]), c3c = t8(&padded[r + 16]);
+            uint32_t c4a, c5;
+            csa(pl[3], c3a, c3b, pl[3], c4a);
+            const uint32_t c4b = pl[3] & c3c;  // half_plane (rtx_hit_common.hpp): a carry-save adder with one input 0
+            pl[3] ^= c3c;
+            csa(pl[4], c4a, c4b, pl[4], c5);
+            planes_ripple<NP, 5>(pl, c5);
+        }
+        return;
+    }
+    for (; r + 32 <= n_rows; r += 32) {
+        uint32_t c3a = t8(rows + r), c3b = t8(rows + r + 8), c4a, c4b, c5;
+        csa(pl[3], c3a, c3b, pl[3], c4a);
+        c3a = t8(rows + r + 16);
+        c3b = t8(rows + r + 24);
+        csa(pl[3], c3a, c3b, pl[3], c4b);
+        csa(pl[4], c4a, c4b, pl[4], c5);
+        planes_ripple<NP, 5>(pl, c5);
+    }
+    for (; r + 8 <= n_rows; r += 8)
+        planes_add8<NP>(pl, rows[r], rows[r + 1], rows[r + 2], rows[r + 3], rows[r + 4], rows[r + 5], rows[r + 6], rows[r + 7]);
+}
+
+// the 32 counters of a word by planes_unpack4; the two other unpack forms of the epilogues must give the same (else the counter is
+// poisoned: 0xFFFFFFFF planes_unpack8, 0xFFFFFFFE planes_unpack32 + planes_unpack8_hi)
+template <int NP>
+static void emul_unpack(const uint32_t (&pl)[NP], uint32_t *out) {
+    for (int g = 0; g < 8; g++) {
+        uint32_t lo, hi;
+        planes_unpack4<NP>(pl, g, lo, hi);
+        for (int j = 0; j < 4; j++) out[4 * g + j] = ((lo >> (8 * j)) & 0xFF) | (((hi >> (8 * j)) & 0xFF) << 8);
+    }
+    for (int b = 0; b < 4; b++) {
+        uint32_t lo0, hi0, lo1, hi1;
+        planes_unpack8<NP>(pl, b, lo0, hi0, lo1, hi1);
+        for (int j = 0; j < 4; j++) {
+            const uint32_t c0 = ((lo0 >> (8 * j)) & 0xFF) | (((hi0 >> (8 * j)) & 0xFF) << 8);
+            const uint32_t c1 = ((lo1 >> (8 * j)) & 0xFF) | (((hi1 >> (8 * j)) & 0xFF) << 8);
+            if (c0 != out[8 * b + j] || c1 != out[8 * b + 4 + j]) out[8 * b + j] = 0xFFFFFFFFu;  // poison: the test fails
+        }
+    }
+    uint32_t lo[4][2];
+    planes_unpack32<NP>(pl, lo);
+    for (int b = 0; b < 4; b++) {
+        uint32_t hi0, hi1;
+        planes_unpack8_hi<NP>(pl, b, hi0, hi1);
+        for (int j = 0; j < 4; j++) {
+            const uint32_t c0 = ((lo[b][0] >> (8 * j)) & 0xFF) | (((hi0 >> (8 * j)) & 0xFF) << 8);
+            const uint32_t c1 = ((lo[b][1] >> (8 * j)) & 0xFF) | (((hi1 >> (8 * j)) & 0xFF) << 8);
+            if (c0 != out[8 * b + j] || c1 != out[8 * b + 4 + j]) out[8 * b + j] = 0xFFFFFFFEu;
+        }
+    }
+}
+
+template <typename F>
+static int emul_with_planes(int planes, F &&f) {  // the plane counts the kernels are instantiated with
+    switch (planes) {
+        case 8: f(std::integral_constant<int, 8>{}); return 0;
+        case 10: f(std::integral_constant<int, 10>{}); return 0;
+        case 11: f(std::integral_constant<int, 11>{}); return 0;
+        case 12: f(std::integral_constant<int, 12>{}); return 0;
+        case 16: f(std::integral_constant<int, 16>{}); return 0;
+    }
+    return -1;
+}
+
 extern "C" {
+
+void emul_merge_bytes(const uint32_t *sb, uint32_t *st);
 
 // The arithmetic of the two-level bounds pass (rtx_bounds2.hip) on one 32-counter column: the rows are dealt to `groups` lane groups as the
 // load instructions deal them (unit of 8 * groups rows: group g takes rows 8 g .. 8 g + 7 of the unit), every group folds its own (tree8 +
@@ -52,62 +134,74 @@ uint32_t emul_planes_grouped(const uint32_t *rows, uint32_t n_rows, uint32_t gro
     return (m << 8) | (uint32_t)__builtin_ctz(cand);
 }
 
-// rows: n_rows x 1 words (one 32-reference column).  n_rows must be a multiple of 8.
-// out: 32 counters.
-void emul_planes_count(const uint32_t *rows, uint32_t n_rows, int planes, uint32_t *out) {
-    auto run = [&](auto tag) {
+// rows: n_rows x 1 words (one 32-reference column).  n_rows must be a multiple of 8; planes 8, 10, 11, 12 or 16; sched 32 or 24
+// (emul_fold).  out: 32 counters.  Returns 0, or -1 for arguments it does not cover (out untouched).
+int emul_planes_count_sched(const uint32_t *rows, uint32_t n_rows, int planes, int sched, uint32_t *out) {
+    if ((n_rows & 7u) || (sched != 32 && sched != 24)) return -1;
+    return emul_with_planes(planes, [&](auto tag) {
         constexpr int NP = decltype(tag)::value;
         uint32_t pl[NP];
         for (int p = 0; p < NP; p++) pl[p] = 0;
-        uint32_t r = 0;
-        // the kernel's schedule: 32 rows = four tree8 + two CSAs on plane 3 + one on plane 4 + ripple
-        for (; r + 32 <= n_rows; r += 32) {
-            auto t8 = [&](uint32_t o) {
-                return planes_tree8<NP>(pl, rows[o], rows[o + 1], rows[o + 2], rows[o + 3], rows[o + 4], rows[o + 5],
-                                        rows[o + 6], rows[o + 7]);
-            };
-            uint32_t c3a = t8(r), c3b = t8(r + 8), c4a, c4b, c5;
-            csa(pl[3], c3a, c3b, pl[3], c4a);
-            c3a = t8(r + 16);
-            c3b = t8(r + 24);
-            csa(pl[3], c3a, c3b, pl[3], c4b);
-            csa(pl[4], c4a, c4b, pl[4], c5);
-            planes_ripple<NP, 5>(pl, c5);
+        emul_fold<NP>(pl, rows, n_rows, sched);
+        emul_unpack<NP>(pl, out);
+    });
+}
+void emul_planes_count(const uint32_t *rows, uint32_t n_rows, int planes, uint32_t *out) {
+    emul_planes_count_sched(rows, n_rows, planes, 32, out);
+}
+
+// planes_gt on the planes that hold the 32 counters `counts` (each < 2^planes): bit r = counts[r] > c.  *mask; returns 0 / -1 as above.
+int emul_planes_gt(const uint32_t *counts, int planes, uint32_t c, uint32_t *mask) {
+    return emul_with_planes(planes, [&](auto tag) {
+        constexpr int NP = decltype(tag)::value;
+        uint32_t pl[NP];
+        for (int p = 0; p < NP; p++) {
+            pl[p] = 0;
+            for (int r = 0; r < 32; r++) pl[p] |= ((counts[r] >> p) & 1u) << r;
         }
-        for (; r + 8 <= n_rows; r += 8)
-            planes_add8<NP>(pl, rows[r], rows[r + 1], rows[r + 2], rows[r + 3], rows[r + 4], rows[r + 5], rows[r + 6],
-                            rows[r + 7]);
-        for (int g = 0; g < 8; g++) {
-            uint32_t lo, hi;
-            planes_unpack4<NP>(pl, g, lo, hi);
-            for (int j = 0; j < 4; j++) out[4 * g + j] = ((lo >> (8 * j)) & 0xFF) | (((hi >> (8 * j)) & 0xFF) << 8);
+        *mask = planes_gt<NP>(pl, c);
+    });
+}
+
+// The counts of one 32-reference word of a (query, tile) as kmer_extract and the epilogue of hit_count make them: of the rows flagged
+// sparse the first kSegMaxSparseRows go through byte counters -- word-wide adds of 1 << 8 (r & 3), as the LDS atomics of sparse_hits:
+// a 256th hit would carry into the neighbour's byte -- the rest and every dense row are folded into the planes (padded to eight with
+// the zero row); then the merge: planes 8 the byte form of hit_epilogue_x (lo + sb, word-wide), else the SWAR merge (emul_merge_bytes).
+int emul_tile_word_counts(const uint32_t *rows, const uint8_t *sparse, uint32_t n_rows, int planes, int sched, uint32_t *out) {
+    uint32_t cnt8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    std::vector<uint32_t> dense;
+    uint32_t ns = 0;
+    for (uint32_t i = 0; i < n_rows; i++) {
+        if (sparse[i] && ns < kSegMaxSparseRows) {
+            ns++;
+            for (uint32_t r = 0; r < 32; r++)
+                if ((rows[i] >> r) & 1u) cnt8[r >> 2] += 1u << ((r & 3u) * 8u);
+        } else {
+            dense.push_back(rows[i]);
         }
-        // the eight-at-a-time unpack of the epilogue (bit-matrix transpose) must give the same counters
-        for (int b = 0; b < 4; b++) {
-            uint32_t lo0, hi0, lo1, hi1;
-            planes_unpack8<NP>(pl, b, lo0, hi0, lo1, hi1);
-            for (int j = 0; j < 4; j++) {
-                const uint32_t c0 = ((lo0 >> (8 * j)) & 0xFF) | (((hi0 >> (8 * j)) & 0xFF) << 8);
-                const uint32_t c1 = ((lo1 >> (8 * j)) & 0xFF) | (((hi1 >> (8 * j)) & 0xFF) << 8);
-                if (c0 != out[8 * b + j] || c1 != out[8 * b + 4 + j]) out[8 * b + j] = 0xFFFFFFFFu;  // poison: the test fails
-            }
-        }
-        // ... and so must the unpack of the whole word at once (delta swaps between the plane registers)
+    }
+    dense.resize((dense.size() + 7u) / 8u * 8u, 0u);
+    return emul_with_planes(planes, [&](auto tag) {
+        constexpr int NP = decltype(tag)::value;
+        uint32_t pl[NP];
+        for (int p = 0; p < NP; p++) pl[p] = 0;
+        emul_fold<NP>(pl, dense.data(), (uint32_t)dense.size(), sched);
         uint32_t lo[4][2];
         planes_unpack32<NP>(pl, lo);
-        for (int b = 0; b < 4; b++) {
-            uint32_t hi0, hi1;
-            planes_unpack8_hi<NP>(pl, b, hi0, hi1);
-            for (int j = 0; j < 4; j++) {
-                const uint32_t c0 = ((lo[b][0] >> (8 * j)) & 0xFF) | (((hi0 >> (8 * j)) & 0xFF) << 8);
-                const uint32_t c1 = ((lo[b][1] >> (8 * j)) & 0xFF) | (((hi1 >> (8 * j)) & 0xFF) << 8);
-                if (c0 != out[8 * b + j] || c1 != out[8 * b + 4 + j]) out[8 * b + j] = 0xFFFFFFFEu;
+        for (int b = 0; b < 4; b++) {  // references 8 b .. 8 b + 7: byte counters cnt8[2 b], cnt8[2 b + 1]
+            if (NP <= 8) {
+                const uint32_t w[2] = {lo[b][0] + cnt8[2 * b], lo[b][1] + cnt8[2 * b + 1]};
+                for (int j = 0; j < 8; j++) out[8 * b + j] = (w[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
+            } else {
+                uint32_t hi0, hi1;
+                planes_unpack8_hi<NP>(pl, b, hi0, hi1);
+                uint32_t st[4] = {byte_perm(hi0, lo[b][0], 0x05010400u), byte_perm(hi0, lo[b][0], 0x07030602u),
+                                  byte_perm(hi1, lo[b][1], 0x05010400u), byte_perm(hi1, lo[b][1], 0x07030602u)};
+                emul_merge_bytes(&cnt8[2 * b], st);
+                for (int j = 0; j < 8; j++) out[8 * b + j] = (st[j >> 1] >> ((j & 1) * 16)) & 0xFFFFu;
             }
         }
-    };
-    if (planes == 10) run(std::integral_constant<int, 10>{});
-    else if (planes == 12) run(std::integral_constant<int, 12>{});
-    else run(std::integral_constant<int, 16>{});
+    });
 }
 
 // Sequential emulation of prob_table_kernel (same lane grouping, pruning and arithmetic; only the

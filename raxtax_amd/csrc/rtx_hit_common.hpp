@@ -560,18 +560,7 @@ __device__ __forceinline__ void hit_epilogue_x(const HitParams &p, uint32_t (&pl
 //   count = dense part (planes) + sparse part (byte counters, at most smax): candidates = dense > u - smax, then the exact test.
 // Reference order: group g, lane l, reference j <-> local reference (g * L + l) * 8 + j (ref_slot): ascending in (g, l, j).
 // ---------------------------------------------------------------------------
-template <int NP>
-__device__ __forceinline__ uint32_t planes_gt(const uint32_t (&pl)[NP], uint32_t c) {  // bit r: counter r of the word > c (c < 2^NP)
-    uint32_t gt = 0, eq = 0xFFFFFFFFu;
-#pragma unroll
-    for (int b = NP - 1; b >= 0; b--) {
-        const uint32_t cb = (c >> b) & 1u ? 0xFFFFFFFFu : 0u;  // scalar
-        gt |= eq & pl[b] & ~cb;
-        eq &= ~(pl[b] ^ cb);
-    }
-    return gt;
-}
-
+// (planes_gt: rtx_math.hpp)
 // raxtax.rs:65-68 on the bit planes: the counters of this query's exact matches in this tile are cleared (the dense part)
 template <int NP>
 __device__ __forceinline__ void zero_exact_dense(const HitParams &p, uint32_t (&pl)[4][NP], uint32_t q, uint32_t tile, uint32_t lane, uint32_t L) {
@@ -644,8 +633,8 @@ __device__ __forceinline__ void rec_epilogue(const HitParams &p, uint32_t (&pl)[
         smax = wave_max_u32((orw | (orw >> 8)) & 0xFFu);  // at least every byte counter of the tile
     }
     if (active && skip_exact) zero_exact_dense<NP>(p, pl, q, tile, lane, L);
-    // candidates: a count above u needs a dense part above u - smax; with smax > u (never seen: a reference in more than u sparse
-    // segments) every reference is one
+    // candidates: a count above u needs a dense part above u - smax; with smax > u (a reference in more than u sparse
+    // segments: tests/test_gpu_saturated_counts.py runs it) every reference is one
     uint32_t gt[4];
     {
         const bool all = smax > h_thr;  // wave-uniform

@@ -20,8 +20,7 @@ constexpr uint32_t kWalkMaxRows = 208;
 // segment classes (rtx_segments.hip): a (row, tile) segment with at most kSegSparseMax references is kept as a
 // slot of kSegSlotEntries local ids (on the bench workload 31.0 % of the requested segments hold <= 16 references,
 // 31.3 % <= 32); a (query, tile) pair takes at most kSegMaxSparseRows such segments through the
-// byte counters of hit_count (more are read as dense segments)
-constexpr uint32_t kSegSlotEntries = 16, kSegSparseMax = 16, kSegMaxSparseRows = 255;
+// byte counters of hit_count (more are read as dense segments): kSegSlotEntries, kSegSparseMax, kSegMaxSparseRows (rtx_math.hpp)
 // unused entry i of a slot: local id kSegPad + 4 (i mod 64) -- 64 different pad words behind the byte counters of hit_count, so that
 // the LDS atomics of the unused entries of a wave-instruction do not all hit one address (no compare, no exec mask per atomic)
 constexpr uint32_t kSegPad = 8192;

@@ -14,6 +14,10 @@
 
 namespace rtx {
 
+// segment classes (rtx_kernels.hpp): entries of a slot, the most references of a sparse (row, tile) segment, the most sparse segments
+// of a (query, tile) -- here because the CPU emulation of the epilogue's merge (rtx_emul.cpp) applies the same cap
+constexpr uint32_t kSegSlotEntries = 16, kSegSparseMax = 16, kSegMaxSparseRows = 255;
+
 // ---------------------------------------------------------------------------
 // Bit-sliced ("vertical") counters.
 //
@@ -486,6 +490,20 @@ RTX_HD uint32_t planes_max(const uint32_t (&r)[NP], uint32_t &cand) {
         m |= nz ? 1u << p : 0u;
     }
     return m;
+}
+
+// bit r: counter r of the bit-sliced word is > c (c < 2^NP) -- a comparison with a constant from the top plane down, ~3 operations
+// per plane (rec_epilogue, rtx_hit_common.hpp: the candidates above a pruned query's threshold)
+template <int NP>
+RTX_HD uint32_t planes_gt(const uint32_t (&pl)[NP], uint32_t c) {
+    uint32_t gt = 0, eq = 0xFFFFFFFFu;
+#pragma unroll
+    for (int b = NP - 1; b >= 0; b--) {
+        const uint32_t cb = (c >> b) & 1u ? 0xFFFFFFFFu : 0u;  // scalar
+        gt |= eq & pl[b] & ~cb;
+        eq &= ~(pl[b] ^ cb);
+    }
+    return gt;
 }
 
 // Spreads the 4 bits x[3:0] into the low bit of the 4 bytes of the result.

@@ -23,6 +23,132 @@ def test_bit_planes_exact(emul, planes, n_rows, density):
     assert np.array_equal(out, bits.sum(axis=0).astype(np.uint32))
 
 
+ALL_PLANES = (8, 10, 11, 12, 16)     # every plane count the counting kernels are instantiated with
+
+
+def _column_words(col_counts, n_rows, rng=None):
+    """n_rows words whose column r is set in exactly col_counts[r] rows: the first ones, or (rng) a random choice of them."""
+    bits = np.zeros((n_rows, 32), bool)
+    for r, c in enumerate(col_counts):
+        assert 0 <= c <= n_rows
+        idx = np.arange(c) if rng is None else rng.choice(n_rows, c, replace=False)
+        bits[idx, r] = True
+    rows = (bits.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32)
+    return bits, np.ascontiguousarray(rows)
+
+
+def _planes_count(emul, rows, planes, sched):
+    out = np.zeros(32, dtype=np.uint32)
+    emul.emul_planes_count_sched.restype = C.c_int
+    rc = emul.emul_planes_count_sched(rows.ctypes.data_as(C.c_void_p), C.c_uint32(len(rows)), planes, sched, out.ctypes.data_as(C.c_void_p))
+    assert rc == 0
+    return out
+
+
+@pytest.mark.parametrize("sched", [32, 24])
+@pytest.mark.parametrize("planes", ALL_PLANES)
+def test_bit_planes_saturated_and_carry_columns(emul, planes, sched):
+    """Counts where a plane adder goes wrong unnoticed by random densities: a column set in all 2^NP - 1 rows (every plane set) beside
+    an empty one and one of 2^NP - 2, and columns on either side of every carry boundary (2^k - 1, 2^k for every k < NP) -- through
+    the 32-row schedule of hit_count and the 24-row schedule of the pair kernel, the three unpack forms agreeing (a poisoned counter
+    fails the comparison)."""
+    full = (1 << planes) - 1
+    n_rows = (full + 7) // 8 * 8
+    cols = [full, 0, full - 1]
+    for k in range(planes):
+        cols += [(1 << k) - 1, 1 << k]
+    assert len(cols) == 3 + 2 * planes
+    for rng in (None, np.random.default_rng(planes * 100 + sched)):     # the set rows in front (every carry chain at once), then scattered
+        for a in range(3, len(cols), 29):                               # 32 columns per word: the saturated three beside every chunk
+            chunk = (cols[:3] + cols[a:a + 29] + [0] * 32)[:32]
+            bits, rows = _column_words(chunk, n_rows, rng)
+            want = bits.sum(axis=0).astype(np.uint32)
+            assert list(want) == chunk
+            assert np.array_equal(_planes_count(emul, rows, planes, sched), want)
+
+
+@pytest.mark.parametrize("sched", [32, 24])
+@pytest.mark.parametrize("planes", ALL_PLANES)
+def test_bit_planes_every_row_count_residue(emul, planes, sched):
+    """n_rows at every residue of 8 modulo 24 and modulo 32 (the tails of both schedules; the pair kernel pads its last group with the
+    zero row), from no full group to several, every column full -- the count equals n_rows, the largest it can be."""
+    top = min(255 if planes == 8 else 1 << 30, (1 << planes) - 1)
+    rng = np.random.default_rng(planes)
+    for n_rows in [n for n in range(0, 224, 8) if n <= top]:       # 0 .. 216: every residue of 8 mod 24 and mod 32 at least twice
+        bits = rng.random((n_rows, 32)) < 0.9
+        bits[:, 0] = True                                             # a column that holds every row
+        rows = np.ascontiguousarray((bits.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32))
+        got = _planes_count(emul, rows, planes, sched)
+        assert np.array_equal(got, bits.sum(axis=0).astype(np.uint32)), n_rows
+        assert got[0] == n_rows
+    assert {n % 24 for n in range(0, 224, 8)} == {0, 8, 16} and {n % 32 for n in range(0, 224, 8)} == {0, 8, 16, 24}
+
+
+def test_bit_planes_refuse_what_they_do_not_cover(emul):
+    rows = np.zeros(8, np.uint32)
+    out = np.full(32, 7, np.uint32)
+    emul.emul_planes_count_sched.restype = C.c_int
+    for planes, n, sched in ((9, 8, 32), (10, 7, 32), (10, 8, 16)):
+        assert emul.emul_planes_count_sched(rows.ctypes.data_as(C.c_void_p), C.c_uint32(n), planes, sched, out.ctypes.data_as(C.c_void_p)) == -1
+    assert (out == 7).all()
+
+
+@pytest.mark.parametrize("planes", ALL_PLANES)
+def test_planes_gt_against_the_counts(emul, planes):
+    """planes_gt (rec_epilogue's candidates above a threshold, rtx_math.hpp) against counts > c, on columns of 0, c - 1, c, c + 1 and
+    2^NP - 1, for c on either side of every carry boundary and at both ends."""
+    full = (1 << planes) - 1
+    cs = {0, 1, full - 1, full}
+    for k in range(planes):
+        cs |= {(1 << k) - 1, 1 << k}
+    emul.emul_planes_gt.restype = C.c_int
+    rng = np.random.default_rng(planes)
+    for c in sorted(cs):
+        special = [v for v in (0, c - 1, c, c + 1, full) if 0 <= v <= full]
+        counts = np.array((special * 16)[:32], np.uint32)
+        counts[10:] = rng.permutation(counts[10:])                  # every special value at several bit positions
+        counts[-6:] = rng.integers(0, full + 1, 6)
+        mask = C.c_uint32()
+        assert emul.emul_planes_gt(counts.ctypes.data_as(C.c_void_p), planes, C.c_uint32(c), C.byref(mask)) == 0
+        want = sum(1 << r for r in range(32) if counts[r] > c)
+        assert mask.value == want, (c, counts.tolist(), hex(mask.value), hex(want))
+        assert c in counts.tolist() and (c == full or c + 1 in counts.tolist())   # the values the comparison must tell apart were there
+
+
+def _tile_word_counts(emul, rows, sparse, planes, sched=32):
+    out = np.zeros(32, np.uint32)
+    emul.emul_tile_word_counts.restype = C.c_int
+    sp = np.ascontiguousarray(sparse, np.uint8)
+    assert emul.emul_tile_word_counts(rows.ctypes.data_as(C.c_void_p), sp.ctypes.data_as(C.c_void_p), C.c_uint32(len(rows)), planes, sched,
+                                      out.ctypes.data_as(C.c_void_p)) == 0
+    return out
+
+
+@pytest.mark.parametrize("planes,n_sparse", [(p, n) for p in ALL_PLANES for n in (0, 1, 127, 254, 255, 256, 300)
+                                             if p > 8 or n <= 255])     # (eight planes: t <= 255, a query has no more rows)
+def test_sparse_cap_and_dense_remainder_of_a_tile_word(emul, planes, n_sparse):
+    """The counts of a (query, tile) word as the kernels split them: at most kSegMaxSparseRows = 255 sparse segments through byte
+    counters, the rest and the dense rows through the planes, then the merge (eight planes: the byte-wise add).  A reference that
+    sits in every sparse row reaches the cap exactly at 255 -- handled as 256, its byte counter wraps and carries into its
+    neighbour's, which holds a count that is checked."""
+    full = (1 << planes) - 1
+    n_dense = min(full, 1023) - n_sparse         # reference 5 ends at the largest count of the class (1023 beyond ten planes)
+    n = n_sparse + n_dense
+    bits = np.zeros((n, 32), bool)
+    sparse = np.zeros(n, np.uint8)
+    sparse[:n_sparse] = 1
+    bits[:n_sparse, 4] = True           # reference 4: in every sparse row and no dense one (0 + 255 at the cap)
+    bits[:, 5] = True                   # its neighbour in the word: every row (dense + sparse = the largest count)
+    bits[n_sparse:, 6] = True           # dense rows only
+    bits[:min(n_sparse, 1), 7] = True   # one sparse row
+    bits[::3, 9] = True
+    bits[:n_sparse:2, 2] = True
+    rows = np.ascontiguousarray((bits.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32))
+    for sched in (32, 24):
+        got = _tile_word_counts(emul, rows, sparse, planes, sched)
+        assert np.array_equal(got, bits.sum(axis=0).astype(np.uint32)), (got.tolist(), bits.sum(axis=0).tolist())
+
+
 @pytest.mark.parametrize("groups,n_rows,density", [(4, 1024, 0.3), (16, 1024, 0.9), (4, 128, 0.02), (16, 896, 0.5)])
 def test_grouped_bit_planes_of_the_two_level_bounds(emul, groups, n_rows, density):
     """rtx_bounds2.hip: R lane groups fold different rows of the same columns, their bit-sliced partial counters are added pairwise
@@ -165,6 +291,26 @@ def test_epilogue_byte_merge_and_transpose(emul):
         st = cnt.view(np.uint32).copy()
         emul.emul_merge_bytes(sb.view(np.uint32).ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p))
         assert np.array_equal(st.view(np.uint16), cnt + sb)
+    # the saturated cases: a byte counter of 255 on a count with low byte 0 and high bits 3 (0x300 -> 0x3FF: nothing may reach the
+    # neighbour), a count of 0xFF that gets nothing beside neighbours that do, all eight at once
+    for sb, cnt in (([255, 0, 255, 1, 0, 255, 255, 255], [0x300, 0xFF, 0x300, 0xFE, 0xFF, 0x300, 0, 0x300]),
+                    ([0, 255, 0, 255, 0, 255, 0, 255], [0xFF, 0x300, 0x3FF, 0x300, 0xFF, 0x2FF, 0xFFFF, 0]),
+                    ([255] * 8, [0x300] * 8), ([0] * 8, [0xFF] * 8), ([255] * 8, [0] * 8)):
+        sb, cnt = np.array(sb, np.uint8), np.array(cnt, np.uint16)
+        st = cnt.view(np.uint32).copy()
+        emul.emul_merge_bytes(sb.view(np.uint32).ctypes.data_as(C.c_void_p), st.ctypes.data_as(C.c_void_p))
+        assert np.array_equal(st.view(np.uint16).astype(np.uint32), cnt.astype(np.uint32) + sb), (sb.tolist(), cnt.tolist())
+    # the byte form of the eight-plane epilogue (lo8 = lo + sb, word-wide): all eight references of a group at dense + sparse = 255
+    # exactly, in every split -- no carry leaves a byte
+    splits = [255, 0, 128, 127, 1, 254, 255, 0]                      # sparse part of references 8 .. 15; the dense part is the rest
+    bits = np.zeros((510, 32), bool)                                  # rows 0 .. 254 sparse, 255 .. 509 dense
+    for j, sp in enumerate(splits):
+        bits[:sp, 8 + j] = True
+        bits[255:255 + 255 - sp, 8 + j] = True
+    bits[:255:2, 3] = True
+    rows = np.ascontiguousarray((bits.astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32))
+    got = _tile_word_counts(emul, rows, np.arange(510) < 255, 8)
+    assert (got[8:16] == 255).all() and np.array_equal(got, bits.sum(axis=0).astype(np.uint32))
     m = rng.integers(0, 2, (64, 64)).astype(np.uint64)
     rows = (m << np.arange(64, dtype=np.uint64)[None, :]).sum(axis=1).astype(np.uint64)
     cols = np.zeros(64, np.uint64)

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import raxtax_amd as rx
+from debruijn_common import de_bruijn_4_8 as _de_bruijn_4_8
 from gpu_common import check_properties
 from raxtax_amd import synth
 from raxtax_amd.checks import assert_rows_equivalent
@@ -118,29 +119,6 @@ def test_coi_reads_with_long_and_short_reads_in_one_batch(oracle):
     for q in list(ids_long) + list(ids_coi[:100]) + list(ids_short[:30]):
         a, b = plain.rows(int(q)), res.rows(int(q))
         assert [x.lineage for x in a] == [x.lineage for x in b] and [x.confidence_values for x in a] == [x.confidence_values for x in b], int(q)
-
-
-def _de_bruijn_4_8():
-    """B(4, 8) as encoded bases (1, 2, 4, 8), linearised: 4^8 + 7 bases that hold every 8-mer once (the standard Lyndon-word construction)."""
-    k, n = 4, 8
-    a = [0] * (k * n)
-    seq = []
-
-    def db(t, p):
-        if t > n:
-            if n % p == 0:
-                seq.extend(a[1:p + 1])
-        else:
-            a[t] = a[t - p]
-            db(t + 1, p)
-            for j in range(a[t - p] + 1, k):
-                a[t] = j
-                db(t + 1, t)
-    import sys
-    sys.setrecursionlimit(10000)
-    db(1, 1)
-    seq = seq + seq[:n - 1]
-    return (1 << np.array(seq, np.uint8)).astype(np.uint8)
 
 
 def test_reads_up_to_the_reference_limit(oracle):
