@@ -46,7 +46,8 @@ extern "C" {
                                 and with primer trimming, rtx_trim_* / rtx_primer_search / rtx_index_set_primers / rtx_raxtax_last_trim /
                                 rtx_raxtax_multi_ex4: exports and a setting that is off by default; and with FASTQ and the quality filter,
                                 rtx_queries_parse_fastq* / rtx_fastq_block_end / rtx_queries_quals / rtx_qual_* / rtx_index_set_quality /
-                                rtx_raxtax_last_qual / rtx_raxtax_multi_ex5: the same) */
+                                rtx_raxtax_last_qual / rtx_raxtax_multi_ex5: the same; and with paired-end merging, rtx_merge_* /
+                                rtx_queries_merge_report / rtx_fastq_block_end_n: exports only) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -682,6 +683,75 @@ int rtx_qual_read(const rtx_qual_params *params, const uint8_t *bases, const uin
 int rtx_index_set_quality(rtx_index *index, const rtx_qual_params *params);
 int rtx_index_quality(const rtx_index *index, rtx_qual_params *params, int *on);
 int rtx_raxtax_last_qual(uint64_t *queries, uint64_t *passed, uint64_t *truncated, uint64_t reasons[7], double *busy_seconds);
+
+/* ---- paired-end merging (rtx_merge.hip; host_merge.cpp has the host function) ---------------------------------------------------------------
+ * The first step of an amplicon pipeline (`vsearch --fastq_mergepairs`, PEAR, DADA2 `mergePairs`) on the device: the two mates of a pair
+ * overlapped into one read.  Exact integers, no tolerance anywhere; the host function, the x86 emulator and the device agree bit for bit.
+ * Still ABI 6: exports only, nothing that exists changes.
+ *   per pair     the forward mate F (nf base codes and raw quality bytes) and the reverse mate R (nr of each).  Codes are the 4-bit codes of
+ *                the parsers (A=1, C=2, G=4, T=8, IUPAC codes as unions, 0 for anything else; a byte above 15 counts as 0).  R' is the
+ *                reverse complement of R as rtx_revcomp defines it, its quality bytes reversed.  Q = byte - ascii_base.
+ *   parameters   ascii_base 33 (33 or 64), min_overlap 16 (at least 1), max_diffs 10, max_diff_pct 100 (0 .. 100), q_cap 41 (0 .. 93);
+ *                RTX_ERR_INVALID otherwise.  The cost of a mismatch is the constant RTX_MERGE_MISMATCH_COST.
+ *   verdict      the first of these that applies, and only that one: RTX_MG_BAD_QUALITY -- a byte of either mate, anywhere, with Q outside
+ *                0 .. 93; RTX_MG_TOO_LONG -- a mate of more than RTX_MERGE_MAX_READ bases; RTX_MG_TOO_SHORT -- a mate of fewer than
+ *                min_overlap bases; RTX_MG_NO_OVERLAP -- no candidate is accepted; 0 -- merged.  A pair that is not merged has overlap =
+ *                diffs = 0 and the empty merged read.
+ *   candidates   no gaps, no staggered alignments: ov = min_overlap .. min(nf, nr), F[nf - ov + i] against R'[i] for i in [0, ov).  d(ov) is
+ *                the number of positions with (a & b) == 0, score = ov - RTX_MERGE_MISMATCH_COST * d.  A candidate is accepted iff
+ *                d <= max_diffs, 100 * d <= max_diff_pct * ov and score >= min_overlap.  The largest score wins, among equal scores the
+ *                larger ov.
+ *   merged read  nf + nr - ov bases under the forward mate's label.  In front of the overlap F, behind it R', codes and quality bytes as
+ *                they are.  Inside, with a, qa of F and b, qb of R':  a == b and a != 0: code a, Q = max(max(qa, qb), min(qa + qb, q_cap));
+ *                otherwise (a & b) != 0: code a & b, Q = max(qa, qb); otherwise (a diff): the code of the mate with the larger Q, the forward
+ *                one on a tie, Q = max(|qa - qb|, 2).  The quality byte is ascii_base + Q: the quality filter reads a merged read like any
+ *                FASTQ read.  Never depends on the rest of the batch.
+ *   rtx_merge_create   an object of its own on GPU `device` like rtx_qual: one stream, its own buffers (they only grow), no rtx_index.
+ *                Checked in this order: null arguments, the parameters (RTX_ERR_INVALID), the device (RTX_ERR_NO_DEVICE without a gfx950).
+ *   rtx_merge_run      n pairs as two (bases, quals, base_off) triples, base_off [n + 1] each as rtx_batch_prefetch takes it.  overlap / diffs /
+ *                verdict / merged_len: [n] each.  The merged read of pair i lies at slot_off[i] of merged_bases and of merged_quals; the slot
+ *                of a pair has (nf + nr rounded up to 16) bytes, slot_off [n + 1] is written by the call, and slot_cap -- the bytes of each of
+ *                the two arrays -- must be at least slot_off[n]; what lies in a slot behind its merged read is undefined.  One byte per base
+ *                code and one per quality byte travel to the device, as given.  n == 0: RTX_OK; RTX_ERR_INVALID: offsets that are not
+ *                monotone, a mate of 2^31 bases or more, a quality byte of 128 or more, slots that do not fit.  Synchronous; calls on one
+ *                object are serialised by the caller.
+ *   rtx_merge_stage_times  seconds of the last rtx_merge_run: the host's staging pass, the copies and the wait around the kernel, all of it.
+ *   rtx_merge_pair     the same for ONE pair on the host (no device), the candidates one after the other through the functions the kernel
+ *                calls; merged_bases / merged_quals take nf + nr bytes (needed only when the pair merges).
+ *   rtx_merge_queries  two handles of FASTQ parses with equal record counts (the forward and the reverse file, or blocks of them cut at the
+ *                same record: rtx_fastq_block_end_n) -> a new handle with the forward labels, the merged bases and the merged quality bytes,
+ *                on which rtx_queries_data / _quals / _label / _len work as on any other; a pair that is not merged becomes the empty read;
+ *                pairs whose forward label is in `skip` are dropped.  The labels of the two mates must be equal up to their first blank,
+ *                after a final /1 of the forward and /2 of the reverse label is taken off: RTX_ERR_PARSE otherwise -- as for record counts
+ *                that differ -- with the number of the pair (from 1) in rtx_last_error.  The pairing is checked before the stage is
+ *                looked at (a NULL stage: RTX_ERR_INVALID).
+ *   rtx_queries_merge_report  nf, nr, overlap, diffs and verdict of every pair of such a handle, owned by it; RTX_ERR_STATE for another handle.
+ *   rtx_fastq_block_end_n  as rtx_fastq_block_end, but behind the last whole record among the first max_records; *n_records: how many that
+ *                is.  Two files read piecewise are cut at the same record with it. */
+#define RTX_MERGE_MAX_READ 1024u
+#define RTX_MERGE_MISMATCH_COST 5
+#define RTX_MG_BAD_QUALITY 1u
+#define RTX_MG_TOO_LONG 2u
+#define RTX_MG_TOO_SHORT 4u
+#define RTX_MG_NO_OVERLAP 8u
+typedef struct {
+    uint32_t ascii_base, min_overlap, max_diffs, max_diff_pct, q_cap;
+} rtx_merge_params;
+typedef struct rtx_merge rtx_merge;
+int rtx_merge_create(int device, const rtx_merge_params *params, rtx_merge **out);
+int rtx_merge_run(rtx_merge *m, uint64_t n, const uint8_t *f_bases, const uint8_t *f_quals, const uint64_t *f_off, const uint8_t *r_bases,
+                  const uint8_t *r_quals, const uint64_t *r_off, uint32_t *overlap /*[n]*/, uint32_t *diffs /*[n]*/, uint32_t *verdict /*[n]*/,
+                  uint32_t *merged_len /*[n]*/, uint64_t *slot_off /*[n + 1]*/, uint8_t *merged_bases, uint8_t *merged_quals, uint64_t slot_cap);
+void rtx_merge_destroy(rtx_merge *m);
+int rtx_merge_kernel_time(const rtx_merge *m, float *ms); /* milliseconds of the kernel of the last rtx_merge_run, from HIP events around it */
+int rtx_merge_stage_times(const rtx_merge *m, double seconds[3]);
+int rtx_merge_pair(const rtx_merge_params *params, const uint8_t *f_bases, const uint8_t *f_quals, uint32_t nf, const uint8_t *r_bases,
+                   const uint8_t *r_quals, uint32_t nr, uint32_t *overlap, uint32_t *diffs, uint32_t *verdict, uint32_t *merged_len,
+                   uint8_t *merged_bases, uint8_t *merged_quals);
+int rtx_merge_queries(rtx_merge *m, const rtx_queries *fwd, const rtx_queries *rev, const char *const *skip, uint64_t n_skip, rtx_queries **merged);
+int rtx_queries_merge_report(const rtx_queries *merged, const uint32_t **nf, const uint32_t **nr, const uint32_t **overlap, const uint32_t **diffs,
+                             const uint32_t **verdict);
+uint64_t rtx_fastq_block_end_n(const char *text, uint64_t len, uint64_t max_records, uint64_t *n_records);
 
 /* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
  * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte

@@ -10,7 +10,9 @@ from .api import (EvaluationResult, Index, Result, Tree, parse_query_fasta_str, 
                   raxtax, raxtax_last_timing, NO_REF, NO_DIST, semiglobal_distance, Profile, profile_merge, profile_text, Derep, derep_plan, raxtax_last_derep,
                   Trim, TrimPrimer, primer_patterns, primer_search, trim_apply, trim_hit, encode_iupac, raxtax_last_trim, TRIM_5P, TRIM_3P, TRIM_NO_PATTERN,
                   parse_query_fastq_str, Qual, QualParams, qual_read, qual_error_table, qual_verdict_names, raxtax_last_qual, QUAL_MAX_READ,
-                  QC_BAD_QUALITY, QC_SHORT_FOR_TRUNC_LEN, QC_TOO_SHORT, QC_TOO_LONG, QC_TOO_MANY_N, QC_MAX_EE, QC_MAX_EE_RATE)
+                  QC_BAD_QUALITY, QC_SHORT_FOR_TRUNC_LEN, QC_TOO_SHORT, QC_TOO_LONG, QC_TOO_MANY_N, QC_MAX_EE, QC_MAX_EE_RATE,
+                  Merge, MergeParams, merge_pair, merge_queries, merge_verdict_names, fastq_text, fastq_block_end_n, MERGE_MAX_READ,
+                  MG_BAD_QUALITY, MG_TOO_LONG, MG_TOO_SHORT, MG_NO_OVERLAP)
 from ._lib import (RTX_RAW_CONFIDENCE, RTX_SKIP_EXACT_MATCHES, RtxError)  # noqa: F401
 
 __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last_timing", "parse_reference_fasta_str",
@@ -18,4 +20,6 @@ __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last
            "Profile", "profile_merge", "profile_text", "Derep", "derep_plan", "raxtax_last_derep",
            "Trim", "TrimPrimer", "primer_patterns", "primer_search", "trim_apply", "trim_hit", "encode_iupac", "raxtax_last_trim", "TRIM_5P", "TRIM_3P",
            "TRIM_NO_PATTERN", "parse_query_fastq_str", "Qual", "QualParams", "qual_read", "qual_error_table", "qual_verdict_names", "raxtax_last_qual",
-           "QUAL_MAX_READ", "QC_BAD_QUALITY", "QC_SHORT_FOR_TRUNC_LEN", "QC_TOO_SHORT", "QC_TOO_LONG", "QC_TOO_MANY_N", "QC_MAX_EE", "QC_MAX_EE_RATE"]
+           "QUAL_MAX_READ", "QC_BAD_QUALITY", "QC_SHORT_FOR_TRUNC_LEN", "QC_TOO_SHORT", "QC_TOO_LONG", "QC_TOO_MANY_N", "QC_MAX_EE", "QC_MAX_EE_RATE",
+           "Merge", "MergeParams", "merge_pair", "merge_queries", "merge_verdict_names", "fastq_text", "fastq_block_end_n", "MERGE_MAX_READ",
+           "MG_BAD_QUALITY", "MG_TOO_LONG", "MG_TOO_SHORT", "MG_NO_OVERLAP"]

@@ -31,6 +31,9 @@ RTX_TRIM_MAX_PATTERNS, RTX_TRIM_MAX_PATTERN, RTX_TRIM_MAX_WINDOW, RTX_TRIM_NO_PA
 RTX_QUAL_MAX_READ, RTX_QUAL_TABLE = 1 << 20, 94
 RTX_QC_NAMES = ("bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate")   # bit b of a verdict: RTX_QC_*
 
+RTX_MERGE_MAX_READ, RTX_MERGE_MISMATCH_COST = 1024, 5
+RTX_MG_NAMES = ("bad_quality", "too_long", "too_short", "no_overlap")   # bit b of a verdict: RTX_MG_* (a verdict holds one reason)
+
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
 u32p = C.POINTER(C.c_uint32)
@@ -67,6 +70,10 @@ class TrimPattern(C.Structure):
 class QualParams(C.Structure):   # rtx_qual_params
     _fields_ = [("ascii_base", C.c_uint32), ("trunc_len", C.c_uint32), ("trunc_qual", C.c_int32), ("trunc_ee", C.c_double), ("min_len", C.c_uint32),
                 ("max_len", C.c_uint32), ("max_ns", C.c_int32), ("max_ee", C.c_double), ("max_ee_rate", C.c_double)]
+
+
+class MergeParams(C.Structure):   # rtx_merge_params
+    _fields_ = [("ascii_base", C.c_uint32), ("min_overlap", C.c_uint32), ("max_diffs", C.c_uint32), ("max_diff_pct", C.c_uint32), ("q_cap", C.c_uint32)]
 
 
 class RtxError(RuntimeError):
@@ -218,6 +225,15 @@ _SIGNATURES = {
     "rtx_index_quality": (C.c_int, [C.c_void_p, C.POINTER(QualParams), C.POINTER(C.c_int)]),
     "rtx_raxtax_last_qual": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_raxtax_multi_ex5": (C.c_int, None),
+    "rtx_merge_create": (C.c_int, [C.c_int, C.POINTER(MergeParams), C.POINTER(C.c_void_p)]),
+    "rtx_merge_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u8p, u64p, u8p, u8p, u64p, u32p, u32p, u32p, u32p, u64p, u8p, u8p, C.c_uint64]),
+    "rtx_merge_destroy": (None, [C.c_void_p]),
+    "rtx_merge_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_merge_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rtx_merge_pair": (C.c_int, [C.POINTER(MergeParams), u8p, u8p, C.c_uint32, u8p, u8p, C.c_uint32, u32p, u32p, u32p, u32p, u8p, u8p]),
+    "rtx_merge_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(C.c_void_p)]),
+    "rtx_queries_merge_report": (C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p)]),
+    "rtx_fastq_block_end_n": (C.c_uint64, [C.c_char_p, C.c_uint64, C.c_uint64, u64p]),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

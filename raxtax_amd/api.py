@@ -1014,6 +1014,151 @@ def raxtax_last_qual() -> Tuple[int, int, int, List[int], float]:
     return int(a.value), int(b.value), int(c.value), [int(x) for x in r], float(s.value)
 
 
+MERGE_MAX_READ = _lib.RTX_MERGE_MAX_READ
+MG_BAD_QUALITY, MG_TOO_LONG, MG_TOO_SHORT, MG_NO_OVERLAP = (1 << b for b in range(4))
+
+
+@dataclass
+class MergeParams:
+    """The parameters of paired-end merging (rtx_merge_params).  A candidate overlap of ov bases with d diffs scores ov - 5 d and is accepted
+    iff d <= max_diffs, 100 d <= max_diff_pct * ov and the score is at least min_overlap; q_cap caps the Q of two agreeing bases."""
+    ascii_base: int = 33
+    min_overlap: int = 16
+    max_diffs: int = 10
+    max_diff_pct: int = 100
+    q_cap: int = 41
+
+    def _c(self) -> "_lib.MergeParams":
+        return _lib.MergeParams(int(self.ascii_base), int(self.min_overlap), int(self.max_diffs), int(self.max_diff_pct), int(self.q_cap))
+
+
+def merge_verdict_names(v: int) -> List[str]:
+    """The reason of a verdict (RTX_MG_*), [] for a pair that is merged."""
+    return [name for b, name in enumerate(_lib.RTX_MG_NAMES) if (int(v) >> b) & 1]
+
+
+def _mate(bases, quals):
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    quals = np.ascontiguousarray(quals, dtype=np.uint8)
+    if len(bases) != len(quals):
+        raise ValueError(f"{len(quals)} quality bytes for {len(bases)} bases")
+    return bases, quals
+
+
+def merge_pair(params: MergeParams, f_bases, f_quals, r_bases, r_quals) -> Tuple[int, int, int, np.ndarray, np.ndarray]:
+    """rtx_merge_pair: (overlap, diffs, verdict, merged bases, merged quality bytes) of ONE pair on the host, with the functions the device
+    kernel calls; the merged read is empty unless the verdict is 0."""
+    fb, fq = _mate(f_bases, f_quals)
+    rb, rq = _mate(r_bases, r_quals)
+    one = np.zeros(1, np.uint8)
+    mb, mq = (np.zeros(len(fb) + len(rb) + 1, np.uint8) for _ in range(2))
+    ov, d, v, ml = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+    check(_lib.load().rtx_merge_pair(C.byref(params._c()), ptr(fb if len(fb) else one, u8p), ptr(fq if len(fq) else one, u8p), len(fb),
+                                     ptr(rb if len(rb) else one, u8p), ptr(rq if len(rq) else one, u8p), len(rb), C.byref(ov), C.byref(d), C.byref(v),
+                                     C.byref(ml), ptr(mb, u8p), ptr(mq, u8p)))
+    return int(ov.value), int(d.value), int(v.value), mb[:ml.value].copy(), mq[:ml.value].copy()
+
+
+class Merge:
+    """The paired-end merging stage on one GPU (rtx_merge): an object of its own beside any Index, one stream, buffers that only grow."""
+
+    def __init__(self, device: int, params: MergeParams):
+        self._lib = _lib.load()
+        self._h = None
+        h = C.c_void_p()
+        check(self._lib.rtx_merge_create(device, C.byref(params._c()), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_merge_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, f_bases, f_quals, f_off, r_bases, r_quals, r_off):
+        """(overlap, diffs, verdict, merged_len, merged_bases, merged_quals, slot_off) of n pairs (rtx_merge_run): the merged read of pair i
+        is merged_bases[slot_off[i] : slot_off[i] + merged_len[i]], its quality bytes likewise; verdict 0: merged (merge_verdict_names)."""
+        fb, fq = _mate(f_bases, f_quals)
+        rb, rq = _mate(r_bases, r_quals)
+        f_off = np.ascontiguousarray(f_off, dtype=np.uint64)
+        r_off = np.ascontiguousarray(r_off, dtype=np.uint64)
+        if len(f_off) != len(r_off) or len(f_off) < 1:
+            raise ValueError(f"{len(f_off)} / {len(r_off)} offsets: the two mate arrays must describe the same number of pairs")
+        n = len(f_off) - 1
+        one = np.zeros(1, np.uint8)
+        ov, d, v, ml = (np.zeros(max(n, 1), dtype=np.uint32) for _ in range(4))
+        slot = np.zeros(n + 1, dtype=np.uint64)
+        with np.errstate(over="ignore"):
+            lens = (f_off[1:] - f_off[:-1]) + (r_off[1:] - r_off[:-1])
+        ok = n > 0 and bool((f_off[1:] >= f_off[:-1]).all() and (r_off[1:] >= r_off[:-1]).all())
+        cap = int((((lens + np.uint64(15)) // np.uint64(16)) * np.uint64(16)).sum()) if ok else 0   # (offsets that are not monotone: the call refuses them)
+        mb, mq = (np.zeros(cap + 1, np.uint8) for _ in range(2))
+        check(self._lib.rtx_merge_run(self._h, n, ptr(fb if len(fb) else one, u8p), ptr(fq if len(fq) else one, u8p), ptr(f_off, u64p),
+                                      ptr(rb if len(rb) else one, u8p), ptr(rq if len(rq) else one, u8p), ptr(r_off, u64p), ptr(ov, u32p), ptr(d, u32p),
+                                      ptr(v, u32p), ptr(ml, u32p), ptr(slot, u64p), ptr(mb, u8p), ptr(mq, u8p), cap))
+        return ov[:n], d[:n], v[:n], ml[:n], mb[:cap], mq[:cap], slot
+
+    def kernel_ms(self) -> float:
+        """Milliseconds of the kernel of the last run(), from HIP events (rtx_merge_kernel_time)."""
+        ms = C.c_float()
+        check(self._lib.rtx_merge_kernel_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def stage_seconds(self) -> Tuple[float, float, float]:
+        """(host staging, copies and waiting around the kernel, the whole call) of the last run(), in seconds (rtx_merge_stage_times)."""
+        t = (C.c_double * 3)()
+        check(self._lib.rtx_merge_stage_times(self._h, t))
+        return float(t[0]), float(t[1]), float(t[2])
+
+
+_IUPAC_CHARS = {v: k for k, v in IUPAC.items()}
+
+
+def fastq_text(records) -> str:
+    """(label, bases, quals) triples as FASTQ text in the four-line form (the inverse of parse_query_fastq_str; a base code 0 has no letter)."""
+    out = []
+    for label, bases, quals in records:
+        out.append("@%s\n%s\n+\n%s\n" % (label, "".join(_IUPAC_CHARS[int(c)] for c in bases), bytes(np.asarray(quals, np.uint8)).decode("latin-1")))
+    return "".join(out)
+
+
+def fastq_block_end_n(text, max_records: int) -> Tuple[int, int]:
+    """rtx_fastq_block_end_n: (the offset behind the last whole record among the first max_records of the text, how many records that is)."""
+    b = text.encode() if isinstance(text, str) else bytes(text)
+    n = C.c_uint64()
+    end = _lib.load().rtx_fastq_block_end_n(b, len(b), int(max_records), C.byref(n))
+    return int(end), int(n.value)
+
+
+def merge_queries(stage: Optional[Merge], fwd, rev, queries_to_skip: Sequence[str] = (), ascii_base: int = 33):
+    """rtx_merge_queries: the pairs of two FASTQ inputs -- texts, or lists of (label, bases, quals) triples as parse_query_fastq_str returns
+    them -- merged on the stage's GPU.  Returns ((label, bases, quals) triples ready for raxtax(..., quals=...), a pair that is not merged
+    being the empty read, and the report: a list of (nf, nr, overlap, diffs, verdict) per pair)."""
+    lib = _lib.load()
+    texts = [(t if isinstance(t, (str, bytes)) else fastq_text(t)) for t in (fwd, rev)]
+    skip = (C.c_char_p * max(len(queries_to_skip), 1))(*[s.encode() for s in queries_to_skip])
+    handles = []
+    try:
+        for t in texts:
+            b = t.encode("latin-1") if isinstance(t, str) else bytes(t)
+            h = C.c_void_p()
+            check(lib.rtx_queries_parse_fastq(b, len(b), None, 0, int(ascii_base), C.byref(h)))
+            handles.append(h)
+        m = C.c_void_p()
+        check(lib.rtx_merge_queries(stage._h if stage is not None else None, handles[0], handles[1], skip, len(queries_to_skip), C.byref(m)))
+        handles.append(m)
+        n = lib.rtx_queries_len(m)
+        p = [u32p() for _ in range(5)]
+        check(lib.rtx_queries_merge_report(m, *[C.byref(x) for x in p]))
+        cols = [np.ctypeslib.as_array(x, shape=(n,)).copy() if n else np.zeros(0, np.uint32) for x in p]
+        return _queries_records(lib, m), [tuple(int(c[i]) for c in cols) for i in range(n)]
+    finally:
+        for h in handles:
+            lib.rtx_queries_destroy(h)
+
+
 def semiglobal_distance(q: np.ndarray, r: np.ndarray) -> int:
     """rtx_semiglobal_distance: the least Levenshtein distance between the encoded sequence q and any substring of r (the empty one
     included) -- what Result.nearest_dist holds for a query and its nearest reference, computed on the host."""

@@ -25,6 +25,13 @@
 //    then label, length, start, end, expected errors, verdict per query in input order -- the read kept [start, end) of its length bases with
 //    that many expected errors (six decimals, truncated), verdict `pass` or the reasons it was discarded for joined by '+'; a discarded read has
 //    no result lines; the totals go to the log.  A filter option on FASTA input is refused.)
+//   (--reverse R2.fastq, short -r: -i holds the forward mates and this file the reverse mates of the same pairs, record for record; the two
+//    mates of every pair are merged on the first device of the run before anything else sees them (rtx_merge_queries, rtx_merge.hip), block
+//    by block on the reader's thread, so that merging overlaps with the classification of the block before.  --merge-minovlen N (16),
+//    --merge-maxdiffs N (10), --merge-maxdiffpct N (100), --merge-qcap N (41) are the fields of rtx_merge_params.  Primers, quality filter,
+//    dereplication and classification see merged reads; a pair that is not merged is the empty read: no result lines.  PREFIX/raxtax.merge: a
+//    header, then label, forward length, reverse length, overlap, diffs, merged length and verdict (`merged`, or the reason it was not) per
+//    pair in input order; the totals go to the log.  --reverse with FASTA input, or a merge option without --reverse, is refused.)
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
@@ -137,7 +144,7 @@ std::string fingerprint(const std::string &path) {
 // (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
 // (... and --primers with its two settings, as given: trimmed reads are other reads)
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
-                            const std::string &primers = std::string(), const std::string &quality = std::string()) {
+                            const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
@@ -145,6 +152,7 @@ std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv
     if (profile) ss << ",\n  \"profile\": " << profile;
     if (!primers.empty()) ss << ",\n  \"primers\": \"" << primers << "\"";
     if (!quality.empty()) ss << ",\n  \"quality\": \"" << quality << "\"";  // (... and the quality filter's settings, as given)
+    if (!merge.empty()) ss << ",\n  \"merge\": \"" << merge << "\"";  // (... and --reverse with the merge settings: merged reads are other reads)
     ss << "\n}\n";
     return ss.str();
 }
@@ -183,7 +191,7 @@ uint8_t iupac_code(char ch) {
 }
 
 struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits, trim, qc;
+    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge;
     bool want_tsv = false, want_strand = false, want_hits = false;
     const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
 };
@@ -212,6 +220,9 @@ int main(int argc, char **argv) {
     uint32_t primer_pct = 10, primer_window = 0;                   // --primer-errors PCT, --primer-window N
     rtx_qual_params qual{33u, 0u, -1, -1.0, 0u, 0u, -1, -1.0, -1.0};  // --fastq-ascii and the filter options: rtx_index_set_quality on every handle, PREFIX/raxtax.qc
     std::string qual_spec;                                             // the filter options as given (empty: none) -- part of the checkpoint
+    std::string rev_file;                                              // --reverse FILE: the reverse mates of the pairs of -i, merged on the device (rtx_merge_queries), PREFIX/raxtax.merge
+    rtx_merge_params merge{33u, 16u, 10u, 100u, 41u};                  // --merge-minovlen, --merge-maxdiffs, --merge-maxdiffpct, --merge-qcap (ascii_base: --fastq-ascii)
+    std::string merge_opts;                                            // the merge options as given (empty: none)
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -302,6 +313,16 @@ int main(int argc, char **argv) {
             (a == "--truncee" ? qual.trunc_ee : a == "--maxee" ? qual.max_ee : qual.max_ee_rate) = x;
             qual_spec += (qual_spec.empty() ? "" : ";") + a.substr(2) + "=" + v;
         }
+        else if (a == "-r" || a == "--reverse") rev_file = val();
+        else if (a == "--merge-minovlen" || a == "--merge-maxdiffs" || a == "--merge-maxdiffpct" || a == "--merge-qcap") {
+            const char *v = val();
+            char *end = nullptr;
+            const long x = strtol(v, &end, 10);
+            const long least = a == "--merge-minovlen" ? 1 : 0, most = a == "--merge-maxdiffpct" ? 100 : (a == "--merge-qcap" ? 93 : (long)RTX_MERGE_MAX_READ);
+            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
+            (a == "--merge-minovlen" ? merge.min_overlap : a == "--merge-maxdiffs" ? merge.max_diffs : a == "--merge-maxdiffpct" ? merge.max_diff_pct : merge.q_cap) = (uint32_t)x;
+            merge_opts += (merge_opts.empty() ? "" : " ") + a;
+        }
         else if (a == "--profile") {
             char *end = nullptr;
             const char *v = val();
@@ -314,7 +335,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -341,6 +362,22 @@ int main(int argc, char **argv) {
         return 64;
     }
     if (qual_on) qual_spec += ";ascii=" + std::to_string(qual.ascii_base);
+    // --reverse: paired input, merged before anything else.  Refused here as well -- before the database is read -- where it cannot work
+    const bool merge_on = !rev_file.empty();
+    if (!merge_opts.empty() && !merge_on) {
+        fprintf(stderr, "raxtax-hip: %s sets how pairs are merged and needs --reverse FILE (the reverse mates)\n", merge_opts.c_str());
+        return 64;
+    }
+    if (merge_on && !fastq) {
+        fprintf(stderr, "raxtax-hip: --reverse needs FASTQ input: %s does not start with '@'\n", qf.empty() ? "-i" : qf.c_str());
+        return 64;
+    }
+    std::string merge_spec;
+    if (merge_on) {
+        merge.ascii_base = qual.ascii_base;
+        merge_spec = "reverse=" + rev_file + ";minovlen=" + std::to_string(merge.min_overlap) + ";maxdiffs=" + std::to_string(merge.max_diffs) + ";maxdiffpct=" +
+                     std::to_string(merge.max_diff_pct) + ";qcap=" + std::to_string(merge.q_cap) + ";ascii=" + std::to_string(merge.ascii_base);
+    }
     // --primers: the pattern list, checked here -- before the database is read and any device is touched
     struct Primer { std::string name; std::vector<uint8_t> codes; uint32_t end; };
     std::vector<Primer> primers;
@@ -374,7 +411,7 @@ int main(int argc, char **argv) {
         primer_spec += (primer_spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
     }
     if (!primer_spec.empty()) primer_spec += ";errors=" + std::to_string(primer_pct) + ";window=" + std::to_string(primer_window);
-    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc";
+    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && derep) {
         fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
@@ -386,7 +423,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -406,6 +443,7 @@ int main(int argc, char **argv) {
             if (want_hits) purge_incomplete(hits_path, done);
             if (!primers.empty()) purge_incomplete(trim_path, done, true);
             if (qual_on) purge_incomplete(qc_path, done, true);
+            if (merge_on) purge_incomplete(merge_path, done, true);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -459,7 +497,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -477,7 +515,7 @@ int main(int argc, char **argv) {
     // (parser.rs:150-153).
     std::vector<const char *> skip;
     for (const std::string &l : done) skip.push_back(l.c_str());
-    struct Parsed { rtx_queries *qs = nullptr; int rc = RTX_OK; std::string err; bool end = false; };
+    struct Parsed { rtx_queries *qs = nullptr; int rc = RTX_OK; std::string err; bool end = false; double merge_s[3] = {0, 0, 0}; float merge_ms = 0; };
     std::mutex qmu;
     std::condition_variable qcv;
     std::deque<Parsed> ready;  // at most two blocks ahead
@@ -489,6 +527,85 @@ int main(int argc, char **argv) {
             ready.push_back(std::move(pz));
             qcv.notify_all();
         };
+        if (merge_on) {
+            // Paired input: both files block by block, cut at the same record (rtx_fastq_block_end_n), parsed, and merged on the first device
+            // of the run; what is queued is the handle of merged reads.  Nothing behind the queue knows.
+            auto fail = [&](int rc, const std::string &msg) { Parsed e; e.rc = rc; e.err = msg; e.end = true; push(std::move(e)); };
+            Input in[2];
+            const std::string *name[2] = {&qf, &rev_file};
+            if (!in[0].open(qf)) { fail(RTX_ERR_PARSE, "cannot open file"); return; }
+            if (!in[1].open(rev_file)) { in[0].close(); fail(RTX_ERR_PARSE, "cannot open " + rev_file); return; }
+            rtx_merge *stage = nullptr;
+            if (const int mrc = rtx_merge_create(devices[0], &merge, &stage)) { fail(mrc, std::string("paired-end merging on device ") + std::to_string(devices[0]) + ": " + rtx_last_error()); in[0].close(); in[1].close(); return; }
+            std::string buf[2];
+            bool eof[2] = {false, false};
+            uint64_t records = 0;  // pairs handed on so far
+            bool force = false;
+            for (;;) {
+                bool failed = false;
+                for (int k = 0; k < 2 && !failed; k++) {
+                    if (eof[k] || (buf[k].size() >= block_bytes && !force)) continue;
+                    const size_t have = buf[k].size();
+                    buf[k].resize(have + block_bytes);
+                    const size_t got = in[k].read(&buf[k][have], block_bytes);
+                    if (got == (size_t)-1) { fail(RTX_ERR_PARSE, "read error in " + *name[k] + " (corrupt gzip stream?)"); failed = true; break; }
+                    buf[k].resize(have + got);
+                    eof[k] = got < block_bytes;
+                    if (eof[k] && !buf[k].empty() && buf[k].back() != '\n') buf[k].push_back('\n');  // (the last record may lack its newline: counted as whole from here on)
+                }
+                if (failed) break;
+                force = false;
+                uint64_t n_rec[2] = {0, 0}, end[2] = {0, 0};
+                for (int k = 0; k < 2; k++) (void)rtx_fastq_block_end_n(buf[k].data(), buf[k].size(), ~0ull, &n_rec[k]);
+                const bool last = eof[0] && eof[1];
+                const uint64_t take = std::min(n_rec[0], n_rec[1]);
+                if (!last && take == 0) {
+                    const int out = eof[0] ? 0 : (eof[1] ? 1 : -1);
+                    if (out >= 0 && n_rec[out] == 0 && n_rec[1 - out] > 0) {
+                        fail(RTX_ERR_PARSE, "paired FASTQ: " + *name[out] + " ends after record " + std::to_string(records) + ", " + *name[1 - out] + " goes on");
+                        break;
+                    }
+                    force = true;  // no whole record of one file yet: read on
+                    continue;
+                }
+                for (int k = 0; k < 2; k++) end[k] = last ? buf[k].size() : rtx_fastq_block_end_n(buf[k].data(), buf[k].size(), take, nullptr);
+                auto blank = [](const std::string &t) { return t.find_first_not_of(" \t\r\n\v\f") == std::string::npos; };
+                Parsed pz;
+                pz.end = last;
+                if (last && blank(buf[0]) && blank(buf[1])) { push(std::move(pz)); break; }  // both files ended with the block before
+                if (last && n_rec[0] != n_rec[1]) {  // the files run out at different records
+                    const int out = n_rec[0] < n_rec[1] ? 0 : 1;
+                    fail(RTX_ERR_PARSE, "paired FASTQ: " + *name[out] + " ends after record " + std::to_string(records + n_rec[out]) + ", " + *name[1 - out] + " goes on");
+                    break;
+                }
+                rtx_queries *mates[2] = {nullptr, nullptr};
+                for (int k = 0; k < 2 && pz.rc == RTX_OK; k++) {
+                    pz.rc = rtx_queries_parse_fastq_block(buf[k].data(), end[k], nullptr, 0, qual.ascii_base, 0u, &mates[k]);
+                    if (pz.rc != RTX_OK) pz.err = *name[k] + ", records from " + std::to_string(records + 1) + " on: " + rtx_last_error();
+                }
+                if (pz.rc == RTX_OK) {
+                    pz.rc = rtx_merge_queries(stage, mates[0], mates[1], skip.empty() ? nullptr : skip.data(), skip.size(), &pz.qs);
+                    if (pz.rc != RTX_OK) pz.err = "pairs from record " + std::to_string(records + 1) + " on: " + rtx_last_error();
+                    else { (void)rtx_merge_stage_times(stage, pz.merge_s); (void)rtx_merge_kernel_time(stage, &pz.merge_ms); }
+                }
+                rtx_queries_destroy(mates[0]);
+                rtx_queries_destroy(mates[1]);
+                records += take;
+                failed = pz.rc != RTX_OK;
+                pz.end = last || failed;
+                push(std::move(pz));
+                if (failed || last) break;
+                for (int k = 0; k < 2; k++) buf[k].erase(0, end[k]);
+                {
+                    std::lock_guard<std::mutex> g(qmu);
+                    if (stop_reader) break;
+                }
+            }
+            rtx_merge_destroy(stage);
+            in[0].close();
+            in[1].close();
+            return;
+        }
         Input f;
         if (!f.open(qf)) { Parsed e; e.rc = RTX_ERR_PARSE; e.err = "cannot open file"; e.end = true; push(std::move(e)); return; }
         std::string buf;
@@ -597,6 +714,13 @@ int main(int argc, char **argv) {
         sink.qc.open(qc_path, mode);
         if (header) sink.qc << "label\tlength\tstart\tend\texpected_errors\tverdict\n";
     } else if (mode == std::ios::trunc) remove(qc_path.c_str());  // (likewise)
+    if (merge_on) {
+        const bool header = mode == std::ios::trunc || !is_file(merge_path);
+        sink.merge.open(merge_path, mode);
+        if (header) sink.merge << "label\tforward_length\treverse_length\toverlap\tdiffs\tmerged_length\tverdict\n";
+        fprintf(stderr, "[INFO ] --reverse: pairs of %s and %s are merged on device %d: overlap at least %u, at most %u diffs and %u %% of the overlap, Q capped at %u\n", qf.c_str(),
+                rev_file.c_str(), devices[0], merge.min_overlap, merge.max_diffs, merge.max_diff_pct, merge.q_cap);
+    } else if (mode == std::ios::trunc) remove(merge_path.c_str());  // (likewise)
     sink.want_strand = both_strands;
     sink.want_hits = want_hits;
     sink.tree = tree;
@@ -680,6 +804,8 @@ int main(int argc, char **argv) {
     double qual_busy = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
     double derep_busy = 0;
+    uint64_t merge_total[6] = {0, 0, 0, 0, 0, 0};  // --reverse: pairs, merged, and not merged for each of the four reasons (RTX_MG_*)
+    double merge_busy = 0;
     bool parse_failed = false;
     for (;;) {
         Parsed pz;
@@ -702,6 +828,22 @@ int main(int argc, char **argv) {
             const uint8_t *bases;
             const uint64_t *off;
             rtx_queries_data(pz.qs, &bases, &off);
+            if (merge_on) {  // what the merge made of every pair of the block, before the block is classified
+                static const char *const names[4] = {"bad_quality", "too_long", "too_short", "no_overlap"};
+                const uint32_t *mnf, *mnr, *mov, *md, *mv;
+                if (rtx_queries_merge_report(pz.qs, &mnf, &mnr, &mov, &md, &mv) == RTX_OK)
+                    for (uint64_t i = 0; i < nb; i++) {
+                        const char *verdict = "merged";
+                        merge_total[0]++;
+                        if (!mv[i]) merge_total[1]++;
+                        for (uint32_t b = 0; b < 4u; b++)
+                            if ((mv[i] >> b) & 1u) { verdict = names[b]; merge_total[2 + b]++; break; }
+                        sink.merge << labels[i] << '\t' << mnf[i] << '\t' << mnr[i] << '\t' << mov[i] << '\t' << md[i] << '\t' << (off[i + 1] - off[i]) << '\t' << verdict << '\n';
+                    }
+                merge_busy += pz.merge_s[2];
+                if (timing) fprintf(stderr, "[TIMING] merging of this block: %llu pairs, kernel %.3f ms, staging %.3f s, copies and wait %.3f s, all %.3f s (on the reader's thread, beside the classification of the block before)\n",
+                                    (unsigned long long)nb, pz.merge_ms, pz.merge_s[0], pz.merge_s[1], pz.merge_s[2]);
+            }
             // Chunks of 131 072 queries are what a device handles best (two sub-batches of 65 536 on its two streams, the next chunk enqueued ahead:
             // 43 ms per 524 288 queries against 101-113 with chunks of 32 768, the default until round 6); smaller ones when the block would
             // otherwise leave a device without two chunks of its own, never below 32 768.
@@ -765,8 +907,14 @@ int main(int argc, char **argv) {
     if (want_hits) sink.hits.flush();
     if (!primers.empty()) sink.trim.flush();
     if (qual_on) sink.qc.flush();
+    if (merge_on) sink.merge.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
+    if (merge_on) {
+        fprintf(stderr, "[INFO ] --reverse: %llu pairs, %llu merged; not merged for bad_quality %llu, too_long %llu, too_short %llu, no_overlap %llu\n", (unsigned long long)merge_total[0],
+                (unsigned long long)merge_total[1], (unsigned long long)merge_total[2], (unsigned long long)merge_total[3], (unsigned long long)merge_total[4], (unsigned long long)merge_total[5]);
+        if (timing) t_log << ", \"merge_busy\": " << merge_busy;
+    }
     if (!primers.empty()) {
         fprintf(stderr, "[INFO ] --primers: %llu queries, %llu with a 5' primer, %llu with a 3' primer, %llu left empty\n", (unsigned long long)trim_total[0],
                 (unsigned long long)trim_total[1], (unsigned long long)trim_total[2], (unsigned long long)trim_total[3]);

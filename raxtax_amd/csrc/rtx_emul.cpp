@@ -862,6 +862,59 @@ void emul_qual_read(const int32_t *cfg32, const uint64_t *cfg64, const uint64_t 
     *verdict = qual_verdict(cfg, bad, short_tl, hi, carry_e, carry_n);
 }
 
+// One pair as merge_kernel (rtx_merge.hip) merges it, with the functions the kernel calls, in the kernel's geometry: the mates staged four
+// bases per lane and step (a too-long mate only streamed for its bad bytes), the candidates dealt over 64 lanes in strides of 64 -- each
+// walked in words of 16 with the early leave --, the maximum over the lanes, then the merged bases written lane l at l + 64 k.
+// cfg: ascii_base, min_overlap, max_diffs, max_diff_pct, q_cap; out: overlap, diffs, verdict, merged length; mb / mq take nf + nr bytes.
+void emul_merge_pair(const uint32_t *cfg5, const uint8_t *fb, const uint8_t *fq, uint32_t nf, const uint8_t *rb, const uint8_t *rq, uint32_t nr, uint32_t *out,
+                     uint8_t *mb, uint8_t *mq) {
+    const MergeCfg cfg{cfg5[0], cfg5[1], cfg5[2], cfg5[3], cfg5[4]};
+    std::vector<uint16_t> hf(4u * kMergeWords, 0xFFFFu), hr(4u * kMergeWords, 0xFFFFu);  // (what no lane wrote is never taken as data)
+    std::vector<uint8_t> qf(kMergeMaxRead, 0xFF), qr(kMergeMaxRead, 0xFF);
+    const bool fits = nf <= kMergeMaxRead && nr <= kMergeMaxRead;
+    bool bad = false;
+    for (uint32_t side = 0; side < 2u; side++) {
+        const uint8_t *codes = side ? rb : fb, *quals = side ? rq : fq;
+        const uint32_t n = side ? nr : nf;
+        for (uint32_t lane = 0; lane < 64u; lane++) {
+            if (fits) {
+                for (uint32_t h = lane; 4u * h < n; h += 64u) {
+                    uint32_t nib16, q32;
+                    bool b;
+                    merge_stage4(cfg, [codes](uint32_t k) { return (uint32_t)codes[k]; }, [quals](uint32_t k) { return (uint32_t)quals[k]; }, n, side == 1u, h, nib16, q32, b);
+                    (side ? hr : hf)[h] = (uint16_t)nib16;
+                    memcpy((side ? qr : qf).data() + 4u * h, &q32, 4);
+                    bad = bad || b;
+                }
+            } else {
+                for (uint32_t k = lane; k < n; k += 64u) bad = bad || merge_bad_byte(cfg, quals[k]);
+            }
+        }
+    }
+    out[0] = out[1] = out[3] = 0u;
+    out[2] = merge_pre_verdict(cfg, bad, nf, nr);
+    if (out[2]) return;
+    auto word = [](const std::vector<uint16_t> &h, uint32_t w) { uint64_t v; memcpy(&v, h.data() + 4u * w, 8); return v; };
+    auto word_f = [&](uint32_t w) { return word(hf, w); };
+    auto word_r = [&](uint32_t w) { return word(hr, w); };
+    uint32_t best = 0;
+    for (uint32_t lane = 0; lane < 64u; lane++) {
+        uint32_t mine = 0;
+        for (uint32_t c = cfg.min_overlap + lane; c <= std::min(nf, nr); c += kMergeStride) mine = std::max(mine, merge_candidate(cfg, word_f, word_r, nf, c));
+        best = std::max(best, mine);
+    }
+    if (!best) { out[2] = kMgNoOverlap; return; }
+    merge_key_read(best, out[0], out[1]);
+    out[3] = nf + nr - out[0];
+    for (uint32_t lane = 0; lane < 64u; lane++)
+        for (uint32_t at = lane; at < out[3]; at += 64u) {
+            uint32_t code, byte;
+            merge_base_at(cfg, word_f, word_r, [&qf](uint32_t k) { return (uint32_t)qf[k]; }, [&qr](uint32_t k) { return (uint32_t)qr[k]; }, nf, out[0], at, code, byte);
+            mb[at] = (uint8_t)code;
+            mq[at] = (uint8_t)byte;
+        }
+}
+
 // byte, high-bit word and shift of local reference rl in the packed counts of its tile (packed_count_pos)
 void emul_packed_count_pos(uint32_t rl, uint32_t *byte, uint32_t *hi_word, uint32_t *hi_shift) { packed_count_pos(rl, *byte, *hi_word, *hi_shift); }
 

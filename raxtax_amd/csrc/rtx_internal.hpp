@@ -114,4 +114,6 @@ struct rtx_queries {
     std::vector<uint64_t> base_off{0};
     std::vector<uint8_t> quals;  // FASTQ: the quality bytes as they stand in the file, indexed like bases (rtx_queries_quals)
     bool fastq = false;
+    bool merged = false;         // made by rtx_merge_queries: the per-pair report (rtx_queries_merge_report), indexed like labels
+    std::vector<uint32_t> mg_nf, mg_nr, mg_overlap, mg_diffs, mg_verdict;
 };

@@ -374,6 +374,134 @@ RTX_HD void qual_read_serial(const QualCfg &cfg, const uint64_t *table, const L 
 }
 
 // ---------------------------------------------------------------------------
+// Paired-end merging (merge_kernel, rtx_merge.hip; rtx_merge_pair on the host; emul_merge_pair on x86): the two mates of a pair overlapped
+// into one read -- include/raxtax_hip.h has the semantics.  Exact integers.
+// A mate is staged as nibble words -- 16 base codes to a uint64, base p in bits 4 (p & 15) of word p >> 4 -- and a byte of Q per base; the
+// reverse mate as its reverse complement R', so that candidate ov sets F[nf - ov + i] against R'[i]: an unaligned read of F (merge_word_at),
+// an aligned one of R', an AND, and the zero nibbles of it under the tail mask (merge_word_diffs).  merge_stage4 builds four bases of either
+// array, merge_candidate walks one candidate and returns its key, merge_base_at gives one base of the merged read.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kMergeMaxRead = 1024u;          // RTX_MERGE_MAX_READ
+constexpr uint32_t kMergeMismatchCost = 5u;        // RTX_MERGE_MISMATCH_COST
+constexpr uint32_t kMergeStride = 64u;             // candidates of a step: the lanes of a wave
+constexpr uint32_t kMergeWords = kMergeMaxRead / 16u + 2u;  // words of a staged mate: the unaligned read of the last word takes its neighbour (and one to keep 16 bytes)
+constexpr uint32_t kMergeKeyOvBits = 11u;          // ov <= 1024
+constexpr uint32_t kMgBadQuality = 1u, kMgTooLong = 2u, kMgTooShort = 4u, kMgNoOverlap = 8u;  // RTX_MG_*
+struct MergeCfg { uint32_t base, min_overlap, max_diffs, max_diff_pct, q_cap; };  // rtx_merge_params, checked (host_merge.cpp: merge_check_params)
+
+RTX_HD uint32_t merge_code(uint32_t b) { return b > 15u ? 0u : b; }  // a byte that is no 4-bit code counts as 0
+RTX_HD uint32_t merge_comp(uint32_t c) { return ((c & 1u) << 3) | ((c & 2u) << 1) | ((c & 4u) >> 1) | ((c & 8u) >> 3); }  // rtx_revcomp of one code
+RTX_HD bool merge_bad_byte(const MergeCfg &cfg, uint32_t byte) { return byte - cfg.base > kQualMaxQ; }  // (wraps below the base)
+// the verdicts that need no candidate, in their order; 0: the candidates decide
+RTX_HD uint32_t merge_pre_verdict(const MergeCfg &cfg, bool bad, uint32_t nf, uint32_t nr) {
+    if (bad) return kMgBadQuality;
+    if (nf > kMergeMaxRead || nr > kMergeMaxRead) return kMgTooLong;
+    if (nf < cfg.min_overlap || nr < cfg.min_overlap) return kMgTooShort;
+    return 0u;
+}
+// Bases 4 h .. 4 h + 3 of a staged mate of n bases (n <= kMergeMaxRead; rev: of its reverse complement): their codes as 16 bits of a nibble word,
+// their quality bytes as they came (little-endian), 0 behind the mate's end; bad: one of them has Q outside 0 .. 93.
+template <class LC, class LQ>
+RTX_HD void merge_stage4(const MergeCfg &cfg, const LC &code_at, const LQ &qual_at, uint32_t n, bool rev, uint32_t h, uint32_t &nib16, uint32_t &q32, bool &bad) {
+    nib16 = q32 = 0u;
+    bad = false;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; k++) {
+        const uint32_t p = 4u * h + k;
+        if (p >= n) continue;
+        const uint32_t at = rev ? n - 1u - p : p;
+        const uint32_t c = merge_code(code_at(at)), q = qual_at(at);
+        nib16 |= (rev ? merge_comp(c) : c) << (4u * k);
+        q32 |= (q & 0xFFu) << (8u * k);
+        bad = bad || merge_bad_byte(cfg, q & 0xFFu);
+    }
+}
+RTX_HD uint64_t merge_tail_mask(uint32_t nibbles) { return nibbles >= 16u ? ~0ull : (1ull << (4u * nibbles)) - 1ull; }  // the first `nibbles` of a word
+// the nibbles of x & y that are zero, among those of the mask: the diffs of one candidate in one word
+RTX_HD uint32_t merge_word_diffs(uint64_t x, uint64_t y, uint64_t mask) {
+    uint64_t z = x & y;
+    z |= z >> 1;
+    z |= z >> 2;  // bit 0 of every nibble: the nibble is not zero
+    const uint64_t zero = ~z & 0x1111111111111111ull & mask;
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__popcll(zero);
+#else
+    return (uint32_t)__builtin_popcountll(zero);
+#endif
+}
+// 16 nibbles from nibble `nib` (0 .. 15) of lo on, continued in hi
+RTX_HD uint64_t merge_word_at(uint64_t lo, uint64_t hi, uint32_t nib) { return nib ? (lo >> (4u * nib)) | (hi << (64u - 4u * nib)) : lo; }
+RTX_HD uint32_t merge_nibble(uint64_t w, uint32_t p) { return (uint32_t)(w >> (4u * (p & 15u))) & 15u; }
+// (score, ov) as one integer: the best candidate is the maximum, among equal scores the larger ov.  Only for an accepted candidate
+// (ov >= 5 d + min_overlap >= 1): never 0, which stands for none.
+RTX_HD uint32_t merge_key(uint32_t ov, uint32_t d) { return ((ov - kMergeMismatchCost * d) << kMergeKeyOvBits) | ov; }
+RTX_HD void merge_key_read(uint32_t key, uint32_t &ov, uint32_t &d) {
+    ov = key & ((1u << kMergeKeyOvBits) - 1u);
+    d = (ov - (key >> kMergeKeyOvBits)) / kMergeMismatchCost;
+}
+RTX_HD bool merge_accept(const MergeCfg &cfg, uint32_t ov, uint32_t d) {  // (d <= ov <= 1024: nothing wraps)
+    return d <= cfg.max_diffs && 100u * d <= cfg.max_diff_pct * ov && ov >= kMergeMismatchCost * d + cfg.min_overlap;
+}
+// Candidate ov (min_overlap <= ov <= min(nf, nr)): its key, or 0 when it is not accepted.  word_f(w) / word_r(w): word w of the staged F / R'.
+// Left as soon as d is above max_diffs.
+template <class WF, class WR>
+RTX_HD uint32_t merge_candidate(const MergeCfg &cfg, const WF &word_f, const WR &word_r, uint32_t nf, uint32_t ov) {
+    const uint32_t f0 = nf - ov, w0 = f0 >> 4, nib = f0 & 15u;
+    uint32_t d = 0;
+    uint64_t lo = word_f(w0);
+    for (uint32_t w = 0; 16u * w < ov; w++) {
+        const uint64_t hi = word_f(w0 + w + 1u);
+        d += merge_word_diffs(merge_word_at(lo, hi, nib), word_r(w), merge_tail_mask(ov - 16u * w));
+        if (d > cfg.max_diffs) return 0u;
+        lo = hi;
+    }
+    return merge_accept(cfg, ov, d) ? merge_key(ov, d) : 0u;
+}
+// one position of an overlap: a, qa of F against b, qb of R' (Q values, 0 .. 93)
+RTX_HD void merge_consensus(const MergeCfg &cfg, uint32_t a, uint32_t qa, uint32_t b, uint32_t qb, uint32_t &code, uint32_t &q) {
+    const uint32_t hi = qa > qb ? qa : qb;
+    if (a == b && a != 0u) {
+        const uint32_t sum = qa + qb, capped = sum < cfg.q_cap ? sum : cfg.q_cap;
+        code = a;
+        q = hi > capped ? hi : capped;
+    } else if ((a & b) != 0u) {
+        code = a & b;
+        q = hi;
+    } else {
+        const uint32_t diff = qa > qb ? qa - qb : qb - qa;
+        code = qb > qa ? b : a;
+        q = diff > 2u ? diff : 2u;
+    }
+}
+// Base p of the read merged at overlap ov (p < nf + nr - ov): its code and its quality BYTE.  qual_f(p) / qual_r(i): the quality byte of F[p] / R'[i].
+template <class WF, class WR, class QF, class QR>
+RTX_HD void merge_base_at(const MergeCfg &cfg, const WF &word_f, const WR &word_r, const QF &qual_f, const QR &qual_r, uint32_t nf, uint32_t ov, uint32_t p,
+                          uint32_t &code, uint32_t &byte) {
+    const uint32_t f0 = nf - ov;
+    if (p < f0) {
+        code = merge_nibble(word_f(p >> 4), p);
+        byte = qual_f(p);
+    } else if (p >= nf) {
+        code = merge_nibble(word_r((p - f0) >> 4), p - f0);
+        byte = qual_r(p - f0);
+    } else {
+        uint32_t q;
+        merge_consensus(cfg, merge_nibble(word_f(p >> 4), p), qual_f(p) - cfg.base, merge_nibble(word_r((p - f0) >> 4), p - f0), qual_r(p - f0) - cfg.base, code, q);
+        byte = cfg.base + q;
+    }
+}
+// One pair whose mates are staged, the candidates one after the other: the best key, 0 for none.
+template <class WF, class WR>
+RTX_HD uint32_t merge_best_serial(const MergeCfg &cfg, const WF &word_f, const WR &word_r, uint32_t nf, uint32_t nr) {
+    uint32_t best = 0;
+    for (uint32_t ov = cfg.min_overlap; ov <= (nf < nr ? nf : nr); ov++) {
+        const uint32_t k = merge_candidate(cfg, word_f, word_r, nf, ov);
+        best = k > best ? k : best;
+    }
+    return best;
+}
+
+// ---------------------------------------------------------------------------
 // Hash of an encoded sequence for the exact-match lookup (Tree.sequences.get, raxtax.rs:42) on the device.  The bytes are taken
 // as 8-byte little-endian words (the last one zero-padded); every word is mixed with its position and the mixes are ADDED, so
 // that the lanes of a wave can hash their words independently and meet in one sum.  Equal sequences hash equal; a collision only
