@@ -136,6 +136,14 @@ int enqueue_kmer(rtx_index *ix, const SubBatch &b, hipStream_t s) {
     // with tile pruning the per-tile lists wait until the live tiles are known (enqueue_hit); databases of few tiles build
     // their lists in one pass per tile whatever is live
     kp.mode = run_prunes(ix, *b.cls) && ix->seg_blocks ? 1u : 0u;
+    if (run_prunes(ix, *b.cls)) {  // the counters enqueue_hit's kernels add to, zeroed here instead of by fill launches on its critical chain (ItemList)
+        rtx_index::Scratch &sc = ix->sc[b.set];
+        const ItemsLayout items(b.nq, ix->ntiles);
+        const FineItemsLayout fine(b.nq, ix->f_ntiles);
+        if (sc.d_items.p) { kp.zero[0] = items.count(sc.d_items.p); kp.zero_n[0] = 9u; }
+        if (sc.d_fine_items.p) { kp.zero[1] = fine.count(sc.d_fine_items.p); kp.zero_n[1] = 9u + ix->f_ntiles; }  // header | cursors
+        if (sc.d_cnt_cursor.p) { kp.zero[2] = sc.d_cnt_cursor.p; kp.zero_n[2] = 1u; }
+    }
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_KMER_EXTRACT, 0), s));
     launch_kmer_extract(s, kp, b.nq);
     if (b.timed_all) RTX_HIP(hipEventRecord(stage_event(ix, b, RTX_STAGE_KMER_EXTRACT, 1), s));
@@ -343,10 +351,10 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         if (records) { pr.rec = rr; pr.rec_max_slots = rr.stride; }
         if (k.diet && !diet) { set_error("internal: the counts buffer is on its diet without the records path"); return RTX_ERR_STATE; }
         if (diet) {
-            RTX_HIP(hipMemsetAsync(sc.d_cnt_cursor.p, 0, 4, s));
             pr.cnt_row = sc.d_cnt_row.p;
-            pr.cnt_cursor = sc.d_cnt_cursor.p;
+            pr.cnt_cursor = sc.d_cnt_cursor.p;  // (zero since this sub-batch's kmer_extract: enqueue_kmer)
             pr.cnt_cap = k.cnt_rows;
+            pr.dense_q = sc.d_dense_q.p;
             pr.flags_out = r.d_flags.p;
             hp.cnt_row = sc.d_cnt_row.p;
         }
@@ -354,11 +362,11 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         if (part == 1) { RTX_HIP(hipGetLastError()); return RTX_OK; }  // the caller exchanges RTX_BUF_BEST, then part 2
         // (2b) second stage of the bounds (whole-database handles with a fine union bitmap): the pairs that are left many live tiles are
         // counted against the union bitmap over blocks of 8 references, which takes the tiles without a block above the threshold off
-        // their lists (fine_epilogue); prune_kernel's number of live tiles per pair is brought up to date for the list below
+        // their lists (fine_epilogue); the list below is built from the masks as this pass leaves them
         if (part == 0 && ix->fine_opt && ix->d_fbitmap.p && k.pair && sc.d_fine_items.p) {
             const FineItemsLayout fine(b.nq, ix->f_ntiles);
             uint32_t *const fi = sc.d_fine_items.p;
-            launch_fine_bounds(s, fine_params(ix, sc, hp), b.nq, ix->ntiles, ix->f_ntiles, pr.pair_live, fine.cursors(fi), fine.items(fi), fine.count(fi), k.planes);
+            launch_fine_bounds(s, fine_params(ix, sc, hp), b.nq, ix->f_ntiles, pr.pair_live, fine.cursors(fi), fine.items(fi), fine.count(fi), k.planes);
         }
         // (3) tiles that are not counted keep a largest count of 0: taxon_prefix leaves them out
         RTX_HIP(hipMemsetAsync(sc.d_tilemax.p, 0, (size_t)b.nq * ix->ntiles * 2, s));
@@ -368,7 +376,8 @@ int enqueue_hit(rtx_index *ix, const SubBatch &b, uint32_t flags, hipStream_t s,
         if (records) hp.rec = rr;
         if (k.pair) {  // the grid of the counting pass walks the live (pair, tile) blocks instead of all of them
             const ItemsLayout items(b.nq, ix->ntiles);
-            launch_live_items(s, sc.d_live.p, pr.live_words, pr.pair_live, b.nq, ix->ntiles, items.offsets(sc.d_items.p), items.items(sc.d_items.p), items.count(sc.d_items.p));
+            launch_live_items(s, sc.d_live.p, pr.live_words, b.nq, ix->ntiles, items.items(sc.d_items.p), items.count(sc.d_items.p),
+                              ix->d_prune_stats.p ? ix->d_prune_stats.p + 2 * kPruneStatCopies * 8 : nullptr);
             hp.items = items.items(sc.d_items.p);
             hp.n_items = items.count(sc.d_items.p);
         }
@@ -463,6 +472,12 @@ int enqueue_prob_prefix(rtx_index *ix, const SubBatch &b, bool fuse_walk, bool p
     const bool records = fuse_walk && on_records_path(ix, k, sc);
     fp.rec_nslots = records ? sc.d_rec_nslots.p : nullptr;
     fp.cnt_row = fuse_walk && on_diet(ix, k, sc) ? sc.d_cnt_row.p : nullptr;
+    if (fp.cnt_row) {  // the launch is over the rows prune_kernel handed out, not over the queries (PrefixParams::dense_q)
+        fp.dense_q = sc.d_dense_q.p;
+        fp.cnt_cursor = sc.d_cnt_cursor.p;
+        fp.cnt_cap = k.cnt_rows;
+        fp.nq = b.nq;
+    }
     if (fuse_walk) {
         fp.walk = walk_params(ix, b, sc.d_prefix.p);
         int rc_r = fp.walk.sub_alloc ? reset_sub_alloc(ix, s) : RTX_OK;
@@ -738,7 +753,7 @@ int begin_run(rtx_index *ix, uint32_t *n_sub_out, bool *timed_out, bool cluster)
                   scratch_ok(s0, k.sub_batch) && (!ix->staged || scratch_ok(ix->sc[1], k.sub_batch));
         k.rec = k.prune && whole && ix->rec_opt != 0u && ix->n_bnd_local == ix->n_bnd && s0.d_rec.p != nullptr && s0.d_rec.n >= need.rec;
         // the diet of the counts buffer: only with the records path (the queries without rows are exactly those on it), in every set the class may run through
-        auto diet_ok = [&](const rtx_index::Scratch &sc) { return sc.d_rec.p != nullptr && sc.d_cnt_row.p != nullptr && sc.d_cnt_cursor.p != nullptr && sc.d_cnt_row.n >= need.cnt_row; };
+        auto diet_ok = [&](const rtx_index::Scratch &sc) { return sc.d_rec.p != nullptr && sc.d_cnt_row.p != nullptr && sc.d_cnt_cursor.p != nullptr && sc.d_dense_q.p != nullptr && sc.d_cnt_row.n >= need.cnt_row; };
         k.diet = k.rec && diet_rows(ix, k.sub_batch) < k.sub_batch && diet_ok(s0);
         if (k.diet && !k.side)
             for (uint32_t j = 1; j <= 2u; j++)
@@ -748,10 +763,12 @@ int begin_run(rtx_index *ix, uint32_t *n_sub_out, bool *timed_out, bool cluster)
             need.add_class(ix, k, k.sub_batch, k.cnt_rows);  // (the rows of the boundary prefix sums go with those of the counts)
             for (uint32_t j = 0; j < 4u; j++) {
                 rtx_index::Scratch &sc = ix->sc[j];
-                if ((j == kSideSet) != k.side || sc.d_kmers.p == nullptr || (sc.d_counts.n >= need.counts && sc.d_prefix.n >= need.prefix)) continue;
+                const bool list_ok = !k.diet || sc.d_dense_q.n >= need.dense_q;  // (the list of the rows' queries grows with the rows)
+                if ((j == kSideSet) != k.side || sc.d_kmers.p == nullptr || (sc.d_counts.n >= need.counts && sc.d_prefix.n >= need.prefix && list_ok)) continue;
                 RTX_HIP(hipStreamSynchronize(ix->stream));  // (nothing of an earlier run may still read the old buffers)
                 int rc_c = sc.d_counts.alloc(need.counts);
                 if (!rc_c) rc_c = sc.d_prefix.alloc(need.prefix);
+                if (!rc_c && !list_ok) rc_c = sc.d_dense_q.alloc(need.dense_q);
                 if (rc_c) return rc_c;
             }
         }
@@ -1303,7 +1320,7 @@ int alloc_scratch_set(rtx_index *ix, uint32_t k) {
         if (ix->d_fbitmap.p && sc.d_fine_items.alloc(n.fine_items)) sc.d_fine_items.release();
         if (ix->rec_opt && ix->n_refs == ix->n_total) {  // the records path; without its buffers the run takes the dense epilogues
             if (sc.d_rec_nslots.alloc(n.rec_nslots) || sc.d_rec_slots.alloc(n.rec_slots) || sc.d_rec_cnt.alloc(n.rec_cnt) ||
-                sc.d_rec.alloc(n.rec) || sc.d_cnt_row.alloc(n.cnt_row) || sc.d_cnt_cursor.alloc(n.cnt_cursor))
+                sc.d_rec.alloc(n.rec) || sc.d_cnt_row.alloc(n.cnt_row) || sc.d_cnt_cursor.alloc(n.cnt_cursor) || sc.d_dense_q.alloc(n.dense_q))
                 sc.d_rec.release();
         }
     }

@@ -372,52 +372,22 @@ __global__ __launch_bounds__(64, RTX_PAIR_WAVES) void hit_count_pair_kernel(HitP
     pair_tile_block<NP, kPacked, kBounds>(p, lds_dw, pair, blockIdx.y, lane);
 }
 
-// The (pair, tile) blocks in which a query of the pair is live: entry = pair * ntiles + tile.  prune_kernel left the number of
-// live tiles of every pair; live_offsets_kernel (one workgroup) scans them, live_items_kernel (a thread per pair) writes the entries.
-__global__ __launch_bounds__(1024) void live_offsets_kernel(const uint32_t *__restrict__ pair_live, uint32_t np, uint32_t *__restrict__ off,
-                                                            uint32_t *__restrict__ n_items) {
-    // pieces of 8192 pairs, a thread takes eight neighbours (a wave reads and writes 2 KB in one stretch; with a thread per run of
-    // np / 1024 pairs every load and store of the one workgroup was a line of its own: 48 us per 32 768 pairs)
-    __shared__ uint32_t wsum[2][16];  // double-buffered: one barrier per piece
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    constexpr uint32_t kPer = 8;
-    uint32_t carry = 0, buf = 0;
-    for (uint32_t base = 0; base < np; base += 1024u * kPer, buf ^= 1u) {
-        const uint32_t i0 = base + tid * kPer;
-        uint32_t c[kPer], cnt = 0;
-#pragma unroll
-        for (uint32_t j = 0; j < kPer; j++) c[j] = i0 + j < np ? pair_live[i0 + j] : 0u;
-#pragma unroll
-        for (uint32_t j = 0; j < kPer; j++) cnt += c[j];
-        const uint32_t incl = wave_incl_scan_u32(cnt);
-        if (lane == 63u) wsum[buf][wave] = incl;
-        __syncthreads();
-        uint32_t o = carry + incl - cnt, tot = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 16u; w++) {
-            const uint32_t sw = wsum[buf][w];
-            o += w < wave ? sw : 0u;
-            tot += sw;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < kPer; j++) {
-            if (i0 + j < np) off[i0 + j] = o;
-            o += c[j];
-        }
-        carry += tot;
-    }
-    if (tid == 0u) n_items[0] = carry;
-    if (tid < 8u) n_items[1u + tid] = 0;  // the queues of the XCDs (hit_count_pair_kernel)
-}
-
+// The (pair, tile) blocks in which a query of the pair is live: entry = pair * ntiles + tile, from the live masks as prune_kernel (and the
+// fine pass) left them.  One launch: a workgroup counts the entries of its group of pairs, takes their stretch of the list with one atomic on
+// n_items[0] (zeroed by kmer_extract_kernel: KmerParams::zero) and writes them.  (A recount of the masks and a scan by ONE workgroup used
+// to hand every group its offset: three launches, 43 us of a sub-batch's critical chain, for 31 numbers.)
+//
 // Groups of 1024 pairs, and inside a group the entries TILE by tile: the workgroups of the counting pass that run at the same time then
 // work on few tiles and many neighbouring pairs, whatever the number of live tiles per pair -- rows are shared in L2 between pairs of
 // the same tile.  (Pair by pair, queries far from their best hit -- tens of live tiles each -- spread the resident workgroups over
 // all tiles of 57 pairs: 0.64 M queries/s at 10 % divergence where the two-dimensional grid, tile-major by construction, gave 1.36 M.)
-// The order of the pairs inside a (group, tile) run is whatever the LDS atomics make it: it decides nothing but scheduling.
+// The order of the GROUPS in the list is whatever order their atomics arrive in, and the order of the pairs inside a (group, tile) run is
+// whatever the LDS atomics make it: both decide nothing but scheduling -- every entry is a block of its own, counted by one wave into
+// outputs that no other block writes (or adds to with integer atomics).  A group stays contiguous and tile-major inside.
 __global__ __launch_bounds__(1024) void live_items_kernel(const uint32_t *__restrict__ live, uint32_t live_words, uint32_t nq, uint32_t ntiles,
-                                                          const uint32_t *__restrict__ off, uint32_t *__restrict__ items) {
-    extern __shared__ uint32_t tl[];  // [ntiles] entries of the group in the tile -> where they start -> cursor
+                                                          uint32_t *__restrict__ items, uint32_t *__restrict__ n_items,
+                                                          unsigned long long *__restrict__ stats) {
+    extern __shared__ uint32_t tl[];  // [ntiles] entries of the group in the tile -> where they start -> cursor | [1] where the group starts in the list
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t np = (nq + 1u) / 2u, g0 = blockIdx.x * 1024u, pair = g0 + tid;
     for (uint32_t T = tid; T < ntiles; T += 1024) tl[T] = 0;
@@ -443,10 +413,14 @@ __global__ __launch_bounds__(1024) void live_items_kernel(const uint32_t *__rest
             if (T0 + lane < ntiles) tl[T0 + lane] = running + incl - v;
             running += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
         }
+        if (lane == 0u) {  // the group's stretch of the list; the blocks of the counting pass (reporting)
+            tl[ntiles] = running ? atomicAdd(&n_items[0], running) : 0u;
+            if (stats && running) atomicAdd(&stats[(size_t)(blockIdx.x & (kPruneStatCopies - 1u)) * 8u + 2u], (unsigned long long)running);
+        }
     }
     __syncthreads();
     if (!valid) return;
-    const uint32_t base = off[g0];  // entries in front of the group
+    const uint32_t base = tl[ntiles];  // where the group starts
     for (uint32_t w = 0; w < nw; w++) {
         uint32_t bits = wa[w] | (hb ? wa[live_words + w] : 0u);
         while (bits) {
@@ -490,11 +464,10 @@ void launch_hit_count_pair(hipStream_t s, const HitParams &p, uint32_t nq, uint3
     else launch_hit_count_pair_np<11>(s, p, nq, ntiles);  // reads of 1 031 .. 2 054 bases: u16 counts
 }
 
-void launch_live_items(hipStream_t s, const uint32_t *live, uint32_t live_words, const uint32_t *pair_live, uint32_t nq, uint32_t ntiles, uint32_t *off,
-                       uint32_t *items, uint32_t *n_items) {
+void launch_live_items(hipStream_t s, const uint32_t *live, uint32_t live_words, uint32_t nq, uint32_t ntiles, uint32_t *items, uint32_t *n_items,
+                       unsigned long long *stats) {
     const uint32_t np = (nq + 1u) / 2u;
-    hipLaunchKernelGGL(live_offsets_kernel, dim3(1), dim3(1024), 0, s, pair_live, np, off, n_items);
-    hipLaunchKernelGGL(live_items_kernel, dim3((np + 1023u) / 1024u), dim3(1024), (size_t)ntiles * 4, s, live, live_words, nq, ntiles, off, items);
+    hipLaunchKernelGGL(live_items_kernel, dim3((np + 1023u) / 1024u), dim3(1024), ((size_t)ntiles + 1u) * 4, s, live, live_words, nq, ntiles, items, n_items, stats);
 }
 
 void launch_hit_count_pair_bounds(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t u_ntiles, int planes) {
@@ -516,7 +489,8 @@ void launch_hit_count_pair_bounds_items(hipStream_t s, const HitParams &p, uint3
 // The fine bounds pass: which pairs, which fine tiles.  A pair qualifies with kFineMinLive live tiles or more (prune_kernel's
 // number); it gets an item for every fine tile (eight tiles of the database) in which either query has a live tile.  The items are
 // grouped by fine tile -- the workgroups that run together then read one region of the fine bitmap: fine_count (entries per fine
-// tile), fine_scan (one thread: offsets, the header of the list), fine_scatter.
+// tile; the workgroup that finishes last: offsets, the header of the list), fine_scatter.  The order inside a fine tile decides
+// nothing but scheduling.
 // ---------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t fine_pair_mask(const uint32_t *live, uint32_t live_words, uint32_t pair, uint32_t nq, uint32_t U) {
     const uint32_t T0 = U * 8u;
@@ -525,8 +499,10 @@ __device__ __forceinline__ uint32_t fine_pair_mask(const uint32_t *live, uint32_
     if (pair * 2u + 1u < nq) m |= (wa[live_words] >> (T0 & 31u)) & 0xFFu;
     return m;
 }
+// cnt [f_ntiles] and n_items [9] come in zeroed (KmerParams::zero).  n_items[0] serves as the ticket counter of the workgroups first: the one
+// that draws the last ticket finds every count in place, turns them into the offsets of the fine tiles and leaves the length of the list there.
 __global__ __launch_bounds__(256) void fine_count_kernel(const uint32_t *__restrict__ live, uint32_t live_words, const uint32_t *__restrict__ pair_live,
-                                                         uint32_t nq, uint32_t f_ntiles, uint32_t *__restrict__ cnt) {
+                                                         uint32_t nq, uint32_t f_ntiles, uint32_t *__restrict__ cnt, uint32_t *__restrict__ n_items) {
     // one atomic per wave and fine tile (the lanes that hold an item are counted with a ballot): at 10 % divergence every pair qualifies, and
     // 32 768 atomics of a launch on each of eight addresses took 0.4 ms
     const uint32_t pair = blockIdx.x * 256u + threadIdx.x, np = (nq + 1u) / 2u, lane = threadIdx.x & 63u;
@@ -535,16 +511,22 @@ __global__ __launch_bounds__(256) void fine_count_kernel(const uint32_t *__restr
         const unsigned long long b = __ballot(on && fine_pair_mask(live, live_words, pair, nq, U) != 0u);
         if (b && lane == (uint32_t)__builtin_ctzll(b)) atomicAdd(&cnt[U], (uint32_t)__popcll(b));
     }
-}
-__global__ void fine_scan_kernel(uint32_t *__restrict__ cnt, uint32_t f_ntiles, uint32_t *__restrict__ n_items) {  // one thread
-    uint32_t run = 0;
-    for (uint32_t U = 0; U < f_ntiles; U++) {
-        const uint32_t c = cnt[U];
-        cnt[U] = run;  // becomes the cursor of fine tile U
-        run += c;
+    __shared__ uint32_t s_last;
+    __threadfence();  // this workgroup's counts are in place before its ticket is drawn
+    __syncthreads();
+    if (threadIdx.x == 0u) s_last = atomicAdd(&n_items[0], 1u) == gridDim.x - 1u ? 1u : 0u;
+    __syncthreads();
+    if (s_last == 0u || threadIdx.x >= 64u) return;
+    __threadfence();
+    uint32_t run = 0;  // one wave of the last workgroup: the exclusive scan over the fine tiles
+    for (uint32_t U0 = 0; U0 < f_ntiles; U0 += 64) {
+        const uint32_t U = U0 + lane;
+        const uint32_t c = U < f_ntiles ? __hip_atomic_load(&cnt[U], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;  // (written by atomics of other CUs: not from this CU's L1)
+        const uint32_t incl = wave_incl_scan_u32(c);
+        if (U < f_ntiles) cnt[U] = run + incl - c;  // becomes the cursor of fine tile U
+        run += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
     }
-    n_items[0] = run;
-    for (uint32_t x = 1; x <= 8u; x++) n_items[x] = 0;  // the queues of the XCDs
+    if (lane == 0u) n_items[0] = run;  // (the queues of the XCDs, n_items[1 .. 8], stay zero)
 }
 __global__ __launch_bounds__(256) void fine_scatter_kernel(const uint32_t *__restrict__ live, uint32_t live_words, const uint32_t *__restrict__ pair_live,
                                                            uint32_t nq, uint32_t f_ntiles, uint32_t *__restrict__ cursor, uint32_t *__restrict__ items) {
@@ -561,40 +543,26 @@ __global__ __launch_bounds__(256) void fine_scatter_kernel(const uint32_t *__res
         if (has) items[base + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = pair * f_ntiles + U;
     }
 }
-// live tiles per pair again, from the masks as the fine pass left them (live_offsets_kernel sizes the list of the counting pass with them)
-__global__ __launch_bounds__(256) void pair_live_recount_kernel(const uint32_t *__restrict__ live, uint32_t live_words, uint32_t nq, uint32_t ntiles,
-                                                                uint32_t *__restrict__ pair_live, unsigned long long *__restrict__ stats) {
-    const uint32_t pair = blockIdx.x * 256u + threadIdx.x, np = (nq + 1u) / 2u;
-    uint32_t n = 0;
-    if (pair < np) {
-        const uint32_t *wa = live + (size_t)(pair * 2u) * live_words;
-        const bool hb = pair * 2u + 1u < nq;
-        for (uint32_t w = 0; w < (ntiles + 31u) >> 5; w++) n += (uint32_t)__popc(wa[w] | (hb ? wa[live_words + w] : 0u));
-        pair_live[pair] = n;
-    }
-    if (stats) {  // reporting: the (pair, tile) blocks the counting pass is left with
-        n = wave_incl_scan_u32(n);
-        if ((threadIdx.x & 63u) == 63u && n) atomicAdd(&stats[(size_t)(blockIdx.x & (kPruneStatCopies - 1u)) * 8u + 2u], (unsigned long long)n);
-    }
-}
-
-// cnt: [f_ntiles] scratch; items: [pairs * f_ntiles]; n_items: [9]
-void launch_fine_bounds(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t ntiles, uint32_t f_ntiles, uint32_t *pair_live, uint32_t *cnt,
+#ifndef RTX_FINE_GRID_CAP
+#define RTX_FINE_GRID_CAP 4096  // workgroups of the fine pass at most: one residency
+#endif
+// cnt: [f_ntiles], zeroed; items: [pairs * f_ntiles]; n_items: [9], zeroed.  The masks the pass leaves are read by live_items_kernel.
+void launch_fine_bounds(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t f_ntiles, const uint32_t *pair_live, uint32_t *cnt,
                         uint32_t *items, uint32_t *n_items, int planes) {
     const uint32_t np = (nq + 1u) / 2u, nb = (np + 255u) / 256u;
-    (void)hipMemsetAsync(cnt, 0, (size_t)f_ntiles * 4, s);
-    hipLaunchKernelGGL(fine_count_kernel, dim3(nb), dim3(256), 0, s, p.live, p.live_words, pair_live, nq, f_ntiles, cnt);
-    hipLaunchKernelGGL(fine_scan_kernel, dim3(1), dim3(1), 0, s, cnt, f_ntiles, n_items);
+    hipLaunchKernelGGL(fine_count_kernel, dim3(nb), dim3(256), 0, s, p.live, p.live_words, pair_live, nq, f_ntiles, cnt, n_items);
     hipLaunchKernelGGL(fine_scatter_kernel, dim3(nb), dim3(256), 0, s, p.live, p.live_words, pair_live, nq, f_ntiles, cnt, items);
     HitParams fp = p;
     fp.items = items;
     fp.n_items = n_items;
-    // as many workgroups as a pass of the counting list: the list is walked through the queues of the XCDs
-    const dim3 grid((uint32_t)((std::min<uint64_t>((uint64_t)np * f_ntiles, std::max<uint64_t>((uint64_t)RTX_ITEM_GRID_HALVES * np / 2u, 2048ull)) + 7u) & ~7ull));
+    // a grid of one residency, as launch_hit_count_pair_bounds_items: a long list is walked through the queues of the XCDs.  (It used to be the
+    // counting pass's 2 x pairs.  Measured at 4096 / 8192 / 16384 / 65536 workgroups, on the bench workload -- 0.05 items per pair -- and at 10 %
+    // divergence -- every pair qualifies: no difference beyond the spread of the runs either way, tools/NOTES.md.  The 100 us of a launch on the
+    // bench workload are the time of its few blocks, not the dispatch of the workgroups that find none.)
+    const dim3 grid((uint32_t)((std::min<uint64_t>((uint64_t)np * f_ntiles, (uint64_t)RTX_FINE_GRID_CAP) + 7u) & ~7ull));
     if (planes <= 8) hipLaunchKernelGGL((hit_count_pair_kernel<8, true, 2, true>), grid, dim3(64), kPairLdsBytes, s, fp);
     else if (planes <= 10) hipLaunchKernelGGL((hit_count_pair_kernel<10, true, 2, true>), grid, dim3(64), kPairLdsBytes, s, fp);
     else hipLaunchKernelGGL((hit_count_pair_kernel<11, false, 2, true>), grid, dim3(64), kPairLdsBytes, s, fp);
-    hipLaunchKernelGGL(pair_live_recount_kernel, dim3(nb), dim3(256), 0, s, p.live, p.live_words, nq, ntiles, pair_live, p.fine_stats);
 }
 
 }  // namespace rtx

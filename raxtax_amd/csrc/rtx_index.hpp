@@ -332,13 +332,14 @@ struct rtx_index {
         DevBuf<uint16_t> d_rec_nslots, d_rec_slots;
         DevBuf<uint32_t> d_rec_cnt, d_rec;
         DevBuf<uint32_t> d_cnt_row, d_cnt_cursor;  // [B] row of the counts buffer per query | [1] rows handed out (HitParams::cnt_row)
+        DevBuf<uint32_t> d_dense_q;                // [cnt_rows] the query that holds each row handed out (PruneParams::dense_q)
         // every buffer of a set, once: what release_all and bytes() (and whoever else wants all of them) walk
         template <class S, class F>
         static void each(S &s, F &&f) {
             f(s.d_kmers); f(s.d_counts); f(s.d_tilemax); f(s.d_rows); f(s.d_t); f(s.d_nrows); f(s.d_hist); f(s.d_order); f(s.d_srows); f(s.d_nsparse);
             f(s.d_dmask); f(s.d_table_z); f(s.d_prefix); f(s.d_urec); f(s.d_nu); f(s.d_live); f(s.d_best_key); f(s.d_items); f(s.d_tile_ub); f(s.d_prune_thr);
             f(s.d_prune_i1); f(s.d_best); f(s.d_heavy); f(s.d_heavy_items); f(s.d_fine_items); f(s.d_rec_nslots); f(s.d_rec_slots); f(s.d_rec_cnt); f(s.d_rec);
-            f(s.d_cnt_row); f(s.d_cnt_cursor);
+            f(s.d_cnt_row); f(s.d_cnt_cursor); f(s.d_dense_q);
         }
         void release_all() { each(*this, [](auto &b) { b.release(); }); }
         // HBM of the set as rtx_index_workspace_bytes reports it.  d_cnt_row and d_cnt_cursor are left out: the reported figure never held them
@@ -587,6 +588,18 @@ int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of 
 // of the sub-batch being enqueued: the kernels index by nq.
 
 // A list of (pair, tile) items as the kernels that fill it and walk it lay it out: [pairs x tiles] items | [1] their number | [8] queue per XCD
+//
+// The header (count(): n_items[0 .. 8]) of a list that is built by more than one workgroup holds counters that are ADDED to, so it has to be zero
+// when the sub-batch starts.  The invariant, for the counting list (ItemsLayout) and the fine list (FineItemsLayout, with its cursors):
+//   zeroed by  kmer_extract_kernel<false>, workgroup 0 (KmerParams::zero, filled in by enqueue_kmer): the first kernel of a sub-batch on its
+//              scratch set, enqueued behind the wait for the set's previous user (ev_back / ev_set_free in enqueue_batch; one stream otherwise).
+//              A reference shard's part 2 (rtx_shard_count) finds them as the kmer_extract of its part 1 left them: nothing in between adds.
+//              The offsets depend on nq, so enqueue_kmer and enqueue_hit of a sub-batch must be handed the same SubBatch -- they are.
+//   added to   [0] by live_items_kernel (a group's stretch of the list) or fine_count_kernel (tickets, then the length, stored by the last
+//              workgroup); [1 .. 8] by the ONE launch of hit_count_pair_kernel that walks the list.  Each list is walked once per sub-batch.
+//   read by    that launch of hit_count_pair_kernel ([0]: the length).  Nothing resets them afterwards: the next sub-batch's kmer_extract does.
+// Both scratch sets and the chunks of a run-ahead have lists of their own (they live in the set), so no two sub-batches in flight share a header.
+// The heavy list (HeavyItemsLayout) is built by one workgroup, which stores its header itself (heavy_items_kernel).
 struct ItemList {
     size_t np, ntiles;  // pairs of queries; tiles per pair
     ItemList(size_t nq, size_t tiles) : np((nq + 1u) / 2u), ntiles(tiles) {}
@@ -595,11 +608,10 @@ struct ItemList {
     uint32_t *items(uint32_t *p) const { return p; }
     uint32_t *count(uint32_t *p) const { return p + cap(); }
 };
-struct ItemsLayout : ItemList {  // d_items (tiles of the database): the list | [pairs] live tiles per pair | [pairs] offsets (launch_live_items)
+struct ItemsLayout : ItemList {  // d_items (tiles of the database): the list (launch_live_items) | [pairs] live tiles per pair (prune_kernel)
     using ItemList::ItemList;
-    size_t total() const { return end() + 2u * np; }
+    size_t total() const { return end() + np; }
     uint32_t *pair_live(uint32_t *p) const { return p + end(); }
-    uint32_t *offsets(uint32_t *p) const { return p + end() + np; }
 };
 struct FineItemsLayout : ItemList {  // d_fine_items (tiles of the fine union bitmap): the list | [tiles] cursors (launch_fine_bounds)
     using ItemList::ItemList;
@@ -628,6 +640,7 @@ struct ScratchNeed {
     size_t tile_ub = 0, best_key = 0, prune_thr = 0, prune_i1 = 0, best = 0, live = 0, items = 0;                   // ... tile pruning
     size_t heavy = 0, heavy_items = 0, fine_items = 0;                                                              // ... two-level bounds, fine bounds
     size_t rec_nslots = 0, rec_slots = 0, rec_cnt = 0, rec = 0, cnt_row = 0, cnt_cursor = 0;                        // ... the records path and the diet
+    size_t dense_q = 0;                                                                                             // ... the diet, by its rows (add_class)
     ScratchNeed &set_queries(const rtx_index *ix, size_t B) {  // a sub-batch of B queries, whatever their class
         const size_t nt = ix->ntiles;
         t = nrows = order = best_key = prune_thr = prune_i1 = rec_nslots = cnt_row = B;
@@ -653,6 +666,7 @@ struct ScratchNeed {
         up(dmask, B * ix->ntiles * (kc.rstride / 64));
         up(counts, counts_elems(ix, kc.planes, cnt_rows));
         up(prefix, cnt_rows * ix->n_bnd_local);
+        up(dense_q, cnt_rows);
         up(hist, B * kc.hstride);
         up(urec, ((B + 1u) / 2u) * 2u * kc.rstride);
         if (kc.huge) up(prob_scratch, B * ((prob_table_lds_bytes(kc.tmax) + 7) / 8));

@@ -167,6 +167,11 @@ __global__ __launch_bounds__(64) void kmer_extract_kernel(KmerParams p) {
         uint32_t *h = p.hist + (size_t)q * p.hstride;
         for (uint32_t i = lane; i < p.hstride; i += 64) h[i] = 0;
     }
+    if (q == 0u) {  // the counters the later kernels of the sub-batch add to (KmerParams::zero)
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+            for (uint32_t i = lane; i < p.zero_n[k]; i += 64) p.zero[k][i] = 0;
+    }
     __syncthreads();
 
     if (len >= 8) {
@@ -906,7 +911,18 @@ template <int NW, bool TZ_LDS, bool PACKED>
 __global__ __launch_bounds__(NW * 64) void taxon_prefix_kernel(PrefixParams p) {
     extern __shared__ double tz_lds[];
     __shared__ double wsum[2][NW];  // double-buffered: one barrier per sweep
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    uint32_t q = blockIdx.x;
+    if (p.dense_q) {
+        // the rows of the counts buffer on their diet: the grid is the rows, and row r names its query.  (A workgroup per QUERY came up 61 k
+        // times per launch of the bench workload to find 99 % of the queries on the records path and leave.)
+        const uint32_t handed = *p.cnt_cursor;
+        if (handed > p.cnt_cap && p.fuse_walk && tid == 0u)  // the rows ran out (the host repeats the run): the queries left without one get no result rows
+            for (uint32_t o = blockIdx.x; o < p.nq; o += gridDim.x)
+                if ((!p.rec_nslots || p.rec_nslots[o] == 0u) && p.cnt_row[o] == 0xFFFFFFFFu) { p.walk.n_rows[p.q0 + o] = 0; p.walk.row_start[p.q0 + o] = 0; }
+        if (q >= (handed < p.cnt_cap ? handed : p.cnt_cap)) return;
+        q = p.dense_q[q];
+    }
     const uint64_t gq = p.q0 + q;
     if (p.rec_nslots && p.rec_nslots[q] != 0u) return;  // a query on the records path: records_tail_kernel has it (rtx_records.hip)
     // a query of the dense path that was left without a row of the counts buffer (HitParams::cnt_row: the rows ran out, the host repeats the
@@ -1245,8 +1261,9 @@ void launch_taxon_prefix(hipStream_t s, const PrefixParams &p, uint32_t nq) {
     // in flight) beat four (N = 500k, per 1 M queries: 18.2 ms with four, 14.5 with two, 15.2 with one).  A run that sweeps every tile: two as
     // well since round 5 (131 072 short barcodes against 14 tiles: 11.7 ms with eight, 8.7 with four, 7.6 with two, 8.8 with one; 65 536 COI reads
     // against 62 tiles, most of them skipped by their largest count: 1.2 with four, 0.8 with two) -- the kernel is short of issue slots, not of waves
-    if (p.prune_thr) launch_taxon_prefix_nw<RTX_PREFIX_NW_PRUNED>(s, p, nq, lds);
-    else launch_taxon_prefix_nw<RTX_PREFIX_NW>(s, p, nq, lds);
+    const uint32_t grid = p.dense_q ? std::min(nq, p.cnt_cap) : nq;  // (the diet: a workgroup per row of the counts buffer)
+    if (p.prune_thr) launch_taxon_prefix_nw<RTX_PREFIX_NW_PRUNED>(s, p, grid, lds);
+    else launch_taxon_prefix_nw<RTX_PREFIX_NW>(s, p, grid, lds);
 }
 void launch_lineage_walk(hipStream_t s, const WalkParams &p, uint32_t nq) {
     hipLaunchKernelGGL(lineage_walk_kernel, dim3(nq), dim3(64), 0, s, p);

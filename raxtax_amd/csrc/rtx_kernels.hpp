@@ -229,6 +229,11 @@ struct KmerParams {
     uint32_t mode;           // 0: everything; 1: k-mers and row list; 2: the per-tile lists of the live tiles (after a launch with 1)
     const uint32_t *live;    // mode 2: [B][live_words] a mask per query (rtx_prune.hip)
     uint32_t live_words;
+    // modes 0 and 1: the counters of the scratch set that the later kernels of the sub-batch add to (the headers of the item lists, the cursors of
+    // the fine list, the cursor of the diet's rows), zeroed by workgroup 0 -- the first kernel of a sub-batch, behind the wait for the set's
+    // previous user, instead of a fill launch in front of each of them (rtx_index.hpp: ItemList).  Unused entries: n = 0
+    uint32_t *zero[3];
+    uint32_t zero_n[3];
 };
 
 // The RECORDS path (round 5).  A pruned query (threshold u) only ever needs its references with a count ABOVE u: everything else is
@@ -376,7 +381,7 @@ struct PruneParams {
     uint32_t hstride;
     uint32_t *live;           // [B][live_words] bit T: tile T is counted for the query
     uint32_t live_words;
-    uint32_t *pair_live;      // [pairs] tiles counted for either query of the pair (live_offsets_kernel turns them into the list of blocks) or null
+    uint32_t *pair_live;      // [pairs] tiles counted for either query of the pair (fine_count_kernel: which pairs go through the fine pass) or null
     uint16_t *thr_out;        // [B] the threshold of every query (0: not pruned, every tile is counted)
     uint16_t *i1_out;         // [B] i* + 1 of every query with a threshold: Z holds less than eps = 1e-10 at i <= i* (prob_lookup starts there)
     unsigned long long *stats;  // [kPruneStatCopies][8]: [0] += live tiles, [1] += pairs ... (reporting) or null
@@ -385,8 +390,9 @@ struct PruneParams {
     RecordRef rec;              // rec.nslots != null: queries with a threshold and at most rec_max_slots live tiles take the records path
     uint32_t rec_max_slots;
     uint32_t *cnt_row;          // [B] out: the row of the counts buffer of every query that takes the dense epilogues (HitParams::cnt_row) or null
-    uint32_t *cnt_cursor;       // [1] rows handed out in this launch (zeroed before it)
+    uint32_t *cnt_cursor;       // [1] rows handed out in this launch (zeroed before it: KmerParams::zero)
     uint32_t cnt_cap;           // rows there are
+    uint32_t *dense_q;          // [cnt_cap] out: the query that holds row r (taxon_prefix_kernel is launched over the rows, not over the queries) or null
     uint32_t *flags_out;        // bit2: the rows ran out
 };
 constexpr uint32_t kPruneDetailWords = 72;
@@ -512,6 +518,12 @@ struct PrefixParams {
     WalkParams walk;
     const uint16_t *rec_nslots; // [B] records path (RecordRef::nslots): a query with slots is left to records_tail_kernel; or null
     const uint32_t *cnt_row;    // [B] row of the counts buffer per query (HitParams::cnt_row) or null: row q
+    // with the rows on their diet the grid is the ROWS (cnt_cap workgroups): workgroup r takes the query prune_kernel gave row r, the workgroups
+    // behind the rows handed out leave.  Null: a workgroup per query
+    const uint32_t *dense_q;    // [cnt_cap] PruneParams::dense_q
+    const uint32_t *cnt_cursor; // [1] rows handed out (past cnt_cap: the rows ran out, the queries left without one are written off here)
+    uint32_t cnt_cap;
+    uint32_t nq;
 };
 
 
@@ -548,13 +560,15 @@ void launch_hit_count(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t n
 void launch_pair_union(hipStream_t s, const uint32_t *rows, const uint32_t *nrows, uint32_t rstride, uint32_t nq, uint2 *urec,
                        uint32_t *nu, uint32_t ustride);
 void launch_hit_count_pair(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t ntiles, int planes);  // 8 (every t <= 255) or 10 bit planes
-// the list of the live (pair, tile) blocks from the masks and the per-pair numbers prune_kernel left: off = [pairs] scratch
-void launch_live_items(hipStream_t s, const uint32_t *live, uint32_t live_words, const uint32_t *pair_live, uint32_t nq, uint32_t ntiles, uint32_t *off,
-                       uint32_t *items, uint32_t *n_items);
+// the list of the live (pair, tile) blocks from the masks prune_kernel (and the fine pass) left; n_items: [9] zeroed (KmerParams::zero);
+// stats: += the blocks of the list in slot 2 (reporting) or null
+void launch_live_items(hipStream_t s, const uint32_t *live, uint32_t live_words, uint32_t nq, uint32_t ntiles, uint32_t *items, uint32_t *n_items,
+                       unsigned long long *stats);
 void launch_hit_count_pair_bounds(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t u_ntiles, int planes);
 void launch_hit_count_pair_bounds_items(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t u_ntiles, int planes);  // ... over a list of (pair, union tile) items (p.items)
-// the fine bounds pass over the pairs with many live tiles (p: the fine union bitmap, live masks, thresholds, histogram); updates pair_live
-void launch_fine_bounds(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t ntiles, uint32_t f_ntiles, uint32_t *pair_live, uint32_t *cnt,
+// the fine bounds pass over the pairs with many live tiles (p: the fine union bitmap, live masks, thresholds, histogram); pair_live: prune_kernel's
+// numbers; cnt [f_ntiles] and n_items [9]: zeroed (KmerParams::zero)
+void launch_fine_bounds(hipStream_t s, const HitParams &p, uint32_t nq, uint32_t f_ntiles, const uint32_t *pair_live, uint32_t *cnt,
                         uint32_t *items, uint32_t *n_items, int planes);  // ... on the union bitmap: bounds_epilogue
 size_t prob_table_lds_bytes(uint32_t tmax);
 void launch_prob_table(hipStream_t s, const ProbParams &p, uint32_t nq);
