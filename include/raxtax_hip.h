@@ -899,9 +899,21 @@ int rtx_debug_run_mode(rtx_index *index, uint64_t query, uint32_t *n_segments);
 int rtx_debug_prune_detail(rtx_index *index, uint64_t query, uint32_t *out /*72*/);
 /* Lineage::new(label, tree, probs).evaluate() (src/lineage.rs:61-112) on a caller-supplied
  * probability vector: runs taxon_prefix + lineage_walk + the host finalisation for one
- * pseudo-query.  Lets the reference's lineage KATs pin the device walk.  Small trees only
- * (n_refs up to a few thousand: the workspace is sized as for a query with n_refs k-mers). */
+ * pseudo-query.  Lets the reference's lineage KATs pin the device walk.  Mode 0 of
+ * rtx_debug_evaluate_mode below (the workspace is sized as for a query with as many k-mers as probs has distinct values). */
 int rtx_debug_evaluate(rtx_index *index, const double *probs /*n_refs*/, rtx_result_view *out);
+/* The same evaluation through the path a run takes.  The pseudo-query is an honest one: the count of reference r is the rank of
+ * probs[r] among the DISTINCT values of the vector (ascending; rank 0 is the value 0.0 where it occurs), the table holds the distinct
+ * values, t = their number - 1, and the largest "count" of a tile of 8192 references is its largest rank.  At most 65 536 distinct
+ * values (counts are 16 bits wide), whatever the number of references; rtx_debug_evaluate is mode 0.
+ *   mode 0: taxon_prefix without tile maxima, the table in global memory, the lineage walk as a kernel of its own
+ *   mode 1: the walk fused into taxon_prefix, as on every whole-database handle; no tile maxima.  The table is copied to LDS where a run
+ *           would copy it (a table row of at most 16 KiB: up to 2048 distinct values), else read from global memory
+ *   mode 2: mode 1 with tile maxima: tiles that hold no non-zero probability are not swept, the boundaries inside them reach the walk
+ *           as gaps (up to six; further ones are written out)
+ * table_in_lds (may be NULL): 1 if the launch took the table from LDS.  With probabilities that are multiples of 2^-40 and sum to 1
+ * every partial sum is exact in any order, so the rows must equal the reference's bit for bit, ties included. */
+int rtx_debug_evaluate_mode(rtx_index *index, const double *probs /*n_refs*/, uint32_t mode, rtx_result_view *out, uint32_t *table_in_lds);
 
 /* ------------------------------------------------------------------------- */
 /* Host mirror of the output formatting (src/lineage.rs:17-48, utils.rs:62-89) */

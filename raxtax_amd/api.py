@@ -730,11 +730,15 @@ class Index:
                 "tiles_above_threshold_per_query": int(out[8]) / max(int(out[9]), 1), "queries_with_threshold": int(out[9]),
                 "record_queries": int(out[14]), "records_per_record_query": int(out[13]) / max(int(out[14]), 1), "record_slow_path_queries": int(out[15])}
 
-    def debug_evaluate(self, probs) -> Result:
-        """Lineage::new(label, tree, probs).evaluate() on the device (lineage.rs:61-112)."""
+    def debug_evaluate(self, probs, mode: int = 0) -> Result:
+        """Lineage::new(label, tree, probs).evaluate() on the device (lineage.rs:61-112).  mode 0: the walk as a kernel of its own; 1: fused into
+        taxon_prefix, as a run has it; 2: with tile maxima as well, so that tiles without a probability are skipped (rtx_debug_evaluate_mode).
+        last_evaluate_table_in_lds tells whether the launch read the probability table from LDS."""
         probs = np.ascontiguousarray(probs, dtype=np.float64)
         assert len(probs) == self.n_refs
-        check(self._lib.rtx_debug_evaluate(self._h, ptr(probs, f64p), C.byref(self._view)))
+        in_lds = C.c_uint32()
+        check(self._lib.rtx_debug_evaluate_mode(self._h, ptr(probs, f64p), mode, C.byref(self._view), C.byref(in_lds)))
+        self.last_evaluate_table_in_lds = bool(in_lds.value)
         return Result(self._view)
 
     def format_query(self, q: int, label: str, seq: np.ndarray, exact_ids: np.ndarray, flags: int = 0,

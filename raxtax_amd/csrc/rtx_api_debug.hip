@@ -450,39 +450,64 @@ int rtx_debug_probs(rtx_index *ix, uint64_t query, double *probs) {
     return RTX_OK;
 }
 
-// Runs taxon_prefix + lineage_walk + host finalisation on a caller-supplied probability vector
+// Runs taxon_prefix + the lineage walk + finalisation on a caller-supplied probability vector
 // (Lineage::new(label, tree, probs).evaluate(), lineage.rs:61-112), so that the reference's
-// lineage KATs (lineage.rs:192-334) pin the device walk directly.  n_refs <= 65535.
-int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out) {
+// lineage KATs (lineage.rs:192-334) and exact inputs pin the device walk directly.
+//
+// The pseudo-query is an honest one: count_r = the rank of p_r among the DISTINCT values of the vector (ascending; rank 0 is the value 0.0
+// where it occurs), table[c] = the c-th distinct value, t = the number of distinct values - 1, tile_max[T] = the largest rank in tile T --
+// so "the largest count of the tile" means what it means in a run, and a tile without a non-zero probability is a tile taxon_prefix skips.
+// At most 65 536 distinct values (counts are u16), whatever the number of references.
+//   mode 0: taxon_prefix without tile maxima, the table in global memory, lineage_walk_kernel as a kernel of its own
+//   mode 1: the walk fused into taxon_prefix (what a whole-database handle runs: enqueue_prob_prefix), no tile maxima; the table in LDS
+//           where enqueue_prob_prefix would put it there (hstride * 8 <= 16 KiB)
+//   mode 2: mode 1 with tile maxima: unswept runs of tiles reach the walk as gaps (rtx_walk.hpp: PrefixGaps)
+static int debug_evaluate_impl(rtx_index *ix, const double *probs, uint32_t mode, rtx_result_view *out, uint32_t *table_in_lds) {
     int rc = bind(ix);
     if (rc) return rc;
     if (!probs || !out) { set_error("null argument"); return RTX_ERR_INVALID; }
+    if (mode > 2u) { set_error("rtx_debug_evaluate_mode: mode %u (0, 1 or 2)", mode); return RTX_ERR_INVALID; }
     const uint64_t N = ix->n_refs;
-    if (N > 65535) { set_error("rtx_debug_evaluate supports at most 65535 references"); return RTX_ERR_INVALID; }
+    if (mode != 0u && ix->n_bnd_local != ix->n_bnd) { set_error("rtx_debug_evaluate_mode: the fused walk needs a whole-database handle"); return RTX_ERR_STATE; }
+    for (uint64_t r = 0; r < N; r++)
+        if (probs[r] != probs[r]) { set_error("rtx_debug_evaluate: probability %llu is not a number", (unsigned long long)r); return RTX_ERR_INVALID; }
+    std::vector<double> table(probs, probs + N);
+    std::sort(table.begin(), table.end());
+    table.erase(std::unique(table.begin(), table.end()), table.end());
+    const uint64_t D = table.size();
+    if (D > 65536) { set_error("rtx_debug_evaluate supports at most 65536 distinct probabilities (got %llu)", (unsigned long long)D); return RTX_ERR_INVALID; }
     ix->uploaded = ix->ran = ix->synced = false;
-    if ((rc = prepare_workspace_single(ix, 1, std::max<uint64_t>(N, 8), 0))) return rc;
+    if ((rc = prepare_workspace_single(ix, 1, std::max<uint64_t>(D - 1, 8), 0))) return rc;
     const SubBatch b = sub_batch_of(ix, 0, false);  // the one pseudo-query, in the one class
+    if (b.cls->hstride < D) { set_error("internal: table row of rtx_debug_evaluate too short"); return RTX_ERR_STATE; }
     ix->last_set = b.set;
     ix->sum_query_bytes = 0;
     record_batch(ix);
     rtx_index::ResultSet &res = ix->res();
+    rtx_index::Scratch &sc = ix->sc[ix->last_set];
     if ((rc = order_batch(ix, false))) return rc;
-    if ((rc = ix->sc[0].d_counts.alloc(ix->npad))) return rc;  // u16 format here whatever the batch format would be
+    if ((rc = sc.d_counts.alloc(ix->npad))) return rc;  // u16 format here whatever the batch format would be
+    if (mode == 2u && sc.d_tilemax.n < ix->ntiles) { set_error("internal: no room for the tile maxima of rtx_debug_evaluate"); return RTX_ERR_STATE; }
     std::vector<uint16_t> counts(ix->npad, 0);
-    for (uint64_t r = 0; r < N; r++) counts[r] = (uint16_t)r;  // count_r = r, table[r] = probs[r]
+    std::vector<uint16_t> tile_max(ix->ntiles, 0);
+    for (uint64_t r = 0; r < N; r++) {
+        const uint16_t c = (uint16_t)(std::lower_bound(table.begin(), table.end(), probs[r]) - table.begin());
+        counts[r] = c;
+        tile_max[r >> 13] = std::max(tile_max[r >> 13], c);
+    }
     double gs = 0.0;
     for (uint64_t r = 0; r < N; r++) { const double d = probs[r] - 1.0 / (double)N; gs += d * d; }
     gs = std::sqrt(gs);
     const uint8_t ok = RTX_Q_OK;
     hipStream_t s = ix->stream;
-    RTX_HIP(hipMemcpy(ix->sc[ix->last_set].d_counts.p, counts.data(), ix->npad * 2, hipMemcpyHostToDevice));
-    RTX_HIP(hipMemcpy(ix->sc[ix->last_set].d_table_z.p, probs, N * 8, hipMemcpyHostToDevice));
+    RTX_HIP(hipMemcpy(sc.d_counts.p, counts.data(), ix->npad * 2, hipMemcpyHostToDevice));
+    RTX_HIP(hipMemcpy(sc.d_table_z.p, table.data(), D * 8, hipMemcpyHostToDevice));
+    if (mode == 2u) RTX_HIP(hipMemcpy(sc.d_tilemax.p, tile_max.data(), (size_t)ix->ntiles * 2, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(res.d_status.p, &ok, 1, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(res.d_gs.p, &gs, 8, hipMemcpyHostToDevice));
-    {   // taxon_prefix scans table[0 .. t] of the slot for the smallest count with a probability: the pseudo-query's
-        // "counts" are 0 .. N-1 (the slot's t was left to whatever the allocation held: an out-of-bounds scan)
-        const uint32_t t_pseudo = (uint32_t)N - 1u;
-        RTX_HIP(hipMemcpy(ix->sc[ix->last_set].d_t.p, &t_pseudo, 4, hipMemcpyHostToDevice));
+    {   // taxon_prefix scans table[0 .. t] of the slot for the smallest count with a probability
+        const uint32_t t_pseudo = (uint32_t)D - 1u;
+        RTX_HIP(hipMemcpy(sc.d_t.p, &t_pseudo, 4, hipMemcpyHostToDevice));
     }
     RTX_HIP(hipMemset(res.d_t_all.p, 0, 4));
     RTX_HIP(hipMemset(res.d_nrows_all.p, 0, 4));
@@ -491,25 +516,10 @@ int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out)
     RTX_HIP(hipMemset(res.d_cursor.p, 0, 16));  // both cursors: the download reads the side classes' one as well (left to the allocation it sized the host arrays by garbage)
     RTX_HIP(hipMemset(res.d_flags.p, 0, 4));
     RTX_HIP(hipMemset(res.d_fin_cursor.p, 0, 16));
-    PrefixParams fp{};
-    fp.status = res.d_status.p;
-    fp.t = ix->sc[ix->last_set].d_t.p;
-    fp.tz_in_lds = 0;  // the pseudo-query's "counts" index the probability vector directly
-    fp.q0 = 0;
-    fp.counts = ix->sc[ix->last_set].d_counts.p;
-    fp.npad = ix->npad;
-    fp.table_z = ix->sc[ix->last_set].d_table_z.p;
-    fp.hstride = b.cls->hstride;
-    fp.n_refs = N;
-    fp.bnd_bits = ix->d_bnd_bits.p;
-    fp.bnd_rank = ix->d_bnd_rank.p;
-    fp.prefix = ix->sc[ix->last_set].d_prefix.p;
-    fp.n_bnd = ix->n_bnd_local;
-    launch_taxon_prefix(s, fp, 1);
-    WalkParams wp{};
+    WalkParams wp{};  // (walk_params of rtx_api_batch.hip, for a run that has no side classes: the whole arena, no sub-allocators for one walk)
     wp.status = res.d_status.p;
     wp.q0 = 0;
-    wp.prefix = ix->sc[ix->last_set].d_prefix.p;
+    wp.prefix = sc.d_prefix.p;
     wp.n_bnd = ix->n_bnd;
     wp.rec = ix->d_noderec.p;
     wp.arena = res.d_arena.p;
@@ -518,13 +528,39 @@ int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out)
     wp.n_rows = res.d_n_rows.p;
     wp.row_start = res.d_row_start.p;
     wp.flags_out = res.d_flags.p;
-    launch_lineage_walk(s, wp, 1);
+    PrefixParams fp{};
+    fp.status = res.d_status.p;
+    fp.t = sc.d_t.p;
+    fp.tz_in_lds = mode != 0u && (size_t)b.cls->hstride * 8 <= 16 * 1024 ? 1u : 0u;  // (enqueue_prob_prefix)
+    fp.q0 = 0;
+    fp.counts = sc.d_counts.p;
+    fp.npad = ix->npad;
+    fp.table_z = sc.d_table_z.p;
+    fp.hstride = b.cls->hstride;
+    fp.n_refs = N;
+    fp.bnd_bits = ix->d_bnd_bits.p;
+    fp.bnd_rank = ix->d_bnd_rank.p;
+    fp.prefix = sc.d_prefix.p;
+    fp.n_bnd = ix->n_bnd_local;
+    fp.tile_max = mode == 2u ? sc.d_tilemax.p : nullptr;
+    fp.ntiles = ix->ntiles;
+    fp.fuse_walk = mode != 0u ? 1u : 0u;
+    if (fp.fuse_walk) fp.walk = wp;
+    launch_taxon_prefix(s, fp, 1);
+    if (!fp.fuse_walk) launch_lineage_walk(s, wp, 1);
     if ((rc = enqueue_finalise(ix, b, s))) return rc;
     RTX_HIP(hipGetLastError());
     ix->n_sub_last = 0;
     ix->ran = true;
     ix->last_flags = 0;
+    if (table_in_lds) *table_in_lds = fp.tz_in_lds;
     return rtx_batch_download(ix, out);
+}
+
+int rtx_debug_evaluate(rtx_index *ix, const double *probs, rtx_result_view *out) { return debug_evaluate_impl(ix, probs, 0, out, nullptr); }
+
+int rtx_debug_evaluate_mode(rtx_index *ix, const double *probs, uint32_t mode, rtx_result_view *out, uint32_t *table_in_lds) {
+    return debug_evaluate_impl(ix, probs, mode, out, table_in_lds);
 }
 
 }  // extern "C"
