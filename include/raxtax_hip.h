@@ -914,6 +914,24 @@ int rtx_debug_evaluate(rtx_index *index, const double *probs /*n_refs*/, rtx_res
  * table_in_lds (may be NULL): 1 if the launch took the table from LDS.  With probabilities that are multiples of 2^-40 and sum to 1
  * every partial sum is exact in any order, so the rows must equal the reference's bit for bit, ties included. */
 int rtx_debug_evaluate_mode(rtx_index *index, const double *probs /*n_refs*/, uint32_t mode, rtx_result_view *out, uint32_t *table_in_lds);
+/* out[x] = ln x! for x < n (n <= 98320) as every handle uploads it for its kernels: CPU restatements of the device arithmetic start from the
+ * same table (it differs from other implementations of ln Gamma in the last place, and Z carries that once per reference).  No device needed. */
+int rtx_debug_ln_factorial(uint32_t n, double *out /*n*/);
+/* The probability stage (src/prob.rs:8-103) on caller-supplied histograms: n_q queries, query q with t[q] distinct k-mers and
+ * hist[q * hstride + m] references of hit count m (hstride > the largest t, no count above t[q]).  n_refs is the caller's, not the handle's
+ * -- a handle over a dozen references carries histograms that stand for millions -- and one per launch, as in a run: it enters the global
+ * signal (its 1 / N) and nothing else, so rows of other totals may ride along.  One launch of the kernels a run launches, with
+ * the parameters a sub-batch of the class of the largest t would get:
+ *   kernel 0: the lookup in the memoised tables (t <= 2047, else RTX_ERR_TOO_LONG; the tables are built or grown as a batch would), through
+ *             the processing order a sub-batch gets; prune_thr / prune_i1 (both or neither): the thresholds tile pruning would hand over
+ *   kernel 1: the recurrence with its arrays in LDS
+ *   kernel 2: the recurrence with its arrays in global memory, at any t (a run takes it for reads of tens of kilobases only)
+ * Out, per query: table / Z (NaN at the counts the histogram does not hold: the kernels never write those), Z, the global signal, the
+ * status (RTX_Q_*) and the number of distinct counts.  Needs no batch and leaves a later one what it would have been. */
+int rtx_debug_prob_hist(rtx_index *index, uint32_t n_q, const uint32_t *t /*n_q*/, const uint32_t *hist /*n_q x hstride*/, uint32_t hstride,
+                        uint64_t n_refs, uint32_t kernel, const uint16_t *prune_thr /*n_q or NULL*/, const uint16_t *prune_i1 /*n_q or NULL*/,
+                        double *table_over_z /*n_q x hstride*/, double *z /*n_q*/, double *gs /*n_q*/, uint8_t *status /*n_q*/,
+                        uint32_t *ndist /*n_q*/);
 
 /* ------------------------------------------------------------------------- */
 /* Host mirror of the output formatting (src/lineage.rs:17-48, utils.rs:62-89) */

@@ -171,6 +171,8 @@ _SIGNATURES = {
     "rtx_debug_prune_detail": (C.c_int, [C.c_void_p, C.c_uint64, u32p]),
     "rtx_debug_evaluate": (C.c_int, [C.c_void_p, f64p, C.POINTER(ResultView)]),
     "rtx_debug_evaluate_mode": (C.c_int, [C.c_void_p, f64p, C.c_uint32, C.POINTER(ResultView), u32p]),
+    "rtx_debug_ln_factorial": (C.c_int, [C.c_uint32, f64p]),
+    "rtx_debug_prob_hist": (C.c_int, [C.c_void_p, C.c_uint32, u32p, u32p, C.c_uint32, C.c_uint64, C.c_uint32, u16p, u16p, f64p, f64p, f64p, u8p, u32p]),
     "rtx_result_pack": (C.c_int64, [C.POINTER(ResultView), u8p, C.c_uint64]),
     "rtx_records_format": (C.c_int64, [C.c_void_p, u8p, C.c_uint64, C.POINTER(C.c_char_p), u32p, C.c_uint32, C.c_char_p, C.c_uint64, u64p, C.c_uint32]),
     "rtx_format_query": (C.c_int64, [C.c_void_p, C.POINTER(ResultView), C.c_uint64, C.c_char_p, u8p, C.c_uint64,

@@ -741,6 +741,28 @@ class Index:
         self.last_evaluate_table_in_lds = bool(in_lds.value)
         return Result(self._view)
 
+    def debug_prob_hist(self, ts, hists, n_refs: int, kernel: int, thr=None, i1=None) -> dict:
+        """The probability kernels on given histograms (rtx_debug_prob_hist): ts [n_q], hists [n_q, hstride] (hstride > max t; n_refs is the N of the
+        global signal's 1 / N and enters nothing else).  kernel 0: the lookup in the memoised tables (thr / i1: the thresholds of a pruned run), 1: the recurrence in LDS,
+        2: the recurrence in global memory.  table_z is NaN at the counts a histogram does not hold."""
+        ts = np.ascontiguousarray(ts, dtype=np.uint32)
+        hists = np.ascontiguousarray(hists, dtype=np.uint32)
+        assert hists.ndim == 2 and hists.shape[0] == len(ts)
+        n_q, hstride = hists.shape
+        tz = np.zeros((n_q, hstride), dtype=np.float64)
+        z = np.zeros(n_q, dtype=np.float64)
+        gs = np.zeros(n_q, dtype=np.float64)
+        status = np.zeros(n_q, dtype=np.uint8)
+        ndist = np.zeros(n_q, dtype=np.uint32)
+        if thr is not None:
+            thr = np.ascontiguousarray(thr, dtype=np.uint16)
+            i1 = np.ascontiguousarray(i1, dtype=np.uint16)
+            assert len(thr) == n_q and len(i1) == n_q
+        check(self._lib.rtx_debug_prob_hist(self._h, n_q, ptr(ts, u32p), ptr(hists, u32p), hstride, int(n_refs), int(kernel),
+                                            ptr(thr, u16p) if thr is not None else None, ptr(i1, u16p) if thr is not None else None,
+                                            ptr(tz, f64p), ptr(z, f64p), ptr(gs, f64p), ptr(status, u8p), ptr(ndist, u32p)))
+        return {"table_z": tz, "z": z, "gs": gs, "status": status, "ndist": ndist}
+
     def format_query(self, q: int, label: str, seq: np.ndarray, exact_ids: np.ndarray, flags: int = 0,
                      tsv: bool = False):
         """Lines of query q of the last download (after override raxtax.rs:73-84)."""

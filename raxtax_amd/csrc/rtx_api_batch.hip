@@ -1067,7 +1067,7 @@ int ensure_prob_tables(rtx_index *ix, uint32_t tmax, bool *usable) {
         return RTX_OK;
     }
     if ((rc = ix->d_tab_cmf.alloc(run)) || (rc = ix->d_tab_ratio.alloc(run)) || (rc = ix->d_tab_off.alloc(T + 1)) ||
-        (rc = ix->d_tab_moff.alloc(T + 1)) || (rc = ix->d_tab_ilo.alloc(mrun)) || (rc = ix->d_tab_sat.alloc(mrun)))
+        (rc = ix->d_tab_moff.alloc(T + 1)) || (rc = ix->d_tab_ilo.alloc(mrun)) || (rc = ix->d_tab_sat.alloc(2 * (size_t)mrun)))
         return rc;
     RTX_HIP(hipMemcpy(ix->d_tab_off.p, off.data(), (T + 1) * 8, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(ix->d_tab_moff.p, moff.data(), (T + 1) * 4, hipMemcpyHostToDevice));
@@ -1105,7 +1105,6 @@ constexpr uint32_t kDefaultSubBatch = 20480, kDefaultSubBatchLarge = 16384, kDef
 //                 kMinMidClass of them in a batch ride with class 3 (the tables of this class are gigabytes, built for the batch's longest read)
 //   3: longer     12 / 16 planes, one query per wave, prob_table_kernel with its arrays in LDS (t up to ~ 6 600)
 //   4: up to t = 65 535 (raxtax.rs:56): 16 planes, the histogram of hit_count and the arrays of prob_table in global memory
-constexpr size_t kProbTableLdsLimit = 160 * 1024 - 512;
 constexpr uint64_t kMidClassMaxT = 2047;
 
 uint32_t length_class(uint64_t len) {

@@ -563,4 +563,97 @@ int rtx_debug_evaluate_mode(rtx_index *ix, const double *probs, uint32_t mode, r
     return debug_evaluate_impl(ix, probs, mode, out, table_in_lds);
 }
 
+// The probability kernels on caller-supplied histograms: a whole batch of (t, histogram) pairs through the launches a run makes
+// (enqueue_prob_prefix), so that exact references can pin them on shapes no synthetic read produces.  ProbParams as a sub-batch of
+// the class of the largest t would have them; every buffer but the memoised tables (which only ever grow, and hold what they held)
+// is the call's own, and no field of the handle that a batch reads is touched: a later run computes what it computed before.
+//   kernel 0: prob_order_kernel + prob_lookup_kernel (t <= 2047; with prune_thr / prune_i1 as a pruned run hands them over)
+//   kernel 1: prob_table_kernel with its arrays in LDS
+//   kernel 2: prob_table_kernel with its arrays in global memory (what reads of tens of kilobases run), at any t
+// Entries of table_over_z at counts a histogram does not hold are never written by the kernels: they come back as NaN.
+int rtx_debug_prob_hist(rtx_index *ix, uint32_t n_q, const uint32_t *t, const uint32_t *hist, uint32_t hstride, uint64_t n_refs, uint32_t kernel,
+                        const uint16_t *prune_thr, const uint16_t *prune_i1, double *table_over_z, double *z, double *gs, uint8_t *status,
+                        uint32_t *ndist) {
+    if (!ix || !t || !hist || !table_over_z || !z || !gs || !status || !ndist) { set_error("null argument"); return RTX_ERR_INVALID; }
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (kernel > 2u) { set_error("rtx_debug_prob_hist: kernel %u (0, 1 or 2)", kernel); return RTX_ERR_INVALID; }
+    if (n_q == 0 || n_refs == 0) { set_error("rtx_debug_prob_hist: no queries, or no references"); return RTX_ERR_INVALID; }
+    if ((prune_thr || prune_i1) && (kernel != 0u || !prune_thr || !prune_i1)) { set_error("rtx_debug_prob_hist: thresholds go with the lookup kernel, both arrays"); return RTX_ERR_INVALID; }
+    uint32_t tmax = 0;
+    for (uint32_t q = 0; q < n_q; q++) tmax = std::max(tmax, t[q]);
+    if (tmax > 65535u) { set_error("rtx_debug_prob_hist: t = %u (at most 65535)", tmax); return RTX_ERR_TOO_LONG; }
+    if (hstride < tmax + 1u) { set_error("rtx_debug_prob_hist: histogram rows of %u entries, t = %u needs %u", hstride, tmax, tmax + 1u); return RTX_ERR_INVALID; }
+    if (kernel == 0u && tmax > 2047u) { set_error("prob tables need t <= 2047 (got %u)", tmax); return RTX_ERR_TOO_LONG; }
+    if (kernel == 1u && prob_table_lds_bytes(tmax) > kProbTableLdsLimit) { set_error("rtx_debug_prob_hist: the arrays of t = %u do not fit LDS", tmax); return RTX_ERR_TOO_LONG; }
+    for (uint32_t q = 0; q < n_q; q++) {  // counts reach t at most: what hit_count hands over (the kernels index their arrays by it)
+        const uint32_t *h = hist + (size_t)q * hstride;
+        for (uint32_t m = t[q] + 1u; m < hstride; m++)
+            if (h[m]) { set_error("rtx_debug_prob_hist: query %u holds a count above its t", q); return RTX_ERR_INVALID; }
+    }
+    RTX_HIP(hipStreamSynchronize(ix->stream));
+    hipStream_t s = ix->stream;
+    if (kernel == 0u && tmax >= 2u) {
+        bool usable = false;
+        if ((rc = ensure_prob_tables(ix, tmax, &usable))) return rc;
+        if (!usable) { set_error("rtx_debug_prob_hist: the memoised tables are switched off or do not fit"); return RTX_ERR_STATE; }
+    }
+    DevBuf<uint32_t> d_t, d_hist, d_order, d_ndist;
+    DevBuf<uint16_t> d_thr, d_i1;
+    DevBuf<double> d_tz, d_z, d_gs, d_scratch;
+    DevBuf<uint8_t> d_status;
+    const size_t nh = (size_t)n_q * hstride;
+    if ((rc = d_t.alloc(n_q)) || (rc = d_hist.alloc(nh)) || (rc = d_order.alloc(n_q)) || (rc = d_ndist.alloc(n_q)) || (rc = d_tz.alloc(nh)) ||
+        (rc = d_z.alloc(n_q)) || (rc = d_gs.alloc(n_q)) || (rc = d_status.alloc(n_q)))
+        return rc;
+    RTX_HIP(hipMemcpy(d_t.p, t, (size_t)n_q * 4, hipMemcpyHostToDevice));
+    RTX_HIP(hipMemcpy(d_hist.p, hist, nh * 4, hipMemcpyHostToDevice));
+    RTX_HIP(hipMemset(d_tz.p, 0xFF, nh * 8));  // NaN: an entry no kernel wrote cannot pass for a result
+    RTX_HIP(hipMemset(d_z.p, 0xFF, (size_t)n_q * 8));
+    RTX_HIP(hipMemset(d_gs.p, 0xFF, (size_t)n_q * 8));
+    RTX_HIP(hipMemset(d_status.p, 0xFF, n_q));
+    RTX_HIP(hipMemset(d_ndist.p, 0xFF, (size_t)n_q * 4));
+    ProbParams pp{};  // (enqueue_prob_prefix)
+    pp.t = d_t.p;
+    pp.hist = d_hist.p;
+    pp.hstride = hstride;
+    pp.tmax = tmax;
+    pp.n1max = tmax / 2 + 1;
+    pp.lnfact = ix->d_lnfact.p;
+    pp.n_refs = n_refs;
+    pp.q0 = 0;
+    pp.table_z = d_tz.p;
+    pp.z = d_z.p;
+    pp.gs = d_gs.p;
+    pp.status = d_status.p;
+    pp.ndist = d_ndist.p;
+    if (prune_thr) {
+        if ((rc = d_thr.alloc(n_q)) || (rc = d_i1.alloc(n_q))) return rc;
+        RTX_HIP(hipMemcpy(d_thr.p, prune_thr, (size_t)n_q * 2, hipMemcpyHostToDevice));
+        RTX_HIP(hipMemcpy(d_i1.p, prune_i1, (size_t)n_q * 2, hipMemcpyHostToDevice));
+        pp.prune_thr = d_thr.p;
+        pp.prune_i1 = d_i1.p;
+    }
+    if (kernel == 0u) {
+        launch_prob_order(s, d_t.p, n_q, d_order.p);
+        pp.order = d_order.p;
+        launch_prob_lookup(s, pp, ProbTables{ix->d_tab_cmf.p, ix->d_tab_ratio.p, ix->d_tab_off.p, ix->d_tab_moff.p, ix->d_tab_ilo.p, ix->d_tab_sat.p, ix->tab_tmax}, n_q);
+    } else {
+        if (kernel == 2u) {
+            pp.gstride = (uint32_t)((prob_table_lds_bytes(tmax) + 7) / 8);
+            if ((rc = d_scratch.alloc((size_t)n_q * pp.gstride))) return rc;
+            pp.gscratch = d_scratch.p;
+        }
+        launch_prob_table(s, pp, n_q);
+    }
+    RTX_HIP(hipGetLastError());
+    RTX_HIP(hipStreamSynchronize(s));
+    RTX_HIP(hipMemcpy(table_over_z, d_tz.p, nh * 8, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(z, d_z.p, (size_t)n_q * 8, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(gs, d_gs.p, (size_t)n_q * 8, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(status, d_status.p, n_q, hipMemcpyDeviceToHost));
+    RTX_HIP(hipMemcpy(ndist, d_ndist.p, (size_t)n_q * 4, hipMemcpyDeviceToHost));
+    return RTX_OK;
+}
+
 }  // extern "C"

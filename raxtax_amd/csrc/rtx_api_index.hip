@@ -62,6 +62,16 @@ void fill_ln_factorial(std::vector<double> &lf) {
 
 extern "C" {
 
+// The ln-factorial table as every handle uploads it (entries 0 .. n - 1): the emulation of the device arithmetic on the CPU starts from
+// the same numbers as the kernels (the table's rounding enters Z once per reference).  Needs no device.
+int rtx_debug_ln_factorial(uint32_t n, double *out) {
+    if (!out || n > kLnFactLen) { set_error("rtx_debug_ln_factorial: null argument, or more than %u entries", kLnFactLen); return RTX_ERR_INVALID; }
+    std::vector<double> lf;
+    fill_ln_factorial(lf);
+    std::copy(lf.begin(), lf.begin() + n, out);
+    return RTX_OK;
+}
+
 int rtx_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;

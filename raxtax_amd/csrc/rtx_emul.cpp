@@ -339,6 +339,8 @@ int emul_prob_table(uint32_t t, const uint32_t *hist, uint64_t n_refs, const dou
 // Sequential emulation of prob_lookup_kernel + prob_tables_build_kernel (rtx_prob_tables.hip): the rows
 // C = ln cmf, R = pmf/cmf, sat and ilo are produced by the same recurrence (here on demand instead of from the
 // memoised table), then P(i) and table[m] are formed exactly as the lookup kernel does.
+// stats (may be null): [0] rows still moving at i_lo (the live rows), [1] points (row, i) folded into P, [2] i_lo, [3] bit s set: some
+// live row moves last in the s-th 64-wide slice of i from i_lo (what the kernel's s_nlive is built from).
 // u_thr > 0: the query as tile pruning treats it (prob_lookup_kernel with ProbParams::prune_thr / prune_i1): the counts up to u_thr
 // become references without a hit (bin 0) with probability 0, and the sums over i start at i1 if that lies beyond i_lo.
 static int emul_prob_lookup_x(uint32_t t, const uint32_t *hist_in, uint64_t n_refs, const double *lf, uint32_t u_thr, uint32_t i1,
@@ -355,12 +357,20 @@ static int emul_prob_lookup_x(uint32_t t, const uint32_t *hist_in, uint64_t n_re
     for (uint32_t x = 1; x <= t + n; x++) inv[x] = 1.0 / (double)x;
     const double ln_total = ln_binom_tab(lf, t + n - 1, n);
     std::vector<double> tab(t + 1, 0.0);
-    uint64_t st_rows = 0, st_points = 0;
+    uint64_t st_rows = 0, st_points = 0, st_ilo = 0, st_slices = 0;
+    uint32_t sat2 = 0;  // first i behind sat at which pmf / cmf < 2^-90 (prob_tables_build_kernel: kRatioNegligible)
     auto build_row = [&](uint32_t m, std::vector<double> &C, std::vector<double> &R, uint32_t &sat, uint32_t &ilo) {
         C.assign(n + 1, 0.0);
         R.assign(n + 1, 0.0);
+        double ln_end = 0.0;  // the row is stored relative to its final value (prob_tables_build_kernel)
+        {
+            PmfState e = pmf_start(lf, t, n, m, ln_total);
+            for (uint32_t i = 1; i <= n; i++) pmf_step(e, inv.data(), t, n, m, i);
+            if (e.k == 0 && e.c > 0.0) ln_end = log(e.c);
+        }
         PmfState st = pmf_start(lf, t, n, m, ln_total);
         sat = n + 1;
+        sat2 = n + 1;
         ilo = n;
         bool found = false;
         for (uint32_t i = 0; i <= n; i++) {
@@ -371,8 +381,9 @@ static int emul_prob_lookup_x(uint32_t t, const uint32_t *hist_in, uint64_t n_re
                 if (sat == n + 1 && st.c == c_old && k_old == 0 && st.k == 0) sat = i;
             }
             const bool live = st.k == 0 && st.c > 0.0;
-            C[i] = live ? log(st.c) : -INFINITY;
+            C[i] = live ? log(st.c) - ln_end : -INFINITY;
             R[i] = live ? st.v / st.c : 0.0;
+            if (sat2 == n + 1 && sat != n + 1 && R[i] < 8.0779356694631609e-28) sat2 = i;
             if (!found && ln_pmf_tab(lf, t, n, m, i, ln_total) >= kLnNegligibleP) { ilo = i; found = true; }
         }
     };
@@ -385,6 +396,7 @@ static int emul_prob_lookup_x(uint32_t t, const uint32_t *hist_in, uint64_t n_re
         uint32_t sat = 0, ilo = 0, i_lo = 0;
         if (M > 0) { build_row(M, C, R, sat, ilo); i_lo = ilo; }
         if (u_thr && i1 > i_lo && i1 <= n) i_lo = i1;
+        st_ilo = i_lo;
         std::vector<double> Pi(n + 1, 0.0);  // sum_m hist[m] ln cmf_m(i), then exp
         struct Row { uint32_t m, sat; std::vector<double> R; };
         std::vector<Row> rows;
@@ -392,11 +404,14 @@ static int emul_prob_lookup_x(uint32_t t, const uint32_t *hist_in, uint64_t n_re
             const uint32_t m = ms[j];
             if (m == 0) continue;
             build_row(m, C, R, sat, ilo);
-            if (sat <= i_lo) continue;  // saturated before i_lo: factor 1, table 0
+            if (sat2 <= i_lo) continue;  // nothing left of the row at i_lo: factor 1, table 0
             for (uint32_t i = i_lo; i <= n; i++)
                 if (i < sat) { Pi[i] = fma((double)hist[m], C[i], Pi[i]); st_points++; }
-            rows.push_back(Row{m, sat, R});
+            rows.push_back(Row{m, sat2, R});
             st_rows++;
+            const uint32_t s_end = std::min(sat, n + 1);
+            const uint32_t nsl = s_end > i_lo ? (s_end - i_lo + 63u) >> 6 : 1u;  // (prob_lookup_kernel: s_nlive)
+            st_slices |= 1ull << (std::min(nsl, 16u) - 1u);
         }
         for (uint32_t i = 0; i <= n; i++) Pi[i] = exp(Pi[i]);
         for (const Row &r : rows) {
@@ -419,7 +434,7 @@ static int emul_prob_lookup_x(uint32_t t, const uint32_t *hist_in, uint64_t n_re
     }
     *z = Z;
     *gs = sqrt(g);
-    if (stats) { stats[0] = st_rows; stats[1] = st_points; stats[2] = 0; stats[3] = 0; }
+    if (stats) { stats[0] = st_rows; stats[1] = st_points; stats[2] = st_ilo; stats[3] = st_slices; }
     return 0;
 }
 int emul_prob_lookup(uint32_t t, const uint32_t *hist, uint64_t n_refs, const double *lf, double *table_z, double *z,
@@ -439,10 +454,16 @@ static void emul_ln_cmf_row(uint32_t t, uint32_t m, const double *lf, std::vecto
     std::vector<double> inv(t + n + 2, 0.0);
     for (uint32_t x = 1; x <= t + n; x++) inv[x] = 1.0 / (double)x;
     const double ln_total = ln_binom_tab(lf, t + n - 1, n);
+    double ln_end = 0.0;  // relative to the row's final value (prob_tables_build_kernel)
+    {
+        PmfState e = pmf_start(lf, t, n, m, ln_total);
+        for (uint32_t i = 1; i <= n; i++) pmf_step(e, inv.data(), t, n, m, i);
+        if (e.k == 0 && e.c > 0.0) ln_end = log(e.c);
+    }
     PmfState st = pmf_start(lf, t, n, m, ln_total);
     for (uint32_t i = 0; i <= n; i++) {
         if (i > 0) pmf_step(st, inv.data(), t, n, m, i);
-        C[i] = st.k == 0 && st.c > 0.0 ? log(st.c) : -INFINITY;
+        C[i] = st.k == 0 && st.c > 0.0 ? log(st.c) - ln_end : -INFINITY;
     }
 }
 

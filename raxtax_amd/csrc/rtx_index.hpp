@@ -27,6 +27,7 @@ namespace rtxi {
 
 constexpr uint32_t kEmptyRow = 0xFFFFFFFFu;
 constexpr uint32_t kLnFactLen = 98320;  // covers t + n - 1 for every t <= 65535
+constexpr size_t kProbTableLdsLimit = 160 * 1024 - 512;  // prob_table_kernel with its arrays in LDS up to here (rtx_api_batch.hip: length classes)
 
 #define RTX_HIP(call)                                                                          \
     do {                                                                                       \

@@ -407,7 +407,7 @@ struct ProbTables {
     const uint64_t *off;   // [tmax+1]
     const uint32_t *moff;  // [tmax+1] offset of row t in ilo / sat
     uint16_t *ilo;         // [moff[t] + m] first i with ln pmf_m(i) >= -100
-    uint16_t *sat;         // [moff[t] + m] first i at which cmf_m has stopped changing
+    uint16_t *sat;         // [2 (moff[t] + m)] first i at which cmf_m has stopped changing, [.. + 1] first i behind it at which pmf / cmf counts as 0
     uint32_t tmax;
 };
 

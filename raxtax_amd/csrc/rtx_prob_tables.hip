@@ -3,10 +3,11 @@
 // pmf_m(i) and cmf_m(i) of prob.rs:121-170 depend on (t, n = t/2, m, i) only -- not on the query
 // beyond its number of distinct k-mers t.  For queries of t <= 2047 (barcodes; since round 6 full-length 16S) the library
 // therefore builds, once per index handle, for every t <= tmax and every 0 < m < t
-//     L[t][m][i] = ln cmf_m(i)           R[t][m][i] = pmf_m(i) / cmf_m(i)
+//     L[t][m][i] = ln cmf_m(i) - ln cmf_m(n)   R[t][m][i] = pmf_m(i) / cmf_m(i)      (cmf_m(n) = 1 but for its rounding)
 // with the very recurrence of rtx_math.hpp (same arithmetic as prob_table_kernel), plus per (t, m)
 //     ilo[t][m] = first i with ln pmf_m(i) >= -100          (i_lo when m is the largest count)
-//     sat[t][m] = first i at which cmf_m stops changing      (cmf == its final value from there on)
+//     sat[t][m] = first i at which cmf_m stops changing      (cmf == its final value from there on), and behind it
+//     sat2[t][m] = first i at which pmf_m / cmf_m < 2^-90    (pass 2 reads a row up to there)
 // A query then needs no recurrence at all:
 //     P(i)     = exp(sum_m hist[m] L[t][m][i])      (lanes <-> i, rows streamed coalesced; this is
 //                                                    prod[i] of prob.rs:62-73, one FMA per row and i)
@@ -25,6 +26,10 @@ namespace rtx {
 // ---------------------------------------------------------------------------
 // table build: one thread per (t, m), sequential over i (same recurrence as prob_table_kernel)
 // ---------------------------------------------------------------------------
+// pmf / cmf below this counts as 0 whatever the histogram: 2^-90 times the 2^32 references a bin can hold is 2^-58.  A row's pmf / cmf
+// is read up to there (sat2), its ln cmf only up to where the cmf stops changing (sat <= sat2): the terms between the two are below
+// 2^-53 each, but a count that h references share carries them h times in Z (3e-16 h of it: 1e-9 with 4 M references in one bin).
+constexpr double kRatioNegligible = 8.0779356694631609e-28;  // 2^-90
 __global__ __launch_bounds__(256) void prob_tables_build_kernel(ProbTables tb, const double *__restrict__ lf,
                                                                 const double *__restrict__ inv) {
     const uint32_t t = blockIdx.y + 2;  // t = 2 .. tmax
@@ -34,16 +39,27 @@ __global__ __launch_bounds__(256) void prob_tables_build_kernel(ProbTables tb, c
     double *C = tb.cmf + tb.off[t] + (size_t)m * n1;
     double *R = tb.ratio + tb.off[t] + (size_t)m * n1;
     uint16_t *meta_ilo = tb.ilo + tb.moff[t];
-    uint16_t *meta_sat = tb.sat + tb.moff[t];
+    uint16_t *meta_sat = tb.sat + 2u * tb.moff[t];
     if (m == 0) {  // pmf = [1, 0, ...], cmf = 1, ln cmf = 0 (prob.rs:134-137)
         for (uint32_t i = 0; i <= n; i++) { C[i] = 0.0; R[i] = i == 0 ? 1.0 : 0.0; }
         meta_ilo[0] = 0;
         meta_sat[0] = 1;
+        meta_sat[1] = 1;
         return;
     }
     const double ln_total = ln_binom_tab(lf, t + n - 1, n);
+    // A row is stored relative to its own final value: ln cmf_m(i) - ln cmf_m(n).  The true cmf_m(n) is 1; the summed one misses it by a
+    // few ulp, and a row that is read up to its saturation and counted as ln = 0 from there on (prob_lookup_kernel) would jump by
+    // h ln cmf_m(n) at that index -- 1e-9 of P(i) for a count that millions of references share.  Relative to its end the row runs into
+    // exactly 0 where it saturates.  The end comes from a first run of the recurrence that stores nothing.
+    double ln_end = 0.0;
+    {
+        PmfState e = pmf_start(lf, t, n, m, ln_total);
+        for (uint32_t i = 1; i <= n; i++) pmf_step(e, inv, t, n, m, i);
+        if (e.k == 0 && e.c > 0.0) ln_end = log(e.c);
+    }
     PmfState st = pmf_start(lf, t, n, m, ln_total);
-    uint32_t sat = n + 1, ilo = n;
+    uint32_t sat = n + 1, sat2 = n + 1, ilo = n;
     bool ilo_found = false;
     for (uint32_t i = 0; i <= n; i++) {
         if (i > 0) {
@@ -53,12 +69,14 @@ __global__ __launch_bounds__(256) void prob_tables_build_kernel(ProbTables tb, c
             if (sat == n + 1 && st.c == c_old && k_old == 0 && st.k == 0) sat = i;
         }
         const bool live = st.k == 0 && st.c > 0.0;  // below 2^-412 the cmf counts as 0 (rtx_math.hpp)
-        C[i] = live ? log(st.c) : -INFINITY;
+        C[i] = live ? log(st.c) - ln_end : -INFINITY;
         R[i] = live ? st.v / st.c : 0.0;
+        if (sat2 == n + 1 && sat != n + 1 && R[i] < kRatioNegligible) sat2 = i;
         if (!ilo_found && ln_pmf_tab(lf, t, n, m, i, ln_total) >= kLnNegligibleP) { ilo = i; ilo_found = true; }
     }
     meta_ilo[m] = (uint16_t)ilo;
-    meta_sat[m] = (uint16_t)sat;
+    meta_sat[2 * m] = (uint16_t)sat;
+    meta_sat[2 * m + 1] = (uint16_t)sat2;
 }
 
 // One f64 of a table row through a raw buffer load.  The descriptor covers the table of this t from its base up to
@@ -157,7 +175,7 @@ __global__ __launch_bounds__(256, RTX_PROB_WAVES) void prob_lookup_kernel(ProbPa
             return;
         }
         const uint16_t *t_ilo = tb.ilo + tb.moff[t];
-        const uint16_t *t_sat = tb.sat + tb.moff[t];
+        const uint16_t *t_sat = tb.sat + 2u * tb.moff[t];
         const double *Ct = tb.cmf + tb.off[t];
         const double *Rt = tb.ratio + tb.off[t];
         uint32_t i_lo = M > 0 ? t_ilo[M] : 0u;
@@ -167,7 +185,7 @@ __global__ __launch_bounds__(256, RTX_PROB_WAVES) void prob_lookup_kernel(ProbPa
         // saturation index of every distinct count, gathered by all threads at once (row_h as staging)
         for (uint32_t j = tid; j < D; j += 256) {
             const uint32_t m = ms[D - 1 - j];
-            row_h[j] = m ? t_sat[m] : 0u;
+            row_h[j] = m ? (uint32_t)t_sat[2u * m] | (uint32_t)t_sat[2u * m + 1u] << 16 : 0u;  // sat | sat2 << 16
         }
         __syncthreads();
         // rows still moving at i_lo, in descending order of m; everything else gets table = 0
@@ -176,23 +194,25 @@ __global__ __launch_bounds__(256, RTX_PROB_WAVES) void prob_lookup_kernel(ProbPa
             if (lane < 16) s_nlive[lane] = 0;
             for (uint32_t j0 = 0; j0 < D; j0 += 64) {
                 const uint32_t j = j0 + lane;
-                uint32_t m = 0, sat = 0;
+                uint32_t m = 0, sat = 0, sat2 = 0;
                 if (j < D) {
                     m = ms[D - 1 - j];
-                    sat = row_h[j];
-                    if (m && sat <= i_lo) tzl[m] = 0.0;
+                    sat = row_h[j] & 0xFFFFu;
+                    sat2 = row_h[j] >> 16;
+                    if (m && sat2 <= i_lo) tzl[m] = 0.0;
                 }
-                const bool keep = m != 0 && sat > i_lo;
+                const bool keep = m != 0 && sat2 > i_lo;  // (sat <= i_lo < sat2: the row moves no P(i) any more, its own sum still has terms)
                 const unsigned long long bal = __ballot(keep);
                 if (keep) {
                     const uint32_t pos = na + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
                     row_m[pos] = (uint16_t)m;
-                    row_sat[pos] = (uint16_t)sat;
+                    row_sat[pos] = (uint16_t)(sat2 < n1 ? sat2 : n1);  // pass 2 reads pmf / cmf up to here
                     row_h[pos] = hl[m];  // pos <= j: the staged entries still needed lie at indices > j
                     row_off[pos] = m * n1 * 8u;
                     row_end[pos] = (m * n1 + (sat < n1 ? sat : n1)) * 8u;
                     // last slice of 64 values of i (from i_lo) in which this row still moves
-                    const uint32_t nsl = ((sat < n1 ? sat : n1) - i_lo + 63u) >> 6;
+                    const uint32_t s_end = sat < n1 ? sat : n1;
+                    const uint32_t nsl = s_end > i_lo ? (s_end - i_lo + 63u) >> 6 : 1u;
                     atomicMax(&s_nlive[(nsl < 16u ? nsl : 16u) - 1u], pos + 1u);
                 }
                 na += (uint32_t)__popcll(bal);
@@ -264,8 +284,8 @@ __global__ __launch_bounds__(256, RTX_PROB_WAVES) void prob_lookup_kernel(ProbPa
             for (int k = 0; k < 8; k++) {
                 acc[k] = 0.0;
                 off[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_off[r0 + k]);
-                end[k] = (uint32_t)__builtin_amdgcn_readfirstlane((int)row_end[r0 + k]);
-                const uint32_t cnt = (end[k] - off[k]) >> 3;  // entries below saturation (0 for a padding row)
+                end[k] = off[k] + 8u * (uint32_t)__builtin_amdgcn_readfirstlane((int)row_sat[r0 + k]);
+                const uint32_t cnt = (end[k] - off[k]) >> 3;  // entries with a pmf / cmf that counts (0 for a padding row)
                 lmax = max(lmax, cnt ? cnt - 1u : 0u);
             }
             for (uint32_t ib = i_lo; ib <= lmax; ib += 128) {
