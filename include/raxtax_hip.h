@@ -47,7 +47,9 @@ extern "C" {
                                 rtx_raxtax_multi_ex4: exports and a setting that is off by default; and with FASTQ and the quality filter,
                                 rtx_queries_parse_fastq* / rtx_fastq_block_end / rtx_queries_quals / rtx_qual_* / rtx_index_set_quality /
                                 rtx_raxtax_last_qual / rtx_raxtax_multi_ex5: the same; and with paired-end merging, rtx_merge_* /
-                                rtx_queries_merge_report / rtx_fastq_block_end_n: exports only) */
+                                rtx_queries_merge_report / rtx_fastq_block_end_n: exports only; and with the chimera check, rtx_chimera_* /
+                                rtx_index_set_chimera / rtx_index_chimera / rtx_raxtax_last_chimera / rtx_raxtax_multi_ex6: exports and a
+                                setting that is off by default) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -753,6 +755,57 @@ int rtx_queries_merge_report(const rtx_queries *merged, const uint32_t **nf, con
                              const uint32_t **verdict);
 uint64_t rtx_fastq_block_end_n(const char *text, uint64_t len, uint64_t max_records, uint64_t *n_records);
 
+/* ---- chimera check against the references (rtx_chimera.hip) ----------------------------------------------------------------------------
+ * A PCR chimera is the head of one template joined to the tail of another: one reference explains its left part, another its right part,
+ * and no single reference explains both.  The check is the counting problem of hit_count with positions kept.  Exact integers; the host
+ * function, the x86 emulator and the device agree in every field.
+ *   parameters   segments S (2 .. RTX_CHIMERA_MAX_SEGMENTS; RTX_CHIMERA_DEFAULT_SEGMENTS) and mindelta (RTX_CHIMERA_DEFAULT_MINDELTA:
+ *                one substitution removes at most 8 windows, three differences per side).
+ *   per read     of len bases, in the orientation given.  Window i (0 <= i < n_pos = max(0, len - 7)) is valid when its 8 bases are all
+ *                plain codes (1, 2, 4, 8).  x_r[i] = 1 when window i is valid and its 8-mer occurs in reference r: positions count, a
+ *                repeated 8-mer counts once per position (the classifier counts distinct 8-mers).  n_valid: the valid windows.
+ *                b_s = floor(s n_pos / S), s = 0 .. S;  P_r[s] = sum of x_r[i] over i < b_s;  T_r = P_r[S];  Suf_r[s] = T_r - P_r[s].
+ *                single = max_r T_r, parent the lowest r that attains it.  two[s] = max_r P_r[s] + max_r Suf_r[s] for s = 1 .. S - 1;
+ *                seg the lowest s with the largest two[s], pos = b_seg; left = max_r P_r[seg] with parent_a the lowest r that attains
+ *                it, right = max_r Suf_r[seg] with parent_b likewise; delta = two[seg] - single (never negative, and both flanks are
+ *                decided by at least delta); flag = delta >= mindelta.  A parent whose count is 0 is RTX_NO_REF.
+ *   status       RTX_CHIM_OK; RTX_CHIM_NO_KMER: n_valid = 0, everything 0 or RTX_NO_REF, not flagged; RTX_CHIM_TOO_LONG: more than
+ *                RTX_CHIMERA_MAX_QUERY bases, not checked and not flagged.  A read's record never depends on the rest of its batch.
+ *   rtx_chimera_create  an object of its own in front of a handle like rtx_qual: one stream, its own buffers (they only grow).  It BORROWS
+ *                the handle's bitmap and row table, which never change: the index must outlive the object.  RTX_ERR_INVALID: segments
+ *                out of range, a reference shard, a handle with RTX_OPT_STRAND set (a read given as its reverse complement matches
+ *                nothing: checking both orientations is not done).
+ *   rtx_chimera_run     the records of n reads, bases / base_off as rtx_batch_prefetch takes them.  Processed in slices, so that the
+ *                device scratch stays under about 1 GB whatever the database size.  n == 0: RTX_OK.  Synchronous; calls on one object
+ *                are serialised by the caller, and may run beside the handle's own batches.
+ *   rtx_chimera_kernel_time  milliseconds of the scan kernels of the last run, from HIP events around them.
+ *   rtx_chimera_read    the same for ONE read on the host (no device), from the reference sequences (ref_off [n_refs + 1]).
+ *   rtx_index_set_chimera  the setting a handle holds for the callers that run the stage in front of it (NULL, the default: off -- nothing
+ *                runs and nothing is allocated); the handle itself never reads it.  rtx_index_chimera: the setting and whether it is on. */
+#define RTX_CHIMERA_MAX_QUERY 4096u
+#define RTX_CHIMERA_MAX_SEGMENTS 32u
+#define RTX_CHIMERA_DEFAULT_SEGMENTS 16u
+#define RTX_CHIMERA_DEFAULT_MINDELTA 24u
+#define RTX_CHIM_OK 0u
+#define RTX_CHIM_NO_KMER 1u
+#define RTX_CHIM_TOO_LONG 2u
+typedef struct {
+    uint32_t segments;
+    uint32_t mindelta;
+} rtx_chimera_params;
+typedef struct {
+    uint32_t status, n_valid, single, parent, seg, pos, left, parent_a, right, parent_b, delta, flag;
+} rtx_chimera_rec;
+typedef struct rtx_chimera rtx_chimera;
+int rtx_chimera_create(const rtx_index *index, const rtx_chimera_params *params, rtx_chimera **out);
+int rtx_chimera_run(rtx_chimera *ch, uint64_t n, const uint8_t *bases, const uint64_t *base_off, rtx_chimera_rec *out /*[n]*/);
+void rtx_chimera_destroy(rtx_chimera *ch);
+int rtx_chimera_kernel_time(const rtx_chimera *ch, float *ms);
+int rtx_chimera_read(const rtx_chimera_params *params, const uint8_t *read, uint64_t len, const uint8_t *ref_bases, const uint64_t *ref_off,
+                     uint64_t n_refs, rtx_chimera_rec *rec);
+int rtx_index_set_chimera(rtx_index *index, const rtx_chimera_params *params);
+int rtx_index_chimera(const rtx_index *index, rtx_chimera_params *params, int *on);
+
 /* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
  * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte
  * for byte what rtx_format_query prints for the view, the label, the bases and the exact matches of the query (the override of
@@ -1032,6 +1085,20 @@ int rtx_raxtax_multi_ex5(rtx_index *const *indices, uint32_t n_indices, const rt
                          int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                          rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
                          rtx_query_qual_fn qual, void *qual_ctx);
+/* rtx_raxtax_multi_ex5 with a callback for the chimera check (rtx_index_set_chimera on the handles, which must agree on it: RTX_ERR_INVALID
+ * otherwise, and with RTX_OPT_STRAND set): called for EVERY query of the caller, in input order, directly after its `qual` callback, with the
+ * query's record (valid during the call).  The stage runs behind the dereplication, so a distinct read is checked once and a copy carries
+ * its representative's record; a flagged read is classified as the empty read, exactly as one the quality filter discards: reported, not
+ * classified, not counted by an open profile.  With no check set: RTX_CHIM_OK, zeros and RTX_NO_REF.  Any callback may be NULL. */
+typedef int (*rtx_query_chimera_fn)(void *ctx, const char *label, const rtx_chimera_rec *rec);
+int rtx_raxtax_multi_ex6(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                         rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx);
+/* The last rtx_raxtax* call of the process: its queries, the reads the stage checked (the distinct ones under RTX_OPT_DEREP), the queries
+ * whose record is flagged, and the busy seconds of the stage; all 0 when its handles had no chimera check set. */
+int rtx_raxtax_last_chimera(uint64_t *queries, uint64_t *checked, uint64_t *flagged, double *busy_seconds);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

@@ -12,7 +12,8 @@ from .api import (EvaluationResult, Index, Result, Tree, parse_query_fasta_str, 
                   parse_query_fastq_str, Qual, QualParams, qual_read, qual_error_table, qual_verdict_names, raxtax_last_qual, QUAL_MAX_READ,
                   QC_BAD_QUALITY, QC_SHORT_FOR_TRUNC_LEN, QC_TOO_SHORT, QC_TOO_LONG, QC_TOO_MANY_N, QC_MAX_EE, QC_MAX_EE_RATE,
                   Merge, MergeParams, merge_pair, merge_queries, merge_verdict_names, fastq_text, fastq_block_end_n, MERGE_MAX_READ,
-                  MG_BAD_QUALITY, MG_TOO_LONG, MG_TOO_SHORT, MG_NO_OVERLAP)
+                  MG_BAD_QUALITY, MG_TOO_LONG, MG_TOO_SHORT, MG_NO_OVERLAP,
+                  Chimera, ChimeraParams, chimera_read, raxtax_last_chimera, CHIMERA_DTYPE, CHIMERA_MAX_QUERY, CHIM_OK, CHIM_NO_KMER, CHIM_TOO_LONG)
 from ._lib import (RTX_RAW_CONFIDENCE, RTX_SKIP_EXACT_MATCHES, RtxError)  # noqa: F401
 
 __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last_timing", "parse_reference_fasta_str",
@@ -22,4 +23,5 @@ __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last
            "TRIM_NO_PATTERN", "parse_query_fastq_str", "Qual", "QualParams", "qual_read", "qual_error_table", "qual_verdict_names", "raxtax_last_qual",
            "QUAL_MAX_READ", "QC_BAD_QUALITY", "QC_SHORT_FOR_TRUNC_LEN", "QC_TOO_SHORT", "QC_TOO_LONG", "QC_TOO_MANY_N", "QC_MAX_EE", "QC_MAX_EE_RATE",
            "Merge", "MergeParams", "merge_pair", "merge_queries", "merge_verdict_names", "fastq_text", "fastq_block_end_n", "MERGE_MAX_READ",
-           "MG_BAD_QUALITY", "MG_TOO_LONG", "MG_TOO_SHORT", "MG_NO_OVERLAP"]
+           "MG_BAD_QUALITY", "MG_TOO_LONG", "MG_TOO_SHORT", "MG_NO_OVERLAP",
+           "Chimera", "ChimeraParams", "chimera_read", "raxtax_last_chimera", "CHIMERA_DTYPE", "CHIMERA_MAX_QUERY", "CHIM_OK", "CHIM_NO_KMER", "CHIM_TOO_LONG"]

@@ -34,6 +34,10 @@ RTX_QC_NAMES = ("bad_quality", "short_for_trunc_len", "too_short", "too_long", "
 RTX_MERGE_MAX_READ, RTX_MERGE_MISMATCH_COST = 1024, 5
 RTX_MG_NAMES = ("bad_quality", "too_long", "too_short", "no_overlap")   # bit b of a verdict: RTX_MG_* (a verdict holds one reason)
 
+RTX_CHIMERA_MAX_QUERY, RTX_CHIMERA_MAX_SEGMENTS, RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA = 4096, 32, 16, 24
+RTX_CHIM_OK, RTX_CHIM_NO_KMER, RTX_CHIM_TOO_LONG = 0, 1, 2
+RTX_CHIM_FIELDS = ("status", "n_valid", "single", "parent", "seg", "pos", "left", "parent_a", "right", "parent_b", "delta", "flag")   # rtx_chimera_rec: twelve uint32
+
 u8p = C.POINTER(C.c_uint8)
 u16p = C.POINTER(C.c_uint16)
 u32p = C.POINTER(C.c_uint32)
@@ -74,6 +78,14 @@ class QualParams(C.Structure):   # rtx_qual_params
 
 class MergeParams(C.Structure):   # rtx_merge_params
     _fields_ = [("ascii_base", C.c_uint32), ("min_overlap", C.c_uint32), ("max_diffs", C.c_uint32), ("max_diff_pct", C.c_uint32), ("q_cap", C.c_uint32)]
+
+
+class ChimeraParams(C.Structure):   # rtx_chimera_params
+    _fields_ = [("segments", C.c_uint32), ("mindelta", C.c_uint32)]
+
+
+class ChimeraRec(C.Structure):   # rtx_chimera_rec
+    _fields_ = [(f, C.c_uint32) for f in RTX_CHIM_FIELDS]
 
 
 class RtxError(RuntimeError):
@@ -237,6 +249,15 @@ _SIGNATURES = {
     "rtx_merge_queries": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.POINTER(C.c_void_p)]),
     "rtx_queries_merge_report": (C.c_int, [C.c_void_p, C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p), C.POINTER(u32p)]),
     "rtx_fastq_block_end_n": (C.c_uint64, [C.c_char_p, C.c_uint64, C.c_uint64, u64p]),
+    "rtx_chimera_create": (C.c_int, [C.c_void_p, C.POINTER(ChimeraParams), C.POINTER(C.c_void_p)]),
+    "rtx_chimera_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, C.c_void_p]),
+    "rtx_chimera_destroy": (None, [C.c_void_p]),
+    "rtx_chimera_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_chimera_read": (C.c_int, [C.POINTER(ChimeraParams), u8p, C.c_uint64, u8p, u64p, C.c_uint64, C.c_void_p]),
+    "rtx_index_set_chimera": (C.c_int, [C.c_void_p, C.POINTER(ChimeraParams)]),
+    "rtx_index_chimera": (C.c_int, [C.c_void_p, C.POINTER(ChimeraParams), C.POINTER(C.c_int)]),
+    "rtx_raxtax_multi_ex6": (C.c_int, None),
+    "rtx_raxtax_last_chimera": (C.c_int, [u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_sender_discard": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]),
     "rtx_batch_prefetch": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u64p]),
     "rtx_batch_activate": (C.c_int, [C.c_void_p]),

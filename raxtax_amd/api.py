@@ -313,7 +313,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None):
+                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -378,6 +378,8 @@ class Index:
             self.set_primers(primers)
         if quality is not None:   # rtx_index_set_quality: raxtax() filters every read by its quality string (rtx_qual.hip); classify() ignores it
             self.set_quality(quality)
+        if chimera is not None:   # rtx_index_set_chimera: raxtax() checks every read against the references first (rtx_chimera.hip); classify() ignores it
+            self.set_chimera(ChimeraParams() if chimera is True else chimera)
         self._view = ResultView()
         self._keep = None
 
@@ -392,6 +394,17 @@ class Index:
         c, on = _lib.QualParams(), C.c_int()
         check(self._lib.rtx_index_quality(self._h, C.byref(c), C.byref(on)))
         return QualParams._of(c) if on.value else None
+
+    def set_chimera(self, params) -> None:
+        """rtx_index_set_chimera: the ChimeraParams raxtax() checks every read with; None switches the stage off."""
+        check(self._lib.rtx_index_set_chimera(self._h, C.byref(params._c()) if params is not None else None))
+
+    @property
+    def chimera(self):
+        """The ChimeraParams the handle holds, or None (rtx_index_chimera)."""
+        c, on = _lib.ChimeraParams(), C.c_int()
+        check(self._lib.rtx_index_chimera(self._h, C.byref(c), C.byref(on)))
+        return ChimeraParams(c.segments, c.mindelta) if on.value else None
 
     def set_primers(self, patterns) -> None:
         """rtx_index_set_primers: the patterns (TrimPrimer, or (codes, end, max_errors[, window]) tuples; see primer_patterns) raxtax()
@@ -1040,6 +1053,79 @@ def raxtax_last_qual() -> Tuple[int, int, int, List[int], float]:
     return int(a.value), int(b.value), int(c.value), [int(x) for x in r], float(s.value)
 
 
+_CHIM = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(_lib.ChimeraRec))
+CHIMERA_MAX_QUERY = _lib.RTX_CHIMERA_MAX_QUERY
+CHIM_OK, CHIM_NO_KMER, CHIM_TOO_LONG = _lib.RTX_CHIM_OK, _lib.RTX_CHIM_NO_KMER, _lib.RTX_CHIM_TOO_LONG
+CHIMERA_DTYPE = np.dtype([(f, np.uint32) for f in _lib.RTX_CHIM_FIELDS])   # rtx_chimera_rec
+
+
+@dataclass
+class ChimeraParams:
+    """The chimera check's parameters (rtx_chimera_params): a read is cut into `segments` parts (2 .. 32) of its 8-mer windows, and flagged
+    when the best pair of references over a left and a right part explains `mindelta` windows more than the best single reference."""
+    segments: int = _lib.RTX_CHIMERA_DEFAULT_SEGMENTS
+    mindelta: int = _lib.RTX_CHIMERA_DEFAULT_MINDELTA
+
+    def _c(self) -> "_lib.ChimeraParams":
+        return _lib.ChimeraParams(int(self.segments), int(self.mindelta))
+
+
+def chimera_read(params: ChimeraParams, read: np.ndarray, ref_bases: np.ndarray, ref_off: np.ndarray) -> np.void:
+    """rtx_chimera_read: the record (a CHIMERA_DTYPE scalar) of ONE read on the host, computed from the reference sequences."""
+    read = np.ascontiguousarray(read, dtype=np.uint8)
+    ref_bases = np.ascontiguousarray(ref_bases, dtype=np.uint8)
+    ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
+    one = np.zeros(1, np.uint8)
+    rec = np.zeros(1, CHIMERA_DTYPE)
+    check(_lib.load().rtx_chimera_read(C.byref(params._c()), ptr(read if len(read) else one, u8p), len(read), ptr(ref_bases if len(ref_bases) else one, u8p),
+                                       ptr(ref_off, u64p), len(ref_off) - 1, rec.ctypes.data_as(C.c_void_p)))
+    return rec[0]
+
+
+class Chimera:
+    """The chimera check in front of one Index (rtx_chimera): one stream and buffers of its own; it borrows the handle's bitmap, so it keeps
+    the Index alive."""
+
+    def __init__(self, index: "Index", params: Optional[ChimeraParams] = None):
+        self._lib = _lib.load()
+        self._h = None
+        self._index = index
+        h = C.c_void_p()
+        check(self._lib.rtx_chimera_create(index._h, C.byref((params or ChimeraParams())._c()), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_chimera_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, bases: np.ndarray, base_off: np.ndarray) -> np.ndarray:
+        """One record per read (rtx_chimera_run), as a structured array of CHIMERA_DTYPE."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        n = len(base_off) - 1
+        out = np.zeros(max(n, 1), CHIMERA_DTYPE)
+        check(self._lib.rtx_chimera_run(self._h, n, ptr(bases if len(bases) else np.zeros(1, np.uint8), u8p), ptr(base_off, u64p), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def kernel_ms(self) -> float:
+        """Milliseconds of the scan kernels of the last run(), from HIP events (rtx_chimera_kernel_time)."""
+        ms = C.c_float()
+        check(self._lib.rtx_chimera_kernel_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
+
+def raxtax_last_chimera() -> Tuple[int, int, int, float]:
+    """rtx_raxtax_last_chimera: (queries, reads the stage checked -- the distinct ones under derep --, queries whose record is flagged, busy
+    seconds of the stage) of the last raxtax() call of this process; all 0 when its handles had no chimera check set."""
+    a, b, c, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    check(_lib.load().rtx_raxtax_last_chimera(C.byref(a), C.byref(b), C.byref(c), C.byref(s)))
+    return int(a.value), int(b.value), int(c.value), float(s.value)
+
+
 MERGE_MAX_READ = _lib.RTX_MERGE_MAX_READ
 MG_BAD_QUALITY, MG_TOO_LONG, MG_TOO_SHORT, MG_NO_OVERLAP = (1 << b for b in range(4))
 
@@ -1211,7 +1297,8 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
            align: Optional[Callable[[str, int, int, int, int, int, int, int], None]] = None,
            trim: Optional[Callable[[str, int, int, int, int], None]] = None,
            quals: Optional[Sequence[np.ndarray]] = None,
-           qual: Optional[Callable[[str, int, int, int, int, int], None]] = None) -> None:
+           qual: Optional[Callable[[str, int, int, int, int, int], None]] = None,
+           chimera: Optional[Callable[[str, np.void], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
@@ -1225,7 +1312,10 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     Handles built with quality=QualParams(...) need the quality strings of the reads: queries as (label, bases, quals) triples
     (parse_query_fastq_str) or `quals`, one array per query.  `qual(label, raw_len, lo, hi, ee, verdict)` is called for every query directly
     after `trim` (rtx_raxtax_multi_ex5): the range the primers and the filter kept, the expected errors times 2^40 and the verdict (0: passed;
-    qual_verdict_names); it goes with `align`, `trim` or alone."""
+    qual_verdict_names); it goes with `align`, `trim` or alone.
+    `chimera(label, record)` is called for every query directly after `qual` (rtx_raxtax_multi_ex6; handles built with chimera=ChimeraParams(...),
+    else an empty record): the query's CHIMERA_DTYPE record -- its representative's under derep; a flagged read is classified as the empty
+    read.  It goes with `align`, `trim`, `qual` or alone."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
@@ -1237,8 +1327,9 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     if (info is not None) + (hit is not None) + (align is not None) > 1:
         raise ValueError("raxtax: give one of info, hit and align")
     lib.rtx_raxtax_multi_ex5.argtypes = lib.rtx_raxtax_multi_ex4.argtypes + [u8p, _QUAL, C.c_void_p]
-    if (trim is not None or qual is not None) and (info is not None or hit is not None):
-        raise ValueError("raxtax: trim and qual go with align or alone")
+    lib.rtx_raxtax_multi_ex6.argtypes = lib.rtx_raxtax_multi_ex5.argtypes + [_CHIM, C.c_void_p]
+    if (trim is not None or qual is not None or chimera is not None) and (info is not None or hit is not None):
+        raise ValueError("raxtax: trim, qual and chimera go with align or alone")
     if quals is None and info is None and hit is None and len(queries) and all(len(q) == 3 for q in queries):
         quals = [q[2] for q in queries]   # (info and hit go through calls that carry no quality strings: triples are then read as pairs)
     if quals is not None and (info is not None or hit is not None):
@@ -1301,7 +1392,23 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if flat_q is not None or qual is not None:
+    def cb_chim(_ctx, label, rec):
+        try:
+            chimera(label.decode(), np.array([tuple(getattr(rec.contents, f) for f in _lib.RTX_CHIM_FIELDS)], CHIMERA_DTYPE)[0])
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if chimera is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex6(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
+                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None,
+                                      _TRIM(cb_trim) if trim is not None else C.cast(None, _TRIM), None,
+                                      ptr(flat_q, u8p) if flat_q is not None else None,
+                                      _QUAL(cb_qual) if qual is not None else C.cast(None, _QUAL), None, _CHIM(cb_chim), None)
+    elif flat_q is not None or qual is not None:
         arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         rc = lib.rtx_raxtax_multi_ex5(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                       int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),

@@ -32,6 +32,13 @@
 //    dereplication and classification see merged reads; a pair that is not merged is the empty read: no result lines.  PREFIX/raxtax.merge: a
 //    header, then label, forward length, reverse length, overlap, diffs, merged length and verdict (`merged`, or the reason it was not) per
 //    pair in input order; the totals go to the log.  --reverse with FASTA input, or a merge option without --reverse, is refused.)
+//   (--chimera [--chimera-mindelta N] [--chimera-segments S]: every read is checked against the references on the device before it is classified
+//    (rtx_index_set_chimera, rtx_chimera.hip; behind --derep, so a distinct read is checked once): the best pair of references over a left and
+//    a right part of the read against the best single reference, at S - 1 breakpoints (S = 2 .. 32, default 16); a read whose pair explains N
+//    windows more (default 24) is flagged and has no result lines, like a read the quality filter discards.  PREFIX/raxtax.chimera: a header,
+//    then label, status (ok, no_kmer, too_long), windows, single, parent_id, seg, pos, left, a_id, right, b_id, delta, Y|N|? (? where the read
+//    was not checked) and the lineages of the three references per query in input order, '-' where there is none; the totals go to the log.
+//    --chimera with --strand both is refused: a read is checked in the orientation given.)
 // A rerun with the same flags and database resumes: labels listed in raxtax.ckp are skipped
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
@@ -144,7 +151,8 @@ std::string fingerprint(const std::string &path) {
 // (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
 // (... and --primers with its two settings, as given: trimmed reads are other reads)
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
-                            const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string()) {
+                            const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string(),
+                            const std::string &chimera = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
@@ -153,6 +161,7 @@ std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv
     if (!primers.empty()) ss << ",\n  \"primers\": \"" << primers << "\"";
     if (!quality.empty()) ss << ",\n  \"quality\": \"" << quality << "\"";  // (... and the quality filter's settings, as given)
     if (!merge.empty()) ss << ",\n  \"merge\": \"" << merge << "\"";  // (... and --reverse with the merge settings: merged reads are other reads)
+    if (!chimera.empty()) ss << ",\n  \"chimera\": \"" << chimera << "\"";  // (... and --chimera with its two settings: flagged reads have no lines)
     ss << "\n}\n";
     return ss.str();
 }
@@ -191,7 +200,7 @@ uint8_t iupac_code(char ch) {
 }
 
 struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge;
+    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera;
     bool want_tsv = false, want_strand = false, want_hits = false;
     const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
 };
@@ -223,6 +232,9 @@ int main(int argc, char **argv) {
     std::string rev_file;                                              // --reverse FILE: the reverse mates of the pairs of -i, merged on the device (rtx_merge_queries), PREFIX/raxtax.merge
     rtx_merge_params merge{33u, 16u, 10u, 100u, 41u};                  // --merge-minovlen, --merge-maxdiffs, --merge-maxdiffpct, --merge-qcap (ascii_base: --fastq-ascii)
     std::string merge_opts;                                            // the merge options as given (empty: none)
+    bool chim_on = false;                                              // --chimera: rtx_index_set_chimera on every handle, PREFIX/raxtax.chimera
+    rtx_chimera_params chim{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA};  // --chimera-segments, --chimera-mindelta
+    std::string chim_opts;                                             // those two as given (empty: none)
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -323,6 +335,16 @@ int main(int argc, char **argv) {
             (a == "--merge-minovlen" ? merge.min_overlap : a == "--merge-maxdiffs" ? merge.max_diffs : a == "--merge-maxdiffpct" ? merge.max_diff_pct : merge.q_cap) = (uint32_t)x;
             merge_opts += (merge_opts.empty() ? "" : " ") + a;
         }
+        else if (a == "--chimera") chim_on = true;
+        else if (a == "--chimera-mindelta" || a == "--chimera-segments") {
+            const char *v = val();
+            char *end = nullptr;
+            const long x = strtol(v, &end, 10);
+            const long least = a == "--chimera-segments" ? 2 : 0, most = a == "--chimera-segments" ? (long)RTX_CHIMERA_MAX_SEGMENTS : (long)RTX_CHIMERA_MAX_QUERY;
+            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
+            (a == "--chimera-segments" ? chim.segments : chim.mindelta) = (uint32_t)x;
+            chim_opts += (chim_opts.empty() ? "" : " ") + a;
+        }
         else if (a == "--profile") {
             char *end = nullptr;
             const char *v = val();
@@ -335,7 +357,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -372,6 +394,16 @@ int main(int argc, char **argv) {
         fprintf(stderr, "raxtax-hip: --reverse needs FASTQ input: %s does not start with '@'\n", qf.empty() ? "-i" : qf.c_str());
         return 64;
     }
+    // --chimera: refused here as well where it cannot work
+    if (!chim_opts.empty() && !chim_on) {
+        fprintf(stderr, "raxtax-hip: %s sets how reads are checked for chimeras and needs --chimera\n", chim_opts.c_str());
+        return 64;
+    }
+    if (chim_on && both_strands) {
+        fprintf(stderr, "raxtax-hip: --chimera checks a read in the orientation given and cannot go with --strand both\n");
+        return 64;
+    }
+    const std::string chim_spec = chim_on ? "segments=" + std::to_string(chim.segments) + ";mindelta=" + std::to_string(chim.mindelta) : std::string();
     std::string merge_spec;
     if (merge_on) {
         merge.ascii_base = qual.ascii_base;
@@ -411,7 +443,7 @@ int main(int argc, char **argv) {
         primer_spec += (primer_spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
     }
     if (!primer_spec.empty()) primer_spec += ";errors=" + std::to_string(primer_pct) + ";window=" + std::to_string(primer_window);
-    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge";
+    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge", chim_path = prefix + "/raxtax.chimera";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && derep) {
         fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
@@ -423,7 +455,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -444,6 +476,7 @@ int main(int argc, char **argv) {
             if (!primers.empty()) purge_incomplete(trim_path, done, true);
             if (qual_on) purge_incomplete(qc_path, done, true);
             if (merge_on) purge_incomplete(merge_path, done, true);
+            if (chim_on) purge_incomplete(chim_path, done, true);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -497,7 +530,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -670,6 +703,7 @@ int main(int argc, char **argv) {
                     rcs[k] = rtx_index_set_primers(indices[k], pats.data(), (uint32_t)pats.size());
                 }
                 if (rcs[k] == RTX_OK && qual_on) rcs[k] = rtx_index_set_quality(indices[k], &qual);
+                if (rcs[k] == RTX_OK && chim_on) rcs[k] = rtx_index_set_chimera(indices[k], &chim);
                 if (rcs[k] == RTX_OK && profile_cutoff)
                     rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
@@ -721,6 +755,12 @@ int main(int argc, char **argv) {
         fprintf(stderr, "[INFO ] --reverse: pairs of %s and %s are merged on device %d: overlap at least %u, at most %u diffs and %u %% of the overlap, Q capped at %u\n", qf.c_str(),
                 rev_file.c_str(), devices[0], merge.min_overlap, merge.max_diffs, merge.max_diff_pct, merge.q_cap);
     } else if (mode == std::ios::trunc) remove(merge_path.c_str());  // (likewise)
+    if (chim_on) {
+        const bool header = mode == std::ios::trunc || !is_file(chim_path);
+        sink.chimera.open(chim_path, mode);
+        if (header) sink.chimera << "label\tstatus\twindows\tsingle\tparent_id\tseg\tpos\tleft\ta_id\tright\tb_id\tdelta\tchimera\tparent\ta\tb\n";
+        fprintf(stderr, "[INFO ] --chimera: %u segments, a read is flagged from delta %u on\n", chim.segments, chim.mindelta);
+    } else if (mode == std::ios::trunc) remove(chim_path.c_str());  // (likewise)
     sink.want_strand = both_strands;
     sink.want_hits = want_hits;
     sink.tree = tree;
@@ -785,6 +825,27 @@ int main(int argc, char **argv) {
         s->qc << '\n';
         return s->qc.good() ? 0 : 1;
     };
+    // ... and, under --chimera, what the check made of every query (also one without result lines: a flagged read)
+    auto checked = [](void *c, const char *label, const rtx_chimera_rec *r) -> int {
+        static const char *const status[3] = {"ok", "no_kmer", "too_long"};
+        Sink *s = static_cast<Sink *>(c);
+        auto id = [s](uint32_t ref) { if (ref == RTX_NO_REF) s->chimera << '-'; else s->chimera << ref; };
+        auto lin = [s](uint32_t ref) { if (ref == RTX_NO_REF) s->chimera << '-'; else s->chimera << rtx_tree_lineage(s->tree, ref); };
+        s->chimera << label << '\t' << status[r->status < 3u ? r->status : 0u] << '\t' << r->n_valid << '\t' << r->single << '\t';
+        id(r->parent);
+        s->chimera << '\t' << r->seg << '\t' << r->pos << '\t' << r->left << '\t';
+        id(r->parent_a);
+        s->chimera << '\t' << r->right << '\t';
+        id(r->parent_b);
+        s->chimera << '\t' << r->delta << '\t' << (r->status != RTX_CHIM_OK ? '?' : (r->flag ? 'Y' : 'N')) << '\t';
+        lin(r->parent);
+        s->chimera << '\t';
+        lin(r->parent_a);
+        s->chimera << '\t';
+        lin(r->parent_b);
+        s->chimera << '\n';
+        return s->chimera.good() ? 0 : 1;
+    };
     // (rtx_raxtax_multi_ex4 carries the callback of --identity: without that option the one of --strand both / --hits stands in its shape)
     auto info_as_align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {
         Sink *s = static_cast<Sink *>(c);
@@ -802,6 +863,8 @@ int main(int argc, char **argv) {
     double trim_busy = 0;
     uint64_t qual_total[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the quality filter: queries, passed, cut short, the seven reasons (rtx_raxtax_last_qual)
     double qual_busy = 0;
+    uint64_t chim_total[3] = {0, 0, 0};  // --chimera: queries, reads checked, queries flagged (rtx_raxtax_last_chimera)
+    double chim_busy = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
     double derep_busy = 0;
     uint64_t merge_total[6] = {0, 0, 0, 0, 0, 0};  // --reverse: pairs, merged, and not merged for each of the four reasons (RTX_MG_*)
@@ -849,7 +912,14 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            if (qual_on) {
+            if (chim_on) {
+                const uint8_t *quals = nullptr;
+                if (qual_on) rtx_queries_quals(pz.qs, &quals);
+                rc = rtx_raxtax_multi_ex6(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                          want_identity ? +align : (want_hits ? +info_as_align : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
+                                          quals, qual_on ? +filtered : nullptr, &sink, +checked, &sink);
+            }
+            else if (qual_on) {
                 const uint8_t *quals = nullptr;
                 rtx_queries_quals(pz.qs, &quals);
                 rc = rtx_raxtax_multi_ex5(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
@@ -877,6 +947,12 @@ int main(int argc, char **argv) {
                 double qb = 0;
                 if (rtx_raxtax_last_qual(&qq[0], &qq[1], &qq[2], qq + 3, &qb) == RTX_OK) { for (int k = 0; k < 10; k++) qual_total[k] += qq[k]; qual_busy += qb; }
                 if (timing) fprintf(stderr, "[TIMING] quality filter of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)qq[0], qb);
+            }
+            if (chim_on) {
+                uint64_t cq[3] = {0, 0, 0};
+                double cb = 0;
+                if (rtx_raxtax_last_chimera(&cq[0], &cq[1], &cq[2], &cb) == RTX_OK) { for (int k = 0; k < 3; k++) chim_total[k] += cq[k]; chim_busy += cb; }
+                if (timing) fprintf(stderr, "[TIMING] chimera check of this block: %llu queries, %llu reads checked, busy %.3f s (ahead of the device stage)\n", (unsigned long long)cq[0], (unsigned long long)cq[1], cb);
             }
             if (derep) {
                 uint64_t dq = 0, du = 0;
@@ -908,6 +984,7 @@ int main(int argc, char **argv) {
     if (!primers.empty()) sink.trim.flush();
     if (qual_on) sink.qc.flush();
     if (merge_on) sink.merge.flush();
+    if (chim_on) sink.chimera.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
     if (merge_on) {
@@ -926,6 +1003,11 @@ int main(int argc, char **argv) {
                 (unsigned long long)qual_total[2], (unsigned long long)qual_total[3], (unsigned long long)qual_total[4], (unsigned long long)qual_total[5],
                 (unsigned long long)qual_total[6], (unsigned long long)qual_total[7], (unsigned long long)qual_total[8], (unsigned long long)qual_total[9]);
         if (timing) t_log << ", \"qual_busy\": " << qual_busy;
+    }
+    if (chim_on) {
+        fprintf(stderr, "[INFO ] --chimera: %llu queries, %llu reads checked, %llu queries flagged\n", (unsigned long long)chim_total[0], (unsigned long long)chim_total[1],
+                (unsigned long long)chim_total[2]);
+        if (timing) t_log << ", \"chimera_busy\": " << chim_busy;
     }
     if (derep) {  // (per chunk: a copy in another chunk counts as a distinct read of its own)
         fprintf(stderr, "[INFO ] --derep: %llu queries, %llu distinct\n", (unsigned long long)derep_queries, (unsigned long long)derep_distinct);

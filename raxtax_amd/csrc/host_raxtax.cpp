@@ -81,6 +81,8 @@ struct LastTrim { uint64_t queries, with5, with3, emptied; double busy; };  // r
 LastTrim g_trim{0, 0, 0, 0, 0.0};
 struct LastQual { uint64_t queries, passed, truncated, reasons[7]; double busy; };  // rtx_raxtax_last_qual (under g_timing_mu)
 LastQual g_qual{0, 0, 0, {0, 0, 0, 0, 0, 0, 0}, 0.0};
+struct LastChim { uint64_t queries, checked, flagged; double busy; };  // rtx_raxtax_last_chimera (under g_timing_mu)
+LastChim g_chim{0, 0, 0, 0.0};
 
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
@@ -92,6 +94,8 @@ using RawInfo = std::function<bool(const char *, int, uint32_t, uint32_t, uint32
 using RawTrim = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint32_t)>;
 // (label, length as given, lo, hi, expected errors, verdict) of every query, directly after its RawTrim call (rtx_query_qual_fn)
 using RawQual = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint64_t, uint32_t)>;
+// (label, record) of every query, directly after its RawQual call (rtx_query_chimera_fn)
+using RawChim = std::function<bool(const char *, const rtx_chimera_rec *)>;
 
 // Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the
 // one thread that dereplicates, which was most of the stage; the buffers travel between the chunks of a call through a pool, so that
@@ -178,6 +182,11 @@ struct Chunk {
     std::vector<uint64_t> q_ee;
     ByteBuf t_bases;
     std::vector<uint64_t> t_off;
+    // chimera check (rtx_index_set_chimera): rtx_chimera_run on the reads handed to the handle, [nu] (empty: off) -- query i's record is that of
+    // its representative; where a read was flagged the handle is given c_bases / c_off ([nu + 1] from 0) with the flagged reads emptied
+    std::vector<rtx_chimera_rec> chim;
+    ByteBuf c_bases;
+    std::vector<uint64_t> c_off;
     rtx_text_view text{};              // RTX_OPT_DEVICE_TEXT: the messages as the device formatted them (valid as long as `res`)
     rtx_result_view res{};
     int stage = 0;                     // 1: exact matches looked up (or left to the device), 2: classified, 3: formatted, 4: sent
@@ -198,12 +207,15 @@ struct Chunk {
 //                   stage): the copies are looked for among the trimmed reads, and everything downstream sees those (Chunk::src_bases)
 //                   With a quality filter set (rtx_index_set_quality) the ranges the primers left are filtered next (rtx_qual_run, again
 //                   such a stage); both ranges are applied in one rtx_trim_apply, a discarded read goes on as the empty read
+//                   With the chimera check set (rtx_index_set_chimera) the reads that go to the handle -- behind the dereplication, so a
+//                   distinct read is checked once -- run through rtx_chimera_run (a stage object per handle: it borrows that handle's
+//                   bitmap); a flagged read goes on as the empty read through one more rtx_trim_apply, exactly as a discarded one
 //   calling thread: the sender, one message per query in INPUT order (raxtax.rs:85-87): chunk 0, 1, 2 ... as they become ready.
 // A handle keeps two result sets, so the view of its k-th chunk stays valid until its (k + 2)-th is classified.
 int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_t n_queries, const char *const *labels,
         const uint8_t *bases, const uint64_t *base_off, bool skip_exact_matches, bool raw_confidence, uint64_t chunk_size,
         const RawSender &sender, bool tsv, const RawInfo &info = RawInfo(), const RawTrim &trim_cb = RawTrim(), const uint8_t *quals = nullptr,
-        const RawQual &qual_cb = RawQual()) {
+        const RawQual &qual_cb = RawQual(), const RawChim &chim_cb = RawChim()) {
     if (!indices || n_dev == 0 || !tree || !base_off || !labels) { rtx::set_error("rtx_raxtax: null argument"); return RTX_ERR_INVALID; }
     for (uint32_t d = 0; d < n_dev; d++) {
         if (!indices[d]) { rtx::set_error("rtx_raxtax: null index handle"); return RTX_ERR_INVALID; }
@@ -318,6 +330,28 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             qualstages.own.push_back(qualstages.of[d]);
         }
     }
+    // Chimera check (rtx_index_set_chimera): the same setting on every handle.  One stage object (rtx_chimera.hip) per HANDLE: it reads that
+    // handle's bitmap.  Not with RTX_OPT_STRAND (rtx_chimera_create refuses it: a read is checked in the orientation given).
+    rtx_chimera_params cparams{};
+    const bool chim = rtx::index_chimera(indices[0], &cparams);
+    for (uint32_t d = 1; d < n_dev; d++) {
+        rtx_chimera_params other{};
+        if (rtx::index_chimera(indices[d], &other) != chim || (chim && (other.segments != cparams.segments || other.mindelta != cparams.mindelta))) {
+            rtx::set_error("rtx_raxtax_multi: the handles disagree on their chimera check (rtx_index_set_chimera)");
+            return RTX_ERR_INVALID;
+        }
+    }
+    struct Chims {
+        std::vector<rtx_chimera *> of;  // per handle
+        ~Chims() { for (auto *p : of) rtx_chimera_destroy(p); }
+    } chims;
+    if (chim) {
+        chims.of.assign(n_dev, nullptr);
+        for (uint32_t d = 0; d < n_dev; d++) {
+            const int rc = rtx_chimera_create(indices[d], &cparams, &chims.of[d]);
+            if (rc) return rc;
+        }
+    }
     for (uint32_t d = 0; d < n_dev; d++) {
         dev_lookup[d] = rtx_index_has_exact_lookup(indices[d]) != 0;
         any_host_lookup = any_host_lookup || !dev_lookup[d];
@@ -364,7 +398,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         chunks[c].dev_off = chunks[c].src_off = base_off + chunks[c].q0;
     }
     // busy seconds of the stages (rtx_raxtax_last_timing: which stage bounds an end-to-end run)
-    double busy_lookup = 0, busy_send = 0, busy_derep = 0, busy_trim = 0, busy_qual = 0;
+    double busy_lookup = 0, busy_send = 0, busy_derep = 0, busy_trim = 0, busy_qual = 0, busy_chim = 0;
+    uint64_t chim_queries = 0, chim_checked = 0, chim_flagged = 0;
     uint64_t qual_queries = 0, qual_passed = 0, qual_truncated = 0, qual_reasons[7] = {0, 0, 0, 0, 0, 0, 0};
     uint64_t derep_queries = 0, derep_distinct = 0;
     uint64_t trim_queries = 0, trim_with5 = 0, trim_with3 = 0, trim_emptied = 0;
@@ -399,7 +434,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     std::thread lookup([&] {
         for (uint64_t c = 0; c < n_chunks; c++) {
             Chunk &ch = chunks[c];
-            if (!derep && !trim && !qual && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
+            if (!derep && !trim && !qual && !chim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
             if (c >= ahead && !wait_stage(c - ahead, 2)) return;
             if (trim || qual) {  // the primers of the chunk's reads, then their quality, on the device (streams of their own beside the handle's); then the kept ranges
                 const double t_t0 = now();
@@ -463,7 +498,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 if (rc) { fail(rc, rtx_last_error()); return; }
                 if (trim) { trim_queries += ch.nq; busy_trim += (qual ? t_q0 : now()) - t_t0; }
                 if (qual) { qual_queries += ch.nq; busy_qual += now() - t_q0; }
-                if (!derep && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
+                if (!derep && !chim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
             }
             if (derep) {  // the copies of the chunk, on the device (a stream of its own beside the handle's); then the map's host side
                 const double t_r0 = now();
@@ -502,6 +537,42 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 derep_queries += ch.nq;
                 derep_distinct += ch.nu;
                 busy_derep += now() - t_r0;
+                if (!chim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
+            }
+            if (chim) {  // the reads that go to the handle, on the device (a stream of its own beside the handle's); a flagged one goes on empty
+                const double t_c0 = now();
+                ch.chim.resize(ch.nu);
+                int rc = rtx_chimera_run(chims.of[c % n_dev], ch.nu, ch.dev_bases, ch.dev_off, ch.chim.data());
+                bool any = false;
+                for (uint64_t u = 0; u < ch.nu && !rc && !any; u++) any = ch.chim[u].flag != 0u;
+                if (!rc && any) {  // (a chunk without a flagged read goes on as it came, without a copy)
+                    std::vector<uint32_t> lo(ch.nu, 0u), hi(ch.nu);
+                    uint64_t kept = 0;
+                    for (uint64_t u = 0; u < ch.nu; u++) {  // (a flagged read has at most RTX_CHIMERA_MAX_QUERY bases; a longer one is not checked and is not cut here)
+                        const uint64_t len = ch.dev_off[u + 1] - ch.dev_off[u];
+                        if (!ch.chim[u].flag && len > 0xFFFFFFFFull) { rc = RTX_ERR_INVALID; rtx::set_error("rtx_raxtax: a read of 2^32 bases or more with the chimera check set"); break; }
+                        hi[u] = ch.chim[u].flag ? 0u : (uint32_t)len;
+                        kept += hi[u];
+                    }
+                    if (!rc) {
+                        {
+                            std::lock_guard<std::mutex> g(pool_mu);
+                            if (!bases_pool.empty()) { ch.c_bases = std::move(bases_pool.back()); bases_pool.pop_back(); }
+                        }
+                        if (!ch.c_bases.reserve(kept + 1)) { fail(RTX_ERR_OOM, "no memory for the checked reads of a chunk"); return; }
+                        ch.c_off.resize(ch.nu + 1);
+                        rc = rtx_trim_apply(ch.nu, ch.dev_bases, ch.dev_off, lo.data(), hi.data(), ch.c_bases.p, ch.c_off.data());
+                    }
+                    if (!rc) {
+                        ch.dev_bases = ch.c_bases.p;
+                        ch.dev_off = ch.c_off.data();
+                    }
+                }
+                if (rc) { fail(rc, rtx_last_error()); return; }
+                chim_queries += ch.nq;
+                chim_checked += ch.nu;
+                for (uint64_t i = 0; i < ch.nq; i++) chim_flagged += ch.chim[ch.slot.empty() ? i : ch.slot[i]].flag != 0u;
+                busy_chim += now() - t_c0;
                 if (dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
             }
             const double t_l0 = now();
@@ -785,6 +856,10 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 const bool ranged = !ch.lo.empty(), on = !ch.q_hi.empty();
                 if (!qual_cb(labels[q], raw, ranged ? ch.lo[i] : 0u, on ? ch.q_hi[i] : (ranged ? ch.hi[i] : raw), on ? ch.q_ee[i] : 0ull, on ? ch.q_verdict[i] : 0u)) { closed = true; break; }
             }
+            if (chim_cb) {  // likewise; a copy takes its representative's record
+                static const rtx_chimera_rec none{RTX_CHIM_OK, 0u, 0u, RTX_NO_REF, 0u, 0u, 0u, RTX_NO_REF, 0u, RTX_NO_REF, 0u, 0u};
+                if (!chim_cb(labels[q], ch.chim.empty() ? &none : &ch.chim[ch.slot.empty() ? i : ch.slot[i]])) { closed = true; break; }
+            }
             if (ch.status[i] != RTX_Q_OK) {
                 // the reference aborts here (prob.rs:21/162); report and skip the query instead
                 if (ch.status[i] == RTX_Q_ALL_KMERS) fprintf(stderr, "[ERROR] query %s holds every 8-mer (t = 65536): the reference asserts t < 65536 (raxtax.rs:56)\n", labels[q]);
@@ -823,10 +898,13 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint32_t>().swap(ch.keep_hi);
         std::vector<uint64_t>().swap(ch.q_ee);
         std::vector<uint64_t>().swap(ch.t_off);
+        std::vector<rtx_chimera_rec>().swap(ch.chim);
+        std::vector<uint64_t>().swap(ch.c_off);
         {
             std::lock_guard<std::mutex> g(pool_mu);
             if (ch.u_bases.p) bases_pool.push_back(std::move(ch.u_bases));
             if (ch.t_bases.p) bases_pool.push_back(std::move(ch.t_bases));
+            if (ch.c_bases.p) bases_pool.push_back(std::move(ch.c_bases));
             for (auto &a : ch.out_arena) arena_pool.push_back(std::move(a));
             for (auto &a : ch.tsv_arena) arena_pool.push_back(std::move(a));
         }
@@ -847,6 +925,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         g_timing = {{any_host_lookup ? busy_lookup : 0.0, bd, bf, busy_send}, n_chunks};
         g_derep = {derep_queries, derep_distinct, busy_derep};
         g_trim = {trim_queries, trim_with5, trim_with3, trim_emptied, busy_trim};
+        g_chim = {chim_queries, chim_checked, chim_flagged, busy_chim};
         g_qual = {qual_queries, qual_passed, qual_truncated, {qual_reasons[0], qual_reasons[1], qual_reasons[2], qual_reasons[3], qual_reasons[4], qual_reasons[5], qual_reasons[6]}, busy_qual};
     }
     if (failed != RTX_OK) { rtx::set_error("%s", failed_msg.c_str()); return failed; }
@@ -948,6 +1027,16 @@ extern "C" int rtx_raxtax_multi_ex5(rtx_index *const *indices, uint32_t n_indice
                                     int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                                     rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
                                     rtx_query_qual_fn qual, void *qual_ctx) {
+    return rtx_raxtax_multi_ex6(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender,
+                                sender_ctx, tsv, align, align_ctx, trim, trim_ctx, quals, qual, qual_ctx, nullptr, nullptr);
+}
+
+// ... and the chimera record of every query (rtx_index_set_chimera)
+extern "C" int rtx_raxtax_multi_ex6(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                                    rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx) {
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
@@ -959,8 +1048,10 @@ extern "C" int rtx_raxtax_multi_ex5(rtx_index *const *indices, uint32_t n_indice
     if (trim) ft = [&](const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit) { return trim(trim_ctx, label, raw_len, lo, hi, hit) == 0; };
     RawQual fq;
     if (qual) fq = [&](const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) { return qual(qual_ctx, label, raw_len, lo, hi, ee, verdict) == 0; };
+    RawChim fc;
+    if (chimera) fc = [&](const char *label, const rtx_chimera_rec *rec) { return chimera(chimera_ctx, label, rec) == 0; };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
-               tsv != 0, fi, ft, quals, fq);
+               tsv != 0, fi, ft, quals, fq, fc);
 }
 
 extern "C" int rtx_raxtax_last_timing(double busy[4], uint64_t *n_chunks) {
@@ -996,6 +1087,15 @@ extern "C" int rtx_raxtax_last_qual(uint64_t *queries, uint64_t *passed, uint64_
     if (truncated) *truncated = g_qual.truncated;
     if (reasons) for (int b = 0; b < 7; b++) reasons[b] = g_qual.reasons[b];
     if (busy_seconds) *busy_seconds = g_qual.busy;
+    return RTX_OK;
+}
+
+extern "C" int rtx_raxtax_last_chimera(uint64_t *queries, uint64_t *checked, uint64_t *flagged, double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_chim.queries;
+    if (checked) *checked = g_chim.checked;
+    if (flagged) *flagged = g_chim.flagged;
+    if (busy_seconds) *busy_seconds = g_chim.busy;
     return RTX_OK;
 }
 

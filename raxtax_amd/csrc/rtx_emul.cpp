@@ -963,4 +963,68 @@ void emul_profile(uint64_t nq, const uint8_t *status, const uint32_t *row_count,
     }
 }
 
+// ---- chimera check (rtx_chimera.hip) --------------------------------------------------------------------------------------------------
+// The boundaries b[S + 1] and the padded layout of both directions (off0 / off1 [S + 1]: chimera_layout); returns the entries a list of
+// it is allotted (chimera_list_cap), 0 for an S out of range.
+uint32_t emul_chimera_layout(uint32_t n_pos, uint32_t S, uint32_t *b, uint32_t *off0, uint32_t *off1) {
+    if (S < 2u || S > kChimMaxSegments) return 0u;
+    for (uint32_t s = 0; s <= S; s++) b[s] = chimera_boundary(n_pos, S, s);
+    const uint32_t rows = chimera_layout(n_pos, S, 0u, off0);
+    chimera_layout(n_pos, S, 1u, off1);
+    return rows == chimera_list_rows(n_pos, S) && off1[S] == rows ? chimera_list_cap(rows) : 0u;
+}
+// The list of direction `dir` as chimera_rows_kernel fills it: out[j] = the window of entry j or 0xFFFFFFFF (the zero row), for j < cap.
+void emul_chimera_list(uint32_t n_pos, uint32_t S, uint32_t dir, uint32_t cap, uint32_t *out) {
+    uint32_t off[kChimMaxSegments + 1];
+    chimera_layout(n_pos, S, dir, off);
+    for (uint32_t lane = 0; lane < 64u; lane++)
+        for (uint32_t j = lane; j < cap; j += 64u) out[j] = chimera_list_window(n_pos, S, dir, off, j);
+}
+uint32_t emul_chimera_n_pos(uint32_t len) { return chimera_n_pos(len); }
+// A checkpoint of chimera_scan_kernel on one tile: counts[8192] (each < 2^planes; 0 behind the references the tile holds) are laid into the
+// planes of the 64 lanes by ref_slot, every lane runs chimera_lane_best, then the wave maximum and the minimum over the lanes that hold it.
+// *count / *ref (global id, 0xFFFFFFFF: none); returns 0 / -1 as above.
+int emul_chimera_checkpoint(const uint16_t *counts, int planes, uint32_t stride_bytes, uint32_t tile, uint32_t *count, uint32_t *ref) {
+    return emul_with_planes(planes, [&](auto tag) {
+        constexpr int NP = decltype(tag)::value;
+        const uint32_t L = tile_lanes(stride_bytes, tile);
+        std::vector<std::array<std::array<uint32_t, NP>, 4>> pl(64);
+        for (auto &l : pl)
+            for (auto &w : l) w.fill(0u);
+        for (uint32_t rl = 0; rl < 8192u && (rl >> 3) < L * 16u; rl++) {
+            uint32_t word, bit;
+            ref_slot(tile * 8192u + rl, stride_bytes, word, bit);
+            word -= tile * 256u;
+            for (int p = 0; p < NP; p++) pl[word >> 2][word & 3u][p] |= (((uint32_t)counts[rl] >> p) & 1u) << bit;
+        }
+        uint32_t m[64], r[64], M = 0;
+        for (uint32_t lane = 0; lane < 64u; lane++) {
+            uint32_t a[4][NP];
+            for (int w = 0; w < 4; w++)
+                for (int p = 0; p < NP; p++) a[w][p] = pl[lane][w][p];
+            chimera_lane_best<NP>(a, lane, L, m[lane], r[lane]);
+            M = std::max(M, m[lane]);
+        }
+        uint32_t R = kChimNoRef;
+        for (uint32_t lane = 0; lane < 64u; lane++) R = std::min(R, M != 0u && m[lane] == M ? tile * 8192u + r[lane] : kChimNoRef);
+        *count = M;
+        *ref = R;
+    });
+}
+// chimera_reduce_kernel: best [2][S][ntiles][2] (count, reference) as the scan stores them -> the record (twelve words)
+void emul_chimera_reduce(uint32_t len, uint32_t n_valid, uint32_t S, uint32_t mindelta, uint32_t ntiles, const uint32_t *best, uint32_t *rec) {
+    uint32_t pm[kChimMaxSegments + 1] = {0}, sm[kChimMaxSegments + 1] = {0}, pr[kChimMaxSegments + 1], sr[kChimMaxSegments + 1];
+    for (uint32_t s = 0; s <= kChimMaxSegments; s++) pr[s] = sr[s] = kChimNoRef;
+    if (n_valid != 0u && len <= kChimMaxQuery)
+        for (uint32_t lane = 0; lane < 2u * S; lane++) {
+            const uint32_t dir = lane / S, k = lane % S;
+            uint32_t bc = 0u, br = kChimNoRef;
+            for (uint32_t t = 0; t < ntiles; t++) chimera_take(bc, br, best[((size_t)lane * ntiles + t) * 2u], best[((size_t)lane * ntiles + t) * 2u + 1u]);
+            if (dir == 0u) { pm[k + 1u] = bc; pr[k + 1u] = br; }
+            else { sm[S - 1u - k] = bc; sr[S - 1u - k] = br; }
+        }
+    const ChimRec r = chimera_record(len, n_valid, S, mindelta, pm, pr, sm, sr);
+    std::memcpy(rec, &r, sizeof r);
+}
+
 }  // extern "C"

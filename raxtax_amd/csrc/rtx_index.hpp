@@ -467,6 +467,8 @@ struct rtx_index {
     uint32_t derep_opt = 0;          // RTX_OPT_DEREP: rtx_raxtax* classify each distinct read of a chunk once (rtx_derep.hip); the handle itself never reads it
     rtx_qual_params quality{};       // rtx_index_set_quality: rtx_raxtax* filter every read by its quality string (rtx_qual.hip); the handle itself never reads it
     bool quality_on = false;
+    rtx_chimera_params chimera{};    // rtx_index_set_chimera: the chimera check its callers run in front of it (rtx_chimera.hip); the handle itself never reads it
+    bool chimera_on = false;
     std::vector<rtx::TrimPrimer> primers;  // rtx_index_set_primers: rtx_raxtax* trim every read with them first (rtx_trim.hip); the handle itself never reads them
     DevBuf<char> d_lin_bytes, d_text;
     DevBuf<uint64_t> d_lin_off;

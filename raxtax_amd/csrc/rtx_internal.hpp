@@ -50,6 +50,10 @@ bool qual_params_on(const rtx_qual_params &p);
 bool qual_params_equal(const rtx_qual_params &a, const rtx_qual_params &b);
 const uint64_t *qual_table();
 bool index_quality(const rtx_index *index, rtx_qual_params *params);
+// chimera check (rtx_chimera.hip): the checks of a parameter struct (RTX_OK, or RTX_ERR_INVALID with the field named) and the setting a
+// handle holds (rtx_index_set_chimera; false: off)
+int chimera_check_params(const char *who, const rtx_chimera_params *p);
+bool index_chimera(const rtx_index *index, rtx_chimera_params *params);
 bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value
 bool hw_queues_for_run_ahead();  // (host_threads.cpp) GPU_MAX_HW_QUEUES reads six or more: transfers do not share a hardware queue with kernels
 

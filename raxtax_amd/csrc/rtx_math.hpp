@@ -1267,4 +1267,112 @@ RTX_HD ProfileStep profile_step(const ProfileSrc &s, uint64_t q, uint32_t one, u
     return r;
 }
 
+// ---------------------------------------------------------------------------
+// Chimera check (rtx_chimera.hip; rtx_chimera_read on the host; emul_chimera_* on x86) -- include/raxtax_hip.h has the definition.  Exact
+// integers.  A read of n_pos windows is cut into S segments at b_s = floor(s n_pos / S); the scan kernel folds the bitmap rows of the
+// windows in position order and looks at the planes after every segment (a checkpoint), so every segment of the row list is padded with
+// the zero row to a multiple of eight rows: a checkpoint then falls between two fold groups.  Two lists per read: direction 0 holds the
+// segments 0 .. S-1 (checkpoint k: P[k + 1]), direction 1 the segments S-1 .. 0 (checkpoint k: Suf[S - 1 - k]).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kChimMaxSegments = 32u;     // RTX_CHIMERA_MAX_SEGMENTS
+constexpr uint32_t kChimMaxQuery = 4096u;      // RTX_CHIMERA_MAX_QUERY: n_pos <= 4089 fits twelve planes
+constexpr uint32_t kChimNoRef = 0xFFFFFFFFu;   // RTX_NO_REF
+constexpr uint32_t kChimOk = 0u, kChimNoKmer = 1u, kChimTooLong = 2u;  // RTX_CHIM_*
+constexpr uint32_t kChimListTail = 192u;       // zero rows behind a list: what the scan's look-ahead loads reach (chimera_scan_kernel)
+RTX_HD uint32_t chimera_n_pos(uint32_t len) { return len > kChimMaxQuery || len < 8u ? 0u : len - 7u; }
+RTX_HD uint32_t chimera_boundary(uint32_t n_pos, uint32_t S, uint32_t s) { return s * n_pos / S; }  // (s n_pos <= 32 * 4089)
+// segment of direction `dir`'s k-th place
+RTX_HD uint32_t chimera_seg_at(uint32_t S, uint32_t dir, uint32_t k) { return dir ? S - 1u - k : k; }
+// off[k]: the first row of the k-th segment of direction `dir` in its list, off[S]: the rows of the list (a multiple of 8)
+RTX_HD uint32_t chimera_layout(uint32_t n_pos, uint32_t S, uint32_t dir, uint32_t *off /*[S + 1]*/) {
+    uint32_t at = 0;
+    for (uint32_t k = 0; k < S; k++) {
+        const uint32_t s = chimera_seg_at(S, dir, k);
+        off[k] = at;
+        at += (chimera_boundary(n_pos, S, s + 1u) - chimera_boundary(n_pos, S, s) + 7u) & ~7u;
+    }
+    off[S] = at;
+    return at;
+}
+// rows of a list whatever the direction, and the entries a list of it is allotted (the tail, to whole groups of 64)
+RTX_HD uint32_t chimera_list_rows(uint32_t n_pos, uint32_t S) {
+    uint32_t at = 0;
+    for (uint32_t s = 0; s < S; s++) at += (chimera_boundary(n_pos, S, s + 1u) - chimera_boundary(n_pos, S, s) + 7u) & ~7u;
+    return at;
+}
+RTX_HD uint32_t chimera_list_cap(uint32_t rows) { return ((rows + 63u) & ~63u) + kChimListTail; }
+// the window that entry j of direction `dir`'s list holds, or kChimNoRef: padding (off: chimera_layout of that direction)
+RTX_HD uint32_t chimera_list_window(uint32_t n_pos, uint32_t S, uint32_t dir, const uint32_t *off, uint32_t j) {
+    if (j >= off[S]) return kChimNoRef;
+    uint32_t k = 0;
+    while (k + 1u < S && off[k + 1u] <= j) k++;
+    const uint32_t s = chimera_seg_at(S, dir, k);
+    const uint32_t b0 = chimera_boundary(n_pos, S, s), b1 = chimera_boundary(n_pos, S, s + 1u);
+    const uint32_t i = b0 + (j - off[k]);
+    return i < b1 ? i : kChimNoRef;
+}
+// One lane's part of a checkpoint: the largest of its 128 counters and the lowest local reference of the tile that holds it (ref_slot
+// inverted: bit b of word w of lane l is group g = 4 w + b / 8, local reference (g L + l) 8 + b % 8 -- ascending in (w, b)).
+template <int NP>
+RTX_HD void chimera_lane_best(const uint32_t (&pl)[4][NP], uint32_t lane, uint32_t L, uint32_t &m, uint32_t &rl) {
+    m = 0;
+    rl = kChimNoRef;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {  // word by word (one candidate mask alive at a time): a later word wins only with a larger count
+        uint32_t cand;
+        const uint32_t mw = planes_max<NP>(pl[w], cand);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint32_t b = (uint32_t)__ffs((int)cand) - 1u;
+#else
+        const uint32_t b = (uint32_t)__builtin_ctz(cand);  // (planes_max never leaves cand empty)
+#endif
+        const uint32_t r = (((uint32_t)w * 4u + (b >> 3)) * L + lane) * 8u + (b & 7u);
+        const bool take = w == 0 || mw > m;
+        rl = take ? r : rl;
+        m = take ? mw : m;
+    }
+}
+// (count, reference) of one checkpoint over the tiles, in ascending order: a later tile wins only with a larger count
+RTX_HD void chimera_take(uint32_t &best, uint32_t &ref, uint32_t count, uint32_t r) {
+    if (count > best) { best = count; ref = r; }
+}
+// The record of a read from its checkpoints over all tiles: pm / pr [S + 1] = max_r P_r[s] and the lowest r (kChimNoRef where 0), sm / sr
+// the same for Suf.  P[S] and Suf[0] are both `single`; the caller hands in what it has (pm[0], sm[S] are 0 by definition).
+struct ChimRec { uint32_t status, n_valid, single, parent, seg, pos, left, parent_a, right, parent_b, delta, flag; };
+RTX_HD ChimRec chimera_record(uint32_t len, uint32_t n_valid, uint32_t S, uint32_t mindelta, const uint32_t *pm, const uint32_t *pr,
+                              const uint32_t *sm, const uint32_t *sr) {
+    ChimRec r{kChimOk, 0u, 0u, kChimNoRef, 0u, 0u, 0u, kChimNoRef, 0u, kChimNoRef, 0u, 0u};
+    if (len > kChimMaxQuery) { r.status = kChimTooLong; return r; }
+    if (n_valid == 0u) { r.status = kChimNoKmer; return r; }
+    const uint32_t n_pos = chimera_n_pos(len);
+    r.n_valid = n_valid;
+    r.single = pm[S];
+    r.parent = r.single ? pr[S] : kChimNoRef;
+    uint32_t best = 0;
+    r.seg = 1u;
+    for (uint32_t s = 1; s < S; s++) {
+        const uint32_t two = pm[s] + sm[s];
+        if (s == 1u || two > best) { best = two; r.seg = s; }
+    }
+    r.pos = chimera_boundary(n_pos, S, r.seg);
+    r.left = pm[r.seg];
+    r.parent_a = r.left ? pr[r.seg] : kChimNoRef;
+    r.right = sm[r.seg];
+    r.parent_b = r.right ? sr[r.seg] : kChimNoRef;
+    r.delta = best - r.single;
+    r.flag = r.delta >= mindelta ? 1u : 0u;
+    return r;
+}
+// the 8-mer of window i of a read (sequence_to_kmers' rule: all eight bases plain codes), false: not valid
+RTX_HD bool chimera_window_kmer(const uint8_t *seq, uint32_t i, uint32_t &k) {
+    k = 0;
+    bool ok = true;
+    for (uint32_t j = 0; j < 8u; j++) {
+        const uint32_t c = seq[i + j];
+        ok = ok && (c == 1u || c == 2u || c == 4u || c == 8u);
+        k = (k << 2) | (c == 2u ? 1u : (c == 4u ? 2u : (c == 8u ? 3u : 0u)));
+    }
+    return ok;
+}
+
 }  // namespace rtx
