@@ -49,7 +49,10 @@ extern "C" {
                                 rtx_raxtax_last_qual / rtx_raxtax_multi_ex5: the same; and with paired-end merging, rtx_merge_* /
                                 rtx_queries_merge_report / rtx_fastq_block_end_n: exports only; and with the chimera check, rtx_chimera_* /
                                 rtx_index_set_chimera / rtx_index_chimera / rtx_raxtax_last_chimera / rtx_raxtax_multi_ex6: exports and a
-                                setting that is off by default) */
+                                setting that is off by default; and with sample demultiplexing, rtx_demux_* / rtx_index_set_tags /
+                                rtx_index_tags / rtx_raxtax_last_demux / rtx_raxtax_multi_ex7 and the per-sample counters
+                                rtx_index_profile_begin_samples / _read_samples / rtx_batch_prefetch_samples / rtx_sample_profile_merge /
+                                rtx_sample_table_format: the same) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -522,6 +525,47 @@ int64_t rtx_profile_format(const rtx_tree *tree, const uint64_t *clade, const ui
  * stage the copies of every distinct read this way under RTX_OPT_DEREP. */
 int rtx_batch_prefetch_weights(rtx_index *index, uint64_t n_queries, const uint32_t *weights);
 
+/* ---- per-sample counts beside the profile (rtx_profile.hip: profile_samples_kernel) ------------------------------------------------------
+ * The taxon x sample table of a pooled run: the profile's `direct` and `totals` once more, split by the sample every query belongs to
+ * (rtx_demux_run names it).  A query with a sample s adds its weight (or 1) to direct_by_sample[s][a_{L-1}] when it is classified, and to
+ * totals_by_sample[s][0] and the entry of its kind, exactly as it adds to the profile's own counters -- with the same best lineage, cutoff
+ * and flags, once per accepted batch.  Integer adds: exact, independent of the order.  The per-sample clade is derived on the host
+ * (clade[n] = direct[n] + the clade of n's children: rtx_sample_table_format does).  A sparse table, per-sample conf_sum and
+ * dereplication together with samples are out of scope.
+ *   rtx_index_profile_begin_samples  opens a profile exactly as rtx_index_profile_begin does -- every rtx_index_profile_* call works on it
+ *                            unchanged, end frees everything -- and allocates and zeroes direct_by_sample[n_samples][n_nodes] and
+ *                            totals_by_sample[n_samples][4] (uint64).  RTX_ERR_INVALID besides: n_samples == 0, or n_samples x n_nodes
+ *                            above RTX_PROFILE_MAX_SAMPLE_COUNTERS (2^28 counters, 2 GiB; rtx_last_error names the limit).
+ *   rtx_batch_prefetch_samples  one sample per query for the batch that the NEXT rtx_batch_prefetch / rtx_batch_upload stages: the path and
+ *                            the rules of rtx_batch_prefetch_weights (asynchronous, taken or dropped at that prefetch, dropped on a count
+ *                            that does not match, indexed by the caller's query under RTX_OPT_STRAND).  RTX_DEMUX_NONE: the query
+ *                            counts in no sample; any other value >= n_samples: RTX_ERR_INVALID; RTX_ERR_STATE without such a profile.
+ *                            A batch with nothing staged counts in no sample.
+ *   rtx_index_profile_read_samples  the per-sample counters of everything downloaded so far, copied to host arrays that stay valid until
+ *                            the next such read, reset or end.  RTX_ERR_STATE without such a profile.  rtx_index_profile_reset zeroes
+ *                            them with the rest.
+ *   rtx_sample_profile_merge sums n such views (one handle per GPU) into caller arrays of n_samples x n_nodes and n_samples x 4 entries;
+ *                            RTX_ERR_INVALID when the views differ in n_nodes, n_samples, cutoff or flags.
+ *   rtx_sample_table_format  the table: "# cutoff=0.80<TAB>samples=S"; four lines "# queries", "# classified", "# unclassified",
+ *                            "# unclassifiable", each followed by S tab-separated values; "depth<TAB>taxon<TAB>lineage" followed by the S
+ *                            names; then one line per node whose clade is not zero in some sample, in the pre-order of rtx_profile_format:
+ *                            depth, taxon, lineage and the S clade counts.  Every line ends in '\n', no NUL; the return convention of
+ *                            rtx_profile_format. */
+#define RTX_PROFILE_MAX_SAMPLE_COUNTERS (1ull << 28)
+typedef struct {
+    uint32_t n_nodes, n_samples;
+    uint32_t cutoff_hundredths;
+    uint32_t flags;
+    const uint64_t *direct; /* [n_samples][n_nodes] */
+    const uint64_t *totals; /* [n_samples][4] */
+} rtx_sample_profile_view;
+int rtx_index_profile_begin_samples(rtx_index *index, uint32_t cutoff_hundredths, uint32_t flags, uint32_t n_samples);
+int rtx_batch_prefetch_samples(rtx_index *index, uint64_t n_queries, const uint32_t *sample);
+int rtx_index_profile_read_samples(rtx_index *index, rtx_sample_profile_view *out);
+int rtx_sample_profile_merge(rtx_sample_profile_view *const *views, uint32_t n, uint64_t *direct, uint64_t *totals);
+int64_t rtx_sample_table_format(const rtx_tree *tree, uint32_t n_samples, const char *const *names, const uint64_t *direct, const uint64_t *totals,
+                                uint32_t cutoff_hundredths, char *out, uint64_t cap);
+
 /* The same in stages, so that a caller (bench.py) can keep inputs resident in HBM and
  * time the device part alone, or overlap stages of different batches. */
 int rtx_batch_upload(rtx_index *index, uint64_t n_queries, const uint8_t *bases,
@@ -614,6 +658,81 @@ int rtx_trim_apply(uint64_t n, const uint8_t *bases, const uint64_t *base_off, c
 int rtx_index_set_primers(rtx_index *index, const rtx_trim_pattern *pats, uint32_t n);
 int rtx_index_primers(const rtx_index *index, uint32_t *n);
 int rtx_raxtax_last_trim(uint64_t *queries, uint64_t *with5, uint64_t *with3, uint64_t *emptied, double *busy_seconds);
+
+/* ---- sample demultiplexing (rtx_demux.hip) -------------------------------------------------------------------------------------------------
+ * Pooled amplicon libraries carry a short tag in front of each primer that names the PCR, and with it the sample: what OBITools `ngsfilter`,
+ * `cutadapt -g file:tags.fasta` or `vsearch --fastx_demux` are run for, on the device.  Exact integers; the host function and the device
+ * agree bit for bit.
+ *   bytes        as in the primer trimming: codes 1 .. 15, two bytes match when both are codes and share a bit; a read byte that is 0 or
+ *                above 15 matches nothing; a tag byte must be a code.
+ *   placement    a tag of m codes at offset s (0 <= s <= max_offset, s + m <= len) covers the read's positions s .. s + m - 1; its distance
+ *                d is the number of positions that do not match.  Substitutions only: tags are designed in Hamming space, an insertion or
+ *                deletion inside a tag is NOT found (out of scope).  The offsets are for the heterogeneity spacers of 0 .. N bases in front
+ *                of a tag.
+ *   3' tag       given as it reads on the read, 5'->3'; the offset counts from the read's end, the tag covers [len - s - m, len - s): the 5'
+ *                problem of the reversed read.
+ *   one end      d* = the least d over all tags of that end and all admissible offsets (none admissible: nothing is found).  The end is
+ *                FOUND iff d* <= max_mismatches; it is AMBIGUOUS iff it is found and two different tags of it reach d*, at any offsets;
+ *                otherwise its tag is the one that reaches d*, at its least offset.  An end HAS A TAG when it is found and not
+ *                ambiguous.  An end with no tags in the list is not searched and cuts nothing.
+ *   verdict      the first that applies: RTX_DEMUX_AMBIGUOUS (3) either end is ambiguous; RTX_DEMUX_NO_TAG5 (1) the list has 5' tags and
+ *                none was found; RTX_DEMUX_NO_TAG3 (2) the same for 3'; RTX_DEMUX_UNKNOWN_PAIR (4) (tag5, tag3) is no pair of the table
+ *                (an end without tags in the list pairs as RTX_DEMUX_NO_TAG); RTX_DEMUX_OK (0).
+ *   per read     sample = the pair's sample when the verdict is RTX_DEMUX_OK, else RTX_DEMUX_NONE; lo = s5 + m5 where the 5' end has a
+ *                tag, else 0; hi = len - (s3 + m3) where the 3' end has one, else len; hi < lo: hi = lo (the read is left empty);
+ *                hit = tag5 | tag3 << 16 (places in the tag list, RTX_DEMUX_NO_TAG for an end that has none);
+ *                info = verdict | d5 << 8 | d3 << 16 | s5 << 24 | s3 << 28, zeros for an end that has no tag.
+ *                Never depends on the rest of the batch.
+ *   pairs        tag5 names a 5' tag and tag3 a 3' tag of the list; either, not both, may be RTX_DEMUX_NO_TAG (single-ended: it pairs
+ *                only while the list has no tag of that end); sample is any value but RTX_DEMUX_NONE.
+ *   rtx_demux_create  an object of its own on GPU `device` like rtx_trim: one stream, its own buffers (they only grow), no rtx_index, a
+ *                copy of the tags and a dense pair table.  Checked in this order: null arguments; n_tags == 0 or more than
+ *                RTX_DEMUX_MAX_TAGS on one end; every tag (len 0 or above RTX_DEMUX_MAX_TAG, a byte that is no code, an unknown end);
+ *                parameters above RTX_DEMUX_MAX_MISMATCHES / RTX_DEMUX_MAX_OFFSET; every pair (a tag out of range or of the wrong end,
+ *                both RTX_DEMUX_NO_TAG, sample RTX_DEMUX_NONE); the same (tag5, tag3) twice: RTX_ERR_INVALID; then the device:
+ *                RTX_ERR_NO_DEVICE without a gfx950.
+ *   rtx_demux_run     sample / lo / hi / hit / info of n reads, [n] each; bases / base_off as rtx_batch_prefetch takes them.  Only the
+ *                first and last max_offset + 32 bases of a read travel to the device.  n == 0: RTX_OK; a base_off that is not monotone,
+ *                a read of 2^32 bases or more, n > 2^31 - 2: RTX_ERR_INVALID.  Synchronous; calls on one object are serialised by the
+ *                caller.
+ *   rtx_demux_read    one read on the host (no device), with the function the kernel calls; the checks of rtx_demux_create.
+ *   rtx_index_set_tags  the tag list rtx_raxtax* demultiplex every read with before anything else sees it (n_tags == 0, the default: off --
+ *                no new code runs, nothing is allocated, every output is what it is without; otherwise the checks of rtx_demux_create).
+ *                Like rtx_index_set_primers honoured by the mirror alone, the handle keeps a copy, and the handles of one call must hold
+ *                the same list: RTX_ERR_INVALID otherwise.  The stage stands behind the merging of read pairs and in front of the primer
+ *                trimming: the chunk's own copies of the bases (and qualities) are cut to [lo, hi) first, so trimming, quality filter,
+ *                dereplication and chimera check run unchanged on the cut read and their callbacks report positions in it.  A read
+ *                whose verdict is not RTX_DEMUX_OK is reported and not classified: it goes on as the empty read, as a discarded or
+ *                flagged read does.  Where a profile with samples is open (rtx_index_profile_begin_samples) every chunk's samples are
+ *                staged with rtx_batch_prefetch_samples.  Tags together with RTX_OPT_DEREP and an open profile: RTX_ERR_INVALID
+ *                (copies from different samples would be counted as one read); tags with RTX_OPT_DEREP alone are allowed.
+ *                rtx_index_tags: how many tags it holds. */
+#define RTX_DEMUX_MAX_TAGS 1024 /* per end */
+#define RTX_DEMUX_MAX_TAG 32    /* codes per tag */
+#define RTX_DEMUX_MAX_OFFSET 15
+#define RTX_DEMUX_MAX_MISMATCHES 8
+#define RTX_DEMUX_NO_TAG 0xFFFFu
+#define RTX_DEMUX_NONE 0xFFFFFFFFu /* no sample */
+#define RTX_DEMUX_OK 0u
+#define RTX_DEMUX_NO_TAG5 1u
+#define RTX_DEMUX_NO_TAG3 2u
+#define RTX_DEMUX_AMBIGUOUS 3u
+#define RTX_DEMUX_UNKNOWN_PAIR 4u
+typedef struct { const uint8_t *codes; uint32_t len, end; } rtx_demux_tag;  /* end: RTX_TRIM_5P / RTX_TRIM_3P */
+typedef struct { uint32_t tag5, tag3, sample; } rtx_demux_pair;             /* places in the tag list */
+typedef struct { uint32_t max_mismatches, max_offset; } rtx_demux_params;
+typedef struct rtx_demux rtx_demux;
+int rtx_demux_create(int device, const rtx_demux_tag *tags, uint32_t n_tags, const rtx_demux_pair *pairs, uint32_t n_pairs,
+                     const rtx_demux_params *params, rtx_demux **out);
+int rtx_demux_run(rtx_demux *d, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *sample /*[n]*/, uint32_t *lo /*[n]*/,
+                  uint32_t *hi /*[n]*/, uint32_t *hit /*[n]*/, uint32_t *info /*[n]*/);
+void rtx_demux_destroy(rtx_demux *d);
+int rtx_demux_kernel_time(const rtx_demux *d, float *ms); /* milliseconds of the kernel of the last rtx_demux_run, from HIP events around it */
+int rtx_index_set_tags(rtx_index *index, const rtx_demux_tag *tags, uint32_t n_tags, const rtx_demux_pair *pairs, uint32_t n_pairs,
+                       const rtx_demux_params *params);
+int rtx_index_tags(const rtx_index *index, uint32_t *n_tags);
+int rtx_demux_read(const rtx_demux_params *params, const rtx_demux_tag *tags, uint32_t n_tags, const rtx_demux_pair *pairs, uint32_t n_pairs,
+                   const uint8_t *read, uint64_t len, uint32_t *sample, uint32_t *lo, uint32_t *hi, uint32_t *hit, uint32_t *info);
 
 /* ---- quality filter (rtx_qual.hip; rtx_index_set_quality is the host mirror's use of it) -----------------------------------------------------
  * The step that starts an amplicon pipeline (`vsearch --fastq_filter`, DADA2 `filterAndTrim`) on the device: where a read is cut and whether
@@ -1099,6 +1218,21 @@ int rtx_raxtax_multi_ex6(rtx_index *const *indices, uint32_t n_indices, const rt
 /* The last rtx_raxtax* call of the process: its queries, the reads the stage checked (the distinct ones under RTX_OPT_DEREP), the queries
  * whose record is flagged, and the busy seconds of the stage; all 0 when its handles had no chimera check set. */
 int rtx_raxtax_last_chimera(uint64_t *queries, uint64_t *checked, uint64_t *flagged, double *busy_seconds);
+/* rtx_raxtax_multi_ex6 with a callback for the sample demultiplexing (rtx_index_set_tags): called for EVERY query of the caller, in input
+ * order, directly before its other callbacks: the length of the read as given, its sample, the range [lo, hi) the tags left of it and the
+ * hit and info words of rtx_demux_run -- RTX_DEMUX_NONE, 0, raw_len, no tags and 0 with no tags set.  The callbacks behind it then speak of
+ * the demultiplexed read: their raw_len is hi - lo (0 for a read that is not assigned), their positions count from lo.  Any callback may
+ * be NULL. */
+typedef int (*rtx_query_demux_fn)(void *ctx, const char *label, uint32_t raw_len, uint32_t sample, uint32_t lo, uint32_t hi, uint32_t hit, uint32_t info);
+int rtx_raxtax_multi_ex7(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                         rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx, rtx_query_demux_fn demux,
+                         void *demux_ctx);
+/* The last rtx_raxtax* call of the process: its queries, those assigned to a sample, the queries of every verdict (reasons[v], v =
+ * RTX_DEMUX_OK .. RTX_DEMUX_UNKNOWN_PAIR) and the busy seconds of the stage; all 0 when its handles had no tags set. */
+int rtx_raxtax_last_demux(uint64_t *queries, uint64_t *assigned, uint64_t reasons[5], double *busy_seconds);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

@@ -28,6 +28,11 @@ STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_wa
 RTX_TRIM_5P, RTX_TRIM_3P = 0, 1      # rtx_trim_pattern.end
 RTX_TRIM_MAX_PATTERNS, RTX_TRIM_MAX_PATTERN, RTX_TRIM_MAX_WINDOW, RTX_TRIM_NO_PATTERN = 8, 64, 256, 0xFF
 
+RTX_DEMUX_MAX_TAGS, RTX_DEMUX_MAX_TAG, RTX_DEMUX_MAX_OFFSET, RTX_DEMUX_MAX_MISMATCHES = 1024, 32, 15, 8
+RTX_DEMUX_NO_TAG, RTX_DEMUX_NONE = 0xFFFF, 0xFFFFFFFF
+RTX_PROFILE_MAX_SAMPLE_COUNTERS = 1 << 28
+RTX_DEMUX_NAMES = ("ok", "no_tag5", "no_tag3", "ambiguous", "unknown_pair")   # a verdict: RTX_DEMUX_OK .. RTX_DEMUX_UNKNOWN_PAIR
+
 RTX_QUAL_MAX_READ, RTX_QUAL_TABLE = 1 << 20, 94
 RTX_QC_NAMES = ("bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate")   # bit b of a verdict: RTX_QC_*
 
@@ -67,8 +72,24 @@ class ProfileView(C.Structure):
                 ("conf_sum", u64p), ("totals", C.c_uint64 * 4)]
 
 
+class SampleProfileView(C.Structure):   # rtx_sample_profile_view
+    _fields_ = [("n_nodes", C.c_uint32), ("n_samples", C.c_uint32), ("cutoff_hundredths", C.c_uint32), ("flags", C.c_uint32), ("direct", u64p), ("totals", u64p)]
+
+
 class TrimPattern(C.Structure):
     _fields_ = [("codes", u8p), ("len", C.c_uint32), ("end", C.c_uint32), ("max_errors", C.c_uint32), ("window", C.c_uint32)]
+
+
+class DemuxTag(C.Structure):   # rtx_demux_tag
+    _fields_ = [("codes", u8p), ("len", C.c_uint32), ("end", C.c_uint32)]
+
+
+class DemuxPair(C.Structure):   # rtx_demux_pair
+    _fields_ = [("tag5", C.c_uint32), ("tag3", C.c_uint32), ("sample", C.c_uint32)]
+
+
+class DemuxParams(C.Structure):   # rtx_demux_params
+    _fields_ = [("max_mismatches", C.c_uint32), ("max_offset", C.c_uint32)]
 
 
 class QualParams(C.Structure):   # rtx_qual_params
@@ -210,6 +231,11 @@ _SIGNATURES = {
     "rtx_profile_merge": (C.c_int, [C.POINTER(C.POINTER(ProfileView)), C.c_uint32, u64p, u64p, u64p, u64p]),
     "rtx_profile_format": (C.c_int64, [C.c_void_p, u64p, u64p, u64p, u64p, C.c_uint32, C.c_char_p, C.c_uint64]),
     "rtx_batch_prefetch_weights": (C.c_int, [C.c_void_p, C.c_uint64, u32p]),
+    "rtx_index_profile_begin_samples": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "rtx_batch_prefetch_samples": (C.c_int, [C.c_void_p, C.c_uint64, u32p]),
+    "rtx_index_profile_read_samples": (C.c_int, [C.c_void_p, C.POINTER(SampleProfileView)]),
+    "rtx_sample_profile_merge": (C.c_int, [C.POINTER(C.POINTER(SampleProfileView)), C.c_uint32, u64p, u64p]),
+    "rtx_sample_table_format": (C.c_int64, [C.c_void_p, C.c_uint32, C.POINTER(C.c_char_p), u64p, u64p, C.c_uint32, C.c_char_p, C.c_uint64]),
     "rtx_derep_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "rtx_derep_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, C.POINTER(C.c_uint64)]),
     "rtx_derep_destroy": (None, [C.c_void_p]),
@@ -225,6 +251,15 @@ _SIGNATURES = {
     "rtx_index_primers": (C.c_int, [C.c_void_p, u32p]),
     "rtx_raxtax_last_trim": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_raxtax_multi_ex4": (C.c_int, None),
+    "rtx_demux_create": (C.c_int, [C.c_int, C.POINTER(DemuxTag), C.c_uint32, C.POINTER(DemuxPair), C.c_uint32, C.POINTER(DemuxParams), C.POINTER(C.c_void_p)]),
+    "rtx_demux_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u32p, u32p, u32p, u32p]),
+    "rtx_demux_destroy": (None, [C.c_void_p]),
+    "rtx_demux_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_index_set_tags": (C.c_int, [C.c_void_p, C.POINTER(DemuxTag), C.c_uint32, C.POINTER(DemuxPair), C.c_uint32, C.POINTER(DemuxParams)]),
+    "rtx_index_tags": (C.c_int, [C.c_void_p, u32p]),
+    "rtx_raxtax_multi_ex7": (C.c_int, None),
+    "rtx_raxtax_last_demux": (C.c_int, [u64p, u64p, u64p, C.POINTER(C.c_double)]),
+    "rtx_demux_read": (C.c_int, [C.POINTER(DemuxParams), C.POINTER(DemuxTag), C.c_uint32, C.POINTER(DemuxPair), C.c_uint32, u8p, C.c_uint64, u32p, u32p, u32p, u32p, u32p]),
     "rtx_queries_parse_fastq": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.POINTER(C.c_void_p)]),
     "rtx_fastq_block_end": (C.c_uint64, [C.c_char_p, C.c_uint64]),
     "rtx_queries_parse_fastq_block": (C.c_int, [C.c_char_p, C.c_uint64, C.POINTER(C.c_char_p), C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),

@@ -297,6 +297,54 @@ def profile_text(tree: Tree, profile: Profile) -> str:
     return buf.raw[:n].decode()
 
 
+@dataclass
+class SampleProfile:
+    """The per-sample counters beside a profile (rtx_index_profile_read_samples), or a sum of several (sample_profile_merge): direct[s][n] the
+    queries of sample s assigned to node n of Tree.nodes(), totals[s] = queries, classified, unclassified, unclassifiable of sample s."""
+    cutoff: int
+    flags: int
+    direct: np.ndarray
+    totals: np.ndarray
+
+    def _view(self) -> "_lib.SampleProfileView":
+        self.direct = np.ascontiguousarray(self.direct, dtype=np.uint64)
+        self.totals = np.ascontiguousarray(self.totals, dtype=np.uint64)
+        v = _lib.SampleProfileView()
+        v.n_samples, v.n_nodes = self.direct.shape
+        v.cutoff_hundredths, v.flags = self.cutoff, self.flags
+        v.direct, v.totals = ptr(self.direct, u64p), ptr(self.totals, u64p)
+        return v
+
+
+def sample_profile_merge(profiles: Sequence[SampleProfile]) -> SampleProfile:
+    """rtx_sample_profile_merge: the sum of the per-sample counters of several handles (one per GPU); they must agree on the nodes, the samples,
+    the cutoff and the flags."""
+    if not profiles:
+        raise ValueError("sample_profile_merge: no profiles")
+    views = [p._view() for p in profiles]
+    arr = (C.POINTER(_lib.SampleProfileView) * len(views))(*[C.pointer(v) for v in views])
+    direct = np.zeros(profiles[0].direct.shape, np.uint64)
+    totals = np.zeros((direct.shape[0], 4), np.uint64)
+    check(_lib.load().rtx_sample_profile_merge(arr, len(views), ptr(direct if direct.size else np.zeros(1, np.uint64), u64p), ptr(totals, u64p)))
+    return SampleProfile(profiles[0].cutoff, profiles[0].flags, direct, totals)
+
+
+def sample_table_text(tree: Tree, names: Sequence[str], profile: SampleProfile) -> str:
+    """rtx_sample_table_format: the taxon x sample table of per-sample clade counts over `tree` (what raxtax-hip --tags --profile writes to
+    PREFIX/raxtax.samples); names: one per sample."""
+    lib = _lib.load()
+    direct = np.ascontiguousarray(profile.direct, dtype=np.uint64)
+    totals = np.ascontiguousarray(profile.totals, dtype=np.uint64)
+    if len(names) != direct.shape[0] or totals.shape != (direct.shape[0], 4):
+        raise ValueError(f"sample_table_text: {len(names)} names, counters of shape {direct.shape} and {totals.shape}")
+    cn = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    args = [tree._h, len(names), cn, ptr(direct if direct.size else np.zeros(1, np.uint64), u64p), ptr(totals, u64p), int(profile.cutoff)]
+    n = check(lib.rtx_sample_table_format(*args, None, 0))
+    buf = C.create_string_buffer(max(n, 1))
+    check(lib.rtx_sample_table_format(*args, buf, n))
+    return buf.raw[:n].decode()
+
+
 DEFAULT_SEGMENT_CLASSES = 1   # RTX_DEFAULT_SEGMENT_CLASSES of the library (rtx_api_index.hip: g_seg_classes)
 
 
@@ -313,7 +361,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None):
+                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None, tags=None):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -376,6 +424,8 @@ class Index:
             check(self._lib.rtx_index_set_option(self._h, _lib.RTX_OPT_DEREP, 1))
         if primers:   # rtx_index_set_primers: raxtax() trims every read with them first (rtx_trim.hip); classify() ignores them
             self.set_primers(primers)
+        if tags:   # rtx_index_set_tags: raxtax() assigns every read to a sample and cuts its tags first (rtx_demux.hip); classify() ignores them
+            self.set_tags(*tags)
         if quality is not None:   # rtx_index_set_quality: raxtax() filters every read by its quality string (rtx_qual.hip); classify() ignores it
             self.set_quality(quality)
         if chimera is not None:   # rtx_index_set_chimera: raxtax() checks every read against the references first (rtx_chimera.hip); classify() ignores it
@@ -405,6 +455,19 @@ class Index:
         c, on = _lib.ChimeraParams(), C.c_int()
         check(self._lib.rtx_index_chimera(self._h, C.byref(c), C.byref(on)))
         return ChimeraParams(c.segments, c.mindelta) if on.value else None
+
+    def set_tags(self, tags, pairs=(), params=None) -> None:
+        """rtx_index_set_tags: the tags (DemuxTag or (codes, end)), pairs ((tag5, tag3, sample), None: no tag at that end) and DemuxParams (see
+        sample_sheet) raxtax() demultiplexes every read with; an empty tag list switches the stage off."""
+        arr, n_tags, parr, n_pairs, cp, _keep = _demux_args(tags, pairs, params)
+        check(self._lib.rtx_index_set_tags(self._h, arr, n_tags, parr, n_pairs, C.byref(cp)))
+
+    @property
+    def tags(self) -> int:
+        """How many tags the handle holds (rtx_index_tags)."""
+        n = C.c_uint32()
+        check(self._lib.rtx_index_tags(self._h, C.byref(n)))
+        return int(n.value)
 
     def set_primers(self, patterns) -> None:
         """rtx_index_set_primers: the patterns (TrimPrimer, or (codes, end, max_errors[, window]) tuples; see primer_patterns) raxtax()
@@ -485,6 +548,12 @@ class Index:
         w = np.ascontiguousarray(weights, dtype=np.uint32)
         check(self._lib.rtx_batch_prefetch_weights(self._h, len(w), ptr(w if len(w) else np.zeros(1, np.uint32), u32p)))
 
+    def prefetch_samples(self, samples: np.ndarray):
+        """One sample per query of the batch the NEXT prefetch() / upload() / classify() stages, for the per-sample counters of the open profile
+        (rtx_batch_prefetch_samples); DEMUX_NONE: the query counts in no sample.  A count that does not match that batch is dropped."""
+        s = np.ascontiguousarray(samples, dtype=np.uint32)
+        check(self._lib.rtx_batch_prefetch_samples(self._h, len(s), ptr(s if len(s) else np.zeros(1, np.uint32), u32p)))
+
     def activate(self):
         check(self._lib.rtx_batch_activate(self._h))
 
@@ -532,11 +601,23 @@ class Index:
         return float(ms.value), int(n.value)
 
     # ---- taxon profile (rtx_profile.hip) ----------------------------------------------------
-    def profile_begin(self, cutoff: float = 0.8, skip_exact_matches: bool = False, raw_confidence: bool = False):
+    def profile_begin(self, cutoff: float = 0.8, skip_exact_matches: bool = False, raw_confidence: bool = False, n_samples: Optional[int] = None):
         """Opens the taxon profile of the handle: every batch downloaded from now on is added once (rtx_index_profile_begin).  cutoff: the
-        confidence a level needs to count, in (0, 1]; either flag switches the single-exact-match override off, as in the `.out` text."""
+        confidence a level needs to count, in (0, 1]; either flag switches the single-exact-match override off, as in the `.out` text.
+        n_samples: also count per sample (rtx_index_profile_begin_samples; prefetch_samples() names the sample of every query,
+        profile_read_samples() reads the counters)."""
         flags = (RTX_SKIP_EXACT_MATCHES if skip_exact_matches else 0) | (RTX_RAW_CONFIDENCE if raw_confidence else 0)
-        check(self._lib.rtx_index_profile_begin(self._h, int(round(cutoff * 100)), flags))
+        if n_samples is None:
+            check(self._lib.rtx_index_profile_begin(self._h, int(round(cutoff * 100)), flags))
+        else:
+            check(self._lib.rtx_index_profile_begin_samples(self._h, int(round(cutoff * 100)), flags, int(n_samples)))
+
+    def profile_read_samples(self) -> "SampleProfile":
+        v = _lib.SampleProfileView()
+        check(self._lib.rtx_index_profile_read_samples(self._h, C.byref(v)))
+        nn, ns = int(v.n_nodes), int(v.n_samples)
+        direct = np.ctypeslib.as_array(v.direct, shape=(ns, nn)).copy() if nn else np.zeros((ns, 0), np.uint64)
+        return SampleProfile(int(v.cutoff_hundredths), int(v.flags), direct, np.ctypeslib.as_array(v.totals, shape=(ns, 4)).copy())
 
     def profile_read(self) -> Profile:
         v = _lib.ProfileView()
@@ -930,6 +1011,157 @@ def raxtax_last_trim() -> Tuple[int, int, int, int, float]:
     return int(a.value), int(b.value), int(c.value), int(d.value), float(s.value)
 
 
+_DEMUX = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
+DEMUX_NO_TAG, DEMUX_NONE = _lib.RTX_DEMUX_NO_TAG, _lib.RTX_DEMUX_NONE
+DEMUX_OK, DEMUX_NO_TAG5, DEMUX_NO_TAG3, DEMUX_AMBIGUOUS, DEMUX_UNKNOWN_PAIR = range(5)
+
+
+@dataclass
+class DemuxTag:
+    """One inline tag of the sample demultiplexing (rtx_demux_tag): its codes (1 .. 15, at most 32) and the end it stands at (TRIM_5P /
+    TRIM_3P; a 3' tag as it reads on the read, 5'->3')."""
+    codes: np.ndarray
+    end: int
+
+
+@dataclass
+class DemuxParams:
+    """rtx_demux_params: the substitutions a tag may carry (at most 8) and the bases that may stand in front of it (at most 15)."""
+    max_mismatches: int = 0
+    max_offset: int = 0
+
+
+def _demux_args(tags, pairs, params):
+    """(rtx_demux_tag array, n_tags, rtx_demux_pair array, n_pairs, rtx_demux_params, the arrays they point into) of DemuxTag objects or
+    (codes, end) tuples, (tag5, tag3, sample) triples (None: no tag at that end) and a DemuxParams or (max_mismatches, max_offset)."""
+    ts = [t if isinstance(t, DemuxTag) else DemuxTag(*t) for t in tags]
+    keep = [np.ascontiguousarray(t.codes, dtype=np.uint8) for t in ts]
+    arr = (_lib.DemuxTag * max(len(ts), 1))()
+    for i, (t, k) in enumerate(zip(ts, keep)):
+        arr[i].codes = ptr(k if len(k) else np.zeros(1, np.uint8), u8p)
+        arr[i].len, arr[i].end = len(k), int(t.end)
+    pairs = list(pairs)
+    parr = (_lib.DemuxPair * max(len(pairs), 1))()
+    for i, (a, b, s) in enumerate(pairs):
+        parr[i].tag5 = DEMUX_NO_TAG if a is None else int(a)
+        parr[i].tag3 = DEMUX_NO_TAG if b is None else int(b)
+        parr[i].sample = int(s)
+    p = params if isinstance(params, DemuxParams) else DemuxParams(*(params or ()))
+    return arr, len(ts), parr, len(pairs), _lib.DemuxParams(int(p.max_mismatches), int(p.max_offset)), keep
+
+
+def demux_hit(hit: int, info: int) -> Tuple[int, Optional[int], int, int, Optional[int], int, int]:
+    """(verdict, tag5 or None, mismatches5, offset5, tag3 or None, mismatches3, offset3) of a read's hit and info words."""
+    hit, info = int(hit), int(info)
+    t5, t3 = hit & 0xFFFF, hit >> 16
+    return (info & 0xFF, None if t5 == DEMUX_NO_TAG else t5, (info >> 8) & 0xFF, (info >> 24) & 0xF,
+            None if t3 == DEMUX_NO_TAG else t3, (info >> 16) & 0xFF, (info >> 28) & 0xF)
+
+
+def demux_verdict_names() -> Tuple[str, ...]:
+    """The name of every verdict of the demultiplexing, by its code."""
+    return _lib.RTX_DEMUX_NAMES
+
+
+def demux_read(tags, pairs, params, read: np.ndarray) -> Tuple[int, int, int, int, int]:
+    """rtx_demux_read: (sample, lo, hi, hit, info) of one read on the host, with the function the device kernel calls."""
+    arr, n_tags, parr, n_pairs, cp, _keep = _demux_args(tags, pairs, params)
+    x = np.ascontiguousarray(read, dtype=np.uint8)
+    out = [C.c_uint32() for _ in range(5)]
+    check(_lib.load().rtx_demux_read(C.byref(cp), arr, n_tags, parr, n_pairs, ptr(x if len(x) else np.zeros(1, np.uint8), u8p), len(x),
+                                     *[C.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+class Demux:
+    """The sample-demultiplexing stage on one GPU (rtx_demux): an object of its own beside any Index, one stream, buffers that only grow."""
+
+    def __init__(self, device: int, tags, pairs, params=None):
+        self._lib = _lib.load()
+        self._h = None
+        arr, n_tags, parr, n_pairs, cp, _keep = _demux_args(tags, pairs, params)
+        h = C.c_void_p()
+        check(self._lib.rtx_demux_create(device, arr, n_tags, parr, n_pairs, C.byref(cp), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_demux_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, bases: np.ndarray, base_off: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(sample, lo, hi, hit, info) per read (rtx_demux_run): the read belongs to `sample` (DEMUX_NONE: to none) and keeps [lo, hi);
+        hit and info as demux_hit() takes them apart."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        n = len(base_off) - 1
+        out = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(5)]
+        check(self._lib.rtx_demux_run(self._h, n, ptr(bases if len(bases) else np.zeros(1, np.uint8), u8p), ptr(base_off, u64p),
+                                      *[ptr(o, u32p) for o in out]))
+        return tuple(o[:n] for o in out)
+
+    def kernel_ms(self) -> float:
+        """Milliseconds of the kernel of the last run(), from HIP events (rtx_demux_kernel_time)."""
+        ms = C.c_float()
+        check(self._lib.rtx_demux_kernel_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
+
+def raxtax_last_demux() -> Tuple[int, int, List[int], float]:
+    """rtx_raxtax_last_demux: (queries, assigned to a sample, queries of every verdict by its code, busy seconds of the stage) of the last
+    raxtax() call of this process; all 0 when its handles had no tags set."""
+    q, a, s = C.c_uint64(), C.c_uint64(), C.c_double()
+    reasons = (C.c_uint64 * 5)()
+    check(_lib.load().rtx_raxtax_last_demux(C.byref(q), C.byref(a), reasons, C.byref(s)))
+    return int(q.value), int(a.value), [int(r) for r in reasons], float(s.value)
+
+
+def sample_sheet(text: str, both_orientations: bool = False) -> Tuple[List[DemuxTag], List[Tuple[Optional[int], Optional[int], int]], List[str]]:
+    """(tags, pairs, names) of a sample sheet: tab-separated lines `sample<TAB>fwd_tag<TAB>rev_tag` in IUPAC letters, `#` starts a comment.
+    rev_tag is written as on the oligo (the read ends with its reverse complement); empty or `-`: single-ended.  A sample may own several
+    lines; samples are numbered by first appearance, a tag that several lines share is listed once.  both_orientations=True adds the flipped
+    layout of every line for the same sample: rev_tag at 5' and the reverse complement of fwd_tag at 3'.  ValueError names a malformed line
+    and a (fwd_tag, rev_tag) pair that two lines give."""
+    tags: List[DemuxTag] = []
+    place = {}
+    pairs, names, seen = [], [], {}
+
+    def tag(codes, end):
+        key = (bytes(codes), end)
+        if key not in place:
+            place[key] = len(tags)
+            tags.append(DemuxTag(np.array(codes, np.uint8), end))
+        return place[key]
+
+    def add(t5, t3, sample, line_no):
+        if (t5, t3) in seen:
+            raise ValueError(f"sample sheet line {line_no}: the tag pair is given twice (line {seen[(t5, t3)]})")
+        seen[(t5, t3)] = line_no
+        pairs.append((t5, t3, sample))
+
+    for line_no, line in enumerate(text.splitlines(), 1):
+        line = line.split("#", 1)[0].rstrip()
+        if not line.strip():
+            continue
+        f = [x.strip() for x in line.split("\t")]
+        if len(f) < 2 or len(f) > 3 or not f[0] or not f[1]:
+            raise ValueError(f"sample sheet line {line_no}: expected sample<TAB>fwd_tag<TAB>rev_tag")
+        fwd = encode_iupac(f[1])
+        rev = encode_iupac(f[2]) if len(f) == 3 and f[2] not in ("", "-") else None
+        if f[0] not in names:
+            names.append(f[0])
+        sample = names.index(f[0])
+        add(tag(fwd, TRIM_5P), None if rev is None else tag(revcomp(rev), TRIM_3P), sample, line_no)
+        if both_orientations:
+            if rev is None:   # (a single-ended pair holds only while the list has no tag at the other end: the flipped line would add one)
+                raise ValueError(f"sample sheet line {line_no}: both_orientations needs a rev_tag")
+            add(tag(rev, TRIM_5P), tag(revcomp(fwd), TRIM_3P), sample, line_no)
+    return tags, pairs, names
+
+
 _QUAL = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32)
 QUAL_MAX_READ = _lib.RTX_QUAL_MAX_READ
 QC_BAD_QUALITY, QC_SHORT_FOR_TRUNC_LEN, QC_TOO_SHORT, QC_TOO_LONG, QC_TOO_MANY_N, QC_MAX_EE, QC_MAX_EE_RATE = (1 << b for b in range(7))
@@ -1298,7 +1530,8 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
            trim: Optional[Callable[[str, int, int, int, int], None]] = None,
            quals: Optional[Sequence[np.ndarray]] = None,
            qual: Optional[Callable[[str, int, int, int, int, int], None]] = None,
-           chimera: Optional[Callable[[str, np.void], None]] = None) -> None:
+           chimera: Optional[Callable[[str, np.void], None]] = None,
+           demux: Optional[Callable[[str, int, int, int, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
@@ -1315,7 +1548,10 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     qual_verdict_names); it goes with `align`, `trim` or alone.
     `chimera(label, record)` is called for every query directly after `qual` (rtx_raxtax_multi_ex6; handles built with chimera=ChimeraParams(...),
     else an empty record): the query's CHIMERA_DTYPE record -- its representative's under derep; a flagged read is classified as the empty
-    read.  It goes with `align`, `trim`, `qual` or alone."""
+    read.  It goes with `align`, `trim`, `qual` or alone.
+    `demux(label, raw_len, sample, lo, hi, hit, info)` is called for every query directly before `trim` (rtx_raxtax_multi_ex7; handles built with
+    tags=(tags, pairs, params): the read belongs to `sample` (DEMUX_NONE: to none) and kept [lo, hi) of its raw_len bases; hit and info as
+    demux_hit() takes them apart).  The callbacks behind it then speak of the cut read.  It goes with `align`, `trim`, `qual`, `chimera` or alone."""
     lib = _lib.load()
     lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
                                C.c_uint64, _SENDER, C.c_void_p, C.c_int]
@@ -1328,8 +1564,9 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
         raise ValueError("raxtax: give one of info, hit and align")
     lib.rtx_raxtax_multi_ex5.argtypes = lib.rtx_raxtax_multi_ex4.argtypes + [u8p, _QUAL, C.c_void_p]
     lib.rtx_raxtax_multi_ex6.argtypes = lib.rtx_raxtax_multi_ex5.argtypes + [_CHIM, C.c_void_p]
-    if (trim is not None or qual is not None or chimera is not None) and (info is not None or hit is not None):
-        raise ValueError("raxtax: trim, qual and chimera go with align or alone")
+    lib.rtx_raxtax_multi_ex7.argtypes = lib.rtx_raxtax_multi_ex6.argtypes + [_DEMUX, C.c_void_p]
+    if (trim is not None or qual is not None or chimera is not None or demux is not None) and (info is not None or hit is not None):
+        raise ValueError("raxtax: trim, qual, chimera and demux go with align or alone")
     if quals is None and info is None and hit is None and len(queries) and all(len(q) == 3 for q in queries):
         quals = [q[2] for q in queries]   # (info and hit go through calls that carry no quality strings: triples are then read as pairs)
     if quals is not None and (info is not None or hit is not None):
@@ -1400,7 +1637,24 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
             err.append(e)
             return 1
 
-    if chimera is not None:
+    def cb_demux(_ctx, label, raw_len, sample, lo, hi, hit_word, info_word):
+        try:
+            demux(label.decode(), int(raw_len), int(sample), int(lo), int(hi), int(hit_word), int(info_word))
+            return 0
+        except BaseException as e:  # noqa: BLE001 - forwarded below
+            err.append(e)
+            return 1
+
+    if demux is not None:
+        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+        rc = lib.rtx_raxtax_multi_ex7(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
+                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None,
+                                      _TRIM(cb_trim) if trim is not None else C.cast(None, _TRIM), None,
+                                      ptr(flat_q, u8p) if flat_q is not None else None,
+                                      _QUAL(cb_qual) if qual is not None else C.cast(None, _QUAL), None,
+                                      _CHIM(cb_chim) if chimera is not None else C.cast(None, _CHIM), None, _DEMUX(cb_demux), None)
+    elif chimera is not None:
         arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
         rc = lib.rtx_raxtax_multi_ex6(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                       int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),

@@ -12,6 +12,15 @@
 //   (--identity, implies --hits: two more columns at the end of every line of raxtax.hits -- the semi-global edit distance of the query to that
 //    reference and the identity in percent, two decimals; '-' twice where there is no distance: RTX_OPT_IDENTITY)
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
+//   PREFIX/raxtax.demux (--tags SHEET) and PREFIX/raxtax.samples (with --profile as well): below
+//   (--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]: every read is assigned to a sample by the inline tags at
+//    its ends and loses them, on the device, before anything else sees it (rtx_index_set_tags, rtx_demux.hip).  SHEET: tab-separated lines
+//    sample, fwd_tag, rev_tag in IUPAC letters, '#' starts a comment; rev_tag as on the oligo (the read ends with its reverse complement),
+//    empty or '-': single-ended; a sample may own several lines.  N substitutions per tag (default 0), up to N bases in front of a tag
+//    (default 0); --tags-both-orientations also registers every line flipped (rev_tag at 5', the reverse complement of fwd_tag at 3').
+//    PREFIX/raxtax.demux: a header, then label, sample or '*', verdict, tag5, mm5, off5, tag3, mm3, off3, lo, hi per query in input order
+//    -- the tags by their place in the list the run logs, '-' where an end has none.  A read without a sample has no result lines.  With
+//    --profile the taxon x sample table of read counts goes to PREFIX/raxtax.samples (rtx_sample_table_format); not together with --derep.)
 //   (--primers FWD:REV [--primer-errors PCT] [--primer-window N]: the PCR primers are trimmed off every read on the device before anything else
 //    sees it (rtx_index_set_primers, rtx_trim.hip).  The oligos as ordered, 5'->3', IUPAC codes allowed, either side may be empty, the option
 //    may be given twice: FWD is looked for at the 5' end and the reverse complement of REV at the 3' end -- under --strand both REV at the
@@ -152,7 +161,7 @@ std::string fingerprint(const std::string &path) {
 // (... and --primers with its two settings, as given: trimmed reads are other reads)
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
                             const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string(),
-                            const std::string &chimera = std::string()) {
+                            const std::string &chimera = std::string(), const std::string &tags = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
@@ -162,6 +171,7 @@ std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv
     if (!quality.empty()) ss << ",\n  \"quality\": \"" << quality << "\"";  // (... and the quality filter's settings, as given)
     if (!merge.empty()) ss << ",\n  \"merge\": \"" << merge << "\"";  // (... and --reverse with the merge settings: merged reads are other reads)
     if (!chimera.empty()) ss << ",\n  \"chimera\": \"" << chimera << "\"";  // (... and --chimera with its two settings: flagged reads have no lines)
+    if (!tags.empty()) ss << ",\n  \"tags\": \"" << tags << "\"";  // (... and --tags with its settings: demultiplexed reads are other reads)
     ss << "\n}\n";
     return ss.str();
 }
@@ -200,7 +210,8 @@ uint8_t iupac_code(char ch) {
 }
 
 struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera;
+    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera, demux;
+    const std::vector<std::string> *sample_names = nullptr;  // --tags: the samples of the sheet (raxtax.demux)
     bool want_tsv = false, want_strand = false, want_hits = false;
     const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
 };
@@ -235,6 +246,10 @@ int main(int argc, char **argv) {
     bool chim_on = false;                                              // --chimera: rtx_index_set_chimera on every handle, PREFIX/raxtax.chimera
     rtx_chimera_params chim{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA};  // --chimera-segments, --chimera-mindelta
     std::string chim_opts;                                             // those two as given (empty: none)
+    std::string tags_file;                                             // --tags SHEET: rtx_index_set_tags on every handle, PREFIX/raxtax.demux (and raxtax.samples with --profile)
+    rtx_demux_params tag_params{0u, 0u};                               // --tag-mismatches N, --tag-offset N
+    bool tags_both = false;                                            // --tags-both-orientations
+    std::string tag_opts;                                              // those three as given (empty: none)
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -345,6 +360,17 @@ int main(int argc, char **argv) {
             (a == "--chimera-segments" ? chim.segments : chim.mindelta) = (uint32_t)x;
             chim_opts += (chim_opts.empty() ? "" : " ") + a;
         }
+        else if (a == "--tags") tags_file = val();
+        else if (a == "--tags-both-orientations") { tags_both = true; tag_opts += (tag_opts.empty() ? "" : " ") + a; }
+        else if (a == "--tag-mismatches" || a == "--tag-offset") {
+            const char *v = val();
+            char *end = nullptr;
+            const long x = strtol(v, &end, 10);
+            const long most = a == "--tag-mismatches" ? (long)RTX_DEMUX_MAX_MISMATCHES : (long)RTX_DEMUX_MAX_OFFSET;
+            if (end == v || *end != 0 || x < 0 || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, 0 .. %ld, not '%s'\n", a.c_str(), most, v); return 64; }
+            (a == "--tag-mismatches" ? tag_params.max_mismatches : tag_params.max_offset) = (uint32_t)x;
+            tag_opts += (tag_opts.empty() ? "" : " ") + a;
+        }
         else if (a == "--profile") {
             char *end = nullptr;
             const char *v = val();
@@ -357,7 +383,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -443,6 +469,74 @@ int main(int argc, char **argv) {
         primer_spec += (primer_spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
     }
     if (!primer_spec.empty()) primer_spec += ";errors=" + std::to_string(primer_pct) + ";window=" + std::to_string(primer_window);
+    // --tags: the sample sheet, read and checked here as well
+    struct Tag { std::string name; std::vector<uint8_t> codes; uint32_t end; };
+    std::vector<Tag> tags;
+    std::vector<rtx_demux_pair> tag_pairs;
+    std::vector<std::string> sample_names;
+    std::string tag_spec;
+    const bool tags_on = !tags_file.empty();
+    if (!tag_opts.empty() && !tags_on) { fprintf(stderr, "raxtax-hip: %s sets how reads are assigned to samples and needs --tags SHEET\n", tag_opts.c_str()); return 64; }
+    if (tags_on) {
+        if (derep && profile_cutoff) {
+            fprintf(stderr, "raxtax-hip: --tags cannot go with --derep and --profile together: copies from different samples would be counted as one read\n");
+            return 64;
+        }
+        std::string sheet;
+        if (!slurp(tags_file, sheet)) { fprintf(stderr, "raxtax-hip: --tags: cannot read %s\n", tags_file.c_str()); return 66; }
+        auto rc_of = [](const std::vector<uint8_t> &x) { std::vector<uint8_t> y(x.size() + 1); (void)rtx_revcomp(x.data(), x.size(), y.data()); y.resize(x.size()); return y; };
+        auto strip = [](std::string s) {
+            while (!s.empty() && isspace((unsigned char)s.back())) s.pop_back();
+            size_t a = 0;
+            while (a < s.size() && isspace((unsigned char)s[a])) a++;
+            return s.substr(a);
+        };
+        auto tag_of = [&](const std::string &name, const std::vector<uint8_t> &codes, uint32_t end) -> uint32_t {  // a tag that several lines share is listed once
+            for (size_t k = 0; k < tags.size(); k++)
+                if (tags[k].end == end && tags[k].codes == codes) return (uint32_t)k;
+            tags.push_back({name, codes, end});
+            return (uint32_t)tags.size() - 1u;
+        };
+        std::istringstream lines(sheet);
+        std::string line;
+        for (unsigned line_no = 1; std::getline(lines, line); line_no++) {
+            line = line.substr(0, line.find('#'));
+            if (strip(line).empty()) continue;
+            std::vector<std::string> f;
+            for (size_t a = 0;;) {
+                const size_t t = line.find('\t', a);
+                f.push_back(strip(line.substr(a, t == std::string::npos ? std::string::npos : t - a)));
+                if (t == std::string::npos) break;
+                a = t + 1;
+            }
+            if (f.size() < 2 || f.size() > 3 || f[0].empty() || f[1].empty()) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: expected sample<TAB>fwd_tag<TAB>rev_tag\n", tags_file.c_str(), line_no); return 64; }
+            std::vector<uint8_t> fwd, rev;
+            const bool single = f.size() == 2 || f[2].empty() || f[2] == "-";
+            for (int side = 0; side < (single ? 1 : 2); side++)
+                for (char ch : f[1 + side]) {
+                    const uint8_t c = iupac_code(ch);
+                    if (!c) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: '%c' is no IUPAC code\n", tags_file.c_str(), line_no, ch); return 64; }
+                    (side ? rev : fwd).push_back(c);
+                }
+            size_t s = 0;
+            while (s < sample_names.size() && sample_names[s] != f[0]) s++;
+            if (s == sample_names.size()) sample_names.push_back(f[0]);
+            tag_pairs.push_back({tag_of(f[1], fwd, RTX_TRIM_5P), single ? RTX_DEMUX_NO_TAG : tag_of("revcomp(" + f[2] + ")", rc_of(rev), RTX_TRIM_3P), (uint32_t)s});
+            if (tags_both) {
+                if (single) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: --tags-both-orientations needs a rev_tag\n", tags_file.c_str(), line_no); return 64; }
+                tag_pairs.push_back({tag_of(f[2], rev, RTX_TRIM_5P), tag_of("revcomp(" + f[1] + ")", rc_of(fwd), RTX_TRIM_3P), (uint32_t)s});
+            }
+        }
+        std::vector<rtx_demux_tag> ct;
+        for (const Tag &t : tags) ct.push_back({t.codes.data(), (uint32_t)t.codes.size(), t.end});
+        uint32_t x[5];  // the checks of the library on the list (rtx_demux_create makes them again): one read through the host function
+        if (rtx_demux_read(&tag_params, ct.data(), (uint32_t)ct.size(), tag_pairs.data(), (uint32_t)tag_pairs.size(), nullptr, 0, &x[0], &x[1], &x[2], &x[3], &x[4]) != RTX_OK) {
+            fprintf(stderr, "raxtax-hip: --tags: %s: %s\n", tags_file.c_str(), rtx_last_error());
+            return 64;
+        }
+        tag_spec = fingerprint(tags_file) + ";mismatches=" + std::to_string(tag_params.max_mismatches) + ";offset=" + std::to_string(tag_params.max_offset) + ";both=" + (tags_both ? "1" : "0");
+    }
+    const std::string demux_path = prefix + "/raxtax.demux", samples_path = prefix + "/raxtax.samples";
     const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge", chim_path = prefix + "/raxtax.chimera";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && derep) {
@@ -455,7 +549,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -477,6 +571,7 @@ int main(int argc, char **argv) {
             if (qual_on) purge_incomplete(qc_path, done, true);
             if (merge_on) purge_incomplete(merge_path, done, true);
             if (chim_on) purge_incomplete(chim_path, done, true);
+            if (tags_on) purge_incomplete(demux_path, done, true);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -530,7 +625,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -702,9 +797,17 @@ int main(int argc, char **argv) {
                     for (const Primer &p : primers) pats.push_back({p.codes.data(), (uint32_t)p.codes.size(), p.end, (uint32_t)(p.codes.size() * primer_pct / 100u), primer_window});
                     rcs[k] = rtx_index_set_primers(indices[k], pats.data(), (uint32_t)pats.size());
                 }
+                if (rcs[k] == RTX_OK && tags_on) {
+                    std::vector<rtx_demux_tag> ct;
+                    for (const Tag &t : tags) ct.push_back({t.codes.data(), (uint32_t)t.codes.size(), t.end});
+                    rcs[k] = rtx_index_set_tags(indices[k], ct.data(), (uint32_t)ct.size(), tag_pairs.data(), (uint32_t)tag_pairs.size(), &tag_params);
+                }
                 if (rcs[k] == RTX_OK && qual_on) rcs[k] = rtx_index_set_quality(indices[k], &qual);
                 if (rcs[k] == RTX_OK && chim_on) rcs[k] = rtx_index_set_chimera(indices[k], &chim);
-                if (rcs[k] == RTX_OK && profile_cutoff)
+                if (rcs[k] == RTX_OK && profile_cutoff && tags_on)  // ... with a column of counters per sample (PREFIX/raxtax.samples)
+                    rcs[k] = rtx_index_profile_begin_samples(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u),
+                                                             (uint32_t)sample_names.size());
+                else if (rcs[k] == RTX_OK && profile_cutoff)
                     rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
                 if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
             });
@@ -743,6 +846,17 @@ int main(int argc, char **argv) {
             fprintf(stderr, "[INFO ] --primers: pattern %zu at the %s end: %s, at most %zu error(s)\n", k, primers[k].end == RTX_TRIM_3P ? "3'" : "5'", primers[k].name.c_str(),
                     primers[k].codes.size() * primer_pct / 100u);
     } else if (mode == std::ios::trunc) remove(trim_path.c_str());  // (likewise)
+    if (mode == std::ios::trunc) remove(samples_path.c_str());  // (written at the end of a run with --tags and --profile)
+    if (tags_on) {
+        const bool header = mode == std::ios::trunc || !is_file(demux_path);
+        sink.demux.open(demux_path, mode);
+        sink.sample_names = &sample_names;
+        if (header) sink.demux << "label\tsample\tverdict\ttag5\tmm5\toff5\ttag3\tmm3\toff3\tlo\thi\n";
+        for (size_t k = 0; k < tags.size(); k++)
+            fprintf(stderr, "[INFO ] --tags: tag %zu at the %s end: %s\n", k, tags[k].end == RTX_TRIM_3P ? "3'" : "5'", tags[k].name.c_str());
+        fprintf(stderr, "[INFO ] --tags: %zu samples, %zu pairs, at most %u mismatch(es), at most %u base(s) in front of a tag\n", sample_names.size(), tag_pairs.size(),
+                tag_params.max_mismatches, tag_params.max_offset);
+    } else if (mode == std::ios::trunc) remove(demux_path.c_str());  // (likewise)
     if (qual_on) {
         const bool header = mode == std::ios::trunc || !is_file(qc_path);
         sink.qc.open(qc_path, mode);
@@ -846,6 +960,22 @@ int main(int argc, char **argv) {
         s->chimera << '\n';
         return s->chimera.good() ? 0 : 1;
     };
+    // ... and, under --tags, which sample every query belongs to (also one without result lines: a read that is not assigned)
+    auto assigned = [](void *c, const char *label, uint32_t, uint32_t sample, uint32_t lo, uint32_t hi, uint32_t hit, uint32_t info) -> int {
+        static const char *const verdicts[5] = {"ok", "no_tag5", "no_tag3", "ambiguous", "unknown_pair"};
+        Sink *s = static_cast<Sink *>(c);
+        const uint32_t t5 = hit & 0xFFFFu, t3 = hit >> 16, v = info & 0xFFu;
+        s->demux << label << '\t';
+        if (sample == RTX_DEMUX_NONE || sample >= s->sample_names->size()) s->demux << '*';
+        else s->demux << (*s->sample_names)[sample];
+        s->demux << '\t' << verdicts[v < 5u ? v : 0u] << '\t';
+        if (t5 == RTX_DEMUX_NO_TAG) s->demux << "-\t-\t-\t";
+        else s->demux << t5 << '\t' << ((info >> 8) & 0xFFu) << '\t' << ((info >> 24) & 0xFu) << '\t';
+        if (t3 == RTX_DEMUX_NO_TAG) s->demux << "-\t-\t-\t";
+        else s->demux << t3 << '\t' << ((info >> 16) & 0xFFu) << '\t' << (info >> 28) << '\t';
+        s->demux << lo << '\t' << hi << '\n';
+        return s->demux.good() ? 0 : 1;
+    };
     // (rtx_raxtax_multi_ex4 carries the callback of --identity: without that option the one of --strand both / --hits stands in its shape)
     auto info_as_align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {
         Sink *s = static_cast<Sink *>(c);
@@ -865,6 +995,8 @@ int main(int argc, char **argv) {
     double qual_busy = 0;
     uint64_t chim_total[3] = {0, 0, 0};  // --chimera: queries, reads checked, queries flagged (rtx_raxtax_last_chimera)
     double chim_busy = 0;
+    uint64_t demux_total[7] = {0, 0, 0, 0, 0, 0, 0};  // --tags: queries, assigned, and the queries of every verdict (rtx_raxtax_last_demux)
+    double demux_busy = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
     double derep_busy = 0;
     uint64_t merge_total[6] = {0, 0, 0, 0, 0, 0};  // --reverse: pairs, merged, and not merged for each of the four reasons (RTX_MG_*)
@@ -912,7 +1044,14 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            if (chim_on) {
+            if (tags_on) {
+                const uint8_t *quals = nullptr;
+                if (qual_on) rtx_queries_quals(pz.qs, &quals);
+                rc = rtx_raxtax_multi_ex7(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                          want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
+                                          quals, qual_on ? +filtered : nullptr, &sink, chim_on ? +checked : nullptr, &sink, +assigned, &sink);
+            }
+            else if (chim_on) {
                 const uint8_t *quals = nullptr;
                 if (qual_on) rtx_queries_quals(pz.qs, &quals);
                 rc = rtx_raxtax_multi_ex6(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
@@ -936,6 +1075,12 @@ int main(int argc, char **argv) {
                 rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
                                           both_strands || want_hits ? +info : nullptr, &sink);
             n += nb;
+            if (tags_on) {
+                uint64_t xq[7] = {0, 0, 0, 0, 0, 0, 0};
+                double xb = 0;
+                if (rtx_raxtax_last_demux(&xq[0], &xq[1], xq + 2, &xb) == RTX_OK) { for (int k = 0; k < 7; k++) demux_total[k] += xq[k]; demux_busy += xb; }
+                if (timing) fprintf(stderr, "[TIMING] demultiplexing of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)xq[0], xb);
+            }
             if (!primers.empty()) {
                 uint64_t tq[4] = {0, 0, 0, 0};
                 double tb = 0;
@@ -985,12 +1130,19 @@ int main(int argc, char **argv) {
     if (qual_on) sink.qc.flush();
     if (merge_on) sink.merge.flush();
     if (chim_on) sink.chimera.flush();
+    if (tags_on) sink.demux.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
     if (merge_on) {
         fprintf(stderr, "[INFO ] --reverse: %llu pairs, %llu merged; not merged for bad_quality %llu, too_long %llu, too_short %llu, no_overlap %llu\n", (unsigned long long)merge_total[0],
                 (unsigned long long)merge_total[1], (unsigned long long)merge_total[2], (unsigned long long)merge_total[3], (unsigned long long)merge_total[4], (unsigned long long)merge_total[5]);
         if (timing) t_log << ", \"merge_busy\": " << merge_busy;
+    }
+    if (tags_on) {
+        fprintf(stderr, "[INFO ] --tags: %llu queries, %llu assigned to a sample; not assigned for no_tag5 %llu, no_tag3 %llu, ambiguous %llu, unknown_pair %llu\n",
+                (unsigned long long)demux_total[0], (unsigned long long)demux_total[1], (unsigned long long)demux_total[3], (unsigned long long)demux_total[4],
+                (unsigned long long)demux_total[5], (unsigned long long)demux_total[6]);
+        if (timing) t_log << ", \"demux_busy\": " << demux_busy;
     }
     if (!primers.empty()) {
         fprintf(stderr, "[INFO ] --primers: %llu queries, %llu with a 5' primer, %llu with a 3' primer, %llu left empty\n", (unsigned long long)trim_total[0],
@@ -1047,6 +1199,35 @@ int main(int argc, char **argv) {
         pf << text;
         pf.close();
         if (!pf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", profile_path.c_str()); return 74; }
+    }
+    if (profile_cutoff && tags_on) {  // ... and the taxon x sample table beside it: the per-sample counters summed over the handles
+        std::vector<rtx_sample_profile_view> views(indices.size());
+        std::vector<rtx_sample_profile_view *> ptrs(indices.size());
+        int prc = RTX_OK;
+        for (size_t k = 0; k < indices.size() && prc == RTX_OK; k++) {
+            prc = rtx_index_profile_read_samples(indices[k], &views[k]);
+            ptrs[k] = &views[k];
+        }
+        const size_t nn = prc == RTX_OK ? views[0].n_nodes : 0, ns = sample_names.size();
+        std::vector<uint64_t> direct(ns * nn + 1), totals(ns * 4);
+        if (prc == RTX_OK) prc = rtx_sample_profile_merge(ptrs.data(), (uint32_t)ptrs.size(), direct.data(), totals.data());
+        std::vector<const char *> names;
+        for (const std::string &s : sample_names) names.push_back(s.c_str());
+        std::string text;
+        if (prc == RTX_OK) {
+            const int64_t need = rtx_sample_table_format(tree, (uint32_t)ns, names.data(), direct.data(), totals.data(), profile_cutoff, nullptr, 0);
+            if (need < 0) prc = (int)need;
+            else {
+                text.resize((size_t)need);
+                const int64_t got = rtx_sample_table_format(tree, (uint32_t)ns, names.data(), direct.data(), totals.data(), profile_cutoff, &text[0], text.size());
+                if (got != need) prc = got < 0 ? (int)got : RTX_ERR_STATE;
+            }
+        }
+        if (prc != RTX_OK) { fprintf(stderr, "[ERROR] sample table: %s\n", rtx_last_error()); return 70; }
+        std::ofstream sf(samples_path, std::ios::trunc);
+        sf << text;
+        sf.close();
+        if (!sf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", samples_path.c_str()); return 74; }
     }
     if (clean) {  // Checkpoint::cleanup (io.rs:80-89)
         remove(ckp_json.c_str());

@@ -438,3 +438,96 @@ extern "C" int64_t rtx_profile_format(const rtx_tree *tree, const uint64_t *clad
     memcpy(out, text.data(), text.size());
     return (int64_t)text.size();
 }
+
+// ---- the per-sample counters beside the profile (rtx_index_profile_begin_samples) on the host: the sum over handles and the table
+
+extern "C" int rtx_sample_profile_merge(rtx_sample_profile_view *const *views, uint32_t n, uint64_t *direct, uint64_t *totals) {
+    if (!views || n == 0 || !direct || !totals) { rtx::set_error("rtx_sample_profile_merge: null argument"); return RTX_ERR_INVALID; }
+    for (uint32_t i = 0; i < n; i++) {
+        if (!views[i] || !views[i]->direct || !views[i]->totals) { rtx::set_error("rtx_sample_profile_merge: view %u is null or empty", i); return RTX_ERR_INVALID; }
+        if (views[i]->n_nodes != views[0]->n_nodes || views[i]->n_samples != views[0]->n_samples || views[i]->cutoff_hundredths != views[0]->cutoff_hundredths ||
+            views[i]->flags != views[0]->flags) {
+            rtx::set_error("rtx_sample_profile_merge: view %u differs from view 0 in its nodes, samples, cutoff or flags (%u / %u / %u / %#x against %u / %u / %u / %#x)", i,
+                           views[i]->n_nodes, views[i]->n_samples, views[i]->cutoff_hundredths, views[i]->flags, views[0]->n_nodes, views[0]->n_samples,
+                           views[0]->cutoff_hundredths, views[0]->flags);
+            return RTX_ERR_INVALID;
+        }
+    }
+    const size_t nd = (size_t)views[0]->n_samples * views[0]->n_nodes, nt = (size_t)views[0]->n_samples * 4u;
+    for (size_t k = 0; k < nd; k++) {  // (an output may be the array of one of the views: every entry is read before it is written)
+        uint64_t d = 0;
+        for (uint32_t i = 0; i < n; i++) d += views[i]->direct[k];
+        direct[k] = d;
+    }
+    for (size_t k = 0; k < nt; k++) {
+        uint64_t t = 0;
+        for (uint32_t i = 0; i < n; i++) t += views[i]->totals[k];
+        totals[k] = t;
+    }
+    return RTX_OK;
+}
+
+// The taxon x sample table: the per-sample clade of a node is its direct count plus the clades of its children -- the nodes come breadth
+// first, every child behind its parent, so one pass from the last node to the first adds every clade to its parent's.
+extern "C" int64_t rtx_sample_table_format(const rtx_tree *tree, uint32_t n_samples, const char *const *names, const uint64_t *direct, const uint64_t *totals,
+                                           uint32_t cutoff_hundredths, char *out, uint64_t cap) {
+    if (!tree || !names || !direct || !totals || n_samples == 0) { rtx::set_error("rtx_sample_table_format: null argument"); return RTX_ERR_INVALID; }
+    for (uint32_t s = 0; s < n_samples; s++)
+        if (!names[s]) { rtx::set_error("rtx_sample_table_format: sample %u has no name", s); return RTX_ERR_INVALID; }
+    const rtx::FlatNodes &f = tree->flat;
+    const uint32_t nn = f.size();
+    std::vector<uint64_t> clade(direct, direct + (size_t)n_samples * nn);
+    for (uint32_t v = nn; v-- > 1u;) {
+        if (f.parent[v] >= v) { rtx::set_error("rtx_sample_table_format: node %u comes before its parent", v); return RTX_ERR_INVALID; }
+        for (uint32_t s = 0; s < n_samples; s++) clade[(size_t)s * nn + f.parent[v]] += clade[(size_t)s * nn + v];
+    }
+    std::vector<uint32_t> order;
+    for (uint32_t v = 1; v < nn; v++)
+        for (uint32_t s = 0; s < n_samples; s++)
+            if (clade[(size_t)s * nn + v]) { order.push_back(v); break; }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return f.begin[a] != f.begin[b] ? f.begin[a] < f.begin[b] : f.depth[a] < f.depth[b]; });
+    char num[64];
+    std::string text;
+    snprintf(num, sizeof num, "# cutoff=%u.%02u\tsamples=%u\n", cutoff_hundredths / 100u, cutoff_hundredths % 100u, n_samples);
+    text += num;
+    static const char *const kinds[4] = {"# queries", "# classified", "# unclassified", "# unclassifiable"};
+    for (int k = 0; k < 4; k++) {
+        text += kinds[k];
+        for (uint32_t s = 0; s < n_samples; s++) {
+            snprintf(num, sizeof num, "\t%llu", (unsigned long long)totals[(size_t)s * 4u + k]);
+            text += num;
+        }
+        text += '\n';
+    }
+    text += "depth\ttaxon\tlineage";
+    for (uint32_t s = 0; s < n_samples; s++) { text += '\t'; text += names[s]; }
+    text += '\n';
+    for (uint32_t v : order) {
+        if (f.begin[v] >= tree->lineages.size()) { rtx::set_error("rtx_sample_table_format: node %u begins behind the tree's lineages", v); return RTX_ERR_INVALID; }
+        snprintf(num, sizeof num, "%u\t", f.depth[v]);
+        text += num;
+        const std::string &lin = tree->lineages[f.begin[v]];
+        size_t end = 0, start = 0;  // the first depth levels: [0, end), the last of them [start, end)
+        for (uint32_t d = 0; d < f.depth[v]; d++) {
+            start = d ? end + 1 : 0;
+            const size_t c = start <= lin.size() ? lin.find(',', start) : std::string::npos;
+            end = c == std::string::npos ? lin.size() : c;
+        }
+        start = std::min(start, lin.size());
+        text.append(lin, start, end - start);
+        text += '\t';
+        text.append(lin, 0, end);
+        for (uint32_t s = 0; s < n_samples; s++) {
+            snprintf(num, sizeof num, "\t%llu", (unsigned long long)clade[(size_t)s * nn + v]);
+            text += num;
+        }
+        text += '\n';
+    }
+    if (!out) return (int64_t)text.size();
+    if (cap < text.size()) {  // (as rtx_profile_format answers it)
+        rtx::set_error("rtx_sample_table_format: buffer of %llu bytes, need %llu", (unsigned long long)cap, (unsigned long long)text.size());
+        return -(int64_t)text.size() - (int64_t)RTX_NEED_BASE;
+    }
+    memcpy(out, text.data(), text.size());
+    return (int64_t)text.size();
+}

@@ -83,6 +83,8 @@ struct LastQual { uint64_t queries, passed, truncated, reasons[7]; double busy; 
 LastQual g_qual{0, 0, 0, {0, 0, 0, 0, 0, 0, 0}, 0.0};
 struct LastChim { uint64_t queries, checked, flagged; double busy; };  // rtx_raxtax_last_chimera (under g_timing_mu)
 LastChim g_chim{0, 0, 0, 0.0};
+struct LastDemux { uint64_t queries, assigned, reasons[5]; double busy; };  // rtx_raxtax_last_demux (under g_timing_mu)
+LastDemux g_demux{0, 0, {0, 0, 0, 0, 0}, 0.0};
 
 // (label, out_lines, tsv_lines or null) as C strings: what the C ABI's callback takes; false = the sink is closed
 using RawSender = std::function<bool(const char *, const char *, const char *)>;
@@ -96,6 +98,8 @@ using RawTrim = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, u
 using RawQual = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint64_t, uint32_t)>;
 // (label, record) of every query, directly after its RawQual call (rtx_query_chimera_fn)
 using RawChim = std::function<bool(const char *, const rtx_chimera_rec *)>;
+// (label, length as given, sample, lo, hi, hit, info) of every query, directly before its RawTrim call (rtx_query_demux_fn)
+using RawDemux = std::function<bool(const char *, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t)>;
 
 // Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the
 // one thread that dereplicates, which was most of the stage; the buffers travel between the chunks of a call through a pool, so that
@@ -171,6 +175,14 @@ struct Chunk {
     std::vector<uint32_t> size;        // [nu] copies of every distinct read: its weight in an open profile
     ByteBuf u_bases;
     std::vector<uint64_t> u_off;
+    // sample demultiplexing (rtx_index_set_tags): rtx_demux_run per query of the caller (empty: off), and the reads of the chunk as the stages
+    // behind it are given them -- the caller's arrays (in_off = base_off + q0), or, where a tag was cut or a read was not assigned, the kept
+    // ranges back to back (x_bases / x_quals / x_off, [nq + 1] from 0).  Query i: in_bases + in_off[i], its qualities in_quals + in_off[i].
+    const uint8_t *in_bases = nullptr, *in_quals = nullptr;
+    const uint64_t *in_off = nullptr;
+    std::vector<uint32_t> dx_sample, dx_lo, dx_hi, dx_hit, dx_info;
+    ByteBuf x_bases, x_quals;
+    std::vector<uint64_t> x_off;
     // primer trimming (rtx_index_set_primers): the reads of the chunk as everything downstream sees them -- the caller's arrays, or, where a
     // primer was found in the chunk, the kept ranges back to back (t_bases / t_off, [nq + 1] from 0).  Query i: src_bases + src_off[i].
     const uint8_t *src_bases = nullptr;
@@ -203,6 +215,9 @@ struct Chunk {
 //                   Under RTX_OPT_DEREP it first finds the copies of the chunk on the device (rtx_derep_run, a stream of its own beside
 //                   the handle's) and cuts the chunk down to its distinct reads: the handle classifies those, the format thread and
 //                   the sender go on per query of the caller (Chunk::slot)
+//                   With tags set (rtx_index_set_tags) it first assigns the reads of the chunk to their samples (rtx_demux_run, the same
+//                   kind of stage) and cuts the tags off: every stage below is given the cut reads (Chunk::in_bases), a read that is
+//                   not assigned goes on as the empty read
 //                   With primers set (rtx_index_set_primers) it trims the reads of the chunk before that (rtx_trim_run, the same kind of
 //                   stage): the copies are looked for among the trimmed reads, and everything downstream sees those (Chunk::src_bases)
 //                   With a quality filter set (rtx_index_set_quality) the ranges the primers left are filtered next (rtx_qual_run, again
@@ -215,7 +230,7 @@ struct Chunk {
 int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_t n_queries, const char *const *labels,
         const uint8_t *bases, const uint64_t *base_off, bool skip_exact_matches, bool raw_confidence, uint64_t chunk_size,
         const RawSender &sender, bool tsv, const RawInfo &info = RawInfo(), const RawTrim &trim_cb = RawTrim(), const uint8_t *quals = nullptr,
-        const RawQual &qual_cb = RawQual(), const RawChim &chim_cb = RawChim()) {
+        const RawQual &qual_cb = RawQual(), const RawChim &chim_cb = RawChim(), const RawDemux &demux_cb = RawDemux()) {
     if (!indices || n_dev == 0 || !tree || !base_off || !labels) { rtx::set_error("rtx_raxtax: null argument"); return RTX_ERR_INVALID; }
     for (uint32_t d = 0; d < n_dev; d++) {
         if (!indices[d]) { rtx::set_error("rtx_raxtax: null index handle"); return RTX_ERR_INVALID; }
@@ -277,6 +292,37 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             const int rc = rtx_derep_create(rtx::index_device(indices[d]), &dereps.of[d]);
             if (rc) return rc;
             dereps.own.push_back(dereps.of[d]);
+        }
+    }
+    // Tags (rtx_index_set_tags): the same list on every handle.  One stage object (rtx_demux.hip) per distinct device, as for derep.
+    const rtx::DemuxList &taglist = rtx::index_tags(indices[0]);
+    const bool demux = !taglist.empty();
+    for (uint32_t d = 1; d < n_dev; d++)
+        if (!(rtx::index_tags(indices[d]) == taglist)) { rtx::set_error("rtx_raxtax_multi: the handles disagree on their tags (rtx_index_set_tags)"); return RTX_ERR_INVALID; }
+    const uint32_t prof_samples = rtx::index_profile_samples(indices[0]);
+    for (uint32_t d = 1; d < n_dev; d++)
+        if (rtx::index_profile_samples(indices[d]) != prof_samples) { rtx::set_error("rtx_raxtax_multi: the handles disagree on the samples of their taxon profile (rtx_index_profile_begin_samples)"); return RTX_ERR_INVALID; }
+    if (demux && derep && prof) {
+        rtx::set_error("rtx_raxtax: tags (rtx_index_set_tags) together with RTX_OPT_DEREP and an open taxon profile: copies from different samples would be counted as one read");
+        return RTX_ERR_INVALID;
+    }
+    struct Demuxes {
+        std::vector<rtx_demux *> of;  // per handle; handles of one device share an object
+        std::vector<rtx_demux *> own;
+        ~Demuxes() { for (auto *p : own) rtx_demux_destroy(p); }
+    } demuxes;
+    if (demux) {
+        std::vector<rtx_demux_tag> tags(taglist.codes.size());
+        for (size_t i = 0; i < tags.size(); i++) tags[i] = {taglist.codes[i].data(), (uint32_t)taglist.codes[i].size(), taglist.end[i]};
+        demuxes.of.assign(n_dev, nullptr);
+        for (uint32_t d = 0; d < n_dev; d++) {
+            for (uint32_t e = 0; e < d && !demuxes.of[d]; e++)
+                if (rtx::index_device(indices[e]) == rtx::index_device(indices[d])) demuxes.of[d] = demuxes.of[e];
+            if (demuxes.of[d]) continue;
+            const int rc = rtx_demux_create(rtx::index_device(indices[d]), tags.data(), (uint32_t)tags.size(), taglist.pairs.data(), (uint32_t)taglist.pairs.size(),
+                                            &taglist.params, &demuxes.of[d]);
+            if (rc) return rc;
+            demuxes.own.push_back(demuxes.of[d]);
         }
     }
     // Primers (rtx_index_set_primers): the same list on every handle.  One stage object (rtx_trim.hip) per distinct device, as for derep.
@@ -396,6 +442,9 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         chunks[c].nq = chunks[c].nu = std::min<uint64_t>(chunk_size, n_queries - chunks[c].q0);
         chunks[c].dev_bases = chunks[c].src_bases = bases;
         chunks[c].dev_off = chunks[c].src_off = base_off + chunks[c].q0;
+        chunks[c].in_bases = bases;
+        chunks[c].in_off = base_off + chunks[c].q0;
+        chunks[c].in_quals = quals;
     }
     // busy seconds of the stages (rtx_raxtax_last_timing: which stage bounds an end-to-end run)
     double busy_lookup = 0, busy_send = 0, busy_derep = 0, busy_trim = 0, busy_qual = 0, busy_chim = 0;
@@ -403,6 +452,8 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     uint64_t qual_queries = 0, qual_passed = 0, qual_truncated = 0, qual_reasons[7] = {0, 0, 0, 0, 0, 0, 0};
     uint64_t derep_queries = 0, derep_distinct = 0;
     uint64_t trim_queries = 0, trim_with5 = 0, trim_with3 = 0, trim_emptied = 0;
+    double busy_demux = 0;
+    uint64_t demux_queries = 0, demux_assigned = 0, demux_reasons[5] = {0, 0, 0, 0, 0};
     std::vector<double> busy_device(n_dev, 0.0), busy_format(n_dev, 0.0);
     auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     std::mutex mu;
@@ -434,8 +485,46 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
     std::thread lookup([&] {
         for (uint64_t c = 0; c < n_chunks; c++) {
             Chunk &ch = chunks[c];
-            if (!derep && !trim && !qual && !chim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
+            if (!demux && !derep && !trim && !qual && !chim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }  // Tree.sequences.get runs on the device, inside rtx_classify_batch
             if (c >= ahead && !wait_stage(c - ahead, 2)) return;
+            if (demux) {  // the sample of every read of the chunk, on the device (a stream of its own beside the handle's); then the reads without their tags
+                const double t_x0 = now();
+                for (auto *v : {&ch.dx_sample, &ch.dx_lo, &ch.dx_hi, &ch.dx_hit, &ch.dx_info}) v->resize(ch.nq);
+                int rc = rtx_demux_run(demuxes.of[c % n_dev], ch.nq, bases, base_off + ch.q0, ch.dx_sample.data(), ch.dx_lo.data(), ch.dx_hi.data(), ch.dx_hit.data(),
+                                       ch.dx_info.data());
+                std::vector<uint32_t> keep_hi(ch.nq);  // a read that is not assigned goes on empty
+                bool any = false;
+                uint64_t kept = 0;
+                if (!rc)
+                    for (uint64_t i = 0; i < ch.nq; i++) {
+                        const uint32_t v = ch.dx_info[i] & 0xFFu;
+                        keep_hi[i] = v == RTX_DEMUX_OK ? ch.dx_hi[i] : ch.dx_lo[i];
+                        kept += keep_hi[i] - ch.dx_lo[i];
+                        any = any || ch.dx_lo[i] != 0u || keep_hi[i] != base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
+                        demux_assigned += v == RTX_DEMUX_OK;
+                        if (v < 5u) demux_reasons[v]++;
+                    }
+                if (!rc && any) {  // (a chunk in which nothing was cut goes on as it came, without a copy)
+                    {
+                        std::lock_guard<std::mutex> g(pool_mu);
+                        if (!bases_pool.empty()) { ch.x_bases = std::move(bases_pool.back()); bases_pool.pop_back(); }
+                        if (quals && !bases_pool.empty()) { ch.x_quals = std::move(bases_pool.back()); bases_pool.pop_back(); }
+                    }
+                    if (!ch.x_bases.reserve(kept + 1) || (quals && !ch.x_quals.reserve(kept + 1))) { fail(RTX_ERR_OOM, "no memory for the demultiplexed reads of a chunk"); return; }
+                    ch.x_off.resize(ch.nq + 1);
+                    rc = rtx_trim_apply(ch.nq, bases, base_off + ch.q0, ch.dx_lo.data(), keep_hi.data(), ch.x_bases.p, ch.x_off.data());
+                    if (!rc && quals) rc = rtx_trim_apply(ch.nq, quals, base_off + ch.q0, ch.dx_lo.data(), keep_hi.data(), ch.x_quals.p, ch.x_off.data());
+                    if (!rc) {
+                        ch.dev_bases = ch.src_bases = ch.in_bases = ch.x_bases.p;
+                        ch.dev_off = ch.src_off = ch.in_off = ch.x_off.data();
+                        if (quals) ch.in_quals = ch.x_quals.p;
+                    }
+                }
+                if (rc) { fail(rc, rtx_last_error()); return; }
+                demux_queries += ch.nq;
+                busy_demux += now() - t_x0;
+                if (!derep && !trim && !qual && !chim && dev_lookup[c % n_dev]) { set_stage(c, 1); continue; }
+            }
             if (trim || qual) {  // the primers of the chunk's reads, then their quality, on the device (streams of their own beside the handle's); then the kept ranges
                 const double t_t0 = now();
                 ch.lo.resize(ch.nq);
@@ -443,10 +532,10 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 ch.hit.resize(ch.nq);
                 int rc = RTX_OK;
                 if (trim) {
-                    rc = rtx_trim_run(trims.of[c % n_dev], ch.nq, bases, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.hit.data());
+                    rc = rtx_trim_run(trims.of[c % n_dev], ch.nq, ch.in_bases, ch.in_off, ch.lo.data(), ch.hi.data(), ch.hit.data());
                     if (!rc)
                         for (uint64_t i = 0; i < ch.nq; i++) {
-                            const uint64_t len = base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
+                            const uint64_t len = ch.in_off[i + 1] - ch.in_off[i];
                             const bool f5 = (ch.hit[i] & 0xFFu) != RTX_TRIM_NO_PATTERN, f3 = ((ch.hit[i] >> 16) & 0xFFu) != RTX_TRIM_NO_PATTERN;
                             trim_with5 += f5;
                             trim_with3 += f3;
@@ -455,7 +544,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 } else {
                     for (uint64_t i = 0; i < ch.nq; i++) {
                         ch.lo[i] = 0u;
-                        ch.hi[i] = (uint32_t)std::min<uint64_t>(base_off[ch.q0 + i + 1] - base_off[ch.q0 + i], 0xFFFFFFFFull);
+                        ch.hi[i] = (uint32_t)std::min<uint64_t>(ch.in_off[i + 1] - ch.in_off[i], 0xFFFFFFFFull);
                         ch.hit[i] = RTX_TRIM_NO_PATTERN | RTX_TRIM_NO_PATTERN << 16;
                     }
                 }
@@ -465,7 +554,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     ch.q_verdict.resize(ch.nq);
                     ch.q_ee.resize(ch.nq);
                     ch.keep_hi.resize(ch.nq);
-                    rc = rtx_qual_run(qualstages.of[c % n_dev], ch.nq, bases, quals, base_off + ch.q0, ch.lo.data(), ch.hi.data(), ch.q_hi.data(), ch.q_ee.data(),
+                    rc = rtx_qual_run(qualstages.of[c % n_dev], ch.nq, ch.in_bases, ch.in_quals, ch.in_off, ch.lo.data(), ch.hi.data(), ch.q_hi.data(), ch.q_ee.data(),
                                       ch.q_verdict.data());
                     if (!rc)
                         for (uint64_t i = 0; i < ch.nq; i++) {
@@ -479,7 +568,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 const std::vector<uint32_t> &keep_hi = qual ? ch.keep_hi : ch.hi;
                 bool any = false;
                 if (!rc)
-                    for (uint64_t i = 0; i < ch.nq && !any; i++) any = ch.lo[i] != 0u || keep_hi[i] != base_off[ch.q0 + i + 1] - base_off[ch.q0 + i];
+                    for (uint64_t i = 0; i < ch.nq && !any; i++) any = ch.lo[i] != 0u || keep_hi[i] != ch.in_off[i + 1] - ch.in_off[i];
                 if (!rc && any) {  // (a chunk in which nothing was cut goes on as it came, without a copy)
                     uint64_t kept = 0;
                     for (uint64_t i = 0; i < ch.nq; i++) kept += keep_hi[i] - ch.lo[i];
@@ -489,7 +578,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                     }
                     if (!ch.t_bases.reserve(kept + 1)) { fail(RTX_ERR_OOM, "no memory for the trimmed reads of a chunk"); return; }
                     ch.t_off.resize(ch.nq + 1);
-                    rc = rtx_trim_apply(ch.nq, bases, base_off + ch.q0, ch.lo.data(), keep_hi.data(), ch.t_bases.p, ch.t_off.data());
+                    rc = rtx_trim_apply(ch.nq, ch.in_bases, ch.in_off, ch.lo.data(), keep_hi.data(), ch.t_bases.p, ch.t_off.data());
                     if (!rc) {
                         ch.dev_bases = ch.src_bases = ch.t_bases.p;
                         ch.dev_off = ch.src_off = ch.t_off.data();
@@ -607,6 +696,10 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             const int rc = rtx_batch_prefetch_weights(indices[d], ch.nu, ch.size.data());
             if (rc) return rc;
         }
+        if (prof_samples && demux) {  // the sample of every read for the per-sample counters (no dereplication beside them: nu == nq)
+            const int rc = rtx_batch_prefetch_samples(indices[d], ch.nq, ch.dx_sample.data());
+            if (rc) return rc;
+        }
         if (dev_lookup[d]) return rtx_batch_prefetch(indices[d], ch.nu, ch.dev_bases, ch.dev_off, nullptr, nullptr);
         return rtx_batch_prefetch(indices[d], ch.nu, ch.dev_bases, ch.dev_off, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
     };
@@ -638,6 +731,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
             if (rc == RTX_RETRY_CHUNK) {  // the run-ahead was abandoned (this chunk outgrew a buffer with the next one enqueued already): this chunk on its own
                 rc = dev_text[d] ? rtx_batch_prefetch_labels(indices[d], ch.nq, labels + ch.q0) : RTX_OK;
                 if (!rc && prof && !ch.size.empty()) rc = rtx_batch_prefetch_weights(indices[d], ch.nu, ch.size.data());
+                if (!rc && prof_samples && demux) rc = rtx_batch_prefetch_samples(indices[d], ch.nq, ch.dx_sample.data());
                 if (!rc) rc = dev_lookup[d] ? rtx_batch_upload(indices[d], ch.nu, ch.dev_bases, ch.dev_off, nullptr, nullptr)
                                    : rtx_batch_upload(indices[d], ch.nu, ch.dev_bases, ch.dev_off, ch.exact_ids.empty() ? nullptr : ch.exact_ids.data(), ch.exact_off.data());
                 if (!rc) rc = rtx_batch_run(indices[d], flags);
@@ -846,13 +940,19 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
                 fprintf(stderr, "[WARN ] Exact matches for %s differ above the leafs of the lineage tree!\n", labels[q]);
                 warnings = true;
             }
-            if (trim_cb) {  // every query, also one without a message (an emptied read)
+            if (demux_cb) {  // every query, also one without a message (a read that is not assigned)
                 const uint32_t raw = (uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull);
+                const bool on = !ch.dx_info.empty();
+                if (!demux_cb(labels[q], raw, on ? ch.dx_sample[i] : RTX_DEMUX_NONE, on ? ch.dx_lo[i] : 0u, on ? ch.dx_hi[i] : raw,
+                              on ? ch.dx_hit[i] : (RTX_DEMUX_NO_TAG | RTX_DEMUX_NO_TAG << 16), on ? ch.dx_info[i] : 0u)) { closed = true; break; }
+            }
+            if (trim_cb) {  // every query, also one without a message (an emptied read)
+                const uint32_t raw = (uint32_t)std::min<uint64_t>(ch.in_off[i + 1] - ch.in_off[i], 0xFFFFFFFFull);
                 const bool on = !ch.lo.empty();
                 if (!trim_cb(labels[q], raw, on ? ch.lo[i] : 0u, on ? ch.hi[i] : raw, on ? ch.hit[i] : (RTX_TRIM_NO_PATTERN | RTX_TRIM_NO_PATTERN << 16))) { closed = true; break; }
             }
             if (qual_cb) {  // likewise
-                const uint32_t raw = (uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull);
+                const uint32_t raw = (uint32_t)std::min<uint64_t>(ch.in_off[i + 1] - ch.in_off[i], 0xFFFFFFFFull);
                 const bool ranged = !ch.lo.empty(), on = !ch.q_hi.empty();
                 if (!qual_cb(labels[q], raw, ranged ? ch.lo[i] : 0u, on ? ch.q_hi[i] : (ranged ? ch.hi[i] : raw), on ? ch.q_ee[i] : 0ull, on ? ch.q_verdict[i] : 0u)) { closed = true; break; }
             }
@@ -900,8 +1000,12 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         std::vector<uint64_t>().swap(ch.t_off);
         std::vector<rtx_chimera_rec>().swap(ch.chim);
         std::vector<uint64_t>().swap(ch.c_off);
+        for (auto *v : {&ch.dx_sample, &ch.dx_lo, &ch.dx_hi, &ch.dx_hit, &ch.dx_info}) std::vector<uint32_t>().swap(*v);
+        std::vector<uint64_t>().swap(ch.x_off);
         {
             std::lock_guard<std::mutex> g(pool_mu);
+            if (ch.x_bases.p) bases_pool.push_back(std::move(ch.x_bases));
+            if (ch.x_quals.p) bases_pool.push_back(std::move(ch.x_quals));
             if (ch.u_bases.p) bases_pool.push_back(std::move(ch.u_bases));
             if (ch.t_bases.p) bases_pool.push_back(std::move(ch.t_bases));
             if (ch.c_bases.p) bases_pool.push_back(std::move(ch.c_bases));
@@ -926,6 +1030,7 @@ int run(rtx_index *const *indices, uint32_t n_dev, const rtx_tree *tree, uint64_
         g_derep = {derep_queries, derep_distinct, busy_derep};
         g_trim = {trim_queries, trim_with5, trim_with3, trim_emptied, busy_trim};
         g_chim = {chim_queries, chim_checked, chim_flagged, busy_chim};
+        g_demux = {demux_queries, demux_assigned, {demux_reasons[0], demux_reasons[1], demux_reasons[2], demux_reasons[3], demux_reasons[4]}, busy_demux};
         g_qual = {qual_queries, qual_passed, qual_truncated, {qual_reasons[0], qual_reasons[1], qual_reasons[2], qual_reasons[3], qual_reasons[4], qual_reasons[5], qual_reasons[6]}, busy_qual};
     }
     if (failed != RTX_OK) { rtx::set_error("%s", failed_msg.c_str()); return failed; }
@@ -1037,6 +1142,17 @@ extern "C" int rtx_raxtax_multi_ex6(rtx_index *const *indices, uint32_t n_indice
                                     int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                                     rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
                                     rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx) {
+    return rtx_raxtax_multi_ex7(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender,
+                                sender_ctx, tsv, align, align_ctx, trim, trim_ctx, quals, qual, qual_ctx, chimera, chimera_ctx, nullptr, nullptr);
+}
+
+// ... and the sample of every query (rtx_index_set_tags)
+extern "C" int rtx_raxtax_multi_ex7(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                                    rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx, rtx_query_demux_fn demux,
+                                    void *demux_ctx) {
     if (!sender) { rtx::set_error("rtx_raxtax_multi: null sender"); return RTX_ERR_INVALID; }
     RawSender s = [&](const char *label, const char *out, const char *t) { return sender(sender_ctx, label, out, t) == 0; };
     RawInfo fi;
@@ -1050,8 +1166,22 @@ extern "C" int rtx_raxtax_multi_ex6(rtx_index *const *indices, uint32_t n_indice
     if (qual) fq = [&](const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) { return qual(qual_ctx, label, raw_len, lo, hi, ee, verdict) == 0; };
     RawChim fc;
     if (chimera) fc = [&](const char *label, const rtx_chimera_rec *rec) { return chimera(chimera_ctx, label, rec) == 0; };
+    RawDemux fx;
+    if (demux)
+        fx = [&](const char *label, uint32_t raw_len, uint32_t sample, uint32_t lo, uint32_t hi, uint32_t hit, uint32_t info) {
+            return demux(demux_ctx, label, raw_len, sample, lo, hi, hit, info) == 0;
+        };
     return run(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, s,
-               tsv != 0, fi, ft, quals, fq, fc);
+               tsv != 0, fi, ft, quals, fq, fc, fx);
+}
+
+extern "C" int rtx_raxtax_last_demux(uint64_t *queries, uint64_t *assigned, uint64_t reasons[5], double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_demux.queries;
+    if (assigned) *assigned = g_demux.assigned;
+    if (reasons) for (int v = 0; v < 5; v++) reasons[v] = g_demux.reasons[v];
+    if (busy_seconds) *busy_seconds = g_demux.busy;
+    return RTX_OK;
 }
 
 extern "C" int rtx_raxtax_last_timing(double busy[4], uint64_t *n_chunks) {

@@ -1343,6 +1343,8 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
     in.labels_pending = in.has_labels = false;
     const bool with_weights = in.weights_pending && in.n_weights == n_queries;  // ... and so do its weights (rtx_batch_prefetch_weights)
     in.weights_pending = in.has_weights = false;
+    const bool with_samples = in.samples_pending && in.n_samples == n_queries;  // ... and its samples (rtx_batch_prefetch_samples)
+    in.samples_pending = in.has_samples = false;
     if (n_queries == 0 || !base_off || (!bases && base_off[n_queries])) {
         set_error("rtx_batch_upload: invalid argument");
         return RTX_ERR_INVALID;
@@ -1414,6 +1416,7 @@ int rtx_batch_prefetch(rtx_index *ix, uint64_t n_queries, const uint8_t *bases, 
     in.has_exact = exact_off != nullptr;
     in.has_labels = with_labels;
     in.has_weights = with_weights;
+    in.has_samples = with_samples;
     in.staged = true;
     return RTX_OK;
 }

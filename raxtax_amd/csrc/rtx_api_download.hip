@@ -144,6 +144,16 @@ int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r) {
     }
     launch_profile(s, p);
     RTX_HIP(hipGetLastError());
+    if (pf.n_samples && in.has_samples && in.n_samples == r.n_user) {  // the per-sample counters beside it (nothing staged: the batch counts in no sample)
+        SampleProfileParams sp{};
+        sp.p = p;
+        sp.sample = in.d_samples.p;
+        sp.n_samples = pf.n_samples;
+        sp.direct = pf.d_by_sample.p;
+        sp.totals = sp.direct + (size_t)pf.n_samples * p.n_nodes;
+        launch_profile_samples(s, sp);
+        RTX_HIP(hipGetLastError());
+    }
     if (timed) RTX_HIP(hipEventRecord(pf.ev[1], s));
     RTX_HIP(hipStreamSynchronize(s));
     if (timed) {
@@ -443,7 +453,8 @@ int rtx_batch_nearest(rtx_index *ix, const uint32_t **nearest, const uint32_t **
 }
 
 // ---- the taxon profile of the handle (rtx_profile.hip): open between begin and end; every accepted download adds its batch once
-int rtx_index_profile_begin(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t flags) {
+// n_samples != 0: with the per-sample counters (rtx_index_profile_begin_samples)
+static int profile_begin(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t flags, uint32_t n_samples) {
     int rc = bind(ix);
     if (rc) return rc;
     rtx_index::Profile &pf = ix->prof;
@@ -453,14 +464,23 @@ int rtx_index_profile_begin(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t 
     if (pf.on) { set_error("rtx_index_profile_begin: a profile is open already (rtx_index_profile_end)"); return RTX_ERR_STATE; }
     const FlatNodes &f = ix->nodes;
     const uint32_t nn = f.size();
+    if ((uint64_t)n_samples * nn > RTX_PROFILE_MAX_SAMPLE_COUNTERS) {
+        set_error("rtx_index_profile_begin_samples: %u samples x %u nodes are more than RTX_PROFILE_MAX_SAMPLE_COUNTERS = %llu counters", n_samples, nn,
+                  (unsigned long long)RTX_PROFILE_MAX_SAMPLE_COUNTERS);
+        return RTX_ERR_INVALID;
+    }
+    const size_t by_sample = (size_t)n_samples * ((size_t)nn + 4u);
     // the Taxon node of every reference: the nodes come breadth first, so the deepest Taxon node over a reference is the last one written
     std::vector<uint32_t> leaf(ix->n_total ? ix->n_total : 1u, kNoNode);
     for (uint32_t v = 0; v < nn; v++)
         if (f.type[v] == kTaxon) std::fill(leaf.begin() + f.begin[v], leaf.begin() + f.end[v], v);
-    if ((rc = pf.d_parent.alloc(nn)) || (rc = pf.d_ref_leaf.alloc(leaf.size())) || (rc = pf.d_acc.alloc(3u * (size_t)nn + 4u))) {
-        pf.d_parent.release(); pf.d_ref_leaf.release(); pf.d_acc.release();
+    if ((rc = pf.d_parent.alloc(nn)) || (rc = pf.d_ref_leaf.alloc(leaf.size())) || (rc = pf.d_acc.alloc(3u * (size_t)nn + 4u)) ||
+        (by_sample && (rc = pf.d_by_sample.alloc(by_sample)))) {
+        pf.d_parent.release(); pf.d_ref_leaf.release(); pf.d_acc.release(); pf.d_by_sample.release();
         return rc;
     }
+    if (by_sample) RTX_HIP(hipMemset(pf.d_by_sample.p, 0, by_sample * 8));
+    pf.n_samples = n_samples;
     RTX_HIP(hipMemcpy(pf.d_parent.p, f.parent.data(), (size_t)nn * 4, hipMemcpyHostToDevice));
     RTX_HIP(hipMemcpy(pf.d_ref_leaf.p, leaf.data(), leaf.size() * 4, hipMemcpyHostToDevice));
     RTX_HIP(hipMemset(pf.d_acc.p, 0, (3u * (size_t)nn + 4u) * 8));
@@ -469,6 +489,31 @@ int rtx_index_profile_begin(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t 
     pf.ms = 0.f;
     pf.launches = 0;
     pf.on = true;
+    return RTX_OK;
+}
+
+int rtx_index_profile_begin(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t flags) { return profile_begin(ix, cutoff_hundredths, flags, 0u); }
+
+int rtx_index_profile_begin_samples(rtx_index *ix, uint32_t cutoff_hundredths, uint32_t flags, uint32_t n_samples) {
+    if (n_samples == 0) { set_error("rtx_index_profile_begin_samples: no samples"); return RTX_ERR_INVALID; }
+    return profile_begin(ix, cutoff_hundredths, flags, n_samples);
+}
+
+int rtx_index_profile_read_samples(rtx_index *ix, rtx_sample_profile_view *out) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (!out) { set_error("rtx_index_profile_read_samples: null argument"); return RTX_ERR_INVALID; }
+    rtx_index::Profile &pf = ix->prof;
+    if (!pf.on || !pf.n_samples) { set_error("rtx_index_profile_read_samples: no profile with samples is open (rtx_index_profile_begin_samples)"); return RTX_ERR_STATE; }
+    const uint32_t nn = ix->nodes.size();
+    pf.h_by_sample.resize((size_t)pf.n_samples * ((size_t)nn + 4u));
+    RTX_HIP(hipMemcpy(pf.h_by_sample.data(), pf.d_by_sample.p, pf.h_by_sample.size() * 8, hipMemcpyDeviceToHost));
+    out->n_nodes = nn;
+    out->n_samples = pf.n_samples;
+    out->cutoff_hundredths = pf.cutoff;
+    out->flags = pf.flags;
+    out->direct = pf.h_by_sample.data();
+    out->totals = out->direct + (size_t)pf.n_samples * nn;
     return RTX_OK;
 }
 
@@ -498,6 +543,7 @@ int rtx_index_profile_reset(rtx_index *ix) {
     rtx_index::Profile &pf = ix->prof;
     if (!pf.on) { set_error("rtx_index_profile_reset: no profile is open"); return RTX_ERR_STATE; }
     RTX_HIP(hipMemset(pf.d_acc.p, 0, (3u * (size_t)ix->nodes.size() + 4u) * 8));
+    if (pf.n_samples) RTX_HIP(hipMemset(pf.d_by_sample.p, 0, (size_t)pf.n_samples * ((size_t)ix->nodes.size() + 4u) * 8));
     pf.ms = 0.f;
     pf.launches = 0;
     return RTX_OK;
@@ -509,8 +555,10 @@ int rtx_index_profile_end(rtx_index *ix) {
     rtx_index::Profile &pf = ix->prof;
     if (!pf.on) { set_error("rtx_index_profile_end: no profile is open"); return RTX_ERR_STATE; }
     pf.on = false;
-    pf.d_acc.release(); pf.d_parent.release(); pf.d_ref_leaf.release();
+    pf.d_acc.release(); pf.d_parent.release(); pf.d_ref_leaf.release(); pf.d_by_sample.release();
+    pf.n_samples = 0;
     std::vector<uint64_t>().swap(pf.h_acc);
+    std::vector<uint64_t>().swap(pf.h_by_sample);
     for (auto &e : pf.ev) {
         if (e) (void)hipEventDestroy(e);
         e = nullptr;
@@ -546,6 +594,34 @@ int rtx_batch_prefetch_weights(rtx_index *ix, uint64_t n_queries, const uint32_t
     in.recorded = true;
     in.weights_pending = true;
     in.n_weights = n_queries;
+    return RTX_OK;
+}
+
+// One sample per query for the batch that the NEXT rtx_batch_prefetch / rtx_batch_upload stages, for the per-sample counters of the open
+// profile (rtx_index_profile_begin_samples): the path and the rules of the weights above.
+int rtx_batch_prefetch_samples(rtx_index *ix, uint64_t n_queries, const uint32_t *sample) {
+    int rc = bind(ix);
+    if (rc) return rc;
+    if (!sample && n_queries) { set_error("rtx_batch_prefetch_samples: null samples"); return RTX_ERR_INVALID; }
+    const uint32_t n_samples = ix->prof.on ? ix->prof.n_samples : 0u;
+    if (!n_samples) { set_error("rtx_batch_prefetch_samples: no profile with samples is open (rtx_index_profile_begin_samples)"); return RTX_ERR_STATE; }
+    for (uint64_t q = 0; q < n_queries; q++)
+        if (sample[q] != RTX_DEMUX_NONE && sample[q] >= n_samples) {
+            set_error("rtx_batch_prefetch_samples: query %llu has sample %u of %u", (unsigned long long)q, sample[q], n_samples);
+            return RTX_ERR_INVALID;
+        }
+    rtx_index::Inputs &in = ix->in[ix->cur_in ^ 1u];
+    if (!ix->h2d_stream) RTX_HIP(hipStreamCreateWithFlags(&ix->h2d_stream, hipStreamNonBlocking));
+    if (!in.ready) RTX_HIP(hipEventCreateWithFlags(&in.ready, hipEventDisableTiming));
+    if (in.recorded) RTX_HIP(hipEventSynchronize(in.ready));  // the last transfer out of this set's pinned buffers
+    if (ix->ev_activated) RTX_HIP(hipStreamWaitEvent(ix->h2d_stream, ix->ev_activated, 0));
+    if ((rc = in.h_samples.resize(n_queries + 1)) || (rc = in.d_samples.alloc(n_queries + 1))) return rc;
+    if (n_queries) std::memcpy(in.h_samples.data(), sample, n_queries * 4);
+    if (n_queries) RTX_HIP(hipMemcpyAsync(in.d_samples.p, in.h_samples.data(), n_queries * 4, hipMemcpyHostToDevice, ix->h2d_stream));
+    RTX_HIP(hipEventRecord(in.ready, ix->h2d_stream));
+    in.recorded = true;
+    in.samples_pending = true;
+    in.n_samples = n_queries;
     return RTX_OK;
 }
 

@@ -822,6 +822,42 @@ void emul_trim_read(uint32_t n_pat, const uint8_t *codes, const uint32_t *code_o
     trim_read(pat.data(), n5, n3, loader(row5), loader(row3), len, *lo, *hi, *hit);
 }
 
+// Sample demultiplexing as demux_kernel (rtx_demux.hip) runs it, with the functions the kernel calls: the tags packed (demux_tag_init), the
+// dense pair table, the ends of every read staged into rows (trim_stage_row) and one read against them (demux_read).  codes / code_off /
+// end: the tags as given; pairs: n_pairs x (tag5, tag3, sample) with 0xFFFF for no tag, every one valid (the library checks, not this);
+// bases / base_off: n reads; out: [5][n] sample, lo, hi, hit, info.
+void emul_demux_reads(uint32_t n_tags, const uint8_t *codes, const uint32_t *code_off, const uint32_t *end, uint32_t n_pairs, const uint32_t *pairs,
+                      uint32_t max_mismatches, uint32_t max_offset, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *out) {
+    std::vector<DemuxTag> tags;
+    std::vector<uint32_t> rank(n_tags);
+    uint32_t cnt[2] = {0u, 0u};
+    for (uint32_t e = 0; e < 2; e++)
+        for (uint32_t i = 0; i < n_tags; i++) {
+            if (end[i] != e) continue;
+            DemuxTag t;
+            demux_tag_init(t, codes + code_off[i], code_off[i + 1] - code_off[i], e == 1u, i);
+            tags.push_back(t);
+            rank[i] = cnt[e]++;
+        }
+    const uint32_t n5 = cnt[0], n3 = cnt[1];
+    std::vector<uint32_t> table(demux_table_size(n5, n3), kDemuxNone);
+    for (uint32_t i = 0; i < n_pairs; i++) {
+        const uint32_t a = pairs[3 * i], b = pairs[3 * i + 1];
+        table[demux_table_slot(n3, a == kDemuxNoTag ? n5 : rank[a], b == kDemuxNoTag ? n3 : rank[b])] = pairs[3 * i + 2];
+    }
+    const uint32_t w = demux_window(max_offset), stride = trim_row_stride(w);
+    auto pair = [&](uint32_t i5, uint32_t i3) { return table[demux_table_slot(n3, i5, i3)]; };
+    for (uint64_t q = 0; q < n; q++) {
+        const uint8_t *x = bases + base_off[q];
+        const uint64_t len = base_off[q + 1] - base_off[q];
+        uint8_t row5[32], row3[32];
+        trim_stage_row(x, len, w, false, row5);
+        trim_stage_row(x, len, w, true, row3);
+        demux_read(tags.data(), n5, n3, pair, max_mismatches, max_offset, demux_window_of(row5, stride), demux_window_of(row3, stride), (uint32_t)len,
+                   out[q], out[n + q], out[2 * n + q], out[3 * n + q], out[4 * n + q]);
+    }
+}
+
 // The quality filter as qual_kernel (rtx_qual.hip) runs it, with the functions the kernel calls, in the kernel's geometry: steps of 16 pieces
 // of 16 bytes, the piece sums of a step first, then the scan over them, then every piece's stop with what lies in front of it, the first of
 // the step, and the sums read from the piece that holds it.  cfg: the parameters as integers (base, trunc_len, trunc_qual, min_len,

@@ -269,6 +269,11 @@ struct rtx_index {
         PinBuf<uint32_t> h_weights;
         uint64_t n_weights = 0;
         bool weights_pending = false, has_weights = false;
+        // ... and its samples for the per-sample counters (rtx_batch_prefetch_samples: the same path)
+        DevBuf<uint32_t> d_samples;
+        PinBuf<uint32_t> h_samples;
+        uint64_t n_samples = 0;
+        bool samples_pending = false, has_samples = false;
         hipEvent_t ready = nullptr;        // its transfer has arrived
     } in[2];
     uint32_t cur_in = 0;               // the set of the current (activated) batch
@@ -469,6 +474,7 @@ struct rtx_index {
     bool quality_on = false;
     rtx_chimera_params chimera{};    // rtx_index_set_chimera: the chimera check its callers run in front of it (rtx_chimera.hip); the handle itself never reads it
     bool chimera_on = false;
+    rtx::DemuxList tags;  // rtx_index_set_tags: rtx_raxtax* assign every read to a sample and cut its tags first (rtx_demux.hip); the handle itself never reads them
     std::vector<rtx::TrimPrimer> primers;  // rtx_index_set_primers: rtx_raxtax* trim every read with them first (rtx_trim.hip); the handle itself never reads them
     DevBuf<char> d_lin_bytes, d_text;
     DevBuf<uint64_t> d_lin_off;
@@ -503,6 +509,10 @@ struct rtx_index {
         // hits a table that stays in L2 (2 MB at 500 000 nodes); the Taxon node of every reference for the override
         DevBuf<uint32_t> d_parent, d_ref_leaf;
         std::vector<uint64_t> h_acc;           // rtx_index_profile_read: valid until the next read, reset or end
+        // the per-sample counters (rtx_index_profile_begin_samples; n_samples == 0: none): direct [n_samples][n_nodes] | totals [n_samples][4]
+        uint32_t n_samples = 0;
+        DevBuf<unsigned long long> d_by_sample;
+        std::vector<uint64_t> h_by_sample;     // rtx_index_profile_read_samples
         float ms = 0.f;                        // RTX_OPT_STAGE_TIMING: the kernel's time and launches since begin or reset
         uint32_t launches = 0;
         hipEvent_t ev[2] = {nullptr, nullptr};

@@ -43,6 +43,22 @@ struct TrimPrimer {
 };
 int trim_check_patterns(const char *who, const rtx_trim_pattern *pats, uint32_t n);  // RTX_OK, or RTX_ERR_INVALID with the pattern named
 const std::vector<TrimPrimer> &index_primers(const rtx_index *index);
+// sample demultiplexing (host_demux.cpp / rtx_demux.hip): a tag list with its codes owned, as a handle holds it (rtx_index_set_tags; no tags: off)
+struct DemuxList {
+    std::vector<std::vector<uint8_t>> codes;  // per tag
+    std::vector<uint32_t> end;
+    std::vector<rtx_demux_pair> pairs;
+    rtx_demux_params params{0u, 0u};
+    bool empty() const { return codes.empty(); }
+    bool operator==(const DemuxList &o) const {
+        if (codes != o.codes || end != o.end || pairs.size() != o.pairs.size() || params.max_mismatches != o.params.max_mismatches || params.max_offset != o.params.max_offset) return false;
+        for (size_t i = 0; i < pairs.size(); i++)
+            if (pairs[i].tag5 != o.pairs[i].tag5 || pairs[i].tag3 != o.pairs[i].tag3 || pairs[i].sample != o.pairs[i].sample) return false;
+        return true;
+    }
+};
+const DemuxList &index_tags(const rtx_index *index);
+uint32_t index_profile_samples(const rtx_index *index);  // the samples of the open profile (rtx_index_profile_begin_samples), 0: none
 // quality filter (host_qual.cpp / rtx_qual.hip): the checks of a parameter struct (RTX_OK, or RTX_ERR_INVALID with the field named), whether it
 // filters anything, the error table (computed once), and the setting a handle holds (rtx_index_set_quality; false: off)
 int qual_check_params(const char *who, const rtx_qual_params *p);

@@ -170,6 +170,15 @@ struct ProfileParams {
     const uint32_t *weight; // [n_user] how many reads query q stands for (rtx_batch_prefetch_weights); null: 1 each
 };
 void launch_profile(hipStream_t s, const ProfileParams &p);
+// ... and what they add to the per-sample counters beside it (rtx_index_profile_begin_samples): the same lanes, the same step
+struct SampleProfileParams {
+    ProfileParams p;         // as launch_profile takes it (clade, direct, conf_sum and totals are not touched)
+    const uint32_t *sample;  // [n_user] the sample of query q (rtx_batch_prefetch_samples); RTX_DEMUX_NONE, like anything >= n_samples: none
+    uint32_t n_samples;
+    unsigned long long *direct;  // [n_samples][n_nodes]
+    unsigned long long *totals;  // [n_samples][4]
+};
+void launch_profile_samples(hipStream_t s, const SampleProfileParams &p);
 
 // rtx_identity.hip: the semi-global edit distance of every query of the caller to its nearest reference (RTX_OPT_IDENTITY), once per run
 // behind strand_select_kernel

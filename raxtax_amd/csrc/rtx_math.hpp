@@ -254,6 +254,101 @@ RTX_HD void trim_read(const TrimPattern *pat, uint32_t n5, uint32_t n3, const L5
 }
 
 // ---------------------------------------------------------------------------
+// Sample demultiplexing (demux_kernel, rtx_demux.hip; rtx_demux_read on the host; emul_demux_reads on x86): which inline tag stands at
+// each end of a read, by Hamming distance over the admissible offsets -- include/raxtax_hip.h has the semantics.
+// A tag is at most 32 codes, packed like the text: code j in nibble j of two 64-bit words, the nibbles behind the tag zero (they match
+// nothing, which is the length mask: no second mask is carried).  The text arrives as trim_stage_row packs it: the first (3': the last,
+// reversed) max_offset + 32 bases of the read, a byte above 15 as 0, what lies behind them zero -- 47 nibbles at the most, three words.
+// Placing a tag at offset s is a shift of the window by 4 s bits; the matching positions are the nibbles where tag AND window is not zero,
+// folded to one bit each and counted: d = m - popcount.
+// ---------------------------------------------------------------------------
+struct DemuxTag {        // one tag as the kernel reads it, by a wave-uniform index (scalar loads)
+    uint64_t w[2];       // code j AS IT IS SEARCHED (a 3' tag reversed) in nibble j
+    uint32_t m, index;   // codes; its place in the caller's list (what the hit word names)
+};
+struct DemuxWindow { uint64_t w[3]; };
+constexpr uint32_t kDemuxNoTag = 0xFFFFu, kDemuxNone = 0xFFFFFFFFu, kDemuxMaxMismatches = 8u;
+enum : uint32_t { kDemuxOk = 0u, kDemuxNoTag5 = 1u, kDemuxNoTag3 = 2u, kDemuxAmbiguous = 3u, kDemuxUnknownPair = 4u };
+RTX_HD uint32_t demux_window(uint32_t max_offset) { return max_offset + 32u; }  // bases of an end that are staged
+RTX_HD void demux_tag_init(DemuxTag &t, const uint8_t *codes, uint32_t m, bool reversed, uint32_t index) {
+    t.w[0] = t.w[1] = 0ull;
+    for (uint32_t j = 0; j < m; j++) t.w[j >> 4] |= (uint64_t)identity_code(codes[reversed ? m - 1u - j : j]) << ((j & 15u) * 4u);
+    t.m = m;
+    t.index = index;
+}
+// the window of a staged row of `stride` bytes (trim_row_stride: 16 or 32), word by word
+RTX_HD DemuxWindow demux_window_of(const uint8_t *row, uint32_t stride) {
+    DemuxWindow x{{0ull, 0ull, 0ull}};
+    for (uint32_t b = 0; b < (stride < 24u ? stride : 24u); b++) x.w[b >> 3] |= (uint64_t)row[b] << ((b & 7u) * 8u);
+    return x;
+}
+// bit 4 j: nibble j of x is not zero
+RTX_HD uint64_t demux_fold(uint64_t x) {
+    x |= x >> 1;
+    x |= x >> 2;
+    return x & 0x1111111111111111ull;
+}
+// One end: tags[0 .. n) against the window at the offsets 0 .. max_offset (both loops uniform over a wave; a placement with s + m > len
+// sits out).  best = the least distance (~0: no placement), tag / off = the first (offset, tag) that reaches it -- when one tag alone
+// reaches it, that tag at its least offset -- and two = another tag reaches it as well.
+RTX_HD void demux_end(const DemuxTag *tags, uint32_t n, const DemuxWindow &x, uint32_t len, uint32_t max_offset, uint32_t &best,
+                      uint32_t &tag, uint32_t &off, bool &two) {
+    best = ~0u;
+    tag = 0u;
+    off = 0u;
+    two = false;
+    uint64_t x0 = x.w[0], x1 = x.w[1], x2 = x.w[2];
+    for (uint32_t s = 0; s <= max_offset; s++) {
+        for (uint32_t i = 0; i < n; i++) {
+            const DemuxTag &t = tags[i];
+            const uint32_t hits = (uint32_t)__builtin_popcountll(demux_fold(t.w[0] & x0)) + (uint32_t)__builtin_popcountll(demux_fold(t.w[1] & x1));
+            const uint32_t d = s + t.m <= len ? t.m - hits : ~0u;  // (selects, no branches: the lanes of a wave differ here all the time)
+            const bool less = d < best;
+            two = !less && (two || (d == best && i != tag));  // (while best is ~0 this may hold: `two` counts only once something is found)
+            tag = less ? i : tag;
+            off = less ? s : off;
+            best = less ? d : best;
+        }
+        x0 = (x0 >> 4) | (x1 << 60);
+        x1 = (x1 >> 4) | (x2 << 60);
+        x2 >>= 4;
+    }
+}
+// One read against the tags of both ends (tags[0 .. n5): 5', tags[n5 .. n5 + n3): 3', each end in the order of the caller's list).
+// pair(i5, i3): the sample of the pair of the i5-th 5' tag (n5: none) and the i3-th 3' tag (n3: none), kDemuxNone when the table has no
+// such pair.  An end has a tag when its least distance is at most max_mismatches and one tag alone reaches it.
+template <class P>
+RTX_HD void demux_read(const DemuxTag *tags, uint32_t n5, uint32_t n3, const P &pair, uint32_t max_mismatches, uint32_t max_offset,
+                       const DemuxWindow &x5, const DemuxWindow &x3, uint32_t len, uint32_t &sample, uint32_t &lo, uint32_t &hi, uint32_t &hit,
+                       uint32_t &info) {
+    uint32_t d5 = ~0u, t5 = 0u, s5 = 0u, d3 = ~0u, t3 = 0u, s3 = 0u;
+    bool two5 = false, two3 = false;
+    if (n5) demux_end(tags, n5, x5, len, max_offset, d5, t5, s5, two5);
+    if (n3) demux_end(tags + n5, n3, x3, len, max_offset, d3, t3, s3, two3);
+    const bool found5 = d5 <= max_mismatches, found3 = d3 <= max_mismatches;
+    const bool has5 = found5 && !two5, has3 = found3 && !two3;
+    const uint32_t i5 = has5 ? t5 : n5, i3 = has3 ? t3 : n3;
+    uint32_t verdict = kDemuxOk;
+    sample = kDemuxNone;
+    if ((found5 && two5) || (found3 && two3)) verdict = kDemuxAmbiguous;
+    else if (n5 && !found5) verdict = kDemuxNoTag5;
+    else if (n3 && !found3) verdict = kDemuxNoTag3;
+    else {
+        sample = pair(i5, i3);
+        if (sample == kDemuxNone) verdict = kDemuxUnknownPair;
+    }
+    lo = has5 ? s5 + tags[i5].m : 0u;
+    hi = has3 ? len - (s3 + tags[n5 + i3].m) : len;
+    if (hi < lo) hi = lo;  // the cuts overlap: the read is left empty
+    hit = (has5 ? tags[i5].index : kDemuxNoTag) | ((has3 ? tags[n5 + i3].index : kDemuxNoTag) << 16);
+    info = verdict | ((has5 ? d5 : 0u) << 8) | ((has3 ? d3 : 0u) << 16) | ((has5 ? s5 : 0u) << 24) | ((has3 ? s3 : 0u) << 28);
+}
+// The dense pair table the kernel looks up: (n5 + 1) x (n3 + 1) samples, row i5 (n5: no 5' tag), column i3 (n3: no 3' tag), kDemuxNone
+// where there is no pair.  rank[t]: the place of tag t of the caller's list within its end.
+RTX_HD size_t demux_table_size(uint32_t n5, uint32_t n3) { return (size_t)(n5 + 1u) * (n3 + 1u); }
+RTX_HD size_t demux_table_slot(uint32_t n3, uint32_t i5, uint32_t i3) { return (size_t)i5 * (n3 + 1u) + i3; }
+
+// ---------------------------------------------------------------------------
 // Quality filter (qual_kernel, rtx_qual.hip; rtx_qual_read on the host; emul_qual_read on x86): where a read is cut and why it is discarded,
 // from its FASTQ quality string -- include/raxtax_hip.h has the semantics.  Exact integers: the error probability of quality Q is
 // e[Q] = llround(10^(-Q/10) * 2^40), computed once on the host (qual_table), a threshold x is floor(x * 2^40); a read has at most 2^20 bases,

@@ -114,6 +114,64 @@ __global__ __launch_bounds__(kProfileThreads) void profile_kernel(ProfileParams 
     }
 }
 
+// The per-sample counters (rtx_index_profile_begin_samples): a lane per position like profile_kernel, the same profile_step, and the same
+// wave-level group-by -- once on the sample for the totals, once on (sample, node) for the direct counts of the classified queries: the
+// first lane still to be served names its key, a ballot finds the lanes that hold it, their weights are summed over the wave and the
+// leader adds them with one 64-bit integer atomic.  No lane leaves early; a query without a sample takes part in nothing.
+__global__ __launch_bounds__(kProfileThreads) void profile_samples_kernel(SampleProfileParams sp) {
+    const ProfileParams &p = sp.p;
+    const uint32_t lane = lane_id();
+    const uint64_t pos = (uint64_t)blockIdx.x * kProfileThreads + threadIdx.x;
+    bool active = pos < p.n_pos;
+    uint64_t q = 0;
+    if (active) {
+        q = p.perm[pos];
+        active = q < p.n_user;
+    }
+    const uint32_t smp = active ? sp.sample[q] : sp.n_samples;
+    active = active && smp < sp.n_samples;
+    ProfileStep st{kProfUnclassifiable, 0u, 0u, nullptr};
+    if (active) {
+        const uint64_t qx = p.strand && p.strand[q] ? q + p.n_user : q;
+        st = profile_step(p.src, q, p.override_ok ? exact_only(p.exact, qx) : kTextNoOverride, p.cutoff);
+    }
+    const unsigned long long w = active ? (p.weight ? p.weight[q] : 1ull) : 0ull;
+    unsigned long long todo = __ballot(active);
+    while (todo) {  // (wave-uniform) the totals, by sample
+        const uint32_t lead = (uint32_t)__ffsll((long long)todo) - 1u;
+        const uint32_t key = (uint32_t)__shfl((int)smp, (int)lead, 64);
+        const bool mine = active && smp == key;
+        const unsigned long long n_act = wave_sum_u64(mine ? w : 0ull);
+        const unsigned long long n_cls = wave_sum_u64(mine && st.kind == kProfClassified ? w : 0ull);
+        const unsigned long long n_unc = wave_sum_u64(mine && st.kind == kProfUnclassified ? w : 0ull);
+        if (lane == lead && n_act) {
+            unsigned long long *t = sp.totals + (size_t)key * 4u;
+            atomicAdd(t + 0, n_act);
+            if (n_cls) atomicAdd(t + 1, n_cls);
+            if (n_unc) atomicAdd(t + 2, n_unc);
+            if (n_act - n_cls - n_unc) atomicAdd(t + 3, n_act - n_cls - n_unc);
+        }
+        todo &= ~__ballot(mine);
+    }
+    const bool part = active && st.kind == kProfClassified && st.node < p.n_nodes;  // (a node id outside the table: never from a well-formed result)
+    const uint64_t slot = (uint64_t)smp * p.n_nodes + st.node;
+    todo = __ballot(part);
+    while (todo) {  // the direct counts, by (sample, node)
+        const uint32_t lead = (uint32_t)__ffsll((long long)todo) - 1u;
+        const uint64_t key = (uint64_t)__shfl((unsigned long long)slot, (int)lead, 64);
+        const bool mine = part && slot == key;
+        const unsigned long long n_dir = wave_sum_u64(mine ? w : 0ull);
+        if (lane == lead && n_dir) atomicAdd(sp.direct + key, n_dir);
+        todo &= ~__ballot(mine);
+    }
+}
+
+void launch_profile_samples(hipStream_t s, const SampleProfileParams &p) {
+    if (p.p.n_pos == 0) return;
+    const dim3 grid((unsigned)((p.p.n_pos + kProfileThreads - 1u) / kProfileThreads));
+    hipLaunchKernelGGL(profile_samples_kernel, grid, dim3(kProfileThreads), 0, s, p);
+}
+
 void launch_profile(hipStream_t s, const ProfileParams &p) {
     if (p.n_pos == 0) return;
     const dim3 grid((unsigned)((p.n_pos + kProfileThreads - 1u) / kProfileThreads));
