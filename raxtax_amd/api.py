@@ -1553,22 +1553,14 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     tags=(tags, pairs, params): the read belongs to `sample` (DEMUX_NONE: to none) and kept [lo, hi) of its raw_len bases; hit and info as
     demux_hit() takes them apart).  The callbacks behind it then speak of the cut read.  It goes with `align`, `trim`, `qual`, `chimera` or alone."""
     lib = _lib.load()
-    lib.rtx_raxtax.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int,
-                               C.c_uint64, _SENDER, C.c_void_p, C.c_int]
-    lib.rtx_raxtax_multi.argtypes = [C.POINTER(C.c_void_p), C.c_uint32] + lib.rtx_raxtax.argtypes[1:]
-    lib.rtx_raxtax_multi_ex.argtypes = lib.rtx_raxtax_multi.argtypes + [_INFO, C.c_void_p]
-    lib.rtx_raxtax_multi_ex2.argtypes = lib.rtx_raxtax_multi.argtypes + [_HIT, C.c_void_p]
-    lib.rtx_raxtax_multi_ex3.argtypes = lib.rtx_raxtax_multi.argtypes + [_ALIGN, C.c_void_p]
-    lib.rtx_raxtax_multi_ex4.argtypes = lib.rtx_raxtax_multi_ex3.argtypes + [_TRIM, C.c_void_p]
+    common = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int, C.c_uint64, _SENDER, C.c_void_p, C.c_int]
+    lib.rtx_raxtax_multi_ex7.argtypes = common + [_ALIGN, C.c_void_p, _TRIM, C.c_void_p, u8p, _QUAL, C.c_void_p, _CHIM, C.c_void_p, _DEMUX, C.c_void_p]
     if (info is not None) + (hit is not None) + (align is not None) > 1:
         raise ValueError("raxtax: give one of info, hit and align")
-    lib.rtx_raxtax_multi_ex5.argtypes = lib.rtx_raxtax_multi_ex4.argtypes + [u8p, _QUAL, C.c_void_p]
-    lib.rtx_raxtax_multi_ex6.argtypes = lib.rtx_raxtax_multi_ex5.argtypes + [_CHIM, C.c_void_p]
-    lib.rtx_raxtax_multi_ex7.argtypes = lib.rtx_raxtax_multi_ex6.argtypes + [_DEMUX, C.c_void_p]
     if (trim is not None or qual is not None or chimera is not None or demux is not None) and (info is not None or hit is not None):
         raise ValueError("raxtax: trim, qual, chimera and demux go with align or alone")
     if quals is None and info is None and hit is None and len(queries) and all(len(q) == 3 for q in queries):
-        quals = [q[2] for q in queries]   # (info and hit go through calls that carry no quality strings: triples are then read as pairs)
+        quals = [q[2] for q in queries]   # (info and hit are the callbacks of calls that carried no quality strings: triples are then read as pairs)
     if quals is not None and (info is not None or hit is not None):
         raise ValueError("raxtax: quals go with align, trim and qual")
     flat_q = None
@@ -1581,119 +1573,33 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     flat, off = _flatten([q[1] for q in queries])
     err: List[BaseException] = []
 
-    def cb(_ctx, label, out, tsv_lines):
-        try:
-            sender(label.decode(), out.decode(), tsv_lines.decode() if tsv_lines is not None else None)
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
+    def guarded(ctype, fn, convert=lambda *a: [int(x) for x in a]):
+        """fn(label, *convert(the C arguments)) as a callback of `ctype` (null for None): an exception is kept for the caller and closes the sink."""
+        if fn is None and ctype is not _SENDER:
+            return C.cast(None, ctype)
 
-    def cb_info(_ctx, label, strand, peak, t):
-        try:
-            info(label.decode(), int(strand), int(peak), int(t))
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
+        def cb(_ctx, label, *args):
+            try:
+                fn(label.decode(), *convert(*args))
+                return 0
+            except BaseException as e:  # noqa: BLE001 - forwarded below
+                err.append(e)
+                return 1
 
-    def cb_hit(_ctx, label, strand, peak, t, nearest, ties):
-        try:
-            hit(label.decode(), int(strand), int(peak), int(t), int(nearest), int(ties))
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
+        return ctype(cb)
 
-    def cb_align(_ctx, label, strand, peak, t, nearest, ties, dist, qlen):
-        try:
-            align(label.decode(), int(strand), int(peak), int(t), int(nearest), int(ties), int(dist), int(qlen))
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
-
-    def cb_trim(_ctx, label, raw_len, lo, hi, hit_word):
-        try:
-            trim(label.decode(), int(raw_len), int(lo), int(hi), int(hit_word))
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
-
-    def cb_qual(_ctx, label, raw_len, lo, hi, ee, verdict):
-        try:
-            qual(label.decode(), int(raw_len), int(lo), int(hi), int(ee), int(verdict))
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
-
-    def cb_chim(_ctx, label, rec):
-        try:
-            chimera(label.decode(), np.array([tuple(getattr(rec.contents, f) for f in _lib.RTX_CHIM_FIELDS)], CHIMERA_DTYPE)[0])
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
-
-    def cb_demux(_ctx, label, raw_len, sample, lo, hi, hit_word, info_word):
-        try:
-            demux(label.decode(), int(raw_len), int(sample), int(lo), int(hi), int(hit_word), int(info_word))
-            return 0
-        except BaseException as e:  # noqa: BLE001 - forwarded below
-            err.append(e)
-            return 1
-
-    if demux is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex7(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
-                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None,
-                                      _TRIM(cb_trim) if trim is not None else C.cast(None, _TRIM), None,
-                                      ptr(flat_q, u8p) if flat_q is not None else None,
-                                      _QUAL(cb_qual) if qual is not None else C.cast(None, _QUAL), None,
-                                      _CHIM(cb_chim) if chimera is not None else C.cast(None, _CHIM), None, _DEMUX(cb_demux), None)
-    elif chimera is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex6(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
-                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None,
-                                      _TRIM(cb_trim) if trim is not None else C.cast(None, _TRIM), None,
-                                      ptr(flat_q, u8p) if flat_q is not None else None,
-                                      _QUAL(cb_qual) if qual is not None else C.cast(None, _QUAL), None, _CHIM(cb_chim), None)
-    elif flat_q is not None or qual is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex5(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
-                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None,
-                                      _TRIM(cb_trim) if trim is not None else C.cast(None, _TRIM), None,
-                                      ptr(flat_q, u8p) if flat_q is not None else None,
-                                      _QUAL(cb_qual) if qual is not None else C.cast(None, _QUAL), None)
-    elif trim is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex4(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv),
-                                      _ALIGN(cb_align) if align is not None else C.cast(None, _ALIGN), None, _TRIM(cb_trim), None)
-    elif align is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex3(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _ALIGN(cb_align), None)
+    if info is not None:    # the narrower callbacks, in the shape of align
+        align = lambda label, strand, peak, t, *_: info(label, strand, peak, t)  # noqa: E731
     elif hit is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex2(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                      int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _HIT(cb_hit), None)
-    elif info is not None:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi_ex(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                     int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv), _INFO(cb_info), None)
-    elif len(handles) == 1:
-        rc = lib.rtx_raxtax(handles[0]._h, handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                            int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv))
-    else:
-        arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-        rc = lib.rtx_raxtax_multi(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
-                                  int(skip_exact_matches), int(raw_confidence), chunk_size, _SENDER(cb), None, int(tsv))
+        align = lambda label, strand, peak, t, nearest, ties, *_: hit(label, strand, peak, t, nearest, ties)  # noqa: E731
+    arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
+    rc = lib.rtx_raxtax_multi_ex7(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+                                  int(skip_exact_matches), int(raw_confidence), chunk_size,
+                                  guarded(_SENDER, sender, lambda out, tsv_lines: (out.decode(), tsv_lines.decode() if tsv_lines is not None else None)), None, int(tsv),
+                                  guarded(_ALIGN, align), None, guarded(_TRIM, trim), None, ptr(flat_q, u8p) if flat_q is not None else None,
+                                  guarded(_QUAL, qual), None,
+                                  guarded(_CHIM, chimera, lambda rec: [np.array([tuple(getattr(rec.contents, f) for f in _lib.RTX_CHIM_FIELDS)], CHIMERA_DTYPE)[0]]), None,
+                                  guarded(_DEMUX, demux), None)
     if err:
         raise err[0]
     check(rc)

@@ -888,7 +888,7 @@ int main(int argc, char **argv) {
     };
     // ... and in front of them, under --strand both, which orientation the lines are of
     // ... and, under --hits, which reference they look like: peak, t, ties, id and lineage of the nearest reference ('-' twice where no reference shares a k-mer)
-    auto info = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties) -> int {
+    auto info = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {   // (in the shape of --identity's callback)
         Sink *s = static_cast<Sink *>(c);
         if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
         if (s->want_hits) {
@@ -976,17 +976,6 @@ int main(int argc, char **argv) {
         s->demux << lo << '\t' << hi << '\n';
         return s->demux.good() ? 0 : 1;
     };
-    // (rtx_raxtax_multi_ex4 carries the callback of --identity: without that option the one of --strand both / --hits stands in its shape)
-    auto info_as_align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {
-        Sink *s = static_cast<Sink *>(c);
-        if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
-        if (s->want_hits) {
-            s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
-            if (nearest == RTX_NO_REF) s->hits << "-\t-\n";
-            else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest) << '\n';
-        }
-        return (!s->want_strand || s->strand.good()) && (!s->want_hits || s->hits.good()) ? 0 : 1;
-    };
     int rc = RTX_OK;
     uint64_t n = 0;
     uint64_t trim_total[4] = {0, 0, 0, 0};  // --primers: over the blocks of the file (rtx_raxtax_last_trim)
@@ -1044,36 +1033,12 @@ int main(int argc, char **argv) {
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
             const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
-            if (tags_on) {
-                const uint8_t *quals = nullptr;
-                if (qual_on) rtx_queries_quals(pz.qs, &quals);
-                rc = rtx_raxtax_multi_ex7(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                          want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
-                                          quals, qual_on ? +filtered : nullptr, &sink, chim_on ? +checked : nullptr, &sink, +assigned, &sink);
-            }
-            else if (chim_on) {
-                const uint8_t *quals = nullptr;
-                if (qual_on) rtx_queries_quals(pz.qs, &quals);
-                rc = rtx_raxtax_multi_ex6(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                          want_identity ? +align : (want_hits ? +info_as_align : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
-                                          quals, qual_on ? +filtered : nullptr, &sink, +checked, &sink);
-            }
-            else if (qual_on) {
-                const uint8_t *quals = nullptr;
-                rtx_queries_quals(pz.qs, &quals);
-                rc = rtx_raxtax_multi_ex5(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                          want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
-                                          quals, +filtered, &sink);
-            }
-            else if (!primers.empty())
-                rc = rtx_raxtax_multi_ex4(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                          want_identity ? +align : (both_strands || want_hits ? +info_as_align : nullptr), &sink, +trimmed, &sink);
-            else if (want_identity)
-                rc = rtx_raxtax_multi_ex3(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                          +align, &sink);
-            else
-                rc = rtx_raxtax_multi_ex2(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                          both_strands || want_hits ? +info : nullptr, &sink);
+            // one entry point takes everything a run can bring: an option that is off passes no callback
+            const uint8_t *quals = nullptr;
+            if (qual_on) rtx_queries_quals(pz.qs, &quals);
+            rc = rtx_raxtax_multi_ex7(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+                                      want_identity ? +align : (both_strands || want_hits ? +info : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
+                                      quals, qual_on ? +filtered : nullptr, &sink, chim_on ? +checked : nullptr, &sink, tags_on ? +assigned : nullptr, &sink);
             n += nb;
             if (tags_on) {
                 uint64_t xq[7] = {0, 0, 0, 0, 0, 0, 0};

@@ -1,0 +1,256 @@
+// The read front of the host mirror: see host_front.hpp.
+#include "host_front.hpp"
+
+#include <chrono>
+#include <cstring>
+#include <tuple>
+#include <utility>
+
+namespace rtx_front {
+
+namespace {
+
+double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The sample of every read of the chunk, on the device (a stream of its own beside the handle's); then the reads without their tags, a
+// read that is not assigned empty.
+int run_demux(rtx_demux *stage, FrontChunk &fc, BufPool &pool, FrontTotals &tot) {
+    const double t0 = now();
+    const uint64_t nq = fc.given.n;
+    for (auto *v : {&fc.dx_sample, &fc.dx_lo, &fc.dx_hi, &fc.dx_hit, &fc.dx_info}) v->resize(nq);
+    int rc = rtx_demux_run(stage, nq, fc.given.bases, fc.given.off, fc.dx_sample.data(), fc.dx_lo.data(), fc.dx_hi.data(), fc.dx_hit.data(), fc.dx_info.data());
+    if (rc) return rc;
+    std::vector<uint32_t> keep_hi(nq);
+    auto x = tot.demux;  // (counted in locals: the loop runs per read)
+    for (uint64_t i = 0; i < nq; i++) {
+        const uint32_t v = fc.dx_info[i] & 0xFFu;
+        keep_hi[i] = v == RTX_DEMUX_OK ? fc.dx_hi[i] : fc.dx_lo[i];
+        x.assigned += v == RTX_DEMUX_OK;
+        if (v < 5u) x.reasons[v]++;
+    }
+    tot.demux = x;
+    rc = cut(fc.given, fc.dx_lo.data(), keep_hi.data(), fc.given.quals != nullptr, fc.x, pool, "no memory for the demultiplexed reads of a chunk", fc.in);
+    if (rc) return rc;
+    fc.src = fc.dev = fc.in;
+    tot.demux.queries += nq;
+    tot.demux.busy += now() - t0;
+    return RTX_OK;
+}
+
+// The primers of the chunk's reads, then the quality of the ranges they left, on the device (streams of their own beside the handle's); then
+// both ranges in one cut, a discarded read empty.
+int run_trim_qual(rtx_trim *trim, rtx_qual *qual, FrontChunk &fc, BufPool &pool, FrontTotals &tot) {
+    const double t_t0 = now();
+    const Reads &in = fc.in;
+    const uint64_t nq = in.n;
+    fc.lo.resize(nq);
+    fc.hi.resize(nq);
+    fc.hit.resize(nq);
+    if (trim) {
+        const int rc = rtx_trim_run(trim, nq, in.bases, in.off, fc.lo.data(), fc.hi.data(), fc.hit.data());
+        if (rc) return rc;
+        auto t = tot.trim;  // (counted in locals: the loops run per read)
+        for (uint64_t i = 0; i < nq; i++) {
+            t.with5 += (fc.hit[i] & 0xFFu) != RTX_TRIM_NO_PATTERN;
+            t.with3 += ((fc.hit[i] >> 16) & 0xFFu) != RTX_TRIM_NO_PATTERN;
+            t.emptied += in.len(i) != 0 && fc.hi[i] == fc.lo[i];
+        }
+        tot.trim = t;
+    } else {
+        for (uint64_t i = 0; i < nq; i++) {
+            fc.lo[i] = 0u;
+            fc.hi[i] = in.len32(i);
+            fc.hit[i] = RTX_TRIM_NO_PATTERN | RTX_TRIM_NO_PATTERN << 16;
+        }
+    }
+    const double t_q0 = now();
+    if (qual) {
+        fc.q_hi.resize(nq);
+        fc.q_verdict.resize(nq);
+        fc.q_ee.resize(nq);
+        fc.keep_hi.resize(nq);
+        const int rc = rtx_qual_run(qual, nq, in.bases, in.quals, in.off, fc.lo.data(), fc.hi.data(), fc.q_hi.data(), fc.q_ee.data(), fc.q_verdict.data());
+        if (rc) return rc;
+        auto q = tot.qual;
+        for (uint64_t i = 0; i < nq; i++) {
+            const uint32_t v = fc.q_verdict[i];
+            fc.keep_hi[i] = v ? fc.lo[i] : fc.q_hi[i];
+            q.passed += v == 0u;
+            q.truncated += v == 0u && fc.q_hi[i] < fc.hi[i];
+            for (uint32_t b = 0; b < 7u; b++) q.reasons[b] += (v >> b) & 1u;
+        }
+        tot.qual = q;
+    }
+    const int rc = cut(in, fc.lo.data(), (qual ? fc.keep_hi : fc.hi).data(), false, fc.t, pool, "no memory for the trimmed reads of a chunk", fc.src);
+    if (rc) return rc;
+    fc.dev = fc.src;
+    if (trim) { tot.trim.queries += nq; tot.trim.busy += (qual ? t_q0 : now()) - t_t0; }
+    if (qual) { tot.qual.queries += nq; tot.qual.busy += now() - t_q0; }
+    return RTX_OK;
+}
+
+// The copies of the chunk, on the device (a stream of its own beside the handle's); then the map's host side and the distinct reads.
+int run_derep(rtx_derep *stage, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTotals &tot) {
+    const double t0 = now();
+    const uint64_t nq = fc.src.n;
+    std::vector<uint32_t> rep(nq);
+    uint64_t nu = 0;
+    int rc = rtx_derep_run(stage, nq, fc.src.bases, fc.src.off, rep.data(), &nu);
+    if (!rc && nu < nq) {  // (a chunk without copies goes on as it came)
+        std::vector<uint32_t> uniq(nq);
+        fc.slot.resize(nq);
+        fc.size.resize(nq);
+        rc = rtx_derep_plan(nq, rep.data(), uniq.data(), fc.slot.data(), fc.size.data(), &nu);
+        if (!rc) {
+            fc.size.resize(nu);
+            rc = gather(fc.src, uniq.data(), nu, fc.u, pool, nt, fc.dev);
+        }
+    }
+    if (rc) return rc;
+    tot.derep.queries += nq;
+    tot.derep.distinct += fc.dev.n;
+    tot.derep.busy += now() - t0;
+    return RTX_OK;
+}
+
+// The reads that go to the handle, on the device (a stream of its own beside the handle's); a flagged one goes on empty.
+int run_chimera(rtx_chimera *stage, FrontChunk &fc, BufPool &pool, FrontTotals &tot) {
+    const double t0 = now();
+    const Reads dev = fc.dev;
+    fc.chim.resize(dev.n);
+    int rc = rtx_chimera_run(stage, dev.n, dev.bases, dev.off, fc.chim.data());
+    if (rc) return rc;
+    bool any = false;
+    for (uint64_t u = 0; u < dev.n && !any; u++) any = fc.chim[u].flag != 0u;
+    if (any) {  // (a flagged read has at most RTX_CHIMERA_MAX_QUERY bases; a longer one is not checked and is not cut here)
+        std::vector<uint32_t> lo(dev.n, 0u), hi(dev.n);
+        for (uint64_t u = 0; u < dev.n; u++) {
+            if (!fc.chim[u].flag && dev.len(u) > 0xFFFFFFFFull) { rtx::set_error("rtx_raxtax: a read of 2^32 bases or more with the chimera check set"); return RTX_ERR_INVALID; }
+            hi[u] = fc.chim[u].flag ? 0u : (uint32_t)dev.len(u);
+        }
+        rc = cut(dev, lo.data(), hi.data(), false, fc.c, pool, "no memory for the checked reads of a chunk", fc.dev);
+        if (rc) return rc;
+    }
+    tot.chim.queries += fc.given.n;
+    tot.chim.checked += dev.n;
+    for (uint64_t i = 0; i < fc.given.n; i++) tot.chim.flagged += fc.chim[fc.at(i)].flag != 0u;
+    tot.chim.busy += now() - t0;
+    return RTX_OK;
+}
+
+}  // namespace
+
+int cut(const Reads &from, const uint32_t *lo, const uint32_t *keep_hi, bool with_quals, Cut &out, BufPool &pool, const char *oom, Reads &to) {
+    bool any = false;
+    for (uint64_t i = 0; i < from.n && !any; i++) any = lo[i] != 0u || keep_hi[i] != from.len(i);
+    Reads r = from;
+    if (any) {  // (a chunk in which nothing was cut goes on as it came, without a copy)
+        uint64_t kept = 0;
+        for (uint64_t i = 0; i < from.n; i++) kept += keep_hi[i] - lo[i];
+        pool.take(out.bases);
+        if (with_quals) pool.take(out.quals);
+        if (!out.bases.reserve(kept + 1) || (with_quals && !out.quals.reserve(kept + 1))) { rtx::set_error("%s", oom); return RTX_ERR_OOM; }
+        out.off.resize(from.n + 1);
+        int rc = rtx_trim_apply(from.n, from.bases, from.off, lo, keep_hi, out.bases.p, out.off.data());
+        if (!rc && with_quals) rc = rtx_trim_apply(from.n, from.quals, from.off, lo, keep_hi, out.quals.p, out.off.data());
+        if (rc) return rc;
+        r = Reads{out.bases.p, with_quals ? out.quals.p : nullptr, out.off.data(), from.n};
+    }
+    to = r;
+    return RTX_OK;
+}
+
+int gather(const Reads &from, const uint32_t *uniq, uint64_t nu, Cut &out, BufPool &pool, unsigned nt, Reads &to) {
+    out.off.assign(nu + 1, 0);
+    for (uint64_t u = 0; u < nu; u++) out.off[u + 1] = out.off[u] + from.len(uniq[u]);
+    pool.take(out.bases);
+    if (!out.bases.reserve(out.off[nu] + 1)) { rtx::set_error("no memory for the distinct reads of a chunk"); return RTX_ERR_OOM; }
+    // runs of neighbouring distinct reads that are neighbours in the input as well (most of a chunk with few copies) move in one memcpy
+    const Reads src = from;
+    const uint64_t *const off = out.off.data();
+    uint8_t *const dst = out.bases.p;
+    parallel_ranges(nu, nt, [&](uint64_t a, uint64_t b) {
+        for (uint64_t u = a; u < b;) {
+            uint64_t v = u + 1;
+            while (v < b && uniq[v] == uniq[v - 1] + 1u) v++;
+            if (off[v] > off[u]) memcpy(dst + off[u], src.bases + src.off[uniq[u]], off[v] - off[u]);
+            u = v;
+        }
+    });
+    to = Reads{dst, nullptr, off, nu};
+    return RTX_OK;
+}
+
+int Front::open(rtx_index *const *indices, uint32_t n_dev, bool has_quals, bool prof) {
+    // RTX_OPT_DEREP: on every handle, or on none.  One stage object (rtx_derep.hip) per distinct device for the duration of the call: the
+    // lookup thread runs chunk c through the object of handle c mod n_dev's device while that handle still classifies an earlier chunk.
+    derep = rtx::index_derep(indices[0]);
+    int rc = agree(indices, n_dev, rtx::index_derep, "rtx_raxtax_multi: the handles disagree on RTX_OPT_DEREP");
+    if (!rc && derep) rc = dereps.open(indices, n_dev, true, [&](uint32_t d, rtx_derep **out) { return rtx_derep_create(rtx::index_device(indices[d]), out); });
+    if (rc) return rc;
+    // Tags (rtx_index_set_tags): the same list on every handle
+    const rtx::DemuxList &taglist = rtx::index_tags(indices[0]);
+    demux = !taglist.empty();
+    rc = agree(indices, n_dev, [](const rtx_index *ix) -> const rtx::DemuxList & { return rtx::index_tags(ix); }, "rtx_raxtax_multi: the handles disagree on their tags (rtx_index_set_tags)");
+    if (rc) return rc;
+    prof_samples = rtx::index_profile_samples(indices[0]);
+    rc = agree(indices, n_dev, rtx::index_profile_samples, "rtx_raxtax_multi: the handles disagree on the samples of their taxon profile (rtx_index_profile_begin_samples)");
+    if (rc) return rc;
+    if (demux && derep && prof) {
+        rtx::set_error("rtx_raxtax: tags (rtx_index_set_tags) together with RTX_OPT_DEREP and an open taxon profile: copies from different samples would be counted as one read");
+        return RTX_ERR_INVALID;
+    }
+    if (demux) {
+        std::vector<rtx_demux_tag> tags(taglist.codes.size());
+        for (size_t i = 0; i < tags.size(); i++) tags[i] = {taglist.codes[i].data(), (uint32_t)taglist.codes[i].size(), taglist.end[i]};
+        rc = demuxes.open(indices, n_dev, true, [&](uint32_t d, rtx_demux **out) {
+            return rtx_demux_create(rtx::index_device(indices[d]), tags.data(), (uint32_t)tags.size(), taglist.pairs.data(), (uint32_t)taglist.pairs.size(), &taglist.params, out);
+        });
+        if (rc) return rc;
+    }
+    // Primers (rtx_index_set_primers): the same list on every handle
+    const std::vector<rtx::TrimPrimer> &primers = rtx::index_primers(indices[0]);
+    trim = !primers.empty();
+    rc = agree(indices, n_dev, [](const rtx_index *ix) -> const std::vector<rtx::TrimPrimer> & { return rtx::index_primers(ix); },
+               "rtx_raxtax_multi: the handles disagree on their primers (rtx_index_set_primers)");
+    if (rc) return rc;
+    if (trim) {
+        std::vector<rtx_trim_pattern> pats(primers.size());
+        for (size_t i = 0; i < primers.size(); i++) pats[i] = {primers[i].codes.data(), (uint32_t)primers[i].codes.size(), primers[i].end, primers[i].max_errors, primers[i].window};
+        rc = trims.open(indices, n_dev, true, [&](uint32_t d, rtx_trim **out) { return rtx_trim_create(rtx::index_device(indices[d]), pats.data(), (uint32_t)pats.size(), out); });
+        if (rc) return rc;
+    }
+    // Quality filter (rtx_index_set_quality): the same setting on every handle, and the call brings the quality strings
+    auto quality = [](const rtx_index *ix) { std::pair<bool, rtx_qual_params> s{false, {}}; s.first = rtx::index_quality(ix, &s.second); return s; };
+    const rtx_qual_params qparams = quality(indices[0]).second;
+    qual = quality(indices[0]).first;
+    rc = agree(indices, n_dev, quality, "rtx_raxtax_multi: the handles disagree on their quality filter (rtx_index_set_quality)",
+               [](const auto &a, const auto &b) { return a.first == b.first && (!a.first || rtx::qual_params_equal(a.second, b.second)); });
+    if (rc) return rc;
+    if (qual && !has_quals) { rtx::set_error("rtx_raxtax: a quality filter is set (rtx_index_set_quality) and the call brings no quality strings (rtx_raxtax_multi_ex5)"); return RTX_ERR_INVALID; }
+    if (qual) {
+        rc = quals.open(indices, n_dev, true, [&](uint32_t d, rtx_qual **out) { return rtx_qual_create(rtx::index_device(indices[d]), &qparams, out); });
+        if (rc) return rc;
+    }
+    // Chimera check (rtx_index_set_chimera): the same setting on every handle.  One stage object (rtx_chimera.hip) per HANDLE: it reads that
+    // handle's bitmap.  Not with RTX_OPT_STRAND (rtx_chimera_create refuses it: a read is checked in the orientation given).
+    auto chimera = [](const rtx_index *ix) { std::pair<bool, rtx_chimera_params> s{false, {}}; s.first = rtx::index_chimera(ix, &s.second); return s; };
+    const rtx_chimera_params cparams = chimera(indices[0]).second;
+    chim = chimera(indices[0]).first;
+    rc = agree(indices, n_dev, chimera, "rtx_raxtax_multi: the handles disagree on their chimera check (rtx_index_set_chimera)",
+               [](const auto &a, const auto &b) { return a.first == b.first && (!a.first || (a.second.segments == b.second.segments && a.second.mindelta == b.second.mindelta)); });
+    if (rc) return rc;
+    if (chim) rc = chims.open(indices, n_dev, false, [&](uint32_t d, rtx_chimera **out) { return rtx_chimera_create(indices[d], &cparams, out); });
+    return rc;
+}
+
+int Front::run(uint32_t d, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTotals &tot) const {
+    int rc = RTX_OK;
+    if (demux) rc = run_demux(demuxes.of[d], fc, pool, tot);
+    if (!rc && (trim || qual)) rc = run_trim_qual(trim ? trims.of[d] : nullptr, qual ? quals.of[d] : nullptr, fc, pool, tot);
+    if (!rc && derep) rc = run_derep(dereps.of[d], fc, pool, nt, tot);
+    if (!rc && chim) rc = run_chimera(chims.of[d], fc, pool, tot);
+    return rc;
+}
+
+}  // namespace rtx_front
