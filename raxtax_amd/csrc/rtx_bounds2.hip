@@ -33,8 +33,8 @@ namespace rtx {
 constexpr uint32_t kB2Pad = 256u;                        // the largest group of rows of either level (level B: 16 instructions x 16 rows)
 // entries per list (t <= 1023; eleven planes: t <= 2047), padded with the zero row to multiples of kB2Pad
 constexpr uint32_t b2_cap(int planes) { return planes > 10 ? 2048u : 1024u; }
-// lists | zero rows; behind them per A-tile [2][64] u16: the level-A bounds both queries' lanes found
-constexpr uint32_t b2_lds_dw(int planes) { return 3u * b2_cap(planes) + kB2Pad; }
+// the three lists; behind them per A-tile [2][64] u16: the level-A bounds both queries' lanes found
+constexpr uint32_t b2_lds_dw(int planes) { return 3u * b2_cap(planes); }
 
 // eight load instructions of R rows each: this lane's rows are list[8 * grp .. + 8) of the unit, its bytes col .. col + 16 of each
 template <int SHIFT>
@@ -50,18 +50,20 @@ __device__ __forceinline__ void load_unit(uint4 (&buf)[8], __amdgpu_buffer_rsrc_
 
 // One list: `ng` groups of NB units (8 instructions of R rows each) folded into A's planes (MODE 1) or B's (MODE 2).  As fold_seg
 // (rtx_hit_pair.hip): on entry the buffers hold the first group, every buffer is requested again as soon as it has been folded -- in
-// the last group with the first rows of the next list --, so that the lists of a level run as one pipeline.
+// the last group with the first rows of the next list --, so that the lists of a level run as one pipeline.  The last list of a level
+// has no next one (`next` = nullptr): its last group is folded by a copy of the body that requests nothing (the look-ahead used to issue
+// NB * 8 instructions on the zero row per level: 32 at level A, 16 per refined B-tile).
 template <int NP, int MODE, int R, int NB, int SHIFT>
 __device__ __forceinline__ void fold_list(uint32_t (&pa)[4][NP], uint32_t (&pb)[4][NP], uint4 (&buf)[4][8], const uint32_t *list, uint32_t ng,
                                           const uint32_t *next, uint32_t grp, uint32_t col, __amdgpu_buffer_rsrc_t rsrc) {
     constexpr uint32_t kUnit = 8u * (uint32_t)R, kGroup = kUnit * (uint32_t)NB;
-    for (uint32_t g = 0; g < ng; g++) {
-        const uint32_t *src = g + 1 < ng ? list + (g + 1) * kGroup : next;  // wave-uniform
+    auto group = [&](auto load_tag, const uint32_t *src) {
+        constexpr bool kLoad = decltype(load_tag)::value;
         uint4 c[NB];
 #pragma unroll
         for (int b = 0; b < NB; b++) {
             c[b] = MODE == 1 ? tree8<NP>(pa, buf[b]) : tree8<NP>(pb, buf[b]);
-            load_unit<SHIFT>(buf[b], rsrc, src + (uint32_t)b * kUnit, grp, col);
+            if constexpr (kLoad) load_unit<SHIFT>(buf[b], rsrc, src + (uint32_t)b * kUnit, grp, col);
         }
         if (MODE == 1) {
             if constexpr (NB == 4) ripple4<NP, 5>(pa, csa_plane<NP, 4>(pa, csa_plane<NP, 3>(pa, c[0], c[1]), csa_plane<NP, 3>(pa, c[2], c[3])));
@@ -70,7 +72,10 @@ __device__ __forceinline__ void fold_list(uint32_t (&pa)[4][NP], uint32_t (&pb)[
             if constexpr (NB == 4) ripple4<NP, 5>(pb, csa_plane<NP, 4>(pb, csa_plane<NP, 3>(pb, c[0], c[1]), csa_plane<NP, 3>(pb, c[2], c[3])));
             else ripple4<NP, 4>(pb, csa_plane<NP, 3>(pb, c[0], c[1]));
         }
-    }
+    };
+    const uint32_t n_loop = next ? ng : ng - 1u;  // wave-uniform; ng >= 1: fold_level calls with the lists that have a group
+    for (uint32_t g = 0; g < n_loop; g++) group(std::true_type{}, g + 1 < ng ? list + (g + 1) * kGroup : next);
+    if (!next) group(std::false_type{}, nullptr);
 }
 
 // The four DPP rows of the wave hold partial counters of the same columns: summed over the rows, DPP row r ends with word r of its
@@ -112,9 +117,8 @@ __global__ __launch_bounds__(64, 2) void bounds2_kernel(Bounds2Params p) {
     const uint32_t qa = pair * 2u, qb = qa + 1u;
     const bool has_b = qb < p.nq;
     constexpr uint32_t kB2Cap = b2_cap(NP);
-    uint32_t *l_both = b2_lds, *l_a = b2_lds + kB2Cap, *l_b = b2_lds + 2u * kB2Cap, *l_zero = b2_lds + 3u * kB2Cap;
-    uint16_t *l_keep = reinterpret_cast<uint16_t *>(l_zero + kB2Pad);  // [n_atiles][2][64] level-A bound of every lane's tile, per query
-    for (uint32_t i = lane; i < kB2Pad; i += 64) l_zero[i] = p.zero_row;
+    uint32_t *l_both = b2_lds, *l_a = b2_lds + kB2Cap, *l_b = b2_lds + 2u * kB2Cap;
+    uint16_t *l_keep = reinterpret_cast<uint16_t *>(b2_lds + b2_lds_dw(NP));  // [n_atiles][2][64] level-A bound of every lane's tile, per query
 
     // ---- the three lists: rows of both queries, of A only, of B only (every row of a query counts: a union bitmap has no classes)
     const uint2 *urec = p.pair_urec + (size_t)pair * p.pair_ustride;
@@ -174,7 +178,7 @@ __global__ __launch_bounds__(64, 2) void bounds2_kernel(Bounds2Params p) {
         if (!first) return;
 #pragma unroll
         for (int b = 0; b < NB; b++) load_unit<SHIFT>(buf[b], rsrc, first + (uint32_t)b * 8u * (uint32_t)R, grp, col);
-        const uint32_t *after_a = g_b ? l_b : l_zero, *after_both = g_a ? l_a : after_a;
+        const uint32_t *after_a = g_b ? l_b : nullptr, *after_both = g_a ? l_a : after_a;  // (nullptr: the last list of the level)
         if (g_both) {  // the rows both queries share are folded once, into A's planes while B's are empty, and copied
             fold_list<NP, 1, R, NB, SHIFT>(pa, pb, buf, l_both, g_both, after_both, grp, col, rsrc);
 #pragma unroll
@@ -183,7 +187,7 @@ __global__ __launch_bounds__(64, 2) void bounds2_kernel(Bounds2Params p) {
                 for (int b = 0; b < NP; b++) pb[w][b] = pa[w][b];
         }
         if (g_a) fold_list<NP, 1, R, NB, SHIFT>(pa, pb, buf, l_a, g_a, after_a, grp, col, rsrc);
-        if (g_b) fold_list<NP, 2, R, NB, SHIFT>(pa, pb, buf, l_b, g_b, l_zero, grp, col, rsrc);
+        if (g_b) fold_list<NP, 2, R, NB, SHIFT>(pa, pb, buf, l_b, g_b, nullptr, grp, col, rsrc);
         n_instr += (g_both + g_a + g_b) * 8u * (uint32_t)NB;
     };
 

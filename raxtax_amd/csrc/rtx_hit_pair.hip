@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "rtx_hit_common.hpp"
 
@@ -112,22 +113,25 @@ __global__ __launch_bounds__(64) void pair_union_kernel(const uint32_t *__restri
 // One segment of the row loop: `ng` groups of 32 rows of `list`, folded into both plane sets (MODE 0), A's (1) or B's (2).
 // On entry the four buffers hold (have requested) the first group; every buffer is requested again as soon as it has
 // been folded -- in the last group with the first rows of the NEXT segment (`next`), so that the three segments of a
-// wave run as one pipeline: the load latency is exposed once per wave, not once per list.
+// wave run as one pipeline: the load latency is exposed once per wave, not once per list.  The last segment of a block has no
+// next one (`next` = nullptr): its last group is folded by a copy of the body that requests nothing -- a wave-uniform choice
+// between two whole bodies, no branch around a load (the look-ahead used to re-request the zero row NB * 8 times per block).
 template <int NP, int MODE, int NB>
 __device__ __forceinline__ void fold_seg(uint32_t (&pa)[4][NP], uint32_t (&pb)[4][NP], uint4 (&buf)[NB][8], const uint32_t *list,
                                          uint32_t ng, const uint32_t *next, uint32_t lane, __amdgpu_buffer_rsrc_t rsrc,
                                          uint32_t voff) {
     static_assert(NB >= 2 && NB <= 4, "groups of 16, 24 or 32 rows");
     constexpr uint32_t GR = 8u * (uint32_t)NB;
-    for (uint32_t g = 0; g < ng; g++) {
-        const uint32_t *src = g + 1 < ng ? list + (g + 1) * GR : next;  // wave-uniform
-        const uint32_t idn = src[lane < GR ? lane : 0u];
+    auto group = [&](auto load_tag, const uint32_t *src) {
+        constexpr bool kLoad = decltype(load_tag)::value;
+        uint32_t idn = 0;
+        if constexpr (kLoad) idn = src[lane < GR ? lane : 0u];
         uint4 ca[NB], cb[NB];
 #pragma unroll
         for (int b = 0; b < NB; b++) {
             if (MODE != 2) ca[b] = tree8<NP>(pa, buf[b]);
             if (MODE != 1) cb[b] = tree8<NP>(pb, buf[b]);
-            load8v_at(buf[b], rsrc, voff, idn, b * 8);
+            if constexpr (kLoad) load8v_at(buf[b], rsrc, voff, idn, b * 8);
         }
         if (MODE != 2) {
             const uint4 c4a = csa_plane<NP, 3>(pa, ca[0], ca[1]);
@@ -145,7 +149,10 @@ __device__ __forceinline__ void fold_seg(uint32_t (&pa)[4][NP], uint32_t (&pb)[4
                 ripple4<NP, 5>(pb, csa_plane<NP, 4>(pb, c4a, c4b));
             }
         }
-    }
+    };
+    const uint32_t n_loop = next ? ng : ng - 1u;  // wave-uniform; ng >= 1: pair_tile_block calls with the lists that have a group
+    for (uint32_t g = 0; g < n_loop; g++) group(std::true_type{}, g + 1 < ng ? list + (g + 1) * GR : next);
+    if (!next) group(std::false_type{}, nullptr);
 }
 
 // One (pair, tile) block: the rows of the pair in this tile, then the epilogue of each query that is live there.
@@ -176,8 +183,10 @@ __device__ __forceinline__ void pair_tile_block(const HitParams &p, uint32_t *ld
     }
     uint32_t *l_both = lds_dw, *l_a = lds_dw + kPairListDw, *l_b = lds_dw + 2u * kPairListDw;
     unsigned long long *m_a = reinterpret_cast<unsigned long long *>(lds_dw + 3u * kPairListDw), *m_b = m_a + kPairMaskWords;
+    // eleven planes keep the look-ahead on the zero row behind the last list: there the second body costs ten spilled registers more
+    constexpr bool kLookAhead = NP > 10;
     uint32_t *l_zero = reinterpret_cast<uint32_t *>(m_b + kPairMaskWords);
-    if (lane < 32u) l_zero[lane] = p.zero_row << 10;
+    if (kLookAhead && lane < 32u) l_zero[lane] = p.zero_row << 10;
     uint32_t *l_sid = l_zero + 32;  // [2][kSparseIt * 64]
     const uint32_t col = tile * 1024u + lane * 16u;
     const bool active = col < p.stride_bytes;
@@ -278,7 +287,8 @@ __device__ __forceinline__ void pair_tile_block(const HitParams &p, uint32_t *ld
             const uint32_t idv = first[lane < GR ? lane : 0u];
 #pragma unroll
             for (int b = 0; b < NB; b++) load8v_at(buf[b], rsrc, voff, idv, b * 8);
-            const uint32_t *after_a = g_b ? l_b : l_zero, *after_both = g_a ? l_a : after_a;
+            const uint32_t *after_b = kLookAhead ? l_zero : nullptr;  // (nullptr: the last list of the block requests nothing behind its rows)
+            const uint32_t *after_a = g_b ? l_b : after_b, *after_both = g_a ? l_a : after_a;
             // the shared rows are folded ONCE, into A's planes while B's are still empty, and copied: every row of the
             // union costs one fold (first round only: later rounds -- t > kPairCap - 64 -- have no shared list)
             if (g_both) {
@@ -289,7 +299,7 @@ __device__ __forceinline__ void pair_tile_block(const HitParams &p, uint32_t *ld
                     for (int b = 0; b < NP; b++) pb[w][b] = pa[w][b];
             }
             if (g_a) fold_seg<NP, 1, NB>(pa, pb, buf, l_a, g_a, after_a, lane, rsrc, voff);
-            if (g_b) fold_seg<NP, 2, NB>(pa, pb, buf, l_b, g_b, l_zero, lane, rsrc, voff);
+            if (g_b) fold_seg<NP, 2, NB>(pa, pb, buf, l_b, g_b, after_b, lane, rsrc, voff);
         }
         wave_lds_sync();  // the lists are rewritten (next round) or become the histogram and the byte counters
         first_round = false;
