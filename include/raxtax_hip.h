@@ -52,7 +52,8 @@ extern "C" {
                                 setting that is off by default; and with sample demultiplexing, rtx_demux_* / rtx_index_set_tags /
                                 rtx_index_tags / rtx_raxtax_last_demux / rtx_raxtax_multi_ex7 and the per-sample counters
                                 rtx_index_profile_begin_samples / _read_samples / rtx_batch_prefetch_samples / rtx_sample_profile_merge /
-                                rtx_sample_table_format: the same) */
+                                rtx_sample_table_format: the same; and with the contaminant screen, rtx_screen_* / rtx_index_set_screen /
+                                rtx_index_screen / rtx_raxtax_last_screen / rtx_raxtax_multi_ex8: the same) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -805,6 +806,73 @@ int rtx_index_set_quality(rtx_index *index, const rtx_qual_params *params);
 int rtx_index_quality(const rtx_index *index, rtx_qual_params *params, int *on);
 int rtx_raxtax_last_qual(uint64_t *queries, uint64_t *passed, uint64_t *truncated, uint64_t reasons[7], double *busy_seconds);
 
+/* ---- contaminant screen (rtx_screen.hip; host_screen.cpp has the set and the host function; rtx_index_set_screen is the host mirror's use) ----
+ * The step that takes PhiX, organelle and vector reads out of an amplicon run (DADA2 `rm.phix`, `bbduk`) on the device: the 16-mers of a read
+ * looked up in a set of canonical 16-mers.  Exact integers; the host function, the x86 emulator and the device agree bit for bit.
+ *   window       RTX_SCREEN_K = 16.  A window at position p of a range is VALID iff its 16 codes are each one of 1, 2, 4, 8 (the parsers'
+ *                4-bit codes); anything else -- IUPAC unions, 0 -- breaks every window it lies in.  Its value w is the 32-bit word of the
+ *                2-bit codes A 0, C 1, G 2, T 3, the first base in the most significant bits, as the classifier packs its 8-mers.  rc(w)
+ *                is the value of the reverse complement: its base j is 3 - base 15 - j.  The CANONICAL value is c = min(w, rc(w)).  No
+ *                canonical value is 0xFFFFFFFF (rc of sixteen T is 0): that word marks an empty slot.
+ *   set          from n contaminant sequences, bases / base_off like references: S, the distinct canonical values of all their valid
+ *                windows; src(c), the lowest index of a sequence that holds c.  RTX_ERR_INVALID: a base_off that is not monotone, more
+ *                than RTX_SCREEN_MAX_BASES bases in total (checked from base_off before a base is read), no valid window at all.
+ *   table        m slots {key, src}, m the smallest power of two with m >= 2 |S| and m >= 1024.  The home slot of c is
+ *                h(c) = (uint32)(c * 0x9E3779B1) >> (32 - log2 m); the keys are inserted in ascending order of c with linear probing
+ *                modulo m; a lookup walks from h(c) until it finds c or an empty slot.  rtx_screen_set_info: |S|, m, the longest
+ *                displacement of a stored key, the number of keys stored below their home slot (their chain wrapped), and a 64-bit
+ *                fingerprint of the keys and their sources (any pointer may be NULL).  rtx_screen_set_table hands the slots out.
+ *   parameters   min_hits (default 2, at least 1), min_pct (default 50, 0 .. 100); RTX_ERR_INVALID otherwise.
+ *   per read     over the input range [lo, hi) -- the whole read, or what primers and quality kept: windows, the number of valid windows;
+ *                hits, the number of valid windows whose canonical value is in S (positions are counted, not distinct values); first,
+ *                the position, counted from lo, of the hitting window at the lowest position, RTX_SCREEN_NONE without one; source, src
+ *                of that window, or RTX_SCREEN_NONE; verdict, RTX_SCREEN_CONTAMINANT iff hits >= min_hits and
+ *                100 * hits >= min_pct * windows (compared in 64 bits), 0 otherwise.  A range shorter than 16 has windows = hits = 0 and
+ *                passes.  Never depends on the rest of the batch, nor on the orientation in which the read is given (first and source
+ *                speak of the read as given).
+ *   rtx_screen_set_build  the set as an immutable host object holding the table, built on the host (at most 2^26 keys are sorted).
+ *   rtx_screen_create  an object of its own on GPU `device` like rtx_qual: one stream, its own buffers (they only grow), the table uploaded
+ *                once; the set may be freed afterwards.  Checked in this order: null arguments, the parameters (RTX_ERR_INVALID), the
+ *                device (RTX_ERR_NO_DEVICE without a gfx950).
+ *   rtx_screen_run    windows / hits / first / source / verdict of n reads, [n] each; bases / base_off as rtx_batch_prefetch takes them;
+ *                lo_in / hi_in [n] or both NULL (whole reads).  One byte per base of the ranges travels to the device and an offset and a
+ *                length per read.  n == 0: RTX_OK; RTX_ERR_INVALID: a base_off that is not monotone, a range outside its read, a read of
+ *                more than RTX_SCREEN_MAX_READ bases.  Synchronous; calls on one object are serialised by the caller.
+ *   rtx_screen_stage_times  seconds of the last rtx_screen_run: the host's staging pass, the copies and the wait around the kernel, all of it.
+ *   rtx_screen_read   the same for ONE read on the host (no device), with the functions the kernel calls.
+ *   rtx_index_set_screen  the screen rtx_raxtax* run every read through (NULL set, the default: off -- no new code runs, nothing is
+ *                allocated, every output is what it is without).  The handle keeps what it needs: the caller may free the set.  Like the
+ *                primers and the quality filter honoured by the mirror alone, shapes no workspace; the handles of one call must hold
+ *                the same set and parameters (a 64-bit fingerprint of the keys and the two parameters is compared): RTX_ERR_INVALID
+ *                otherwise.  The stage runs behind the quality filter, on the range primers and quality kept, and in front of the
+ *                dereplication.  rtx_index_screen: the parameters, whether it is on, and that fingerprint (0 when off).
+ *   rtx_raxtax_last_screen  see rtx_raxtax_multi_ex8. */
+#define RTX_SCREEN_K 16u
+#define RTX_SCREEN_NONE 0xFFFFFFFFu
+#define RTX_SCREEN_MAX_READ (1u << 20)
+#define RTX_SCREEN_MAX_BASES (1ull << 26)
+#define RTX_SCREEN_CONTAMINANT 1u
+typedef struct {
+    uint32_t min_hits, min_pct;
+} rtx_screen_params;
+typedef struct rtx_screen_set rtx_screen_set;
+typedef struct rtx_screen rtx_screen;
+int rtx_screen_set_build(uint64_t n_seqs, const uint8_t *bases, const uint64_t *base_off /*[n_seqs + 1]*/, rtx_screen_set **out);
+void rtx_screen_set_free(rtx_screen_set *set);
+int rtx_screen_set_info(const rtx_screen_set *set, uint64_t *n_keys, uint64_t *n_slots, uint64_t *max_displacement, uint64_t *n_wrapped, uint64_t *fingerprint);
+int rtx_screen_set_table(const rtx_screen_set *set, const uint32_t **slots /*[2 m]: key, src per slot; valid as long as the set*/, uint32_t *log2m);
+int rtx_screen_create(int device, const rtx_screen_set *set, const rtx_screen_params *params, rtx_screen **out);
+int rtx_screen_run(rtx_screen *s, uint64_t n, const uint8_t *bases, const uint64_t *base_off, const uint32_t *lo_in /*[n] or NULL*/,
+                   const uint32_t *hi_in /*[n] or NULL*/, uint32_t *windows /*[n]*/, uint32_t *hits /*[n]*/, uint32_t *first /*[n]*/,
+                   uint32_t *source /*[n]*/, uint32_t *verdict /*[n]*/);
+void rtx_screen_destroy(rtx_screen *s);
+int rtx_screen_kernel_time(const rtx_screen *s, float *ms); /* milliseconds of the kernel of the last rtx_screen_run, from HIP events around it */
+int rtx_screen_stage_times(const rtx_screen *s, double seconds[3]);
+int rtx_screen_read(const rtx_screen_set *set, const rtx_screen_params *params, const uint8_t *bases, uint64_t len, uint32_t lo, uint32_t hi,
+                    uint32_t *windows, uint32_t *hits, uint32_t *first, uint32_t *source, uint32_t *verdict);
+int rtx_index_set_screen(rtx_index *index, const rtx_screen_set *set, const rtx_screen_params *params);
+int rtx_index_screen(const rtx_index *index, rtx_screen_params *params, int *on, uint64_t *fingerprint);
+
 /* ---- paired-end merging (rtx_merge.hip; host_merge.cpp has the host function) ---------------------------------------------------------------
  * The first step of an amplicon pipeline (`vsearch --fastq_mergepairs`, PEAR, DADA2 `mergePairs`) on the device: the two mates of a pair
  * overlapped into one read.  Exact integers, no tolerance anywhere; the host function, the x86 emulator and the device agree bit for bit.
@@ -1233,6 +1301,22 @@ int rtx_raxtax_multi_ex7(rtx_index *const *indices, uint32_t n_indices, const rt
 /* The last rtx_raxtax* call of the process: its queries, those assigned to a sample, the queries of every verdict (reasons[v], v =
  * RTX_DEMUX_OK .. RTX_DEMUX_UNKNOWN_PAIR) and the busy seconds of the stage; all 0 when its handles had no tags set. */
 int rtx_raxtax_last_demux(uint64_t *queries, uint64_t *assigned, uint64_t reasons[5], double *busy_seconds);
+/* rtx_raxtax_multi_ex7 with a callback for the contaminant screen (rtx_index_set_screen on the handles, which must hold the same set and
+ * parameters: RTX_ERR_INVALID otherwise): called for EVERY query of the caller, in input order, directly after its `qual` callback and
+ * before `chimera`, with what rtx_screen_run says of the range that primers and quality left.  A contaminant is classified as the empty
+ * read, exactly as one the quality filter discards: reported, not classified, no message, no align callback, not counted by an open
+ * profile, not offered to dereplication or the chimera check.  Per query of the caller also under RTX_OPT_DEREP.  With no screen set:
+ * 0, 0, RTX_SCREEN_NONE, RTX_SCREEN_NONE, 0.  The stage needs no quality strings.  Any callback may be NULL. */
+typedef int (*rtx_query_screen_fn)(void *ctx, const char *label, uint32_t windows, uint32_t hits, uint32_t first, uint32_t source, uint32_t verdict);
+int rtx_raxtax_multi_ex8(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                         const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                         int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                         rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                         rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx, rtx_query_demux_fn demux,
+                         void *demux_ctx, rtx_query_screen_fn screen, void *screen_ctx);
+/* The last rtx_raxtax* call of the process: its queries, those whose range was not already empty when the screen saw it, the
+ * contaminants among them, and the busy seconds of the stage; all 0 when its handles had no screen set. */
+int rtx_raxtax_last_screen(uint64_t *queries, uint64_t *screened, uint64_t *contaminants, double *busy_seconds);
 /* A ready-made sender that discards the messages and only counts them: ctx = NULL or uint64_t[2] {messages, bytes of text} */
 int rtx_sender_discard(void *ctx, const char *label, const char *out_lines, const char *tsv_lines);
 /* Busy seconds of the stages of the last rtx_raxtax / rtx_raxtax_multi call of this process (which stage bounds an end-to-end run):

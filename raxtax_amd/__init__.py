@@ -15,6 +15,7 @@ from .api import (EvaluationResult, Index, Result, Tree, parse_query_fasta_str, 
                   QC_BAD_QUALITY, QC_SHORT_FOR_TRUNC_LEN, QC_TOO_SHORT, QC_TOO_LONG, QC_TOO_MANY_N, QC_MAX_EE, QC_MAX_EE_RATE,
                   Merge, MergeParams, merge_pair, merge_queries, merge_verdict_names, fastq_text, fastq_block_end_n, MERGE_MAX_READ,
                   MG_BAD_QUALITY, MG_TOO_LONG, MG_TOO_SHORT, MG_NO_OVERLAP,
+                  Screen, ScreenSet, ScreenParams, screen_read, raxtax_last_screen, SCREEN_K, SCREEN_NONE, SCREEN_MAX_READ, SCREEN_MAX_BASES, SCREEN_CONTAMINANT,
                   Chimera, ChimeraParams, chimera_read, raxtax_last_chimera, CHIMERA_DTYPE, CHIMERA_MAX_QUERY, CHIM_OK, CHIM_NO_KMER, CHIM_TOO_LONG)
 from ._lib import (RTX_RAW_CONFIDENCE, RTX_SKIP_EXACT_MATCHES, RtxError)  # noqa: F401
 
@@ -27,4 +28,5 @@ __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last
            "QUAL_MAX_READ", "QC_BAD_QUALITY", "QC_SHORT_FOR_TRUNC_LEN", "QC_TOO_SHORT", "QC_TOO_LONG", "QC_TOO_MANY_N", "QC_MAX_EE", "QC_MAX_EE_RATE",
            "Merge", "MergeParams", "merge_pair", "merge_queries", "merge_verdict_names", "fastq_text", "fastq_block_end_n", "MERGE_MAX_READ",
            "MG_BAD_QUALITY", "MG_TOO_LONG", "MG_TOO_SHORT", "MG_NO_OVERLAP",
+           "Screen", "ScreenSet", "ScreenParams", "screen_read", "raxtax_last_screen", "SCREEN_K", "SCREEN_NONE", "SCREEN_MAX_READ", "SCREEN_MAX_BASES", "SCREEN_CONTAMINANT",
            "Chimera", "ChimeraParams", "chimera_read", "raxtax_last_chimera", "CHIMERA_DTYPE", "CHIMERA_MAX_QUERY", "CHIM_OK", "CHIM_NO_KMER", "CHIM_TOO_LONG"]

@@ -36,6 +36,8 @@ RTX_DEMUX_NAMES = ("ok", "no_tag5", "no_tag3", "ambiguous", "unknown_pair")   # 
 RTX_QUAL_MAX_READ, RTX_QUAL_TABLE = 1 << 20, 94
 RTX_QC_NAMES = ("bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate")   # bit b of a verdict: RTX_QC_*
 
+RTX_SCREEN_K, RTX_SCREEN_NONE, RTX_SCREEN_MAX_READ, RTX_SCREEN_MAX_BASES, RTX_SCREEN_CONTAMINANT = 16, 0xFFFFFFFF, 1 << 20, 1 << 26, 1
+
 RTX_MERGE_MAX_READ, RTX_MERGE_MISMATCH_COST = 1024, 5
 RTX_MG_NAMES = ("bad_quality", "too_long", "too_short", "no_overlap")   # bit b of a verdict: RTX_MG_* (a verdict holds one reason)
 
@@ -95,6 +97,10 @@ class DemuxParams(C.Structure):   # rtx_demux_params
 class QualParams(C.Structure):   # rtx_qual_params
     _fields_ = [("ascii_base", C.c_uint32), ("trunc_len", C.c_uint32), ("trunc_qual", C.c_int32), ("trunc_ee", C.c_double), ("min_len", C.c_uint32),
                 ("max_len", C.c_uint32), ("max_ns", C.c_int32), ("max_ee", C.c_double), ("max_ee_rate", C.c_double)]
+
+
+class ScreenParams(C.Structure):   # rtx_screen_params
+    _fields_ = [("min_hits", C.c_uint32), ("min_pct", C.c_uint32)]
 
 
 class MergeParams(C.Structure):   # rtx_merge_params
@@ -275,6 +281,20 @@ _SIGNATURES = {
     "rtx_index_quality": (C.c_int, [C.c_void_p, C.POINTER(QualParams), C.POINTER(C.c_int)]),
     "rtx_raxtax_last_qual": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_raxtax_multi_ex5": (C.c_int, None),
+    "rtx_screen_set_build": (C.c_int, [C.c_uint64, u8p, u64p, C.POINTER(C.c_void_p)]),
+    "rtx_screen_set_free": (None, [C.c_void_p]),
+    "rtx_screen_set_info": (C.c_int, [C.c_void_p, u64p, u64p, u64p, u64p, u64p]),
+    "rtx_screen_set_table": (C.c_int, [C.c_void_p, C.POINTER(u32p), u32p]),
+    "rtx_screen_create": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(ScreenParams), C.POINTER(C.c_void_p)]),
+    "rtx_screen_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u32p, u32p, u32p, u32p, u32p, u32p]),
+    "rtx_screen_destroy": (None, [C.c_void_p]),
+    "rtx_screen_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "rtx_screen_stage_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rtx_screen_read": (C.c_int, [C.c_void_p, C.POINTER(ScreenParams), u8p, C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p, u32p]),
+    "rtx_index_set_screen": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(ScreenParams)]),
+    "rtx_index_screen": (C.c_int, [C.c_void_p, C.POINTER(ScreenParams), C.POINTER(C.c_int), u64p]),
+    "rtx_raxtax_multi_ex8": (C.c_int, None),
+    "rtx_raxtax_last_screen": (C.c_int, [u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_merge_create": (C.c_int, [C.c_int, C.POINTER(MergeParams), C.POINTER(C.c_void_p)]),
     "rtx_merge_run": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u8p, u64p, u8p, u8p, u64p, u32p, u32p, u32p, u32p, u64p, u8p, u8p, C.c_uint64]),
     "rtx_merge_destroy": (None, [C.c_void_p]),

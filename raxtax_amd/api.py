@@ -361,7 +361,7 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None, tags=None):
+                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None, tags=None, contaminants=None):
         self._lib = _lib.load()
         self.tree = tree
         if segment_classes is None:
@@ -430,8 +430,25 @@ class Index:
             self.set_quality(quality)
         if chimera is not None:   # rtx_index_set_chimera: raxtax() checks every read against the references first (rtx_chimera.hip); classify() ignores it
             self.set_chimera(ChimeraParams() if chimera is True else chimera)
+        if contaminants is not None:   # rtx_index_set_screen: raxtax() screens every read against the set first (rtx_screen.hip); classify() ignores it
+            self.set_screen(*(contaminants if isinstance(contaminants, tuple) else (contaminants,)))
         self._view = ResultView()
         self._keep = None
+
+    def set_screen(self, sset, params=None) -> None:
+        """rtx_index_set_screen: the ScreenSet and ScreenParams raxtax() screens every read with; None switches the stage off.  The handle
+        keeps what it needs of the set."""
+        if sset is None:
+            check(self._lib.rtx_index_set_screen(self._h, None, None))
+        else:
+            check(self._lib.rtx_index_set_screen(self._h, sset._h, C.byref((params or ScreenParams())._c())))
+
+    @property
+    def screen(self):
+        """(ScreenParams, fingerprint of the keys and the parameters) the handle holds, or None (rtx_index_screen)."""
+        c, on, fp = _lib.ScreenParams(), C.c_int(), C.c_uint64()
+        check(self._lib.rtx_index_screen(self._h, C.byref(c), C.byref(on), C.byref(fp)))
+        return (ScreenParams(c.min_hits, c.min_pct), int(fp.value)) if on.value else None
 
     def set_quality(self, params) -> None:
         """rtx_index_set_quality: the QualParams raxtax() filters every read with (its queries then come with quality strings); None, or
@@ -1285,6 +1302,143 @@ def raxtax_last_qual() -> Tuple[int, int, int, List[int], float]:
     return int(a.value), int(b.value), int(c.value), [int(x) for x in r], float(s.value)
 
 
+_SCREEN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32)
+SCREEN_K, SCREEN_NONE, SCREEN_MAX_READ, SCREEN_MAX_BASES, SCREEN_CONTAMINANT = (_lib.RTX_SCREEN_K, _lib.RTX_SCREEN_NONE, _lib.RTX_SCREEN_MAX_READ, _lib.RTX_SCREEN_MAX_BASES,
+                                                                                 _lib.RTX_SCREEN_CONTAMINANT)
+
+
+@dataclass
+class ScreenParams:
+    """The contaminant screen's parameters (rtx_screen_params): a read is a contaminant iff at least min_hits of its valid 16-base windows
+    are in the set and they are at least min_pct percent of its valid windows."""
+    min_hits: int = 2
+    min_pct: int = 50
+
+    def _c(self) -> "_lib.ScreenParams":
+        return _lib.ScreenParams(int(self.min_hits), int(self.min_pct))
+
+
+class ScreenSet:
+    """The canonical 16-mers of contaminant sequences as the table the device probes (rtx_screen_set): built on the host from FASTA text
+    (read with the query parser: the labels need no lineage), from (label, bases) records or from plain code arrays.  Immutable."""
+
+    def __init__(self, records_or_fasta_text):
+        self._lib = _lib.load()
+        self._h = None
+        if isinstance(records_or_fasta_text, (str, bytes)):
+            records_or_fasta_text = parse_query_fasta_str(records_or_fasta_text)
+        recs = [r if isinstance(r, tuple) else ("", r) for r in records_or_fasta_text]
+        self.labels = [r[0] for r in recs]
+        flat, off = _flatten([np.ascontiguousarray(r[1], dtype=np.uint8) for r in recs])
+        self._build(flat, off)
+
+    @classmethod
+    def from_arrays(cls, bases: np.ndarray, base_off: np.ndarray, labels=None) -> "ScreenSet":
+        """The set of the sequences bases[base_off[i] : base_off[i + 1]] (rtx_screen_set_build as it stands)."""
+        self = cls.__new__(cls)
+        self._lib = _lib.load()
+        self._h = None
+        self.labels = list(labels) if labels is not None else [""] * (len(base_off) - 1)
+        self._build(np.ascontiguousarray(bases, dtype=np.uint8), np.ascontiguousarray(base_off, dtype=np.uint64))
+        return self
+
+    def _build(self, flat, off):
+        h = C.c_void_p()
+        check(self._lib.rtx_screen_set_build(len(off) - 1, ptr(flat if len(flat) else np.zeros(1, np.uint8), u8p), ptr(off, u64p), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_screen_set_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def info(self) -> dict:
+        """rtx_screen_set_info: the number of keys, the slots of the table, the longest displacement of a stored key, the keys stored below
+        their home slot (their chain wrapped) and the fingerprint of the keys."""
+        v = [C.c_uint64() for _ in range(5)]
+        check(self._lib.rtx_screen_set_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("keys", "slots", "max_displacement", "wrapped", "fingerprint"), (int(x.value) for x in v)))
+
+    def table(self) -> Tuple[np.ndarray, int]:
+        """rtx_screen_set_table: (the slots as [m, 2] uint32 -- key, src -- and log2 m)."""
+        p, lg = u32p(), C.c_uint32()
+        check(self._lib.rtx_screen_set_table(self._h, C.byref(p), C.byref(lg)))
+        return np.ctypeslib.as_array(p, shape=(1 << lg.value, 2)).copy(), int(lg.value)
+
+
+def screen_read(sset: ScreenSet, params: ScreenParams, bases: np.ndarray, lo: int = 0, hi: Optional[int] = None) -> Tuple[int, int, int, int, int]:
+    """rtx_screen_read: (windows, hits, first, source, verdict) of ONE read on the host, with the functions the device kernel calls; [lo, hi)
+    is the input range (the whole read by default), first counts from lo."""
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    one = np.zeros(1, np.uint8)
+    v = [C.c_uint32() for _ in range(5)]
+    check(_lib.load().rtx_screen_read(sset._h, C.byref(params._c()), ptr(bases if len(bases) else one, u8p), len(bases), int(lo),
+                                      len(bases) if hi is None else int(hi), *[C.byref(x) for x in v]))
+    return tuple(int(x.value) for x in v)
+
+
+class Screen:
+    """The contaminant-screen stage on one GPU (rtx_screen): an object of its own beside any Index, one stream, buffers that only grow,
+    the table of the set uploaded once."""
+
+    def __init__(self, device: int, sset: ScreenSet, params: Optional[ScreenParams] = None):
+        self._lib = _lib.load()
+        self._h = None
+        h = C.c_void_p()
+        check(self._lib.rtx_screen_create(device, sset._h, C.byref((params or ScreenParams())._c()), C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_screen_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def run(self, bases: np.ndarray, base_off: np.ndarray, lo=None, hi=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(windows, hits, first, source, verdict) per read (rtx_screen_run) over [lo, hi) -- the whole read by default; first counts from lo."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+        if (lo is None) != (hi is None):
+            raise ValueError("Screen.run: give both lo and hi, or neither")
+        n = len(base_off) - 1
+        out = [np.zeros(max(n, 1), dtype=np.uint32) for _ in range(5)]
+        if lo is not None:
+            lo = np.ascontiguousarray(lo, dtype=np.uint32)
+            hi = np.ascontiguousarray(hi, dtype=np.uint32)
+            if len(lo) != n or len(hi) != n:
+                raise ValueError(f"{len(lo)} / {len(hi)} ranges for {n} reads")
+            if n == 0:
+                lo = hi = np.zeros(1, np.uint32)
+        check(self._lib.rtx_screen_run(self._h, n, ptr(bases if len(bases) else np.zeros(1, np.uint8), u8p), ptr(base_off, u64p),
+                                       ptr(lo, u32p) if lo is not None else None, ptr(hi, u32p) if hi is not None else None, *[ptr(a, u32p) for a in out]))
+        return tuple(a[:n] for a in out)
+
+    def kernel_ms(self) -> float:
+        """Milliseconds of the kernel of the last run(), from HIP events (rtx_screen_kernel_time)."""
+        ms = C.c_float()
+        check(self._lib.rtx_screen_kernel_time(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def stage_seconds(self) -> Tuple[float, float, float]:
+        """(host staging, copies and waiting around the kernel, the whole call) of the last run(), in seconds (rtx_screen_stage_times)."""
+        t = (C.c_double * 3)()
+        check(self._lib.rtx_screen_stage_times(self._h, t))
+        return float(t[0]), float(t[1]), float(t[2])
+
+
+def raxtax_last_screen() -> Tuple[int, int, int, float]:
+    """rtx_raxtax_last_screen: (queries, those whose range was not already empty, the contaminants among them, busy seconds of the stage)
+    of the last raxtax() call of this process; all 0 when its handles had no screen set."""
+    a, b, c, s = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    check(_lib.load().rtx_raxtax_last_screen(C.byref(a), C.byref(b), C.byref(c), C.byref(s)))
+    return int(a.value), int(b.value), int(c.value), float(s.value)
+
+
 _CHIM = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_char_p, C.POINTER(_lib.ChimeraRec))
 CHIMERA_MAX_QUERY = _lib.RTX_CHIMERA_MAX_QUERY
 CHIM_OK, CHIM_NO_KMER, CHIM_TOO_LONG = _lib.RTX_CHIM_OK, _lib.RTX_CHIM_NO_KMER, _lib.RTX_CHIM_TOO_LONG
@@ -1531,7 +1685,8 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
            quals: Optional[Sequence[np.ndarray]] = None,
            qual: Optional[Callable[[str, int, int, int, int, int], None]] = None,
            chimera: Optional[Callable[[str, np.void], None]] = None,
-           demux: Optional[Callable[[str, int, int, int, int, int, int], None]] = None) -> None:
+           demux: Optional[Callable[[str, int, int, int, int, int, int], None]] = None,
+           screen: Optional[Callable[[str, int, int, int, int, int], None]] = None) -> None:
     """src/raxtax.rs:14-22 -- same arguments; `tree` is the device Index built from the Tree, or a list of them (one per GPU,
     all built from the same Tree): rtx_raxtax_multi then deals the chunks to the handles, one driving thread each.
     `sender(label, out_lines, tsv_lines_or_None)` is called once per query, in input order; raising from it
@@ -1551,14 +1706,18 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     read.  It goes with `align`, `trim`, `qual` or alone.
     `demux(label, raw_len, sample, lo, hi, hit, info)` is called for every query directly before `trim` (rtx_raxtax_multi_ex7; handles built with
     tags=(tags, pairs, params): the read belongs to `sample` (DEMUX_NONE: to none) and kept [lo, hi) of its raw_len bases; hit and info as
-    demux_hit() takes them apart).  The callbacks behind it then speak of the cut read.  It goes with `align`, `trim`, `qual`, `chimera` or alone."""
+    demux_hit() takes them apart).  The callbacks behind it then speak of the cut read.  It goes with `align`, `trim`, `qual`, `chimera` or alone.
+    `screen(label, windows, hits, first, source, verdict)` is called for every query directly after `qual` and before `chimera`
+    (rtx_raxtax_multi_ex8; handles built with contaminants=(ScreenSet, ScreenParams), else 0, 0, SCREEN_NONE, SCREEN_NONE, 0): what the
+    contaminant screen said of the range primers and quality kept; a contaminant is classified as the empty read.  It goes with the same."""
     lib = _lib.load()
     common = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_uint64, C.POINTER(C.c_char_p), u8p, u64p, C.c_int, C.c_int, C.c_uint64, _SENDER, C.c_void_p, C.c_int]
     lib.rtx_raxtax_multi_ex7.argtypes = common + [_ALIGN, C.c_void_p, _TRIM, C.c_void_p, u8p, _QUAL, C.c_void_p, _CHIM, C.c_void_p, _DEMUX, C.c_void_p]
+    lib.rtx_raxtax_multi_ex8.argtypes = lib.rtx_raxtax_multi_ex7.argtypes + [_SCREEN, C.c_void_p]
     if (info is not None) + (hit is not None) + (align is not None) > 1:
         raise ValueError("raxtax: give one of info, hit and align")
-    if (trim is not None or qual is not None or chimera is not None or demux is not None) and (info is not None or hit is not None):
-        raise ValueError("raxtax: trim, qual, chimera and demux go with align or alone")
+    if (trim is not None or qual is not None or chimera is not None or demux is not None or screen is not None) and (info is not None or hit is not None):
+        raise ValueError("raxtax: trim, qual, chimera, demux and screen go with align or alone")
     if quals is None and info is None and hit is None and len(queries) and all(len(q) == 3 for q in queries):
         quals = [q[2] for q in queries]   # (info and hit are the callbacks of calls that carried no quality strings: triples are then read as pairs)
     if quals is not None and (info is not None or hit is not None):
@@ -1593,13 +1752,13 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     elif hit is not None:
         align = lambda label, strand, peak, t, nearest, ties, *_: hit(label, strand, peak, t, nearest, ties)  # noqa: E731
     arr = (C.c_void_p * len(handles))(*[h._h.value for h in handles])
-    rc = lib.rtx_raxtax_multi_ex7(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
+    rc = lib.rtx_raxtax_multi_ex8(arr, len(handles), handles[0].tree._h, len(queries), labels, ptr(flat, u8p), ptr(off, u64p),
                                   int(skip_exact_matches), int(raw_confidence), chunk_size,
                                   guarded(_SENDER, sender, lambda out, tsv_lines: (out.decode(), tsv_lines.decode() if tsv_lines is not None else None)), None, int(tsv),
                                   guarded(_ALIGN, align), None, guarded(_TRIM, trim), None, ptr(flat_q, u8p) if flat_q is not None else None,
                                   guarded(_QUAL, qual), None,
                                   guarded(_CHIM, chimera, lambda rec: [np.array([tuple(getattr(rec.contents, f) for f in _lib.RTX_CHIM_FIELDS)], CHIMERA_DTYPE)[0]]), None,
-                                  guarded(_DEMUX, demux), None)
+                                  guarded(_DEMUX, demux), None, guarded(_SCREEN, screen), None)
     if err:
         raise err[0]
     check(rc)

@@ -41,6 +41,12 @@
 //    dereplication and classification see merged reads; a pair that is not merged is the empty read: no result lines.  PREFIX/raxtax.merge: a
 //    header, then label, forward length, reverse length, overlap, diffs, merged length and verdict (`merged`, or the reason it was not) per
 //    pair in input order; the totals go to the log.  --reverse with FASTA input, or a merge option without --reverse, is refused.)
+//   (--contaminants FILE[.gz] [--contam-minhits N] [--contam-minpct P]: every read is screened against the 16-mers of the FASTA records of FILE on
+//    the device before it is classified (rtx_index_set_screen, rtx_screen.hip; behind primers and quality filter, in front of --derep): a read
+//    with at least N (2) of its 16-base windows in the set, and at least P (50) percent of them, is a contaminant and has no result lines, like a
+//    read the quality filter discards.  PREFIX/raxtax.screen: a header, then label, the length of the screened range, its valid windows, the
+//    hits, the position of the first hit or -, the record of FILE that holds it (its label up to the first blank) or -, pass or contaminant,
+//    one line per read in input order.  FASTA and FASTQ input alike.)
 //   (--chimera [--chimera-mindelta N] [--chimera-segments S]: every read is checked against the references on the device before it is classified
 //    (rtx_index_set_chimera, rtx_chimera.hip; behind --derep, so a distinct read is checked once): the best pair of references over a left and
 //    a right part of the read against the best single reference, at S - 1 breakpoints (S = 2 .. 32, default 16); a read whose pair explains N
@@ -161,7 +167,7 @@ std::string fingerprint(const std::string &path) {
 // (... and --primers with its two settings, as given: trimmed reads are other reads)
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
                             const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string(),
-                            const std::string &chimera = std::string(), const std::string &tags = std::string()) {
+                            const std::string &chimera = std::string(), const std::string &tags = std::string(), const std::string &contaminants = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
@@ -172,6 +178,7 @@ std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv
     if (!merge.empty()) ss << ",\n  \"merge\": \"" << merge << "\"";  // (... and --reverse with the merge settings: merged reads are other reads)
     if (!chimera.empty()) ss << ",\n  \"chimera\": \"" << chimera << "\"";  // (... and --chimera with its two settings: flagged reads have no lines)
     if (!tags.empty()) ss << ",\n  \"tags\": \"" << tags << "\"";  // (... and --tags with its settings: demultiplexed reads are other reads)
+    if (!contaminants.empty()) ss << ",\n  \"contaminants\": \"" << contaminants << "\"";  // (... and --contaminants with its settings and the set's fingerprint: contaminants have no lines)
     ss << "\n}\n";
     return ss.str();
 }
@@ -210,7 +217,10 @@ uint8_t iupac_code(char ch) {
 }
 
 struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera, demux;
+    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera, demux, screen;
+    bool want_qc = false;                                    // the quality filter is on (raxtax.qc); its callback also serves --contaminants:
+    uint32_t screen_len = 0;                                 // the length of the range the screen was given, of the query whose callbacks are running
+    const std::vector<std::string> *contam_names = nullptr;  // --contaminants: the records of the file (raxtax.screen)
     const std::vector<std::string> *sample_names = nullptr;  // --tags: the samples of the sheet (raxtax.demux)
     bool want_tsv = false, want_strand = false, want_hits = false;
     const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
@@ -246,6 +256,9 @@ int main(int argc, char **argv) {
     bool chim_on = false;                                              // --chimera: rtx_index_set_chimera on every handle, PREFIX/raxtax.chimera
     rtx_chimera_params chim{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA};  // --chimera-segments, --chimera-mindelta
     std::string chim_opts;                                             // those two as given (empty: none)
+    std::string contam_file;                                           // --contaminants FILE: rtx_index_set_screen on every handle, PREFIX/raxtax.screen
+    rtx_screen_params contam{2u, 50u};                                 // --contam-minhits N, --contam-minpct P
+    std::string contam_opts;                                           // those two as given (empty: none)
     std::string tags_file;                                             // --tags SHEET: rtx_index_set_tags on every handle, PREFIX/raxtax.demux (and raxtax.samples with --profile)
     rtx_demux_params tag_params{0u, 0u};                               // --tag-mismatches N, --tag-offset N
     bool tags_both = false;                                            // --tags-both-orientations
@@ -360,6 +373,16 @@ int main(int argc, char **argv) {
             (a == "--chimera-segments" ? chim.segments : chim.mindelta) = (uint32_t)x;
             chim_opts += (chim_opts.empty() ? "" : " ") + a;
         }
+        else if (a == "--contaminants") contam_file = val();
+        else if (a == "--contam-minhits" || a == "--contam-minpct") {
+            const char *v = val();
+            char *end = nullptr;
+            const long x = strtol(v, &end, 10);
+            const long least = a == "--contam-minhits" ? 1 : 0, most = a == "--contam-minhits" ? 0x7FFFFFFFl : 100;
+            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
+            (a == "--contam-minhits" ? contam.min_hits : contam.min_pct) = (uint32_t)x;
+            contam_opts += (contam_opts.empty() ? "" : " ") + a;
+        }
         else if (a == "--tags") tags_file = val();
         else if (a == "--tags-both-orientations") { tags_both = true; tag_opts += (tag_opts.empty() ? "" : " ") + a; }
         else if (a == "--tag-mismatches" || a == "--tag-offset") {
@@ -383,7 +406,7 @@ int main(int argc, char **argv) {
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -536,7 +559,39 @@ int main(int argc, char **argv) {
         }
         tag_spec = fingerprint(tags_file) + ";mismatches=" + std::to_string(tag_params.max_mismatches) + ";offset=" + std::to_string(tag_params.max_offset) + ";both=" + (tags_both ? "1" : "0");
     }
-    const std::string demux_path = prefix + "/raxtax.demux", samples_path = prefix + "/raxtax.samples";
+    // --contaminants: the set, built here as well -- before the database is read and any device is touched
+    const bool screen_on = !contam_file.empty();
+    if (!contam_opts.empty() && !screen_on) { fprintf(stderr, "raxtax-hip: %s sets how reads are screened and needs --contaminants FILE\n", contam_opts.c_str()); return 64; }
+    rtx_screen_set *contam_set = nullptr;
+    std::vector<std::string> contam_names;
+    std::string contam_spec;
+    if (screen_on) {
+        std::string text;
+        if (!slurp(contam_file, text)) { fprintf(stderr, "raxtax-hip: --contaminants: cannot read %s\n", contam_file.c_str()); return 66; }
+        rtx_queries *cq = nullptr;  // (the query parser: the labels need no lineage)
+        if (rtx_queries_parse_fasta(text.data(), text.size(), nullptr, 0, &cq) != RTX_OK) { fprintf(stderr, "raxtax-hip: --contaminants: %s: %s\n", contam_file.c_str(), rtx_last_error()); return 66; }
+        const uint8_t *cb = nullptr;
+        const uint64_t *co = nullptr;
+        rtx_queries_data(cq, &cb, &co);
+        const uint64_t nc = rtx_queries_len(cq);
+        for (uint64_t i = 0; i < nc; i++) {
+            const std::string label = rtx_queries_label(cq, i);
+            contam_names.push_back(label.substr(0, label.find_first_of(" \t")));
+        }
+        uint64_t keys = 0, slots = 0, fp = 0;
+        const int brc = rtx_screen_set_build(nc, cb, co, &contam_set);
+        rtx_queries_destroy(cq);
+        if (brc != RTX_OK || rtx_screen_set_info(contam_set, &keys, &slots, nullptr, nullptr, &fp) != RTX_OK) {
+            fprintf(stderr, "raxtax-hip: --contaminants: %s: %s\n", contam_file.c_str(), rtx_last_error());
+            return 64;
+        }
+        char hex[24];
+        snprintf(hex, sizeof hex, "%016llx", (unsigned long long)fp);
+        contam_spec = "file=" + contam_file + ";minhits=" + std::to_string(contam.min_hits) + ";minpct=" + std::to_string(contam.min_pct) + ";keys=" + hex;
+        fprintf(stderr, "[INFO ] --contaminants: %llu record(s) of %s, %llu distinct 16-mers in %llu slots; a read is a contaminant from %u hit(s) and %u %% of its windows on\n",
+                (unsigned long long)nc, contam_file.c_str(), (unsigned long long)keys, (unsigned long long)slots, contam.min_hits, contam.min_pct);
+    }
+    const std::string demux_path = prefix + "/raxtax.demux", samples_path = prefix + "/raxtax.samples", screen_path = prefix + "/raxtax.screen";
     const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge", chim_path = prefix + "/raxtax.chimera";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     if (device_format && derep) {
@@ -549,7 +604,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -572,6 +627,7 @@ int main(int argc, char **argv) {
             if (merge_on) purge_incomplete(merge_path, done, true);
             if (chim_on) purge_incomplete(chim_path, done, true);
             if (tags_on) purge_incomplete(demux_path, done, true);
+            if (screen_on) purge_incomplete(screen_path, done, true);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
@@ -625,7 +681,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -803,6 +859,7 @@ int main(int argc, char **argv) {
                     rcs[k] = rtx_index_set_tags(indices[k], ct.data(), (uint32_t)ct.size(), tag_pairs.data(), (uint32_t)tag_pairs.size(), &tag_params);
                 }
                 if (rcs[k] == RTX_OK && qual_on) rcs[k] = rtx_index_set_quality(indices[k], &qual);
+                if (rcs[k] == RTX_OK && screen_on) rcs[k] = rtx_index_set_screen(indices[k], contam_set, &contam);
                 if (rcs[k] == RTX_OK && chim_on) rcs[k] = rtx_index_set_chimera(indices[k], &chim);
                 if (rcs[k] == RTX_OK && profile_cutoff && tags_on)  // ... with a column of counters per sample (PREFIX/raxtax.samples)
                     rcs[k] = rtx_index_profile_begin_samples(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u),
@@ -819,6 +876,8 @@ int main(int argc, char **argv) {
                 return 71;  // exitcode::OSERR
             }
     }
+    rtx_screen_set_free(contam_set);  // (the handles keep what they need)
+    contam_set = nullptr;
     lap("index");
     if (timing) {  // the handle's own verdict on tile pruning (rtx_index_self_sample: a property of the database)
         int on = 1;
@@ -875,6 +934,13 @@ int main(int argc, char **argv) {
         if (header) sink.chimera << "label\tstatus\twindows\tsingle\tparent_id\tseg\tpos\tleft\ta_id\tright\tb_id\tdelta\tchimera\tparent\ta\tb\n";
         fprintf(stderr, "[INFO ] --chimera: %u segments, a read is flagged from delta %u on\n", chim.segments, chim.mindelta);
     } else if (mode == std::ios::trunc) remove(chim_path.c_str());  // (likewise)
+    if (screen_on) {
+        const bool header = mode == std::ios::trunc || !is_file(screen_path);
+        sink.screen.open(screen_path, mode);
+        sink.contam_names = &contam_names;
+        if (header) sink.screen << "label\tlength\twindows\thits\tfirst\tsource\tverdict\n";
+    } else if (mode == std::ios::trunc) remove(screen_path.c_str());  // (likewise)
+    sink.want_qc = qual_on;
     sink.want_strand = both_strands;
     sink.want_hits = want_hits;
     sink.tree = tree;
@@ -930,6 +996,8 @@ int main(int argc, char **argv) {
     auto filtered = [](void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) -> int {
         static const char *const names[7] = {"bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate"};
         Sink *s = static_cast<Sink *>(c);
+        s->screen_len = verdict ? 0u : hi - lo;  // (what the contaminant screen is given of this query)
+        if (!s->want_qc) return 0;
         char frac[8];  // six decimals of ee / 2^40, truncated: from the integer, no floating point
         snprintf(frac, sizeof frac, "%06llu", (unsigned long long)(((ee & ((1ull << 40) - 1)) * 1000000ull) >> 40));
         s->qc << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t' << (ee >> 40) << '.' << frac << '\t';
@@ -960,6 +1028,18 @@ int main(int argc, char **argv) {
         s->chimera << '\n';
         return s->chimera.good() ? 0 : 1;
     };
+    // ... and, under --contaminants, what the screen made of every query (also one without result lines: a contaminant)
+    auto screened = [](void *c, const char *label, uint32_t windows, uint32_t hits, uint32_t first, uint32_t source, uint32_t verdict) -> int {
+        Sink *s = static_cast<Sink *>(c);
+        s->screen << label << '\t' << s->screen_len << '\t' << windows << '\t' << hits << '\t';
+        if (first == RTX_SCREEN_NONE) s->screen << '-';
+        else s->screen << first;
+        s->screen << '\t';
+        if (source == RTX_SCREEN_NONE || source >= s->contam_names->size()) s->screen << '-';
+        else s->screen << (*s->contam_names)[source];
+        s->screen << '\t' << (verdict ? "contaminant" : "pass") << '\n';
+        return s->screen.good() ? 0 : 1;
+    };
     // ... and, under --tags, which sample every query belongs to (also one without result lines: a read that is not assigned)
     auto assigned = [](void *c, const char *label, uint32_t, uint32_t sample, uint32_t lo, uint32_t hi, uint32_t hit, uint32_t info) -> int {
         static const char *const verdicts[5] = {"ok", "no_tag5", "no_tag3", "ambiguous", "unknown_pair"};
@@ -984,6 +1064,8 @@ int main(int argc, char **argv) {
     double qual_busy = 0;
     uint64_t chim_total[3] = {0, 0, 0};  // --chimera: queries, reads checked, queries flagged (rtx_raxtax_last_chimera)
     double chim_busy = 0;
+    uint64_t screen_total[3] = {0, 0, 0};  // --contaminants: queries, screened, contaminants (rtx_raxtax_last_screen)
+    double screen_busy = 0;
     uint64_t demux_total[7] = {0, 0, 0, 0, 0, 0, 0};  // --tags: queries, assigned, and the queries of every verdict (rtx_raxtax_last_demux)
     double demux_busy = 0;
     uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
@@ -1036,10 +1118,17 @@ int main(int argc, char **argv) {
             // one entry point takes everything a run can bring: an option that is off passes no callback
             const uint8_t *quals = nullptr;
             if (qual_on) rtx_queries_quals(pz.qs, &quals);
-            rc = rtx_raxtax_multi_ex7(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
+            rc = rtx_raxtax_multi_ex8(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
                                       want_identity ? +align : (both_strands || want_hits ? +info : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
-                                      quals, qual_on ? +filtered : nullptr, &sink, chim_on ? +checked : nullptr, &sink, tags_on ? +assigned : nullptr, &sink);
+                                      quals, qual_on || screen_on ? +filtered : nullptr, &sink, chim_on ? +checked : nullptr, &sink, tags_on ? +assigned : nullptr, &sink,
+                                      screen_on ? +screened : nullptr, &sink);
             n += nb;
+            if (screen_on) {
+                uint64_t sq[3] = {0, 0, 0};
+                double sb = 0;
+                if (rtx_raxtax_last_screen(&sq[0], &sq[1], &sq[2], &sb) == RTX_OK) { for (int k = 0; k < 3; k++) screen_total[k] += sq[k]; screen_busy += sb; }
+                if (timing) fprintf(stderr, "[TIMING] contaminant screen of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)sq[0], sb);
+            }
             if (tags_on) {
                 uint64_t xq[7] = {0, 0, 0, 0, 0, 0, 0};
                 double xb = 0;
@@ -1096,6 +1185,7 @@ int main(int argc, char **argv) {
     if (merge_on) sink.merge.flush();
     if (chim_on) sink.chimera.flush();
     if (tags_on) sink.demux.flush();
+    if (screen_on) sink.screen.flush();
     if (parse_failed) { join_bin_writer(); return 66; }
     lap("classify_and_write");
     if (merge_on) {
@@ -1120,6 +1210,11 @@ int main(int argc, char **argv) {
                 (unsigned long long)qual_total[2], (unsigned long long)qual_total[3], (unsigned long long)qual_total[4], (unsigned long long)qual_total[5],
                 (unsigned long long)qual_total[6], (unsigned long long)qual_total[7], (unsigned long long)qual_total[8], (unsigned long long)qual_total[9]);
         if (timing) t_log << ", \"qual_busy\": " << qual_busy;
+    }
+    if (screen_on) {
+        fprintf(stderr, "[INFO ] --contaminants: %llu queries, %llu screened, %llu contaminants\n", (unsigned long long)screen_total[0], (unsigned long long)screen_total[1],
+                (unsigned long long)screen_total[2]);
+        if (timing) t_log << ", \"screen_busy\": " << screen_busy;
     }
     if (chim_on) {
         fprintf(stderr, "[INFO ] --chimera: %llu queries, %llu reads checked, %llu queries flagged\n", (unsigned long long)chim_total[0], (unsigned long long)chim_total[1],

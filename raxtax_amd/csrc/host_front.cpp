@@ -1,5 +1,9 @@
 // The read front of the host mirror: see host_front.hpp.
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>  // (host_screen.hpp -> rtx_math.hpp: __forceinline__)
+#endif
 #include "host_front.hpp"
+#include "host_screen.hpp"
 
 #include <chrono>
 #include <cstring>
@@ -37,9 +41,9 @@ int run_demux(rtx_demux *stage, FrontChunk &fc, BufPool &pool, FrontTotals &tot)
     return RTX_OK;
 }
 
-// The primers of the chunk's reads, then the quality of the ranges they left, on the device (streams of their own beside the handle's); then
-// both ranges in one cut, a discarded read empty.
-int run_trim_qual(rtx_trim *trim, rtx_qual *qual, FrontChunk &fc, BufPool &pool, FrontTotals &tot) {
+// The primers of the chunk's reads, then the quality of the ranges they left, then the contaminants among what is still kept, on the device
+// (streams of their own beside the handle's); then all three in one cut, a discarded read or a contaminant empty.
+int run_trim_qual_screen(rtx_trim *trim, rtx_qual *qual, rtx_screen *screen, FrontChunk &fc, BufPool &pool, FrontTotals &tot) {
     const double t_t0 = now();
     const Reads &in = fc.in;
     const uint64_t nq = in.n;
@@ -81,11 +85,28 @@ int run_trim_qual(rtx_trim *trim, rtx_qual *qual, FrontChunk &fc, BufPool &pool,
         }
         tot.qual = q;
     }
-    const int rc = cut(in, fc.lo.data(), (qual ? fc.keep_hi : fc.hi).data(), false, fc.t, pool, "no memory for the trimmed reads of a chunk", fc.src);
+    const double t_s0 = now();
+    if (screen) {
+        if (!qual) fc.keep_hi = fc.hi;
+        for (auto *v : {&fc.s_windows, &fc.s_hits, &fc.s_first, &fc.s_source, &fc.s_verdict}) v->resize(nq);
+        const int rc = rtx_screen_run(screen, nq, in.bases, in.off, fc.lo.data(), fc.keep_hi.data(), fc.s_windows.data(), fc.s_hits.data(), fc.s_first.data(),
+                                      fc.s_source.data(), fc.s_verdict.data());
+        if (rc) return rc;
+        auto x = tot.screen;
+        for (uint64_t i = 0; i < nq; i++) {
+            x.screened += fc.keep_hi[i] != fc.lo[i];
+            if (fc.s_verdict[i]) { x.contaminants++; fc.keep_hi[i] = fc.lo[i]; }
+        }
+        tot.screen = x;
+    }
+    const double t_c0 = now();
+    const int rc = cut(in, fc.lo.data(), (qual || screen ? fc.keep_hi : fc.hi).data(), false, fc.t, pool, "no memory for the trimmed reads of a chunk", fc.src);
     if (rc) return rc;
     fc.dev = fc.src;
-    if (trim) { tot.trim.queries += nq; tot.trim.busy += (qual ? t_q0 : now()) - t_t0; }
-    if (qual) { tot.qual.queries += nq; tot.qual.busy += now() - t_q0; }
+    const double t_end = now(), t_cut = t_end - t_c0;  // (the cut counts with the last stage that is on, as before)
+    if (trim) { tot.trim.queries += nq; tot.trim.busy += t_q0 - t_t0 + (!qual && !screen ? t_end - t_q0 : 0.0); }
+    if (qual) { tot.qual.queries += nq; tot.qual.busy += t_s0 - t_q0 + (!screen ? t_cut : 0.0); }
+    if (screen) { tot.screen.queries += nq; tot.screen.busy += t_end - t_s0; }
     return RTX_OK;
 }
 
@@ -232,6 +253,21 @@ int Front::open(rtx_index *const *indices, uint32_t n_dev, bool has_quals, bool 
         rc = quals.open(indices, n_dev, true, [&](uint32_t d, rtx_qual **out) { return rtx_qual_create(rtx::index_device(indices[d]), &qparams, out); });
         if (rc) return rc;
     }
+    // Contaminant screen (rtx_index_set_screen): the same set and parameters on every handle, by their fingerprint (0: off)
+    auto screen_fp = [](const rtx_index *ix) {
+        rtx_screen_params p{};
+        const rtx_screen_set *set = rtx::index_screen(ix, &p);
+        return set ? rtx::screen_fingerprint(*set->data, p) : 0ull;
+    };
+    screen = screen_fp(indices[0]) != 0ull;
+    rc = agree(indices, n_dev, screen_fp, "rtx_raxtax_multi: the handles disagree on their contaminant screen (rtx_index_set_screen)");
+    if (rc) return rc;
+    if (screen) {
+        rtx_screen_params sparams{};
+        const rtx_screen_set *set = rtx::index_screen(indices[0], &sparams);
+        rc = screens.open(indices, n_dev, true, [&](uint32_t d, rtx_screen **out) { return rtx_screen_create(rtx::index_device(indices[d]), set, &sparams, out); });
+        if (rc) return rc;
+    }
     // Chimera check (rtx_index_set_chimera): the same setting on every handle.  One stage object (rtx_chimera.hip) per HANDLE: it reads that
     // handle's bitmap.  Not with RTX_OPT_STRAND (rtx_chimera_create refuses it: a read is checked in the orientation given).
     auto chimera = [](const rtx_index *ix) { std::pair<bool, rtx_chimera_params> s{false, {}}; s.first = rtx::index_chimera(ix, &s.second); return s; };
@@ -247,7 +283,7 @@ int Front::open(rtx_index *const *indices, uint32_t n_dev, bool has_quals, bool 
 int Front::run(uint32_t d, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTotals &tot) const {
     int rc = RTX_OK;
     if (demux) rc = run_demux(demuxes.of[d], fc, pool, tot);
-    if (!rc && (trim || qual)) rc = run_trim_qual(trim ? trims.of[d] : nullptr, qual ? quals.of[d] : nullptr, fc, pool, tot);
+    if (!rc && (trim || qual || screen)) rc = run_trim_qual_screen(trim ? trims.of[d] : nullptr, qual ? quals.of[d] : nullptr, screen ? screens.of[d] : nullptr, fc, pool, tot);
     if (!rc && derep) rc = run_derep(dereps.of[d], fc, pool, nt, tot);
     if (!rc && chim) rc = run_chimera(chims.of[d], fc, pool, tot);
     return rc;

@@ -2,15 +2,16 @@
 //
 //   stage (in this order)          on when                       reads    replaces   object per
 //   tags      rtx_demux_run        rtx_index_set_tags            given    in ..      device
-//   primers   rtx_trim_run         rtx_index_set_primers         in       src ..     device   (one cut for primers and quality)
+//   primers   rtx_trim_run         rtx_index_set_primers         in       src ..     device   (one cut for primers, quality and contaminants)
 //   quality   rtx_qual_run         rtx_index_set_quality         in       src ..     device
+//   contaminants rtx_screen_run    rtx_index_set_screen          in       src ..     device   (the same cut: no further copy)
 //   copies    rtx_derep_run        RTX_OPT_DEREP                 src      dev        device
 //   chimeras  rtx_chimera_run      rtx_index_set_chimera         dev      dev        handle   (it borrows the handle's bitmap)
 //
 // A chunk holds four views of its reads (Reads).  Each starts as the one before it; the stage that cuts replaces it and every later one:
 //   given  the caller's arrays
 //   in     the tags cut, a read that is not assigned empty: trim and qual read it, and their callbacks measure raw_len on it
-//   src    primers and low quality cut, a discarded read empty: derep reads it, and so do the `.tsv` sequence column and qlen of the align callback
+//   src    primers and low quality cut, a discarded read or a contaminant empty: derep reads it, and so do the `.tsv` sequence column and qlen of the align callback
 //   dev    the distinct reads (dev.n of them), a flagged one empty: what the handle and the host lookup are given
 // Every cut but the gather of the distinct reads goes through cut(): a chunk in which nothing is cut goes on as it came, without a copy.
 #pragma once
@@ -103,6 +104,7 @@ struct FrontTotals {
     struct { uint64_t queries, assigned, reasons[5]; double busy; } demux;
     struct { uint64_t queries, with5, with3, emptied; double busy; } trim;
     struct { uint64_t queries, passed, truncated, reasons[7]; double busy; } qual;
+    struct { uint64_t queries, screened, contaminants; double busy; } screen;
     struct { uint64_t queries, distinct; double busy; } derep;
     struct { uint64_t queries, checked, flagged; double busy; } chim;
     double busy[4];
@@ -114,8 +116,9 @@ struct FrontChunk {
     Reads given, in, src, dev;
     std::vector<uint32_t> dx_sample, dx_lo, dx_hi, dx_hit, dx_info;  // rtx_demux_run
     std::vector<uint32_t> lo, hi, hit;                               // rtx_trim_run (the whole read without primers), filled with either of primers and quality on
-    std::vector<uint32_t> q_hi, q_verdict, keep_hi;                  // rtx_qual_run on [lo, hi); keep_hi: the end of what goes on -- q_hi, or lo for a discarded read
+    std::vector<uint32_t> q_hi, q_verdict, keep_hi;                  // rtx_qual_run on [lo, hi); keep_hi (quality or screen on): the end of what goes on -- q_hi, or lo for a discarded read
     std::vector<uint64_t> q_ee;
+    std::vector<uint32_t> s_windows, s_hits, s_first, s_source, s_verdict;  // rtx_screen_run on [lo, keep_hi): a contaminant's keep_hi becomes lo
     std::vector<uint32_t> slot;  // RTX_OPT_DEREP: the position of query i's representative in `dev`; empty: i itself (no copies, or the option off)
     std::vector<uint32_t> size;  // [dev.n] copies of every distinct read: its weight in an open profile
     std::vector<rtx_chimera_rec> chim;  // [dev.n] rtx_chimera_run; query i's record is that of its representative
@@ -160,16 +163,17 @@ int agree(rtx_index *const *indices, uint32_t n_dev, Get get, const char *msg, S
 
 // The front of a call: which stages are on (the same on every handle) and their objects.
 struct Front {
-    bool demux = false, trim = false, qual = false, derep = false, chim = false;
+    bool demux = false, trim = false, qual = false, screen = false, derep = false, chim = false;
     uint32_t prof_samples = 0;  // the samples of the open profile (rtx_index_profile_begin_samples): the same on every handle
     StageSet<rtx_demux, rtx_demux_destroy> demuxes;
     StageSet<rtx_trim, rtx_trim_destroy> trims;
     StageSet<rtx_qual, rtx_qual_destroy> quals;
+    StageSet<rtx_screen, rtx_screen_destroy> screens;
     StageSet<rtx_derep, rtx_derep_destroy> dereps;
     StageSet<rtx_chimera, rtx_chimera_destroy> chims;
     // checks that the handles agree on every stage and creates the objects; has_quals: the call brings quality strings, prof: a taxon profile is open
     int open(rtx_index *const *indices, uint32_t n_dev, bool has_quals, bool prof);
-    bool any() const { return demux || trim || qual || derep || chim; }
+    bool any() const { return demux || trim || qual || screen || derep || chim; }
     // chunk `fc` (given set, the other views as given) through the stages that are on, with the objects of handle d
     int run(uint32_t d, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTotals &tot) const;
 };

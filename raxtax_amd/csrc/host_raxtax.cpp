@@ -72,13 +72,13 @@ private:
 };
 
 std::mutex g_timing_mu;
-FrontTotals g_last{};  // the last call of this process: what the six rtx_raxtax_last_* report (under g_timing_mu)
+FrontTotals g_last{};  // the last call of this process: what the seven rtx_raxtax_last_* report (under g_timing_mu)
 
 // The arguments of a call.  A callback is a function of the C ABI with its context (0: go on, else the sink is closed); null: nobody asked.
 //   sender (label, out_lines, tsv_lines or null) of every query that has a message
 //   align  (label, strand, peak, t, nearest, ties, dist, qlen) directly before it: RTX_NO_REF and 0 with RTX_OPT_NEAREST off, RTX_NO_DIST and the
 //          length with RTX_OPT_IDENTITY off
-//   demux, trim, qual, chimera: of EVERY query, in this order, before its align call
+//   demux, trim, qual, screen, chimera: of EVERY query, in this order, before its align call
 struct Call {
     rtx_index *const *indices; uint32_t n_dev;
     const rtx_tree *tree;
@@ -95,6 +95,7 @@ struct Call {
     rtx_query_qual_fn qual; void *qual_ctx;
     rtx_query_chimera_fn chimera; void *chimera_ctx;
     rtx_query_demux_fn demux; void *demux_ctx;
+    rtx_query_screen_fn screen; void *screen_ctx;
 };
 
 // The text of a formatting thread's queries: NUL-terminated messages back to back
@@ -166,7 +167,7 @@ void per_query(std::vector<T> &dst, const T *src, const std::vector<uint32_t> &s
 //   device thread : classification of its chunks, one after the other  (rtx_classify_batch, raxtax.rs:42,55-71)
 //   format thread : lineage check of the exact matches (raxtax.rs:43-53), override + formatting (raxtax.rs:73-84), chunk by chunk
 // and for all of them
-//   lookup thread : the read front (host_front.hpp: tags, primers, quality, copies, chimeras -- each on the device, on a stream of its own
+//   lookup thread : the read front (host_front.hpp: tags, primers, quality, contaminants, copies, chimeras -- each on the device, on a stream of its own
 //                   beside the handle's, while that handle still classifies an earlier chunk), then the exact-match ids (host hash map,
 //                   raxtax.rs:42) -- only for handles without the device lookup (rtx_index_has_exact_lookup): otherwise the ids come back
 //                   with the results of the device stage.  The handle classifies front.dev; the format thread and the sender go on
@@ -579,6 +580,11 @@ int run(const Call &call) {
                 const bool ranged = !fc.lo.empty(), on = !fc.q_hi.empty();
                 if (call.qual(call.qual_ctx, labels[q], raw, ranged ? fc.lo[i] : 0u, on ? fc.q_hi[i] : (ranged ? fc.hi[i] : raw), on ? fc.q_ee[i] : 0ull, on ? fc.q_verdict[i] : 0u)) { closed = true; break; }
             }
+            if (call.screen) {  // likewise
+                const bool on = !fc.s_verdict.empty();
+                if (call.screen(call.screen_ctx, labels[q], on ? fc.s_windows[i] : 0u, on ? fc.s_hits[i] : 0u, on ? fc.s_first[i] : RTX_SCREEN_NONE, on ? fc.s_source[i] : RTX_SCREEN_NONE,
+                                on ? fc.s_verdict[i] : 0u)) { closed = true; break; }
+            }
             if (call.chimera) {  // likewise; a copy takes its representative's record
                 static const rtx_chimera_rec none{RTX_CHIM_OK, 0u, 0u, RTX_NO_REF, 0u, 0u, 0u, RTX_NO_REF, 0u, RTX_NO_REF, 0u, 0u};
                 if (call.chimera(call.chimera_ctx, labels[q], fc.chim.empty() ? &none : &fc.chim[fc.at(i)])) { closed = true; break; }
@@ -673,15 +679,26 @@ int raxtax(const std::vector<std::pair<std::string, std::vector<uint8_t>>> &quer
 // The same over several device handles (one per GPU, or several on one): the reference's parallel driver is one call inside the
 // process as well (par_chunks over a rayon pool, raxtax.rs:35-36, main.rs:40-57).  Chunks of `chunk_size` queries are dealt to the
 // handles in turn, one driving thread per handle; the messages reach the sender in input order.
-// rtx_raxtax_multi_ex7 takes everything a call can bring; every entry point before it is the next one with nulls appended.
+// rtx_raxtax_multi_ex8 takes everything a call can bring; every entry point before it is the next one with nulls appended.
+extern "C" int rtx_raxtax_multi_ex8(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
+                                    const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
+                                    int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
+                                    rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
+                                    rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx, rtx_query_demux_fn demux,
+                                    void *demux_ctx, rtx_query_screen_fn screen, void *screen_ctx) {
+    return run(Call{indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, sender, sender_ctx, tsv != 0,
+                    quals, align, align_ctx, trim, trim_ctx, qual, qual_ctx, chimera, chimera_ctx, demux, demux_ctx, screen, screen_ctx});
+}
+
+// ... without the contaminant screen's callback (rtx_index_set_screen)
 extern "C" int rtx_raxtax_multi_ex7(rtx_index *const *indices, uint32_t n_indices, const rtx_tree *tree, uint64_t n_queries,
                                     const char *const *labels, const uint8_t *bases, const uint64_t *base_off, int skip_exact_matches,
                                     int raw_confidence, uint64_t chunk_size, rtx_sender_fn sender, void *sender_ctx, int tsv,
                                     rtx_query_align_fn align, void *align_ctx, rtx_query_trim_fn trim, void *trim_ctx, const uint8_t *quals,
                                     rtx_query_qual_fn qual, void *qual_ctx, rtx_query_chimera_fn chimera, void *chimera_ctx, rtx_query_demux_fn demux,
                                     void *demux_ctx) {
-    return run(Call{indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches != 0, raw_confidence != 0, chunk_size, sender, sender_ctx, tsv != 0,
-                    quals, align, align_ctx, trim, trim_ctx, qual, qual_ctx, chimera, chimera_ctx, demux, demux_ctx});
+    return rtx_raxtax_multi_ex8(indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender, sender_ctx, tsv,
+                                align, align_ctx, trim, trim_ctx, quals, qual, qual_ctx, chimera, chimera_ctx, demux, demux_ctx, nullptr, nullptr);
 }
 
 #define RTX_COMMON_ARGS indices, n_indices, tree, n_queries, labels, bases, base_off, skip_exact_matches, raw_confidence, chunk_size, sender, sender_ctx, tsv
@@ -797,6 +814,15 @@ extern "C" int rtx_raxtax_last_qual(uint64_t *queries, uint64_t *passed, uint64_
     if (truncated) *truncated = g_last.qual.truncated;
     if (reasons) for (int b = 0; b < 7; b++) reasons[b] = g_last.qual.reasons[b];
     if (busy_seconds) *busy_seconds = g_last.qual.busy;
+    return RTX_OK;
+}
+
+extern "C" int rtx_raxtax_last_screen(uint64_t *queries, uint64_t *screened, uint64_t *contaminants, double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_last.screen.queries;
+    if (screened) *screened = g_last.screen.screened;
+    if (contaminants) *contaminants = g_last.screen.contaminants;
+    if (busy_seconds) *busy_seconds = g_last.screen.busy;
     return RTX_OK;
 }
 

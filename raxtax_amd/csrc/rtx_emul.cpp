@@ -919,6 +919,38 @@ void emul_qual_read(const int32_t *cfg32, const uint64_t *cfg64, const uint64_t 
     *verdict = qual_verdict(cfg, bad, short_tl, hi, carry_e, carry_n);
 }
 
+// The contaminant screen as screen_kernel (rtx_screen.hip) runs it, with the functions the kernel calls, in the kernel's geometry: a group of
+// 16 lanes, every lane its pieces of 16 window positions in steps of 256, each piece loaded with the 16 bytes behind it (zeros where they
+// start at or behind the end), the lanes' counts summed and the lowest first hit taken with the source of the lane that holds it.
+// slots: the table of the set, key and src per slot (rtx_screen_set_table); x: the codes of one range, len of them; out: windows, hits, first,
+// source.
+void emul_screen_read(const uint32_t *slots, uint32_t log2m, const uint8_t *x, uint32_t len, uint32_t *out) {
+    const ScreenTable t{reinterpret_cast<const ScreenSlot *>(slots), log2m};
+    std::vector<uint8_t> row((size_t)(len + 15u) / 16u * 16u + 16u, 0xFF);  // (what lies behind the range is never taken as data)
+    if (len) memcpy(row.data(), x, len);
+    ScreenAcc acc[kScreenGroup];
+    for (uint32_t gl = 0; gl < kScreenGroup; gl++) {
+        acc[gl] = ScreenAcc{0u, 0u, kScreenNone, kScreenNone};
+        for (uint32_t pos = gl * kScreenPiece; pos + kScreenK <= len; pos += kScreenGroup * kScreenPiece) {
+            ScreenWords a, b{{0u, 0u, 0u, 0u}};
+            memcpy(a.w, row.data() + pos, 16);
+            if (pos + kScreenPiece < len) memcpy(b.w, row.data() + pos + kScreenPiece, 16);
+            screen_piece(t, a, b, pos, len, acc[gl]);
+        }
+    }
+    uint32_t windows = 0, hits = 0, first = kScreenNone, source = kScreenNone;
+    for (uint32_t gl = 0; gl < kScreenGroup; gl++) {
+        windows += acc[gl].windows;
+        hits += acc[gl].hits;
+        first = std::min(first, acc[gl].first);
+    }
+    for (uint32_t gl = 0; gl < kScreenGroup; gl++) source = std::min(source, acc[gl].first == first ? acc[gl].source : kScreenNone);
+    out[0] = windows;
+    out[1] = hits;
+    out[2] = first;
+    out[3] = source;
+}
+
 // One pair as merge_kernel (rtx_merge.hip) merges it, with the functions the kernel calls, in the kernel's geometry: the mates staged four
 // bases per lane and step (a too-long mate only streamed for its bad bytes), the candidates dealt over 64 lanes in strides of 64 -- each
 // walked in words of 16 with the early leave --, the maximum over the lanes, then the merged bases written lane l at l + 64 k.

@@ -16,6 +16,7 @@
 #include <cstring>
 #include <thread>
 
+#include "host_screen.hpp"
 #include "rtx_internal.hpp"
 #include "rtx_kernels.hpp"
 #include "rtx_math.hpp"
@@ -474,6 +475,8 @@ struct rtx_index {
     bool quality_on = false;
     rtx_chimera_params chimera{};    // rtx_index_set_chimera: the chimera check its callers run in front of it (rtx_chimera.hip); the handle itself never reads it
     bool chimera_on = false;
+    rtx_screen_set screen_set;       // rtx_index_set_screen: the contaminant screen rtx_raxtax* run every read through (rtx_screen.hip); the handle itself never reads it
+    rtx_screen_params screen{};      // (screen_set.data is null: off)
     rtx::DemuxList tags;  // rtx_index_set_tags: rtx_raxtax* assign every read to a sample and cut its tags first (rtx_demux.hip); the handle itself never reads them
     std::vector<rtx::TrimPrimer> primers;  // rtx_index_set_primers: rtx_raxtax* trim every read with them first (rtx_trim.hip); the handle itself never reads them
     DevBuf<char> d_lin_bytes, d_text;

@@ -469,6 +469,73 @@ RTX_HD void qual_read_serial(const QualCfg &cfg, const uint64_t *table, const L 
 }
 
 // ---------------------------------------------------------------------------
+// Contaminant screen (screen_kernel, rtx_screen.hip; rtx_screen_read on the host; emul_screen_read on x86): the 16-mers of a read looked up
+// in a set of canonical 16-mers -- include/raxtax_hip.h has the semantics and the table's layout.  Exact integers.
+// The read arrives as its 4-bit codes, one byte per base, in pieces of 16 bytes (ScreenWords: one load).  A piece is the 16 window
+// positions that START in it: screen_piece takes the piece and the one behind it (the 15 bases beyond), rolls the forward and the
+// reverse-complement word over the 31 bases and probes every valid window (screen_probe).  Nothing is carried from piece to piece.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kScreenK = 16u;                 // RTX_SCREEN_K
+constexpr uint32_t kScreenNone = 0xFFFFFFFFu;      // RTX_SCREEN_NONE; as a key: an empty slot (no canonical value is all ones)
+constexpr uint32_t kScreenMaxRead = 1u << 20;      // RTX_SCREEN_MAX_READ
+constexpr uint32_t kScreenPiece = 16u;             // window positions of a piece: the bytes of one load
+constexpr uint32_t kScreenGroup = 16u;             // pieces of a step: the lanes of a group
+constexpr uint32_t kScreenMinSlots = 1024u;
+constexpr uint32_t kScreenHashMul = 0x9E3779B1u;
+struct ScreenWords { uint32_t w[4]; };
+struct alignas(8) ScreenSlot { uint32_t key, src; };
+struct ScreenTable { const ScreenSlot *slots; uint32_t log2m; };   // m = 1 << log2m slots, at least one of them empty
+struct ScreenAcc { uint32_t windows, hits, first, source; };       // of the pieces a lane has seen; first / source: kScreenNone without a hit
+
+RTX_HD uint32_t screen_home(uint32_t c, uint32_t log2m) { return (uint32_t)(c * kScreenHashMul) >> (32u - log2m); }
+// The reverse complement of a 16-mer word: base j is 3 - base 15 - j
+RTX_HD uint32_t screen_rc(uint32_t w) {
+    w = ~w;
+    w = (w >> 2 & 0x33333333u) | (w & 0x33333333u) << 2;
+    w = (w >> 4 & 0x0F0F0F0Fu) | (w & 0x0F0F0F0Fu) << 4;
+    w = (w >> 8 & 0x00FF00FFu) | (w & 0x00FF00FFu) << 8;
+    return w >> 16 | w << 16;
+}
+// One chain: from the home slot of c to c (true, src set) or to an empty slot (false).  At most m slots are looked at.
+RTX_HD bool screen_probe(const ScreenTable &t, uint32_t c, uint32_t &src) {
+    const uint32_t mask = (1u << t.log2m) - 1u;
+    uint32_t h = screen_home(c, t.log2m);
+    for (uint32_t i = 0; i <= mask; i++) {
+        const ScreenSlot s = t.slots[h];
+        if (s.key == c) { src = s.src; return true; }
+        if (s.key == kScreenNone) return false;
+        h = (h + 1u) & mask;
+    }
+    return false;
+}
+// The windows that start at pos .. pos + 15 of a range of len bases; a: bytes pos .. pos + 15, b: bytes pos + 16 .. pos + 31 (anything where
+// they lie at or behind len).  Adds to acc; the pieces of a lane come in ascending order, so the first hit ever seen stays.
+RTX_HD void screen_piece(const ScreenTable &t, const ScreenWords &a, const ScreenWords &b, uint32_t pos, uint32_t len, ScreenAcc &acc) {
+    uint32_t fw = 0u, rc = 0u, run = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 2u * kScreenPiece - 1u; j++) {
+        const uint32_t code = ((j < kScreenPiece ? a.w[j >> 2] : b.w[(j - kScreenPiece) >> 2]) >> (8u * (j & 3u))) & 0xFFu;
+        const bool acgt = pos + j < len && (code == 1u || code == 2u || code == 4u || code == 8u);
+        const uint32_t two = (code >> 1 & 1u) | (code >> 2 & 1u) << 1 | (code >> 3 & 1u) * 3u;  // 1, 2, 4, 8 -> 0, 1, 2, 3
+        fw = fw << 2 | two;
+        rc = rc >> 2 | (3u - two) << 30;
+        run = acgt ? run + 1u : 0u;
+        if (j >= kScreenK - 1u && run >= kScreenK) {  // the window that starts at pos + j - 15 and ends with this base
+            const uint32_t c = fw < rc ? fw : rc;
+            uint32_t src = kScreenNone;
+            acc.windows++;
+            if (screen_probe(t, c, src)) {
+                acc.hits++;
+                if (acc.first == kScreenNone) { acc.first = pos + j - (kScreenK - 1u); acc.source = src; }
+            }
+        }
+    }
+}
+RTX_HD uint32_t screen_verdict(uint32_t hits, uint32_t windows, uint32_t min_hits, uint32_t min_pct) {
+    return hits >= min_hits && 100ull * hits >= (uint64_t)min_pct * windows ? 1u : 0u;
+}
+
+// ---------------------------------------------------------------------------
 // Paired-end merging (merge_kernel, rtx_merge.hip; rtx_merge_pair on the host; emul_merge_pair on x86): the two mates of a pair overlapped
 // into one read -- include/raxtax_hip.h has the semantics.  Exact integers.
 // A mate is staged as nibble words -- 16 base codes to a uint64, base p in bits 4 (p & 15) of word p >> 4 -- and a byte of Q per base; the

@@ -34,6 +34,23 @@ __device__ __forceinline__ uint32_t row16_max_u32(uint32_t v) {  // maximum over
     return v;
 }
 
+__device__ __forceinline__ uint32_t row16_min_u32(uint32_t v) {  // minimum over the 16 lanes of a DPP row, in every lane of the row
+    uint32_t o;
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true); v = o < v ? o : v;   // quad_perm [1,0,3,2]
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true); v = o < v ? o : v;   // quad_perm [2,3,0,1]
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true); v = o < v ? o : v;  // row_half_mirror
+    o = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true); v = o < v ? o : v;  // row_mirror
+    return v;
+}
+
+__device__ __forceinline__ uint32_t row16_sum_u32(uint32_t v) {  // sum over the 16 lanes of a DPP row, in every lane of the row
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, true);   // quad_perm [1,0,3,2]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xF, 0xF, true);   // quad_perm [2,3,0,1]
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x141, 0xF, 0xF, true);  // row_half_mirror
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x140, 0xF, 0xF, true);  // row_mirror
+    return v;
+}
+
 // Maximum over the 64 lanes, in every lane: DPP inside the rows, the four row maxima through v_readlane
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     v = row16_max_u32(v);
