@@ -984,24 +984,45 @@ def trim_apply(bases: np.ndarray, base_off: np.ndarray, lo: np.ndarray, hi: np.n
     return out[:int(off[-1])].copy(), off
 
 
-class Trim:
-    """The primer-trimming stage on one GPU (rtx_trim): an object of its own beside any Index, one stream, buffers that only grow."""
+class _Stage:
+    """What the stage classes share: the library, the handle of their C object rtx_<_c>, its release through rtx_<_c>_destroy and its times."""
 
-    def __init__(self, device: int, patterns):
+    _c = ""  # trim, demux, qual, screen, chimera, merge, derep
+
+    def _open(self, *args):
         self._lib = _lib.load()
         self._h = None
-        arr, keep = _trim_patterns(patterns)
         h = C.c_void_p()
-        check(self._lib.rtx_trim_create(device, arr, len(keep), C.byref(h)))
+        check(getattr(self._lib, f"rtx_{self._c}_create")(*args, C.byref(h)))
         self._h = h
 
     def __del__(self):
         try:
             if self._h:
-                self._lib.rtx_trim_destroy(self._h)
+                getattr(self._lib, f"rtx_{self._c}_destroy")(self._h)
                 self._h = None
         except Exception:
             pass
+
+    def _kernel_ms(self) -> float:
+        ms = C.c_float()
+        check(getattr(self._lib, f"rtx_{self._c}_kernel_time")(self._h, C.byref(ms)))
+        return float(ms.value)
+
+    def _stage_seconds(self) -> Tuple[float, float, float]:
+        t = (C.c_double * 3)()
+        check(getattr(self._lib, f"rtx_{self._c}_stage_times")(self._h, t))
+        return float(t[0]), float(t[1]), float(t[2])
+
+
+class Trim(_Stage):
+    """The primer-trimming stage on one GPU (rtx_trim): an object of its own beside any Index, one stream, buffers that only grow."""
+
+    _c = "trim"
+
+    def __init__(self, device: int, patterns):
+        arr, keep = _trim_patterns(patterns)
+        self._open(device, arr, len(keep))
 
     def run(self, bases: np.ndarray, base_off: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(lo, hi, hit) per read (rtx_trim_run): the read keeps [lo, hi); hit as trim_hit() takes it apart."""
@@ -1015,9 +1036,7 @@ class Trim:
 
     def kernel_ms(self) -> float:
         """Milliseconds of the kernel of the last run(), from HIP events (rtx_trim_kernel_time)."""
-        ms = C.c_float()
-        check(self._lib.rtx_trim_kernel_time(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms()
 
 
 def raxtax_last_trim() -> Tuple[int, int, int, int, float]:
@@ -1090,24 +1109,14 @@ def demux_read(tags, pairs, params, read: np.ndarray) -> Tuple[int, int, int, in
     return tuple(int(o.value) for o in out)
 
 
-class Demux:
+class Demux(_Stage):
     """The sample-demultiplexing stage on one GPU (rtx_demux): an object of its own beside any Index, one stream, buffers that only grow."""
 
-    def __init__(self, device: int, tags, pairs, params=None):
-        self._lib = _lib.load()
-        self._h = None
-        arr, n_tags, parr, n_pairs, cp, _keep = _demux_args(tags, pairs, params)
-        h = C.c_void_p()
-        check(self._lib.rtx_demux_create(device, arr, n_tags, parr, n_pairs, C.byref(cp), C.byref(h)))
-        self._h = h
+    _c = "demux"
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.rtx_demux_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def __init__(self, device: int, tags, pairs, params=None):
+        arr, n_tags, parr, n_pairs, cp, _keep = _demux_args(tags, pairs, params)
+        self._open(device, arr, n_tags, parr, n_pairs, C.byref(cp))
 
     def run(self, bases: np.ndarray, base_off: np.ndarray) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """(sample, lo, hi, hit, info) per read (rtx_demux_run): the read belongs to `sample` (DEMUX_NONE: to none) and keeps [lo, hi);
@@ -1122,9 +1131,7 @@ class Demux:
 
     def kernel_ms(self) -> float:
         """Milliseconds of the kernel of the last run(), from HIP events (rtx_demux_kernel_time)."""
-        ms = C.c_float()
-        check(self._lib.rtx_demux_kernel_time(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms()
 
 
 def raxtax_last_demux() -> Tuple[int, int, List[int], float]:
@@ -1236,23 +1243,13 @@ def qual_read(params: QualParams, bases: np.ndarray, quals: np.ndarray, lo: int 
     return int(h.value), int(e.value), int(v.value)
 
 
-class Qual:
+class Qual(_Stage):
     """The quality-filter stage on one GPU (rtx_qual): an object of its own beside any Index, one stream, buffers that only grow."""
 
-    def __init__(self, device: int, params: QualParams):
-        self._lib = _lib.load()
-        self._h = None
-        h = C.c_void_p()
-        check(self._lib.rtx_qual_create(device, C.byref(params._c()), C.byref(h)))
-        self._h = h
+    _c = "qual"
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.rtx_qual_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def __init__(self, device: int, params: QualParams):
+        self._open(device, C.byref(params._c()))
 
     def run(self, bases: np.ndarray, quals: np.ndarray, base_off: np.ndarray, lo=None, hi=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(hi, ee, verdict) per read (rtx_qual_run): the read keeps [lo, hi) -- lo as given, 0 by default -- with ee expected errors
@@ -1282,15 +1279,11 @@ class Qual:
 
     def kernel_ms(self) -> float:
         """Milliseconds of the kernel of the last run(), from HIP events (rtx_qual_kernel_time)."""
-        ms = C.c_float()
-        check(self._lib.rtx_qual_kernel_time(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms()
 
     def stage_seconds(self) -> Tuple[float, float, float]:
         """(host staging, copies and waiting around the kernel, the whole call) of the last run(), in seconds (rtx_qual_stage_times)."""
-        t = (C.c_double * 3)()
-        check(self._lib.rtx_qual_stage_times(self._h, t))
-        return float(t[0]), float(t[1]), float(t[2])
+        return self._stage_seconds()
 
 
 def raxtax_last_qual() -> Tuple[int, int, int, List[int], float]:
@@ -1380,24 +1373,14 @@ def screen_read(sset: ScreenSet, params: ScreenParams, bases: np.ndarray, lo: in
     return tuple(int(x.value) for x in v)
 
 
-class Screen:
+class Screen(_Stage):
     """The contaminant-screen stage on one GPU (rtx_screen): an object of its own beside any Index, one stream, buffers that only grow,
     the table of the set uploaded once."""
 
-    def __init__(self, device: int, sset: ScreenSet, params: Optional[ScreenParams] = None):
-        self._lib = _lib.load()
-        self._h = None
-        h = C.c_void_p()
-        check(self._lib.rtx_screen_create(device, sset._h, C.byref((params or ScreenParams())._c()), C.byref(h)))
-        self._h = h
+    _c = "screen"
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.rtx_screen_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def __init__(self, device: int, sset: ScreenSet, params: Optional[ScreenParams] = None):
+        self._open(device, sset._h, C.byref((params or ScreenParams())._c()))
 
     def run(self, bases: np.ndarray, base_off: np.ndarray, lo=None, hi=None) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """(windows, hits, first, source, verdict) per read (rtx_screen_run) over [lo, hi) -- the whole read by default; first counts from lo."""
@@ -1420,15 +1403,11 @@ class Screen:
 
     def kernel_ms(self) -> float:
         """Milliseconds of the kernel of the last run(), from HIP events (rtx_screen_kernel_time)."""
-        ms = C.c_float()
-        check(self._lib.rtx_screen_kernel_time(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms()
 
     def stage_seconds(self) -> Tuple[float, float, float]:
         """(host staging, copies and waiting around the kernel, the whole call) of the last run(), in seconds (rtx_screen_stage_times)."""
-        t = (C.c_double * 3)()
-        check(self._lib.rtx_screen_stage_times(self._h, t))
-        return float(t[0]), float(t[1]), float(t[2])
+        return self._stage_seconds()
 
 
 def raxtax_last_screen() -> Tuple[int, int, int, float]:
@@ -1468,25 +1447,15 @@ def chimera_read(params: ChimeraParams, read: np.ndarray, ref_bases: np.ndarray,
     return rec[0]
 
 
-class Chimera:
+class Chimera(_Stage):
     """The chimera check in front of one Index (rtx_chimera): one stream and buffers of its own; it borrows the handle's bitmap, so it keeps
     the Index alive."""
 
-    def __init__(self, index: "Index", params: Optional[ChimeraParams] = None):
-        self._lib = _lib.load()
-        self._h = None
-        self._index = index
-        h = C.c_void_p()
-        check(self._lib.rtx_chimera_create(index._h, C.byref((params or ChimeraParams())._c()), C.byref(h)))
-        self._h = h
+    _c = "chimera"
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.rtx_chimera_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def __init__(self, index: "Index", params: Optional[ChimeraParams] = None):
+        self._index = index
+        self._open(index._h, C.byref((params or ChimeraParams())._c()))
 
     def run(self, bases: np.ndarray, base_off: np.ndarray) -> np.ndarray:
         """One record per read (rtx_chimera_run), as a structured array of CHIMERA_DTYPE."""
@@ -1499,9 +1468,7 @@ class Chimera:
 
     def kernel_ms(self) -> float:
         """Milliseconds of the scan kernels of the last run(), from HIP events (rtx_chimera_kernel_time)."""
-        ms = C.c_float()
-        check(self._lib.rtx_chimera_kernel_time(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms()
 
 
 def raxtax_last_chimera() -> Tuple[int, int, int, float]:
@@ -1557,23 +1524,13 @@ def merge_pair(params: MergeParams, f_bases, f_quals, r_bases, r_quals) -> Tuple
     return int(ov.value), int(d.value), int(v.value), mb[:ml.value].copy(), mq[:ml.value].copy()
 
 
-class Merge:
+class Merge(_Stage):
     """The paired-end merging stage on one GPU (rtx_merge): an object of its own beside any Index, one stream, buffers that only grow."""
 
-    def __init__(self, device: int, params: MergeParams):
-        self._lib = _lib.load()
-        self._h = None
-        h = C.c_void_p()
-        check(self._lib.rtx_merge_create(device, C.byref(params._c()), C.byref(h)))
-        self._h = h
+    _c = "merge"
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.rtx_merge_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def __init__(self, device: int, params: MergeParams):
+        self._open(device, C.byref(params._c()))
 
     def run(self, f_bases, f_quals, f_off, r_bases, r_quals, r_off):
         """(overlap, diffs, verdict, merged_len, merged_bases, merged_quals, slot_off) of n pairs (rtx_merge_run): the merged read of pair i
@@ -1600,15 +1557,11 @@ class Merge:
 
     def kernel_ms(self) -> float:
         """Milliseconds of the kernel of the last run(), from HIP events (rtx_merge_kernel_time)."""
-        ms = C.c_float()
-        check(self._lib.rtx_merge_kernel_time(self._h, C.byref(ms)))
-        return float(ms.value)
+        return self._kernel_ms()
 
     def stage_seconds(self) -> Tuple[float, float, float]:
         """(host staging, copies and waiting around the kernel, the whole call) of the last run(), in seconds (rtx_merge_stage_times)."""
-        t = (C.c_double * 3)()
-        check(self._lib.rtx_merge_stage_times(self._h, t))
-        return float(t[0]), float(t[1]), float(t[2])
+        return self._stage_seconds()
 
 
 _IUPAC_CHARS = {v: k for k, v in IUPAC.items()}
@@ -1764,24 +1717,14 @@ def raxtax(queries: Sequence[Tuple[str, np.ndarray]], tree, skip_exact_matches: 
     check(rc)
 
 
-class Derep:
+class Derep(_Stage):
     """The dereplication stage on one GPU (rtx_derep): an object of its own beside any Index, one stream, buffers that only grow."""
 
-    def __init__(self, device: int = 0):
-        self._lib = _lib.load()
-        self._h = None
-        h = C.c_void_p()
-        check(self._lib.rtx_derep_create(device, C.byref(h)))
-        self._h = h
-        self.n_unique = 0
+    _c = "derep"
 
-    def __del__(self):
-        try:
-            if self._h:
-                self._lib.rtx_derep_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+    def __init__(self, device: int = 0):
+        self._open(device)
+        self.n_unique = 0
 
     def run(self, bases: np.ndarray, base_off: np.ndarray) -> np.ndarray:
         """rep[q] = the lowest query whose sequence is byte for byte that of q (rtx_derep_run); n_unique = the queries with rep[q] == q."""

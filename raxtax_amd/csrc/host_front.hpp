@@ -24,6 +24,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_stage.hpp"
 #include "rtx_internal.hpp"
 
 namespace rtx_front {
@@ -31,11 +32,7 @@ namespace rtx_front {
 // Runs fn(a, b) over contiguous ranges of [0, n) on up to `nt` threads.
 template <class F>
 void parallel_ranges(uint64_t n, unsigned nt, F fn) {
-    nt = (unsigned)std::min<uint64_t>(nt, (n + 255) / 256);
-    if (nt <= 1) { fn(0, n); return; }
-    std::vector<std::thread> th;
-    for (unsigned i = 0; i < nt; i++) th.emplace_back(fn, n * i / nt, n * (i + 1) / nt);
-    for (auto &t : th) t.join();
+    rtx::parallel_ranges(n, nt, 256, [&fn](unsigned, uint64_t a, uint64_t b) { fn(a, b); });
 }
 
 // Bytes without a value yet (RTX_OPT_DEREP: the distinct reads of a chunk).  Not a std::vector: resize() would zero 86 MB per chunk on the

@@ -1,6 +1,6 @@
 // Index creation: the database re-encoded for the device (bitmaps tile by tile, segment classes, union bitmap of the tile
 // pruning, locator table, exact-match table), the taxonomy, the ln-factorial tables; handle options.
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 
 // Two handles on ONE device driven side by side (rtx_raxtax_multi with `--devices 0,0`, the eight-handle test: rehearsals of the multi-GPU
 // path) with two streams each for RTX_OPT_OVERLAP oversubscribe the hardware queues: a run whose chunks change size fell to a tenth of its
@@ -90,18 +90,7 @@ static int create_common(int device, uint64_t n_total, uint64_t ref_lo, uint64_t
         return RTX_ERR_INVALID;
     }
     const uint64_t n_refs = ref_hi - ref_lo;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
+    if (const int rc = check_device(device)) return rc;
     auto ix = new rtx_index();
     ix->device = device;
     ix->n_refs = n_refs;

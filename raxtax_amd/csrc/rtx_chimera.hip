@@ -17,7 +17,7 @@
 //   chimera_reduce_kernel  one wave per read: lane (direction, checkpoint) takes the tiles in ascending order (the first tile that holds the
 //                          maximum holds the lowest reference), lane 0 builds the record (chimera_record).
 // Vector stores and plain C++, no atomics.
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 #include "rtx_hit_common.hpp"
 
 namespace {
@@ -165,27 +165,15 @@ __global__ __launch_bounds__(64) void chimera_reduce_kernel(ChimParams p) {
     }
 }
 
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-
 constexpr uint64_t kBestBudget = 1ull << 30, kListBudget = 1ull << 29;  // bytes of a slice's checkpoint array / row lists
 
 }  // namespace
 
 static_assert(sizeof(rtx_chimera_rec) == 48 && sizeof(ChimRec) == 48, "twelve uint32");
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
-// classifies beside the stage.
-struct rtx_chimera {
+struct rtx_chimera : StageShell {  // (the events stand around the scan kernels of a slice; kernel_ms is their sum over the slices of a run)
     const rtx_index *ix = nullptr;
-    int device = -1;
     uint32_t S = 0, mindelta = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the scan kernels of a slice (rtx_chimera_kernel_time)
-    float kernel_ms = 0.f;
     DevBuf<uint8_t> d_packed, d_bases;
     DevBuf<uint64_t> d_base_off;
     DevBuf<uint32_t> d_lists, d_n_valid, d_ids, d_out;
@@ -194,11 +182,6 @@ struct rtx_chimera {
     PinBuf<uint8_t> h_packed;
     PinBuf<uint64_t> h_base_off;
     PinBuf<uint32_t> h_ids, h_out;
-    ~rtx_chimera() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace rtx {
@@ -230,24 +213,14 @@ int rtx_chimera_create(const rtx_index *index, const rtx_chimera_params *params,
     RTX_HIP(hipSetDevice(index->device));
     auto c = new rtx_chimera();
     c->ix = index;
-    c->device = index->device;
     c->S = params->segments;
     c->mindelta = params->mindelta;
-    if (hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&c->ev0) != hipSuccess ||
-        hipEventCreate(&c->ev1) != hipSuccess) {
-        set_error("hipStreamCreate / hipEventCreate failed");
-        delete c;
-        return RTX_ERR_HIP;
-    }
+    if (const int rc = c->open(index->device)) { delete c; return rc; }  // (the handle's device was checked when the handle was made)
     *out = c;
     return RTX_OK;
 }
 
-void rtx_chimera_destroy(rtx_chimera *c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    delete c;
-}
+void rtx_chimera_destroy(rtx_chimera *c) { destroy(c); }
 
 int rtx_chimera_run(rtx_chimera *c, uint64_t n, const uint8_t *bases, const uint64_t *base_off, rtx_chimera_rec *out) {
     if (!c) { set_error("rtx_chimera_run: null argument"); return RTX_ERR_INVALID; }
@@ -255,14 +228,10 @@ int rtx_chimera_run(rtx_chimera *c, uint64_t n, const uint8_t *bases, const uint
     if (n == 0) return RTX_OK;
     if (n > 0x7FFFFFF0ull) { set_error("rtx_chimera_run: %llu reads in one batch (at most 2^31 - 16)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!base_off || !out) { set_error("rtx_chimera_run: null argument"); return RTX_ERR_INVALID; }
+    if (const int rc = rtx::check_reads("rtx_chimera_run", n, base_off, bases, ~0ull)) return rc;
     uint32_t max_pos = 0;
-    for (uint64_t q = 0; q < n; q++) {
-        if (base_off[q + 1] < base_off[q]) { set_error("base_off not monotone at query %llu", (unsigned long long)q); return RTX_ERR_INVALID; }
-        const uint64_t len = base_off[q + 1] - base_off[q];
-        max_pos = std::max(max_pos, chimera_n_pos(len > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)len));
-    }
+    for (uint64_t q = 0; q < n; q++) max_pos = std::max(max_pos, chimera_n_pos((uint32_t)std::min<uint64_t>(base_off[q + 1] - base_off[q], 0xFFFFFFFFull)));
     const uint64_t total = base_off[n] - base_off[0];
-    if (total && !bases) { set_error("rtx_chimera_run: null bases"); return RTX_ERR_INVALID; }
     const rtx_index *ix = c->ix;
     RTX_HIP(hipSetDevice(c->device));
     const uint32_t S = c->S, nt = ix->ntiles;
@@ -277,18 +246,7 @@ int rtx_chimera_run(rtx_chimera *c, uint64_t n, const uint8_t *bases, const uint
         (rc = grow(c->d_cpg, slice * 2 * S)) || (rc = grow(c->d_best, slice * 2 * S * nt)))
         return rc;
     hipStream_t s = c->stream;
-    for (uint64_t q = 0; q <= n; q++) c->h_base_off[q] = base_off[q] - base_off[0];
-    // two bases per byte over PCIe; a byte above 15 is no code: such a batch travels as it is (rtx_batch_prefetch)
-    const bool packed = total == 0 || rtx::pack_nibbles_mt(bases + base_off[0], total, c->h_packed.data(), rtx::host_threads(4u));
-    if (!packed) std::memcpy(c->h_packed.data(), bases + base_off[0], total);
-    if (total) RTX_HIP(hipMemcpyAsync(c->d_packed.p, c->h_packed.data(), packed ? (total + 1) / 2 : total, hipMemcpyHostToDevice, s));
-    RTX_HIP(hipMemcpyAsync(c->d_base_off.p, c->h_base_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (packed) {
-        rtx::launch_unpack_nibbles(s, c->d_packed.p, c->d_bases.p, total, total + 64);
-    } else {
-        if (total) RTX_HIP(hipMemcpyAsync(c->d_bases.p, c->d_packed.p, total, hipMemcpyDeviceToDevice, s));
-        RTX_HIP(hipMemsetAsync(c->d_bases.p + total, 0, 64, s));
-    }
+    if ((rc = upload_packed_reads(s, n, bases, base_off, c->h_packed, c->h_base_off, c->d_packed, c->d_base_off, c->d_bases))) return rc;
     ChimParams p{};
     p.bases = c->d_bases.p;
     p.base_off = c->d_base_off.p;
@@ -336,20 +294,15 @@ int rtx_chimera_run(rtx_chimera *c, uint64_t n, const uint8_t *bases, const uint
         hipLaunchKernelGGL(chimera_reduce_kernel, dim3(m), dim3(64), 0, s, p);
         RTX_HIP(hipGetLastError());
         RTX_HIP(hipMemcpyAsync(c->h_out.data(), c->d_out.p, (size_t)m * 48, hipMemcpyDeviceToHost, s));
-        RTX_HIP(hipStreamSynchronize(s));
-        float ms = 0.f;
-        (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+        const float ms = c->kernel_ms;  // of the slices before this one
+        if ((rc = c->wait())) return rc;
         c->kernel_ms += ms;
         std::memcpy(out + q0, c->h_out.data(), (size_t)m * 48);
     }
     return RTX_OK;
 }
 
-int rtx_chimera_kernel_time(const rtx_chimera *c, float *ms) {
-    if (!c || !ms) { set_error("rtx_chimera_kernel_time: null argument"); return RTX_ERR_INVALID; }
-    *ms = c->kernel_ms;
-    return RTX_OK;
-}
+int rtx_chimera_kernel_time(const rtx_chimera *c, float *ms) { return kernel_time("rtx_chimera_kernel_time", c, ms); }
 
 int rtx_index_set_chimera(rtx_index *index, const rtx_chimera_params *params) {
     if (!index) { set_error("rtx_index_set_chimera: null index"); return RTX_ERR_INVALID; }

@@ -13,9 +13,7 @@
 //                 window is shifted by one nibble per offset; per (offset, tag) two ANDs, two folds of a nibble to a bit and two
 //                 popcounts (demux_end, rtx_math.hpp).  The pair table is dense, (n5 + 1) x (n3 + 1) uint32 in HBM, one load per read.
 //                 rtx_demux_read and the x86 emulator call the same demux_read.  Vector stores and plain C++, no atomics, no LDS.
-#include <memory>
-
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 
 #include "host_demux.hpp"
 
@@ -57,21 +55,9 @@ __global__ __launch_bounds__(256) void demux_kernel(DemuxKernelParams p) {
     p.info[q] = info;
 }
 
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-
 }  // namespace
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
-// classifies beside the stage.
-struct rtx_demux {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the kernel (rtx_demux_kernel_time)
-    float kernel_ms = 0.f;
+struct rtx_demux : StageShell {
     uint32_t n5 = 0, n3 = 0, max_mismatches = 0, max_offset = 0;
     DevBuf<DemuxTag> d_tags;
     DevBuf<uint32_t> d_table;
@@ -79,11 +65,6 @@ struct rtx_demux {
     DevBuf<uint32_t> d_len, d_out;
     PinBuf<uint8_t> h_rows;
     PinBuf<uint32_t> h_len, h_out;
-    ~rtx_demux() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace rtx {
@@ -123,43 +104,28 @@ int rtx_demux_create(int device, const rtx_demux_tag *tags, uint32_t n_tags, con
     *out = nullptr;
     rtx::DemuxSet set;
     if (const int rc = rtx::demux_build("rtx_demux_create", tags, n_tags, pairs, n_pairs, params, set)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
-    std::unique_ptr<rtx_demux> d(new rtx_demux());
-    d->device = device;
+    if (const int rc = check_device(device)) return rc;
+    auto d = new rtx_demux();
     d->n5 = set.n5;
     d->n3 = set.n3;
     d->max_mismatches = set.max_mismatches;
     d->max_offset = set.max_offset;
     const std::vector<uint32_t> table = set.dense_table();
-    int rc;
-    if ((rc = d->d_tags.alloc(set.tags.size())) || (rc = d->d_table.alloc(table.size()))) return rc;
-    RTX_HIP(hipMemcpy(d->d_tags.p, set.tags.data(), set.tags.size() * sizeof(DemuxTag), hipMemcpyHostToDevice));
-    RTX_HIP(hipMemcpy(d->d_table.p, table.data(), table.size() * 4, hipMemcpyHostToDevice));
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&d->ev0) != hipSuccess ||
-        hipEventCreate(&d->ev1) != hipSuccess) {
-        set_error("hipStreamCreate / hipEventCreate failed");
-        return RTX_ERR_HIP;
-    }
-    *out = d.release();
+    auto upload = [&]() -> int {
+        int rc;
+        if ((rc = d->d_tags.alloc(set.tags.size())) || (rc = d->d_table.alloc(table.size()))) return rc;
+        RTX_HIP(hipMemcpy(d->d_tags.p, set.tags.data(), set.tags.size() * sizeof(DemuxTag), hipMemcpyHostToDevice));
+        RTX_HIP(hipMemcpy(d->d_table.p, table.data(), table.size() * 4, hipMemcpyHostToDevice));
+        return RTX_OK;
+    };
+    int rc = d->open(device);
+    if (!rc) rc = upload();
+    if (rc) { delete d; return rc; }
+    *out = d;
     return RTX_OK;
 }
 
-void rtx_demux_destroy(rtx_demux *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    delete d;
-}
+void rtx_demux_destroy(rtx_demux *d) { destroy(d); }
 
 int rtx_demux_run(rtx_demux *d, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *sample, uint32_t *lo, uint32_t *hi,
                   uint32_t *hit, uint32_t *info) {
@@ -167,11 +133,7 @@ int rtx_demux_run(rtx_demux *d, uint64_t n, const uint8_t *bases, const uint64_t
     if (n == 0) return RTX_OK;
     if (n > 0x7FFFFFFEull) { set_error("rtx_demux_run: %llu reads in one batch (at most 2^31 - 2)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!base_off || !sample || !lo || !hi || !hit || !info) { set_error("rtx_demux_run: null argument"); return RTX_ERR_INVALID; }
-    for (uint64_t q = 0; q < n; q++) {
-        if (base_off[q + 1] < base_off[q]) { set_error("base_off not monotone at query %llu", (unsigned long long)q); return RTX_ERR_INVALID; }
-        if (base_off[q + 1] - base_off[q] > 0xFFFFFFFFull) { set_error("rtx_demux_run: read %llu has %llu bases (at most 2^32 - 1)", (unsigned long long)q, (unsigned long long)(base_off[q + 1] - base_off[q])); return RTX_ERR_INVALID; }
-    }
-    if (base_off[n] != base_off[0] && !bases) { set_error("rtx_demux_run: null bases"); return RTX_ERR_INVALID; }
+    if (const int rc = rtx::check_reads("rtx_demux_run", n, base_off, bases, 0xFFFFFFFFull)) return rc;
     RTX_HIP(hipSetDevice(d->device));
     const uint32_t w = demux_window(d->max_offset), stride = trim_row_stride(w);  // (16 or 32: the 3' rows are aligned as well)
     const size_t row_bytes = (size_t)n * stride * 2u;
@@ -181,23 +143,7 @@ int rtx_demux_run(rtx_demux *d, uint64_t n, const uint8_t *bases, const uint64_t
         return rc;
     uint8_t *h5 = d->h_rows.data(), *h3 = h5 + (size_t)n * stride;
     uint32_t *hl = d->h_len.data();
-    auto stage = [&](uint64_t a, uint64_t b) {
-        for (uint64_t q = a; q < b; q++) {
-            const uint8_t *x = bases + base_off[q];
-            const uint64_t len = base_off[q + 1] - base_off[q];
-            hl[q] = (uint32_t)len;
-            trim_stage_row(x, len, w, false, h5 + q * stride);
-            trim_stage_row(x, len, w, true, h3 + q * stride);
-        }
-    };
-    const unsigned nt = (unsigned)std::min<uint64_t>(rtx::host_threads(4u), (n + 4095) / 4096);
-    if (nt <= 1) {
-        stage(0, n);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned i = 0; i < nt; i++) th.emplace_back(stage, n * i / nt, n * (i + 1) / nt);
-        for (auto &x : th) x.join();
-    }
+    stage_end_rows(n, bases, base_off, w, stride, w, stride, h5, h3, hl);
     hipStream_t s = d->stream;
     RTX_HIP(hipMemcpyAsync(d->d_rows.p, h5, row_bytes, hipMemcpyHostToDevice, s));
     RTX_HIP(hipMemcpyAsync(d->d_len.p, hl, n * 4, hipMemcpyHostToDevice, s));
@@ -223,17 +169,11 @@ int rtx_demux_run(rtx_demux *d, uint64_t n, const uint8_t *bases, const uint64_t
     RTX_HIP(hipGetLastError());
     RTX_HIP(hipEventRecord(d->ev1, s));
     RTX_HIP(hipMemcpyAsync(d->h_out.data(), d->d_out.p, 5 * n * 4, hipMemcpyDeviceToHost, s));
-    RTX_HIP(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&d->kernel_ms, d->ev0, d->ev1);
-    uint32_t *const outs[5] = {sample, lo, hi, hit, info};
-    for (int k = 0; k < 5; k++) std::memcpy(outs[k], d->h_out.data() + (size_t)k * n, n * 4);
+    if ((rc = d->wait())) return rc;
+    scatter_columns(d->h_out.data(), n, {sample, lo, hi, hit, info});
     return RTX_OK;
 }
 
-int rtx_demux_kernel_time(const rtx_demux *d, float *ms) {
-    if (!d || !ms) { set_error("rtx_demux_kernel_time: null argument"); return RTX_ERR_INVALID; }
-    *ms = d->kernel_ms;
-    return RTX_OK;
-}
+int rtx_demux_kernel_time(const rtx_demux *d, float *ms) { return kernel_time("rtx_demux_kernel_time", d, ms); }
 
 }  // extern "C"

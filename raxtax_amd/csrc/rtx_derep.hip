@@ -19,7 +19,7 @@
 // it can meet an empty slot, so a cluster has exactly one owner.
 #include <atomic>
 
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 
 namespace {
 
@@ -107,63 +107,28 @@ namespace rtxi {
 void set_derep_hash_mask(uint64_t mask) { g_derep_hash_mask.store(mask); }
 }  // namespace rtxi
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
-// classifies beside the stage (a buffer that has to grow is replaced, with headroom, so that chunks of one size allocate once).
-struct rtx_derep {
-    int device = -1;
-    hipStream_t stream = nullptr;
+struct rtx_derep : StageShell {  // (its events are never recorded: there is no rtx_derep_kernel_time)
     DevBuf<uint8_t> d_packed, d_bases;
     DevBuf<uint64_t> d_base_off, d_hash;
     DevBuf<uint32_t> d_table, d_owner, d_cluster_min, d_rep;
     PinBuf<uint8_t> h_packed;
     PinBuf<uint64_t> h_base_off;
     PinBuf<uint32_t> h_rep;
-    ~rtx_derep() {
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
-
-namespace {
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-}  // namespace
 
 extern "C" {
 
 int rtx_derep_create(int device, rtx_derep **out) {
     if (!out) { set_error("rtx_derep_create: null argument"); return RTX_ERR_INVALID; }
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
+    if (const int rc = check_device(device)) return rc;
     auto d = new rtx_derep();
-    d->device = device;
-    if (hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking) != hipSuccess) {
-        set_error("hipStreamCreate failed");
-        delete d;
-        return RTX_ERR_HIP;
-    }
+    if (const int rc = d->open(device)) { delete d; return rc; }
     *out = d;
     return RTX_OK;
 }
 
-void rtx_derep_destroy(rtx_derep *d) {
-    if (!d) return;
-    (void)hipSetDevice(d->device);
-    delete d;
-}
+void rtx_derep_destroy(rtx_derep *d) { destroy(d); }
 
 int rtx_derep_run(rtx_derep *d, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *rep, uint64_t *n_unique) {
     if (!d || !n_unique) { set_error("rtx_derep_run: null argument"); return RTX_ERR_INVALID; }
@@ -171,10 +136,8 @@ int rtx_derep_run(rtx_derep *d, uint64_t n, const uint8_t *bases, const uint64_t
     if (n == 0) return RTX_OK;
     if (n > 0x7FFFFFFEull) { set_error("rtx_derep_run: %llu queries in one batch (at most 2^31 - 2)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!base_off || !rep) { set_error("rtx_derep_run: null argument"); return RTX_ERR_INVALID; }
-    for (uint64_t q = 0; q < n; q++)
-        if (base_off[q + 1] < base_off[q]) { set_error("base_off not monotone at query %llu", (unsigned long long)q); return RTX_ERR_INVALID; }
+    if (const int rc = rtx::check_reads("rtx_derep_run", n, base_off, bases, ~0ull)) return rc;
     const uint64_t total = base_off[n] - base_off[0];
-    if (total && !bases) { set_error("rtx_derep_run: null bases"); return RTX_ERR_INVALID; }
     RTX_HIP(hipSetDevice(d->device));
     uint32_t bits = 1;
     while ((1ull << bits) < 2ull * n) bits++;
@@ -185,18 +148,8 @@ int rtx_derep_run(rtx_derep *d, uint64_t n, const uint8_t *bases, const uint64_t
         (rc = grow(d->d_cluster_min, n)) || (rc = grow(d->d_rep, n + 1)) || (rc = d->d_table.alloc(slots)))
         return rc;
     hipStream_t s = d->stream;
-    for (uint64_t q = 0; q <= n; q++) d->h_base_off[q] = base_off[q] - base_off[0];
-    // two bases per byte over PCIe; a byte above 15 is no code of parser.rs:11-34: such a batch travels as it is (rtx_batch_prefetch)
-    const bool packed = total == 0 || rtx::pack_nibbles_mt(bases + base_off[0], total, d->h_packed.data(), rtx::host_threads(4u));
-    if (!packed) std::memcpy(d->h_packed.data(), bases + base_off[0], total);
-    if (total) RTX_HIP(hipMemcpyAsync(d->d_packed.p, d->h_packed.data(), packed ? (total + 1) / 2 : total, hipMemcpyHostToDevice, s));
-    RTX_HIP(hipMemcpyAsync(d->d_base_off.p, d->h_base_off.data(), (n + 1) * 8, hipMemcpyHostToDevice, s));
-    if (packed) {
-        rtx::launch_unpack_nibbles(s, d->d_packed.p, d->d_bases.p, total, total + 64);  // ... and 64 zero bytes: em_load_word reads past an end
-    } else {
-        if (total) RTX_HIP(hipMemcpyAsync(d->d_bases.p, d->d_packed.p, total, hipMemcpyDeviceToDevice, s));
-        RTX_HIP(hipMemsetAsync(d->d_bases.p + total, 0, 64, s));
-    }
+    // two bases per byte over PCIe, and 64 zero bytes behind the end: em_load_word reads past it
+    if ((rc = upload_packed_reads(s, n, bases, base_off, d->h_packed, d->h_base_off, d->d_packed, d->d_base_off, d->d_bases))) return rc;
     RTX_HIP(hipMemsetAsync(d->d_table.p, 0, slots * 4, s));
     RTX_HIP(hipMemsetAsync(d->d_cluster_min.p, 0xFF, n * 4, s));
     RTX_HIP(hipMemsetAsync(d->d_rep.p + n, 0, 4, s));

@@ -15,12 +15,9 @@
 //                 R', an AND and a zero-nibble count; left as soon as d > max_diffs); the best key per lane, a maximum over the wave
 //                 (rtx_wave.hpp: DPP, no atomics); then all 64 lanes write the merged codes and quality bytes, lane l position l + 64 k
 //                 (merge_base_at).  Lane 0 stores overlap, diffs, verdict and the merged length.  Vector stores and plain C++.
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 #include "rtx_wave.hpp"
 #include "host_merge.hpp"
-
-#include <chrono>
-#include <thread>
 
 namespace {
 
@@ -101,23 +98,9 @@ __global__ __launch_bounds__(256) void merge_kernel(MergeParams p) {
     }
 }
 
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs.
-struct rtx_merge {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the kernel (rtx_merge_kernel_time)
-    float kernel_ms = 0.f;
-    double times[3] = {0, 0, 0};              // rtx_merge_stage_times
+struct rtx_merge : StageShell {
     rtx_merge_params params{};
     MergeCfg cfg{};
     DevBuf<uint8_t> d_in, d_out;              // F bases | F quals | R bases | R quals; merged bases | merged quals
@@ -126,11 +109,6 @@ struct rtx_merge {
     PinBuf<uint8_t> h_in;
     PinBuf<uint64_t> h_off;
     PinBuf<uint32_t> h_res;
-    ~rtx_merge() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 extern "C" {
@@ -139,37 +117,16 @@ int rtx_merge_create(int device, const rtx_merge_params *params, rtx_merge **out
     if (!out || !params) { set_error("rtx_merge_create: null argument"); return RTX_ERR_INVALID; }
     *out = nullptr;
     if (const int rc = rtx::merge_check_params("rtx_merge_create", params)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
+    if (const int rc = check_device(device)) return rc;
     auto m = new rtx_merge();
-    m->device = device;
     m->params = *params;
     rtx::merge_cfg_init(m->cfg, *params);
-    if (hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&m->ev0) != hipSuccess ||
-        hipEventCreate(&m->ev1) != hipSuccess) {
-        set_error("hipStreamCreate / hipEventCreate failed");
-        delete m;
-        return RTX_ERR_HIP;
-    }
+    if (const int rc = m->open(device)) { delete m; return rc; }
     *out = m;
     return RTX_OK;
 }
 
-void rtx_merge_destroy(rtx_merge *m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    delete m;
-}
+void rtx_merge_destroy(rtx_merge *m) { destroy(m); }
 
 int rtx_merge_run(rtx_merge *m, uint64_t n, const uint8_t *f_bases, const uint8_t *f_quals, const uint64_t *f_off, const uint8_t *r_bases,
                   const uint8_t *r_quals, const uint64_t *r_off, uint32_t *overlap, uint32_t *diffs, uint32_t *verdict, uint32_t *merged_len,
@@ -181,7 +138,7 @@ int rtx_merge_run(rtx_merge *m, uint64_t n, const uint8_t *f_bases, const uint8_
     }
     if (n > 0x7FFFFFF0ull) { set_error("rtx_merge_run: %llu pairs in one batch (at most 2^31 - 16)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!f_off || !r_off || !overlap || !diffs || !verdict || !merged_len || !slot_off) { set_error("rtx_merge_run: null argument"); return RTX_ERR_INVALID; }
-    const double t0 = now_s();
+    m->begin();
     int rc;
     if ((rc = m->h_off.resize(3 * (n + 1)))) return rc;
     uint64_t *hf = m->h_off.data(), *hr = hf + n + 1, *hs = hr + n + 1;
@@ -213,7 +170,7 @@ int rtx_merge_run(rtx_merge *m, uint64_t n, const uint8_t *f_bases, const uint8_
     const uint64_t cnt[4] = {bf, bf, br, br}, dst[4] = {0, bf, 2 * bf, 2 * bf + br};
     const unsigned nt = std::max(1u, (unsigned)std::min<uint64_t>(rtx::host_threads(4u), (in_bytes + (1u << 22) - 1) >> 22));
     std::vector<uint8_t> seen(nt, 0);
-    auto stage = [&](unsigned k) {
+    rtx::parallel_ranges(nt, nt, 1, [&](unsigned k, uint64_t, uint64_t) {  // (the split is by bytes: thread k takes its share of each array)
         uint8_t s = 0;
         for (int a = 0; a < 4; a++) {
             const uint64_t lo = cnt[a] * k / nt, hi = cnt[a] * (k + 1) / nt;
@@ -223,17 +180,10 @@ int rtx_merge_run(rtx_merge *m, uint64_t n, const uint8_t *f_bases, const uint8_
                 for (uint64_t j = lo; j < hi; j++) s |= src[a][j];
         }
         seen[k] = s;
-    };
-    if (nt <= 1) {
-        stage(0);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned k = 0; k < nt; k++) th.emplace_back(stage, k);
-        for (auto &x : th) x.join();
-    }
+    });
     for (uint8_t s : seen)
         if (s & 0x80u) { set_error("rtx_merge_run: a quality byte of 128 or more"); return RTX_ERR_INVALID; }
-    const double t1 = now_s();
+    m->staged();
     hipStream_t s = m->stream;
     if (in_bytes) RTX_HIP(hipMemcpyAsync(m->d_in.p, hb, in_bytes, hipMemcpyHostToDevice, s));
     RTX_HIP(hipMemcpyAsync(m->d_off.p, hf, 3 * (n + 1) * 8, hipMemcpyHostToDevice, s));
@@ -262,32 +212,16 @@ int rtx_merge_run(rtx_merge *m, uint64_t n, const uint8_t *f_bases, const uint8_
         RTX_HIP(hipMemcpyAsync(merged_bases, m->d_out.p, slots, hipMemcpyDeviceToHost, s));
         RTX_HIP(hipMemcpyAsync(merged_quals, m->d_out.p + slots, slots, hipMemcpyDeviceToHost, s));
     }
-    RTX_HIP(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&m->kernel_ms, m->ev0, m->ev1);
-    const uint32_t *res = m->h_res.data();
-    std::memcpy(overlap, res, n * 4);
-    std::memcpy(diffs, res + n, n * 4);
-    std::memcpy(verdict, res + 2 * n, n * 4);
-    std::memcpy(merged_len, res + 3 * n, n * 4);
+    if ((rc = m->wait())) return rc;
+    scatter_columns(m->h_res.data(), n, {overlap, diffs, verdict, merged_len});
     std::memcpy(slot_off, hs, (n + 1) * 8);
-    const double t2 = now_s();
-    m->times[0] = t1 - t0;
-    m->times[1] = std::max(0.0, t2 - t1 - (double)m->kernel_ms * 1e-3);
-    m->times[2] = t2 - t0;
+    m->finish();
     return RTX_OK;
 }
 
-int rtx_merge_kernel_time(const rtx_merge *m, float *ms) {
-    if (!m || !ms) { set_error("rtx_merge_kernel_time: null argument"); return RTX_ERR_INVALID; }
-    *ms = m->kernel_ms;
-    return RTX_OK;
-}
+int rtx_merge_kernel_time(const rtx_merge *m, float *ms) { return kernel_time("rtx_merge_kernel_time", m, ms); }
 
-int rtx_merge_stage_times(const rtx_merge *m, double seconds[3]) {
-    if (!m || !seconds) { set_error("rtx_merge_stage_times: null argument"); return RTX_ERR_INVALID; }
-    for (int i = 0; i < 3; i++) seconds[i] = m->times[i];
-    return RTX_OK;
-}
+int rtx_merge_stage_times(const rtx_merge *m, double seconds[3]) { return stage_times("rtx_merge_stage_times", m, seconds); }
 
 int rtx_merge_queries(rtx_merge *m, const rtx_queries *fwd, const rtx_queries *rev, const char *const *skip, uint64_t n_skip, rtx_queries **merged) {
     if (!fwd || !rev || !merged || (n_skip && !skip)) { set_error("rtx_merge_queries: null argument"); return RTX_ERR_INVALID; }

@@ -16,11 +16,8 @@
 //                next step -- are read from the lane that holds them.  A read is streamed to its end also behind its cut: a byte outside
 //                Q 0 .. 93 anywhere in the range decides the verdict.  Lane 0 of the group stores hi, ee and the verdict.
 //                Vector stores and plain C++, no atomics.
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 #include "host_qual.hpp"
-
-#include <chrono>
-#include <thread>
 
 namespace {
 
@@ -103,24 +100,9 @@ __global__ __launch_bounds__(256) void qual_kernel(QualParams p) {
     }
 }
 
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
-// classifies beside the stage.
-struct rtx_qual {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the kernel (rtx_qual_kernel_time)
-    float kernel_ms = 0.f;
-    double times[3] = {0, 0, 0};              // rtx_qual_stage_times
+struct rtx_qual : StageShell {
     QualCfg cfg{};
     DevBuf<uint64_t> d_table, d_ee;
     DevBuf<uint8_t> d_bytes;
@@ -128,11 +110,6 @@ struct rtx_qual {
     PinBuf<uint8_t> h_bytes;
     PinBuf<uint32_t> h_in, h_out;
     PinBuf<uint64_t> h_ee;
-    ~rtx_qual() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace rtx {
@@ -148,27 +125,10 @@ int rtx_qual_create(int device, const rtx_qual_params *params, rtx_qual **out) {
     if (!out || !params) { set_error("rtx_qual_create: null argument"); return RTX_ERR_INVALID; }
     *out = nullptr;
     if (const int rc = rtx::qual_check_params("rtx_qual_create", params)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
+    if (const int rc = check_device(device)) return rc;
     auto q = new rtx_qual();
-    q->device = device;
     rtx::qual_cfg_init(q->cfg, *params);
-    if (hipStreamCreateWithFlags(&q->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&q->ev0) != hipSuccess ||
-        hipEventCreate(&q->ev1) != hipSuccess) {
-        set_error("hipStreamCreate / hipEventCreate failed");
-        delete q;
-        return RTX_ERR_HIP;
-    }
+    if (const int rc = q->open(device)) { delete q; return rc; }
     if (q->d_table.alloc(RTX_QUAL_TABLE) != RTX_OK ||
         hipMemcpy(q->d_table.p, rtx::qual_table(), sizeof(uint64_t) * RTX_QUAL_TABLE, hipMemcpyHostToDevice) != hipSuccess) {
         set_error("rtx_qual_create: the error table could not be uploaded");
@@ -179,11 +139,7 @@ int rtx_qual_create(int device, const rtx_qual_params *params, rtx_qual **out) {
     return RTX_OK;
 }
 
-void rtx_qual_destroy(rtx_qual *q) {
-    if (!q) return;
-    (void)hipSetDevice(q->device);
-    delete q;
-}
+void rtx_qual_destroy(rtx_qual *q) { destroy(q); }
 
 int rtx_qual_run(rtx_qual *q, uint64_t n, const uint8_t *bases, const uint8_t *quals, const uint64_t *base_off, const uint32_t *lo_in,
                  const uint32_t *hi_in, uint32_t *hi_out, uint64_t *ee_out, uint32_t *verdict_out) {
@@ -191,22 +147,12 @@ int rtx_qual_run(rtx_qual *q, uint64_t n, const uint8_t *bases, const uint8_t *q
     if (n == 0) return RTX_OK;
     if (n > 0x7FFFFFF0ull) { set_error("rtx_qual_run: %llu reads in one batch (at most 2^31 - 16)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!base_off || !hi_out || !ee_out || !verdict_out || (lo_in == nullptr) != (hi_in == nullptr)) { set_error("rtx_qual_run: null argument"); return RTX_ERR_INVALID; }
-    const double t0 = now_s();
+    q->begin();
     int rc;
     if ((rc = q->h_in.resize(2 * n))) return rc;
     uint32_t *h_off = q->h_in.data(), *h_len = h_off + n;
     uint64_t pieces = 0;
-    for (uint64_t r = 0; r < n; r++) {
-        if (base_off[r + 1] < base_off[r]) { set_error("base_off not monotone at query %llu", (unsigned long long)r); return RTX_ERR_INVALID; }
-        const uint64_t len = base_off[r + 1] - base_off[r];
-        if (len > RTX_QUAL_MAX_READ) { set_error("rtx_qual_run: read %llu has %llu bases (at most %u)", (unsigned long long)r, (unsigned long long)len, RTX_QUAL_MAX_READ); return RTX_ERR_INVALID; }
-        const uint32_t lo = lo_in ? lo_in[r] : 0u, hi = hi_in ? hi_in[r] : (uint32_t)len;
-        if (lo > hi || hi > len) { set_error("rtx_qual_run: read %llu of %llu bases has the range [%u, %u)", (unsigned long long)r, (unsigned long long)len, lo, hi); return RTX_ERR_INVALID; }
-        h_off[r] = (uint32_t)pieces;
-        h_len[r] = hi - lo;
-        pieces += (hi - lo + kQualPiece - 1u) / kQualPiece;
-        if (pieces > 0xFFFFFFFFull) { set_error("rtx_qual_run: the ranges of the batch take more than 2^36 bytes"); return RTX_ERR_INVALID; }
-    }
+    if ((rc = rtx::layout_ranges("rtx_qual_run", n, base_off, lo_in, hi_in, RTX_QUAL_MAX_READ, kQualPiece, h_off, h_len, &pieces))) return rc;
     if (pieces && (!bases || !quals)) { set_error("rtx_qual_run: null bases or quals"); return RTX_ERR_INVALID; }
     RTX_HIP(hipSetDevice(q->device));
     const size_t bytes = (size_t)pieces * kQualPiece;
@@ -214,26 +160,19 @@ int rtx_qual_run(rtx_qual *q, uint64_t n, const uint8_t *bases, const uint8_t *q
         (rc = grow(q->d_in, 2 * n)) || (rc = grow(q->d_out, 2 * n)) || (rc = grow(q->d_ee, n)))
         return rc;
     uint8_t *hb = q->h_bytes.data();
-    const unsigned nt = std::max(1u, (unsigned)std::min<uint64_t>(rtx::host_threads(4u), (n + 4095) / 4096));
-    std::vector<uint8_t> seen(nt, 0);
-    auto stage = [&](unsigned k, uint64_t a, uint64_t b) {
+    const unsigned nt = std::max(1u, rtx::host_threads(4u));
+    std::vector<uint8_t> seen(nt, 0);  // per thread of the fan
+    rtx::parallel_ranges(n, nt, 4096, [&](unsigned k, uint64_t a, uint64_t b) {
         uint8_t s = 0;
         for (uint64_t r = a; r < b; r++) {
             const uint64_t at = base_off[r] + (lo_in ? lo_in[r] : 0u);
             if (h_len[r]) s |= rtx::qual_stage(bases + at, quals + at, h_len[r], hb + (size_t)h_off[r] * kQualPiece);
         }
         seen[k] = s;
-    };
-    if (nt <= 1) {
-        stage(0, 0, n);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned i = 0; i < nt; i++) th.emplace_back(stage, i, n * i / nt, n * (i + 1) / nt);
-        for (auto &x : th) x.join();
-    }
+    });
     for (uint8_t s : seen)
         if (s & 0x80u) { set_error("rtx_qual_run: a quality byte of 128 or more"); return RTX_ERR_INVALID; }
-    const double t1 = now_s();
+    q->staged();
     hipStream_t s = q->stream;
     if (bytes) RTX_HIP(hipMemcpyAsync(q->d_bytes.p, hb, bytes, hipMemcpyHostToDevice, s));
     RTX_HIP(hipMemcpyAsync(q->d_in.p, h_off, 2 * n * 4, hipMemcpyHostToDevice, s));
@@ -254,29 +193,17 @@ int rtx_qual_run(rtx_qual *q, uint64_t n, const uint8_t *bases, const uint8_t *q
     RTX_HIP(hipEventRecord(q->ev1, s));
     RTX_HIP(hipMemcpyAsync(q->h_out.data(), q->d_out.p, 2 * n * 4, hipMemcpyDeviceToHost, s));
     RTX_HIP(hipMemcpyAsync(q->h_ee.data(), q->d_ee.p, n * 8, hipMemcpyDeviceToHost, s));
-    RTX_HIP(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&q->kernel_ms, q->ev0, q->ev1);
+    if ((rc = q->wait())) return rc;
     for (uint64_t r = 0; r < n; r++) hi_out[r] = (lo_in ? lo_in[r] : 0u) + q->h_out.data()[r];
-    std::memcpy(verdict_out, q->h_out.data() + n, n * 4);
+    scatter_columns(q->h_out.data() + n, n, {verdict_out});
     std::memcpy(ee_out, q->h_ee.data(), n * 8);
-    const double t2 = now_s();
-    q->times[0] = t1 - t0;
-    q->times[1] = std::max(0.0, t2 - t1 - (double)q->kernel_ms * 1e-3);
-    q->times[2] = t2 - t0;
+    q->finish();
     return RTX_OK;
 }
 
-int rtx_qual_kernel_time(const rtx_qual *q, float *ms) {
-    if (!q || !ms) { set_error("rtx_qual_kernel_time: null argument"); return RTX_ERR_INVALID; }
-    *ms = q->kernel_ms;
-    return RTX_OK;
-}
+int rtx_qual_kernel_time(const rtx_qual *q, float *ms) { return kernel_time("rtx_qual_kernel_time", q, ms); }
 
-int rtx_qual_stage_times(const rtx_qual *q, double seconds[3]) {
-    if (!q || !seconds) { set_error("rtx_qual_stage_times: null argument"); return RTX_ERR_INVALID; }
-    for (int i = 0; i < 3; i++) seconds[i] = q->times[i];
-    return RTX_OK;
-}
+int rtx_qual_stage_times(const rtx_qual *q, double seconds[3]) { return stage_times("rtx_qual_stage_times", q, seconds); }
 
 int rtx_index_set_quality(rtx_index *index, const rtx_qual_params *params) {
     if (!index) { set_error("rtx_index_set_quality: null index"); return RTX_ERR_INVALID; }

@@ -15,12 +15,9 @@
 //                own steps and keeps its own counts and its first hit.  Behind the loop windows and hits are summed and the lowest
 //                hitting position is a minimum over the 16 lanes (DPP row operations, rtx_wave.hpp); its source comes from the lane
 //                that holds it.  Lane 0 of the group stores the five results.  Vector stores and plain C++, no atomics.
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 #include "rtx_wave.hpp"
 #include "host_screen.hpp"
-
-#include <chrono>
-#include <thread>
 
 namespace {
 
@@ -67,24 +64,9 @@ __global__ __launch_bounds__(256) void screen_kernel(ScreenParams p) {
     }
 }
 
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-
-double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-
 }  // namespace
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
-// classifies beside the stage.
-struct rtx_screen {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the kernel (rtx_screen_kernel_time)
-    float kernel_ms = 0.f;
-    double times[3] = {0, 0, 0};              // rtx_screen_stage_times
+struct rtx_screen : StageShell {
     rtx_screen_params params{};
     uint32_t log2m = 0;
     DevBuf<ScreenSlot> d_table;
@@ -92,11 +74,6 @@ struct rtx_screen {
     DevBuf<uint32_t> d_in, d_out;             // off16 | len; windows | hits | first | source | verdict
     PinBuf<uint8_t> h_bytes;
     PinBuf<uint32_t> h_in, h_out;
-    ~rtx_screen() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace rtx {
@@ -112,28 +89,11 @@ int rtx_screen_create(int device, const rtx_screen_set *set, const rtx_screen_pa
     if (!out || !params || !set || !set->data) { set_error("rtx_screen_create: null argument"); return RTX_ERR_INVALID; }
     *out = nullptr;
     if (const int rc = rtx::screen_check_params("rtx_screen_create", params)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
+    if (const int rc = check_device(device)) return rc;
     auto s = new rtx_screen();
-    s->device = device;
     s->params = *params;
     s->log2m = set->data->log2m;
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&s->ev0) != hipSuccess ||
-        hipEventCreate(&s->ev1) != hipSuccess) {
-        set_error("hipStreamCreate / hipEventCreate failed");
-        delete s;
-        return RTX_ERR_HIP;
-    }
+    if (const int rc = s->open(device)) { delete s; return rc; }
     const std::vector<ScreenSlot> &slots = set->data->slots;
     if (s->d_table.alloc(slots.size()) != RTX_OK ||
         hipMemcpy(s->d_table.p, slots.data(), sizeof(ScreenSlot) * slots.size(), hipMemcpyHostToDevice) != hipSuccess) {
@@ -145,11 +105,7 @@ int rtx_screen_create(int device, const rtx_screen_set *set, const rtx_screen_pa
     return RTX_OK;
 }
 
-void rtx_screen_destroy(rtx_screen *s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    delete s;
-}
+void rtx_screen_destroy(rtx_screen *s) { destroy(s); }
 
 int rtx_screen_run(rtx_screen *s, uint64_t n, const uint8_t *bases, const uint64_t *base_off, const uint32_t *lo_in, const uint32_t *hi_in,
                    uint32_t *windows, uint32_t *hits, uint32_t *first, uint32_t *source, uint32_t *verdict) {
@@ -157,22 +113,12 @@ int rtx_screen_run(rtx_screen *s, uint64_t n, const uint8_t *bases, const uint64
     if (n == 0) return RTX_OK;
     if (n > 0x0FFFFFF0ull) { set_error("rtx_screen_run: %llu reads in one batch (at most 2^28 - 16)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!base_off || !windows || !hits || !first || !source || !verdict || (lo_in == nullptr) != (hi_in == nullptr)) { set_error("rtx_screen_run: null argument"); return RTX_ERR_INVALID; }
-    const double t0 = now_s();
+    s->begin();
     int rc;
     if ((rc = s->h_in.resize(2 * n))) return rc;
     uint32_t *h_off = s->h_in.data(), *h_len = h_off + n;
     uint64_t pieces = 0;
-    for (uint64_t r = 0; r < n; r++) {
-        if (base_off[r + 1] < base_off[r]) { set_error("base_off not monotone at query %llu", (unsigned long long)r); return RTX_ERR_INVALID; }
-        const uint64_t len = base_off[r + 1] - base_off[r];
-        if (len > RTX_SCREEN_MAX_READ) { set_error("rtx_screen_run: read %llu has %llu bases (at most %u)", (unsigned long long)r, (unsigned long long)len, RTX_SCREEN_MAX_READ); return RTX_ERR_INVALID; }
-        const uint32_t lo = lo_in ? lo_in[r] : 0u, hi = hi_in ? hi_in[r] : (uint32_t)len;
-        if (lo > hi || hi > len) { set_error("rtx_screen_run: read %llu of %llu bases has the range [%u, %u)", (unsigned long long)r, (unsigned long long)len, lo, hi); return RTX_ERR_INVALID; }
-        h_off[r] = (uint32_t)pieces;
-        h_len[r] = hi - lo;
-        pieces += (hi - lo + kScreenPiece - 1u) / kScreenPiece;
-        if (pieces > 0xFFFFFFFFull) { set_error("rtx_screen_run: the ranges of the batch take more than 2^36 bytes"); return RTX_ERR_INVALID; }
-    }
+    if ((rc = rtx::layout_ranges("rtx_screen_run", n, base_off, lo_in, hi_in, RTX_SCREEN_MAX_READ, kScreenPiece, h_off, h_len, &pieces))) return rc;
     if (pieces && !bases) { set_error("rtx_screen_run: null bases"); return RTX_ERR_INVALID; }
     RTX_HIP(hipSetDevice(s->device));
     const size_t bytes = (size_t)pieces * kScreenPiece;
@@ -180,19 +126,11 @@ int rtx_screen_run(rtx_screen *s, uint64_t n, const uint8_t *bases, const uint64
         (rc = grow(s->d_out, 5 * n)))
         return rc;
     uint8_t *hb = s->h_bytes.data();
-    const unsigned nt = std::max(1u, (unsigned)std::min<uint64_t>(rtx::host_threads(4u), (n + 4095) / 4096));
-    auto stage = [&](uint64_t a, uint64_t b) {
+    rtx::parallel_ranges(n, rtx::host_threads(4u), 4096, [&](unsigned, uint64_t a, uint64_t b) {
         for (uint64_t r = a; r < b; r++)
             if (h_len[r]) memcpy(hb + (size_t)h_off[r] * kScreenPiece, bases + base_off[r] + (lo_in ? lo_in[r] : 0u), h_len[r]);
-    };
-    if (nt <= 1) {
-        stage(0, n);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned i = 0; i < nt; i++) th.emplace_back(stage, n * i / nt, n * (i + 1) / nt);
-        for (auto &x : th) x.join();
-    }
-    const double t1 = now_s();
+    });
+    s->staged();
     hipStream_t st = s->stream;
     if (bytes) RTX_HIP(hipMemcpyAsync(s->d_bytes.p, hb, bytes, hipMemcpyHostToDevice, st));
     RTX_HIP(hipMemcpyAsync(s->d_in.p, h_off, 2 * n * 4, hipMemcpyHostToDevice, st));
@@ -211,32 +149,15 @@ int rtx_screen_run(rtx_screen *s, uint64_t n, const uint8_t *bases, const uint64
     RTX_HIP(hipGetLastError());
     RTX_HIP(hipEventRecord(s->ev1, st));
     RTX_HIP(hipMemcpyAsync(s->h_out.data(), s->d_out.p, 5 * n * 4, hipMemcpyDeviceToHost, st));
-    RTX_HIP(hipStreamSynchronize(st));
-    (void)hipEventElapsedTime(&s->kernel_ms, s->ev0, s->ev1);
-    const uint32_t *o = s->h_out.data();
-    std::memcpy(windows, o, n * 4);
-    std::memcpy(hits, o + n, n * 4);
-    std::memcpy(first, o + 2 * n, n * 4);
-    std::memcpy(source, o + 3 * n, n * 4);
-    std::memcpy(verdict, o + 4 * n, n * 4);
-    const double t2 = now_s();
-    s->times[0] = t1 - t0;
-    s->times[1] = std::max(0.0, t2 - t1 - (double)s->kernel_ms * 1e-3);
-    s->times[2] = t2 - t0;
+    if ((rc = s->wait())) return rc;
+    scatter_columns(s->h_out.data(), n, {windows, hits, first, source, verdict});
+    s->finish();
     return RTX_OK;
 }
 
-int rtx_screen_kernel_time(const rtx_screen *s, float *ms) {
-    if (!s || !ms) { set_error("rtx_screen_kernel_time: null argument"); return RTX_ERR_INVALID; }
-    *ms = s->kernel_ms;
-    return RTX_OK;
-}
+int rtx_screen_kernel_time(const rtx_screen *s, float *ms) { return kernel_time("rtx_screen_kernel_time", s, ms); }
 
-int rtx_screen_stage_times(const rtx_screen *s, double seconds[3]) {
-    if (!s || !seconds) { set_error("rtx_screen_stage_times: null argument"); return RTX_ERR_INVALID; }
-    for (int i = 0; i < 3; i++) seconds[i] = s->times[i];
-    return RTX_OK;
-}
+int rtx_screen_stage_times(const rtx_screen *s, double seconds[3]) { return stage_times("rtx_screen_stage_times", s, seconds); }
 
 int rtx_index_set_screen(rtx_index *index, const rtx_screen_set *set, const rtx_screen_params *params) {
     if (!index) { set_error("rtx_index_set_screen: null index"); return RTX_ERR_INVALID; }

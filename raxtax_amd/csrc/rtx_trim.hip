@@ -14,7 +14,7 @@
 //                code selects (identity_step), Pv / Mv are 64 bits per lane, the score is followed at bit m - 1, the best (e, j) is kept
 //                with <=.  trim_read / trim_search (rtx_math.hpp) carry all of it; rtx_primer_search and the x86 emulator call the same.
 //                Vector stores and plain C++, no atomics, no LDS.
-#include "rtx_index.hpp"
+#include "rtx_stage.hpp"
 
 namespace {
 
@@ -41,32 +41,15 @@ __global__ __launch_bounds__(256) void trim_kernel(TrimParams p) {
     p.hit[q] = hit;
 }
 
-template <class T>
-int grow(DevBuf<T> &b, size_t count) {
-    if (b.p && count <= b.n) return RTX_OK;
-    return b.alloc(count + count / 4 + 64);
-}
-
 }  // namespace
 
-// One stream (non-blocking, no priority) and buffers that only grow: nothing is freed between runs, a hipFree would stall the handle that
-// classifies beside the stage.
-struct rtx_trim {
-    int device = -1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;  // around the kernel (rtx_trim_kernel_time)
-    float kernel_ms = 0.f;
+struct rtx_trim : StageShell {
     TrimPattern pat[RTX_TRIM_MAX_PATTERNS];
     uint32_t n5 = 0, n3 = 0, w5 = 0, w3 = 0;
     DevBuf<uint8_t> d_rows;
     DevBuf<uint32_t> d_len, d_out;
     PinBuf<uint8_t> h_rows;
     PinBuf<uint32_t> h_len, h_out;
-    ~rtx_trim() {
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
 };
 
 namespace rtx {
@@ -80,20 +63,8 @@ int rtx_trim_create(int device, const rtx_trim_pattern *pats, uint32_t n, rtx_tr
     *out = nullptr;
     if (n == 0) { set_error("rtx_trim_create: no patterns"); return RTX_ERR_INVALID; }
     if (const int rc = rtx::trim_check_patterns("rtx_trim_create", pats, n)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
-        set_error("no usable HIP device (requested %d of %d); libraxtax_hip has no CPU fallback", device, ndev);
-        return RTX_ERR_NO_DEVICE;
-    }
-    RTX_HIP(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    RTX_HIP(hipGetDeviceProperties(&prop, device));
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
-        set_error("device %d is %s; this library carries gfx950 (MI355X) code objects only", device, prop.gcnArchName);
-        return RTX_ERR_NO_DEVICE;
-    }
+    if (const int rc = check_device(device)) return rc;
     auto t = new rtx_trim();
-    t->device = device;
     for (uint32_t e = 0; e < 2u; e++)  // the 5' patterns, then the 3' ones, each end in the order of the list
         for (uint32_t i = 0; i < n; i++) {
             if (pats[i].end != e) continue;
@@ -103,32 +74,19 @@ int rtx_trim_create(int device, const rtx_trim_pattern *pats, uint32_t n, rtx_tr
             uint32_t &w = e ? t->w3 : t->w5;
             w = std::max(w, p.w);
         }
-    if (hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&t->ev0) != hipSuccess ||
-        hipEventCreate(&t->ev1) != hipSuccess) {
-        set_error("hipStreamCreate / hipEventCreate failed");
-        delete t;
-        return RTX_ERR_HIP;
-    }
+    if (const int rc = t->open(device)) { delete t; return rc; }
     *out = t;
     return RTX_OK;
 }
 
-void rtx_trim_destroy(rtx_trim *t) {
-    if (!t) return;
-    (void)hipSetDevice(t->device);
-    delete t;
-}
+void rtx_trim_destroy(rtx_trim *t) { destroy(t); }
 
 int rtx_trim_run(rtx_trim *t, uint64_t n, const uint8_t *bases, const uint64_t *base_off, uint32_t *lo, uint32_t *hi, uint32_t *hit) {
     if (!t) { set_error("rtx_trim_run: null argument"); return RTX_ERR_INVALID; }
     if (n == 0) return RTX_OK;
     if (n > 0x7FFFFFFEull) { set_error("rtx_trim_run: %llu reads in one batch (at most 2^31 - 2)", (unsigned long long)n); return RTX_ERR_INVALID; }
     if (!base_off || !lo || !hi || !hit) { set_error("rtx_trim_run: null argument"); return RTX_ERR_INVALID; }
-    for (uint64_t q = 0; q < n; q++) {
-        if (base_off[q + 1] < base_off[q]) { set_error("base_off not monotone at query %llu", (unsigned long long)q); return RTX_ERR_INVALID; }
-        if (base_off[q + 1] - base_off[q] > 0xFFFFFFFFull) { set_error("rtx_trim_run: read %llu has %llu bases (at most 2^32 - 1)", (unsigned long long)q, (unsigned long long)(base_off[q + 1] - base_off[q])); return RTX_ERR_INVALID; }
-    }
-    if (base_off[n] != base_off[0] && !bases) { set_error("rtx_trim_run: null bases"); return RTX_ERR_INVALID; }
+    if (const int rc = rtx::check_reads("rtx_trim_run", n, base_off, bases, 0xFFFFFFFFull)) return rc;
     RTX_HIP(hipSetDevice(t->device));
     const uint32_t s5 = t->n5 ? trim_row_stride(t->w5) : 0u, s3 = t->n3 ? trim_row_stride(t->w3) : 0u;
     const size_t row_bytes = (size_t)n * (s5 + s3);
@@ -138,24 +96,7 @@ int rtx_trim_run(rtx_trim *t, uint64_t n, const uint8_t *bases, const uint64_t *
         return rc;
     uint8_t *h5 = t->h_rows.data(), *h3 = h5 + (size_t)n * s5;  // (n * s5 is a multiple of 16: the 3' rows are aligned as well)
     uint32_t *hl = t->h_len.data();
-    const uint32_t w5 = t->w5, w3 = t->w3;
-    auto stage = [&](uint64_t a, uint64_t b) {
-        for (uint64_t q = a; q < b; q++) {
-            const uint8_t *x = bases + base_off[q];
-            const uint64_t len = base_off[q + 1] - base_off[q];
-            hl[q] = (uint32_t)len;
-            if (s5) trim_stage_row(x, len, w5, false, h5 + q * s5);
-            if (s3) trim_stage_row(x, len, w3, true, h3 + q * s3);
-        }
-    };
-    const unsigned nt = (unsigned)std::min<uint64_t>(rtx::host_threads(4u), (n + 4095) / 4096);
-    if (nt <= 1) {
-        stage(0, n);
-    } else {
-        std::vector<std::thread> th;
-        for (unsigned i = 0; i < nt; i++) th.emplace_back(stage, n * i / nt, n * (i + 1) / nt);
-        for (auto &x : th) x.join();
-    }
+    stage_end_rows(n, bases, base_off, t->w5, s5, t->w3, s3, h5, h3, hl);
     hipStream_t s = t->stream;
     if (row_bytes) RTX_HIP(hipMemcpyAsync(t->d_rows.p, h5, row_bytes, hipMemcpyHostToDevice, s));
     RTX_HIP(hipMemcpyAsync(t->d_len.p, hl, n * 4, hipMemcpyHostToDevice, s));
@@ -177,11 +118,8 @@ int rtx_trim_run(rtx_trim *t, uint64_t n, const uint8_t *bases, const uint64_t *
     RTX_HIP(hipGetLastError());
     RTX_HIP(hipEventRecord(t->ev1, s));
     RTX_HIP(hipMemcpyAsync(t->h_out.data(), t->d_out.p, 3 * n * 4, hipMemcpyDeviceToHost, s));
-    RTX_HIP(hipStreamSynchronize(s));
-    (void)hipEventElapsedTime(&t->kernel_ms, t->ev0, t->ev1);
-    std::memcpy(lo, t->h_out.data(), n * 4);
-    std::memcpy(hi, t->h_out.data() + n, n * 4);
-    std::memcpy(hit, t->h_out.data() + 2 * n, n * 4);
+    if ((rc = t->wait())) return rc;
+    scatter_columns(t->h_out.data(), n, {lo, hi, hit});
     return RTX_OK;
 }
 
@@ -205,10 +143,6 @@ int rtx_index_primers(const rtx_index *index, uint32_t *n) {
     return RTX_OK;
 }
 
-int rtx_trim_kernel_time(const rtx_trim *t, float *ms) {
-    if (!t || !ms) { set_error("rtx_trim_kernel_time: null argument"); return RTX_ERR_INVALID; }
-    *ms = t->kernel_ms;
-    return RTX_OK;
-}
+int rtx_trim_kernel_time(const rtx_trim *t, float *ms) { return kernel_time("rtx_trim_kernel_time", t, ms); }
 
 }  // extern "C"
