@@ -604,6 +604,96 @@ void rtx_derep_destroy(rtx_derep *d);
 int rtx_derep_plan(uint64_t n, const uint32_t *rep, uint32_t *uniq /*[n]*/, uint32_t *slot /*[n]*/, uint32_t *size /*[n]*/, uint64_t *n_unique);
 int rtx_raxtax_last_derep(uint64_t *queries, uint64_t *distinct, double *busy_seconds);
 
+/* ---- distinct reads of a run (rtx_tally.hip, host_tally.cpp; rtx_index_set_tally is the host mirror's use of it) ----------------------------
+ * The distinct sequences of a whole run with their abundances, per sample -- what `vsearch --derep_fulllength --sizeout` and `--otutabout`
+ * (or DADA2's sequence table) leave -- accumulated on the device over any number of chunks and calls.  Unlike rtx_derep the object owns
+ * its sequences: an open-addressing table of entry + 1 (at most half full), per entry hash, length and offset into an arena of bases (one
+ * byte per base, every entry from a multiple of 8 bytes on), a dense uint32 matrix [entries x columns] of counts, 64-bit totals.  All of
+ * them start small and grow by doubling up to the caps.  Exact: a hash picks the candidates, the bytes decide, always; a read and its
+ * reverse complement are different reads, also under RTX_OPT_STRAND (a read is tallied as given).
+ *   rtx_tally_create  an object of its own on GPU `device` (one stream; RTX_ERR_NO_DEVICE without a gfx950), owned by the caller and alive
+ *                     as long as the caller wants.  params (NULL: all defaults): n_samples columns (0: one column, and `sample` is not
+ *                     needed); max_entries (0: RTX_TALLY_DEFAULT_MAX_ENTRIES; at most 2^31 - 2) and max_bytes (0:
+ *                     RTX_TALLY_DEFAULT_MAX_BYTES) cap the entries and the arena; initial_entries / initial_bytes (0:
+ *                     RTX_TALLY_DEFAULT_INITIAL_ENTRIES / _BYTES) size the first allocation.  RTX_ERR_INVALID: max_entries above
+ *                     2^31 - 2, or a matrix of max_entries x columns cells beyond 2^40.
+ *   rtx_tally_add     one chunk: read q adds weight[q] (NULL: 1) to the cell (its sequence, sample[q]) (NULL: column 0).  A read of weight
+ *                     0 or of length 0 is not looked at any further (its sample may be anything, RTX_DEMUX_NONE included) and creates no
+ *                     entry.  Checked on the host before anything is enqueued, RTX_ERR_INVALID: a sample >= max(1, n_samples) on a read
+ *                     that counts; a total counted weight of the object above 2^32 - 1 (no cell can wrap); n > 2^31 - 2; offsets that are
+ *                     not monotone; a read of 2^32 bases or more.  Three steps on the object's stream, separate launches, so that no wave waits for another:
+ *                     lookup in the table (read-only); the reads it does not know among themselves (the chunk-local table of
+ *                     rtx_derep_run) and a scan that numbers the new distinct reads in the order of their read index -- entry ids are the
+ *                     order of first appearance, whatever the scheduling; then append and count.  Between the second and the third the
+ *                     host learns the scan's totals and grows the buffers.  Caps: a new distinct read is stored if and only if its
+ *                     inclusive scan position is within max_entries and max_bytes; the reads of the others are summed into
+ *                     overflow_reads and their sequences into no entry (presented again, they overflow again): a run never fails for
+ *                     being diverse.  The call returns when the third step is enqueued; bases / base_off as rtx_batch_prefetch takes
+ *                     them, free at return.  Calls on one object are serialised by the caller.
+ *   rtx_tally_read    waits for the object's stream, downloads and sorts: a new table (below), to be destroyed by the caller.  The object
+ *                     goes on counting.
+ *   rtx_tally_info    entries and arena bytes in use, their present capacities, counted weight so far (any pointer may be NULL).
+ *   RTX_DEFAULT_TALLY_HASH_MASK (rtx_set_default_option; default: all ones; 0 restores it): the hash of rtx_tally_add is ANDed with this
+ *                     mask, read at every add (an object whose table was laid out under another mask lays it out again first).  For tests.
+ * rtx_tally_table: the table on the host, opaque.  Rows sorted by total size descending, then by their bytes ascending (a prefix before
+ * the longer sequence); one count per column; totals {reads: the weight of all reads that counted, entries, overflow_reads}.
+ *   rtx_tally_table_create / _add   the same accumulation on the host (a hash map), without caps: the host restatement of rtx_tally_add,
+ *                     with its checks.
+ *   rtx_tally_table_merge           the sum of n tables (one object per handle): equal sequences are summed; RTX_ERR_INVALID when the column
+ *                     counts differ.  A new table.
+ *   rtx_tally_table_view            the rows (valid until the table is added to or destroyed): `first` is the rank of a row's entry in the
+ *                     order of first appearance (of the object, or of the host accumulation; of a merged table: table after table).
+ *   rtx_tally_format_fasta          `>uniq{rank};size={N}\n{sequence}\n` per row, rank from 1 in table order; the letters are those of the
+ *                     `.tsv` sequence column (A C G T, anything else '-').  Rows with a total below minsize are left out; the ranks stay
+ *                     those of the whole table.  Returns the bytes written, with buf == NULL the bytes needed; a buffer that is too small:
+ *                     -(bytes needed) - RTX_NEED_BASE (as rtx_profile_format).
+ *   rtx_tally_format_table          `#uniq\t{names, tab-separated}\n`, then `uniq{rank}\t{counts}\n` per row, under the same minsize and
+ *                     the same protocol.  names: one per column.
+ *   rtx_index_set_tally / rtx_index_tally   the object rtx_raxtax* tally into (NULL: off; the handle itself never reads it).  Its device
+ *                     must be the handle's (RTX_ERR_INVALID).  On every handle of a call or on none, no two handles with one object, and
+ *                     n_samples equal to the samples of the tag list (rtx_index_set_tags) when tags are set, 0 otherwise: RTX_ERR_INVALID
+ *                     from the call otherwise.  The tally is the last stage of the front: it counts exactly the reads that go on to be
+ *                     classified -- not one that is unassigned, emptied, discarded, a contaminant or flagged as a chimera -- each with its
+ *                     own sample, with and without RTX_OPT_DEREP (copies count as reads).
+ *   rtx_raxtax_last_tally  the last rtx_raxtax* call of the process: the queries of its tallied chunks, those that counted, the entries the
+ *                     objects gained and the busy seconds of the stage; all 0 with no tally set. */
+#define RTX_DEFAULT_TALLY_HASH_MASK 4
+#define RTX_TALLY_DEFAULT_MAX_ENTRIES (1ull << 24)
+#define RTX_TALLY_DEFAULT_MAX_BYTES (1ull << 33)
+#define RTX_TALLY_DEFAULT_INITIAL_ENTRIES (1ull << 16)
+#define RTX_TALLY_DEFAULT_INITIAL_BYTES (1ull << 25)
+typedef struct rtx_tally rtx_tally;
+typedef struct rtx_tally_table rtx_tally_table;
+typedef struct rtx_tally_params {
+    uint32_t n_samples;
+    uint64_t max_entries, max_bytes, initial_entries, initial_bytes;
+} rtx_tally_params;
+typedef struct rtx_tally_view {
+    uint64_t n_entries;
+    uint32_t n_columns;
+    const uint8_t *bases;      /* the rows' sequences back to back, one code per byte */
+    const uint64_t *base_off;  /* [n_entries + 1] */
+    const uint64_t *counts;    /* [n_entries x n_columns] */
+    const uint64_t *sizes;     /* [n_entries] the sum of a row */
+    const uint64_t *first;     /* [n_entries] rank in the order of first appearance, from 0 */
+    uint64_t totals[3];        /* reads, entries, overflow_reads */
+} rtx_tally_view;
+int rtx_tally_create(int device, const rtx_tally_params *params, rtx_tally **out);
+int rtx_tally_add(rtx_tally *t, uint64_t n, const uint8_t *bases, const uint64_t *base_off, const uint32_t *sample /*[n] or NULL*/, const uint32_t *weight /*[n] or NULL: 1*/);
+int rtx_tally_read(rtx_tally *t, rtx_tally_table **table);
+int rtx_tally_info(const rtx_tally *t, uint64_t *entries, uint64_t *bytes, uint64_t *entry_capacity, uint64_t *byte_capacity, uint64_t *counted);
+void rtx_tally_destroy(rtx_tally *t);
+int rtx_tally_table_create(uint32_t n_samples, rtx_tally_table **out);
+int rtx_tally_table_add(rtx_tally_table *table, uint64_t n, const uint8_t *bases, const uint64_t *base_off, const uint32_t *sample, const uint32_t *weight);
+int rtx_tally_table_merge(rtx_tally_table *const *tables, uint32_t n, rtx_tally_table **out);
+int rtx_tally_table_view(rtx_tally_table *table, rtx_tally_view *view);
+void rtx_tally_table_destroy(rtx_tally_table *table);
+int64_t rtx_tally_format_fasta(rtx_tally_table *table, uint64_t minsize, char *buf, uint64_t cap);
+int64_t rtx_tally_format_table(rtx_tally_table *table, const char *const *names, uint64_t minsize, char *buf, uint64_t cap);
+int rtx_index_set_tally(rtx_index *index, rtx_tally *tally);
+rtx_tally *rtx_index_tally(const rtx_index *index);
+int rtx_raxtax_last_tally(uint64_t *queries, uint64_t *counted, uint64_t *entries_added, double *busy_seconds);
+
 /* ---- primer trimming (rtx_trim.hip; rtx_index_set_primers is the host mirror's use of it) ---------------------------------------------------
  * Amplicon reads come with their PCR primers attached, the references without: what `cutadapt` is run for in front of a classifier, on the
  * device.  Exact integers; the host function and the device agree bit for bit.

@@ -23,6 +23,7 @@ RTX_TEXT_TSV = 4
 RTX_Q_OK, RTX_Q_NO_KMERS, RTX_Q_ALL_KMERS = 0, 1, 2
 RTX_OPT_DEREP = 27                 # rtx_index_set_option: raxtax() classifies each distinct read of a chunk once
 RTX_DEFAULT_DEREP_HASH_MASK = 3    # rtx_set_default_option: the hash of rtx_derep_run ANDed with a mask (tests)
+RTX_DEFAULT_TALLY_HASH_MASK = 4    # rtx_set_default_option: the hash of rtx_tally_add ANDed with a mask (tests)
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 
 RTX_TRIM_5P, RTX_TRIM_3P = 0, 1      # rtx_trim_pattern.end
@@ -101,6 +102,15 @@ class QualParams(C.Structure):   # rtx_qual_params
 
 class ScreenParams(C.Structure):   # rtx_screen_params
     _fields_ = [("min_hits", C.c_uint32), ("min_pct", C.c_uint32)]
+
+
+class TallyParams(C.Structure):   # rtx_tally_params
+    _fields_ = [("n_samples", C.c_uint32), ("max_entries", C.c_uint64), ("max_bytes", C.c_uint64), ("initial_entries", C.c_uint64), ("initial_bytes", C.c_uint64)]
+
+
+class TallyView(C.Structure):   # rtx_tally_view
+    _fields_ = [("n_entries", C.c_uint64), ("n_columns", C.c_uint32), ("bases", C.POINTER(C.c_uint8)), ("base_off", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_uint64)),
+                ("sizes", C.POINTER(C.c_uint64)), ("first", C.POINTER(C.c_uint64)), ("totals", C.c_uint64 * 3)]
 
 
 class MergeParams(C.Structure):   # rtx_merge_params
@@ -281,6 +291,21 @@ _SIGNATURES = {
     "rtx_index_quality": (C.c_int, [C.c_void_p, C.POINTER(QualParams), C.POINTER(C.c_int)]),
     "rtx_raxtax_last_qual": (C.c_int, [u64p, u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_raxtax_multi_ex5": (C.c_int, None),
+    "rtx_tally_create": (C.c_int, [C.c_int, C.POINTER(TallyParams), C.POINTER(C.c_void_p)]),
+    "rtx_tally_add": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u32p]),
+    "rtx_tally_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "rtx_tally_info": (C.c_int, [C.c_void_p, u64p, u64p, u64p, u64p, u64p]),
+    "rtx_tally_destroy": (None, [C.c_void_p]),
+    "rtx_tally_table_create": (C.c_int, [C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rtx_tally_table_add": (C.c_int, [C.c_void_p, C.c_uint64, u8p, u64p, u32p, u32p]),
+    "rtx_tally_table_merge": (C.c_int, [C.POINTER(C.c_void_p), C.c_uint32, C.POINTER(C.c_void_p)]),
+    "rtx_tally_table_view": (C.c_int, [C.c_void_p, C.POINTER(TallyView)]),
+    "rtx_tally_table_destroy": (None, [C.c_void_p]),
+    "rtx_tally_format_fasta": (C.c_int64, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_tally_format_table": (C.c_int64, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_index_set_tally": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "rtx_index_tally": (C.c_void_p, [C.c_void_p]),
+    "rtx_raxtax_last_tally": (C.c_int, [u64p, u64p, u64p, C.POINTER(C.c_double)]),
     "rtx_screen_set_build": (C.c_int, [C.c_uint64, u8p, u64p, C.POINTER(C.c_void_p)]),
     "rtx_screen_set_free": (None, [C.c_void_p]),
     "rtx_screen_set_info": (C.c_int, [C.c_void_p, u64p, u64p, u64p, u64p, u64p]),

@@ -361,9 +361,10 @@ class Index:
                  debug_taps: bool = False, device_exact: Optional[bool] = None, fine_bounds: Optional[bool] = None,
                  records: Optional[int] = None, overlap: Optional[bool] = None, two_level: Optional[int] = None,
                  prune_self_sample: Optional[bool] = None, device_text: bool = False, strand: str = "plus",
-                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None, tags=None, contaminants=None):
+                 nearest: bool = False, derep: bool = False, identity: bool = False, primers=None, quality=None, chimera=None, tags=None, contaminants=None, tally=None):
         self._lib = _lib.load()
         self.tree = tree
+        self._tally = None
         if segment_classes is None:
             segment_classes = DEFAULT_SEGMENT_CLASSES
         check(self._lib.rtx_set_default_option(1, int(segment_classes)))   # creation-time default of the library
@@ -432,8 +433,20 @@ class Index:
             self.set_chimera(ChimeraParams() if chimera is True else chimera)
         if contaminants is not None:   # rtx_index_set_screen: raxtax() screens every read against the set first (rtx_screen.hip); classify() ignores it
             self.set_screen(*(contaminants if isinstance(contaminants, tuple) else (contaminants,)))
+        if tally is not None:   # rtx_index_set_tally: raxtax() tallies the reads it classifies into the object (rtx_tally.hip); classify() ignores it
+            self.set_tally(tally)
         self._view = ResultView()
         self._keep = None
+
+    def set_tally(self, tally) -> None:
+        """rtx_index_set_tally: the Tally raxtax() counts the classified reads into (on the handle's device); None switches it off."""
+        check(self._lib.rtx_index_set_tally(self._h, tally._h if tally is not None else None))
+        self._tally = tally   # (the object is the caller's: kept alive as long as the handle names it)
+
+    @property
+    def tally(self):
+        """The Tally the handle holds, or None (rtx_index_tally)."""
+        return self._tally if self._lib.rtx_index_tally(self._h) else None
 
     def set_screen(self, sset, params=None) -> None:
         """rtx_index_set_screen: the ScreenSet and ScreenParams raxtax() screens every read with; None switches the stage off.  The handle
@@ -1755,6 +1768,167 @@ def raxtax_last_derep() -> Tuple[int, int, float]:
     q, u, b = C.c_uint64(), C.c_uint64(), C.c_double()
     check(_lib.load().rtx_raxtax_last_derep(C.byref(q), C.byref(u), C.byref(b)))
     return int(q.value), int(u.value), float(b.value)
+
+
+def _tally_args(bases, base_off, sample, weight):
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    base_off = np.ascontiguousarray(base_off, dtype=np.uint64)
+    n = len(base_off) - 1
+    sample = None if sample is None else np.ascontiguousarray(sample, dtype=np.uint32)
+    weight = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint32)
+    for name, a in (("sample", sample), ("weight", weight)):
+        if a is not None and len(a) != n:
+            raise ValueError(f"{len(a)} {name}s for {n} reads")
+    one = np.zeros(1, np.uint32)
+    return (n, ptr(bases if len(bases) else np.zeros(1, np.uint8), u8p), ptr(base_off, u64p), None if sample is None else ptr(sample if n else one, u32p),
+            None if weight is None else ptr(weight if n else one, u32p)), (bases, base_off, sample, weight, one)
+
+
+class TallyTable:
+    """The distinct reads of a run on the host (rtx_tally_table): what Tally.read() downloads, tally_reads() accumulates and tally_merge()
+    sums.  Rows sorted by total size descending, then bytes ascending.
+      seqs    the rows' sequences, one uint8 code array each          counts  [rows, columns] uint64
+      sizes   [rows] the sum of a row                                 first   [rows] rank in the order of first appearance
+      totals  {"reads", "entries", "overflow_reads"}"""
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self._h = handle
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_tally_table_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def add(self, bases, base_off, sample=None, weight=None) -> None:
+        """rtx_tally_table_add: one more chunk into a table made by tally_reads()."""
+        args, _keep = _tally_args(bases, base_off, sample, weight)
+        check(self._lib.rtx_tally_table_add(self._h, *args))
+
+    def _view(self):
+        v = _lib.TallyView()
+        check(self._lib.rtx_tally_table_view(self._h, C.byref(v)))
+        return v
+
+    @property
+    def columns(self) -> int:
+        return int(self._view().n_columns)
+
+    @property
+    def seqs(self) -> List[np.ndarray]:
+        v = self._view()
+        ne = int(v.n_entries)
+        if ne == 0:
+            return []
+        off = np.ctypeslib.as_array(v.base_off, shape=(ne + 1,))
+        flat = np.ctypeslib.as_array(v.bases, shape=(max(int(off[ne]), 1),))
+        return [flat[int(off[r]):int(off[r + 1])].copy() for r in range(ne)]
+
+    def _array(self, field, per_row):
+        v = self._view()
+        ne = int(v.n_entries)
+        if ne == 0:
+            return np.zeros((0, per_row) if per_row else (0,), np.uint64)
+        return np.ctypeslib.as_array(getattr(v, field), shape=(ne, per_row) if per_row else (ne,)).copy()
+
+    @property
+    def counts(self) -> np.ndarray:
+        return self._array("counts", self.columns)
+
+    @property
+    def sizes(self) -> np.ndarray:
+        return self._array("sizes", 0)
+
+    @property
+    def first(self) -> np.ndarray:
+        return self._array("first", 0)
+
+    @property
+    def totals(self) -> dict:
+        v = self._view()
+        return {"reads": int(v.totals[0]), "entries": int(v.totals[1]), "overflow_reads": int(v.totals[2])}
+
+    def as_dict(self) -> dict:
+        """{bytes(sequence): tuple of the row's counts}"""
+        return {bytes(s): tuple(int(x) for x in c) for s, c in zip(self.seqs, self.counts)}
+
+
+class Tally(_Stage):
+    """The distinct reads of a run on one GPU (rtx_tally): a table that persists over any number of add() calls and owns its sequences, with
+    a count per (sequence, sample).  caps: max_entries, max_bytes, initial_entries, initial_bytes (0: the header's defaults)."""
+
+    _c = "tally"
+
+    def __init__(self, device: int = 0, samples: int = 0, max_entries: int = 0, max_bytes: int = 0, initial_entries: int = 0, initial_bytes: int = 0):
+        self.samples = int(samples)
+        self._open(device, C.byref(_lib.TallyParams(self.samples, int(max_entries), int(max_bytes), int(initial_entries), int(initial_bytes))))
+
+    def add(self, bases, base_off, sample=None, weight=None) -> None:
+        """rtx_tally_add: read q adds weight[q] (None: 1) to the cell (its sequence, sample[q]) (None: column 0); a read of weight 0 or
+        length 0 is not looked at."""
+        args, _keep = _tally_args(bases, base_off, sample, weight)
+        check(self._lib.rtx_tally_add(self._h, *args))
+
+    def read(self) -> TallyTable:
+        """rtx_tally_read: the table so far, sorted; the object goes on counting."""
+        h = C.c_void_p()
+        check(self._lib.rtx_tally_read(self._h, C.byref(h)))
+        return TallyTable(h)
+
+    def info(self) -> dict:
+        """rtx_tally_info: entries and arena bytes in use, their capacities, and the weight counted so far."""
+        v = [C.c_uint64() for _ in range(5)]
+        check(self._lib.rtx_tally_info(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("entries", "bytes", "entry_capacity", "byte_capacity", "counted"), (int(x.value) for x in v)))
+
+
+def tally_reads(bases, base_off, sample=None, weight=None, samples: int = 0) -> TallyTable:
+    """rtx_tally_table_create + rtx_tally_table_add: the table of these reads accumulated on the host, without caps -- the host restatement
+    of Tally.add()."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_tally_table_create(int(samples), C.byref(h)))
+    t = TallyTable(h)
+    t.add(bases, base_off, sample, weight)
+    return t
+
+
+def tally_merge(tables: Sequence[TallyTable]) -> TallyTable:
+    """rtx_tally_table_merge: the sum of tables (one Tally per handle of a multi-GPU run); equal sequences are summed."""
+    arr = (C.c_void_p * len(tables))(*[t._h.value for t in tables])
+    h = C.c_void_p()
+    check(_lib.load().rtx_tally_table_merge(arr, len(tables), C.byref(h)))
+    return TallyTable(h)
+
+
+def _tally_text(fn, table, *args) -> str:
+    n = check(fn(table._h, *args, None, 0))
+    buf = C.create_string_buffer(max(n, 1))
+    check(fn(table._h, *args, buf, n))
+    return buf.raw[:n].decode()
+
+
+def tally_fasta(table: TallyTable, minsize: int = 1) -> str:
+    """rtx_tally_format_fasta: `>uniq{rank};size={N}` and the sequence per row (what raxtax-hip --uniques writes to PREFIX/raxtax.uniques)."""
+    return _tally_text(_lib.load().rtx_tally_format_fasta, table, int(minsize))
+
+
+def tally_table_text(table: TallyTable, names: Sequence[str], minsize: int = 1) -> str:
+    """rtx_tally_format_table: the sequence x sample table of read counts (PREFIX/raxtax.uniques.tsv); one name per column."""
+    if len(names) != table.columns:
+        raise ValueError(f"{len(names)} names for {table.columns} column(s)")
+    arr = (C.c_char_p * len(names))(*[s.encode() for s in names])
+    return _tally_text(_lib.load().rtx_tally_format_table, table, arr, int(minsize))
+
+
+def raxtax_last_tally() -> Tuple[int, int, int, float]:
+    """rtx_raxtax_last_tally: (queries of the tallied chunks, those that counted, entries the objects gained, busy seconds of the stage) of
+    the last raxtax() call of this process; all 0 when its handles had no tally."""
+    q, c, a, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_double()
+    check(_lib.load().rtx_raxtax_last_tally(C.byref(q), C.byref(c), C.byref(a), C.byref(b)))
+    return int(q.value), int(c.value), int(a.value), float(b.value)
 
 
 def raxtax_last_timing() -> Tuple[List[float], int]:

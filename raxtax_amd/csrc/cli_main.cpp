@@ -11,6 +11,11 @@
 //   PREFIX/raxtax.hits    (--hits) label, + or -, peak, t, ties, id and lineage of the nearest reference per query, in the order of raxtax.out
 //   (--identity, implies --hits: two more columns at the end of every line of raxtax.hits -- the semi-global edit distance of the query to that
 //    reference and the identity in percent, two decimals; '-' twice where there is no distance: RTX_OPT_IDENTITY)
+//   PREFIX/raxtax.uniques (--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N]) the distinct reads of the whole run with their
+//    abundances, `>uniq{rank};size={N}` and the sequence, largest first (rtx_tally.hip: one object per handle, accumulated on the device over the blocks of
+//    the file; read, summed and written once at the end; rtx_tally_format_fasta).  The reads counted are those that go on to be classified, as given (also
+//    under --strand both).  With --tags also PREFIX/raxtax.uniques.tsv, the sequence x sample table of read counts (rtx_tally_format_table).  Entries
+//    below N (default 1) are left out of both files, the ranks stay.  Sequences beyond the caps are not stored; their reads are named in the log.
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
 //   PREFIX/raxtax.demux (--tags SHEET) and PREFIX/raxtax.samples (with --profile as well): below
 //   (--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]: every read is assigned to a sample by the inline tags at
@@ -167,7 +172,8 @@ std::string fingerprint(const std::string &path) {
 // (... and --primers with its two settings, as given: trimmed reads are other reads)
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
                             const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string(),
-                            const std::string &chimera = std::string(), const std::string &tags = std::string(), const std::string &contaminants = std::string()) {
+                            const std::string &chimera = std::string(), const std::string &tags = std::string(), const std::string &contaminants = std::string(),
+                            const std::string &uniques = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
@@ -179,6 +185,7 @@ std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv
     if (!chimera.empty()) ss << ",\n  \"chimera\": \"" << chimera << "\"";  // (... and --chimera with its two settings: flagged reads have no lines)
     if (!tags.empty()) ss << ",\n  \"tags\": \"" << tags << "\"";  // (... and --tags with its settings: demultiplexed reads are other reads)
     if (!contaminants.empty()) ss << ",\n  \"contaminants\": \"" << contaminants << "\"";  // (... and --contaminants with its settings and the set's fingerprint: contaminants have no lines)
+    if (!uniques.empty()) ss << ",\n  \"uniques\": \"" << uniques << "\"";  // (... and --uniques with its settings: the table is the run's, a resumed run would miss reads)
     ss << "\n}\n";
     return ss.str();
 }
@@ -263,6 +270,9 @@ int main(int argc, char **argv) {
     rtx_demux_params tag_params{0u, 0u};                               // --tag-mismatches N, --tag-offset N
     bool tags_both = false;                                            // --tags-both-orientations
     std::string tag_opts;                                              // those three as given (empty: none)
+    bool uniques = false;         // --uniques: a tally (rtx_tally.hip) on every handle, PREFIX/raxtax.uniques (and raxtax.uniques.tsv with --tags)
+    uint64_t uniques_minsize = 1, uniques_max_entries = 0, uniques_max_bytes = 0;  // --uniques-minsize N, --uniques-max-entries N, --uniques-max-bytes N (0: the library's defaults)
+    std::string uniques_opts;     // those three as given (empty: none)
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -402,11 +412,20 @@ int main(int argc, char **argv) {
             if (c < 1 || c > 100) { fprintf(stderr, "raxtax-hip: --profile takes a confidence cutoff in (0, 1], such as 0.8\n"); return 64; }
             profile_cutoff = (uint32_t)c;
         }
+        else if (a == "--uniques") uniques = true;
+        else if (a == "--uniques-minsize" || a == "--uniques-max-entries" || a == "--uniques-max-bytes") {
+            char *end = nullptr;
+            const char *v = val();
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end != '\0' || x < 1 || (a == "--uniques-max-entries" && x > 0x7FFFFFFELL)) { fprintf(stderr, "raxtax-hip: %s takes a positive integer\n", a.c_str()); return 64; }
+            (a == "--uniques-minsize" ? uniques_minsize : a == "--uniques-max-entries" ? uniques_max_entries : uniques_max_bytes) = (uint64_t)x;
+            uniques_opts += (uniques_opts.empty() ? "" : " ") + a;
+        }
         else if (a == "--batch") chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -594,6 +613,10 @@ int main(int argc, char **argv) {
     const std::string demux_path = prefix + "/raxtax.demux", samples_path = prefix + "/raxtax.samples", screen_path = prefix + "/raxtax.screen";
     const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge", chim_path = prefix + "/raxtax.chimera";
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
+    const std::string uniques_path = prefix + "/raxtax.uniques", uniques_table_path = prefix + "/raxtax.uniques.tsv";
+    if (!uniques_opts.empty() && !uniques) { fprintf(stderr, "raxtax-hip: %s sets how the distinct reads are kept and written and needs --uniques\n", uniques_opts.c_str()); return 64; }
+    std::string uniques_spec;
+    if (uniques) uniques_spec = "minsize=" + std::to_string(uniques_minsize) + " max_entries=" + std::to_string(uniques_max_entries) + " max_bytes=" + std::to_string(uniques_max_bytes);
     if (device_format && derep) {
         fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
         device_format = false;
@@ -604,7 +627,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -615,6 +638,11 @@ int main(int argc, char **argv) {
             while (std::getline(p, l)) done.insert(l);
             if (profile_cutoff && !done.empty()) {  // the queries of the earlier run are not classified again: their share of the sample is gone
                 fprintf(stderr, "raxtax-hip: --profile cannot resume a checkpoint with processed queries (%zu in %s): the profile would miss them; "
+                                "run with --redo to classify the whole sample again\n", done.size(), ckp_path.c_str());
+                return 64;
+            }
+            if (uniques && !done.empty()) {  // (likewise: the table would miss the reads of the earlier run)
+                fprintf(stderr, "raxtax-hip: --uniques cannot resume a checkpoint with processed queries (%zu in %s): the table would miss them; "
                                 "run with --redo to classify the whole sample again\n", done.size(), ckp_path.c_str());
                 return 64;
             }
@@ -681,7 +709,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -836,6 +864,7 @@ int main(int argc, char **argv) {
     };
     // one index handle per device, created side by side (each on a thread of its own: the builds run on their GPUs)
     std::vector<rtx_index *> indices(devices.size(), nullptr);
+    std::vector<rtx_tally *> tallies(uniques ? devices.size() : 0, nullptr);  // --uniques: one object per handle, alive over the blocks of the file
     {
         std::vector<int> rcs(devices.size(), RTX_OK);
         std::vector<std::string> errs(devices.size());
@@ -861,6 +890,11 @@ int main(int argc, char **argv) {
                 if (rcs[k] == RTX_OK && qual_on) rcs[k] = rtx_index_set_quality(indices[k], &qual);
                 if (rcs[k] == RTX_OK && screen_on) rcs[k] = rtx_index_set_screen(indices[k], contam_set, &contam);
                 if (rcs[k] == RTX_OK && chim_on) rcs[k] = rtx_index_set_chimera(indices[k], &chim);
+                if (rcs[k] == RTX_OK && uniques) {
+                    const rtx_tally_params tp{tags_on ? (uint32_t)sample_names.size() : 0u, uniques_max_entries, uniques_max_bytes, 0, 0};
+                    rcs[k] = rtx_tally_create(devices[k], &tp, &tallies[k]);
+                    if (rcs[k] == RTX_OK) rcs[k] = rtx_index_set_tally(indices[k], tallies[k]);
+                }
                 if (rcs[k] == RTX_OK && profile_cutoff && tags_on)  // ... with a column of counters per sample (PREFIX/raxtax.samples)
                     rcs[k] = rtx_index_profile_begin_samples(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u),
                                                              (uint32_t)sample_names.size());
@@ -897,6 +931,7 @@ int main(int argc, char **argv) {
     if (want_hits) sink.hits.open(hits_path, mode);
     else if (mode == std::ios::trunc) remove(hits_path.c_str());  // (likewise)
     if (mode == std::ios::trunc) remove(profile_path.c_str());  // (written at the end of a run with --profile)
+    if (mode == std::ios::trunc) { remove(uniques_path.c_str()); remove(uniques_table_path.c_str()); }  // (written at the end of a run with --uniques)
     if (!primers.empty()) {
         const bool header = mode == std::ios::trunc || !is_file(trim_path);
         sink.trim.open(trim_path, mode);
@@ -1289,12 +1324,51 @@ int main(int argc, char **argv) {
         sf.close();
         if (!sf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", samples_path.c_str()); return 74; }
     }
+    if (uniques) {  // the distinct reads of the whole run: the tables of the handles' objects read, summed and written once
+        std::vector<rtx_tally_table *> tables(tallies.size(), nullptr);
+        rtx_tally_table *sum = nullptr;
+        int trc = RTX_OK;
+        for (size_t k = 0; k < tallies.size() && trc == RTX_OK; k++) trc = rtx_tally_read(tallies[k], &tables[k]);
+        if (trc == RTX_OK) trc = rtx_tally_table_merge(tables.data(), (uint32_t)tables.size(), &sum);
+        rtx_tally_view view{};
+        if (trc == RTX_OK) trc = rtx_tally_table_view(sum, &view);
+        std::vector<const char *> names;
+        for (const std::string &s : sample_names) names.push_back(s.c_str());
+        std::string fasta, table;
+        auto format = [&](std::string &text, auto fn) {  // the two-pass protocol of the formatters
+            const int64_t need = fn(nullptr, 0);
+            if (need < 0) { trc = (int)need; return; }
+            text.resize((size_t)need);
+            const int64_t got = fn(&text[0], text.size());
+            if (got != need) trc = got < 0 ? (int)got : RTX_ERR_STATE;
+        };
+        if (trc == RTX_OK) format(fasta, [&](char *buf, uint64_t cap) { return rtx_tally_format_fasta(sum, uniques_minsize, buf, cap); });
+        if (trc == RTX_OK && tags_on) format(table, [&](char *buf, uint64_t cap) { return rtx_tally_format_table(sum, names.data(), uniques_minsize, buf, cap); });
+        if (trc != RTX_OK) { fprintf(stderr, "[ERROR] distinct reads: %s\n", rtx_last_error()); return 70; }
+        fprintf(stderr, "[INFO ] --uniques: %llu reads, %llu distinct\n", (unsigned long long)view.totals[0], (unsigned long long)view.totals[1]);
+        if (view.totals[2])
+            fprintf(stderr, "[INFO ] --uniques: %llu of %llu reads belong to sequences beyond the caps (--uniques-max-entries, --uniques-max-bytes) and are in no entry\n",
+                    (unsigned long long)view.totals[2], (unsigned long long)view.totals[0]);
+        std::ofstream uf(uniques_path, std::ios::trunc);
+        uf << fasta;
+        uf.close();
+        if (!uf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", uniques_path.c_str()); return 74; }
+        if (tags_on) {
+            std::ofstream tf(uniques_table_path, std::ios::trunc);
+            tf << table;
+            tf.close();
+            if (!tf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", uniques_table_path.c_str()); return 74; }
+        }
+        rtx_tally_table_destroy(sum);
+        for (rtx_tally_table *t : tables) rtx_tally_table_destroy(t);
+    }
     if (clean) {  // Checkpoint::cleanup (io.rs:80-89)
         remove(ckp_json.c_str());
         remove(ckp_path.c_str());
         if (!db_bin.empty()) remove(db_bin.c_str());
     }
     for (rtx_index *ix : indices) rtx_index_destroy(ix);
+    for (rtx_tally *t : tallies) rtx_tally_destroy(t);
     rtx_tree_destroy(tree);
     return 0;
 }

@@ -159,6 +159,32 @@ int run_chimera(rtx_chimera *stage, FrontChunk &fc, BufPool &pool, FrontTotals &
     return RTX_OK;
 }
 
+// The reads that go on to be classified into the handle's tally, on the device (a stream of its own beside the handle's): one entry per query
+// of the caller from `src` -- an unassigned, emptied or discarded read and a contaminant are empty there and count nowhere -- with weight 0
+// for a query whose representative the chimera check flagged, and the query's own sample where tags are set.
+int run_tally(rtx_tally *stage, bool demux, FrontChunk &fc, FrontTotals &tot) {
+    const double t0 = now();
+    const Reads &src = fc.src;
+    const uint64_t nq = src.n;
+    std::vector<uint32_t> weight;
+    uint64_t counted = 0;
+    if (!fc.chim.empty()) {
+        weight.resize(nq);
+        for (uint64_t i = 0; i < nq; i++) weight[i] = fc.chim[fc.at(i)].flag ? 0u : 1u;
+    }
+    for (uint64_t i = 0; i < nq; i++) counted += src.len(i) != 0 && (weight.empty() || weight[i]);
+    uint64_t before = 0, after = 0;
+    int rc = rtx_tally_info(stage, &before, nullptr, nullptr, nullptr, nullptr);
+    if (!rc) rc = rtx_tally_add(stage, nq, src.bases, src.off, demux ? fc.dx_sample.data() : nullptr, weight.empty() ? nullptr : weight.data());
+    if (!rc) rc = rtx_tally_info(stage, &after, nullptr, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    tot.tally.queries += nq;
+    tot.tally.counted += counted;
+    tot.tally.added += after - before;
+    tot.tally.busy += now() - t0;
+    return RTX_OK;
+}
+
 }  // namespace
 
 int cut(const Reads &from, const uint32_t *lo, const uint32_t *keep_hi, bool with_quals, Cut &out, BufPool &pool, const char *oom, Reads &to) {
@@ -277,7 +303,28 @@ int Front::open(rtx_index *const *indices, uint32_t n_dev, bool has_quals, bool 
                [](const auto &a, const auto &b) { return a.first == b.first && (!a.first || (a.second.segments == b.second.segments && a.second.mindelta == b.second.mindelta)); });
     if (rc) return rc;
     if (chim) rc = chims.open(indices, n_dev, false, [&](uint32_t d, rtx_chimera **out) { return rtx_chimera_create(indices[d], &cparams, out); });
-    return rc;
+    if (rc) return rc;
+    // Distinct reads of the run (rtx_index_set_tally): on every handle or on none, an object of its own per handle (each handle's chunks go to
+    // that handle's object; the caller sums them: rtx_tally_table_merge), with a column per sample of the tag list
+    tally = rtx::index_tally(indices[0]) != nullptr;
+    rc = agree(indices, n_dev, [](const rtx_index *ix) { return rtx::index_tally(ix) != nullptr; }, "rtx_raxtax_multi: a tally (rtx_index_set_tally) is set on some handles and not on others");
+    if (rc) return rc;
+    if (tally) {
+        uint32_t want = 0u;  // the samples of the tag list: its highest sample + 1
+        for (const rtx_demux_pair &pr : taglist.pairs) want = std::max(want, pr.sample + 1u);
+        tallies.assign(n_dev, nullptr);
+        for (uint32_t d = 0; d < n_dev; d++) {
+            tallies[d] = rtx::index_tally(indices[d]);
+            for (uint32_t e = 0; e < d; e++)
+                if (tallies[e] == tallies[d]) { rtx::set_error("rtx_raxtax_multi: handles %u and %u share one tally (rtx_index_set_tally): every handle needs an object of its own", e, d); return RTX_ERR_INVALID; }
+            if (rtx::tally_samples(tallies[d]) != want) {
+                rtx::set_error("rtx_raxtax: the tally (rtx_index_set_tally) has n_samples %u; it must be %u: %s", rtx::tally_samples(tallies[d]), want,
+                               demux ? "the samples of the tag list (rtx_index_set_tags)" : "0 without tags");
+                return RTX_ERR_INVALID;
+            }
+        }
+    }
+    return RTX_OK;
 }
 
 int Front::run(uint32_t d, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTotals &tot) const {
@@ -286,6 +333,7 @@ int Front::run(uint32_t d, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTota
     if (!rc && (trim || qual || screen)) rc = run_trim_qual_screen(trim ? trims.of[d] : nullptr, qual ? quals.of[d] : nullptr, screen ? screens.of[d] : nullptr, fc, pool, tot);
     if (!rc && derep) rc = run_derep(dereps.of[d], fc, pool, nt, tot);
     if (!rc && chim) rc = run_chimera(chims.of[d], fc, pool, tot);
+    if (!rc && tally) rc = run_tally(tallies[d], demux, fc, tot);
     return rc;
 }
 

@@ -7,6 +7,7 @@
 //   contaminants rtx_screen_run    rtx_index_set_screen          in       src ..     device   (the same cut: no further copy)
 //   copies    rtx_derep_run        RTX_OPT_DEREP                 src      dev        device
 //   chimeras  rtx_chimera_run      rtx_index_set_chimera         dev      dev        handle   (it borrows the handle's bitmap)
+//   distinct reads rtx_tally_add   rtx_index_set_tally           src      --         handle   (the caller's object: it outlives the call)
 //
 // A chunk holds four views of its reads (Reads).  Each starts as the one before it; the stage that cuts replaces it and every later one:
 //   given  the caller's arrays
@@ -104,6 +105,7 @@ struct FrontTotals {
     struct { uint64_t queries, screened, contaminants; double busy; } screen;
     struct { uint64_t queries, distinct; double busy; } derep;
     struct { uint64_t queries, checked, flagged; double busy; } chim;
+    struct { uint64_t queries, counted, added; double busy; } tally;
     double busy[4];
     uint64_t n_chunks;
 };
@@ -160,7 +162,7 @@ int agree(rtx_index *const *indices, uint32_t n_dev, Get get, const char *msg, S
 
 // The front of a call: which stages are on (the same on every handle) and their objects.
 struct Front {
-    bool demux = false, trim = false, qual = false, screen = false, derep = false, chim = false;
+    bool demux = false, trim = false, qual = false, screen = false, derep = false, chim = false, tally = false;
     uint32_t prof_samples = 0;  // the samples of the open profile (rtx_index_profile_begin_samples): the same on every handle
     StageSet<rtx_demux, rtx_demux_destroy> demuxes;
     StageSet<rtx_trim, rtx_trim_destroy> trims;
@@ -168,9 +170,10 @@ struct Front {
     StageSet<rtx_screen, rtx_screen_destroy> screens;
     StageSet<rtx_derep, rtx_derep_destroy> dereps;
     StageSet<rtx_chimera, rtx_chimera_destroy> chims;
+    std::vector<rtx_tally *> tallies;  // per handle, the callers' (rtx_index_set_tally): not owned
     // checks that the handles agree on every stage and creates the objects; has_quals: the call brings quality strings, prof: a taxon profile is open
     int open(rtx_index *const *indices, uint32_t n_dev, bool has_quals, bool prof);
-    bool any() const { return demux || trim || qual || screen || derep || chim; }
+    bool any() const { return demux || trim || qual || screen || derep || chim || tally; }
     // chunk `fc` (given set, the other views as given) through the stages that are on, with the objects of handle d
     int run(uint32_t d, FrontChunk &fc, BufPool &pool, unsigned nt, FrontTotals &tot) const;
 };

@@ -72,7 +72,7 @@ private:
 };
 
 std::mutex g_timing_mu;
-FrontTotals g_last{};  // the last call of this process: what the seven rtx_raxtax_last_* report (under g_timing_mu)
+FrontTotals g_last{};  // the last call of this process: what the eight rtx_raxtax_last_* report (under g_timing_mu)
 
 // The arguments of a call.  A callback is a function of the C ABI with its context (0: go on, else the sink is closed); null: nobody asked.
 //   sender (label, out_lines, tsv_lines or null) of every query that has a message
@@ -167,7 +167,7 @@ void per_query(std::vector<T> &dst, const T *src, const std::vector<uint32_t> &s
 //   device thread : classification of its chunks, one after the other  (rtx_classify_batch, raxtax.rs:42,55-71)
 //   format thread : lineage check of the exact matches (raxtax.rs:43-53), override + formatting (raxtax.rs:73-84), chunk by chunk
 // and for all of them
-//   lookup thread : the read front (host_front.hpp: tags, primers, quality, contaminants, copies, chimeras -- each on the device, on a stream of its own
+//   lookup thread : the read front (host_front.hpp: tags, primers, quality, contaminants, copies, chimeras, distinct reads -- each on the device, on a stream of its own
 //                   beside the handle's, while that handle still classifies an earlier chunk), then the exact-match ids (host hash map,
 //                   raxtax.rs:42) -- only for handles without the device lookup (rtx_index_has_exact_lookup): otherwise the ids come back
 //                   with the results of the device stage.  The handle classifies front.dev; the format thread and the sender go on
@@ -832,6 +832,15 @@ extern "C" int rtx_raxtax_last_chimera(uint64_t *queries, uint64_t *checked, uin
     if (checked) *checked = g_last.chim.checked;
     if (flagged) *flagged = g_last.chim.flagged;
     if (busy_seconds) *busy_seconds = g_last.chim.busy;
+    return RTX_OK;
+}
+
+extern "C" int rtx_raxtax_last_tally(uint64_t *queries, uint64_t *counted, uint64_t *entries_added, double *busy_seconds) {
+    std::lock_guard<std::mutex> g(g_timing_mu);
+    if (queries) *queries = g_last.tally.queries;
+    if (counted) *counted = g_last.tally.counted;
+    if (entries_added) *entries_added = g_last.tally.added;
+    if (busy_seconds) *busy_seconds = g_last.tally.busy;
     return RTX_OK;
 }
 

@@ -19,73 +19,28 @@
 // it can meet an empty slot, so a cluster has exactly one owner.
 #include <atomic>
 
+#include "rtx_derep_dev.hpp"
 #include "rtx_stage.hpp"
 
 namespace {
 
 std::atomic<uint64_t> g_derep_hash_mask{~0ull};  // RTX_DEFAULT_DEREP_HASH_MASK (tests: a hash of two bits, so that every probe ends in the byte compare)
 
-struct DerepParams {
-    const uint8_t *bases;      // one byte per base, padded behind the end (em_load_word)
-    const uint64_t *base_off;  // [n + 1]
-    uint32_t n;
-    uint64_t *hash;            // [n]
-    uint32_t *table;           // [2^bits] query + 1; 0: empty
-    uint32_t bits;
-    uint64_t hash_mask;
-    uint32_t *owner;           // [n] the query that holds the slot of q's sequence
-    uint32_t *cluster_min;     // [n] at an owner: the lowest query of its cluster (preset to all ones)
-    uint32_t *rep;             // [n] | [1] the number of q with rep[q] == q
-};
-
+// (the device code of the three steps is in rtx_derep_dev.hpp: rtx_tally.hip runs the last two over the reads its own table does not know)
 __global__ __launch_bounds__(256) void derep_hash_kernel(DerepParams p) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (q >= p.n) return;  // wave-uniform
     const uint64_t b0 = p.base_off[q], len = p.base_off[q + 1] - b0;
-    const uint8_t *seq = p.bases + b0;
-    const uint64_t nw = (len + 7u) >> 3;
-    uint64_t sum = 0;
-    for (uint64_t j = lane; j < nw; j += 64) sum += em_mix_word(em_load_word(seq, len, j), j);
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d, 64);
-    if (lane == 0) p.hash[q] = em_finish(sum, len) & p.hash_mask;
+    const uint64_t h = derep_hash_read(p.bases + b0, len, lane);
+    if (lane == 0) p.hash[q] = h & p.hash_mask;
 }
 
 __global__ __launch_bounds__(256) void derep_insert_kernel(DerepParams p) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t q = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (q >= p.n) return;  // wave-uniform
-    const uint64_t b0 = p.base_off[q], len = p.base_off[q + 1] - b0;
-    const uint8_t *seq = p.bases + b0;
-    const uint64_t nw = (len + 7u) >> 3;
-    const uint64_t h = p.hash[q];
-    const uint32_t mask = (uint32_t)((1ull << p.bits) - 1ull);
-    uint32_t slot = em_slot(h, p.bits);
-    uint32_t own = q;
-    for (uint64_t probe = 0; probe <= mask; probe++) {  // wave-uniform; the table is at most half full: an empty slot comes
-        uint32_t e = __builtin_amdgcn_readfirstlane(__hip_atomic_load(p.table + slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (e == 0u) {
-            uint32_t old = 0u;
-            if (lane == 0) old = atomicCAS(p.table + slot, 0u, q + 1u);
-            e = __builtin_amdgcn_readfirstlane(old);
-            if (e == 0u) break;  // the slot is this query's: it owns itself
-        }
-        const uint32_t o = e - 1u;  // an occupant (found, or the winner of the compare-and-swap)
-        if (p.hash[o] == h) {
-            const uint64_t o0 = p.base_off[o], olen = p.base_off[o + 1] - o0;
-            if (olen == len) {
-                bool differ = false;
-                for (uint64_t j = lane; j < nw; j += 64) differ = differ || em_load_word(seq, len, j) != em_load_word(p.bases + o0, len, j);
-                if (__ballot(differ) == 0ull) { own = o; break; }
-            }
-        }
-        slot = (slot + 1u) & mask;
-    }
-    if (lane == 0) {
-        p.owner[q] = own;
-        atomicMin(p.cluster_min + own, q);
-    }
+    derep_insert_read(p, q, lane);
 }
 
 // (no lane leaves early: the ballot runs over whole waves)
@@ -93,7 +48,7 @@ __global__ __launch_bounds__(256) void derep_resolve_kernel(DerepParams p) {
     const uint32_t q = blockIdx.x * 256u + threadIdx.x;
     bool self = false;
     if (q < p.n) {
-        const uint32_t r = p.cluster_min[p.owner[q]];
+        const uint32_t r = derep_resolve_read(p, q);
         p.rep[q] = r;
         self = r == q;
     }

@@ -477,6 +477,7 @@ struct rtx_index {
     bool chimera_on = false;
     rtx_screen_set screen_set;       // rtx_index_set_screen: the contaminant screen rtx_raxtax* run every read through (rtx_screen.hip); the handle itself never reads it
     rtx_screen_params screen{};      // (screen_set.data is null: off)
+    rtx_tally *tally = nullptr;      // rtx_index_set_tally: the object rtx_raxtax* tally the classified reads into (rtx_tally.hip), the caller's; the handle itself never reads it
     rtx::DemuxList tags;  // rtx_index_set_tags: rtx_raxtax* assign every read to a sample and cut its tags first (rtx_demux.hip); the handle itself never reads them
     std::vector<rtx::TrimPrimer> primers;  // rtx_index_set_primers: rtx_raxtax* trim every read with them first (rtx_trim.hip); the handle itself never reads them
     DevBuf<char> d_lin_bytes, d_text;
@@ -595,6 +596,7 @@ int enqueue_finalise(rtx_index *ix, const SubBatch &b, hipStream_t s);  // (rtx_
 int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r);  // the batch being downloaded joins the open profile, once (synchronous; nothing without one)
 // ---- rtx_derep.hip
 void set_derep_hash_mask(uint64_t mask);  // RTX_DEFAULT_DEREP_HASH_MASK (rtx_set_default_option)
+void set_tally_hash_mask(uint64_t mask);  // RTX_DEFAULT_TALLY_HASH_MASK, rtx_tally.hip
 // ---- rtx_text.hip
 int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of the batch being downloaded (synchronous)
 

@@ -72,6 +72,10 @@ int chimera_check_params(const char *who, const rtx_chimera_params *p);
 bool index_chimera(const rtx_index *index, rtx_chimera_params *params);
 // contaminant screen (host_screen.cpp / rtx_screen.hip): the set and the parameters a handle holds (rtx_index_set_screen; null: off)
 const rtx_screen_set *index_screen(const rtx_index *index, rtx_screen_params *params);
+// distinct reads of a run (rtx_tally.hip): the object a handle holds (rtx_index_set_tally; null: off), its device and its samples
+rtx_tally *index_tally(const rtx_index *index);
+int tally_device(const rtx_tally *tally);
+uint32_t tally_samples(const rtx_tally *tally);
 bool index_device_text(const rtx_index *index);  // RTX_OPT_DEVICE_TEXT  // RTX_OPT_RUN_AHEAD, returns the previous value
 bool hw_queues_for_run_ahead();  // (host_threads.cpp) GPU_MAX_HW_QUEUES reads six or more: transfers do not share a hardware queue with kernels
 
