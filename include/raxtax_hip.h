@@ -694,6 +694,69 @@ int rtx_index_set_tally(rtx_index *index, rtx_tally *tally);
 rtx_tally *rtx_index_tally(const rtx_index *index);
 int rtx_raxtax_last_tally(uint64_t *queries, uint64_t *counted, uint64_t *entries_added, double *busy_seconds);
 
+/* ---- OTUs of a run (rtx_otu.hip, host_otu.cpp) ---------------------------------------------------------------------------------------------
+ * The distinct reads of a run collapsed into OTUs by Swarm's d = 1 rule (Mahe et al.), with breaking -- what `swarm` leaves by default.
+ * Exact, integers only, independent of scheduling.  The input is an rtx_tally_table: rows by total size descending, then bytes ascending;
+ * the row index is the rank.  Codes are one per byte; 1, 2, 4, 8 are A, C, G, T.
+ *   link         rows x and y are linked iff y is x with one code deleted (at any position, whatever the code), or the same with x and y
+ *                swapped, or x and y have equal length and differ at exactly one position where at least one of the two holds one of
+ *                1, 2, 4, 8: the symmetric closure of "x generates y by deleting one code or by replacing one code with A, C, G or T".
+ *                An N (15) against a plain base links; two different ambiguity codes at one position do not.  A row longer than
+ *                RTX_OTU_MAX_LEN has no link at all and is counted in long_rows.  The links are pairs (a, b), a < b, sorted by (a, b).
+ *   OTU          take the unassigned row of lowest rank as a seed; grow it breadth-first, a member x pulling in every still unassigned
+ *                linked y with size[y] <= size[x]; repeat until every row is assigned.  Equivalently (what the device computes): the label
+ *                of y is the lowest rank of any row from which y is reached along links whose sizes never increase.  OTUs are numbered
+ *                from 0 in the order of their seeds' ranks; an OTU's size per column is the sum over its members.
+ *   rtx_otu_cluster       on GPU `device` (RTX_ERR_NO_DEVICE without a gfx950): the rows are uploaded and laid out in a table of their own
+ *                ({tag, row + 1} slots, at most half full); the link kernel forms the hash of every single-difference variant of a row from
+ *                the row's own prefix and suffix sums of word mixes and probes the table read-only -- a hash picks the candidates, the
+ *                bytes decide, always; links are appended through a counter that goes on counting past the buffer (initial_links pairs;
+ *                0: a default from the row count), and a pass that does not fit is run once more in a buffer that does (link_passes);
+ *                labels are propagated with atomicMin over the links to the fixed point (rounds); a scan numbers the seeds.
+ *   rtx_otu_cluster_host  the same result from the definition: every variant looked up in the table's own map, then the greedy growth as
+ *                stated.  Equal to the device's result field by field, except rounds and link_passes (1).
+ *                params (NULL: defaults): differences 0 or 1 mean 1, anything else RTX_ERR_INVALID; flags must be 0.  More than 2^31 - 2
+ *                rows: RTX_ERR_INVALID.  The table is laid out (rtx_tally_table_view) and otherwise unchanged.
+ *   rtx_otu_view          valid until the object is destroyed.  rtx_otu_times: seconds of upload (and table layout), link passes, label rounds
+ *                and numbering, download and sort of the last device run; all 0 for a host result.
+ *   rtx_otu_format_fasta  `>otu{k};size={N};seed=uniq{rank}\n{sequence of the seed}\n` per OTU, k from 1, rank as in rtx_tally_format_fasta
+ *                of the same table.  OTUs with a total below minsize are left out, the numbers stay.  Buffer protocol of
+ *                rtx_tally_format_fasta.  `table` must be the table the OTUs were made from (RTX_ERR_INVALID when the row counts differ).
+ *   rtx_otu_format_table  `#otu\t{names, tab-separated}\n`, then `otu{k}\t{counts}\n` per OTU under the same minsize.  One name per column.
+ *   rtx_otu_format_map    `uniq{rank}\totu{k}\n` per row of the table.
+ *   RTX_DEFAULT_OTU_HASH_MASK (rtx_set_default_option; default: all ones; 0 restores it): the hashes of rtx_otu_cluster are ANDed with this
+ *                mask, read at every call.  For tests: under a mask of two bits every probe ends in the byte compare. */
+#define RTX_DEFAULT_OTU_HASH_MASK 5
+#define RTX_OTU_MAX_LEN 4096
+typedef struct rtx_otu rtx_otu;
+typedef struct rtx_otu_params {
+    uint32_t differences; /* 0 or 1: 1 */
+    uint32_t flags;       /* 0 */
+    uint64_t initial_links;
+} rtx_otu_params;
+typedef struct rtx_otu_view_t {
+    uint64_t n_rows, n_otus;
+    uint32_t n_columns;
+    const uint32_t *otu;      /* [n_rows] the OTU of a row */
+    const uint32_t *seed;     /* [n_otus] the rank of the seed */
+    const uint64_t *members;  /* [n_otus] rows */
+    const uint64_t *sizes;    /* [n_otus] the sum of the counts */
+    const uint64_t *counts;   /* [n_otus x n_columns] */
+    uint64_t n_links;
+    const uint32_t *link_a, *link_b; /* [n_links] a < b, sorted by (a, b) */
+    uint32_t rounds;      /* device: label rounds up to and including the first without a change; host: 0 */
+    uint32_t link_passes; /* device: runs of the link kernel (2: the first buffer was too small); host: 1 */
+    uint64_t long_rows;
+} rtx_otu_view_t;
+int rtx_otu_cluster(int device, rtx_tally_table *table, const rtx_otu_params *params, rtx_otu **out);
+int rtx_otu_cluster_host(rtx_tally_table *table, const rtx_otu_params *params, rtx_otu **out);
+int rtx_otu_view(rtx_otu *otu, rtx_otu_view_t *view);
+int rtx_otu_times(const rtx_otu *otu, double seconds[4]);
+void rtx_otu_destroy(rtx_otu *otu);
+int64_t rtx_otu_format_fasta(rtx_otu *otu, rtx_tally_table *table, uint64_t minsize, char *buf, uint64_t cap);
+int64_t rtx_otu_format_table(rtx_otu *otu, const char *const *names, uint64_t minsize, char *buf, uint64_t cap);
+int64_t rtx_otu_format_map(rtx_otu *otu, char *buf, uint64_t cap);
+
 /* ---- primer trimming (rtx_trim.hip; rtx_index_set_primers is the host mirror's use of it) ---------------------------------------------------
  * Amplicon reads come with their PCR primers attached, the references without: what `cutadapt` is run for in front of a classifier, on the
  * device.  Exact integers; the host function and the device agree bit for bit.

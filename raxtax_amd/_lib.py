@@ -24,6 +24,8 @@ RTX_Q_OK, RTX_Q_NO_KMERS, RTX_Q_ALL_KMERS = 0, 1, 2
 RTX_OPT_DEREP = 27                 # rtx_index_set_option: raxtax() classifies each distinct read of a chunk once
 RTX_DEFAULT_DEREP_HASH_MASK = 3    # rtx_set_default_option: the hash of rtx_derep_run ANDed with a mask (tests)
 RTX_DEFAULT_TALLY_HASH_MASK = 4    # rtx_set_default_option: the hash of rtx_tally_add ANDed with a mask (tests)
+RTX_DEFAULT_OTU_HASH_MASK = 5      # rtx_set_default_option: the hashes of rtx_otu_cluster ANDed with a mask (tests)
+RTX_OTU_MAX_LEN = 4096
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 
 RTX_TRIM_5P, RTX_TRIM_3P = 0, 1      # rtx_trim_pattern.end
@@ -111,6 +113,15 @@ class TallyParams(C.Structure):   # rtx_tally_params
 class TallyView(C.Structure):   # rtx_tally_view
     _fields_ = [("n_entries", C.c_uint64), ("n_columns", C.c_uint32), ("bases", C.POINTER(C.c_uint8)), ("base_off", C.POINTER(C.c_uint64)), ("counts", C.POINTER(C.c_uint64)),
                 ("sizes", C.POINTER(C.c_uint64)), ("first", C.POINTER(C.c_uint64)), ("totals", C.c_uint64 * 3)]
+
+
+class OtuParams(C.Structure):   # rtx_otu_params
+    _fields_ = [("differences", C.c_uint32), ("flags", C.c_uint32), ("initial_links", C.c_uint64)]
+
+
+class OtuView(C.Structure):   # rtx_otu_view_t
+    _fields_ = [("n_rows", C.c_uint64), ("n_otus", C.c_uint64), ("n_columns", C.c_uint32), ("otu", u32p), ("seed", u32p), ("members", u64p), ("sizes", u64p), ("counts", u64p),
+                ("n_links", C.c_uint64), ("link_a", u32p), ("link_b", u32p), ("rounds", C.c_uint32), ("link_passes", C.c_uint32), ("long_rows", C.c_uint64)]
 
 
 class MergeParams(C.Structure):   # rtx_merge_params
@@ -303,6 +314,14 @@ _SIGNATURES = {
     "rtx_tally_table_destroy": (None, [C.c_void_p]),
     "rtx_tally_format_fasta": (C.c_int64, [C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
     "rtx_tally_format_table": (C.c_int64, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_otu_cluster": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(OtuParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_cluster_host": (C.c_int, [C.c_void_p, C.POINTER(OtuParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_view": (C.c_int, [C.c_void_p, C.POINTER(OtuView)]),
+    "rtx_otu_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rtx_otu_destroy": (None, [C.c_void_p]),
+    "rtx_otu_format_fasta": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_otu_format_table": (C.c_int64, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_otu_format_map": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "rtx_index_set_tally": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rtx_index_tally": (C.c_void_p, [C.c_void_p]),
     "rtx_raxtax_last_tally": (C.c_int, [u64p, u64p, u64p, C.POINTER(C.c_double)]),

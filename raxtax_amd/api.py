@@ -1923,6 +1923,91 @@ def tally_table_text(table: TallyTable, names: Sequence[str], minsize: int = 1) 
     return _tally_text(_lib.load().rtx_tally_format_table, table, arr, int(minsize))
 
 
+class Otus:
+    """The OTUs of a run (rtx_otu): the rows of a TallyTable clustered by Swarm's d = 1 rule, by otu_cluster() on a GPU or otu_cluster_host().
+      otu      [rows] the OTU of a row, from 0 in the order of the seeds       seed     [otus] the rank of the seed
+      members  [otus] rows                                                     sizes    [otus] the sum of the counts
+      counts   [otus, columns]                                                 links    [n, 2] the linked rows (a, b), a < b, sorted
+      rounds, link_passes (the device's), long_rows (rows above RTX_OTU_MAX_LEN: no links)
+      seconds  upload, link passes, labels and numbering, download of a device run"""
+
+    def __init__(self, handle, table: "TallyTable"):
+        self._lib = _lib.load()
+        self._h = handle
+        self.table = table   # (the formatters read the seeds' sequences from it)
+        v = _lib.OtuView()
+        check(self._lib.rtx_otu_view(self._h, C.byref(v)))
+        nr, no, nl, nc = int(v.n_rows), int(v.n_otus), int(v.n_links), int(v.n_columns)
+
+        def arr(p, n, dtype, shape=None):
+            if n == 0:
+                return np.zeros(shape if shape else (0,), dtype)
+            return np.ctypeslib.as_array(p, shape=(n,)).copy().reshape(shape if shape else (n,))
+
+        self.n_rows, self.n_otus, self.columns = nr, no, nc
+        self.otu = arr(v.otu, nr, np.uint32)
+        self.seed = arr(v.seed, no, np.uint32)
+        self.members = arr(v.members, no, np.uint64)
+        self.sizes = arr(v.sizes, no, np.uint64)
+        self.counts = arr(v.counts, no * nc, np.uint64, (no, nc))
+        self.links = np.stack([arr(v.link_a, nl, np.uint32), arr(v.link_b, nl, np.uint32)], axis=1)
+        self.rounds, self.link_passes, self.long_rows = int(v.rounds), int(v.link_passes), int(v.long_rows)
+        t = (C.c_double * 4)()
+        check(self._lib.rtx_otu_times(self._h, t))
+        self.seconds = tuple(float(x) for x in t)
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_otu_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _otu_params(differences: int = 1, flags: int = 0, initial_links: int = 0):
+    return C.byref(_lib.OtuParams(int(differences), int(flags), int(initial_links)))
+
+
+def otu_cluster(table: TallyTable, device: int = 0, **params) -> Otus:
+    """rtx_otu_cluster: the OTUs of the table's rows, on GPU `device`.  params: differences (1), flags (0), initial_links (0: a default)."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_cluster(int(device), table._h, _otu_params(**params), C.byref(h)))
+    return Otus(h, table)
+
+
+def otu_cluster_host(table: TallyTable, **params) -> Otus:
+    """rtx_otu_cluster_host: the same from the definition, on the host."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_cluster_host(table._h, _otu_params(**params), C.byref(h)))
+    return Otus(h, table)
+
+
+def _otu_text(fn, otus, *args) -> str:
+    n = check(fn(otus._h, *args, None, 0))
+    buf = C.create_string_buffer(max(n, 1))
+    check(fn(otus._h, *args, buf, n))
+    return buf.raw[:n].decode()
+
+
+def otu_fasta(otus: Otus, minsize: int = 1) -> str:
+    """rtx_otu_format_fasta: `>otu{k};size={N};seed=uniq{rank}` and the seed's sequence per OTU (PREFIX/raxtax.otus of raxtax-hip --otus)."""
+    return _otu_text(_lib.load().rtx_otu_format_fasta, otus, otus.table._h, int(minsize))
+
+
+def otu_table_text(otus: Otus, names: Sequence[str], minsize: int = 1) -> str:
+    """rtx_otu_format_table: the OTU x sample table of read counts (PREFIX/raxtax.otus.tsv); one name per column."""
+    if len(names) != otus.columns:
+        raise ValueError(f"{len(names)} names for {otus.columns} column(s)")
+    arr = (C.c_char_p * len(names))(*[s.encode() for s in names])
+    return _otu_text(_lib.load().rtx_otu_format_table, otus, arr, int(minsize))
+
+
+def otu_map_text(otus: Otus) -> str:
+    """rtx_otu_format_map: `uniq{rank}\totu{k}` per row of the table (PREFIX/raxtax.otus.map)."""
+    return _otu_text(_lib.load().rtx_otu_format_map, otus)
+
+
 def raxtax_last_tally() -> Tuple[int, int, int, float]:
     """rtx_raxtax_last_tally: (queries of the tallied chunks, those that counted, entries the objects gained, busy seconds of the stage) of
     the last raxtax() call of this process; all 0 when its handles had no tally."""

@@ -16,6 +16,11 @@
 //    the file; read, summed and written once at the end; rtx_tally_format_fasta).  The reads counted are those that go on to be classified, as given (also
 //    under --strand both).  With --tags also PREFIX/raxtax.uniques.tsv, the sequence x sample table of read counts (rtx_tally_format_table).  Entries
 //    below N (default 1) are left out of both files, the ranks stay.  Sequences beyond the caps are not stored; their reads are named in the log.
+//   PREFIX/raxtax.otus    (--uniques --otus [--otus-minsize N]) the distinct reads of the run collapsed into OTUs by Swarm's d = 1 rule on the first device
+//    (rtx_otu.hip: after the tables of the handles are summed; the whole table is clustered, --uniques-minsize only filters what is printed of the
+//    uniques): `>otu{k};size={N};seed=uniq{rank}` and the seed's sequence (rtx_otu_format_fasta); PREFIX/raxtax.otus.map, `uniq{rank}\totu{k}` per
+//    distinct read; with --tags also PREFIX/raxtax.otus.tsv, the OTU x sample table of read counts.  OTUs below N (default 1) are left out of
+//    raxtax.otus and raxtax.otus.tsv, the numbers stay.
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
 //   PREFIX/raxtax.demux (--tags SHEET) and PREFIX/raxtax.samples (with --profile as well): below
 //   (--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]: every read is assigned to a sample by the inline tags at
@@ -173,7 +178,7 @@ std::string fingerprint(const std::string &path) {
 std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
                             const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string(),
                             const std::string &chimera = std::string(), const std::string &tags = std::string(), const std::string &contaminants = std::string(),
-                            const std::string &uniques = std::string()) {
+                            const std::string &uniques = std::string(), const std::string &otus = std::string()) {
     std::ostringstream ss;
     ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
        << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
@@ -186,6 +191,7 @@ std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv
     if (!tags.empty()) ss << ",\n  \"tags\": \"" << tags << "\"";  // (... and --tags with its settings: demultiplexed reads are other reads)
     if (!contaminants.empty()) ss << ",\n  \"contaminants\": \"" << contaminants << "\"";  // (... and --contaminants with its settings and the set's fingerprint: contaminants have no lines)
     if (!uniques.empty()) ss << ",\n  \"uniques\": \"" << uniques << "\"";  // (... and --uniques with its settings: the table is the run's, a resumed run would miss reads)
+    if (!otus.empty()) ss << ",\n  \"otus\": \"" << otus << "\"";  // (... and --otus with its setting: its files are the run's)
     ss << "\n}\n";
     return ss.str();
 }
@@ -273,6 +279,9 @@ int main(int argc, char **argv) {
     bool uniques = false;         // --uniques: a tally (rtx_tally.hip) on every handle, PREFIX/raxtax.uniques (and raxtax.uniques.tsv with --tags)
     uint64_t uniques_minsize = 1, uniques_max_entries = 0, uniques_max_bytes = 0;  // --uniques-minsize N, --uniques-max-entries N, --uniques-max-bytes N (0: the library's defaults)
     std::string uniques_opts;     // those three as given (empty: none)
+    bool otus = false;            // --otus: the table of --uniques clustered into OTUs (rtx_otu.hip), PREFIX/raxtax.otus, raxtax.otus.map (and raxtax.otus.tsv with --tags)
+    uint64_t otus_minsize = 1;    // --otus-minsize N
+    bool otus_minsize_given = false;
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -421,11 +430,20 @@ int main(int argc, char **argv) {
             (a == "--uniques-minsize" ? uniques_minsize : a == "--uniques-max-entries" ? uniques_max_entries : uniques_max_bytes) = (uint64_t)x;
             uniques_opts += (uniques_opts.empty() ? "" : " ") + a;
         }
+        else if (a == "--otus") otus = true;
+        else if (a == "--otus-minsize") {
+            char *end = nullptr;
+            const char *v = val();
+            const long long x = strtoll(v, &end, 10);
+            if (end == v || *end != '\0' || x < 1) { fprintf(stderr, "raxtax-hip: --otus-minsize takes a positive integer\n"); return 64; }
+            otus_minsize = (uint64_t)x;
+            otus_minsize_given = true;
+        }
         else if (a == "--batch") chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N]]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -615,6 +633,10 @@ int main(int argc, char **argv) {
     const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
     const std::string uniques_path = prefix + "/raxtax.uniques", uniques_table_path = prefix + "/raxtax.uniques.tsv";
     if (!uniques_opts.empty() && !uniques) { fprintf(stderr, "raxtax-hip: %s sets how the distinct reads are kept and written and needs --uniques\n", uniques_opts.c_str()); return 64; }
+    const std::string otus_path = prefix + "/raxtax.otus", otus_map_path = prefix + "/raxtax.otus.map", otus_table_path = prefix + "/raxtax.otus.tsv";
+    if (otus_minsize_given && !otus) { fprintf(stderr, "raxtax-hip: --otus-minsize sets what is written of the OTUs and needs --otus\n"); return 64; }
+    if (otus && !uniques) { fprintf(stderr, "raxtax-hip: --otus clusters the distinct reads of the run and needs --uniques\n"); return 64; }
+    const std::string otus_spec = otus ? "minsize=" + std::to_string(otus_minsize) : std::string();
     std::string uniques_spec;
     if (uniques) uniques_spec = "minsize=" + std::to_string(uniques_minsize) + " max_entries=" + std::to_string(uniques_max_entries) + " max_bytes=" + std::to_string(uniques_max_bytes);
     if (device_format && derep) {
@@ -627,7 +649,7 @@ int main(int argc, char **argv) {
     }
     // ---- checkpoint (io.rs:202-263)
     std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec);
+    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec, otus_spec);
     bool resume = false;
     if (!redo && is_file(ckp_json)) {
         std::string have;
@@ -709,7 +731,7 @@ int main(int argc, char **argv) {
     {
         const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
         std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec));
+        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec, otus_spec));
         f.close();
         rename(tmp.c_str(), ckp_json.c_str());
     }
@@ -931,7 +953,7 @@ int main(int argc, char **argv) {
     if (want_hits) sink.hits.open(hits_path, mode);
     else if (mode == std::ios::trunc) remove(hits_path.c_str());  // (likewise)
     if (mode == std::ios::trunc) remove(profile_path.c_str());  // (written at the end of a run with --profile)
-    if (mode == std::ios::trunc) { remove(uniques_path.c_str()); remove(uniques_table_path.c_str()); }  // (written at the end of a run with --uniques)
+    if (mode == std::ios::trunc) { remove(uniques_path.c_str()); remove(uniques_table_path.c_str()); remove(otus_path.c_str()); remove(otus_map_path.c_str()); remove(otus_table_path.c_str()); }  // (written at the end of a run with --uniques)
     if (!primers.empty()) {
         const bool header = mode == std::ios::trunc || !is_file(trim_path);
         sink.trim.open(trim_path, mode);
@@ -1358,6 +1380,29 @@ int main(int argc, char **argv) {
             tf << table;
             tf.close();
             if (!tf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", uniques_table_path.c_str()); return 74; }
+        }
+        if (otus) {  // the OTUs of the run: the summed table, whole, clustered on the first device
+            rtx_otu *o = nullptr;
+            rtx_otu_view_t ov{};
+            std::string otu_fasta, otu_map, otu_table;
+            trc = rtx_otu_cluster(devices[0], sum, nullptr, &o);
+            if (trc == RTX_OK) trc = rtx_otu_view(o, &ov);
+            if (trc == RTX_OK) format(otu_fasta, [&](char *buf, uint64_t cap) { return rtx_otu_format_fasta(o, sum, otus_minsize, buf, cap); });
+            if (trc == RTX_OK) format(otu_map, [&](char *buf, uint64_t cap) { return rtx_otu_format_map(o, buf, cap); });
+            if (trc == RTX_OK && tags_on) format(otu_table, [&](char *buf, uint64_t cap) { return rtx_otu_format_table(o, names.data(), otus_minsize, buf, cap); });
+            if (trc != RTX_OK) { fprintf(stderr, "[ERROR] OTUs: %s\n", rtx_last_error()); return 70; }
+            fprintf(stderr, "[INFO ] --otus: %llu distinct reads, %llu links, %llu OTUs, %u rounds\n", (unsigned long long)ov.n_rows, (unsigned long long)ov.n_links,
+                    (unsigned long long)ov.n_otus, ov.rounds);
+            if (ov.long_rows)
+                fprintf(stderr, "[INFO ] --otus: %llu distinct reads are longer than %d bases and stand alone\n", (unsigned long long)ov.long_rows, RTX_OTU_MAX_LEN);
+            const std::pair<const std::string *, const std::string *> files[] = {{&otus_path, &otu_fasta}, {&otus_map_path, &otu_map}, {&otus_table_path, &otu_table}};
+            for (size_t k = 0; k < (tags_on ? 3u : 2u); k++) {
+                std::ofstream of(*files[k].first, std::ios::trunc);
+                of << *files[k].second;
+                of.close();
+                if (!of.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", files[k].first->c_str()); return 74; }
+            }
+            rtx_otu_destroy(o);
         }
         rtx_tally_table_destroy(sum);
         for (rtx_tally_table *t : tables) rtx_tally_table_destroy(t);

@@ -72,6 +72,8 @@ void lay_out(rtx_tally_table &t) {
     t.laid_out = true;
 }
 
+}  // namespace
+
 // the two-pass protocol of the formatters (rtx_profile_format)
 int64_t hand_out(const char *who, const std::string &text, char *buf, uint64_t cap) {
     if (!buf) return (int64_t)text.size();
@@ -83,7 +85,6 @@ int64_t hand_out(const char *who, const std::string &text, char *buf, uint64_t c
     return (int64_t)text.size();
 }
 
-}  // namespace
 }  // namespace rtx
 
 extern "C" {

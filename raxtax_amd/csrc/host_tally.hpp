@@ -31,5 +31,7 @@ uint64_t tally_table_entry(rtx_tally_table &t, const uint8_t *seq, uint64_t len)
 // the chunk (*counted) on top of `so_far` within 2^32 - 1.  RTX_ERR_INVALID with the error text set, `who` in front.
 int tally_check_chunk(const char *who, uint64_t n, const uint8_t *bases, const uint64_t *base_off, const uint32_t *sample, const uint32_t *weight, uint32_t columns,
                       uint64_t so_far, uint64_t *counted);
+// the two-pass protocol of the formatters (rtx_profile_format): the bytes of `text`, into buf when it is there and holds them
+int64_t hand_out(const char *who, const std::string &text, char *buf, uint64_t cap);
 
 }  // namespace rtx

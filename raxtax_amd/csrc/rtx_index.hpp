@@ -597,6 +597,7 @@ int enqueue_profile(rtx_index *ix, rtx_index::ResultSet &r);  // the batch being
 // ---- rtx_derep.hip
 void set_derep_hash_mask(uint64_t mask);  // RTX_DEFAULT_DEREP_HASH_MASK (rtx_set_default_option)
 void set_tally_hash_mask(uint64_t mask);  // RTX_DEFAULT_TALLY_HASH_MASK, rtx_tally.hip
+void set_otu_hash_mask(uint64_t mask);    // RTX_DEFAULT_OTU_HASH_MASK, rtx_otu.hip
 // ---- rtx_text.hip
 int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of the batch being downloaded (synchronous)
 
