@@ -68,11 +68,16 @@
 // (parser.rs:150-153) and half-written result lines of unlisted queries are purged first.
 // Inputs ending in .gz / .gzip are decompressed on the fly (utils.rs:42-60 get_reader: the extension decides).
 // Out of scope: raxtax.log, progress bars, thread options.
+//
+// The file in the order of a run, main() at the end: options (Options, parse_args), what they come to before any device is touched (Plan,
+// Identity, validate), the per-read reports (Report, Sink and the callbacks), the reader's thread (BlockQueue, read_single, read_paired),
+// the handles, the loop over blocks with the totals of the stages (Stage), the files written at the end of a run.
 #include <sys/stat.h>
 #include <zlib.h>
 
 #include <cctype>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <condition_variable>
 #include <deque>
@@ -93,6 +98,8 @@
 #include "raxtax_hip.h"
 
 namespace {
+
+using ull = unsigned long long;
 
 // utils::get_reader (utils.rs:42-60): the file's last extension, lower-cased, "gz" or "gzip" = a GzDecoder in front of the reader
 bool is_gz(const std::string &path) {
@@ -141,21 +148,25 @@ struct Input {
     }
 };
 
+// The next piece of the file behind what the buffer holds (eof: it was the last); false on a read error
+bool read_on(Input &in, std::string &buf, size_t piece, bool &eof) {
+    const size_t have = buf.size();
+    buf.resize(have + piece);
+    const size_t got = in.read(&buf[have], piece);
+    if (got == (size_t)-1) return false;
+    buf.resize(have + got);
+    eof = got < piece;
+    return true;
+}
+
 bool slurp(const std::string &path, std::string &out) {
     Input in;
     if (!in.open(path)) return false;
     out.clear();
-    const size_t piece = (size_t)16 << 20;
-    for (;;) {
-        const size_t have = out.size();
-        out.resize(have + piece);
-        const size_t got = in.read(&out[have], piece);
-        if (got == (size_t)-1) { in.close(); return false; }
-        out.resize(have + got);
-        if (got < piece) break;
-    }
+    bool eof = false, ok = true;
+    while (ok && !eof) ok = read_on(in, out, (size_t)16 << 20, eof);
     in.close();
-    return true;
+    return ok;
 }
 
 bool is_file(const std::string &p) { struct stat st; return stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
@@ -172,29 +183,535 @@ std::string fingerprint(const std::string &path) {
     return ss.str();
 }
 
-// (--strand both is part of the checkpoint like the three flags: a rerun with the other setting starts over; a default run writes the file it always wrote)
-// (... and so is --hits, and the cutoff of --profile in hundredths: 0 without the option)
-// (... and --primers with its two settings, as given: trimmed reads are other reads)
-std::string checkpoint_json(const std::string &fp, bool raw, bool skip, bool tsv, bool both, bool hits, uint32_t profile = 0, bool identity = false,
-                            const std::string &primers = std::string(), const std::string &quality = std::string(), const std::string &merge = std::string(),
-                            const std::string &chimera = std::string(), const std::string &tags = std::string(), const std::string &contaminants = std::string(),
-                            const std::string &uniques = std::string(), const std::string &otus = std::string()) {
-    std::ostringstream ss;
-    ss << "{\n  \"db_fingerprint\": \"" << fp << "\",\n  \"raw_confidence\": " << (raw ? "true" : "false")
-       << ",\n  \"skip_exact_matches\": " << (skip ? "true" : "false") << ",\n  \"tsv\": " << (tsv ? "true" : "false")
-       << (both ? ",\n  \"strand\": \"both\"" : "") << (hits ? ",\n  \"hits\": true" : "") << (identity ? ",\n  \"identity\": true" : "");
-    if (profile) ss << ",\n  \"profile\": " << profile;
-    if (!primers.empty()) ss << ",\n  \"primers\": \"" << primers << "\"";
-    if (!quality.empty()) ss << ",\n  \"quality\": \"" << quality << "\"";  // (... and the quality filter's settings, as given)
-    if (!merge.empty()) ss << ",\n  \"merge\": \"" << merge << "\"";  // (... and --reverse with the merge settings: merged reads are other reads)
-    if (!chimera.empty()) ss << ",\n  \"chimera\": \"" << chimera << "\"";  // (... and --chimera with its two settings: flagged reads have no lines)
-    if (!tags.empty()) ss << ",\n  \"tags\": \"" << tags << "\"";  // (... and --tags with its settings: demultiplexed reads are other reads)
-    if (!contaminants.empty()) ss << ",\n  \"contaminants\": \"" << contaminants << "\"";  // (... and --contaminants with its settings and the set's fingerprint: contaminants have no lines)
-    if (!uniques.empty()) ss << ",\n  \"uniques\": \"" << uniques << "\"";  // (... and --uniques with its settings: the table is the run's, a resumed run would miss reads)
-    if (!otus.empty()) ss << ",\n  \"otus\": \"" << otus << "\"";  // (... and --otus with its setting: its files are the run's)
-    ss << "\n}\n";
-    return ss.str();
+// A file written once, at the end of a run; false behind the message
+bool write_whole(const std::string &path, const std::string &text) {
+    std::ofstream f(path, std::ios::trunc);
+    f << text;
+    f.close();
+    if (!f.good()) fprintf(stderr, "[ERROR] cannot write %s\n", path.c_str());
+    return f.good();
 }
+
+// The two-pass protocol of the library's formatters: fn(nullptr, 0) says how long the text is, fn(buf, cap) writes it
+template <class F>
+int format_two_pass(std::string &text, F fn) {
+    const int64_t need = fn(nullptr, 0);
+    if (need < 0) return (int)need;
+    text.resize((size_t)need);
+    const int64_t got = fn(&text[0], text.size());
+    return got == need ? RTX_OK : (got < 0 ? (int)got : RTX_ERR_STATE);
+}
+
+// --timing: seconds per stage of the run, one JSON object on stderr at the end
+struct Laps {
+    std::chrono::steady_clock::time_point prev = std::chrono::steady_clock::now();
+    std::ostringstream log;
+    void lap(const char *what) {
+        const auto now = std::chrono::steady_clock::now();
+        log << (log.tellp() > 0 ? ", " : "") << '"' << what << "\": " << std::chrono::duration<double>(now - prev).count();
+        prev = now;
+    }
+};
+
+// ---- options: everything the argument loop sets
+
+struct Options {
+    std::string db, qf, prefix = "raxtax";
+    bool skip_exact = false, raw = false, tsv = false, only_db = false, skip_db = false, clean = false, redo = false, timing = false;
+    std::vector<int> devices{0};
+    bool device_format = false;  // --device-format: RTX_OPT_DEVICE_TEXT on every handle: the lines are formatted on the GPU
+    bool both_strands = false;   // --strand both: RTX_OPT_STRAND on every handle
+    bool want_hits = false;      // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
+    bool want_identity = false;  // --identity: RTX_OPT_IDENTITY on every handle, dist and identity at the end of every line of raxtax.hits (implies --hits)
+    bool derep = false;          // --derep: RTX_OPT_DEREP on every handle (each distinct read of a chunk is classified once; the files are the same)
+    std::vector<std::pair<std::string, std::string>> primer_pairs;  // --primers FWD:REV (once or twice): rtx_index_set_primers on every handle, PREFIX/raxtax.trim
+    uint32_t primer_pct = 10, primer_window = 0;                   // --primer-errors PCT, --primer-window N
+    rtx_qual_params qual{33u, 0u, -1, -1.0, 0u, 0u, -1, -1.0, -1.0};  // --fastq-ascii and the filter options: rtx_index_set_quality on every handle, PREFIX/raxtax.qc
+    std::string qual_spec;                                             // the filter options as given, name=value (empty: none) -- part of the checkpoint
+    std::string rev_file;                                              // --reverse FILE: the reverse mates of the pairs of -i, merged on the device (rtx_merge_queries), PREFIX/raxtax.merge
+    rtx_merge_params merge{33u, 16u, 10u, 100u, 41u};                  // --merge-minovlen, --merge-maxdiffs, --merge-maxdiffpct, --merge-qcap (ascii_base: --fastq-ascii)
+    std::string merge_opts;                                            // the names of the merge options given (empty: none)
+    bool chim_on = false;                                              // --chimera: rtx_index_set_chimera on every handle, PREFIX/raxtax.chimera
+    rtx_chimera_params chim{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA};  // --chimera-segments, --chimera-mindelta
+    std::string chim_opts;                                             // those two, likewise
+    std::string contam_file;                                           // --contaminants FILE: rtx_index_set_screen on every handle, PREFIX/raxtax.screen
+    rtx_screen_params contam{2u, 50u};                                 // --contam-minhits N, --contam-minpct P
+    std::string contam_opts;                                           // those two, likewise
+    std::string tags_file;                                             // --tags SHEET: rtx_index_set_tags on every handle, PREFIX/raxtax.demux (and raxtax.samples with --profile)
+    rtx_demux_params tag_params{0u, 0u};                               // --tag-mismatches N, --tag-offset N
+    bool tags_both = false;                                            // --tags-both-orientations
+    std::string tag_opts;                                              // those three, likewise
+    bool uniques = false;         // --uniques: a tally (rtx_tally.hip) on every handle, PREFIX/raxtax.uniques (and raxtax.uniques.tsv with --tags)
+    uint64_t uniques_minsize = 1, uniques_max_entries = 0, uniques_max_bytes = 0;  // --uniques-minsize N, --uniques-max-entries N, --uniques-max-bytes N (0: the library's defaults)
+    std::string uniques_opts;     // those three, likewise
+    bool otus = false;            // --otus: the table of --uniques clustered into OTUs (rtx_otu.hip), PREFIX/raxtax.otus, raxtax.otus.map (and raxtax.otus.tsv with --tags)
+    uint64_t otus_minsize = 1;    // --otus-minsize N
+    std::string otus_opts;        // that one, likewise
+    uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
+    size_t chunk = 0;             // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (classify_blocks)
+    size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
+};
+
+// An option that takes one number.  kind: 'u' / 'i' a whole number, least .. most, into a uint32_t / an int32_t; 'r' a number that is not negative
+// into a double; 'p' a positive integer, at most `most`, into a uint64_t.  given: the string of its group that records it
+struct Numeric { const char *flag; char kind; long long least, most; void *to; std::string *given; };
+
+// 0, or the exit code behind the message
+int parse_args(int argc, char **argv, Options &o) {
+    const Numeric numeric[] = {
+        {"--trunclen", 'u', 1, RTX_QUAL_MAX_READ, &o.qual.trunc_len, &o.qual_spec},
+        {"--minlen", 'u', 1, RTX_QUAL_MAX_READ, &o.qual.min_len, &o.qual_spec},
+        {"--maxlen", 'u', 1, RTX_QUAL_MAX_READ, &o.qual.max_len, &o.qual_spec},
+        {"--maxns", 'i', 0, RTX_QUAL_MAX_READ, &o.qual.max_ns, &o.qual_spec},
+        {"--truncq", 'i', 0, 93, &o.qual.trunc_qual, &o.qual_spec},
+        {"--truncee", 'r', 0, 0, &o.qual.trunc_ee, &o.qual_spec},
+        {"--maxee", 'r', 0, 0, &o.qual.max_ee, &o.qual_spec},
+        {"--maxee-rate", 'r', 0, 0, &o.qual.max_ee_rate, &o.qual_spec},
+        {"--merge-minovlen", 'u', 1, RTX_MERGE_MAX_READ, &o.merge.min_overlap, &o.merge_opts},
+        {"--merge-maxdiffs", 'u', 0, RTX_MERGE_MAX_READ, &o.merge.max_diffs, &o.merge_opts},
+        {"--merge-maxdiffpct", 'u', 0, 100, &o.merge.max_diff_pct, &o.merge_opts},
+        {"--merge-qcap", 'u', 0, 93, &o.merge.q_cap, &o.merge_opts},
+        {"--chimera-mindelta", 'u', 0, RTX_CHIMERA_MAX_QUERY, &o.chim.mindelta, &o.chim_opts},
+        {"--chimera-segments", 'u', 2, RTX_CHIMERA_MAX_SEGMENTS, &o.chim.segments, &o.chim_opts},
+        {"--contam-minhits", 'u', 1, 0x7FFFFFFF, &o.contam.min_hits, &o.contam_opts},
+        {"--contam-minpct", 'u', 0, 100, &o.contam.min_pct, &o.contam_opts},
+        {"--tag-mismatches", 'u', 0, RTX_DEMUX_MAX_MISMATCHES, &o.tag_params.max_mismatches, &o.tag_opts},
+        {"--tag-offset", 'u', 0, RTX_DEMUX_MAX_OFFSET, &o.tag_params.max_offset, &o.tag_opts},
+        {"--uniques-minsize", 'p', 1, LLONG_MAX, &o.uniques_minsize, &o.uniques_opts},
+        {"--uniques-max-entries", 'p', 1, 0x7FFFFFFE, &o.uniques_max_entries, &o.uniques_opts},
+        {"--uniques-max-bytes", 'p', 1, LLONG_MAX, &o.uniques_max_bytes, &o.uniques_opts},
+        {"--otus-minsize", 'p', 1, LLONG_MAX, &o.otus_minsize, &o.otus_opts},
+    };
+    for (int i = 1; i < argc; i++) {
+        std::string a = argv[i];
+        auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
+        const Numeric *num = nullptr;
+        for (const Numeric &n : numeric)
+            if (a == n.flag) num = &n;
+        if (num) {
+            const char *v = val();
+            char *end = nullptr;
+            if (num->kind == 'r') {
+                const double x = strtod(v, &end);
+                if (end == v || *end != 0 || !(x >= 0.0)) { fprintf(stderr, "raxtax-hip: %s takes a number that is not negative, not '%s'\n", num->flag, v); return 64; }
+                *static_cast<double *>(num->to) = x;
+            } else {
+                const long long x = strtoll(v, &end, 10);
+                if (end == v || *end != 0 || x < num->least || x > num->most) {
+                    if (num->kind == 'p') fprintf(stderr, "raxtax-hip: %s takes a positive integer\n", num->flag);
+                    else fprintf(stderr, "raxtax-hip: %s takes a whole number, %lld .. %lld, not '%s'\n", num->flag, num->least, num->most, v);
+                    return 64;
+                }
+                if (num->kind == 'p') *static_cast<uint64_t *>(num->to) = (uint64_t)x;
+                else if (num->kind == 'i') *static_cast<int32_t *>(num->to) = (int32_t)x;
+                else *static_cast<uint32_t *>(num->to) = (uint32_t)x;
+            }
+            std::string &given = *num->given;
+            if (&given == &o.qual_spec) given += (given.empty() ? "" : ";") + a.substr(2) + "=" + v;  // (the filter's settings go into the checkpoint as given)
+            else given += (given.empty() ? "" : " ") + a;
+        }
+        else if (a == "-d" || a == "--database-path") o.db = val();
+        else if (a == "-i" || a == "--query-file") o.qf = val();
+        else if (a == "-o" || a == "--prefix") o.prefix = val();
+        else if (a == "--skip-exact-matches") o.skip_exact = true;
+        else if (a == "--raw-confidence") o.raw = true;
+        else if (a == "--tsv") o.tsv = true;
+        else if (a == "--only-db") o.only_db = true;
+        else if (a == "--skip-db") o.skip_db = true;
+        else if (a == "-c" || a == "--clean") o.clean = true;
+        else if (a == "--redo") o.redo = true;
+        else if (a == "--timing") o.timing = true;
+        else if (a == "--device-format") o.device_format = true;
+        // CPU tuning flags of the reference (io.rs:139-153): accepted so that existing command lines keep working,
+        // without effect on the device path.  -t takes a value; clap also accepts -tN, --threads=N, -vv, -qq.
+        else if (a == "-t" || a == "--threads") (void)val();
+        else if (a.rfind("--threads=", 0) == 0 || (a.size() > 2 && a[0] == '-' && a[1] == 't' && isdigit((unsigned char)a[2]))) {}
+        else if (a == "--pin") {}
+        else if (a == "--verbose" || a == "--quiet" || (a.size() >= 2 && a[0] == '-' && a[1] != '-' &&
+                                                        a.find_first_not_of(a[1] == 'v' ? "v" : "q", 1) == std::string::npos &&
+                                                        (a[1] == 'v' || a[1] == 'q'))) {}
+        else if (a == "--device") o.devices.assign(1, atoi(val()));
+        else if (a == "--gpus") {  // devices 0 .. N-1
+            const int n = atoi(val());
+            o.devices.clear();
+            for (int d = 0; d < n; d++) o.devices.push_back(d);
+        } else if (a == "--devices") {  // an explicit list; a device may be named twice (two handles on one GPU)
+            o.devices.clear();
+            std::stringstream ss(val());
+            std::string tok;
+            while (std::getline(ss, tok, ',')) if (!tok.empty()) o.devices.push_back(atoi(tok.c_str()));
+        }
+        else if (a == "--strand") {
+            const std::string v = val();
+            if (v != "plus" && v != "both") { fprintf(stderr, "raxtax-hip: --strand takes plus or both\n"); return 64; }
+            o.both_strands = v == "both";
+        }
+        else if (a == "--hits") o.want_hits = true;
+        else if (a == "--identity") o.want_identity = o.want_hits = true;
+        else if (a == "--derep") o.derep = true;
+        else if (a == "--primers") {
+            const std::string v = val();
+            const size_t colon = v.find(':');
+            if (colon == std::string::npos || v.find(':', colon + 1) != std::string::npos || v.size() < 2) {
+                fprintf(stderr, "raxtax-hip: --primers takes FWD:REV (either side may be empty), not '%s'\n", v.c_str());
+                return 64;
+            }
+            o.primer_pairs.emplace_back(v.substr(0, colon), v.substr(colon + 1));
+        }
+        else if (a == "--primer-errors") {
+            const int x = atoi(val());
+            if (x < 0 || x > 99) { fprintf(stderr, "raxtax-hip: --primer-errors takes a percentage, 0 .. 99\n"); return 64; }
+            o.primer_pct = (uint32_t)x;
+        }
+        else if (a == "--primer-window") {
+            const int x = atoi(val());
+            if (x < 1 || x > RTX_TRIM_MAX_WINDOW) { fprintf(stderr, "raxtax-hip: --primer-window takes 1 .. %d bases\n", RTX_TRIM_MAX_WINDOW); return 64; }
+            o.primer_window = (uint32_t)x;
+        }
+        else if (a == "--fastq-ascii") {
+            const std::string v = val();
+            if (v != "33" && v != "64") { fprintf(stderr, "raxtax-hip: --fastq-ascii takes 33 or 64, not '%s'\n", v.c_str()); return 64; }
+            o.qual.ascii_base = (uint32_t)atoi(v.c_str());
+        }
+        else if (a == "-r" || a == "--reverse") o.rev_file = val();
+        else if (a == "--chimera") o.chim_on = true;
+        else if (a == "--contaminants") o.contam_file = val();
+        else if (a == "--tags") o.tags_file = val();
+        else if (a == "--tags-both-orientations") { o.tags_both = true; o.tag_opts += (o.tag_opts.empty() ? "" : " ") + a; }
+        else if (a == "--profile") {
+            char *end = nullptr;
+            const char *v = val();
+            const double x = strtod(v, &end);
+            const long c = end != v && *end == '\0' && x > 0.0 && x <= 1.0 ? lround(x * 100.0) : 0;
+            if (c < 1 || c > 100) { fprintf(stderr, "raxtax-hip: --profile takes a confidence cutoff in (0, 1], such as 0.8\n"); return 64; }
+            o.profile_cutoff = (uint32_t)c;
+        }
+        else if (a == "--uniques") o.uniques = true;
+        else if (a == "--otus") o.otus = true;
+        else if (a == "--batch") o.chunk = (size_t)atoll(val());
+        else if (a == "--block-bytes") o.block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
+        else {
+            fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N]]]\n"
+                            "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
+            return 64;
+        }
+    }
+    if (o.devices.empty()) { fprintf(stderr, "raxtax-hip: --gpus / --devices need at least one device\n"); return 64; }
+    if (o.db.empty() || (o.qf.empty() && !o.only_db) || (o.only_db && o.skip_db)) {
+        fprintf(stderr, "raxtax-hip: -d is required, -i unless --only-db; --only-db conflicts with --skip-db\n");
+        return 64;
+    }
+    return 0;
+}
+
+// ---- what the options come to, before the database is read and any device is touched
+
+// What makes up a run's identity: the text of PREFIX/raxtax.json, its entries in this order.  A rerun resumes only where the text is the same.  The
+// first four are always there; an entry of an option group is filled where validate() checks the group, and is left out while it is empty.
+struct Identity {
+    struct Entry { const char *key; bool quoted; std::string value; };
+    std::vector<Entry> entries{
+        {"db_fingerprint", true, ""}, {"raw_confidence", false, ""}, {"skip_exact_matches", false, ""}, {"tsv", false, ""},
+        {"strand", true, ""},         // "both": a rerun with the other setting starts over; a default run writes the file it always wrote
+        {"hits", false, ""},          // ... and so is --hits,
+        {"identity", false, ""},      //     --identity,
+        {"profile", false, ""},       //     and the cutoff of --profile in hundredths
+        {"primers", true, ""},        // --primers with its two settings, as given: trimmed reads are other reads
+        {"quality", true, ""},        // the quality filter's settings, as given
+        {"merge", true, ""},          // --reverse with the merge settings: merged reads are other reads
+        {"chimera", true, ""},        // --chimera with its two settings: flagged reads have no lines
+        {"tags", true, ""},           // --tags with its settings: demultiplexed reads are other reads
+        {"contaminants", true, ""},   // --contaminants with its settings and the set's fingerprint: contaminants have no lines
+        {"uniques", true, ""},        // --uniques with its settings: the table is the run's, a resumed run would miss reads
+        {"otus", true, ""},           // --otus with its setting: its files are the run's
+    };
+    std::string &operator[](const std::string &key) {
+        for (Entry &e : entries)
+            if (key == e.key) return e.value;
+        abort();
+    }
+    std::string json() const {
+        std::string s = "{";
+        for (size_t k = 0; k < entries.size(); k++) {
+            const Entry &e = entries[k];
+            if (k >= 4 && e.value.empty()) continue;
+            s += std::string(k ? ",\n  \"" : "\n  \"") + e.key + "\": " + (e.quoted ? "\"" + e.value + "\"" : e.value);
+        }
+        return s + "\n}\n";
+    }
+};
+
+struct Oligo { std::string name; std::vector<uint8_t> codes; uint32_t end; };  // a primer or a tag: at RTX_TRIM_5P or RTX_TRIM_3P
+
+struct Plan {
+    bool fastq = false;                                    // -i is FASTQ
+    bool qual_on = false, merge_on = false, tags_on = false, screen_on = false;  // (primers: !primers.empty(); the other groups are flags of Options)
+    std::vector<Oligo> primers, tags;                      // the patterns of --primers, the distinct tags of the sheet, in the order the run logs them
+    std::vector<rtx_demux_pair> tag_pairs;                 // the lines of the sheet: two tags and a sample
+    std::vector<std::string> sample_names, contam_names;   // the samples of the sheet; the records of --contaminants
+    rtx_screen_set *contam_set = nullptr;                  // freed once the handles hold what they need
+    Identity identity;
+};
+
+// parser.rs:11-34 for an oligo on the command line; 0 where the character is no IUPAC code
+uint8_t iupac_code(char ch) {
+    switch (toupper((unsigned char)ch)) {
+        case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8;
+        case 'W': return 9; case 'S': return 6; case 'M': return 3; case 'K': return 12; case 'R': return 5; case 'Y': return 10;
+        case 'B': return 14; case 'D': return 13; case 'H': return 11; case 'V': return 7; case 'N': return 15;
+        default: return 0;
+    }
+}
+
+// The codes of an oligo in IUPAC letters; false, and the letter, where one is no code
+bool parse_oligo(const std::string &oligo, std::vector<uint8_t> &codes, char &bad) {
+    for (char ch : oligo) {
+        const uint8_t c = iupac_code(ch);
+        if (!c) { bad = ch; return false; }
+        codes.push_back(c);
+    }
+    return true;
+}
+
+std::vector<uint8_t> revcomp(const std::vector<uint8_t> &x) {
+    std::vector<uint8_t> y(x.size() + 1);
+    (void)rtx_revcomp(x.data(), x.size(), y.data());
+    y.resize(x.size());
+    return y;
+}
+
+// An option of a group (given: their names) without the option that turns the group on
+bool orphan(const std::string &given, bool parent_on, const char *sentence) {
+    if (given.empty() || parent_on) return false;
+    fprintf(stderr, "raxtax-hip: %s %s\n", given.c_str(), sentence);
+    return true;
+}
+
+// --primers: the pattern list
+int primer_patterns(const Options &o, Plan &p) {
+    std::string spec;
+    for (const auto &pr : o.primer_pairs) {
+        std::vector<uint8_t> codes[2];
+        for (int side = 0; side < 2; side++) {
+            const std::string &oligo = side ? pr.second : pr.first;
+            char bad = 0;
+            if (!parse_oligo(oligo, codes[side], bad)) { fprintf(stderr, "raxtax-hip: --primers: '%c' in primer %s is no IUPAC code\n", bad, oligo.c_str()); return 64; }
+            if (oligo.size() > RTX_TRIM_MAX_PATTERN) { fprintf(stderr, "raxtax-hip: --primers: primer %s has %zu bases (at most %d)\n", oligo.c_str(), oligo.size(), RTX_TRIM_MAX_PATTERN); return 64; }
+        }
+        auto add = [&](const std::string &name, const std::vector<uint8_t> &c, uint32_t end) {
+            if (!c.empty()) p.primers.push_back({name, c, end});
+        };
+        add(pr.first, codes[0], RTX_TRIM_5P);
+        add("revcomp(" + pr.second + ")", revcomp(codes[1]), RTX_TRIM_3P);
+        if (o.both_strands) {
+            add(pr.second, codes[1], RTX_TRIM_5P);
+            add("revcomp(" + pr.first + ")", revcomp(codes[0]), RTX_TRIM_3P);
+        }
+        if (p.primers.size() > RTX_TRIM_MAX_PATTERNS) {
+            fprintf(stderr, "raxtax-hip: --primers: %s:%s makes %zu patterns (at most %d%s)\n", pr.first.c_str(), pr.second.c_str(), p.primers.size(), RTX_TRIM_MAX_PATTERNS,
+                    o.both_strands ? "; --strand both registers every oligo at both ends" : "");
+            return 64;
+        }
+        spec += (spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
+    }
+    if (!spec.empty()) p.identity["primers"] = spec + ";errors=" + std::to_string(o.primer_pct) + ";window=" + std::to_string(o.primer_window);
+    return 0;
+}
+
+// --tags: the sample sheet
+int read_sample_sheet(const Options &o, Plan &p) {
+    std::string sheet;
+    if (!slurp(o.tags_file, sheet)) { fprintf(stderr, "raxtax-hip: --tags: cannot read %s\n", o.tags_file.c_str()); return 66; }
+    auto strip = [](std::string s) {
+        while (!s.empty() && isspace((unsigned char)s.back())) s.pop_back();
+        size_t a = 0;
+        while (a < s.size() && isspace((unsigned char)s[a])) a++;
+        return s.substr(a);
+    };
+    auto tag_of = [&](const std::string &name, const std::vector<uint8_t> &codes, uint32_t end) -> uint32_t {  // a tag that several lines share is listed once
+        for (size_t k = 0; k < p.tags.size(); k++)
+            if (p.tags[k].end == end && p.tags[k].codes == codes) return (uint32_t)k;
+        p.tags.push_back({name, codes, end});
+        return (uint32_t)p.tags.size() - 1u;
+    };
+    std::istringstream lines(sheet);
+    std::string line;
+    for (unsigned line_no = 1; std::getline(lines, line); line_no++) {
+        line = line.substr(0, line.find('#'));
+        if (strip(line).empty()) continue;
+        std::vector<std::string> f;
+        for (size_t a = 0;;) {
+            const size_t t = line.find('\t', a);
+            f.push_back(strip(line.substr(a, t == std::string::npos ? std::string::npos : t - a)));
+            if (t == std::string::npos) break;
+            a = t + 1;
+        }
+        if (f.size() < 2 || f.size() > 3 || f[0].empty() || f[1].empty()) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: expected sample<TAB>fwd_tag<TAB>rev_tag\n", o.tags_file.c_str(), line_no); return 64; }
+        std::vector<uint8_t> codes[2];
+        const bool single = f.size() == 2 || f[2].empty() || f[2] == "-";
+        char bad = 0;
+        for (int side = 0; side < (single ? 1 : 2); side++)
+            if (!parse_oligo(f[1 + side], codes[side], bad)) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: '%c' is no IUPAC code\n", o.tags_file.c_str(), line_no, bad); return 64; }
+        size_t s = 0;
+        while (s < p.sample_names.size() && p.sample_names[s] != f[0]) s++;
+        if (s == p.sample_names.size()) p.sample_names.push_back(f[0]);
+        p.tag_pairs.push_back({tag_of(f[1], codes[0], RTX_TRIM_5P), single ? RTX_DEMUX_NO_TAG : tag_of("revcomp(" + f[2] + ")", revcomp(codes[1]), RTX_TRIM_3P), (uint32_t)s});
+        if (o.tags_both) {
+            if (single) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: --tags-both-orientations needs a rev_tag\n", o.tags_file.c_str(), line_no); return 64; }
+            p.tag_pairs.push_back({tag_of(f[2], codes[1], RTX_TRIM_5P), tag_of("revcomp(" + f[1] + ")", revcomp(codes[0]), RTX_TRIM_3P), (uint32_t)s});
+        }
+    }
+    std::vector<rtx_demux_tag> ct;
+    for (const Oligo &t : p.tags) ct.push_back({t.codes.data(), (uint32_t)t.codes.size(), t.end});
+    uint32_t x[5];  // the checks of the library on the list (rtx_demux_create makes them again): one read through the host function
+    if (rtx_demux_read(&o.tag_params, ct.data(), (uint32_t)ct.size(), p.tag_pairs.data(), (uint32_t)p.tag_pairs.size(), nullptr, 0, &x[0], &x[1], &x[2], &x[3], &x[4]) != RTX_OK) {
+        fprintf(stderr, "raxtax-hip: --tags: %s: %s\n", o.tags_file.c_str(), rtx_last_error());
+        return 64;
+    }
+    p.identity["tags"] = fingerprint(o.tags_file) + ";mismatches=" + std::to_string(o.tag_params.max_mismatches) + ";offset=" + std::to_string(o.tag_params.max_offset) +
+                         ";both=" + (o.tags_both ? "1" : "0");
+    return 0;
+}
+
+// --contaminants: the set of 16-mers and the names of the records
+int build_contaminant_set(const Options &o, Plan &p) {
+    std::string text;
+    if (!slurp(o.contam_file, text)) { fprintf(stderr, "raxtax-hip: --contaminants: cannot read %s\n", o.contam_file.c_str()); return 66; }
+    rtx_queries *cq = nullptr;  // (the query parser: the labels need no lineage)
+    if (rtx_queries_parse_fasta(text.data(), text.size(), nullptr, 0, &cq) != RTX_OK) { fprintf(stderr, "raxtax-hip: --contaminants: %s: %s\n", o.contam_file.c_str(), rtx_last_error()); return 66; }
+    const uint8_t *cb = nullptr;
+    const uint64_t *co = nullptr;
+    rtx_queries_data(cq, &cb, &co);
+    const uint64_t nc = rtx_queries_len(cq);
+    for (uint64_t i = 0; i < nc; i++) {
+        const std::string label = rtx_queries_label(cq, i);
+        p.contam_names.push_back(label.substr(0, label.find_first_of(" \t")));
+    }
+    uint64_t keys = 0, slots = 0, fp = 0;
+    const int brc = rtx_screen_set_build(nc, cb, co, &p.contam_set);
+    rtx_queries_destroy(cq);
+    if (brc != RTX_OK || rtx_screen_set_info(p.contam_set, &keys, &slots, nullptr, nullptr, &fp) != RTX_OK) {
+        fprintf(stderr, "raxtax-hip: --contaminants: %s: %s\n", o.contam_file.c_str(), rtx_last_error());
+        return 64;
+    }
+    char hex[24];
+    snprintf(hex, sizeof hex, "%016llx", (ull)fp);
+    p.identity["contaminants"] = "file=" + o.contam_file + ";minhits=" + std::to_string(o.contam.min_hits) + ";minpct=" + std::to_string(o.contam.min_pct) + ";keys=" + hex;
+    fprintf(stderr, "[INFO ] --contaminants: %llu record(s) of %s, %llu distinct 16-mers in %llu slots; a read is a contaminant from %u hit(s) and %u %% of its windows on\n",
+            (ull)nc, o.contam_file.c_str(), (ull)keys, (ull)slots, o.contam.min_hits, o.contam.min_pct);
+    return 0;
+}
+
+// Everything between the argument loop and the checkpoint: what cannot work is refused here, in this order, and what the run needs of the options is
+// left in the plan.  0, or the exit code behind the message
+int validate(Options &o, Plan &p) {
+    Identity &id = p.identity;
+    id["db_fingerprint"] = fingerprint(o.db);
+    id["raw_confidence"] = o.raw ? "true" : "false";
+    id["skip_exact_matches"] = o.skip_exact ? "true" : "false";
+    id["tsv"] = o.tsv ? "true" : "false";
+    if (o.both_strands) id["strand"] = "both";
+    if (o.want_hits) id["hits"] = "true";
+    if (o.want_identity) id["identity"] = "true";
+    if (o.profile_cutoff) id["profile"] = std::to_string(o.profile_cutoff);
+    // FASTQ or FASTA: the first non-blank byte of the query file.  A filter option needs quality strings
+    if (!o.qf.empty()) {
+        Input f;
+        if (f.open(o.qf)) {
+            char c = 0;
+            while (f.read(&c, 1) == 1 && isspace((unsigned char)c)) c = 0;
+            p.fastq = c == '@';
+            f.close();
+        }
+    }
+    const char *const input = o.qf.empty() ? "-i" : o.qf.c_str();
+    p.qual_on = !o.qual_spec.empty();
+    if (p.qual_on && !p.fastq) {
+        fprintf(stderr, "raxtax-hip: the quality filter (%s) needs FASTQ input: %s does not start with '@'\n", o.qual_spec.c_str(), input);
+        return 64;
+    }
+    if (p.qual_on) id["quality"] = o.qual_spec + ";ascii=" + std::to_string(o.qual.ascii_base);
+    // --reverse: paired input, merged before anything else
+    p.merge_on = !o.rev_file.empty();
+    if (orphan(o.merge_opts, p.merge_on, "sets how pairs are merged and needs --reverse FILE (the reverse mates)")) return 64;
+    if (p.merge_on && !p.fastq) {
+        fprintf(stderr, "raxtax-hip: --reverse needs FASTQ input: %s does not start with '@'\n", input);
+        return 64;
+    }
+    if (p.merge_on) {
+        o.merge.ascii_base = o.qual.ascii_base;
+        id["merge"] = "reverse=" + o.rev_file + ";minovlen=" + std::to_string(o.merge.min_overlap) + ";maxdiffs=" + std::to_string(o.merge.max_diffs) + ";maxdiffpct=" +
+                      std::to_string(o.merge.max_diff_pct) + ";qcap=" + std::to_string(o.merge.q_cap) + ";ascii=" + std::to_string(o.merge.ascii_base);
+    }
+    if (orphan(o.chim_opts, o.chim_on, "sets how reads are checked for chimeras and needs --chimera")) return 64;
+    if (o.chim_on && o.both_strands) {
+        fprintf(stderr, "raxtax-hip: --chimera checks a read in the orientation given and cannot go with --strand both\n");
+        return 64;
+    }
+    if (o.chim_on) id["chimera"] = "segments=" + std::to_string(o.chim.segments) + ";mindelta=" + std::to_string(o.chim.mindelta);
+    if (const int rc = primer_patterns(o, p)) return rc;
+    p.tags_on = !o.tags_file.empty();
+    if (orphan(o.tag_opts, p.tags_on, "sets how reads are assigned to samples and needs --tags SHEET")) return 64;
+    if (p.tags_on && o.derep && o.profile_cutoff) {
+        fprintf(stderr, "raxtax-hip: --tags cannot go with --derep and --profile together: copies from different samples would be counted as one read\n");
+        return 64;
+    }
+    if (p.tags_on)
+        if (const int rc = read_sample_sheet(o, p)) return rc;
+    p.screen_on = !o.contam_file.empty();
+    if (orphan(o.contam_opts, p.screen_on, "sets how reads are screened and needs --contaminants FILE")) return 64;
+    if (p.screen_on)
+        if (const int rc = build_contaminant_set(o, p)) return rc;
+    if (orphan(o.uniques_opts, o.uniques, "sets how the distinct reads are kept and written and needs --uniques")) return 64;
+    if (orphan(o.otus_opts.empty() ? "" : "--otus-minsize", o.otus, "sets what is written of the OTUs and needs --otus")) return 64;  // (named once, however often it was given)
+    if (orphan(o.otus ? "--otus" : "", o.uniques, "clusters the distinct reads of the run and needs --uniques")) return 64;
+    if (o.uniques) id["uniques"] = "minsize=" + std::to_string(o.uniques_minsize) + " max_entries=" + std::to_string(o.uniques_max_entries) + " max_bytes=" + std::to_string(o.uniques_max_bytes);
+    if (o.otus) id["otus"] = "minsize=" + std::to_string(o.otus_minsize);
+    const char *const on_host = o.derep ? "--derep" : (o.both_strands ? "--strand both" : nullptr);
+    if (o.device_format && on_host) {
+        fprintf(stderr, "[INFO ] %s: the result lines are formatted on the host (--device-format has no effect)\n", on_host);
+        o.device_format = false;
+    }
+    return 0;
+}
+
+// ---- the per-read reports
+
+// What the callbacks of a run write to, and what they need to know
+struct Sink {
+    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera, demux, screen;
+    bool want_tsv = false, want_strand = false, want_hits = false, want_qc = false;
+    uint32_t screen_len = 0;                                 // the length of the range the screen was given, of the query whose callbacks are running
+    const std::vector<std::string> *contam_names = nullptr;  // --contaminants: the records of the file (raxtax.screen)
+    const std::vector<std::string> *sample_names = nullptr;  // --tags: the samples of the sheet (raxtax.demux)
+    const rtx_tree *tree = nullptr;                          // the lineages of references (raxtax.hits, raxtax.chimera)
+};
+
+// A report of an option group: one line per read, in input order, written while the run classifies.  A rerun that resumes purges the lines of
+// unfinished queries and goes on behind the rest; a run that starts over removes the file of a group that is off -- it would describe other lines
+// (raxtax.out, raxtax.tsv and raxtax.ckp stand beside the table: they have no group, and a raxtax.tsv that is off is left alone)
+struct Report { const char *name; bool on; const char *header; std::ofstream *stream; };
+
+std::vector<Report> report_table(const Options &o, const Plan &p, Sink &s) {
+    s.want_tsv = o.tsv;
+    s.want_strand = o.both_strands;
+    s.want_hits = o.want_hits;
+    s.want_qc = p.qual_on;
+    s.sample_names = &p.sample_names;
+    s.contam_names = &p.contam_names;
+    return {{"raxtax.strand", o.both_strands, nullptr, &s.strand},
+            {"raxtax.hits", o.want_hits, nullptr, &s.hits},
+            {"raxtax.trim", !p.primers.empty(), "label\tlength\tstart\tend\tprimer5\terrors5\tprimer3\terrors3\n", &s.trim},
+            {"raxtax.demux", p.tags_on, "label\tsample\tverdict\ttag5\tmm5\toff5\ttag3\tmm3\toff3\tlo\thi\n", &s.demux},
+            {"raxtax.qc", p.qual_on, "label\tlength\tstart\tend\texpected_errors\tverdict\n", &s.qc},
+            {"raxtax.merge", p.merge_on, "label\tforward_length\treverse_length\toverlap\tdiffs\tmerged_length\tverdict\n", &s.merge},
+            {"raxtax.chimera", o.chim_on, "label\tstatus\twindows\tsingle\tparent_id\tseg\tpos\tleft\ta_id\tright\tb_id\tdelta\tchimera\tparent\ta\tb\n", &s.chimera},
+            {"raxtax.screen", p.screen_on, "label\tlength\twindows\thits\tfirst\tsource\tverdict\n", &s.screen}};
+}
+
+// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus): a run that starts over removes them
+const char *const kEndOfRunFiles[] = {"raxtax.profile", "raxtax.samples", "raxtax.uniques", "raxtax.uniques.tsv", "raxtax.otus", "raxtax.otus.map", "raxtax.otus.tsv"};
 
 // check_incomplete_output (io.rs:156-187): keep only the lines whose first field is a finished query
 void purge_incomplete(const std::string &path, const std::set<std::string> &done, bool keep_header = false) {
@@ -219,928 +736,477 @@ void purge_incomplete(const std::string &path, const std::set<std::string> &done
     rename(tmp.c_str(), path.c_str());
 }
 
-// parser.rs:11-34 for an oligo on the command line; 0 where the character is no IUPAC code
-uint8_t iupac_code(char ch) {
-    switch (toupper((unsigned char)ch)) {
-        case 'A': return 1; case 'C': return 2; case 'G': return 4; case 'T': return 8;
-        case 'W': return 9; case 'S': return 6; case 'M': return 3; case 'K': return 12; case 'R': return 5; case 'Y': return 10;
-        case 'B': return 14; case 'D': return 13; case 'H': return 11; case 'V': return 7; case 'N': return 15;
-        default: return 0;
-    }
+// The writer of main.rs:127-135: result lines, then the label into the progress file
+int sender(void *c, const char *label, const char *lines, const char *tsv_lines) {
+    Sink *s = static_cast<Sink *>(c);
+    if (s->want_tsv && tsv_lines) s->tsv << tsv_lines << '\n';
+    s->out << lines << '\n';
+    s->ckp << label << '\n';
+    return s->out.good() && s->ckp.good() ? 0 : 1;
 }
 
-struct Sink {
-    std::ofstream out, tsv, ckp, strand, hits, trim, qc, merge, chimera, demux, screen;
-    bool want_qc = false;                                    // the quality filter is on (raxtax.qc); its callback also serves --contaminants:
-    uint32_t screen_len = 0;                                 // the length of the range the screen was given, of the query whose callbacks are running
-    const std::vector<std::string> *contam_names = nullptr;  // --contaminants: the records of the file (raxtax.screen)
-    const std::vector<std::string> *sample_names = nullptr;  // --tags: the samples of the sheet (raxtax.demux)
-    bool want_tsv = false, want_strand = false, want_hits = false;
-    const rtx_tree *tree = nullptr;  // the lineage of the nearest reference (raxtax.hits)
-};
+// ... and in front of them, under --strand both, which orientation the lines are of (raxtax.strand), and, under --hits, which reference they look
+// like: peak, t, ties, id and lineage of the nearest reference ('-' twice where no reference shares a k-mer) -- the line of raxtax.hits without its end
+void strand_and_nearest(Sink *s, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties) {
+    if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
+    if (!s->want_hits) return;
+    s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
+    if (nearest == RTX_NO_REF) s->hits << "-\t-";
+    else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest);
+}
 
-}  // namespace
+int info(void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) {  // (in the shape of --identity's callback)
+    Sink *s = static_cast<Sink *>(c);
+    strand_and_nearest(s, label, strand, peak, t, nearest, ties);
+    if (s->want_hits) s->hits << '\n';
+    return (!s->want_strand || s->strand.good()) && (!s->want_hits || s->hits.good()) ? 0 : 1;
+}
 
-int main(int argc, char **argv) {
-    std::string db, qf, prefix = "raxtax";
-    bool skip_exact = false, raw = false, tsv = false, only_db = false, skip_db = false, clean = false, redo = false;
-    bool timing = false;
-    using clk = std::chrono::steady_clock;
-    auto t_prev = clk::now();
-    std::ostringstream t_log;
-    auto lap = [&](const char *what) {  // --timing: seconds per stage on stderr
-        const auto now = clk::now();
-        t_log << (t_log.tellp() > 0 ? ", " : "") << '"' << what << "\": " << std::chrono::duration<double>(now - t_prev).count();
-        t_prev = now;
-    };
-    std::vector<int> devices{0};
-    bool device_format = false;
-    bool both_strands = false;  // --strand both: RTX_OPT_STRAND on every handle
-    bool want_hits = false;     // --hits: RTX_OPT_NEAREST on every handle, PREFIX/raxtax.hits
-    bool want_identity = false; // --identity: RTX_OPT_IDENTITY on every handle, dist and identity at the end of every line of raxtax.hits (implies --hits)
-    bool derep = false;         // --derep: RTX_OPT_DEREP on every handle (each distinct read of a chunk is classified once; the files are the same)
-    std::vector<std::pair<std::string, std::string>> primer_pairs;  // --primers FWD:REV (once or twice): rtx_index_set_primers on every handle, PREFIX/raxtax.trim
-    uint32_t primer_pct = 10, primer_window = 0;                   // --primer-errors PCT, --primer-window N
-    rtx_qual_params qual{33u, 0u, -1, -1.0, 0u, 0u, -1, -1.0, -1.0};  // --fastq-ascii and the filter options: rtx_index_set_quality on every handle, PREFIX/raxtax.qc
-    std::string qual_spec;                                             // the filter options as given (empty: none) -- part of the checkpoint
-    std::string rev_file;                                              // --reverse FILE: the reverse mates of the pairs of -i, merged on the device (rtx_merge_queries), PREFIX/raxtax.merge
-    rtx_merge_params merge{33u, 16u, 10u, 100u, 41u};                  // --merge-minovlen, --merge-maxdiffs, --merge-maxdiffpct, --merge-qcap (ascii_base: --fastq-ascii)
-    std::string merge_opts;                                            // the merge options as given (empty: none)
-    bool chim_on = false;                                              // --chimera: rtx_index_set_chimera on every handle, PREFIX/raxtax.chimera
-    rtx_chimera_params chim{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA};  // --chimera-segments, --chimera-mindelta
-    std::string chim_opts;                                             // those two as given (empty: none)
-    std::string contam_file;                                           // --contaminants FILE: rtx_index_set_screen on every handle, PREFIX/raxtax.screen
-    rtx_screen_params contam{2u, 50u};                                 // --contam-minhits N, --contam-minpct P
-    std::string contam_opts;                                           // those two as given (empty: none)
-    std::string tags_file;                                             // --tags SHEET: rtx_index_set_tags on every handle, PREFIX/raxtax.demux (and raxtax.samples with --profile)
-    rtx_demux_params tag_params{0u, 0u};                               // --tag-mismatches N, --tag-offset N
-    bool tags_both = false;                                            // --tags-both-orientations
-    std::string tag_opts;                                              // those three as given (empty: none)
-    bool uniques = false;         // --uniques: a tally (rtx_tally.hip) on every handle, PREFIX/raxtax.uniques (and raxtax.uniques.tsv with --tags)
-    uint64_t uniques_minsize = 1, uniques_max_entries = 0, uniques_max_bytes = 0;  // --uniques-minsize N, --uniques-max-entries N, --uniques-max-bytes N (0: the library's defaults)
-    std::string uniques_opts;     // those three as given (empty: none)
-    bool otus = false;            // --otus: the table of --uniques clustered into OTUs (rtx_otu.hip), PREFIX/raxtax.otus, raxtax.otus.map (and raxtax.otus.tsv with --tags)
-    uint64_t otus_minsize = 1;    // --otus-minsize N
-    bool otus_minsize_given = false;
-    uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
-    size_t chunk = 0;  // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (below)
-    size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
-    for (int i = 1; i < argc; i++) {
-        std::string a = argv[i];
-        auto val = [&]() -> const char * { return i + 1 < argc ? argv[++i] : ""; };
-        if (a == "-d" || a == "--database-path") db = val();
-        else if (a == "-i" || a == "--query-file") qf = val();
-        else if (a == "-o" || a == "--prefix") prefix = val();
-        else if (a == "--skip-exact-matches") skip_exact = true;
-        else if (a == "--raw-confidence") raw = true;
-        else if (a == "--tsv") tsv = true;
-        else if (a == "--only-db") only_db = true;
-        else if (a == "--skip-db") skip_db = true;
-        else if (a == "-c" || a == "--clean") clean = true;
-        else if (a == "--redo") redo = true;
-        else if (a == "--timing") timing = true;
-        else if (a == "--device-format") device_format = true;  // RTX_OPT_DEVICE_TEXT on every handle: the lines are formatted on the GPU
-        // CPU tuning flags of the reference (io.rs:139-153): accepted so that existing command lines keep working,
-        // without effect on the device path.  -t takes a value; clap also accepts -tN, --threads=N, -vv, -qq.
-        else if (a == "-t" || a == "--threads") (void)val();
-        else if (a.rfind("--threads=", 0) == 0 || (a.size() > 2 && a[0] == '-' && a[1] == 't' && isdigit((unsigned char)a[2]))) {}
-        else if (a == "--pin") {}
-        else if (a == "--verbose" || a == "--quiet" || (a.size() >= 2 && a[0] == '-' && a[1] != '-' &&
-                                                        a.find_first_not_of(a[1] == 'v' ? "v" : "q", 1) == std::string::npos &&
-                                                        (a[1] == 'v' || a[1] == 'q'))) {}
-        else if (a == "--device") devices.assign(1, atoi(val()));
-        else if (a == "--gpus") {  // devices 0 .. N-1
-            const int n = atoi(val());
-            devices.clear();
-            for (int d = 0; d < n; d++) devices.push_back(d);
-        } else if (a == "--devices") {  // an explicit list; a device may be named twice (two handles on one GPU)
-            devices.clear();
-            std::stringstream ss(val());
-            std::string tok;
-            while (std::getline(ss, tok, ',')) if (!tok.empty()) devices.push_back(atoi(tok.c_str()));
-        }
-        else if (a == "--strand") {
-            const std::string v = val();
-            if (v != "plus" && v != "both") { fprintf(stderr, "raxtax-hip: --strand takes plus or both\n"); return 64; }
-            both_strands = v == "both";
-        }
-        else if (a == "--hits") want_hits = true;
-        else if (a == "--identity") want_identity = want_hits = true;
-        else if (a == "--derep") derep = true;
-        else if (a == "--primers") {
-            const std::string v = val();
-            const size_t colon = v.find(':');
-            if (colon == std::string::npos || v.find(':', colon + 1) != std::string::npos || v.size() < 2) {
-                fprintf(stderr, "raxtax-hip: --primers takes FWD:REV (either side may be empty), not '%s'\n", v.c_str());
-                return 64;
-            }
-            primer_pairs.emplace_back(v.substr(0, colon), v.substr(colon + 1));
-        }
-        else if (a == "--primer-errors") {
-            const int x = atoi(val());
-            if (x < 0 || x > 99) { fprintf(stderr, "raxtax-hip: --primer-errors takes a percentage, 0 .. 99\n"); return 64; }
-            primer_pct = (uint32_t)x;
-        }
-        else if (a == "--primer-window") {
-            const int x = atoi(val());
-            if (x < 1 || x > RTX_TRIM_MAX_WINDOW) { fprintf(stderr, "raxtax-hip: --primer-window takes 1 .. %d bases\n", RTX_TRIM_MAX_WINDOW); return 64; }
-            primer_window = (uint32_t)x;
-        }
-        else if (a == "--fastq-ascii") {
-            const std::string v = val();
-            if (v != "33" && v != "64") { fprintf(stderr, "raxtax-hip: --fastq-ascii takes 33 or 64, not '%s'\n", v.c_str()); return 64; }
-            qual.ascii_base = (uint32_t)atoi(v.c_str());
-        }
-        else if (a == "--trunclen" || a == "--minlen" || a == "--maxlen" || a == "--maxns" || a == "--truncq") {
-            char *end = nullptr;
-            const char *v = val();
-            const long x = strtol(v, &end, 10);
-            const long least = a == "--maxns" || a == "--truncq" ? 0 : 1, most = a == "--truncq" ? 93 : (long)RTX_QUAL_MAX_READ;
-            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
-            if (a == "--trunclen") qual.trunc_len = (uint32_t)x;
-            else if (a == "--minlen") qual.min_len = (uint32_t)x;
-            else if (a == "--maxlen") qual.max_len = (uint32_t)x;
-            else if (a == "--maxns") qual.max_ns = (int32_t)x;
-            else qual.trunc_qual = (int32_t)x;
-            qual_spec += (qual_spec.empty() ? "" : ";") + a.substr(2) + "=" + v;
-        }
-        else if (a == "--truncee" || a == "--maxee" || a == "--maxee-rate") {
-            char *end = nullptr;
-            const char *v = val();
-            const double x = strtod(v, &end);
-            if (end == v || *end != 0 || !(x >= 0.0)) { fprintf(stderr, "raxtax-hip: %s takes a number that is not negative, not '%s'\n", a.c_str(), v); return 64; }
-            (a == "--truncee" ? qual.trunc_ee : a == "--maxee" ? qual.max_ee : qual.max_ee_rate) = x;
-            qual_spec += (qual_spec.empty() ? "" : ";") + a.substr(2) + "=" + v;
-        }
-        else if (a == "-r" || a == "--reverse") rev_file = val();
-        else if (a == "--merge-minovlen" || a == "--merge-maxdiffs" || a == "--merge-maxdiffpct" || a == "--merge-qcap") {
-            const char *v = val();
-            char *end = nullptr;
-            const long x = strtol(v, &end, 10);
-            const long least = a == "--merge-minovlen" ? 1 : 0, most = a == "--merge-maxdiffpct" ? 100 : (a == "--merge-qcap" ? 93 : (long)RTX_MERGE_MAX_READ);
-            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
-            (a == "--merge-minovlen" ? merge.min_overlap : a == "--merge-maxdiffs" ? merge.max_diffs : a == "--merge-maxdiffpct" ? merge.max_diff_pct : merge.q_cap) = (uint32_t)x;
-            merge_opts += (merge_opts.empty() ? "" : " ") + a;
-        }
-        else if (a == "--chimera") chim_on = true;
-        else if (a == "--chimera-mindelta" || a == "--chimera-segments") {
-            const char *v = val();
-            char *end = nullptr;
-            const long x = strtol(v, &end, 10);
-            const long least = a == "--chimera-segments" ? 2 : 0, most = a == "--chimera-segments" ? (long)RTX_CHIMERA_MAX_SEGMENTS : (long)RTX_CHIMERA_MAX_QUERY;
-            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
-            (a == "--chimera-segments" ? chim.segments : chim.mindelta) = (uint32_t)x;
-            chim_opts += (chim_opts.empty() ? "" : " ") + a;
-        }
-        else if (a == "--contaminants") contam_file = val();
-        else if (a == "--contam-minhits" || a == "--contam-minpct") {
-            const char *v = val();
-            char *end = nullptr;
-            const long x = strtol(v, &end, 10);
-            const long least = a == "--contam-minhits" ? 1 : 0, most = a == "--contam-minhits" ? 0x7FFFFFFFl : 100;
-            if (end == v || *end != 0 || x < least || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, %ld .. %ld, not '%s'\n", a.c_str(), least, most, v); return 64; }
-            (a == "--contam-minhits" ? contam.min_hits : contam.min_pct) = (uint32_t)x;
-            contam_opts += (contam_opts.empty() ? "" : " ") + a;
-        }
-        else if (a == "--tags") tags_file = val();
-        else if (a == "--tags-both-orientations") { tags_both = true; tag_opts += (tag_opts.empty() ? "" : " ") + a; }
-        else if (a == "--tag-mismatches" || a == "--tag-offset") {
-            const char *v = val();
-            char *end = nullptr;
-            const long x = strtol(v, &end, 10);
-            const long most = a == "--tag-mismatches" ? (long)RTX_DEMUX_MAX_MISMATCHES : (long)RTX_DEMUX_MAX_OFFSET;
-            if (end == v || *end != 0 || x < 0 || x > most) { fprintf(stderr, "raxtax-hip: %s takes a whole number, 0 .. %ld, not '%s'\n", a.c_str(), most, v); return 64; }
-            (a == "--tag-mismatches" ? tag_params.max_mismatches : tag_params.max_offset) = (uint32_t)x;
-            tag_opts += (tag_opts.empty() ? "" : " ") + a;
-        }
-        else if (a == "--profile") {
-            char *end = nullptr;
-            const char *v = val();
-            const double x = strtod(v, &end);
-            const long c = end != v && *end == '\0' && x > 0.0 && x <= 1.0 ? lround(x * 100.0) : 0;
-            if (c < 1 || c > 100) { fprintf(stderr, "raxtax-hip: --profile takes a confidence cutoff in (0, 1], such as 0.8\n"); return 64; }
-            profile_cutoff = (uint32_t)c;
-        }
-        else if (a == "--uniques") uniques = true;
-        else if (a == "--uniques-minsize" || a == "--uniques-max-entries" || a == "--uniques-max-bytes") {
-            char *end = nullptr;
-            const char *v = val();
-            const long long x = strtoll(v, &end, 10);
-            if (end == v || *end != '\0' || x < 1 || (a == "--uniques-max-entries" && x > 0x7FFFFFFELL)) { fprintf(stderr, "raxtax-hip: %s takes a positive integer\n", a.c_str()); return 64; }
-            (a == "--uniques-minsize" ? uniques_minsize : a == "--uniques-max-entries" ? uniques_max_entries : uniques_max_bytes) = (uint64_t)x;
-            uniques_opts += (uniques_opts.empty() ? "" : " ") + a;
-        }
-        else if (a == "--otus") otus = true;
-        else if (a == "--otus-minsize") {
-            char *end = nullptr;
-            const char *v = val();
-            const long long x = strtoll(v, &end, 10);
-            if (end == v || *end != '\0' || x < 1) { fprintf(stderr, "raxtax-hip: --otus-minsize takes a positive integer\n"); return 64; }
-            otus_minsize = (uint64_t)x;
-            otus_minsize_given = true;
-        }
-        else if (a == "--batch") chunk = (size_t)atoll(val());
-        else if (a == "--block-bytes") block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
-        else {
-            fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N]]]\n"
-                            "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
-            return 64;
-        }
+// ... and, under --identity (which implies --hits), how far the query is from it: the edit distance and the identity in percent behind the line of --hits
+int align(void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t dist, uint32_t qlen) {
+    Sink *s = static_cast<Sink *>(c);
+    strand_and_nearest(s, label, strand, peak, t, nearest, ties);
+    if (dist == RTX_NO_DIST || qlen == 0u) {
+        s->hits << "\t-\t-\n";
+    } else {
+        const uint64_t h = ((uint64_t)(qlen - dist) * 10000u + qlen / 2u) / qlen;  // hundredths of a percent
+        char pct[32];
+        snprintf(pct, sizeof pct, "%llu.%02llu", (ull)(h / 100u), (ull)(h % 100u));
+        s->hits << '\t' << dist << '\t' << pct << '\n';
     }
-    if (devices.empty()) { fprintf(stderr, "raxtax-hip: --gpus / --devices need at least one device\n"); return 64; }
-    if (db.empty() || (qf.empty() && !only_db) || (only_db && skip_db)) {
-        fprintf(stderr, "raxtax-hip: -d is required, -i unless --only-db; --only-db conflicts with --skip-db\n");
-        return 64;
-    }
-    // FASTQ or FASTA: the first non-blank byte of the query file.  A filter option needs quality strings: refused here, before the database is read
-    bool fastq = false;
-    if (!qf.empty()) {
-        Input f;
-        if (f.open(qf)) {
-            char c = 0;
-            while (f.read(&c, 1) == 1 && isspace((unsigned char)c)) c = 0;
-            fastq = c == '@';
-            f.close();
-        }
-    }
-    const bool qual_on = !qual_spec.empty();
-    if (qual_on && !fastq) {
-        fprintf(stderr, "raxtax-hip: the quality filter (%s) needs FASTQ input: %s does not start with '@'\n", qual_spec.c_str(), qf.empty() ? "-i" : qf.c_str());
-        return 64;
-    }
-    if (qual_on) qual_spec += ";ascii=" + std::to_string(qual.ascii_base);
-    // --reverse: paired input, merged before anything else.  Refused here as well -- before the database is read -- where it cannot work
-    const bool merge_on = !rev_file.empty();
-    if (!merge_opts.empty() && !merge_on) {
-        fprintf(stderr, "raxtax-hip: %s sets how pairs are merged and needs --reverse FILE (the reverse mates)\n", merge_opts.c_str());
-        return 64;
-    }
-    if (merge_on && !fastq) {
-        fprintf(stderr, "raxtax-hip: --reverse needs FASTQ input: %s does not start with '@'\n", qf.empty() ? "-i" : qf.c_str());
-        return 64;
-    }
-    // --chimera: refused here as well where it cannot work
-    if (!chim_opts.empty() && !chim_on) {
-        fprintf(stderr, "raxtax-hip: %s sets how reads are checked for chimeras and needs --chimera\n", chim_opts.c_str());
-        return 64;
-    }
-    if (chim_on && both_strands) {
-        fprintf(stderr, "raxtax-hip: --chimera checks a read in the orientation given and cannot go with --strand both\n");
-        return 64;
-    }
-    const std::string chim_spec = chim_on ? "segments=" + std::to_string(chim.segments) + ";mindelta=" + std::to_string(chim.mindelta) : std::string();
-    std::string merge_spec;
-    if (merge_on) {
-        merge.ascii_base = qual.ascii_base;
-        merge_spec = "reverse=" + rev_file + ";minovlen=" + std::to_string(merge.min_overlap) + ";maxdiffs=" + std::to_string(merge.max_diffs) + ";maxdiffpct=" +
-                     std::to_string(merge.max_diff_pct) + ";qcap=" + std::to_string(merge.q_cap) + ";ascii=" + std::to_string(merge.ascii_base);
-    }
-    // --primers: the pattern list, checked here -- before the database is read and any device is touched
-    struct Primer { std::string name; std::vector<uint8_t> codes; uint32_t end; };
-    std::vector<Primer> primers;
-    std::string primer_spec;
-    for (const auto &pr : primer_pairs) {
-        std::vector<uint8_t> fwd, rev;
-        for (int side = 0; side < 2; side++) {
-            const std::string &oligo = side ? pr.second : pr.first;
-            for (char ch : oligo) {
-                const uint8_t c = iupac_code(ch);
-                if (!c) { fprintf(stderr, "raxtax-hip: --primers: '%c' in primer %s is no IUPAC code\n", ch, oligo.c_str()); return 64; }
-                (side ? rev : fwd).push_back(c);
-            }
-            if (oligo.size() > RTX_TRIM_MAX_PATTERN) { fprintf(stderr, "raxtax-hip: --primers: primer %s has %zu bases (at most %d)\n", oligo.c_str(), oligo.size(), RTX_TRIM_MAX_PATTERN); return 64; }
-        }
-        auto rc_of = [](const std::vector<uint8_t> &x) { std::vector<uint8_t> y(x.size() + 1); (void)rtx_revcomp(x.data(), x.size(), y.data()); y.resize(x.size()); return y; };
-        auto add = [&](const std::string &name, const std::vector<uint8_t> &codes, uint32_t end) {
-            if (!codes.empty()) primers.push_back({name, codes, end});
-        };
-        add(pr.first, fwd, RTX_TRIM_5P);
-        add("revcomp(" + pr.second + ")", rc_of(rev), RTX_TRIM_3P);
-        if (both_strands) {
-            add(pr.second, rev, RTX_TRIM_5P);
-            add("revcomp(" + pr.first + ")", rc_of(fwd), RTX_TRIM_3P);
-        }
-        if (primers.size() > RTX_TRIM_MAX_PATTERNS) {
-            fprintf(stderr, "raxtax-hip: --primers: %s:%s makes %zu patterns (at most %d%s)\n", pr.first.c_str(), pr.second.c_str(), primers.size(), RTX_TRIM_MAX_PATTERNS,
-                    both_strands ? "; --strand both registers every oligo at both ends" : "");
-            return 64;
-        }
-        primer_spec += (primer_spec.empty() ? "" : ",") + pr.first + ":" + pr.second;
-    }
-    if (!primer_spec.empty()) primer_spec += ";errors=" + std::to_string(primer_pct) + ";window=" + std::to_string(primer_window);
-    // --tags: the sample sheet, read and checked here as well
-    struct Tag { std::string name; std::vector<uint8_t> codes; uint32_t end; };
-    std::vector<Tag> tags;
-    std::vector<rtx_demux_pair> tag_pairs;
-    std::vector<std::string> sample_names;
-    std::string tag_spec;
-    const bool tags_on = !tags_file.empty();
-    if (!tag_opts.empty() && !tags_on) { fprintf(stderr, "raxtax-hip: %s sets how reads are assigned to samples and needs --tags SHEET\n", tag_opts.c_str()); return 64; }
-    if (tags_on) {
-        if (derep && profile_cutoff) {
-            fprintf(stderr, "raxtax-hip: --tags cannot go with --derep and --profile together: copies from different samples would be counted as one read\n");
-            return 64;
-        }
-        std::string sheet;
-        if (!slurp(tags_file, sheet)) { fprintf(stderr, "raxtax-hip: --tags: cannot read %s\n", tags_file.c_str()); return 66; }
-        auto rc_of = [](const std::vector<uint8_t> &x) { std::vector<uint8_t> y(x.size() + 1); (void)rtx_revcomp(x.data(), x.size(), y.data()); y.resize(x.size()); return y; };
-        auto strip = [](std::string s) {
-            while (!s.empty() && isspace((unsigned char)s.back())) s.pop_back();
-            size_t a = 0;
-            while (a < s.size() && isspace((unsigned char)s[a])) a++;
-            return s.substr(a);
-        };
-        auto tag_of = [&](const std::string &name, const std::vector<uint8_t> &codes, uint32_t end) -> uint32_t {  // a tag that several lines share is listed once
-            for (size_t k = 0; k < tags.size(); k++)
-                if (tags[k].end == end && tags[k].codes == codes) return (uint32_t)k;
-            tags.push_back({name, codes, end});
-            return (uint32_t)tags.size() - 1u;
-        };
-        std::istringstream lines(sheet);
-        std::string line;
-        for (unsigned line_no = 1; std::getline(lines, line); line_no++) {
-            line = line.substr(0, line.find('#'));
-            if (strip(line).empty()) continue;
-            std::vector<std::string> f;
-            for (size_t a = 0;;) {
-                const size_t t = line.find('\t', a);
-                f.push_back(strip(line.substr(a, t == std::string::npos ? std::string::npos : t - a)));
-                if (t == std::string::npos) break;
-                a = t + 1;
-            }
-            if (f.size() < 2 || f.size() > 3 || f[0].empty() || f[1].empty()) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: expected sample<TAB>fwd_tag<TAB>rev_tag\n", tags_file.c_str(), line_no); return 64; }
-            std::vector<uint8_t> fwd, rev;
-            const bool single = f.size() == 2 || f[2].empty() || f[2] == "-";
-            for (int side = 0; side < (single ? 1 : 2); side++)
-                for (char ch : f[1 + side]) {
-                    const uint8_t c = iupac_code(ch);
-                    if (!c) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: '%c' is no IUPAC code\n", tags_file.c_str(), line_no, ch); return 64; }
-                    (side ? rev : fwd).push_back(c);
-                }
-            size_t s = 0;
-            while (s < sample_names.size() && sample_names[s] != f[0]) s++;
-            if (s == sample_names.size()) sample_names.push_back(f[0]);
-            tag_pairs.push_back({tag_of(f[1], fwd, RTX_TRIM_5P), single ? RTX_DEMUX_NO_TAG : tag_of("revcomp(" + f[2] + ")", rc_of(rev), RTX_TRIM_3P), (uint32_t)s});
-            if (tags_both) {
-                if (single) { fprintf(stderr, "raxtax-hip: --tags: %s line %u: --tags-both-orientations needs a rev_tag\n", tags_file.c_str(), line_no); return 64; }
-                tag_pairs.push_back({tag_of(f[2], rev, RTX_TRIM_5P), tag_of("revcomp(" + f[1] + ")", rc_of(fwd), RTX_TRIM_3P), (uint32_t)s});
-            }
-        }
-        std::vector<rtx_demux_tag> ct;
-        for (const Tag &t : tags) ct.push_back({t.codes.data(), (uint32_t)t.codes.size(), t.end});
-        uint32_t x[5];  // the checks of the library on the list (rtx_demux_create makes them again): one read through the host function
-        if (rtx_demux_read(&tag_params, ct.data(), (uint32_t)ct.size(), tag_pairs.data(), (uint32_t)tag_pairs.size(), nullptr, 0, &x[0], &x[1], &x[2], &x[3], &x[4]) != RTX_OK) {
-            fprintf(stderr, "raxtax-hip: --tags: %s: %s\n", tags_file.c_str(), rtx_last_error());
-            return 64;
-        }
-        tag_spec = fingerprint(tags_file) + ";mismatches=" + std::to_string(tag_params.max_mismatches) + ";offset=" + std::to_string(tag_params.max_offset) + ";both=" + (tags_both ? "1" : "0");
-    }
-    // --contaminants: the set, built here as well -- before the database is read and any device is touched
-    const bool screen_on = !contam_file.empty();
-    if (!contam_opts.empty() && !screen_on) { fprintf(stderr, "raxtax-hip: %s sets how reads are screened and needs --contaminants FILE\n", contam_opts.c_str()); return 64; }
-    rtx_screen_set *contam_set = nullptr;
-    std::vector<std::string> contam_names;
-    std::string contam_spec;
-    if (screen_on) {
-        std::string text;
-        if (!slurp(contam_file, text)) { fprintf(stderr, "raxtax-hip: --contaminants: cannot read %s\n", contam_file.c_str()); return 66; }
-        rtx_queries *cq = nullptr;  // (the query parser: the labels need no lineage)
-        if (rtx_queries_parse_fasta(text.data(), text.size(), nullptr, 0, &cq) != RTX_OK) { fprintf(stderr, "raxtax-hip: --contaminants: %s: %s\n", contam_file.c_str(), rtx_last_error()); return 66; }
-        const uint8_t *cb = nullptr;
-        const uint64_t *co = nullptr;
-        rtx_queries_data(cq, &cb, &co);
-        const uint64_t nc = rtx_queries_len(cq);
-        for (uint64_t i = 0; i < nc; i++) {
-            const std::string label = rtx_queries_label(cq, i);
-            contam_names.push_back(label.substr(0, label.find_first_of(" \t")));
-        }
-        uint64_t keys = 0, slots = 0, fp = 0;
-        const int brc = rtx_screen_set_build(nc, cb, co, &contam_set);
-        rtx_queries_destroy(cq);
-        if (brc != RTX_OK || rtx_screen_set_info(contam_set, &keys, &slots, nullptr, nullptr, &fp) != RTX_OK) {
-            fprintf(stderr, "raxtax-hip: --contaminants: %s: %s\n", contam_file.c_str(), rtx_last_error());
-            return 64;
-        }
-        char hex[24];
-        snprintf(hex, sizeof hex, "%016llx", (unsigned long long)fp);
-        contam_spec = "file=" + contam_file + ";minhits=" + std::to_string(contam.min_hits) + ";minpct=" + std::to_string(contam.min_pct) + ";keys=" + hex;
-        fprintf(stderr, "[INFO ] --contaminants: %llu record(s) of %s, %llu distinct 16-mers in %llu slots; a read is a contaminant from %u hit(s) and %u %% of its windows on\n",
-                (unsigned long long)nc, contam_file.c_str(), (unsigned long long)keys, (unsigned long long)slots, contam.min_hits, contam.min_pct);
-    }
-    const std::string demux_path = prefix + "/raxtax.demux", samples_path = prefix + "/raxtax.samples", screen_path = prefix + "/raxtax.screen";
-    const std::string ckp_json = prefix + "/raxtax.json", ckp_path = prefix + "/raxtax.ckp", trim_path = prefix + "/raxtax.trim", qc_path = prefix + "/raxtax.qc", merge_path = prefix + "/raxtax.merge", chim_path = prefix + "/raxtax.chimera";
-    const std::string out_path = prefix + "/raxtax.out", tsv_path = prefix + "/raxtax.tsv", strand_path = prefix + "/raxtax.strand", hits_path = prefix + "/raxtax.hits", profile_path = prefix + "/raxtax.profile";
-    const std::string uniques_path = prefix + "/raxtax.uniques", uniques_table_path = prefix + "/raxtax.uniques.tsv";
-    if (!uniques_opts.empty() && !uniques) { fprintf(stderr, "raxtax-hip: %s sets how the distinct reads are kept and written and needs --uniques\n", uniques_opts.c_str()); return 64; }
-    const std::string otus_path = prefix + "/raxtax.otus", otus_map_path = prefix + "/raxtax.otus.map", otus_table_path = prefix + "/raxtax.otus.tsv";
-    if (otus_minsize_given && !otus) { fprintf(stderr, "raxtax-hip: --otus-minsize sets what is written of the OTUs and needs --otus\n"); return 64; }
-    if (otus && !uniques) { fprintf(stderr, "raxtax-hip: --otus clusters the distinct reads of the run and needs --uniques\n"); return 64; }
-    const std::string otus_spec = otus ? "minsize=" + std::to_string(otus_minsize) : std::string();
-    std::string uniques_spec;
-    if (uniques) uniques_spec = "minsize=" + std::to_string(uniques_minsize) + " max_entries=" + std::to_string(uniques_max_entries) + " max_bytes=" + std::to_string(uniques_max_bytes);
-    if (device_format && derep) {
-        fprintf(stderr, "[INFO ] --derep: the result lines are formatted on the host (--device-format has no effect)\n");
-        device_format = false;
-    }
-    if (device_format && both_strands) {
-        fprintf(stderr, "[INFO ] --strand both: the result lines are formatted on the host (--device-format has no effect)\n");
-        device_format = false;
-    }
-    // ---- checkpoint (io.rs:202-263)
-    std::set<std::string> done;
-    const std::string want_ckp = checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec, otus_spec);
-    bool resume = false;
-    if (!redo && is_file(ckp_json)) {
+    return (!s->want_strand || s->strand.good()) && s->hits.good() ? 0 : 1;
+}
+
+// ... and, under --primers, what was cut off every query (also one that has no result lines: an emptied read)
+int trimmed(void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit) {
+    Sink *s = static_cast<Sink *>(c);
+    const uint32_t p5 = hit & 0xFFu, e5 = (hit >> 8) & 0xFFu, p3 = (hit >> 16) & 0xFFu, e3 = hit >> 24;
+    s->trim << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t';
+    if (p5 == RTX_TRIM_NO_PATTERN) s->trim << "-\t-\t";
+    else s->trim << p5 << '\t' << e5 << '\t';
+    if (p3 == RTX_TRIM_NO_PATTERN) s->trim << "-\t-\n";
+    else s->trim << p3 << '\t' << e3 << '\n';
+    return s->trim.good() ? 0 : 1;
+}
+
+// The range of every query that is left behind primers and quality filter, and what the filter made of the query.  It serves two groups: the
+// contaminant screen is given that range, and `screened` below prints its length; with a quality filter the line of raxtax.qc is written (also
+// for a query without result lines: a discarded read).  So it is registered when either is on.
+bool wants_range_and_quality(const Plan &p) { return p.qual_on || p.screen_on; }
+int range_and_quality(void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) {
+    static const char *const names[7] = {"bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate"};
+    Sink *s = static_cast<Sink *>(c);
+    s->screen_len = verdict ? 0u : hi - lo;
+    if (!s->want_qc) return 0;
+    char frac[8];  // six decimals of ee / 2^40, truncated: from the integer, no floating point
+    snprintf(frac, sizeof frac, "%06llu", (ull)(((ee & ((1ull << 40) - 1)) * 1000000ull) >> 40));
+    s->qc << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t' << (ee >> 40) << '.' << frac << '\t';
+    if (!verdict) s->qc << "pass";
+    for (uint32_t b = 0, first = 1; b < 7u; b++)
+        if ((verdict >> b) & 1u) { s->qc << (first ? "" : "+") << names[b]; first = 0; }
+    s->qc << '\n';
+    return s->qc.good() ? 0 : 1;
+}
+
+// ... and, under --chimera, what the check made of every query (also one without result lines: a flagged read)
+int checked(void *c, const char *label, const rtx_chimera_rec *r) {
+    static const char *const status[3] = {"ok", "no_kmer", "too_long"};
+    Sink *s = static_cast<Sink *>(c);
+    auto id = [s](uint32_t ref) { if (ref == RTX_NO_REF) s->chimera << '-'; else s->chimera << ref; };
+    auto lin = [s](uint32_t ref) { if (ref == RTX_NO_REF) s->chimera << '-'; else s->chimera << rtx_tree_lineage(s->tree, ref); };
+    s->chimera << label << '\t' << status[r->status < 3u ? r->status : 0u] << '\t' << r->n_valid << '\t' << r->single << '\t';
+    id(r->parent);
+    s->chimera << '\t' << r->seg << '\t' << r->pos << '\t' << r->left << '\t';
+    id(r->parent_a);
+    s->chimera << '\t' << r->right << '\t';
+    id(r->parent_b);
+    s->chimera << '\t' << r->delta << '\t' << (r->status != RTX_CHIM_OK ? '?' : (r->flag ? 'Y' : 'N')) << '\t';
+    lin(r->parent);
+    s->chimera << '\t';
+    lin(r->parent_a);
+    s->chimera << '\t';
+    lin(r->parent_b);
+    s->chimera << '\n';
+    return s->chimera.good() ? 0 : 1;
+}
+
+// ... and, under --contaminants, what the screen made of every query (also one without result lines: a contaminant)
+int screened(void *c, const char *label, uint32_t windows, uint32_t hits, uint32_t first, uint32_t source, uint32_t verdict) {
+    Sink *s = static_cast<Sink *>(c);
+    s->screen << label << '\t' << s->screen_len << '\t' << windows << '\t' << hits << '\t';
+    if (first == RTX_SCREEN_NONE) s->screen << '-';
+    else s->screen << first;
+    s->screen << '\t';
+    if (source == RTX_SCREEN_NONE || source >= s->contam_names->size()) s->screen << '-';
+    else s->screen << (*s->contam_names)[source];
+    s->screen << '\t' << (verdict ? "contaminant" : "pass") << '\n';
+    return s->screen.good() ? 0 : 1;
+}
+
+// ... and, under --tags, which sample every query belongs to (also one without result lines: a read that is not assigned)
+int assigned(void *c, const char *label, uint32_t, uint32_t sample, uint32_t lo, uint32_t hi, uint32_t hit, uint32_t info) {
+    static const char *const verdicts[5] = {"ok", "no_tag5", "no_tag3", "ambiguous", "unknown_pair"};
+    Sink *s = static_cast<Sink *>(c);
+    const uint32_t t5 = hit & 0xFFFFu, t3 = hit >> 16, v = info & 0xFFu;
+    s->demux << label << '\t';
+    if (sample == RTX_DEMUX_NONE || sample >= s->sample_names->size()) s->demux << '*';
+    else s->demux << (*s->sample_names)[sample];
+    s->demux << '\t' << verdicts[v < 5u ? v : 0u] << '\t';
+    if (t5 == RTX_DEMUX_NO_TAG) s->demux << "-\t-\t-\t";
+    else s->demux << t5 << '\t' << ((info >> 8) & 0xFFu) << '\t' << ((info >> 24) & 0xFu) << '\t';
+    if (t3 == RTX_DEMUX_NO_TAG) s->demux << "-\t-\t-\t";
+    else s->demux << t3 << '\t' << ((info >> 16) & 0xFFu) << '\t' << (info >> 28) << '\t';
+    s->demux << lo << '\t' << hi << '\n';
+    return s->demux.good() ? 0 : 1;
+}
+
+// ---- checkpoint and resume (io.rs:202-263): the labels a matching checkpoint lists as finished, the reports purged of everything else
+int resume_or_start(const Options &o, const Plan &p, const std::vector<Report> &reports, std::set<std::string> &done, bool &resume) {
+    const std::string ckp_json = o.prefix + "/raxtax.json", ckp_path = o.prefix + "/raxtax.ckp";
+    if (!o.redo && is_file(ckp_json)) {
         std::string have;
         slurp(ckp_json, have);
-        if (have == want_ckp) {  // checkpoint_valid (io.rs:288-302)
-            std::ifstream p(ckp_path);
+        if (have == p.identity.json()) {  // checkpoint_valid (io.rs:288-302)
+            std::ifstream f(ckp_path);
             std::string l;
-            while (std::getline(p, l)) done.insert(l);
-            if (profile_cutoff && !done.empty()) {  // the queries of the earlier run are not classified again: their share of the sample is gone
-                fprintf(stderr, "raxtax-hip: --profile cannot resume a checkpoint with processed queries (%zu in %s): the profile would miss them; "
-                                "run with --redo to classify the whole sample again\n", done.size(), ckp_path.c_str());
-                return 64;
-            }
-            if (uniques && !done.empty()) {  // (likewise: the table would miss the reads of the earlier run)
-                fprintf(stderr, "raxtax-hip: --uniques cannot resume a checkpoint with processed queries (%zu in %s): the table would miss them; "
-                                "run with --redo to classify the whole sample again\n", done.size(), ckp_path.c_str());
-                return 64;
-            }
-            purge_incomplete(out_path, done);
-            if (tsv) purge_incomplete(tsv_path, done);
-            if (both_strands) purge_incomplete(strand_path, done);
-            if (want_hits) purge_incomplete(hits_path, done);
-            if (!primers.empty()) purge_incomplete(trim_path, done, true);
-            if (qual_on) purge_incomplete(qc_path, done, true);
-            if (merge_on) purge_incomplete(merge_path, done, true);
-            if (chim_on) purge_incomplete(chim_path, done, true);
-            if (tags_on) purge_incomplete(demux_path, done, true);
-            if (screen_on) purge_incomplete(screen_path, done, true);
+            while (std::getline(f, l)) done.insert(l);
+            // the queries of the earlier run are not classified again: their share of the sample is gone
+            const char *const whole_run[2][2] = {{o.profile_cutoff ? "--profile" : nullptr, "the profile"}, {o.uniques ? "--uniques" : nullptr, "the table"}};
+            for (const auto &w : whole_run)
+                if (w[0] && !done.empty()) {
+                    fprintf(stderr, "raxtax-hip: %s cannot resume a checkpoint with processed queries (%zu in %s): %s would miss them; "
+                                    "run with --redo to classify the whole sample again\n", w[0], done.size(), ckp_path.c_str(), w[1]);
+                    return 64;
+                }
+            purge_incomplete(o.prefix + "/raxtax.out", done);
+            if (o.tsv) purge_incomplete(o.prefix + "/raxtax.tsv", done);
+            for (const Report &r : reports)
+                if (r.on) purge_incomplete(o.prefix + "/" + r.name, done, r.header != nullptr);
             resume = true;
             fprintf(stderr, "[INFO ] Restarting from checkpoint %s\n", ckp_json.c_str());
         }
     }
-    if (is_dir(prefix) && !is_file(ckp_json) && !redo) {
+    if (is_dir(o.prefix) && !is_file(ckp_json) && !o.redo) {
         fprintf(stderr, "[ERROR] Output folder %s already exists! Please specify another folder with -o <PATH> or run with --redo "
-                        "to force overriding existing files!\n", prefix.c_str());
+                        "to force overriding existing files!\n", o.prefix.c_str());
         return 73;  // exitcode::CANTCREAT
     }
-    mkdir(prefix.c_str(), 0777);
+    mkdir(o.prefix.c_str(), 0777);
+    return 0;
+}
 
-    // ---- database: try the binary format first, then FASTA (parser.rs:37-44)
-    rtx_tree *tree = nullptr;
+// ---- database: try the binary format first, then FASTA (parser.rs:37-44); db_bin: where its cache goes, empty for none
+int load_database(const Options &o, bool resume, Laps &laps, rtx_tree *&tree, std::string &db_bin) {
     bool store_db = false;
-    if (rtx_tree_load_bin(db.c_str(), &tree) != RTX_OK) {
+    if (rtx_tree_load_bin(o.db.c_str(), &tree) != RTX_OK) {
         std::string db_text;
         // Tree.k_mer_map is only needed for the .bin cache: the device index is built from the sequences
-        if (!slurp(db, db_text) || rtx_tree_parse_reference_fasta_ex(db_text.data(), db_text.size(), RTX_TREE_SKIP_KMER_MAP, &tree) != RTX_OK) {
-            fprintf(stderr, "[ERROR] Failed to parse %s: %s\n", db.c_str(), rtx_last_error());
+        if (!slurp(o.db, db_text) || rtx_tree_parse_reference_fasta_ex(db_text.data(), db_text.size(), RTX_TREE_SKIP_KMER_MAP, &tree) != RTX_OK) {
+            fprintf(stderr, "[ERROR] Failed to parse %s: %s\n", o.db.c_str(), rtx_last_error());
             return 66;  // exitcode::NOINPUT
         }
         store_db = true;
     }
-    lap("database");
-    std::string db_bin;
-    if (store_db && !skip_db) {  // main.rs:72-86, io.rs:269-286
-        std::string base = db.substr(db.find_last_of('/') == std::string::npos ? 0 : db.find_last_of('/') + 1);
+    laps.lap("database");
+    if (store_db && !o.skip_db) {  // main.rs:72-86, io.rs:269-286
+        std::string base = o.db.substr(o.db.find_last_of('/') == std::string::npos ? 0 : o.db.find_last_of('/') + 1);
         const size_t dot = base.find_last_of('.');
-        db_bin = prefix + "/" + (dot == std::string::npos ? base : base.substr(0, dot)) + ".bin";
-        if (is_file(db_bin) && !redo && !resume) {
+        db_bin = o.prefix + "/" + (dot == std::string::npos ? base : base.substr(0, dot)) + ".bin";
+        if (is_file(db_bin) && !o.redo && !resume) {
             fprintf(stderr, "[ERROR] Output database file %s already exists! Delete it or run with --redo\n", db_bin.c_str());
             return 73;
         }
     }
-    // the database cache is written on a thread of its own while the queries are parsed and classified
-    std::thread bin_writer;
-    int bin_rc = RTX_OK;
-    std::string bin_err;
-    auto start_bin_writer = [&]() {
-        if (db_bin.empty()) return;
-        bin_writer = std::thread([&]() {
-            bin_rc = rtx_tree_save_bin(tree, db_bin.c_str());
-            if (bin_rc != RTX_OK) bin_err = rtx_last_error();
-        });
-    };
-    auto join_bin_writer = [&]() -> bool {
-        if (bin_writer.joinable()) bin_writer.join();
-        if (bin_rc != RTX_OK) { fprintf(stderr, "[ERROR] Failed to write database: %s\n", bin_err.c_str()); return false; }
-        return true;
-    };
-    {
-        const std::string tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
-        std::ofstream f(tmp, std::ios::trunc);
-        f << (resume ? want_ckp : checkpoint_json(fingerprint(db), raw, skip_exact, tsv, both_strands, want_hits, profile_cutoff, want_identity, primer_spec, qual_spec, merge_spec, chim_spec, tag_spec, contam_spec, uniques_spec, otus_spec));
-        f.close();
-        rename(tmp.c_str(), ckp_json.c_str());
-    }
-    if (only_db) {
-        start_bin_writer();
-        const bool ok = join_bin_writer();
-        lap("database_cache");
-        if (timing) fprintf(stderr, "{%s}\n", t_log.str().c_str());
-        return ok ? 0 : 74;
-    }
+    return 0;
+}
 
-    // ---- queries: the file is read and parsed block by block on a thread of its own (cut in front of header lines,
-    // rtx_fasta_block_end; FASTQ: behind whole records, rtx_fastq_block_end), so that ingest overlaps with classification and memory stays bounded for very large
-    // files (the reference reads the whole file, parser.rs:112-115).  Already finished labels are dropped
-    // (parser.rs:150-153).
-    std::vector<const char *> skip;
-    for (const std::string &l : done) skip.push_back(l.c_str());
-    struct Parsed { rtx_queries *qs = nullptr; int rc = RTX_OK; std::string err; bool end = false; double merge_s[3] = {0, 0, 0}; float merge_ms = 0; };
-    std::mutex qmu;
-    std::condition_variable qcv;
+// The database cache is written on a thread of its own while the queries are parsed and classified
+struct BinWriter {
+    std::thread th;
+    int rc = RTX_OK;
+    std::string err;
+    void start(rtx_tree *tree, const std::string &path) {
+        if (path.empty()) return;
+        th = std::thread([this, tree, path]() {
+            rc = rtx_tree_save_bin(tree, path.c_str());
+            if (rc != RTX_OK) err = rtx_last_error();
+        });
+    }
+    bool join() {
+        if (th.joinable()) th.join();
+        if (rc != RTX_OK) fprintf(stderr, "[ERROR] Failed to write database: %s\n", err.c_str());
+        return rc == RTX_OK;
+    }
+};
+
+// ---- queries: the file is read and parsed block by block on a thread of its own (cut in front of header lines,
+// rtx_fasta_block_end; FASTQ: behind whole records, rtx_fastq_block_end), so that ingest overlaps with classification and memory stays bounded for very large
+// files (the reference reads the whole file, parser.rs:112-115).  Already finished labels are dropped
+// (parser.rs:150-153).
+
+struct Parsed { rtx_queries *qs = nullptr; int rc = RTX_OK; std::string err; bool end = false; double merge_s[3] = {0, 0, 0}; float merge_ms = 0; };
+
+// The parsed blocks between the reader's thread and the loop over blocks
+class BlockQueue {
+    std::mutex mu;
+    std::condition_variable cv;
     std::deque<Parsed> ready;  // at most two blocks ahead
-    bool stop_reader = false;
-    std::thread reader([&]() {
-        auto push = [&](Parsed &&pz) {
-            std::unique_lock<std::mutex> g(qmu);
-            qcv.wait(g, [&] { return ready.size() < 2 || stop_reader; });
-            ready.push_back(std::move(pz));
-            qcv.notify_all();
-        };
-        if (merge_on) {
-            // Paired input: both files block by block, cut at the same record (rtx_fastq_block_end_n), parsed, and merged on the first device
-            // of the run; what is queued is the handle of merged reads.  Nothing behind the queue knows.
-            auto fail = [&](int rc, const std::string &msg) { Parsed e; e.rc = rc; e.err = msg; e.end = true; push(std::move(e)); };
-            Input in[2];
-            const std::string *name[2] = {&qf, &rev_file};
-            if (!in[0].open(qf)) { fail(RTX_ERR_PARSE, "cannot open file"); return; }
-            if (!in[1].open(rev_file)) { in[0].close(); fail(RTX_ERR_PARSE, "cannot open " + rev_file); return; }
-            rtx_merge *stage = nullptr;
-            if (const int mrc = rtx_merge_create(devices[0], &merge, &stage)) { fail(mrc, std::string("paired-end merging on device ") + std::to_string(devices[0]) + ": " + rtx_last_error()); in[0].close(); in[1].close(); return; }
-            std::string buf[2];
-            bool eof[2] = {false, false};
-            uint64_t records = 0;  // pairs handed on so far
-            bool force = false;
-            for (;;) {
-                bool failed = false;
-                for (int k = 0; k < 2 && !failed; k++) {
-                    if (eof[k] || (buf[k].size() >= block_bytes && !force)) continue;
-                    const size_t have = buf[k].size();
-                    buf[k].resize(have + block_bytes);
-                    const size_t got = in[k].read(&buf[k][have], block_bytes);
-                    if (got == (size_t)-1) { fail(RTX_ERR_PARSE, "read error in " + *name[k] + " (corrupt gzip stream?)"); failed = true; break; }
-                    buf[k].resize(have + got);
-                    eof[k] = got < block_bytes;
-                    if (eof[k] && !buf[k].empty() && buf[k].back() != '\n') buf[k].push_back('\n');  // (the last record may lack its newline: counted as whole from here on)
-                }
-                if (failed) break;
-                force = false;
-                uint64_t n_rec[2] = {0, 0}, end[2] = {0, 0};
-                for (int k = 0; k < 2; k++) (void)rtx_fastq_block_end_n(buf[k].data(), buf[k].size(), ~0ull, &n_rec[k]);
-                const bool last = eof[0] && eof[1];
-                const uint64_t take = std::min(n_rec[0], n_rec[1]);
-                if (!last && take == 0) {
-                    const int out = eof[0] ? 0 : (eof[1] ? 1 : -1);
-                    if (out >= 0 && n_rec[out] == 0 && n_rec[1 - out] > 0) {
-                        fail(RTX_ERR_PARSE, "paired FASTQ: " + *name[out] + " ends after record " + std::to_string(records) + ", " + *name[1 - out] + " goes on");
-                        break;
-                    }
-                    force = true;  // no whole record of one file yet: read on
-                    continue;
-                }
-                for (int k = 0; k < 2; k++) end[k] = last ? buf[k].size() : rtx_fastq_block_end_n(buf[k].data(), buf[k].size(), take, nullptr);
-                auto blank = [](const std::string &t) { return t.find_first_not_of(" \t\r\n\v\f") == std::string::npos; };
-                Parsed pz;
-                pz.end = last;
-                if (last && blank(buf[0]) && blank(buf[1])) { push(std::move(pz)); break; }  // both files ended with the block before
-                if (last && n_rec[0] != n_rec[1]) {  // the files run out at different records
-                    const int out = n_rec[0] < n_rec[1] ? 0 : 1;
-                    fail(RTX_ERR_PARSE, "paired FASTQ: " + *name[out] + " ends after record " + std::to_string(records + n_rec[out]) + ", " + *name[1 - out] + " goes on");
-                    break;
-                }
-                rtx_queries *mates[2] = {nullptr, nullptr};
-                for (int k = 0; k < 2 && pz.rc == RTX_OK; k++) {
-                    pz.rc = rtx_queries_parse_fastq_block(buf[k].data(), end[k], nullptr, 0, qual.ascii_base, 0u, &mates[k]);
-                    if (pz.rc != RTX_OK) pz.err = *name[k] + ", records from " + std::to_string(records + 1) + " on: " + rtx_last_error();
-                }
-                if (pz.rc == RTX_OK) {
-                    pz.rc = rtx_merge_queries(stage, mates[0], mates[1], skip.empty() ? nullptr : skip.data(), skip.size(), &pz.qs);
-                    if (pz.rc != RTX_OK) pz.err = "pairs from record " + std::to_string(records + 1) + " on: " + rtx_last_error();
-                    else { (void)rtx_merge_stage_times(stage, pz.merge_s); (void)rtx_merge_kernel_time(stage, &pz.merge_ms); }
-                }
-                rtx_queries_destroy(mates[0]);
-                rtx_queries_destroy(mates[1]);
-                records += take;
-                failed = pz.rc != RTX_OK;
-                pz.end = last || failed;
-                push(std::move(pz));
-                if (failed || last) break;
-                for (int k = 0; k < 2; k++) buf[k].erase(0, end[k]);
-                {
-                    std::lock_guard<std::mutex> g(qmu);
-                    if (stop_reader) break;
-                }
-            }
-            rtx_merge_destroy(stage);
-            in[0].close();
-            in[1].close();
-            return;
-        }
-        Input f;
-        if (!f.open(qf)) { Parsed e; e.rc = RTX_ERR_PARSE; e.err = "cannot open file"; e.end = true; push(std::move(e)); return; }
-        std::string buf;
-        bool first = true, eof = false;
-        while (!eof) {
-            const size_t have = buf.size();
-            buf.resize(have + block_bytes);
-            const size_t got = f.read(&buf[have], block_bytes);
-            if (got == (size_t)-1) { Parsed e; e.rc = RTX_ERR_PARSE; e.err = "read error (corrupt gzip stream?)"; e.end = true; push(std::move(e)); break; }
-            buf.resize(have + got);
-            eof = got < block_bytes;
-            uint64_t end = buf.size();
-            uint32_t flags = first ? 0u : RTX_FASTA_NOT_FIRST;
-            if (!eof) {
-                end = fastq ? rtx_fastq_block_end(buf.data(), buf.size()) : rtx_fasta_block_end(buf.data(), buf.size());
-                if (end == 0) continue;  // no header (FASTQ: no whole record) inside the block yet: read on
-                flags |= RTX_FASTA_MORE_FOLLOWS;
-            }
-            Parsed pz;
-            pz.rc = fastq ? rtx_queries_parse_fastq_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), qual.ascii_base, flags, &pz.qs)
-                          : rtx_queries_parse_fasta_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), flags, &pz.qs);
-            if (pz.rc != RTX_OK) pz.err = rtx_last_error();
-            pz.end = eof || pz.rc != RTX_OK;
-            const bool failed = pz.rc != RTX_OK;
-            push(std::move(pz));
-            if (failed) break;
-            buf.erase(0, end);
-            first = false;
-            {
-                std::lock_guard<std::mutex> g(qmu);
-                if (stop_reader) break;
-            }
-        }
-        f.close();
-    });
-    auto stop_and_join_reader = [&]() {
+    bool stop = false;
+
+public:
+    void push(Parsed &&pz) {
+        std::unique_lock<std::mutex> g(mu);
+        cv.wait(g, [&] { return ready.size() < 2 || stop; });
+        ready.push_back(std::move(pz));
+        cv.notify_all();
+    }
+    void fail(int rc, const std::string &msg) { push(Parsed{nullptr, rc, msg, true}); }  // the last block of a file that cannot be read on
+    Parsed pop() {
+        std::unique_lock<std::mutex> g(mu);
+        cv.wait(g, [&] { return !ready.empty(); });
+        Parsed pz = std::move(ready.front());
+        ready.pop_front();
+        cv.notify_all();
+        return pz;
+    }
+    bool stopped() {
+        std::lock_guard<std::mutex> g(mu);
+        return stop;
+    }
+    void stop_and_join(std::thread &reader) {  // the reader leaves behind its next block; what it had queued is released
         {
-            std::lock_guard<std::mutex> g(qmu);
-            stop_reader = true;
-            qcv.notify_all();
+            std::lock_guard<std::mutex> g(mu);
+            stop = true;
+            cv.notify_all();
         }
         reader.join();
         for (Parsed &pz : ready) rtx_queries_destroy(pz.qs);
-    };
-    // one index handle per device, created side by side (each on a thread of its own: the builds run on their GPUs)
-    std::vector<rtx_index *> indices(devices.size(), nullptr);
-    std::vector<rtx_tally *> tallies(uniques ? devices.size() : 0, nullptr);  // --uniques: one object per handle, alive over the blocks of the file
-    {
-        std::vector<int> rcs(devices.size(), RTX_OK);
-        std::vector<std::string> errs(devices.size());
-        std::vector<std::thread> th;
-        for (size_t k = 0; k < devices.size(); k++)
-            th.emplace_back([&, k] {
-                rcs[k] = rtx_index_create_from_tree(devices[k], tree, &indices[k]);
-                if (rcs[k] == RTX_OK && device_format) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEVICE_TEXT, 1);
-                if (rcs[k] == RTX_OK && both_strands) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_STRAND, 1);
-                if (rcs[k] == RTX_OK && want_hits) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_NEAREST, 1);
-                if (rcs[k] == RTX_OK && want_identity) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_IDENTITY, 1);
-                if (rcs[k] == RTX_OK && derep) rcs[k] = rtx_index_set_option(indices[k], RTX_OPT_DEREP, 1);
-                if (rcs[k] == RTX_OK && !primers.empty()) {
-                    std::vector<rtx_trim_pattern> pats;
-                    for (const Primer &p : primers) pats.push_back({p.codes.data(), (uint32_t)p.codes.size(), p.end, (uint32_t)(p.codes.size() * primer_pct / 100u), primer_window});
-                    rcs[k] = rtx_index_set_primers(indices[k], pats.data(), (uint32_t)pats.size());
-                }
-                if (rcs[k] == RTX_OK && tags_on) {
-                    std::vector<rtx_demux_tag> ct;
-                    for (const Tag &t : tags) ct.push_back({t.codes.data(), (uint32_t)t.codes.size(), t.end});
-                    rcs[k] = rtx_index_set_tags(indices[k], ct.data(), (uint32_t)ct.size(), tag_pairs.data(), (uint32_t)tag_pairs.size(), &tag_params);
-                }
-                if (rcs[k] == RTX_OK && qual_on) rcs[k] = rtx_index_set_quality(indices[k], &qual);
-                if (rcs[k] == RTX_OK && screen_on) rcs[k] = rtx_index_set_screen(indices[k], contam_set, &contam);
-                if (rcs[k] == RTX_OK && chim_on) rcs[k] = rtx_index_set_chimera(indices[k], &chim);
-                if (rcs[k] == RTX_OK && uniques) {
-                    const rtx_tally_params tp{tags_on ? (uint32_t)sample_names.size() : 0u, uniques_max_entries, uniques_max_bytes, 0, 0};
-                    rcs[k] = rtx_tally_create(devices[k], &tp, &tallies[k]);
-                    if (rcs[k] == RTX_OK) rcs[k] = rtx_index_set_tally(indices[k], tallies[k]);
-                }
-                if (rcs[k] == RTX_OK && profile_cutoff && tags_on)  // ... with a column of counters per sample (PREFIX/raxtax.samples)
-                    rcs[k] = rtx_index_profile_begin_samples(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u),
-                                                             (uint32_t)sample_names.size());
-                else if (rcs[k] == RTX_OK && profile_cutoff)
-                    rcs[k] = rtx_index_profile_begin(indices[k], profile_cutoff, (skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (raw ? RTX_RAW_CONFIDENCE : 0u));
-                if (rcs[k] != RTX_OK) errs[k] = rtx_last_error();
-            });
-        for (auto &t : th) t.join();
-        for (size_t k = 0; k < devices.size(); k++)
-            if (rcs[k] != RTX_OK) {
-                fprintf(stderr, "[ERROR] device %d: %s\n", devices[k], errs[k].c_str());
-                stop_and_join_reader();
-                return 71;  // exitcode::OSERR
-            }
     }
-    rtx_screen_set_free(contam_set);  // (the handles keep what they need)
-    contam_set = nullptr;
-    lap("index");
-    if (timing) {  // the handle's own verdict on tile pruning (rtx_index_self_sample: a property of the database)
-        int on = 1;
-        double share = -1.0;
-        if (rtx_index_prune_verdict(indices[0], &on, &share) == RTX_OK && share >= 0.0)
-            fprintf(stderr, "[TIMING] tile pruning %s: a sample of the database's own references keeps %.1f %% of its tiles live\n", on ? "on" : "off", 100.0 * share);
-    }
-    start_bin_writer();  // after the index: rtx_index_create_from_tree looks at the tree's k-mer map
-    Sink sink;
-    const auto mode = (redo || !resume) ? std::ios::trunc : std::ios::app;
-    sink.out.open(out_path, mode);
-    sink.ckp.open(ckp_path, mode);
-    sink.want_tsv = tsv;
-    if (tsv) sink.tsv.open(tsv_path, mode);
-    if (both_strands) sink.strand.open(strand_path, mode);
-    else if (mode == std::ios::trunc) remove(strand_path.c_str());  // (a run that starts over in a folder of a --strand both run: its file would describe other lines)
-    if (want_hits) sink.hits.open(hits_path, mode);
-    else if (mode == std::ios::trunc) remove(hits_path.c_str());  // (likewise)
-    if (mode == std::ios::trunc) remove(profile_path.c_str());  // (written at the end of a run with --profile)
-    if (mode == std::ios::trunc) { remove(uniques_path.c_str()); remove(uniques_table_path.c_str()); remove(otus_path.c_str()); remove(otus_map_path.c_str()); remove(otus_table_path.c_str()); }  // (written at the end of a run with --uniques)
-    if (!primers.empty()) {
-        const bool header = mode == std::ios::trunc || !is_file(trim_path);
-        sink.trim.open(trim_path, mode);
-        if (header) sink.trim << "label\tlength\tstart\tend\tprimer5\terrors5\tprimer3\terrors3\n";
-        for (size_t k = 0; k < primers.size(); k++)
-            fprintf(stderr, "[INFO ] --primers: pattern %zu at the %s end: %s, at most %zu error(s)\n", k, primers[k].end == RTX_TRIM_3P ? "3'" : "5'", primers[k].name.c_str(),
-                    primers[k].codes.size() * primer_pct / 100u);
-    } else if (mode == std::ios::trunc) remove(trim_path.c_str());  // (likewise)
-    if (mode == std::ios::trunc) remove(samples_path.c_str());  // (written at the end of a run with --tags and --profile)
-    if (tags_on) {
-        const bool header = mode == std::ios::trunc || !is_file(demux_path);
-        sink.demux.open(demux_path, mode);
-        sink.sample_names = &sample_names;
-        if (header) sink.demux << "label\tsample\tverdict\ttag5\tmm5\toff5\ttag3\tmm3\toff3\tlo\thi\n";
-        for (size_t k = 0; k < tags.size(); k++)
-            fprintf(stderr, "[INFO ] --tags: tag %zu at the %s end: %s\n", k, tags[k].end == RTX_TRIM_3P ? "3'" : "5'", tags[k].name.c_str());
-        fprintf(stderr, "[INFO ] --tags: %zu samples, %zu pairs, at most %u mismatch(es), at most %u base(s) in front of a tag\n", sample_names.size(), tag_pairs.size(),
-                tag_params.max_mismatches, tag_params.max_offset);
-    } else if (mode == std::ios::trunc) remove(demux_path.c_str());  // (likewise)
-    if (qual_on) {
-        const bool header = mode == std::ios::trunc || !is_file(qc_path);
-        sink.qc.open(qc_path, mode);
-        if (header) sink.qc << "label\tlength\tstart\tend\texpected_errors\tverdict\n";
-    } else if (mode == std::ios::trunc) remove(qc_path.c_str());  // (likewise)
-    if (merge_on) {
-        const bool header = mode == std::ios::trunc || !is_file(merge_path);
-        sink.merge.open(merge_path, mode);
-        if (header) sink.merge << "label\tforward_length\treverse_length\toverlap\tdiffs\tmerged_length\tverdict\n";
-        fprintf(stderr, "[INFO ] --reverse: pairs of %s and %s are merged on device %d: overlap at least %u, at most %u diffs and %u %% of the overlap, Q capped at %u\n", qf.c_str(),
-                rev_file.c_str(), devices[0], merge.min_overlap, merge.max_diffs, merge.max_diff_pct, merge.q_cap);
-    } else if (mode == std::ios::trunc) remove(merge_path.c_str());  // (likewise)
-    if (chim_on) {
-        const bool header = mode == std::ios::trunc || !is_file(chim_path);
-        sink.chimera.open(chim_path, mode);
-        if (header) sink.chimera << "label\tstatus\twindows\tsingle\tparent_id\tseg\tpos\tleft\ta_id\tright\tb_id\tdelta\tchimera\tparent\ta\tb\n";
-        fprintf(stderr, "[INFO ] --chimera: %u segments, a read is flagged from delta %u on\n", chim.segments, chim.mindelta);
-    } else if (mode == std::ios::trunc) remove(chim_path.c_str());  // (likewise)
-    if (screen_on) {
-        const bool header = mode == std::ios::trunc || !is_file(screen_path);
-        sink.screen.open(screen_path, mode);
-        sink.contam_names = &contam_names;
-        if (header) sink.screen << "label\tlength\twindows\thits\tfirst\tsource\tverdict\n";
-    } else if (mode == std::ios::trunc) remove(screen_path.c_str());  // (likewise)
-    sink.want_qc = qual_on;
-    sink.want_strand = both_strands;
-    sink.want_hits = want_hits;
-    sink.tree = tree;
-    // the writer of main.rs:127-135: result lines, then the label into the progress file
-    auto sender = [](void *c, const char *label, const char *lines, const char *tsv_lines) -> int {
-        Sink *s = static_cast<Sink *>(c);
-        if (s->want_tsv && tsv_lines) s->tsv << tsv_lines << '\n';
-        s->out << lines << '\n';
-        s->ckp << label << '\n';
-        return s->out.good() && s->ckp.good() ? 0 : 1;
-    };
-    // ... and in front of them, under --strand both, which orientation the lines are of
-    // ... and, under --hits, which reference they look like: peak, t, ties, id and lineage of the nearest reference ('-' twice where no reference shares a k-mer)
-    auto info = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t, uint32_t) -> int {   // (in the shape of --identity's callback)
-        Sink *s = static_cast<Sink *>(c);
-        if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
-        if (s->want_hits) {
-            s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
-            if (nearest == RTX_NO_REF) s->hits << "-\t-\n";
-            else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest) << '\n';
+};
+
+void read_single(const Options &o, bool fastq, const std::vector<const char *> &skip, BlockQueue &q) {
+    Input f;
+    if (!f.open(o.qf)) { q.fail(RTX_ERR_PARSE, "cannot open file"); return; }
+    std::string buf;
+    bool first = true, eof = false;
+    while (!eof) {
+        if (!read_on(f, buf, o.block_bytes, eof)) { q.fail(RTX_ERR_PARSE, "read error (corrupt gzip stream?)"); break; }
+        uint64_t end = buf.size();
+        uint32_t flags = first ? 0u : RTX_FASTA_NOT_FIRST;
+        if (!eof) {
+            end = fastq ? rtx_fastq_block_end(buf.data(), buf.size()) : rtx_fasta_block_end(buf.data(), buf.size());
+            if (end == 0) continue;  // no header (FASTQ: no whole record) inside the block yet: read on
+            flags |= RTX_FASTA_MORE_FOLLOWS;
         }
-        return (!s->want_strand || s->strand.good()) && (!s->want_hits || s->hits.good()) ? 0 : 1;
-    };
-    // ... and, under --identity, how far the query is from it: the edit distance and the identity in percent behind the line of --hits
-    auto align = [](void *c, const char *label, int strand, uint32_t peak, uint32_t t, uint32_t nearest, uint32_t ties, uint32_t dist, uint32_t qlen) -> int {
-        Sink *s = static_cast<Sink *>(c);
-        if (s->want_strand) s->strand << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\n';
-        s->hits << label << '\t' << (strand ? '-' : '+') << '\t' << peak << '\t' << t << '\t' << ties << '\t';
-        if (nearest == RTX_NO_REF) s->hits << "-\t-";
-        else s->hits << nearest << '\t' << rtx_tree_lineage(s->tree, nearest);
-        if (dist == RTX_NO_DIST || qlen == 0u) {
-            s->hits << "\t-\t-\n";
-        } else {
-            const uint64_t h = ((uint64_t)(qlen - dist) * 10000u + qlen / 2u) / qlen;  // hundredths of a percent
-            char pct[32];
-            snprintf(pct, sizeof pct, "%llu.%02llu", (unsigned long long)(h / 100u), (unsigned long long)(h % 100u));
-            s->hits << '\t' << dist << '\t' << pct << '\n';
-        }
-        return (!s->want_strand || s->strand.good()) && s->hits.good() ? 0 : 1;
-    };
-    // ... and, under --primers, what was cut off every query (also one that has no result lines: an emptied read)
-    auto trimmed = [](void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint32_t hit) -> int {
-        Sink *s = static_cast<Sink *>(c);
-        const uint32_t p5 = hit & 0xFFu, e5 = (hit >> 8) & 0xFFu, p3 = (hit >> 16) & 0xFFu, e3 = hit >> 24;
-        s->trim << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t';
-        if (p5 == RTX_TRIM_NO_PATTERN) s->trim << "-\t-\t";
-        else s->trim << p5 << '\t' << e5 << '\t';
-        if (p3 == RTX_TRIM_NO_PATTERN) s->trim << "-\t-\n";
-        else s->trim << p3 << '\t' << e3 << '\n';
-        return s->trim.good() ? 0 : 1;
-    };
-    // ... and, with a quality filter, what it made of every query (also one without result lines: a discarded read)
-    auto filtered = [](void *c, const char *label, uint32_t raw_len, uint32_t lo, uint32_t hi, uint64_t ee, uint32_t verdict) -> int {
-        static const char *const names[7] = {"bad_quality", "short_for_trunc_len", "too_short", "too_long", "too_many_n", "max_ee", "max_ee_rate"};
-        Sink *s = static_cast<Sink *>(c);
-        s->screen_len = verdict ? 0u : hi - lo;  // (what the contaminant screen is given of this query)
-        if (!s->want_qc) return 0;
-        char frac[8];  // six decimals of ee / 2^40, truncated: from the integer, no floating point
-        snprintf(frac, sizeof frac, "%06llu", (unsigned long long)(((ee & ((1ull << 40) - 1)) * 1000000ull) >> 40));
-        s->qc << label << '\t' << raw_len << '\t' << lo << '\t' << hi << '\t' << (ee >> 40) << '.' << frac << '\t';
-        if (!verdict) s->qc << "pass";
-        for (uint32_t b = 0, first = 1; b < 7u; b++)
-            if ((verdict >> b) & 1u) { s->qc << (first ? "" : "+") << names[b]; first = 0; }
-        s->qc << '\n';
-        return s->qc.good() ? 0 : 1;
-    };
-    // ... and, under --chimera, what the check made of every query (also one without result lines: a flagged read)
-    auto checked = [](void *c, const char *label, const rtx_chimera_rec *r) -> int {
-        static const char *const status[3] = {"ok", "no_kmer", "too_long"};
-        Sink *s = static_cast<Sink *>(c);
-        auto id = [s](uint32_t ref) { if (ref == RTX_NO_REF) s->chimera << '-'; else s->chimera << ref; };
-        auto lin = [s](uint32_t ref) { if (ref == RTX_NO_REF) s->chimera << '-'; else s->chimera << rtx_tree_lineage(s->tree, ref); };
-        s->chimera << label << '\t' << status[r->status < 3u ? r->status : 0u] << '\t' << r->n_valid << '\t' << r->single << '\t';
-        id(r->parent);
-        s->chimera << '\t' << r->seg << '\t' << r->pos << '\t' << r->left << '\t';
-        id(r->parent_a);
-        s->chimera << '\t' << r->right << '\t';
-        id(r->parent_b);
-        s->chimera << '\t' << r->delta << '\t' << (r->status != RTX_CHIM_OK ? '?' : (r->flag ? 'Y' : 'N')) << '\t';
-        lin(r->parent);
-        s->chimera << '\t';
-        lin(r->parent_a);
-        s->chimera << '\t';
-        lin(r->parent_b);
-        s->chimera << '\n';
-        return s->chimera.good() ? 0 : 1;
-    };
-    // ... and, under --contaminants, what the screen made of every query (also one without result lines: a contaminant)
-    auto screened = [](void *c, const char *label, uint32_t windows, uint32_t hits, uint32_t first, uint32_t source, uint32_t verdict) -> int {
-        Sink *s = static_cast<Sink *>(c);
-        s->screen << label << '\t' << s->screen_len << '\t' << windows << '\t' << hits << '\t';
-        if (first == RTX_SCREEN_NONE) s->screen << '-';
-        else s->screen << first;
-        s->screen << '\t';
-        if (source == RTX_SCREEN_NONE || source >= s->contam_names->size()) s->screen << '-';
-        else s->screen << (*s->contam_names)[source];
-        s->screen << '\t' << (verdict ? "contaminant" : "pass") << '\n';
-        return s->screen.good() ? 0 : 1;
-    };
-    // ... and, under --tags, which sample every query belongs to (also one without result lines: a read that is not assigned)
-    auto assigned = [](void *c, const char *label, uint32_t, uint32_t sample, uint32_t lo, uint32_t hi, uint32_t hit, uint32_t info) -> int {
-        static const char *const verdicts[5] = {"ok", "no_tag5", "no_tag3", "ambiguous", "unknown_pair"};
-        Sink *s = static_cast<Sink *>(c);
-        const uint32_t t5 = hit & 0xFFFFu, t3 = hit >> 16, v = info & 0xFFu;
-        s->demux << label << '\t';
-        if (sample == RTX_DEMUX_NONE || sample >= s->sample_names->size()) s->demux << '*';
-        else s->demux << (*s->sample_names)[sample];
-        s->demux << '\t' << verdicts[v < 5u ? v : 0u] << '\t';
-        if (t5 == RTX_DEMUX_NO_TAG) s->demux << "-\t-\t-\t";
-        else s->demux << t5 << '\t' << ((info >> 8) & 0xFFu) << '\t' << ((info >> 24) & 0xFu) << '\t';
-        if (t3 == RTX_DEMUX_NO_TAG) s->demux << "-\t-\t-\t";
-        else s->demux << t3 << '\t' << ((info >> 16) & 0xFFu) << '\t' << (info >> 28) << '\t';
-        s->demux << lo << '\t' << hi << '\n';
-        return s->demux.good() ? 0 : 1;
-    };
-    int rc = RTX_OK;
-    uint64_t n = 0;
-    uint64_t trim_total[4] = {0, 0, 0, 0};  // --primers: over the blocks of the file (rtx_raxtax_last_trim)
-    double trim_busy = 0;
-    uint64_t qual_total[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};  // the quality filter: queries, passed, cut short, the seven reasons (rtx_raxtax_last_qual)
-    double qual_busy = 0;
-    uint64_t chim_total[3] = {0, 0, 0};  // --chimera: queries, reads checked, queries flagged (rtx_raxtax_last_chimera)
-    double chim_busy = 0;
-    uint64_t screen_total[3] = {0, 0, 0};  // --contaminants: queries, screened, contaminants (rtx_raxtax_last_screen)
-    double screen_busy = 0;
-    uint64_t demux_total[7] = {0, 0, 0, 0, 0, 0, 0};  // --tags: queries, assigned, and the queries of every verdict (rtx_raxtax_last_demux)
-    double demux_busy = 0;
-    uint64_t derep_queries = 0, derep_distinct = 0;  // --derep: over the blocks of the file (rtx_raxtax_last_derep)
-    double derep_busy = 0;
-    uint64_t merge_total[6] = {0, 0, 0, 0, 0, 0};  // --reverse: pairs, merged, and not merged for each of the four reasons (RTX_MG_*)
-    double merge_busy = 0;
-    bool parse_failed = false;
-    for (;;) {
         Parsed pz;
-        {
-            std::unique_lock<std::mutex> g(qmu);
-            qcv.wait(g, [&] { return !ready.empty(); });
-            pz = std::move(ready.front());
-            ready.pop_front();
-            qcv.notify_all();
+        pz.rc = fastq ? rtx_queries_parse_fastq_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), o.qual.ascii_base, flags, &pz.qs)
+                      : rtx_queries_parse_fasta_block(buf.data(), end, skip.empty() ? nullptr : skip.data(), skip.size(), flags, &pz.qs);
+        if (pz.rc != RTX_OK) pz.err = rtx_last_error();
+        pz.end = eof || pz.rc != RTX_OK;
+        const bool failed = pz.rc != RTX_OK;
+        q.push(std::move(pz));
+        if (failed || q.stopped()) break;
+        buf.erase(0, end);
+        first = false;
+    }
+    f.close();
+}
+
+// Paired input: both files block by block, cut at the same record (rtx_fastq_block_end_n), parsed, and merged on the first device
+// of the run; what is queued is the handle of merged reads.  Nothing behind the queue knows.
+void read_paired(const Options &o, const std::vector<const char *> &skip, BlockQueue &q) {
+    Input in[2];
+    const std::string *name[2] = {&o.qf, &o.rev_file};
+    if (!in[0].open(o.qf)) { q.fail(RTX_ERR_PARSE, "cannot open file"); return; }
+    if (!in[1].open(o.rev_file)) { in[0].close(); q.fail(RTX_ERR_PARSE, "cannot open " + o.rev_file); return; }
+    rtx_merge *stage = nullptr;
+    if (const int mrc = rtx_merge_create(o.devices[0], &o.merge, &stage)) {
+        q.fail(mrc, std::string("paired-end merging on device ") + std::to_string(o.devices[0]) + ": " + rtx_last_error());
+        in[0].close();
+        in[1].close();
+        return;
+    }
+    std::string buf[2];
+    bool eof[2] = {false, false};
+    uint64_t records = 0;  // pairs handed on so far
+    bool force = false;
+    for (;;) {
+        bool failed = false;
+        for (int k = 0; k < 2 && !failed; k++) {
+            if (eof[k] || (buf[k].size() >= o.block_bytes && !force)) continue;
+            if (!read_on(in[k], buf[k], o.block_bytes, eof[k])) { q.fail(RTX_ERR_PARSE, "read error in " + *name[k] + " (corrupt gzip stream?)"); failed = true; break; }
+            if (eof[k] && !buf[k].empty() && buf[k].back() != '\n') buf[k].push_back('\n');  // (the last record may lack its newline: counted as whole from here on)
         }
+        if (failed) break;
+        force = false;
+        uint64_t n_rec[2] = {0, 0}, end[2] = {0, 0};
+        for (int k = 0; k < 2; k++) (void)rtx_fastq_block_end_n(buf[k].data(), buf[k].size(), ~0ull, &n_rec[k]);
+        const bool last = eof[0] && eof[1];
+        const uint64_t take = std::min(n_rec[0], n_rec[1]);
+        if (!last && take == 0) {
+            const int out = eof[0] ? 0 : (eof[1] ? 1 : -1);
+            if (out >= 0 && n_rec[out] == 0 && n_rec[1 - out] > 0) {
+                q.fail(RTX_ERR_PARSE, "paired FASTQ: " + *name[out] + " ends after record " + std::to_string(records) + ", " + *name[1 - out] + " goes on");
+                break;
+            }
+            force = true;  // no whole record of one file yet: read on
+            continue;
+        }
+        for (int k = 0; k < 2; k++) end[k] = last ? buf[k].size() : rtx_fastq_block_end_n(buf[k].data(), buf[k].size(), take, nullptr);
+        auto blank = [](const std::string &t) { return t.find_first_not_of(" \t\r\n\v\f") == std::string::npos; };
+        Parsed pz;
+        pz.end = last;
+        if (last && blank(buf[0]) && blank(buf[1])) { q.push(std::move(pz)); break; }  // both files ended with the block before
+        if (last && n_rec[0] != n_rec[1]) {  // the files run out at different records
+            const int out = n_rec[0] < n_rec[1] ? 0 : 1;
+            q.fail(RTX_ERR_PARSE, "paired FASTQ: " + *name[out] + " ends after record " + std::to_string(records + n_rec[out]) + ", " + *name[1 - out] + " goes on");
+            break;
+        }
+        rtx_queries *mates[2] = {nullptr, nullptr};
+        for (int k = 0; k < 2 && pz.rc == RTX_OK; k++) {
+            pz.rc = rtx_queries_parse_fastq_block(buf[k].data(), end[k], nullptr, 0, o.qual.ascii_base, 0u, &mates[k]);
+            if (pz.rc != RTX_OK) pz.err = *name[k] + ", records from " + std::to_string(records + 1) + " on: " + rtx_last_error();
+        }
+        if (pz.rc == RTX_OK) {
+            pz.rc = rtx_merge_queries(stage, mates[0], mates[1], skip.empty() ? nullptr : skip.data(), skip.size(), &pz.qs);
+            if (pz.rc != RTX_OK) pz.err = "pairs from record " + std::to_string(records + 1) + " on: " + rtx_last_error();
+            else { (void)rtx_merge_stage_times(stage, pz.merge_s); (void)rtx_merge_kernel_time(stage, &pz.merge_ms); }
+        }
+        rtx_queries_destroy(mates[0]);
+        rtx_queries_destroy(mates[1]);
+        records += take;
+        failed = pz.rc != RTX_OK;
+        pz.end = last || failed;
+        q.push(std::move(pz));
+        if (failed || last || q.stopped()) break;
+        for (int k = 0; k < 2; k++) buf[k].erase(0, end[k]);
+    }
+    rtx_merge_destroy(stage);
+    in[0].close();
+    in[1].close();
+}
+
+// ---- handles: one index handle per device, created side by side (each on a thread of its own: the builds run on their GPUs), with everything the
+// options turn on; --uniques: a tally per handle as well, alive over the blocks of the file
+bool create_handles(const Options &o, const Plan &p, const rtx_tree *tree, std::vector<rtx_index *> &indices, std::vector<rtx_tally *> &tallies) {
+    const size_t nd = o.devices.size();
+    const uint32_t n_samples = p.tags_on ? (uint32_t)p.sample_names.size() : 0u, mode = (o.skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (o.raw ? RTX_RAW_CONFIDENCE : 0u);
+    std::vector<int> rcs(nd, RTX_OK);
+    std::vector<std::string> errs(nd);
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < nd; k++)
+        th.emplace_back([&, k] {
+            rtx_index *&ix = indices[k];
+            int &rc = rcs[k];
+            rc = rtx_index_create_from_tree(o.devices[k], tree, &ix);
+            const std::pair<bool, int> flags[] = {{o.device_format, RTX_OPT_DEVICE_TEXT}, {o.both_strands, RTX_OPT_STRAND}, {o.want_hits, RTX_OPT_NEAREST},
+                                                       {o.want_identity, RTX_OPT_IDENTITY}, {o.derep, RTX_OPT_DEREP}};
+            for (const auto &f : flags)
+                if (rc == RTX_OK && f.first) rc = rtx_index_set_option(ix, f.second, 1);
+            if (rc == RTX_OK && !p.primers.empty()) {
+                std::vector<rtx_trim_pattern> pats;
+                for (const Oligo &pr : p.primers) pats.push_back({pr.codes.data(), (uint32_t)pr.codes.size(), pr.end, (uint32_t)(pr.codes.size() * o.primer_pct / 100u), o.primer_window});
+                rc = rtx_index_set_primers(ix, pats.data(), (uint32_t)pats.size());
+            }
+            if (rc == RTX_OK && p.tags_on) {
+                std::vector<rtx_demux_tag> ct;
+                for (const Oligo &t : p.tags) ct.push_back({t.codes.data(), (uint32_t)t.codes.size(), t.end});
+                rc = rtx_index_set_tags(ix, ct.data(), (uint32_t)ct.size(), p.tag_pairs.data(), (uint32_t)p.tag_pairs.size(), &o.tag_params);
+            }
+            if (rc == RTX_OK && p.qual_on) rc = rtx_index_set_quality(ix, &o.qual);
+            if (rc == RTX_OK && p.screen_on) rc = rtx_index_set_screen(ix, p.contam_set, &o.contam);
+            if (rc == RTX_OK && o.chim_on) rc = rtx_index_set_chimera(ix, &o.chim);
+            if (rc == RTX_OK && o.uniques) {
+                const rtx_tally_params tp{n_samples, o.uniques_max_entries, o.uniques_max_bytes, 0, 0};
+                rc = rtx_tally_create(o.devices[k], &tp, &tallies[k]);
+                if (rc == RTX_OK) rc = rtx_index_set_tally(ix, tallies[k]);
+            }
+            if (rc == RTX_OK && o.profile_cutoff && p.tags_on)  // ... with a column of counters per sample (PREFIX/raxtax.samples)
+                rc = rtx_index_profile_begin_samples(ix, o.profile_cutoff, mode, n_samples);
+            else if (rc == RTX_OK && o.profile_cutoff)
+                rc = rtx_index_profile_begin(ix, o.profile_cutoff, mode);
+            if (rc != RTX_OK) errs[k] = rtx_last_error();
+        });
+    for (auto &t : th) t.join();
+    for (size_t k = 0; k < nd; k++)
+        if (rcs[k] != RTX_OK) {
+            fprintf(stderr, "[ERROR] device %d: %s\n", o.devices[k], errs[k].c_str());
+            return false;
+        }
+    return true;
+}
+
+// The streams of a run: behind what a resumed run kept, over what an earlier run left otherwise; and what the log says of the groups that are on
+void open_reports(const Options &o, const Plan &p, const std::vector<Report> &reports, Sink &s, bool fresh) {
+    const auto mode = fresh ? std::ios::trunc : std::ios::app;
+    s.out.open(o.prefix + "/raxtax.out", mode);
+    s.ckp.open(o.prefix + "/raxtax.ckp", mode);
+    if (o.tsv) s.tsv.open(o.prefix + "/raxtax.tsv", mode);
+    for (const Report &r : reports) {
+        const std::string path = o.prefix + "/" + r.name;
+        if (r.on) {
+            const bool header = r.header && (fresh || !is_file(path));
+            r.stream->open(path, mode);
+            if (header) *r.stream << r.header;
+        } else if (fresh) remove(path.c_str());
+    }
+    if (fresh)
+        for (const char *name : kEndOfRunFiles) remove((o.prefix + "/" + name).c_str());
+    for (size_t k = 0; k < p.primers.size(); k++)
+        fprintf(stderr, "[INFO ] --primers: pattern %zu at the %s end: %s, at most %zu error(s)\n", k, p.primers[k].end == RTX_TRIM_3P ? "3'" : "5'", p.primers[k].name.c_str(),
+                p.primers[k].codes.size() * o.primer_pct / 100u);
+    for (size_t k = 0; k < p.tags.size(); k++)
+        fprintf(stderr, "[INFO ] --tags: tag %zu at the %s end: %s\n", k, p.tags[k].end == RTX_TRIM_3P ? "3'" : "5'", p.tags[k].name.c_str());
+    if (p.tags_on)
+        fprintf(stderr, "[INFO ] --tags: %zu samples, %zu pairs, at most %u mismatch(es), at most %u base(s) in front of a tag\n", p.sample_names.size(), p.tag_pairs.size(),
+                o.tag_params.max_mismatches, o.tag_params.max_offset);
+    if (p.merge_on)
+        fprintf(stderr, "[INFO ] --reverse: pairs of %s and %s are merged on device %d: overlap at least %u, at most %u diffs and %u %% of the overlap, Q capped at %u\n", o.qf.c_str(),
+                o.rev_file.c_str(), o.devices[0], o.merge.min_overlap, o.merge.max_diffs, o.merge.max_diff_pct, o.merge.q_cap);
+    if (o.chim_on) fprintf(stderr, "[INFO ] --chimera: %u segments, a read is flagged from delta %u on\n", o.chim.segments, o.chim.mindelta);
+}
+
+// ---- the stages in front of the classification and what they count over the blocks of the file.  The rows in the order of the [TIMING] lines of a
+// block; key: "<key>_busy" in the JSON of --timing; n counters, the first the queries; second: what the second counter is, where the line of a block
+// names it; last: the counters and the busy seconds of the last call of rtx_raxtax_multi_ex*
+struct Stage { const char *name, *key, *second; int n; int (*last)(uint64_t *c, double *busy); };
+enum { SCREEN, DEMUX, TRIM, QUAL, CHIMERA, DEREP, MERGE, N_STAGES };
+const Stage kStages[N_STAGES] = {
+    {"contaminant screen", "screen", nullptr, 3, [](uint64_t *c, double *b) { return rtx_raxtax_last_screen(c, c + 1, c + 2, b); }},       // queries, screened, contaminants
+    {"demultiplexing", "demux", nullptr, 7, [](uint64_t *c, double *b) { return rtx_raxtax_last_demux(c, c + 1, c + 2, b); }},               // queries, assigned, and the queries of every verdict
+    {"primer trimming", "trim", nullptr, 4, [](uint64_t *c, double *b) { return rtx_raxtax_last_trim(c, c + 1, c + 2, c + 3, b); }},         // queries, with a 5' primer, with a 3' primer, emptied
+    {"quality filter", "qual", nullptr, 10, [](uint64_t *c, double *b) { return rtx_raxtax_last_qual(c, c + 1, c + 2, c + 3, b); }},         // queries, passed, cut short, the seven reasons
+    {"chimera check", "chimera", "reads checked", 3, [](uint64_t *c, double *b) { return rtx_raxtax_last_chimera(c, c + 1, c + 2, b); }},  // queries, reads checked, queries flagged
+    {"dereplication", "derep", "distinct", 2, [](uint64_t *c, double *b) { return rtx_raxtax_last_derep(c, c + 1, b); }},                   // queries, distinct (per chunk)
+    {nullptr, "merge", nullptr, 6, nullptr},  // --reverse, on the reader's thread (merge_report): pairs, merged, and not merged for each of the four reasons (RTX_MG_*)
+};
+struct Totals { bool on = false; ull c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; double busy = 0; };
+
+// What the merge made of every pair of a block (raxtax.merge), before the block is classified
+void merge_report(const Options &o, const Parsed &pz, uint64_t nb, const char *const *labels, const uint64_t *off, Sink &sink, Totals &tot) {
+    static const char *const names[4] = {"bad_quality", "too_long", "too_short", "no_overlap"};
+    const uint32_t *mnf, *mnr, *mov, *md, *mv;
+    if (rtx_queries_merge_report(pz.qs, &mnf, &mnr, &mov, &md, &mv) == RTX_OK)
+        for (uint64_t i = 0; i < nb; i++) {
+            const char *verdict = "merged";
+            tot.c[0]++;
+            if (!mv[i]) tot.c[1]++;
+            for (uint32_t b = 0; b < 4u; b++)
+                if ((mv[i] >> b) & 1u) { verdict = names[b]; tot.c[2 + b]++; break; }
+            sink.merge << labels[i] << '\t' << mnf[i] << '\t' << mnr[i] << '\t' << mov[i] << '\t' << md[i] << '\t' << (off[i + 1] - off[i]) << '\t' << verdict << '\n';
+        }
+    tot.busy += pz.merge_s[2];
+    if (o.timing) fprintf(stderr, "[TIMING] merging of this block: %llu pairs, kernel %.3f ms, staging %.3f s, copies and wait %.3f s, all %.3f s (on the reader's thread, beside the classification of the block before)\n",
+                          (ull)nb, pz.merge_ms, pz.merge_s[0], pz.merge_s[1], pz.merge_s[2]);
+}
+
+// ---- the loop over blocks: every block of the reader through rtx_raxtax_multi_ex8.  The library's code of the run; parse_failed: the reader gave up
+int classify_blocks(const Options &o, const Plan &p, BlockQueue &queue, std::vector<rtx_index *> &indices, const rtx_tree *tree, Sink &sink, Totals *tot, uint64_t &n, bool &parse_failed) {
+    int rc = RTX_OK;
+    for (;;) {
+        Parsed pz = queue.pop();
         if (pz.rc != RTX_OK) {
-            fprintf(stderr, "[ERROR] Failed to parse %s: %s\n", qf.c_str(), pz.err.c_str());
+            fprintf(stderr, "[ERROR] Failed to parse %s: %s\n", o.qf.c_str(), pz.err.c_str());
             parse_failed = true;
             break;
         }
@@ -1151,265 +1217,259 @@ int main(int argc, char **argv) {
             const uint8_t *bases;
             const uint64_t *off;
             rtx_queries_data(pz.qs, &bases, &off);
-            if (merge_on) {  // what the merge made of every pair of the block, before the block is classified
-                static const char *const names[4] = {"bad_quality", "too_long", "too_short", "no_overlap"};
-                const uint32_t *mnf, *mnr, *mov, *md, *mv;
-                if (rtx_queries_merge_report(pz.qs, &mnf, &mnr, &mov, &md, &mv) == RTX_OK)
-                    for (uint64_t i = 0; i < nb; i++) {
-                        const char *verdict = "merged";
-                        merge_total[0]++;
-                        if (!mv[i]) merge_total[1]++;
-                        for (uint32_t b = 0; b < 4u; b++)
-                            if ((mv[i] >> b) & 1u) { verdict = names[b]; merge_total[2 + b]++; break; }
-                        sink.merge << labels[i] << '\t' << mnf[i] << '\t' << mnr[i] << '\t' << mov[i] << '\t' << md[i] << '\t' << (off[i + 1] - off[i]) << '\t' << verdict << '\n';
-                    }
-                merge_busy += pz.merge_s[2];
-                if (timing) fprintf(stderr, "[TIMING] merging of this block: %llu pairs, kernel %.3f ms, staging %.3f s, copies and wait %.3f s, all %.3f s (on the reader's thread, beside the classification of the block before)\n",
-                                    (unsigned long long)nb, pz.merge_ms, pz.merge_s[0], pz.merge_s[1], pz.merge_s[2]);
-            }
+            if (p.merge_on) merge_report(o, pz, nb, labels.data(), off, sink, tot[MERGE]);
             // Chunks of 131 072 queries are what a device handles best (two sub-batches of 65 536 on its two streams, the next chunk enqueued ahead:
             // 43 ms per 524 288 queries against 101-113 with chunks of 32 768, the default until round 6); smaller ones when the block would
             // otherwise leave a device without two chunks of its own, never below 32 768.
             const size_t per_dev = (size_t)((nb + 2 * indices.size() - 1) / (2 * indices.size()));
-            const size_t chunk_now = chunk ? chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
+            const size_t chunk_now = o.chunk ? o.chunk : std::min<size_t>(131072, std::max<size_t>(32768, per_dev));
             // one entry point takes everything a run can bring: an option that is off passes no callback
             const uint8_t *quals = nullptr;
-            if (qual_on) rtx_queries_quals(pz.qs, &quals);
-            rc = rtx_raxtax_multi_ex8(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, skip_exact, raw, chunk_now, sender, &sink, tsv,
-                                      want_identity ? +align : (both_strands || want_hits ? +info : nullptr), &sink, primers.empty() ? nullptr : +trimmed, &sink,
-                                      quals, qual_on || screen_on ? +filtered : nullptr, &sink, chim_on ? +checked : nullptr, &sink, tags_on ? +assigned : nullptr, &sink,
-                                      screen_on ? +screened : nullptr, &sink);
+            if (p.qual_on) rtx_queries_quals(pz.qs, &quals);
+            rc = rtx_raxtax_multi_ex8(indices.data(), (uint32_t)indices.size(), tree, nb, labels.data(), bases, off, o.skip_exact, o.raw, chunk_now, sender, &sink, o.tsv,
+                                      o.want_identity ? align : (o.both_strands || o.want_hits ? info : nullptr), &sink, p.primers.empty() ? nullptr : trimmed, &sink,
+                                      quals, wants_range_and_quality(p) ? range_and_quality : nullptr, &sink, o.chim_on ? checked : nullptr, &sink, p.tags_on ? assigned : nullptr, &sink,
+                                      p.screen_on ? screened : nullptr, &sink);
             n += nb;
-            if (screen_on) {
-                uint64_t sq[3] = {0, 0, 0};
-                double sb = 0;
-                if (rtx_raxtax_last_screen(&sq[0], &sq[1], &sq[2], &sb) == RTX_OK) { for (int k = 0; k < 3; k++) screen_total[k] += sq[k]; screen_busy += sb; }
-                if (timing) fprintf(stderr, "[TIMING] contaminant screen of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)sq[0], sb);
+            for (int s = 0; s < MERGE; s++) {
+                if (!tot[s].on) continue;
+                const Stage &st = kStages[s];
+                uint64_t c[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+                double busy = 0;
+                if (st.last(c, &busy) == RTX_OK) {
+                    for (int k = 0; k < st.n; k++) tot[s].c[k] += c[k];
+                    tot[s].busy += busy;
+                }
+                if (o.timing && st.second) fprintf(stderr, "[TIMING] %s of this block: %llu queries, %llu %s, busy %.3f s (ahead of the device stage)\n", st.name, (ull)c[0], (ull)c[1], st.second, busy);
+                else if (o.timing) fprintf(stderr, "[TIMING] %s of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", st.name, (ull)c[0], busy);
             }
-            if (tags_on) {
-                uint64_t xq[7] = {0, 0, 0, 0, 0, 0, 0};
-                double xb = 0;
-                if (rtx_raxtax_last_demux(&xq[0], &xq[1], xq + 2, &xb) == RTX_OK) { for (int k = 0; k < 7; k++) demux_total[k] += xq[k]; demux_busy += xb; }
-                if (timing) fprintf(stderr, "[TIMING] demultiplexing of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)xq[0], xb);
-            }
-            if (!primers.empty()) {
-                uint64_t tq[4] = {0, 0, 0, 0};
-                double tb = 0;
-                if (rtx_raxtax_last_trim(&tq[0], &tq[1], &tq[2], &tq[3], &tb) == RTX_OK) { for (int k = 0; k < 4; k++) trim_total[k] += tq[k]; trim_busy += tb; }
-                if (timing) fprintf(stderr, "[TIMING] primer trimming of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)tq[0], tb);
-            }
-            if (qual_on) {
-                uint64_t qq[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-                double qb = 0;
-                if (rtx_raxtax_last_qual(&qq[0], &qq[1], &qq[2], qq + 3, &qb) == RTX_OK) { for (int k = 0; k < 10; k++) qual_total[k] += qq[k]; qual_busy += qb; }
-                if (timing) fprintf(stderr, "[TIMING] quality filter of this block: %llu queries, busy %.3f s (ahead of the device stage)\n", (unsigned long long)qq[0], qb);
-            }
-            if (chim_on) {
-                uint64_t cq[3] = {0, 0, 0};
-                double cb = 0;
-                if (rtx_raxtax_last_chimera(&cq[0], &cq[1], &cq[2], &cb) == RTX_OK) { for (int k = 0; k < 3; k++) chim_total[k] += cq[k]; chim_busy += cb; }
-                if (timing) fprintf(stderr, "[TIMING] chimera check of this block: %llu queries, %llu reads checked, busy %.3f s (ahead of the device stage)\n", (unsigned long long)cq[0], (unsigned long long)cq[1], cb);
-            }
-            if (derep) {
-                uint64_t dq = 0, du = 0;
-                double db_ = 0;
-                if (rtx_raxtax_last_derep(&dq, &du, &db_) == RTX_OK) { derep_queries += dq; derep_distinct += du; derep_busy += db_; }
-                if (timing) fprintf(stderr, "[TIMING] dereplication of this block: %llu queries, %llu distinct, busy %.3f s (ahead of the device stage)\n", (unsigned long long)dq, (unsigned long long)du, db_);
-            }
-            if (timing) {  // busy seconds of the pipeline stages of this block (which stage bounds the run)
+            if (o.timing) {  // busy seconds of the pipeline stages of this block (which stage bounds the run)
                 double busy[4];
                 uint64_t nch = 0;
                 if (rtx_raxtax_last_timing(busy, &nch) == RTX_OK)
                     fprintf(stderr, "[TIMING] pipeline busy seconds over %llu chunk(s) on %zu handle(s): lookup %.3f, device %.3f (busiest handle), format %.3f, sender %.3f\n",
-                            (unsigned long long)nch, indices.size(), busy[0], busy[1], busy[2], busy[3]);
+                            (ull)nch, indices.size(), busy[0], busy[1], busy[2], busy[3]);
                 uint64_t ahead = 0, abandoned = 0;  // RTX_OPT_RUN_AHEAD (the first handle, since its creation)
                 if (rtx_index_run_ahead_stats(indices[0], &ahead, &abandoned) == RTX_OK)
-                    fprintf(stderr, "[TIMING] chunks enqueued ahead of the end of the chunk before them: %llu, abandoned: %llu (queries of this block: %llu)\n", (unsigned long long)ahead,
-                            (unsigned long long)abandoned, (unsigned long long)nb);
+                    fprintf(stderr, "[TIMING] chunks enqueued ahead of the end of the chunk before them: %llu, abandoned: %llu (queries of this block: %llu)\n", (ull)ahead,
+                            (ull)abandoned, (ull)nb);
             }
         }
         rtx_queries_destroy(pz.qs);
         if (rc != RTX_OK || pz.end) break;
     }
-    stop_and_join_reader();
+    return rc;
+}
+
+// What the stages that were on counted over the run, to the log, and their busy seconds to the JSON of --timing: merge, tags, primers, quality,
+// contaminants, chimera, derep
+void print_totals(const Options &o, const Totals *tot, Laps &laps) {
+    const ull *c = tot[MERGE].c;
+    if (tot[MERGE].on)
+        fprintf(stderr, "[INFO ] --reverse: %llu pairs, %llu merged; not merged for bad_quality %llu, too_long %llu, too_short %llu, no_overlap %llu\n", c[0], c[1], c[2], c[3], c[4], c[5]);
+    c = tot[DEMUX].c;
+    if (tot[DEMUX].on)
+        fprintf(stderr, "[INFO ] --tags: %llu queries, %llu assigned to a sample; not assigned for no_tag5 %llu, no_tag3 %llu, ambiguous %llu, unknown_pair %llu\n",
+                c[0], c[1], c[3], c[4], c[5], c[6]);
+    c = tot[TRIM].c;
+    if (tot[TRIM].on) fprintf(stderr, "[INFO ] --primers: %llu queries, %llu with a 5' primer, %llu with a 3' primer, %llu left empty\n", c[0], c[1], c[2], c[3]);
+    c = tot[QUAL].c;
+    if (tot[QUAL].on)
+        fprintf(stderr, "[INFO ] quality filter: %llu queries, %llu passed (%llu of them cut short); discarded for bad_quality %llu, short_for_trunc_len %llu, too_short %llu, "
+                        "too_long %llu, too_many_n %llu, max_ee %llu, max_ee_rate %llu\n", c[0], c[1], c[2], c[3], c[4], c[5], c[6], c[7], c[8], c[9]);
+    c = tot[SCREEN].c;
+    if (tot[SCREEN].on) fprintf(stderr, "[INFO ] --contaminants: %llu queries, %llu screened, %llu contaminants\n", c[0], c[1], c[2]);
+    c = tot[CHIMERA].c;
+    if (tot[CHIMERA].on) fprintf(stderr, "[INFO ] --chimera: %llu queries, %llu reads checked, %llu queries flagged\n", c[0], c[1], c[2]);
+    c = tot[DEREP].c;
+    if (tot[DEREP].on) fprintf(stderr, "[INFO ] --derep: %llu queries, %llu distinct\n", c[0], c[1]);  // (per chunk: a copy in another chunk counts as a distinct read of its own)
+    for (int s : {MERGE, DEMUX, TRIM, QUAL, SCREEN, CHIMERA, DEREP})
+        if (tot[s].on && o.timing) laps.log << ", \"" << kStages[s].key << "_busy\": " << tot[s].busy;
+}
+
+// ---- the files written at the end of a run.  Each: 0, or the exit code behind the message
+
+// --profile: the taxon profile of the whole run: the sum over the handles, written once
+int write_profile(const Options &o, const std::vector<rtx_index *> &indices, const rtx_tree *tree) {
+    std::vector<rtx_profile_view> views(indices.size());
+    std::vector<rtx_profile_view *> ptrs(indices.size());
+    int prc = RTX_OK;
+    for (size_t k = 0; k < indices.size() && prc == RTX_OK; k++) {
+        prc = rtx_index_profile_read(indices[k], &views[k]);
+        ptrs[k] = &views[k];
+    }
+    const size_t nn = prc == RTX_OK ? views[0].n_nodes : 0;
+    std::vector<uint64_t> acc(3 * nn);
+    uint64_t totals[4] = {0, 0, 0, 0};
+    if (prc == RTX_OK) prc = rtx_profile_merge(ptrs.data(), (uint32_t)ptrs.size(), acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals);
+    std::string text;
+    if (prc == RTX_OK)
+        prc = format_two_pass(text, [&](char *buf, uint64_t cap) { return rtx_profile_format(tree, acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals, o.profile_cutoff, buf, cap); });
+    if (prc != RTX_OK) { fprintf(stderr, "[ERROR] taxon profile: %s\n", rtx_last_error()); return 70; }
+    return write_whole(o.prefix + "/raxtax.profile", text) ? 0 : 74;
+}
+
+// --profile with --tags: the taxon x sample table beside it: the per-sample counters summed over the handles
+int write_sample_table(const Options &o, const Plan &p, const std::vector<rtx_index *> &indices, const rtx_tree *tree) {
+    std::vector<rtx_sample_profile_view> views(indices.size());
+    std::vector<rtx_sample_profile_view *> ptrs(indices.size());
+    int prc = RTX_OK;
+    for (size_t k = 0; k < indices.size() && prc == RTX_OK; k++) {
+        prc = rtx_index_profile_read_samples(indices[k], &views[k]);
+        ptrs[k] = &views[k];
+    }
+    const size_t nn = prc == RTX_OK ? views[0].n_nodes : 0, ns = p.sample_names.size();
+    std::vector<uint64_t> direct(ns * nn + 1), totals(ns * 4);
+    if (prc == RTX_OK) prc = rtx_sample_profile_merge(ptrs.data(), (uint32_t)ptrs.size(), direct.data(), totals.data());
+    std::vector<const char *> names;
+    for (const std::string &s : p.sample_names) names.push_back(s.c_str());
+    std::string text;
+    if (prc == RTX_OK)
+        prc = format_two_pass(text, [&](char *buf, uint64_t cap) { return rtx_sample_table_format(tree, (uint32_t)ns, names.data(), direct.data(), totals.data(), o.profile_cutoff, buf, cap); });
+    if (prc != RTX_OK) { fprintf(stderr, "[ERROR] sample table: %s\n", rtx_last_error()); return 70; }
+    return write_whole(o.prefix + "/raxtax.samples", text) ? 0 : 74;
+}
+
+// --uniques: the distinct reads of the whole run: the tables of the handles' objects read, summed and written once;
+// --otus: the summed table, whole, clustered on the first device
+int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rtx_tally *> &tallies) {
+    std::vector<rtx_tally_table *> tables(tallies.size(), nullptr);
+    rtx_tally_table *sum = nullptr;
+    int trc = RTX_OK;
+    for (size_t k = 0; k < tallies.size() && trc == RTX_OK; k++) trc = rtx_tally_read(tallies[k], &tables[k]);
+    if (trc == RTX_OK) trc = rtx_tally_table_merge(tables.data(), (uint32_t)tables.size(), &sum);
+    rtx_tally_view view{};
+    if (trc == RTX_OK) trc = rtx_tally_table_view(sum, &view);
+    std::vector<const char *> names;
+    for (const std::string &s : p.sample_names) names.push_back(s.c_str());
+    std::string fasta, table;
+    if (trc == RTX_OK) trc = format_two_pass(fasta, [&](char *buf, uint64_t cap) { return rtx_tally_format_fasta(sum, o.uniques_minsize, buf, cap); });
+    if (trc == RTX_OK && p.tags_on) trc = format_two_pass(table, [&](char *buf, uint64_t cap) { return rtx_tally_format_table(sum, names.data(), o.uniques_minsize, buf, cap); });
+    if (trc != RTX_OK) { fprintf(stderr, "[ERROR] distinct reads: %s\n", rtx_last_error()); return 70; }
+    fprintf(stderr, "[INFO ] --uniques: %llu reads, %llu distinct\n", (ull)view.totals[0], (ull)view.totals[1]);
+    if (view.totals[2])
+        fprintf(stderr, "[INFO ] --uniques: %llu of %llu reads belong to sequences beyond the caps (--uniques-max-entries, --uniques-max-bytes) and are in no entry\n",
+                (ull)view.totals[2], (ull)view.totals[0]);
+    if (!write_whole(o.prefix + "/raxtax.uniques", fasta)) return 74;
+    if (p.tags_on && !write_whole(o.prefix + "/raxtax.uniques.tsv", table)) return 74;
+    if (o.otus) {
+        rtx_otu *otu = nullptr;
+        rtx_otu_view_t ov{};
+        std::string otu_fasta, otu_map, otu_table;
+        trc = rtx_otu_cluster(o.devices[0], sum, nullptr, &otu);
+        if (trc == RTX_OK) trc = rtx_otu_view(otu, &ov);
+        if (trc == RTX_OK) trc = format_two_pass(otu_fasta, [&](char *buf, uint64_t cap) { return rtx_otu_format_fasta(otu, sum, o.otus_minsize, buf, cap); });
+        if (trc == RTX_OK) trc = format_two_pass(otu_map, [&](char *buf, uint64_t cap) { return rtx_otu_format_map(otu, buf, cap); });
+        if (trc == RTX_OK && p.tags_on) trc = format_two_pass(otu_table, [&](char *buf, uint64_t cap) { return rtx_otu_format_table(otu, names.data(), o.otus_minsize, buf, cap); });
+        if (trc != RTX_OK) { fprintf(stderr, "[ERROR] OTUs: %s\n", rtx_last_error()); return 70; }
+        fprintf(stderr, "[INFO ] --otus: %llu distinct reads, %llu links, %llu OTUs, %u rounds\n", (ull)ov.n_rows, (ull)ov.n_links, (ull)ov.n_otus, ov.rounds);
+        if (ov.long_rows) fprintf(stderr, "[INFO ] --otus: %llu distinct reads are longer than %d bases and stand alone\n", (ull)ov.long_rows, RTX_OTU_MAX_LEN);
+        if (!write_whole(o.prefix + "/raxtax.otus", otu_fasta) || !write_whole(o.prefix + "/raxtax.otus.map", otu_map)) return 74;
+        if (p.tags_on && !write_whole(o.prefix + "/raxtax.otus.tsv", otu_table)) return 74;
+        rtx_otu_destroy(otu);
+    }
+    rtx_tally_table_destroy(sum);
+    for (rtx_tally_table *t : tables) rtx_tally_table_destroy(t);
+    return 0;
+}
+
+}  // namespace
+
+// The stages of a run, in order
+int main(int argc, char **argv) {
+    Laps laps;
+    Options o;
+    Plan plan;
+    if (const int rc = parse_args(argc, argv, o)) return rc;
+    if (const int rc = validate(o, plan)) return rc;
+    Sink sink;
+    const std::vector<Report> reports = report_table(o, plan, sink);
+
+    std::set<std::string> done;
+    bool resume = false;
+    if (const int rc = resume_or_start(o, plan, reports, done, resume)) return rc;
+
+    rtx_tree *tree = nullptr;
+    std::string db_bin;
+    if (const int rc = load_database(o, resume, laps, tree, db_bin)) return rc;
+    sink.tree = tree;
+    {
+        const std::string ckp_json = o.prefix + "/raxtax.json", tmp = ckp_json + ".tmp";  // Checkpoint::save: tmp + rename (io.rs:72-78)
+        std::ofstream f(tmp, std::ios::trunc);
+        f << plan.identity.json();
+        f.close();
+        rename(tmp.c_str(), ckp_json.c_str());
+    }
+    BinWriter bin;
+    if (o.only_db) {
+        bin.start(tree, db_bin);
+        const bool ok = bin.join();
+        laps.lap("database_cache");
+        if (o.timing) fprintf(stderr, "{%s}\n", laps.log.str().c_str());
+        return ok ? 0 : 74;
+    }
+
+    std::vector<const char *> skip;
+    for (const std::string &l : done) skip.push_back(l.c_str());
+    BlockQueue queue;
+    std::thread reader([&]() {
+        if (plan.merge_on) read_paired(o, skip, queue);
+        else read_single(o, plan.fastq, skip, queue);
+    });
+
+    std::vector<rtx_index *> indices(o.devices.size(), nullptr);
+    std::vector<rtx_tally *> tallies(o.uniques ? o.devices.size() : 0, nullptr);
+    if (!create_handles(o, plan, tree, indices, tallies)) {
+        queue.stop_and_join(reader);
+        return 71;  // exitcode::OSERR
+    }
+    rtx_screen_set_free(plan.contam_set);  // (the handles keep what they need)
+    plan.contam_set = nullptr;
+    laps.lap("index");
+    if (o.timing) {  // the handle's own verdict on tile pruning (rtx_index_self_sample: a property of the database)
+        int on = 1;
+        double share = -1.0;
+        if (rtx_index_prune_verdict(indices[0], &on, &share) == RTX_OK && share >= 0.0)
+            fprintf(stderr, "[TIMING] tile pruning %s: a sample of the database's own references keeps %.1f %% of its tiles live\n", on ? "on" : "off", 100.0 * share);
+    }
+    bin.start(tree, db_bin);  // after the index: rtx_index_create_from_tree looks at the tree's k-mer map
+
+    open_reports(o, plan, reports, sink, o.redo || !resume);
+
+    Totals tot[N_STAGES];
+    const bool stage_on[N_STAGES] = {plan.screen_on, plan.tags_on, !plan.primers.empty(), plan.qual_on, o.chim_on, o.derep, plan.merge_on};
+    for (int s = 0; s < N_STAGES; s++) tot[s].on = stage_on[s];
+    uint64_t n = 0;
+    bool parse_failed = false;
+    const int rc = classify_blocks(o, plan, queue, indices, tree, sink, tot, n, parse_failed);
+    queue.stop_and_join(reader);
     sink.out.flush();
     sink.ckp.flush();
-    if (tsv) sink.tsv.flush();
-    if (both_strands) sink.strand.flush();
-    if (want_hits) sink.hits.flush();
-    if (!primers.empty()) sink.trim.flush();
-    if (qual_on) sink.qc.flush();
-    if (merge_on) sink.merge.flush();
-    if (chim_on) sink.chimera.flush();
-    if (tags_on) sink.demux.flush();
-    if (screen_on) sink.screen.flush();
-    if (parse_failed) { join_bin_writer(); return 66; }
-    lap("classify_and_write");
-    if (merge_on) {
-        fprintf(stderr, "[INFO ] --reverse: %llu pairs, %llu merged; not merged for bad_quality %llu, too_long %llu, too_short %llu, no_overlap %llu\n", (unsigned long long)merge_total[0],
-                (unsigned long long)merge_total[1], (unsigned long long)merge_total[2], (unsigned long long)merge_total[3], (unsigned long long)merge_total[4], (unsigned long long)merge_total[5]);
-        if (timing) t_log << ", \"merge_busy\": " << merge_busy;
-    }
-    if (tags_on) {
-        fprintf(stderr, "[INFO ] --tags: %llu queries, %llu assigned to a sample; not assigned for no_tag5 %llu, no_tag3 %llu, ambiguous %llu, unknown_pair %llu\n",
-                (unsigned long long)demux_total[0], (unsigned long long)demux_total[1], (unsigned long long)demux_total[3], (unsigned long long)demux_total[4],
-                (unsigned long long)demux_total[5], (unsigned long long)demux_total[6]);
-        if (timing) t_log << ", \"demux_busy\": " << demux_busy;
-    }
-    if (!primers.empty()) {
-        fprintf(stderr, "[INFO ] --primers: %llu queries, %llu with a 5' primer, %llu with a 3' primer, %llu left empty\n", (unsigned long long)trim_total[0],
-                (unsigned long long)trim_total[1], (unsigned long long)trim_total[2], (unsigned long long)trim_total[3]);
-        if (timing) t_log << ", \"trim_busy\": " << trim_busy;
-    }
-    if (qual_on) {
-        fprintf(stderr, "[INFO ] quality filter: %llu queries, %llu passed (%llu of them cut short); discarded for bad_quality %llu, short_for_trunc_len %llu, too_short %llu, "
-                        "too_long %llu, too_many_n %llu, max_ee %llu, max_ee_rate %llu\n", (unsigned long long)qual_total[0], (unsigned long long)qual_total[1],
-                (unsigned long long)qual_total[2], (unsigned long long)qual_total[3], (unsigned long long)qual_total[4], (unsigned long long)qual_total[5],
-                (unsigned long long)qual_total[6], (unsigned long long)qual_total[7], (unsigned long long)qual_total[8], (unsigned long long)qual_total[9]);
-        if (timing) t_log << ", \"qual_busy\": " << qual_busy;
-    }
-    if (screen_on) {
-        fprintf(stderr, "[INFO ] --contaminants: %llu queries, %llu screened, %llu contaminants\n", (unsigned long long)screen_total[0], (unsigned long long)screen_total[1],
-                (unsigned long long)screen_total[2]);
-        if (timing) t_log << ", \"screen_busy\": " << screen_busy;
-    }
-    if (chim_on) {
-        fprintf(stderr, "[INFO ] --chimera: %llu queries, %llu reads checked, %llu queries flagged\n", (unsigned long long)chim_total[0], (unsigned long long)chim_total[1],
-                (unsigned long long)chim_total[2]);
-        if (timing) t_log << ", \"chimera_busy\": " << chim_busy;
-    }
-    if (derep) {  // (per chunk: a copy in another chunk counts as a distinct read of its own)
-        fprintf(stderr, "[INFO ] --derep: %llu queries, %llu distinct\n", (unsigned long long)derep_queries, (unsigned long long)derep_distinct);
-        if (timing) t_log << ", \"derep_busy\": " << derep_busy;
-    }
-    if (!join_bin_writer()) return 74;
-    lap("database_cache_wait");
-    if (timing) fprintf(stderr, "{\"n_queries\": %llu, %s}\n", (unsigned long long)n, t_log.str().c_str());
+    if (o.tsv) sink.tsv.flush();
+    for (const Report &r : reports)
+        if (r.on) r.stream->flush();
+    if (parse_failed) { bin.join(); return 66; }
+    laps.lap("classify_and_write");
+
+    print_totals(o, tot, laps);
+    if (!bin.join()) return 74;
+    laps.lap("database_cache_wait");
+    if (o.timing) fprintf(stderr, "{\"n_queries\": %llu, %s}\n", (ull)n, laps.log.str().c_str());
     if (rc != RTX_OK) {
         fprintf(stderr, "[ERROR] %s\nRerun raxtax-hip to continue from the last checkpoint.\n", rtx_last_error());
         return rc == RTX_ERR_SENDER ? 75 : 70;  // exitcode::TEMPFAIL / SOFTWARE
     }
-    if (profile_cutoff) {  // the taxon profile of the whole run: the sum over the handles, written once
-        std::vector<rtx_profile_view> views(indices.size());
-        std::vector<rtx_profile_view *> ptrs(indices.size());
-        int prc = RTX_OK;
-        for (size_t k = 0; k < indices.size() && prc == RTX_OK; k++) {
-            prc = rtx_index_profile_read(indices[k], &views[k]);
-            ptrs[k] = &views[k];
-        }
-        std::vector<uint64_t> acc(prc == RTX_OK ? 3 * (size_t)views[0].n_nodes : 0);
-        uint64_t totals[4] = {0, 0, 0, 0};
-        const size_t nn = prc == RTX_OK ? views[0].n_nodes : 0;
-        if (prc == RTX_OK) prc = rtx_profile_merge(ptrs.data(), (uint32_t)ptrs.size(), acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals);
-        std::string text;
-        if (prc == RTX_OK) {
-            const int64_t need = rtx_profile_format(tree, acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals, profile_cutoff, nullptr, 0);
-            if (need < 0) prc = (int)need;
-            else {
-                text.resize((size_t)need);
-                const int64_t got = rtx_profile_format(tree, acc.data(), acc.data() + nn, acc.data() + 2 * nn, totals, profile_cutoff, &text[0], text.size());
-                if (got != need) prc = got < 0 ? (int)got : RTX_ERR_STATE;
-            }
-        }
-        if (prc != RTX_OK) { fprintf(stderr, "[ERROR] taxon profile: %s\n", rtx_last_error()); return 70; }
-        std::ofstream pf(profile_path, std::ios::trunc);
-        pf << text;
-        pf.close();
-        if (!pf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", profile_path.c_str()); return 74; }
-    }
-    if (profile_cutoff && tags_on) {  // ... and the taxon x sample table beside it: the per-sample counters summed over the handles
-        std::vector<rtx_sample_profile_view> views(indices.size());
-        std::vector<rtx_sample_profile_view *> ptrs(indices.size());
-        int prc = RTX_OK;
-        for (size_t k = 0; k < indices.size() && prc == RTX_OK; k++) {
-            prc = rtx_index_profile_read_samples(indices[k], &views[k]);
-            ptrs[k] = &views[k];
-        }
-        const size_t nn = prc == RTX_OK ? views[0].n_nodes : 0, ns = sample_names.size();
-        std::vector<uint64_t> direct(ns * nn + 1), totals(ns * 4);
-        if (prc == RTX_OK) prc = rtx_sample_profile_merge(ptrs.data(), (uint32_t)ptrs.size(), direct.data(), totals.data());
-        std::vector<const char *> names;
-        for (const std::string &s : sample_names) names.push_back(s.c_str());
-        std::string text;
-        if (prc == RTX_OK) {
-            const int64_t need = rtx_sample_table_format(tree, (uint32_t)ns, names.data(), direct.data(), totals.data(), profile_cutoff, nullptr, 0);
-            if (need < 0) prc = (int)need;
-            else {
-                text.resize((size_t)need);
-                const int64_t got = rtx_sample_table_format(tree, (uint32_t)ns, names.data(), direct.data(), totals.data(), profile_cutoff, &text[0], text.size());
-                if (got != need) prc = got < 0 ? (int)got : RTX_ERR_STATE;
-            }
-        }
-        if (prc != RTX_OK) { fprintf(stderr, "[ERROR] sample table: %s\n", rtx_last_error()); return 70; }
-        std::ofstream sf(samples_path, std::ios::trunc);
-        sf << text;
-        sf.close();
-        if (!sf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", samples_path.c_str()); return 74; }
-    }
-    if (uniques) {  // the distinct reads of the whole run: the tables of the handles' objects read, summed and written once
-        std::vector<rtx_tally_table *> tables(tallies.size(), nullptr);
-        rtx_tally_table *sum = nullptr;
-        int trc = RTX_OK;
-        for (size_t k = 0; k < tallies.size() && trc == RTX_OK; k++) trc = rtx_tally_read(tallies[k], &tables[k]);
-        if (trc == RTX_OK) trc = rtx_tally_table_merge(tables.data(), (uint32_t)tables.size(), &sum);
-        rtx_tally_view view{};
-        if (trc == RTX_OK) trc = rtx_tally_table_view(sum, &view);
-        std::vector<const char *> names;
-        for (const std::string &s : sample_names) names.push_back(s.c_str());
-        std::string fasta, table;
-        auto format = [&](std::string &text, auto fn) {  // the two-pass protocol of the formatters
-            const int64_t need = fn(nullptr, 0);
-            if (need < 0) { trc = (int)need; return; }
-            text.resize((size_t)need);
-            const int64_t got = fn(&text[0], text.size());
-            if (got != need) trc = got < 0 ? (int)got : RTX_ERR_STATE;
-        };
-        if (trc == RTX_OK) format(fasta, [&](char *buf, uint64_t cap) { return rtx_tally_format_fasta(sum, uniques_minsize, buf, cap); });
-        if (trc == RTX_OK && tags_on) format(table, [&](char *buf, uint64_t cap) { return rtx_tally_format_table(sum, names.data(), uniques_minsize, buf, cap); });
-        if (trc != RTX_OK) { fprintf(stderr, "[ERROR] distinct reads: %s\n", rtx_last_error()); return 70; }
-        fprintf(stderr, "[INFO ] --uniques: %llu reads, %llu distinct\n", (unsigned long long)view.totals[0], (unsigned long long)view.totals[1]);
-        if (view.totals[2])
-            fprintf(stderr, "[INFO ] --uniques: %llu of %llu reads belong to sequences beyond the caps (--uniques-max-entries, --uniques-max-bytes) and are in no entry\n",
-                    (unsigned long long)view.totals[2], (unsigned long long)view.totals[0]);
-        std::ofstream uf(uniques_path, std::ios::trunc);
-        uf << fasta;
-        uf.close();
-        if (!uf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", uniques_path.c_str()); return 74; }
-        if (tags_on) {
-            std::ofstream tf(uniques_table_path, std::ios::trunc);
-            tf << table;
-            tf.close();
-            if (!tf.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", uniques_table_path.c_str()); return 74; }
-        }
-        if (otus) {  // the OTUs of the run: the summed table, whole, clustered on the first device
-            rtx_otu *o = nullptr;
-            rtx_otu_view_t ov{};
-            std::string otu_fasta, otu_map, otu_table;
-            trc = rtx_otu_cluster(devices[0], sum, nullptr, &o);
-            if (trc == RTX_OK) trc = rtx_otu_view(o, &ov);
-            if (trc == RTX_OK) format(otu_fasta, [&](char *buf, uint64_t cap) { return rtx_otu_format_fasta(o, sum, otus_minsize, buf, cap); });
-            if (trc == RTX_OK) format(otu_map, [&](char *buf, uint64_t cap) { return rtx_otu_format_map(o, buf, cap); });
-            if (trc == RTX_OK && tags_on) format(otu_table, [&](char *buf, uint64_t cap) { return rtx_otu_format_table(o, names.data(), otus_minsize, buf, cap); });
-            if (trc != RTX_OK) { fprintf(stderr, "[ERROR] OTUs: %s\n", rtx_last_error()); return 70; }
-            fprintf(stderr, "[INFO ] --otus: %llu distinct reads, %llu links, %llu OTUs, %u rounds\n", (unsigned long long)ov.n_rows, (unsigned long long)ov.n_links,
-                    (unsigned long long)ov.n_otus, ov.rounds);
-            if (ov.long_rows)
-                fprintf(stderr, "[INFO ] --otus: %llu distinct reads are longer than %d bases and stand alone\n", (unsigned long long)ov.long_rows, RTX_OTU_MAX_LEN);
-            const std::pair<const std::string *, const std::string *> files[] = {{&otus_path, &otu_fasta}, {&otus_map_path, &otu_map}, {&otus_table_path, &otu_table}};
-            for (size_t k = 0; k < (tags_on ? 3u : 2u); k++) {
-                std::ofstream of(*files[k].first, std::ios::trunc);
-                of << *files[k].second;
-                of.close();
-                if (!of.good()) { fprintf(stderr, "[ERROR] cannot write %s\n", files[k].first->c_str()); return 74; }
-            }
-            rtx_otu_destroy(o);
-        }
-        rtx_tally_table_destroy(sum);
-        for (rtx_tally_table *t : tables) rtx_tally_table_destroy(t);
-    }
-    if (clean) {  // Checkpoint::cleanup (io.rs:80-89)
-        remove(ckp_json.c_str());
-        remove(ckp_path.c_str());
+
+    if (o.profile_cutoff)
+        if (const int wrc = write_profile(o, indices, tree)) return wrc;
+    if (o.profile_cutoff && plan.tags_on)
+        if (const int wrc = write_sample_table(o, plan, indices, tree)) return wrc;
+    if (o.uniques)
+        if (const int wrc = write_uniques_and_otus(o, plan, tallies)) return wrc;
+
+    if (o.clean) {  // Checkpoint::cleanup (io.rs:80-89)
+        remove((o.prefix + "/raxtax.json").c_str());
+        remove((o.prefix + "/raxtax.ckp").c_str());
         if (!db_bin.empty()) remove(db_bin.c_str());
     }
     for (rtx_index *ix : indices) rtx_index_destroy(ix);
