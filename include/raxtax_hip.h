@@ -53,7 +53,8 @@ extern "C" {
                                 rtx_index_tags / rtx_raxtax_last_demux / rtx_raxtax_multi_ex7 and the per-sample counters
                                 rtx_index_profile_begin_samples / _read_samples / rtx_batch_prefetch_samples / rtx_sample_profile_merge /
                                 rtx_sample_table_format: the same; and with the contaminant screen, rtx_screen_* / rtx_index_set_screen /
-                                rtx_index_screen / rtx_raxtax_last_screen / rtx_raxtax_multi_ex8: the same) */
+                                rtx_index_screen / rtx_raxtax_last_screen / rtx_raxtax_multi_ex8: the same; and with the de novo chimera check of a
+                                run, rtx_denovo_*: exports only) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -1145,6 +1146,82 @@ int rtx_chimera_read(const rtx_chimera_params *params, const uint8_t *read, uint
                      uint64_t n_refs, rtx_chimera_rec *rec);
 int rtx_index_set_chimera(rtx_index *index, const rtx_chimera_params *params);
 int rtx_index_chimera(const rtx_index *index, rtx_chimera_params *params, int *on);
+
+/* ---- de novo chimera check of a run (rtx_denovo.hip, host_denovo.cpp) ------------------------------------------------------------------
+ * Is a sequence of the run the head of one MORE ABUNDANT sequence of the same run joined to the tail of another?  What
+ * `vsearch --uchime_denovo` and DADA2's removeBimeraDenovo answer between clustering and the final table; the check above only knows the
+ * templates the database holds.  Exact, integers only, independent of scheduling; the host function and the device agree in every field.
+ *   input        an rtx_tally_table, optionally the rtx_otu made from it, and the parameters: segments S (2 .. 32, default 16) and
+ *                mindelta (default 24) as in rtx_chimera_params; abskew (an integer >= 1, RTX_DENOVO_DEFAULT_ABSKEW); max_parents
+ *                (0: RTX_DENOVO_DEFAULT_MAX_PARENTS, which is also the most); flags (0).  params == NULL: the defaults.
+ *   entries      without an OTU object every row of the table, weight = the row's total size, in table order.  With one: the seeds,
+ *                weight = the OTU's total size, ordered by (weight descending, seed rank ascending).  Entry e has the sequence seq[e], the
+ *                weight w[e] and the table rank row[e] (and, with an OTU object, the OTU otu[e]).
+ *   parents      of e: the entries p < lim(e) that are not themselves flagged, lim(e) = min(e, #{p : w[p] >= abskew w[e]}, max_parents).
+ *                Weights never increase along the list, so the set in the middle is a prefix; `e` keeps an entry from being its own
+ *                parent when abskew = 1.
+ *   record       of e: the record of rtx_chimera_read above with seq[e] as the read and the live parents as the references: the same
+ *                windows, x_p[i] = window i valid and its 8-mer anywhere in p, the same b_s, P, Suf, single, two[s], seg (the lowest s
+ *                with the largest two), delta, the lowest parent among equals, flag = delta >= mindelta.  Parent ids are ENTRY indices;
+ *                RTX_NO_REF where a count is 0.
+ *   status       RTX_CHIM_TOO_LONG (more than RTX_CHIMERA_MAX_QUERY bases: not checked, but still a parent of others), else
+ *                RTX_CHIM_NO_KMER (no valid window), else RTX_DENOVO_NO_PARENT when lim(e) = 0 -- each of them with everything 0 or
+ *                RTX_NO_REF and not flagged -- else RTX_CHIM_OK.
+ *   recursion    e's record depends on the flags of entries below lim(e) <= e only: the definition is a recursion over e = 0, 1, ... and
+ *                has exactly one solution.  That a flagged sequence is no parent (uchime's greedy rule) is part of the definition: without
+ *                it a rarer variant of a chimera, two or more differences away from it, is "explained" by the chimera and passes.
+ *   rtx_denovo_check       on GPU `device` (RTX_ERR_NO_DEVICE without a gfx950), in an object made and released inside the call.  The stage
+ *                builds a bitmap of its own over the entries below the largest lim -- the index's layout, one row per 8-mer, the zero
+ *                row, and one more row that holds the live mask: 64 MiB + 2 KiB per tile of 8192 entries -- and scans entry e against the
+ *                tiles below lim(e) only, the planes ANDed at every checkpoint with the live mask and the prefix mask of lim(e).  Round 1
+ *                scans every entry with all parents live; after a round the new flags are compared with the old ones, the live mask is
+ *                rewritten, and the next round scans exactly the entries e with lim(e) > the lowest entry whose flag changed.  It ends
+ *                with a round that changed nothing (a round with nothing to scan is one): the solution of the recursion.  `rounds` counts
+ *                them, `scans` the entries handed to the rounds, summed.
+ *   rtx_denovo_check_host  the definition restated literally: a set of 8-mers per parent, e ascending, explicit parent lists.  Equal to the
+ *                device's result field by field, except rounds (1), scans (the entries) and the times.
+ *                RTX_ERR_INVALID: S out of range, abskew 0, flags != 0, max_parents above the default, an OTU object whose row count is
+ *                not the table's, more than 2^31 - 2 entries.  The table is laid out (rtx_tally_table_view) and otherwise unchanged.
+ *   rtx_denovo_view        valid until the object is destroyed; otu is NULL without an OTU object.  n_checked: the entries with RTX_CHIM_OK.
+ *                rtx_denovo_times: seconds of upload and bitmap, the scan kernels of all rounds (from HIP events around them), the rounds'
+ *                bookkeeping (row lists, reductions, flag updates, read-backs), the download; 0 for a host result.
+ *   rtx_denovo_format_records  `#entry\tweight\tstatus\twindows\tsingle\tparent\tseg\tpos\tleft\ta\tright\tb\tdelta\tchimera\n`, then one
+ *                line per entry: `otu{k}` (k from 1) or `uniq{rank}` (from 1), the weight, status as a number, n_valid, single, parent,
+ *                seg, pos, left, parent_a, right, parent_b, delta, and Y (flagged), N (RTX_CHIM_OK, not flagged) or ? (not checked).
+ *                Parents are named like the entry; RTX_NO_REF is `*`.  Buffer protocol of rtx_tally_format_fasta.
+ *   rtx_denovo_format_fasta    the lines of rtx_otu_format_fasta (with an OTU object) or rtx_tally_format_fasta of the entries that are not
+ *                flagged and whose weight is at least minsize, in the order of those functions; the numbers stay.  `table` as in rtx_otu_format_fasta.
+ *   rtx_denovo_format_table    the same selection of rtx_otu_format_table / rtx_tally_format_table (`otu` NULL without an OTU object). */
+#define RTX_DENOVO_NO_PARENT 3u
+#define RTX_DENOVO_DEFAULT_ABSKEW 2u
+#define RTX_DENOVO_DEFAULT_MAX_PARENTS 262144u
+typedef struct rtx_denovo rtx_denovo;
+typedef struct rtx_denovo_params {
+    uint32_t segments;    /* 2 .. RTX_CHIMERA_MAX_SEGMENTS */
+    uint32_t mindelta;
+    uint32_t abskew;      /* >= 1 */
+    uint32_t max_parents; /* 0: RTX_DENOVO_DEFAULT_MAX_PARENTS */
+    uint32_t flags;       /* 0 */
+} rtx_denovo_params;
+typedef struct rtx_denovo_view_t {
+    uint64_t n_entries;
+    const uint32_t *row;        /* [n_entries] the table rank of an entry */
+    const uint32_t *otu;        /* [n_entries] its OTU, or NULL */
+    const uint64_t *weight;     /* [n_entries] */
+    const uint32_t *lim;        /* [n_entries] */
+    const rtx_chimera_rec *rec; /* [n_entries] */
+    uint64_t n_checked, n_flagged;
+    uint32_t rounds;
+    uint64_t scans;
+} rtx_denovo_view_t;
+int rtx_denovo_check(int device, rtx_tally_table *table, rtx_otu *otu_or_null, const rtx_denovo_params *params, rtx_denovo **out);
+int rtx_denovo_check_host(rtx_tally_table *table, rtx_otu *otu_or_null, const rtx_denovo_params *params, rtx_denovo **out);
+int rtx_denovo_view(rtx_denovo *d, rtx_denovo_view_t *view);
+int rtx_denovo_times(const rtx_denovo *d, double seconds[4]);
+void rtx_denovo_destroy(rtx_denovo *d);
+int64_t rtx_denovo_format_records(rtx_denovo *d, char *buf, uint64_t cap);
+int64_t rtx_denovo_format_fasta(rtx_denovo *d, rtx_tally_table *table, rtx_otu *otu_or_null, uint64_t minsize, char *buf, uint64_t cap);
+int64_t rtx_denovo_format_table(rtx_denovo *d, rtx_tally_table *table, rtx_otu *otu_or_null, const char *const *names, uint64_t minsize, char *buf, uint64_t cap);
 
 /* ---- result text produced on the device (rtx_text.hip) ------------------------------------------------------------------------------
  * The `.out` lines, and with RTX_TEXT_TSV the `.tsv` lines, of every query of a download, formatted by kernels behind the final rows: byte

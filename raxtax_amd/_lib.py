@@ -46,6 +46,9 @@ RTX_MG_NAMES = ("bad_quality", "too_long", "too_short", "no_overlap")   # bit b 
 
 RTX_CHIMERA_MAX_QUERY, RTX_CHIMERA_MAX_SEGMENTS, RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA = 4096, 32, 16, 24
 RTX_CHIM_OK, RTX_CHIM_NO_KMER, RTX_CHIM_TOO_LONG = 0, 1, 2
+RTX_DENOVO_NO_PARENT = 3           # rtx_chimera_rec.status of an entry without a parent prefix (rtx_denovo_check)
+RTX_DENOVO_DEFAULT_ABSKEW = 2
+RTX_DENOVO_DEFAULT_MAX_PARENTS = 262144
 RTX_CHIM_FIELDS = ("status", "n_valid", "single", "parent", "seg", "pos", "left", "parent_a", "right", "parent_b", "delta", "flag")   # rtx_chimera_rec: twelve uint32
 
 u8p = C.POINTER(C.c_uint8)
@@ -124,6 +127,10 @@ class OtuView(C.Structure):   # rtx_otu_view_t
                 ("n_links", C.c_uint64), ("link_a", u32p), ("link_b", u32p), ("rounds", C.c_uint32), ("link_passes", C.c_uint32), ("long_rows", C.c_uint64)]
 
 
+class DenovoParams(C.Structure):   # rtx_denovo_params
+    _fields_ = [("segments", C.c_uint32), ("mindelta", C.c_uint32), ("abskew", C.c_uint32), ("max_parents", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class MergeParams(C.Structure):   # rtx_merge_params
     _fields_ = [("ascii_base", C.c_uint32), ("min_overlap", C.c_uint32), ("max_diffs", C.c_uint32), ("max_diff_pct", C.c_uint32), ("q_cap", C.c_uint32)]
 
@@ -134,6 +141,11 @@ class ChimeraParams(C.Structure):   # rtx_chimera_params
 
 class ChimeraRec(C.Structure):   # rtx_chimera_rec
     _fields_ = [(f, C.c_uint32) for f in RTX_CHIM_FIELDS]
+
+
+class DenovoView(C.Structure):   # rtx_denovo_view_t
+    _fields_ = [("n_entries", C.c_uint64), ("row", u32p), ("otu", u32p), ("weight", u64p), ("lim", u32p), ("rec", C.POINTER(ChimeraRec)), ("n_checked", C.c_uint64),
+                ("n_flagged", C.c_uint64), ("rounds", C.c_uint32), ("scans", C.c_uint64)]
 
 
 class RtxError(RuntimeError):
@@ -322,6 +334,14 @@ _SIGNATURES = {
     "rtx_otu_format_fasta": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
     "rtx_otu_format_table": (C.c_int64, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64]),
     "rtx_otu_format_map": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "rtx_denovo_check": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DenovoParams), C.POINTER(C.c_void_p)]),
+    "rtx_denovo_check_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenovoParams), C.POINTER(C.c_void_p)]),
+    "rtx_denovo_view": (C.c_int, [C.c_void_p, C.POINTER(DenovoView)]),
+    "rtx_denovo_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rtx_denovo_destroy": (None, [C.c_void_p]),
+    "rtx_denovo_format_records": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "rtx_denovo_format_fasta": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_denovo_format_table": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64]),
     "rtx_index_set_tally": (C.c_int, [C.c_void_p, C.c_void_p]),
     "rtx_index_tally": (C.c_void_p, [C.c_void_p]),
     "rtx_raxtax_last_tally": (C.c_int, [u64p, u64p, u64p, C.POINTER(C.c_double)]),

@@ -2008,6 +2008,103 @@ def otu_map_text(otus: Otus) -> str:
     return _otu_text(_lib.load().rtx_otu_format_map, otus)
 
 
+class DenovoParams:
+    """rtx_denovo_params: segments S (2 .. 32) and mindelta as ChimeraParams, abskew (an integer >= 1: a parent is at least abskew times as
+    abundant as the entry), max_parents (0: the default, 262 144, which is also the most), flags (0)."""
+
+    def __init__(self, segments: int = 16, mindelta: int = 24, abskew: int = _lib.RTX_DENOVO_DEFAULT_ABSKEW, max_parents: int = 0, flags: int = 0):
+        self.segments, self.mindelta, self.abskew, self.max_parents, self.flags = int(segments), int(mindelta), int(abskew), int(max_parents), int(flags)
+
+    def _c(self):
+        return C.byref(_lib.DenovoParams(self.segments, self.mindelta, self.abskew, self.max_parents, self.flags))
+
+
+class Denovo:
+    """The de novo chimera check of a run (rtx_denovo), by denovo_check() on a GPU or denovo_check_host().
+      row      [entries] the table rank of an entry          otu     [entries] its OTU, or None without an Otus object
+      weight   [entries]                                     lim     [entries] the entries below it are its candidate parents
+      rec      [entries] structured array of the twelve fields of rtx_chimera_rec; parents are entry indices
+      n_checked, n_flagged, rounds, scans; seconds: upload and bitmap, scans, the rounds' bookkeeping, download of a device run"""
+
+    def __init__(self, handle, table: "TallyTable", otus: Optional["Otus"]):
+        self._lib = _lib.load()
+        self._h = handle
+        self.table, self.otus = table, otus   # (the formatters read them)
+        v = _lib.DenovoView()
+        check(self._lib.rtx_denovo_view(self._h, C.byref(v)))
+        n = int(v.n_entries)
+
+        def arr(p, dtype):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype)
+
+        self.n_entries = n
+        self.row = arr(v.row, np.uint32)
+        self.otu = arr(v.otu, np.uint32) if v.otu else None
+        self.weight = arr(v.weight, np.uint64)
+        self.lim = arr(v.lim, np.uint32)
+        dt = np.dtype([(f, np.uint32) for f in _lib.RTX_CHIM_FIELDS])
+        self.rec = np.frombuffer(C.string_at(v.rec, n * 48), dtype=dt).copy() if n else np.zeros(0, dt)
+        self.n_checked, self.n_flagged, self.rounds, self.scans = int(v.n_checked), int(v.n_flagged), int(v.rounds), int(v.scans)
+        t = (C.c_double * 4)()
+        check(self._lib.rtx_denovo_times(self._h, t))
+        self.seconds = tuple(float(x) for x in t)
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_denovo_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _denovo_params(params):
+    p = params.pop("params", None)
+    if p is not None and params:
+        raise TypeError("either params or keyword parameters")
+    return (p if p is not None else DenovoParams(**params))._c()
+
+
+def denovo_check(table: TallyTable, otus: Optional[Otus] = None, device: int = 0, **params) -> Denovo:
+    """rtx_denovo_check: the de novo chimera check of the table's rows, or of the seeds of `otus` (made from this table), on GPU `device`.
+    params: those of DenovoParams, or params=DenovoParams(...)."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_denovo_check(int(device), table._h, otus._h if otus is not None else None, _denovo_params(params), C.byref(h)))
+    return Denovo(h, table, otus)
+
+
+def denovo_check_host(table: TallyTable, otus: Optional[Otus] = None, **params) -> Denovo:
+    """rtx_denovo_check_host: the same from the definition, on the host."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_denovo_check_host(table._h, otus._h if otus is not None else None, _denovo_params(params), C.byref(h)))
+    return Denovo(h, table, otus)
+
+
+def _denovo_text(fn, d, *args) -> str:
+    n = check(fn(d._h, *args, None, 0))
+    buf = C.create_string_buffer(max(n, 1))
+    check(fn(d._h, *args, buf, n))
+    return buf.raw[:n].decode()
+
+
+def denovo_records_text(d: Denovo) -> str:
+    """rtx_denovo_format_records: a header line and one line per entry (PREFIX/raxtax.otus.denovo of raxtax-hip --denovo)."""
+    return _denovo_text(_lib.load().rtx_denovo_format_records, d)
+
+
+def denovo_fasta(d: Denovo, minsize: int = 1) -> str:
+    """rtx_denovo_format_fasta: the lines of otu_fasta() / tally_fasta() of the entries that are not flagged (PREFIX/raxtax.otus.clean)."""
+    return _denovo_text(_lib.load().rtx_denovo_format_fasta, d, d.table._h, d.otus._h if d.otus is not None else None, int(minsize))
+
+
+def denovo_table_text(d: Denovo, names: Sequence[str], minsize: int = 1) -> str:
+    """rtx_denovo_format_table: the same selection of otu_table_text() / tally_table_text() (PREFIX/raxtax.otus.clean.tsv)."""
+    if len(names) != d.table.columns:
+        raise ValueError(f"{len(names)} names for {d.table.columns} column(s)")
+    arr = (C.c_char_p * len(names))(*[s.encode() for s in names])
+    return _denovo_text(_lib.load().rtx_denovo_format_table, d, d.table._h, d.otus._h if d.otus is not None else None, arr, int(minsize))
+
+
 def raxtax_last_tally() -> Tuple[int, int, int, float]:
     """rtx_raxtax_last_tally: (queries of the tallied chunks, those that counted, entries the objects gained, busy seconds of the stage) of
     the last raxtax() call of this process; all 0 when its handles had no tally."""

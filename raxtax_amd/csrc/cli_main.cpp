@@ -21,6 +21,10 @@
 //    uniques): `>otu{k};size={N};seed=uniq{rank}` and the seed's sequence (rtx_otu_format_fasta); PREFIX/raxtax.otus.map, `uniq{rank}\totu{k}` per
 //    distinct read; with --tags also PREFIX/raxtax.otus.tsv, the OTU x sample table of read counts.  OTUs below N (default 1) are left out of
 //    raxtax.otus and raxtax.otus.tsv, the numbers stay.
+//   PREFIX/raxtax.otus.denovo (--uniques --otus --denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]) the de novo chimera check of the
+//    OTUs on the first device (rtx_denovo.hip), right after the clustering: is an OTU's seed the head of one more abundant OTU of the run joined to the tail
+//    of another?  A header line and one line per OTU (rtx_denovo_format_records); PREFIX/raxtax.otus.clean, the lines of raxtax.otus of the OTUs that
+//    are not flagged (under --otus-minsize); with --tags also PREFIX/raxtax.otus.clean.tsv.  raxtax.otus, .map and .tsv are what they are without it.
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
 //   PREFIX/raxtax.demux (--tags SHEET) and PREFIX/raxtax.samples (with --profile as well): below
 //   (--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]: every read is assigned to a sample by the inline tags at
@@ -247,6 +251,9 @@ struct Options {
     bool otus = false;            // --otus: the table of --uniques clustered into OTUs (rtx_otu.hip), PREFIX/raxtax.otus, raxtax.otus.map (and raxtax.otus.tsv with --tags)
     uint64_t otus_minsize = 1;    // --otus-minsize N
     std::string otus_opts;        // that one, likewise
+    bool denovo = false;          // --denovo: the OTUs checked for chimeras of more abundant OTUs (rtx_denovo.hip), PREFIX/raxtax.otus.denovo, raxtax.otus.clean (and .clean.tsv with --tags)
+    rtx_denovo_params denovo_params{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA, RTX_DENOVO_DEFAULT_ABSKEW, 0, 0};  // --denovo-segments S, --denovo-mindelta N, --denovo-abskew N
+    std::string denovo_opts;      // those three, likewise
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;             // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (classify_blocks)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -281,6 +288,9 @@ int parse_args(int argc, char **argv, Options &o) {
         {"--uniques-max-entries", 'p', 1, 0x7FFFFFFE, &o.uniques_max_entries, &o.uniques_opts},
         {"--uniques-max-bytes", 'p', 1, LLONG_MAX, &o.uniques_max_bytes, &o.uniques_opts},
         {"--otus-minsize", 'p', 1, LLONG_MAX, &o.otus_minsize, &o.otus_opts},
+        {"--denovo-abskew", 'u', 1, 0x7FFFFFFF, &o.denovo_params.abskew, &o.denovo_opts},
+        {"--denovo-mindelta", 'u', 0, RTX_CHIMERA_MAX_QUERY, &o.denovo_params.mindelta, &o.denovo_opts},
+        {"--denovo-segments", 'u', 2, RTX_CHIMERA_MAX_SEGMENTS, &o.denovo_params.segments, &o.denovo_opts},
     };
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
@@ -388,11 +398,12 @@ int parse_args(int argc, char **argv, Options &o) {
         }
         else if (a == "--uniques") o.uniques = true;
         else if (a == "--otus") o.otus = true;
+        else if (a == "--denovo") o.denovo = true;
         else if (a == "--batch") o.chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") o.block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N]]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -425,6 +436,7 @@ struct Identity {
         {"contaminants", true, ""},   // --contaminants with its settings and the set's fingerprint: contaminants have no lines
         {"uniques", true, ""},        // --uniques with its settings: the table is the run's, a resumed run would miss reads
         {"otus", true, ""},           // --otus with its setting: its files are the run's
+        {"denovo", true, ""},         // --denovo with its three settings, likewise
     };
     std::string &operator[](const std::string &key) {
         for (Entry &e : entries)
@@ -668,6 +680,10 @@ int validate(Options &o, Plan &p) {
     if (orphan(o.otus ? "--otus" : "", o.uniques, "clusters the distinct reads of the run and needs --uniques")) return 64;
     if (o.uniques) id["uniques"] = "minsize=" + std::to_string(o.uniques_minsize) + " max_entries=" + std::to_string(o.uniques_max_entries) + " max_bytes=" + std::to_string(o.uniques_max_bytes);
     if (o.otus) id["otus"] = "minsize=" + std::to_string(o.otus_minsize);
+    if (orphan(o.denovo_opts, o.denovo, "sets how the OTUs are checked for chimeras and needs --denovo")) return 64;
+    if (orphan(o.denovo ? "--denovo" : "", o.otus, "checks the OTUs of the run for chimeras and needs --otus")) return 64;
+    if (o.denovo)
+        id["denovo"] = "abskew=" + std::to_string(o.denovo_params.abskew) + ";mindelta=" + std::to_string(o.denovo_params.mindelta) + ";segments=" + std::to_string(o.denovo_params.segments);
     const char *const on_host = o.derep ? "--derep" : (o.both_strands ? "--strand both" : nullptr);
     if (o.device_format && on_host) {
         fprintf(stderr, "[INFO ] %s: the result lines are formatted on the host (--device-format has no effect)\n", on_host);
@@ -710,8 +726,9 @@ std::vector<Report> report_table(const Options &o, const Plan &p, Sink &s) {
             {"raxtax.screen", p.screen_on, "label\tlength\twindows\thits\tfirst\tsource\tverdict\n", &s.screen}};
 }
 
-// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus): a run that starts over removes them
-const char *const kEndOfRunFiles[] = {"raxtax.profile", "raxtax.samples", "raxtax.uniques", "raxtax.uniques.tsv", "raxtax.otus", "raxtax.otus.map", "raxtax.otus.tsv"};
+// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --denovo): a run that starts over removes them
+const char *const kEndOfRunFiles[] = {"raxtax.profile", "raxtax.samples", "raxtax.uniques", "raxtax.uniques.tsv", "raxtax.otus", "raxtax.otus.map", "raxtax.otus.tsv",
+                                      "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv"};
 
 // check_incomplete_output (io.rs:156-187): keep only the lines whose first field is a finished query
 void purge_incomplete(const std::string &path, const std::set<std::string> &done, bool keep_header = false) {
@@ -1333,8 +1350,21 @@ int write_sample_table(const Options &o, const Plan &p, const std::vector<rtx_in
 // --uniques: the distinct reads of the whole run: the tables of the handles' objects read, summed and written once;
 // --otus: the summed table, whole, clustered on the first device
 int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rtx_tally *> &tallies) {
-    std::vector<rtx_tally_table *> tables(tallies.size(), nullptr);
-    rtx_tally_table *sum = nullptr;
+    struct Owned {  // what the function makes, released on every way out
+        std::vector<rtx_tally_table *> tables;
+        rtx_tally_table *sum = nullptr;
+        rtx_otu *otu = nullptr;
+        rtx_denovo *dn = nullptr;
+        ~Owned() {
+            rtx_denovo_destroy(dn);
+            rtx_otu_destroy(otu);
+            rtx_tally_table_destroy(sum);
+            for (rtx_tally_table *t : tables) rtx_tally_table_destroy(t);
+        }
+    } own;
+    own.tables.assign(tallies.size(), nullptr);
+    std::vector<rtx_tally_table *> &tables = own.tables;
+    rtx_tally_table *&sum = own.sum;
     int trc = RTX_OK;
     for (size_t k = 0; k < tallies.size() && trc == RTX_OK; k++) trc = rtx_tally_read(tallies[k], &tables[k]);
     if (trc == RTX_OK) trc = rtx_tally_table_merge(tables.data(), (uint32_t)tables.size(), &sum);
@@ -1353,7 +1383,7 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
     if (!write_whole(o.prefix + "/raxtax.uniques", fasta)) return 74;
     if (p.tags_on && !write_whole(o.prefix + "/raxtax.uniques.tsv", table)) return 74;
     if (o.otus) {
-        rtx_otu *otu = nullptr;
+        rtx_otu *&otu = own.otu;
         rtx_otu_view_t ov{};
         std::string otu_fasta, otu_map, otu_table;
         trc = rtx_otu_cluster(o.devices[0], sum, nullptr, &otu);
@@ -1366,10 +1396,22 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
         if (ov.long_rows) fprintf(stderr, "[INFO ] --otus: %llu distinct reads are longer than %d bases and stand alone\n", (ull)ov.long_rows, RTX_OTU_MAX_LEN);
         if (!write_whole(o.prefix + "/raxtax.otus", otu_fasta) || !write_whole(o.prefix + "/raxtax.otus.map", otu_map)) return 74;
         if (p.tags_on && !write_whole(o.prefix + "/raxtax.otus.tsv", otu_table)) return 74;
-        rtx_otu_destroy(otu);
+        if (o.denovo) {  // the OTUs against the more abundant OTUs of the run
+            rtx_denovo *&dn = own.dn;
+            rtx_denovo_view_t dv{};
+            std::string records, clean, clean_table;
+            trc = rtx_denovo_check(o.devices[0], sum, otu, &o.denovo_params, &dn);
+            if (trc == RTX_OK) trc = rtx_denovo_view(dn, &dv);
+            if (trc == RTX_OK) trc = format_two_pass(records, [&](char *buf, uint64_t cap) { return rtx_denovo_format_records(dn, buf, cap); });
+            if (trc == RTX_OK) trc = format_two_pass(clean, [&](char *buf, uint64_t cap) { return rtx_denovo_format_fasta(dn, sum, otu, o.otus_minsize, buf, cap); });
+            if (trc == RTX_OK && p.tags_on)
+                trc = format_two_pass(clean_table, [&](char *buf, uint64_t cap) { return rtx_denovo_format_table(dn, sum, otu, names.data(), o.otus_minsize, buf, cap); });
+            if (trc != RTX_OK) { fprintf(stderr, "[ERROR] de novo chimera check: %s\n", rtx_last_error()); return 70; }
+            fprintf(stderr, "[INFO ] --denovo: %llu OTUs, %llu checked, %llu flagged, %u rounds\n", (ull)dv.n_entries, (ull)dv.n_checked, (ull)dv.n_flagged, dv.rounds);
+            if (!write_whole(o.prefix + "/raxtax.otus.denovo", records) || !write_whole(o.prefix + "/raxtax.otus.clean", clean)) return 74;
+            if (p.tags_on && !write_whole(o.prefix + "/raxtax.otus.clean.tsv", clean_table)) return 74;
+        }
     }
-    rtx_tally_table_destroy(sum);
-    for (rtx_tally_table *t : tables) rtx_tally_table_destroy(t);
     return 0;
 }
 

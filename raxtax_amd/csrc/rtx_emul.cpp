@@ -1095,4 +1095,47 @@ void emul_chimera_reduce(uint32_t len, uint32_t n_valid, uint32_t S, uint32_t mi
     std::memcpy(rec, &r, sizeof r);
 }
 
+// ---- de novo chimera check (rtx_denovo.hip) ------------------------------------------------------------------------------------------
+// The prefix mask of `lim` over a tile of the stage's bitmap over n_parents entries: out[64][4], lane by lane (denovo_allow); returns the
+// lanes of the tile.
+uint32_t emul_denovo_allow(uint32_t n_parents, uint32_t tile, uint32_t lim, uint32_t *out) {
+    const uint32_t L = tile_lanes(denovo_stride_bytes(n_parents), tile);
+    for (uint32_t lane = 0; lane < 64u; lane++) denovo_allow(lane, L, tile, lim, out + lane * 4u);
+    return L;
+}
+// A checkpoint of denovo_scan_kernel on one tile: emul_chimera_checkpoint with the planes masked by live[8192] (0 / 1 per local entry, laid
+// into the lanes by ref_slot as the live row is) AND the prefix mask of lim.
+int emul_denovo_checkpoint(const uint16_t *counts, const uint8_t *live, int planes, uint32_t n_parents, uint32_t tile, uint32_t lim, uint32_t *count, uint32_t *ref) {
+    return emul_with_planes(planes, [&](auto tag) {
+        constexpr int NP = decltype(tag)::value;
+        const uint32_t stride_bytes = denovo_stride_bytes(n_parents), L = tile_lanes(stride_bytes, tile);
+        std::vector<std::array<std::array<uint32_t, NP>, 4>> pl(64);
+        std::vector<std::array<uint32_t, 4>> lv(64);
+        for (auto &l : pl)
+            for (auto &w : l) w.fill(0u);
+        for (auto &l : lv) l.fill(0u);
+        for (uint32_t rl = 0; rl < 8192u && (rl >> 3) < L * 16u; rl++) {
+            uint32_t word, bit;
+            ref_slot(tile * 8192u + rl, stride_bytes, word, bit);
+            word -= tile * 256u;
+            for (int p = 0; p < NP; p++) pl[word >> 2][word & 3u][p] |= (((uint32_t)counts[rl] >> p) & 1u) << bit;
+            lv[word >> 2][word & 3u] |= (live[rl] ? 1u : 0u) << bit;
+        }
+        uint32_t m[64], r[64], M = 0;
+        for (uint32_t lane = 0; lane < 64u; lane++) {
+            uint32_t a[4][NP], allow[4];
+            for (int w = 0; w < 4; w++)
+                for (int p = 0; p < NP; p++) a[w][p] = pl[lane][w][p];
+            denovo_allow(lane, L, tile, lim, allow);
+            for (int w = 0; w < 4; w++) allow[w] &= lv[lane][w];
+            denovo_lane_best<NP>(a, allow, lane, L, m[lane], r[lane]);
+            M = std::max(M, m[lane]);
+        }
+        uint32_t R = kChimNoRef;
+        for (uint32_t lane = 0; lane < 64u; lane++) R = std::min(R, M != 0u && m[lane] == M ? tile * 8192u + r[lane] : kChimNoRef);
+        *count = M;
+        *ref = R;
+    });
+}
+
 }  // extern "C"

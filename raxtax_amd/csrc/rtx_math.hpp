@@ -1537,4 +1537,57 @@ RTX_HD bool chimera_window_kmer(const uint8_t *seq, uint32_t i, uint32_t &k) {
     return ok;
 }
 
+// ---------------------------------------------------------------------------
+// De novo chimera check (rtx_denovo.hip; rtx_denovo_check_host on the host; emul_denovo_* on x86) -- include/raxtax_hip.h has the definition.
+// The references of entry e are the entries below lim(e) that are not flagged: a PREFIX of the entry list and a live mask.  The scan is
+// chimera_scan_kernel's with every plane word ANDed, at a checkpoint, with the lane's 16 bytes of that mask: a counter that is masked out
+// is 0 and never a candidate.  The stage's own bitmap has the index's layout with the row of k-mer k at k, the zero row behind the 65 536
+// k-mer rows and the live mask as one more row; its stride is a multiple of 16 bytes, so the last tile may span fewer than 64 lanes.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kDenovoNoParent = 3u;                    // RTX_DENOVO_NO_PARENT
+constexpr uint32_t kDenovoZeroRow = 65536u, kDenovoLiveRow = 65537u, kDenovoRows1 = 65538u;
+constexpr uint32_t kDenovoMaxTiles = 32u;                   // RTX_DENOVO_DEFAULT_MAX_PARENTS / 8192
+RTX_HD uint32_t denovo_stride_bytes(uint32_t n_parents) { return (((n_parents + 7u) >> 3) + 15u) & ~15u; }
+RTX_HD uint32_t denovo_tiles(uint32_t lim) { return (lim + 8191u) >> 13; }
+// The prefix mask of lim in the 16 bytes of `lane` of tile `tile` (L lanes): under ref_slot byte g of the lane holds the local entries
+// (g L + lane) 8 + [0, 8), so byte g is the low min(8, lim - first entry) bits, or nothing.  A lane behind the tile's last one holds nothing.
+RTX_HD void denovo_allow(uint32_t lane, uint32_t L, uint32_t tile, uint32_t lim, uint32_t *out /*[4]*/) {
+    const uint64_t t0 = (uint64_t)tile << 13;
+#pragma unroll
+    for (uint32_t w = 0; w < 4u; w++) {
+        uint32_t v = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) {
+            const uint64_t first = t0 + (uint64_t)((w * 4u + j) * L + lane) * 8u;
+            const uint32_t n = lane < L && (uint64_t)lim > first ? (uint32_t)((uint64_t)lim - first < 8u ? (uint64_t)lim - first : 8u) : 0u;
+            v |= ((1u << n) - 1u) << (8u * j);
+        }
+        out[w] = v;
+    }
+}
+// chimera_lane_best over the planes ANDed with allow[w], word by word: only one masked word is alive at a time
+template <int NP>
+RTX_HD void denovo_lane_best(const uint32_t (&pl)[4][NP], const uint32_t (&allow)[4], uint32_t lane, uint32_t L, uint32_t &m, uint32_t &rl) {
+    m = 0;
+    rl = kChimNoRef;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        uint32_t row[NP], cand;
+#pragma unroll
+        for (int b = 0; b < NP; b++) row[b] = pl[w][b] & allow[w];
+        const uint32_t mw = planes_max<NP>(row, cand);
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint32_t b = (uint32_t)__ffs((int)cand) - 1u;
+#else
+        const uint32_t b = (uint32_t)__builtin_ctz(cand);  // (planes_max never leaves cand empty)
+#endif
+        // (mw > 0: every candidate has a plane bit set, so it is allowed; mw == 0: the candidates are all 32 counters, masked ones among
+        // them, but a lane whose maximum is 0 names no entry: the scan decides that by M == 0 and by the wave maximum)
+        const uint32_t r = (((uint32_t)w * 4u + (b >> 3)) * L + lane) * 8u + (b & 7u);
+        const bool take = w == 0 || mw > m;
+        rl = take ? r : rl;
+        m = take ? mw : m;
+    }
+}
+
 }  // namespace rtx
