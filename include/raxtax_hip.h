@@ -1122,7 +1122,11 @@ uint64_t rtx_fastq_block_end_n(const char *text, uint64_t len, uint64_t max_reco
  *   rtx_chimera_kernel_time  milliseconds of the scan kernels of the last run, from HIP events around them.
  *   rtx_chimera_read    the same for ONE read on the host (no device), from the reference sequences (ref_off [n_refs + 1]).
  *   rtx_index_set_chimera  the setting a handle holds for the callers that run the stage in front of it (NULL, the default: off -- nothing
- *                runs and nothing is allocated); the handle itself never reads it.  rtx_index_chimera: the setting and whether it is on. */
+ *                runs and nothing is allocated); the handle itself never reads it.  rtx_index_chimera: the setting and whether it is on.
+ *   RTX_DEFAULT_CHIMERA_SLICE (rtx_set_default_option; default and 0: no cap): a cap on the reads of a slice of rtx_chimera_run and on the
+ *                entries of a slice of rtx_denovo_check, read at every call and applied as a minimum with what the scratch budget gives.
+ *                For tests: a small cap makes a small batch run in many slices.  Results do not depend on it. */
+#define RTX_DEFAULT_CHIMERA_SLICE 6
 #define RTX_CHIMERA_MAX_QUERY 4096u
 #define RTX_CHIMERA_MAX_SEGMENTS 32u
 #define RTX_CHIMERA_DEFAULT_SEGMENTS 16u

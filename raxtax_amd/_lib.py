@@ -25,6 +25,7 @@ RTX_OPT_DEREP = 27                 # rtx_index_set_option: raxtax() classifies e
 RTX_DEFAULT_DEREP_HASH_MASK = 3    # rtx_set_default_option: the hash of rtx_derep_run ANDed with a mask (tests)
 RTX_DEFAULT_TALLY_HASH_MASK = 4    # rtx_set_default_option: the hash of rtx_tally_add ANDed with a mask (tests)
 RTX_DEFAULT_OTU_HASH_MASK = 5      # rtx_set_default_option: the hashes of rtx_otu_cluster ANDed with a mask (tests)
+RTX_DEFAULT_CHIMERA_SLICE = 6      # rtx_set_default_option: a cap on the reads / entries of a slice of rtx_chimera_run / rtx_denovo_check (tests)
 RTX_OTU_MAX_LEN = 4096
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 

@@ -17,10 +17,14 @@
 //   chimera_reduce_kernel  one wave per read: lane (direction, checkpoint) takes the tiles in ascending order (the first tile that holds the
 //                          maximum holds the lowest reference), lane 0 builds the record (chimera_record).
 // Vector stores and plain C++, no atomics.
+#include <atomic>
+
 #include "rtx_stage.hpp"
 #include "rtx_hit_common.hpp"
 
 namespace {
+
+std::atomic<uint64_t> g_chimera_slice{~0ull};  // RTX_DEFAULT_CHIMERA_SLICE (tests: a small batch in many slices)
 
 struct ChimParams {
     const uint8_t *bases;          // the staged reads of the call
@@ -184,6 +188,11 @@ struct rtx_chimera : StageShell {  // (the events stand around the scan kernels 
     PinBuf<uint32_t> h_ids, h_out;
 };
 
+namespace rtxi {
+void set_chimera_slice(uint64_t cap) { g_chimera_slice.store(cap); }
+uint64_t chimera_slice_cap() { return g_chimera_slice.load(); }
+}  // namespace rtxi
+
 namespace rtx {
 int chimera_check_params(const char *who, const rtx_chimera_params *p) {
     if (!p) { set_error("%s: null argument", who); return RTX_ERR_INVALID; }
@@ -238,7 +247,7 @@ int rtx_chimera_run(rtx_chimera *c, uint64_t n, const uint8_t *bases, const uint
     // a list is sized for the longest read of the call (at most 4 313 rows + the tail); a slice keeps the checkpoints and the lists in budget
     const uint32_t list_stride = chimera_list_cap(((max_pos + 7u) & ~7u) + 8u * S);
     const uint64_t best_per_read = 2ull * S * nt * sizeof(uint2), list_per_read = 2ull * list_stride * 4u;
-    const uint64_t slice = std::max<uint64_t>(1, std::min<uint64_t>(n, std::min(kBestBudget / best_per_read, kListBudget / list_per_read)));
+    const uint64_t slice = std::max<uint64_t>(1, std::min({n, kBestBudget / best_per_read, kListBudget / list_per_read, chimera_slice_cap()}));
     int rc;
     if ((rc = c->h_packed.resize(total + 64)) || (rc = c->h_base_off.resize(n + 1)) || (rc = c->h_ids.resize(slice)) || (rc = c->h_out.resize(slice * 12)) ||
         (rc = grow(c->d_packed, total + 64)) || (rc = grow(c->d_bases, total + 64)) || (rc = grow(c->d_base_off, n + 1)) ||
@@ -276,7 +285,7 @@ int rtx_chimera_run(rtx_chimera *c, uint64_t n, const uint8_t *bases, const uint
             const uint64_t len = base_off[q0 + q + 1] - base_off[q0 + q];
             if (len > 1030u && len <= RTX_CHIMERA_MAX_QUERY) ids[n10 + n12++] = q;
         }
-        RTX_HIP(hipMemcpyAsync(c->d_ids.p, ids, (size_t)(n10 + n12) * 4 + 4, hipMemcpyHostToDevice, s));
+        if (n10 + n12) RTX_HIP(hipMemcpyAsync(c->d_ids.p, ids, (size_t)(n10 + n12) * 4, hipMemcpyHostToDevice, s));
         p.q0 = q0;
         hipLaunchKernelGGL(chimera_rows_kernel, dim3(m), dim3(64), 0, s, p);
         RTX_HIP(hipEventRecord(c->ev0, s));

@@ -263,7 +263,7 @@ int run(DenovoStage *st, const rtx_tally_view &v, rtx_denovo &d) {
     const uint64_t bitmap_words = (uint64_t)nt * kDenovoRows1 * 256u;
     const uint32_t list_stride = chimera_list_cap(((max_pos + 7u) & ~7u) + 8u * S);
     const uint64_t best_per = 2ull * S * std::max(nt, 1u) * sizeof(uint2), list_per = 2ull * list_stride * 4u;
-    const uint64_t slice = std::max<uint64_t>(1, std::min<uint64_t>(n, std::min(kBestBudget / best_per, kListBudget / list_per)));
+    const uint64_t slice = std::max<uint64_t>(1, std::min({n, kBestBudget / best_per, kListBudget / list_per, chimera_slice_cap()}));
     if ((rc = st->h_packed.resize(total + 64)) || (rc = st->h_base_off.resize(n + 1)) || (rc = st->h_ids.resize(n + 1)) || (rc = st->h_out.resize(n * 12)) ||
         (rc = st->h_changed.resize(1)) || (rc = st->d_packed.alloc(total + 64)) || (rc = st->d_bases.alloc(total + 64)) || (rc = st->d_base_off.alloc(n + 1)) ||
         (rc = st->d_bitmap.alloc(bitmap_words)) || (rc = st->d_lim.alloc(n)) || (rc = st->d_lists.alloc(slice * 2 * list_stride)) || (rc = st->d_n_valid.alloc(slice)) ||

@@ -44,6 +44,7 @@ class Restatement:
         keys = np.sort(np.concatenate(keys)) if keys else np.zeros(0, np.int64)
         self.post_ref = keys % max(self.n, 1)
         self.post_off = np.searchsorted(keys // max(self.n, 1), np.arange(65537))
+        self._iterated = None   # (rounds() and flag_history() iterate once between them)
 
     def record(self, e, flagged) -> dict:
         """The record of entry e when `flagged` (bool per entry) are the flags of the entries below it."""
@@ -87,11 +88,22 @@ class Restatement:
             flagged[e] = bool(recs[-1]["flag"])
         return recs
 
-    def rounds(self):
-        """(rounds, scans, flags) of the iteration the device runs: round 1 takes every entry with nobody flagged, the next one the entries
-        e with lim(e) > the lowest entry whose flag changed, and the first round that changes nothing is the last."""
+    def totals(self, e):
+        """T_p of entry e for every p below n_par: the valid windows of e whose 8-mer occurs in p, whatever lim and the flags are."""
+        code, valid = self.win[e]
+        idx = np.nonzero(valid)[0]
+        lo, hi = self.post_off[code[idx]], self.post_off[code[idx] + 1]
+        refs = np.concatenate([self.post_ref[a:z] for a, z in zip(lo, hi)]) if len(idx) else np.zeros(0, np.int64)
+        return np.bincount(refs, minlength=self.n_par)
+
+    def _iterate(self):
+        if self._iterated is None:
+            self._iterated = self._iterate_once()
+        return self._iterated
+
+    def _iterate_once(self):
         flagged = np.zeros(self.n, bool)
-        e0, rounds, scans = 0, 0, 0
+        e0, rounds, scans, history = 0, 0, 0, []
         while True:
             rounds += 1
             scans += self.n - e0
@@ -101,9 +113,19 @@ class Restatement:
                 new[e] = bool(self.record(e, flagged)["flag"])
             diff = np.nonzero(new != flagged)[0]
             flagged = new
+            history.append(flagged.copy())
             if len(diff) == 0:
-                return rounds, scans, flagged
+                return rounds, scans, flagged, history
             e0 = next((e for e in range(self.n) if self.lim[e] > diff[0]), self.n)
+
+    def rounds(self):
+        """(rounds, scans, flags) of the iteration the device runs: round 1 takes every entry with nobody flagged, the next one the entries
+        e with lim(e) > the lowest entry whose flag changed, and the first round that changes nothing is the last."""
+        return self._iterate()[:3]
+
+    def flag_history(self):
+        """The flags behind every round of rounds(), one bool array per round (the flags in front of round 1 are all 0)."""
+        return [h.copy() for h in self._iterate()[3]]
 
 
 def as_tuples(recs):
@@ -120,6 +142,8 @@ def check_equal(d, rs: Restatement, what=""):
     for e, (g, w) in enumerate(zip(got, as_tuples(want))):
         assert g == w, (what, e, dict(zip(cc.FIELDS, g)), dict(zip(cc.FIELDS, w)))
     assert d.n_flagged == sum(r["flag"] for r in want) and d.n_checked == sum(r["status"] == cc.OK for r in want), what
+    flagged = {e for e, r in enumerate(want) if r["flag"]}
+    assert not flagged & {int(r[k]) for r in d.rec for k in ("parent", "parent_a", "parent_b")}, what   # nobody names a flagged parent
     return want
 
 
@@ -244,3 +268,110 @@ def planted_world(seed=21, n_templates=40, n_chimeras=20, length=400):
 def table_of(rx, seqs, weights, samples=0, sample=None):
     bases, off = cc.concat([np.asarray(s, np.uint8) for s in seqs])
     return rx.tally_reads(bases, off, sample=sample, weight=np.asarray(weights, np.uint32), samples=samples)
+
+
+def lane_entries(n_parents, tile, groups, lanes=(0, -1), bits=(0, 7)):
+    """The entries of a tile of the stage's bitmap over n_parents entries that lie at bit j of byte g of a lane, for g in groups, j in bits
+    and the lanes given (-1: the tile's last lane, L - 1): ref_slot inverted -- local entry (g L + lane) 8 + j is bit j of byte g of the
+    lane.  Entries 0 and 1 (the templates of live_world) and entries that do not exist are left out."""
+    stride = (((n_parents + 7) >> 3) + 15) & ~15
+    L = min(64, (stride - tile * 1024) >> 4)
+    out = set()
+    for g in groups:
+        for lane in lanes:
+            for j in bits:
+                e = tile * 8192 + ((g * L + lane % L) * 8 + j)
+                if 2 <= e < n_parents:
+                    out.add(e)
+    return sorted(out)
+
+
+WORD_EDGES = (0, 3, 4, 7, 8, 11, 12, 15)   # the first and the last byte of each 32-bit word of a lane's 16 bytes
+LIVE_520 = tuple(lane_entries(520, 0, WORD_EDGES))                       # five lanes: bytes 0 .. 12 are in use, entry 519 is bit 7 of byte 12 of lane 4
+LIVE_8232 = tuple(sorted(set(lane_entries(8232, 0, WORD_EDGES, bits=(7,)) + lane_entries(8232, 1, (0, 3, 4), bits=(0, 7)) + [2048])))
+
+
+def live_world(n_parents, flagged_at, seed=13, qlen=40, head=28):
+    """n_parents parents and one query per f in flagged_at, for segments = 4 and mindelta = 8.  Entries 0 and 1 are templates A and B at more
+    than twice the weight of everything else, so that every other parent has exactly them as its parents.  Entry f is the piece "head of A +
+    tail of B", an N, and the whole of the query Q_f: by the definition a chimera of A and B, flagged, and so no parent of Q_f.  A lower entry
+    j_f that is not flagged -- f - 1 where that is free, so that the bit next to f's counts -- holds Q_f's head and nothing else of it.  Q_f is
+    rarer than every parent: its lim is n_parents, its parent is j_f with `single` below the 33 windows that f holds.
+    Returns (seqs, weights, {f: (entry of Q_f, j_f)})."""
+    rng = np.random.default_rng(seed)
+    flagged_at = sorted(flagged_at)
+    assert flagged_at and 2 < flagged_at[0] and flagged_at[-1] < n_parents and len(set(flagged_at)) == len(flagged_at)
+    A, B = rand_seq(rng, 80), rand_seq(rng, 80)
+    piece = np.concatenate([A[:40], B[40:]])
+    taken, lower = set(flagged_at), {}
+    for f in flagged_at:
+        j = next(j for j in range(f - 1, 1, -1) if j not in taken)
+        taken.add(j)
+        lower[f] = j
+    queries = {f: rand_seq(rng, qlen) for f in flagged_at}
+    head_of = {j: f for f, j in lower.items()}
+    W = 2 * n_parents + 100
+    seqs, weights = [A, B], [8 * W, 8 * W - 1]
+    for p in range(2, n_parents):
+        if p in queries:
+            seqs.append(np.concatenate([piece, N, queries[p]]))
+        elif p in head_of:
+            seqs.append(np.concatenate([queries[head_of[p]][:head], tag(rng)]))
+        else:
+            seqs.append(rand_seq(rng, int(rng.integers(24, 61))))
+        weights.append(2 * (W - p))
+    where = {}
+    for k, f in enumerate(flagged_at):
+        where[f] = (len(seqs), lower[f])
+        seqs.append(queries[f])
+        weights.append(W - n_parents - k)
+    return seqs, weights, where
+
+
+def flipback_world(seed=31, length=200):
+    """Templates A, B and Z (a bystander), then C, D and E at falling weights, for the default parameters.  C = A's head + B's tail: flagged
+    in every round, so live in round 1 only.  D = A with B's bases 100 .. 139 in place of its own, which is also C's first 140 bases + A's
+    tail: while C is live D is C's head joined to A's tail and flagged, once C is flagged A alone explains D as well as any pair and D is
+    not flagged: D's flag goes 0 -> 1 -> 0 and its live bit is cleared and set again.  E = D with three substitutions: its parent is D.
+    Returns (seqs, weights, names -> entry)."""
+    rng = np.random.default_rng(seed)
+    A, B, Z = (rand_seq(rng, length) for _ in range(3))
+    Cc = np.concatenate([A[:100], B[100:]])
+    D = np.concatenate([A[:100], B[100:140], A[140:]])
+    E = substitute_at(D, (30, 120, 175))
+    return [A, B, Z, Cc, D, E], [1000, 900, 800, 100, 20, 4], dict(A=0, B=1, Z=2, C=3, D=4, E=5)
+
+
+def two_tile_rounds_world(seed=41):
+    """8 232 parents in two tiles (the second one a single lane) with the chain of rounds_world laid across them.  In weight tiers, each at
+    least twice the next: A and B; entries 2 .. 8179 with lim = 2, C among them at 8150; entries 8180 .. 8199 with lim = 8180, one tile;
+    entries 8200 .. 8231 with lim = 8200, two tiles, D the first of them; and from 8232 on entries with lim = 8232: E, a query X of 1 100
+    bases (twelve planes) whose first 700 an entry of the second tile holds, and fillers.  Round 1 flags C; round 2 takes the entries from
+    8180 on -- the first entry that scans tile 0 is clipped, the first that scans tile 1 is not -- and flags D; round 3 takes those from
+    8232 on -- both are clipped -- and flags E; round 4 has nothing to scan.
+    H at 8190 is a query of the one-tile tier whose head entry 77 holds and whose whole entry 8185, outside its lim, holds.
+    Returns (seqs, weights, names -> entry)."""
+    rng = np.random.default_rng(seed)
+    A, B = rand_seq(rng, 200), rand_seq(rng, 200)
+    Cc = np.concatenate([A[:100], B[100:]])
+    D = substitute_at(Cc, (20, 70, 150))
+    E = substitute_at(D, (40, 120, 180))
+    H, X = rand_seq(rng, 40), rand_seq(rng, 1100)
+    names = dict(A=0, B=1, H_head=77, C=8150, H_whole=8185, H=8190, D=8200, X_head=8210, E=8232, X=8234)
+    fixed = {0: A, 1: B, 77: np.concatenate([H[:28], tag(rng)]), 8150: Cc, 8185: np.concatenate([H, tag(rng)]), 8190: H, 8200: D,
+             8210: np.concatenate([X[:700], tag(rng)]), 8232: E, 8234: X}
+    n = 8240
+    seqs = [fixed[e] if e in fixed else rand_seq(rng, int(rng.integers(24, 61))) for e in range(n)]
+    weights = []
+    for e in range(n):
+        if e < 2:
+            weights.append(40000 - e)
+        elif e < 8180:
+            weights.append(10000 + 8180 - e)
+        elif e < 8200:
+            weights.append(4300 - (e - 8180))
+        elif e < 8232:
+            weights.append(2100 - (e - 8200))
+        else:
+            weights.append(1000 - (e - 8232))
+    return seqs, weights, names

@@ -67,8 +67,12 @@ def pair_links(seqs):
 
 def brute_force(seqs, sizes, counts):
     """dict(links [n, 2], long_rows, otu, seed, members, sizes, counts) of the rows (numpy uint8 arrays) in rank order"""
-    n = len(seqs)
     links, long_rows = brute_links([bytes(s) for s in seqs])
+    return grow(len(seqs), links, long_rows, sizes, counts)
+
+
+def grow(n, links, long_rows, sizes, counts):
+    """the OTUs over a sorted list of links (a, b), a < b: the greedy breadth-first growth, literally"""
     adj = [[] for _ in range(n)]
     for a, b in links:
         adj[a].append(b)
@@ -88,10 +92,38 @@ def brute_force(seqs, sizes, counts):
                     queue.append(y)
     counts = np.asarray(counts, np.uint64).reshape(n, -1)
     per_otu = np.zeros((len(seed), counts.shape[1]), np.uint64)
-    for r in range(n):
-        per_otu[otu[r]] += counts[r]
+    np.add.at(per_otu, np.array(otu, np.int64), counts)
     return dict(links=np.array(links, np.uint32).reshape(-1, 2), long_rows=long_rows, otu=np.array(otu, np.uint32), seed=np.array(seed, np.uint32),
                 members=np.bincount(np.array(otu, np.int64), minlength=len(seed)).astype(np.uint64), sizes=per_otu.sum(axis=1), counts=per_otu)
+
+
+def equal_length_force(seqs, sizes, counts):
+    """brute_force() said a second time for rows of ONE length over A, C, G, T alone, vectorised: a row is the integer of its base-4
+    digits, the substitution of digit d_i by c is key + (c - d_i) 4^i, and a variant is looked up with a binary search in the sorted keys.
+    Rows of one length have no deletion link.  The growth is grow(), as in brute_force()."""
+    rows = np.stack([np.asarray(s, np.uint8) for s in seqs])
+    n, length = rows.shape
+    assert length <= 31 and np.isin(rows, PLAIN).all()
+    digit = np.zeros(16, np.int64)
+    digit[list(PLAIN)] = np.arange(4)
+    d = digit[rows]
+    keys = (d << (2 * np.arange(length, dtype=np.int64))).sum(axis=1)
+    order = np.argsort(keys, kind="stable")
+    sorted_keys = keys[order]
+    assert (np.diff(sorted_keys) > 0).all()
+    pairs = []
+    for i in range(length):
+        for c in range(4):
+            x = np.flatnonzero(d[:, i] != c)
+            variant = keys[x] + ((c - d[x, i]) << (2 * i))
+            at = np.minimum(np.searchsorted(sorted_keys, variant), n - 1)
+            hit = sorted_keys[at] == variant
+            y = order[at[hit]]
+            x = x[hit]
+            pairs.append(np.stack([x[x < y], y[x < y]], axis=1))   # every link is found from both of its rows: kept from the lower one
+    links = np.concatenate(pairs)
+    links = links[np.lexsort((links[:, 1], links[:, 0]))]
+    return grow(n, [(int(a), int(b)) for a, b in links], 0, sizes, counts)
 
 
 def assert_otus(got, want):
@@ -257,3 +289,92 @@ def check_clusters(table, got, named):
     np.add.at(sums, otu.astype(np.int64), table.counts)
     assert np.array_equal(got.counts, sums) and np.array_equal(got.sizes, sums.sum(axis=1)) and (table.counts[:, 1] > 0).any()
     assert list(got.seed) == sorted(got.seed) and np.array_equal(otu[got.seed], np.arange(got.n_otus))
+
+
+WEIGHTINGS = ("equal", "three", "distinct")
+
+
+@functools.lru_cache(maxsize=None)
+def complete_case(weighting, seed=17):
+    """(table, brute force): the complete world -- all 1 024 rows of 5 codes and all 4 096 rows of 6 codes over A, C, G, T: 5 120 rows in 20
+    blocks of 256, 64 000 links (36 864 + 7 680 substitutions, 1 024 x 19 deletions), which is more than the 4 n links the first pass has room
+    for.  equal: one size, every link runs both ways, one OTU; three: sizes from {1, 2, 3}, a dense plateau with borders; distinct: no link
+    runs both ways."""
+    rng = np.random.default_rng(seed)
+    codes = np.array(PLAIN, np.uint8)
+    seqs = [codes[(k >> (2 * np.arange(length))) & 3] for length in (5, 6) for k in range(4 ** length)]
+    n = len(seqs)
+    weight = {"equal": np.ones(n, np.uint32), "three": rng.integers(1, 4, n).astype(np.uint32), "distinct": (rng.permutation(n) + 1).astype(np.uint32)}[weighting]
+    table = table_of([seqs[i] for i in rng.permutation(n)], weight)
+    return table, brute_of(table)
+
+
+COMPLETE_LINKS = 36864 + 7680 + 1024 * 19
+COMPLETE_MASK = 0xFF00000000000003   # the top 8 bits of the slot and two bits of the tag: 256 chains of about 20 rows in the 16 384 slots
+
+
+def check_complete(table, got, weighting):
+    """what the complete world was built to show, on any result"""
+    sizes = table.sizes
+    assert got.n_rows == 5120 and len(got.links) == COMPLETE_LINKS == 64000 and COMPLETE_LINKS > 4 * got.n_rows
+    assert got.long_rows == 0 and int(got.members.sum()) == 5120
+    a, b = got.links[:, 0].astype(np.int64), got.links[:, 1].astype(np.int64)
+    two_way = int((sizes[a] == sizes[b]).sum())
+    if weighting == "equal":
+        assert two_way == COMPLETE_LINKS and got.n_otus == 1 and got.seed.tolist() == [0] and got.members.tolist() == [5120] and not got.otu.any()
+    elif weighting == "three":
+        assert 0 < two_way < COMPLETE_LINKS     # (rank 0 has the largest size and the rows of that size are connected: still one OTU, by the definition)
+    else:
+        assert two_way == 0 and 1 < got.n_otus < 5120
+
+
+BLOCK_EDGES = (255, 256, 257, 512, 513)
+
+
+@functools.lru_cache(maxsize=None)
+def block_case(n, last):
+    """(table, brute force, planted): n rows of 20 random codes at distinct falling sizes, so that row k of the list has rank k.  The last row
+    is a seed (last = "seed": a random row) or a substitution of row 0 (last = "variant": it lies in OTU 0, across every block edge in
+    front of it); the rows 256 .. 259 that are not the last one are variants of rows of block 0, links across the edge at 256.
+    planted: the (a, b) pairs, a < b, that were built as links."""
+    assert last in ("seed", "variant")
+    rng = np.random.default_rng(1000 + n)
+    seqs = [random_seq(rng, 20) for _ in range(n)]
+    planted = []
+    for k in range(256, min(n - 1, 260)):
+        a = 255 - 3 * (k - 256)
+        seqs[k] = with_sub(rng, seqs[a], k - 250) if k % 2 == 0 else without(seqs[a], k - 250)
+        planted.append((a, k))
+    if last == "variant":
+        seqs[n - 1] = with_sub(rng, seqs[0], 3)
+        planted.append((0, n - 1))
+    table = table_of(seqs, np.arange(2 * n, n, -1, dtype=np.uint32))
+    assert [bytes(s) for s in table.seqs] == [bytes(s) for s in seqs]
+    return table, brute_of(table), planted
+
+
+def check_blocks(got, n, planted):
+    assert got.links.tolist() == [list(l) for l in sorted(planted)]
+    assert got.n_otus == n - len(planted) and all(got.otu[b] == got.otu[a] for a, b in planted)
+    assert (got.seed[got.otu[n - 1]] == n - 1) == ((0, n - 1) not in planted)
+
+
+MANY = 65537
+
+
+@functools.lru_cache(maxsize=None)
+def many_blocks_case(seed=23):
+    """(table, restatement): exactly 65 537 distinct rows of 12 random codes over A, C, G, T at sizes from 1 .. 4: 257 blocks of 256, the last
+    one holding row 65 536 alone -- the second pass of the scan of the block sums.  Nearly every row is a seed: every block adds to the
+    numbering.  The reference is equal_length_force() (test_otu_cpu.py holds it against brute_force() on the complete world's 6-mers)."""
+    rng = np.random.default_rng(seed)
+    rows = np.zeros((0, 12), np.uint8)
+    while len(rows) < MANY:                  # duplicates are drawn again until the count is exact
+        more = np.array(PLAIN, np.uint8)[rng.integers(0, 4, (MANY - len(rows), 12))]
+        both = np.concatenate([rows, more])
+        _, first = np.unique(both, axis=0, return_index=True)
+        rows = both[np.sort(first)]
+    assert rows.shape == (MANY, 12)
+    table = table_of(list(rows), rng.integers(1, 5, MANY).astype(np.uint32))
+    assert len(table.seqs) == MANY
+    return table, equal_length_force(table.seqs, table.sizes, table.counts)

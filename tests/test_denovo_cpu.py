@@ -1,7 +1,8 @@
 """The de novo chimera check without a device: rtx_denovo_check_host (host_denovo.cpp) and the arithmetic the scan kernel adds to the chimera
 check's (rtx_math.hpp through the x86 emulator: the prefix mask of lim and the masked checkpoint, over every lane count of a short last
-tile) against the numpy restatement of the definition (tests/denovo_common.py), field by field; the symbols, the refusals, the texts and
-the command line's refusals."""
+tile) against the numpy restatement of the definition (tests/denovo_common.py), field by field; the worlds that test_gpu_denovo.py puts
+on the device -- the live mask at the byte, word, lane and tile edges, a flag that is taken back, rounds over two tiles -- proven as
+fixtures by the restatement alone; the symbols, the refusals, the texts and the command line's refusals."""
 import ctypes as C
 import subprocess
 from pathlib import Path
@@ -39,6 +40,20 @@ def test_symbols_are_declared_bound_and_exported():
     assert (_lib.RTX_DENOVO_NO_PARENT, _lib.RTX_DENOVO_DEFAULT_ABSKEW, _lib.RTX_DENOVO_DEFAULT_MAX_PARENTS) == (3, 2, 262144)
     for name in ("DenovoParams", "Denovo", "denovo_check", "denovo_check_host", "denovo_records_text", "denovo_fasta", "denovo_table_text"):
         assert name in rx.__all__ and hasattr(rx, name), name
+
+
+def test_slice_option_is_declared_and_accepted():
+    header = (ROOT / "include" / "raxtax_hip.h").read_text()
+    assert "#define RTX_DEFAULT_CHIMERA_SLICE 6\n" in header and _lib.RTX_DEFAULT_CHIMERA_SLICE == 6
+    lib = _lib.load()
+    try:
+        assert lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, 2) == 0
+        seqs, weights = dc.rounds_world()
+        _, _, d, rs = _host(seqs, weights)                  # (the host walk has no slices: the option changes nothing)
+        dc.check_equal(d, rs, "capped")
+    finally:
+        assert lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, 0) == 0
+    assert lib.rtx_set_default_option(7, 0) == _lib.RTX_ERR_INVALID
 
 
 def test_prefix_of_one_tile_on_the_host():
@@ -85,6 +100,72 @@ def test_the_greedy_rule_takes_rounds():
     rounds, scans, flagged = rs.rounds()
     assert rounds == 4 and scans == 5 + 2 + 1 + 0 and list(flagged) == [False, False, True, True, True]
     assert (d.rounds, d.scans) == (1, 5)                # the host walks the entries once
+
+
+def _live(n_parents, flagged_at):
+    seqs, weights, where = dc.live_world(n_parents, flagged_at)
+    _, _, d, rs = _host(seqs, weights, segments=4, mindelta=8)
+    want = dc.check_equal(d, rs, f"live {n_parents}")
+    assert [e for e in range(rs.n) if want[e]["flag"]] == sorted(flagged_at)
+    nobody = np.zeros(rs.n, bool)
+    for f, (e, lower) in where.items():
+        assert rs.lim[e] == n_parents and lower < f and not want[lower]["flag"]
+        assert want[e]["parent"] == lower and 21 <= want[e]["single"] < 33, (f, want[e])   # the head's 21 windows (and a chance 8-mer)
+        unmasked = rs.record(e, nobody)
+        assert unmasked["parent"] == f and unmasked["single"] == 33, (f, unmasked)         # without the mask the query names f: the fixture sees a bit that is not cleared
+    return rs, want, where
+
+
+def test_live_mask_positions_on_the_host():
+    """the flagged entries lie at bits 0 and 7 of the first and last byte of every word of a lane's 16 bytes, in the first and the last lane"""
+    assert set(dc.LIVE_520) >= {7, 32, 39, 120, 127, 160, 280, 320, 440, 480, 512, 519} and len(dc.LIVE_520) == 27
+    _live(520, dc.LIVE_520)
+    assert set(dc.LIVE_8232) >= {7, 2047, 2048, 8191, 8192, 8199, 8224, 8231}
+    _live(8232, dc.LIVE_8232)
+
+
+def test_live_columns_against_the_emulated_checkpoint(emul):
+    """the live row of the 520 world as the scan reads it: a query's total counts per parent, the final flags as the live mask, through the
+    checkpoint of the scan kernel (five lanes): the count and the parent of the record; with everybody live, f and its 33 windows"""
+    rs, want, where = _live(520, dc.LIVE_520)
+    p16, p8 = C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)
+    flagged = np.array([bool(r["flag"]) for r in want])
+    for f, (e, lower) in where.items():
+        counts = np.zeros(8192, np.uint16)
+        counts[:520] = rs.totals(e)
+        for live, result in (((~flagged[:520]), (want[e]["single"], lower)), (np.ones(520, bool), (33, f))):
+            mask = np.zeros(8192, np.uint8)
+            mask[:520] = live
+            m, r = C.c_uint32(), C.c_uint32()
+            assert emul.emul_denovo_checkpoint(counts.ctypes.data_as(p16), mask.ctypes.data_as(p8), 10, 520, 0, 520, C.byref(m), C.byref(r)) == 0
+            assert (m.value, r.value) == result, (f, m.value, r.value, result)
+
+
+def test_a_flag_that_goes_back():
+    seqs, weights, at = dc.flipback_world()
+    _, _, d, rs = _host(seqs, weights)
+    want = dc.check_equal(d, rs, "flipback")
+    nobody, c_flagged = np.zeros(6, bool), np.zeros(6, bool)
+    c_flagged[at["C"]] = True
+    assert rs.record(at["D"], nobody)["flag"] == 1 and rs.record(at["D"], nobody)["parent_a"] == at["C"]
+    assert rs.record(at["D"], c_flagged)["flag"] == 0
+    history = rs.flag_history()
+    assert [int(h[at["D"]]) for h in history] == [1, 0, 0] and all(h[at["C"]] for h in history)    # D: 0 -> 1 -> 0, C flagged in every round
+    assert [r["flag"] for r in want] == [0, 0, 0, 1, 0, 0] and want[at["E"]]["parent"] == at["D"]
+    assert rs.record(at["E"], history[0])["parent"] == at["A"]                                       # while D is flagged E falls back to A
+    assert rs.rounds()[:2] == (3, 6 + 2 + 1)
+
+
+def test_rounds_over_two_tiles_on_the_host():
+    seqs, weights, at = dc.two_tile_rounds_world()
+    _, _, d, rs = _host(seqs, weights)
+    want = dc.check_equal(d, rs, "two tiles")
+    assert rs.n_par == 8232 and [rs.lim[at[k]] for k in ("C", "H", "D", "E", "X")] == [2, 8180, 8200, 8232, 8232] and len(rs.seqs[at["X"]]) > 1030
+    rounds, scans, flagged = rs.rounds()
+    history = rs.flag_history()
+    assert [np.nonzero(h)[0].tolist() for h in history] == [[at["C"]], [at["C"], at["D"]], [at["C"], at["D"], at["E"]], [at["C"], at["D"], at["E"]]]
+    assert (rounds, scans) == (4, 8240 + (8240 - 8180) + (8240 - 8232) + 0)
+    assert want[at["H"]]["parent"] == at["H_head"] and want[at["X"]]["parent"] == at["X_head"] and want[at["X"]]["single"] > 690
 
 
 def test_counts_at_the_class_edges():

@@ -10,14 +10,16 @@ field and for equality:
      definition's sanity check (at least 95 % of the chimeras flagged, no plain read);
   4. through rx.raxtax with and without dereplication: unflagged queries byte for byte as without the option, flagged ones as the empty read,
      the callback's records those of Chimera.run, a copy with its representative's record, raxtax_last_chimera adding up;
-  5. the refusals: a strand-both handle, a reference shard, parameters out of range."""
+  5. the refusals: a strand-both handle, a reference shard, parameters out of range;
+  6. slices: the reads of 3. with reads of 1 031, 4 096 and 4 097 bases, cut by RTX_DEFAULT_CHIMERA_SLICE into slices of 1, 7, 64, n - 1 and
+     n reads -- slices without a ten-plane read, without a twelve-plane read, and of too-long reads alone -- byte for byte the uncapped run."""
 import numpy as np
 import pytest
 
 import chimera_common as cc
 import debruijn_common as dc
 import raxtax_amd as rx
-from raxtax_amd import synth
+from raxtax_amd import _lib, synth
 from raxtax_amd.sharded import ShardIndex
 
 pytestmark = pytest.mark.gpu
@@ -180,6 +182,55 @@ def test_through_raxtax(rnd, derep):
     assert empty == []                                     # (the empty read: no message)
     index.set_chimera(None)
     assert index.chimera is None and run() == base
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# 6: slices
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _sliced_reads(rnd):
+    """64 reads of 4 097 bases, 64 of 1 031 and 4 096 bases in turn, the 600 reads of the random database, and five of every kind: under a
+    cap of 64 slice 0 holds too-long reads alone, slice 1 no ten-plane read, slices 2 .. 10 no twelve-plane read and the last one all
+    kinds; under a cap of 7 the same holds of more slices, and some begin in the middle of a kind."""
+    db = rnd["db"]
+    long = [np.concatenate([db.seq_bytes[int(db.seq_off[r]):int(db.seq_off[r + 1])] for r in range(k, k + 8)]) for k in range(64)]
+    assert min(len(s) for s in long) >= 4097
+    too_long = [s[:4097] for s in long]
+    twelve = [s[k:k + (1031 if k % 2 else 4096)] for k, s in enumerate(long)]
+    ten = rnd["chim"] + rnd["plain"]
+    assert max(len(s) for s in ten) <= 1030
+    return too_long + twelve + ten + [long[3][5:1036], long[4][1:4098], ten[0][:500], long[5][2:4098], ten[1][:31]]
+
+
+def test_slices(rnd):
+    index = rx.Index(rnd["tree"])
+    stage = rx.Chimera(index)
+    seqs = _sliced_reads(rnd)
+    n = len(seqs)
+    bases, off = cc.concat(seqs)
+    free = _check(stage, rnd["rs"], seqs, what="uncapped")
+    status = [int(r["status"]) for r in free]
+    assert status[:64] == [cc.TOO_LONG] * 64 and status[64:128] == [cc.OK] * 64 and status[-5:] == [cc.OK, cc.TOO_LONG, cc.OK, cc.OK, cc.OK]
+    lib = _lib.load()
+    try:
+        for cap in (1, 7, 64, n - 1, n):
+            _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, cap))
+            got = stage.run(bases, off)
+            assert got.tobytes() == free.tobytes(), cap
+            assert stage.kernel_ms() > 0.0, cap
+            if cap == 64:
+                whole = stage.kernel_ms()
+        _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, 0))
+        # the kernel time of a run is the sum over its slices: no smaller than that of any one slice, run as a call of its own
+        parts = []
+        for q0 in range(0, n, 64):
+            part = stage.run(*cc.concat(seqs[q0:q0 + 64]))
+            assert part.tobytes() == free[q0:q0 + 64].tobytes(), q0
+            parts.append(stage.kernel_ms())
+        print(f"kernel ms of the run in slices of 64: {whole:.3f}; of the slices alone: {' '.join(f'{t:.3f}' for t in parts)}")
+        assert all(whole >= t for t in parts) and max(parts) > 0.0
+    finally:
+        _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, 0))
+    assert stage.run(bases, off).tobytes() == free.tobytes()           # (the cap is gone)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -1,13 +1,15 @@
 """rtx_denovo_check on the device (rtx_denovo.hip) against the numpy restatement of the definition (tests/denovo_common.py) and against
 rtx_denovo_check_host, exact in every field: the prefix mask at the byte, word and tile edges and in a short last tile, the skew edge, the
-rounds of the greedy rule, the counts at the plane classes' edges, the entries of an OTU object, a planted scenario, and the reference-based
-check (rx.Chimera) on an index built from the same parents."""
+rounds of the greedy rule, the live mask at every edge of its 16-byte column and in a short last tile, a flag that is taken back, later
+rounds over two tiles, the same worlds cut into slices (RTX_DEFAULT_CHIMERA_SLICE), the counts at the plane classes' edges, the entries of an
+OTU object, a planted scenario, and the reference-based check (rx.Chimera) on an index built from the same parents."""
 import numpy as np
 import pytest
 
 import chimera_common as cc
 import denovo_common as dc
 import raxtax_amd as rx
+from raxtax_amd import _lib
 
 pytestmark = pytest.mark.gpu
 ONE_TILE = (1, 7, 8, 9, 511, 512, 513, 520)   # (520: all the parents, so that the bitmap holds the entry at lim = 513 too)
@@ -70,6 +72,68 @@ def test_rounds_of_the_greedy_rule():
     assert [int(r["flag"]) for r in d.rec] == [0, 0, 1, 1, 1]
     assert d.rounds == 4 and d.scans == 8 < d.rounds * d.n_entries             # C, then D, then E, then a round with nothing left to scan
     assert len(d.seconds) == 4 and all(t >= 0 for t in d.seconds) and d.seconds[1] > 0
+
+
+@pytest.mark.parametrize("n_parents, flagged_at", ((520, dc.LIVE_520), (8232, dc.LIVE_8232)))
+def test_live_mask_at_the_byte_word_lane_and_tile_edges(n_parents, flagged_at):
+    """the flagged entries lie at bits 0 and 7 of the first and last byte of every word of a lane's 16 bytes, in the first and the last lane
+    of a tile of five lanes, of a full tile, and of a last tile of one lane: each one's bit is cleared, and only that one"""
+    seqs, weights, where = dc.live_world(n_parents, flagged_at)
+    d, rs, want = _both(seqs, weights, segments=4, mindelta=8)
+    assert [e for e in range(rs.n) if int(d.rec[e]["flag"])] == sorted(flagged_at) and d.rounds == 2
+    for f, (e, lower) in where.items():
+        assert int(d.lim[e]) == n_parents and int(d.rec[e]["parent"]) == lower and 21 <= int(d.rec[e]["single"]) < 33, (f, d.rec[e])
+
+
+def test_a_flag_that_goes_back():
+    """D is flagged in round 1 and not in round 2: its live bit is cleared and then set again, and E finds D"""
+    seqs, weights, at = dc.flipback_world()
+    d, rs, want = _both(seqs, weights)
+    assert [int(r["flag"]) for r in d.rec] == [0, 0, 0, 1, 0, 0] and (d.rounds, d.scans) == (3, 9)
+    assert int(d.rec[at["E"]]["parent"]) == at["D"]
+
+
+def test_later_rounds_over_two_tiles():
+    """rounds 2 and 3 begin in the middle of the list with two tiles to scan: the first entry of every tile is clipped by the round's, in
+    the ten-plane and in the twelve-plane class"""
+    seqs, weights, at = dc.two_tile_rounds_world()
+    d, rs, want = _both(seqs, weights)
+    assert [e for e in range(rs.n) if int(d.rec[e]["flag"])] == [at["C"], at["D"], at["E"]]
+    assert (d.rounds, d.scans) == (4, 8240 + 60 + 8 + 0)
+    assert int(d.rec[at["X"]]["parent"]) == at["X_head"] and int(d.rec[at["H"]]["parent"]) == at["H_head"]
+
+
+def _capped(cap, seqs, weights, **kw):
+    """_both under RTX_DEFAULT_CHIMERA_SLICE = cap, and the records, rounds and scans of the uncapped run beside it"""
+    free, _, _ = _both(seqs, weights, **kw)
+    lib = _lib.load()
+    _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, cap))
+    try:
+        d, rs, want = _both(seqs, weights, **kw)
+    finally:
+        _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_CHIMERA_SLICE, 0))
+    assert d.rec.tobytes() == free.rec.tobytes() and (d.rounds, d.scans) == (free.rounds, free.scans)
+    assert np.array_equal(d.lim, free.lim) and (d.n_checked, d.n_flagged) == (free.n_checked, free.n_flagged)
+    assert all(t >= 0 for t in d.seconds) and d.seconds[1] > 0
+    return d, rs, want
+
+
+def test_slices_with_a_round_that_begins_inside_one():
+    """slices of two entries: rounds 2 and 3 begin at entries 3 and 4, the second entry of slice 1 and the first of slice 2"""
+    d, rs, _ = _capped(2, *dc.rounds_world())
+    assert (d.rounds, d.scans) == (4, 8) and [int(r["flag"]) for r in d.rec] == [0, 0, 1, 1, 1]
+
+
+def test_slices_of_the_planted_scenario():
+    reads, templates, chimeras = dc.planted_world()
+    d, rs, _ = _capped(50, [s for s, _ in reads], [w for _, w in reads], otus=True)
+    assert d.n_entries == 60 and d.n_flagged == len(chimeras) == 20      # a slice of 50 seeds and one of 10; the chimeras are the rarest
+
+
+def test_slices_of_one_entry():
+    seqs, weights, at = dc.flipback_world()
+    d, rs, _ = _capped(1, seqs, weights)
+    assert (d.rounds, d.scans) == (3, 9) and int(d.rec[at["E"]]["parent"]) == at["D"]
 
 
 @pytest.mark.parametrize("S", (16, 32))

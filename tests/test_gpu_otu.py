@@ -1,12 +1,14 @@
 """The OTUs of a run on the device (rtx_otu.hip): rx.otu_cluster against the brute force of otu_common.py and against rx.otu_cluster_host, field
 by field (all but rounds and link_passes), with no tolerance.  The fixtures are those of test_otu_cpu.py, where the brute force itself is
-checked."""
+checked.  The complete world, the block edges and the 65 537 rows are where the work splits: a second link pass under default parameters,
+labels contended on every link, and a numbering over more than one block and more than 256 of them."""
 import numpy as np
 import pytest
 
 import raxtax_amd as rx
 from raxtax_amd import _lib
-from otu_common import MAX_LEN, assert_otus, brute_of, check_clusters, cluster_case, edge_case, edge_rows, seq, table_of
+from otu_common import (BLOCK_EDGES, COMPLETE_MASK, MANY, MAX_LEN, WEIGHTINGS, assert_otus, block_case, brute_of, check_blocks, check_clusters,
+                        check_complete, cluster_case, complete_case, edge_case, edge_rows, many_blocks_case, seq, table_of)
 from tally_common import concat, random_seq
 
 pytestmark = pytest.mark.gpu
@@ -82,3 +84,47 @@ def test_two_runs_and_two_ways_to_the_table_agree():
     assert [bytes(s) for s in from_device.seqs] == [bytes(s) for s in from_host.seqs]
     assert_otus(rx.otu_cluster(from_device), want)
     assert rx.otu_fasta(rx.otu_cluster(from_device)) == rx.otu_fasta(rx.otu_cluster_host(from_host))
+
+
+@pytest.mark.parametrize("weighting", WEIGHTINGS)
+def test_complete_world(weighting):
+    """5 120 rows in 20 blocks and 64 000 links: more than the 4 n the first pass has room for, so the buffer grows under default parameters"""
+    table, want = complete_case(weighting)
+    got = rx.otu_cluster(table)
+    assert got.link_passes == 2
+    assert_otus(got, want)
+    assert_otus(got, rx.otu_cluster_host(table))
+    check_complete(table, got, weighting)
+    assert got.rounds >= 2
+
+
+def test_complete_world_under_long_chains():
+    """a hash of 256 slots and three tags: every probe walks a chain of about twenty rows, most of them to the byte compare"""
+    table, want = complete_case("three")
+    lib = _lib.load()
+    _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_OTU_HASH_MASK, COMPLETE_MASK))
+    try:
+        got = rx.otu_cluster(table)
+    finally:
+        _lib.check(lib.rtx_set_default_option(_lib.RTX_DEFAULT_OTU_HASH_MASK, 0))
+    assert got.link_passes == 2
+    assert_otus(got, want)
+    check_complete(table, got, "three")
+
+
+@pytest.mark.parametrize("last", ("seed", "variant"))
+@pytest.mark.parametrize("n", BLOCK_EDGES)
+def test_block_edges(n, last):
+    table, want, planted = block_case(n, last)
+    got = rx.otu_cluster(table)
+    assert_otus(got, want)
+    check_blocks(got, n, planted)
+
+
+def test_more_than_256_blocks():
+    """row 65 536 is alone in block 256: the scan of the block sums takes a second pass, and its carry is the number of the last seeds"""
+    table, want = many_blocks_case()
+    got = rx.otu_cluster(table)
+    assert got.n_rows == MANY and got.link_passes == 1
+    assert_otus(got, want)
+    assert got.n_otus > MANY * 9 // 10 and got.seed[-1] > 65280       # nearly every row is a seed, one of them in the last full block or behind it

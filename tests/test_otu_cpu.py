@@ -8,7 +8,8 @@ import pytest
 
 import raxtax_amd as rx
 from raxtax_amd import _lib
-from otu_common import MAX_LEN, assert_otus, brute_of, check_clusters, cluster_case, edge_case, pair_links, ranks, seq, table_of
+from otu_common import (BLOCK_EDGES, MANY, MAX_LEN, PLAIN, WEIGHTINGS, assert_otus, block_case, brute_force, brute_of, check_blocks, check_clusters,
+                        check_complete, cluster_case, complete_case, edge_case, equal_length_force, many_blocks_case, pair_links, ranks, seq, table_of)
 from tally_common import random_seq
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -57,6 +58,51 @@ def test_host_against_the_brute_force_on_the_clusters():
     got = rx.otu_cluster_host(table)
     assert_otus(got, want)
     check_clusters(table, got, named)
+
+
+@pytest.mark.parametrize("weighting", WEIGHTINGS)
+def test_host_against_the_brute_force_on_the_complete_world(weighting):
+    table, want = complete_case(weighting)
+    lens = np.array([len(s) for s in table.seqs])
+    a, b = want["links"][:, 0], want["links"][:, 1]
+    assert len(want["links"]) == 64000                     # by the definition: 36 864 + 7 680 substitutions and 1 024 x 19 deletions
+    assert int(((lens[a] == 6) & (lens[b] == 6)).sum()) == 36864 and int(((lens[a] == 5) & (lens[b] == 5)).sum()) == 7680
+    assert int((lens[a] != lens[b]).sum()) == 1024 * 19
+    got = rx.otu_cluster_host(table)
+    assert_otus(got, want)
+    check_complete(table, got, weighting)
+
+
+def test_the_equal_length_restatement_against_the_brute_force():
+    """on the 4 096 rows of 6 codes of the complete world, at sizes from {1, 2, 3}: 36 864 links, every field equal"""
+    table, _ = complete_case("three")
+    rows = table.seqs
+    six = [r for r, s in enumerate(rows) if len(s) == 6]
+    seqs, sizes, counts = [rows[r] for r in six], table.sizes[six], table.counts[six]
+    want, got = brute_force(seqs, sizes, counts), equal_length_force(seqs, sizes, counts)
+    assert len(want["links"]) == 36864 and 1 < len(want["seed"]) < 4096
+    assert sorted(want) == sorted(got)
+    for k in want:
+        assert np.array_equal(np.asarray(got[k]), np.asarray(want[k])), k
+
+
+@pytest.mark.parametrize("last", ("seed", "variant"))
+@pytest.mark.parametrize("n", BLOCK_EDGES)
+def test_host_against_the_brute_force_on_the_block_edges(n, last):
+    table, want, planted = block_case(n, last)
+    got = rx.otu_cluster_host(table)
+    assert_otus(got, want)
+    check_blocks(got, n, planted)
+    assert any(a < 256 <= b for a, b in planted) == (n > 256 + (last == "seed"))
+
+
+def test_host_against_the_restatement_on_65537_rows():
+    table, want = many_blocks_case()
+    assert len(table.seqs) == MANY == 256 * 256 + 1 and {len(s) for s in table.seqs} == {12} and set(np.unique(table.sizes)) == {1, 2, 3, 4}
+    got = rx.otu_cluster_host(table)
+    assert_otus(got, want)
+    assert len(want["links"]) > 1000 and got.n_otus > MANY * 9 // 10 and got.seed[-1] > 65280
+    assert np.bincount(want["seed"] >> 8, minlength=257).min() > 0      # every block of 256 rows holds a seed, the last one its only row
 
 
 @pytest.fixture(scope="module")
