@@ -758,6 +758,73 @@ int64_t rtx_otu_format_fasta(rtx_otu *otu, rtx_tally_table *table, uint64_t mins
 int64_t rtx_otu_format_table(rtx_otu *otu, const char *const *names, uint64_t minsize, char *buf, uint64_t cap);
 int64_t rtx_otu_format_map(rtx_otu *otu, char *buf, uint64_t cap);
 
+/* ---- Fastidious grafting (rtx_graft.hip, host_otu.cpp) ---------------------------------------------------------------------------------------
+ * Swarm's second pass (`swarm -f`): small OTUs of a d = 1 clustering are grafted onto a large OTU that holds a row at most two differences
+ * away.  Exact, integers only, independent of scheduling.
+ *   input        an rtx_tally_table, the rtx_otu made from it, and the boundary B (default 3, at least 1).
+ *   ball         for a row x of len codes, 1 <= len <= RTX_OTU_MAX_LEN, B1(x) is the set of byte strings holding: x itself; x with one code
+ *                replaced by one of A, C, G, T (1, 2, 4, 8) other than the code that is there; x with one code deleted, only if len >= 2 (no
+ *                empty string is formed); x with one of A, C, G, T inserted at any of the len + 1 places, only if len + 1 <=
+ *                RTX_OTU_MAX_LEN.  A row longer than RTX_OTU_MAX_LEN has no ball.
+ *   near         rows x and y are near iff B1(x) and B1(y) share a string, compared as bytes.  Ambiguity codes are ordinary bytes here: two
+ *                rows that differ in two different ambiguity codes at one position are near (either becomes the same plain row).  For rows
+ *                over A, C, G, T near is "Levenshtein distance <= 2".  Every d = 1 link is near.
+ *   heavy/light  OTU k of the input is heavy iff sizes[k] >= B, light otherwise; a row is what its OTU is.
+ *   parent       for a light row x the lowest rank of a heavy row near x; 0xFFFFFFFF if there is none, and for heavy rows.
+ *   graft        a light OTU with at least one member that has a parent is grafted: its graft is the pair (parent[x], x) that is smallest
+ *                in (parent, child) order over its members, its target otu[parent].  Targets are heavy and heavy OTUs are never grafted: no
+ *                chains.  A light OTU that is near light rows only stays as it is.
+ *   result       a new rtx_otu over the same table.  The surviving OTUs keep THEIR OWN seeds and are numbered from 0 in the order of those
+ *                seeds' ranks (the relative order of their old numbers); otu'[r] is the new number of the target of otu[r], or of otu[r]
+ *                itself; members, sizes and counts are the sums.  A grafted row may outrank the seed of its new OTU: the seed is not the
+ *                lowest-ranked member any more.  Links, rounds, link_passes and long_rows are copied from the input, so rtx_otu_view, the
+ *                three rtx_otu_format_* functions and rtx_denovo_check(table, otu) take the object as any other.  B = 1 grafts nothing.
+ *   rtx_otu_graft         on GPU `device` (RTX_ERR_NO_DEVICE without a gfx950).  Every string of the heavy rows' balls is hashed -- in O(1)
+ *                each, from the row's prefix sums of word mixes, as the link kernel of rtx_otu_cluster does; a third sum over the words
+ *                shifted up by one byte serves the insertions -- and sets k = 4 bits of a Bloom filter of 2^bloom_log2 bits (0: the smallest
+ *                power of two with 16 bits per string, under max_bloom_bytes, 0: 8 GiB).  The light rows' balls are tested against it; what
+ *                passes is a candidate (row, kind, position, code), appended through a counter that goes on counting past the buffer
+ *                (initial_candidates; 0: max(1024, 4 x light rows)); a pass that does not fit is run once more in a buffer that does
+ *                (test_passes).  A candidate string v is then built, and every row that has v in ITS ball -- v itself, v with a plain
+ *                code replaced by any code that occurs in a heavy row, v with such a code inserted, v with a plain code deleted -- is
+ *                looked up in the table of all rows: a hash picks the candidates, the bytes decide, always.  A heavy row found lowers
+ *                parent[x] with atomicMin.  The filter decides nothing: a smaller one only makes more candidates.
+ *   rtx_otu_graft_host    the definition restated: a map from every string of the heavy rows' balls to the lowest heavy rank, the light rows'
+ *                balls looked up in it.  Equal to the device's result field by field, except the filter's counters (variants, candidates,
+ *                confirmed, bloom_log2, test_passes: 0) and the times.
+ *                RTX_ERR_INVALID: a table whose row count is not the object's, flags != 0, bloom_log2 neither 0 nor within 5 .. 40.
+ *                A boundary of 0 is the default.  RTX_DEFAULT_OTU_HASH_MASK applies to this stage too, read at every call.
+ *   rtx_otu_graft_view    of a graft result (RTX_ERR_INVALID on any other rtx_otu): parent, old_to_new, the grafts sorted by the old light
+ *                OTU, the counters, and the seconds of upload, Bloom, test, verify, resolve and download.  Valid until the object is destroyed.
+ *   rtx_otu_format_grafts `#light\tsize\tchild\tparent\theavy\tinto\n`, then `otu{k}\t{size}\tuniq{rank}\tuniq{rank}\totu{k}\totu{k'}\n` per
+ *                graft: the old light OTU and its size, child and parent row, the old heavy OTU, the new number; all counted from 1.
+ *                Buffer protocol of rtx_tally_format_fasta. */
+typedef struct rtx_graft_params {
+    uint64_t boundary;
+    uint32_t bloom_log2;
+    uint32_t flags;
+    uint64_t max_bloom_bytes;
+    uint64_t initial_candidates;
+} rtx_graft_params; /* 0 = default everywhere; flags must be 0 */
+typedef struct rtx_graft_view_t {
+    uint64_t n_rows, n_old_otus, n_otus, n_grafts;
+    uint64_t boundary;
+    const uint32_t *parent;     /* [n_rows] */
+    const uint32_t *old_to_new; /* [n_old_otus] */
+    const uint32_t *light, *child, *par, *heavy, *into; /* [n_grafts] old light OTU, child row, parent row, old heavy OTU, new number; from 0 */
+    const uint64_t *size;       /* [n_grafts] the size of the old light OTU */
+    uint64_t heavy_otus, light_otus, heavy_rows, light_rows;
+    uint64_t variants;          /* strings of the heavy rows' balls put into the filter */
+    uint64_t candidates;        /* strings of the light rows' balls that passed it */
+    uint64_t confirmed;         /* candidates with a heavy row behind them */
+    uint32_t bloom_log2, test_passes;
+    double seconds[5];
+} rtx_graft_view_t;
+int rtx_otu_graft(int device, rtx_tally_table *table, rtx_otu *otu, const rtx_graft_params *params, rtx_otu **out);
+int rtx_otu_graft_host(rtx_tally_table *table, rtx_otu *otu, const rtx_graft_params *params, rtx_otu **out);
+int rtx_otu_graft_view(rtx_otu *grafted, rtx_graft_view_t *view);
+int64_t rtx_otu_format_grafts(rtx_otu *grafted, char *buf, uint64_t cap);
+
 /* ---- primer trimming (rtx_trim.hip; rtx_index_set_primers is the host mirror's use of it) ---------------------------------------------------
  * Amplicon reads come with their PCR primers attached, the references without: what `cutadapt` is run for in front of a classifier, on the
  * device.  Exact integers; the host function and the device agree bit for bit.

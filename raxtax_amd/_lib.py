@@ -128,6 +128,17 @@ class OtuView(C.Structure):   # rtx_otu_view_t
                 ("n_links", C.c_uint64), ("link_a", u32p), ("link_b", u32p), ("rounds", C.c_uint32), ("link_passes", C.c_uint32), ("long_rows", C.c_uint64)]
 
 
+class GraftParams(C.Structure):   # rtx_graft_params
+    _fields_ = [("boundary", C.c_uint64), ("bloom_log2", C.c_uint32), ("flags", C.c_uint32), ("max_bloom_bytes", C.c_uint64), ("initial_candidates", C.c_uint64)]
+
+
+class GraftView(C.Structure):   # rtx_graft_view_t
+    _fields_ = [("n_rows", C.c_uint64), ("n_old_otus", C.c_uint64), ("n_otus", C.c_uint64), ("n_grafts", C.c_uint64), ("boundary", C.c_uint64), ("parent", u32p), ("old_to_new", u32p),
+                ("light", u32p), ("child", u32p), ("par", u32p), ("heavy", u32p), ("into", u32p), ("size", u64p), ("heavy_otus", C.c_uint64), ("light_otus", C.c_uint64),
+                ("heavy_rows", C.c_uint64), ("light_rows", C.c_uint64), ("variants", C.c_uint64), ("candidates", C.c_uint64), ("confirmed", C.c_uint64), ("bloom_log2", C.c_uint32),
+                ("test_passes", C.c_uint32), ("seconds", C.c_double * 5)]
+
+
 class DenovoParams(C.Structure):   # rtx_denovo_params
     _fields_ = [("segments", C.c_uint32), ("mindelta", C.c_uint32), ("abskew", C.c_uint32), ("max_parents", C.c_uint32), ("flags", C.c_uint32)]
 
@@ -335,6 +346,10 @@ _SIGNATURES = {
     "rtx_otu_format_fasta": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
     "rtx_otu_format_table": (C.c_int64, [C.c_void_p, C.POINTER(C.c_char_p), C.c_uint64, C.c_char_p, C.c_uint64]),
     "rtx_otu_format_map": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "rtx_otu_graft": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(GraftParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_graft_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraftParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_graft_view": (C.c_int, [C.c_void_p, C.POINTER(GraftView)]),
+    "rtx_otu_format_grafts": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "rtx_denovo_check": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DenovoParams), C.POINTER(C.c_void_p)]),
     "rtx_denovo_check_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenovoParams), C.POINTER(C.c_void_p)]),
     "rtx_denovo_view": (C.c_int, [C.c_void_p, C.POINTER(DenovoView)]),

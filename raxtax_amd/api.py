@@ -1956,6 +1956,25 @@ class Otus:
         check(self._lib.rtx_otu_times(self._h, t))
         self.seconds = tuple(float(x) for x in t)
 
+    def _read_graft(self):
+        """what a graft result carries beside its clustering (otu_graft, otu_graft_host): parent [rows], old_to_new [old otus], grafts [n, 5]
+        (old light OTU, child row, parent row, old heavy OTU, new number; sorted by the first) and graft_info, the counters"""
+        g = _lib.GraftView()
+        check(self._lib.rtx_otu_graft_view(self._h, C.byref(g)))
+
+        def arr(p, n):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+
+        ng = int(g.n_grafts)
+        self.parent = arr(g.parent, int(g.n_rows))
+        self.old_to_new = arr(g.old_to_new, int(g.n_old_otus))
+        self.grafts = np.stack([arr(p, ng) for p in (g.light, g.child, g.par, g.heavy, g.into)], axis=1)
+        self.graft_info = {k: int(getattr(g, k)) for k in ("boundary", "heavy_otus", "light_otus", "heavy_rows", "light_rows", "variants", "candidates", "confirmed",
+                                                            "bloom_log2", "test_passes")}
+        self.graft_info["grafts"] = ng
+        self.graft_info["seconds"] = tuple(float(x) for x in g.seconds)
+        return self
+
     def __del__(self):
         try:
             if self._h:
@@ -2006,6 +2025,31 @@ def otu_table_text(otus: Otus, names: Sequence[str], minsize: int = 1) -> str:
 def otu_map_text(otus: Otus) -> str:
     """rtx_otu_format_map: `uniq{rank}\totu{k}` per row of the table (PREFIX/raxtax.otus.map)."""
     return _otu_text(_lib.load().rtx_otu_format_map, otus)
+
+
+def _graft_params(boundary: int = 0, bloom_log2: int = 0, flags: int = 0, max_bloom_bytes: int = 0, initial_candidates: int = 0):
+    return C.byref(_lib.GraftParams(int(boundary), int(bloom_log2), int(flags), int(max_bloom_bytes), int(initial_candidates)))
+
+
+def otu_graft(otus: Otus, device: int = 0, **params) -> Otus:
+    """rtx_otu_graft: Swarm's fastidious pass on GPU `device` -- the OTUs of `otus` below the boundary grafted onto an OTU at or above it that
+    holds a row at most two differences away.  A new Otus over the same table, with .parent, .old_to_new, .grafts and .graft_info.
+    params: boundary (0: 3), bloom_log2 (0: from the heavy rows), flags (0), max_bloom_bytes (0: 8 GiB), initial_candidates (0: a default)."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_graft(int(device), otus.table._h, otus._h, _graft_params(**params), C.byref(h)))
+    return Otus(h, otus.table)._read_graft()
+
+
+def otu_graft_host(otus: Otus, **params) -> Otus:
+    """rtx_otu_graft_host: the same from the definition, on the host (the filter's counters stay 0)."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_graft_host(otus.table._h, otus._h, _graft_params(**params), C.byref(h)))
+    return Otus(h, otus.table)._read_graft()
+
+
+def otu_grafts_text(otus: Otus) -> str:
+    """rtx_otu_format_grafts: `otu{k}\t{size}\tuniq{child}\tuniq{parent}\totu{heavy}\totu{new}` per graft (PREFIX/raxtax.otus.grafts)."""
+    return _otu_text(_lib.load().rtx_otu_format_grafts, otus)
 
 
 class DenovoParams:

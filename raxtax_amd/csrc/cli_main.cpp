@@ -21,6 +21,9 @@
 //    uniques): `>otu{k};size={N};seed=uniq{rank}` and the seed's sequence (rtx_otu_format_fasta); PREFIX/raxtax.otus.map, `uniq{rank}\totu{k}` per
 //    distinct read; with --tags also PREFIX/raxtax.otus.tsv, the OTU x sample table of read counts.  OTUs below N (default 1) are left out of
 //    raxtax.otus and raxtax.otus.tsv, the numbers stay.
+//   PREFIX/raxtax.otus.grafts (--uniques --otus --fastidious [--fastidious-boundary N]) Swarm's fastidious pass on the first device (rtx_graft.hip), right after the
+//    clustering: an OTU below N reads (default 3) is grafted onto an OTU of at least N that holds a distinct read at most two differences away.  One line per
+//    graft (rtx_otu_format_grafts); raxtax.otus, .map and .tsv are then those of the grafted OTUs, and --denovo checks those.
 //   PREFIX/raxtax.otus.denovo (--uniques --otus --denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]) the de novo chimera check of the
 //    OTUs on the first device (rtx_denovo.hip), right after the clustering: is an OTU's seed the head of one more abundant OTU of the run joined to the tail
 //    of another?  A header line and one line per OTU (rtx_denovo_format_records); PREFIX/raxtax.otus.clean, the lines of raxtax.otus of the OTUs that
@@ -251,6 +254,9 @@ struct Options {
     bool otus = false;            // --otus: the table of --uniques clustered into OTUs (rtx_otu.hip), PREFIX/raxtax.otus, raxtax.otus.map (and raxtax.otus.tsv with --tags)
     uint64_t otus_minsize = 1;    // --otus-minsize N
     std::string otus_opts;        // that one, likewise
+    bool fastidious = false;      // --fastidious: the small OTUs grafted onto large ones two differences away (rtx_graft.hip), PREFIX/raxtax.otus.grafts; the OTU files are the grafted ones
+    uint64_t fastidious_boundary = 0;  // --fastidious-boundary N (0: the library's default, 3)
+    std::string fastidious_opts;  // that one, likewise
     bool denovo = false;          // --denovo: the OTUs checked for chimeras of more abundant OTUs (rtx_denovo.hip), PREFIX/raxtax.otus.denovo, raxtax.otus.clean (and .clean.tsv with --tags)
     rtx_denovo_params denovo_params{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA, RTX_DENOVO_DEFAULT_ABSKEW, 0, 0};  // --denovo-segments S, --denovo-mindelta N, --denovo-abskew N
     std::string denovo_opts;      // those three, likewise
@@ -288,6 +294,7 @@ int parse_args(int argc, char **argv, Options &o) {
         {"--uniques-max-entries", 'p', 1, 0x7FFFFFFE, &o.uniques_max_entries, &o.uniques_opts},
         {"--uniques-max-bytes", 'p', 1, LLONG_MAX, &o.uniques_max_bytes, &o.uniques_opts},
         {"--otus-minsize", 'p', 1, LLONG_MAX, &o.otus_minsize, &o.otus_opts},
+        {"--fastidious-boundary", 'p', 1, LLONG_MAX, &o.fastidious_boundary, &o.fastidious_opts},
         {"--denovo-abskew", 'u', 1, 0x7FFFFFFF, &o.denovo_params.abskew, &o.denovo_opts},
         {"--denovo-mindelta", 'u', 0, RTX_CHIMERA_MAX_QUERY, &o.denovo_params.mindelta, &o.denovo_opts},
         {"--denovo-segments", 'u', 2, RTX_CHIMERA_MAX_SEGMENTS, &o.denovo_params.segments, &o.denovo_opts},
@@ -398,12 +405,13 @@ int parse_args(int argc, char **argv, Options &o) {
         }
         else if (a == "--uniques") o.uniques = true;
         else if (a == "--otus") o.otus = true;
+        else if (a == "--fastidious") o.fastidious = true;
         else if (a == "--denovo") o.denovo = true;
         else if (a == "--batch") o.chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") o.block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--fastidious [--fastidious-boundary N]] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
             return 64;
         }
@@ -436,6 +444,7 @@ struct Identity {
         {"contaminants", true, ""},   // --contaminants with its settings and the set's fingerprint: contaminants have no lines
         {"uniques", true, ""},        // --uniques with its settings: the table is the run's, a resumed run would miss reads
         {"otus", true, ""},           // --otus with its setting: its files are the run's
+        {"fastidious", true, ""},     // --fastidious with its boundary: the OTU files are the grafted ones
         {"denovo", true, ""},         // --denovo with its three settings, likewise
     };
     std::string &operator[](const std::string &key) {
@@ -680,6 +689,9 @@ int validate(Options &o, Plan &p) {
     if (orphan(o.otus ? "--otus" : "", o.uniques, "clusters the distinct reads of the run and needs --uniques")) return 64;
     if (o.uniques) id["uniques"] = "minsize=" + std::to_string(o.uniques_minsize) + " max_entries=" + std::to_string(o.uniques_max_entries) + " max_bytes=" + std::to_string(o.uniques_max_bytes);
     if (o.otus) id["otus"] = "minsize=" + std::to_string(o.otus_minsize);
+    if (orphan(o.fastidious_opts, o.fastidious, "sets which OTUs are grafted and needs --fastidious")) return 64;
+    if (orphan(o.fastidious ? "--fastidious" : "", o.otus, "grafts the small OTUs of the run onto the large ones and needs --otus")) return 64;
+    if (o.fastidious) id["fastidious"] = "boundary=" + std::to_string(o.fastidious_boundary ? o.fastidious_boundary : 3);
     if (orphan(o.denovo_opts, o.denovo, "sets how the OTUs are checked for chimeras and needs --denovo")) return 64;
     if (orphan(o.denovo ? "--denovo" : "", o.otus, "checks the OTUs of the run for chimeras and needs --otus")) return 64;
     if (o.denovo)
@@ -726,9 +738,9 @@ std::vector<Report> report_table(const Options &o, const Plan &p, Sink &s) {
             {"raxtax.screen", p.screen_on, "label\tlength\twindows\thits\tfirst\tsource\tverdict\n", &s.screen}};
 }
 
-// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --denovo): a run that starts over removes them
+// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --fastidious, --denovo): a run that starts over removes them
 const char *const kEndOfRunFiles[] = {"raxtax.profile", "raxtax.samples", "raxtax.uniques", "raxtax.uniques.tsv", "raxtax.otus", "raxtax.otus.map", "raxtax.otus.tsv",
-                                      "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv"};
+                                      "raxtax.otus.grafts", "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv"};
 
 // check_incomplete_output (io.rs:156-187): keep only the lines whose first field is a finished query
 void purge_incomplete(const std::string &path, const std::set<std::string> &done, bool keep_header = false) {
@@ -1388,6 +1400,19 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
         std::string otu_fasta, otu_map, otu_table;
         trc = rtx_otu_cluster(o.devices[0], sum, nullptr, &otu);
         if (trc == RTX_OK) trc = rtx_otu_view(otu, &ov);
+        rtx_graft_view_t gv{};
+        std::string grafts;
+        if (trc == RTX_OK && o.fastidious) {  // the small OTUs onto the large ones: everything below is written of the grafted object (ov keeps the numbers of the clustering)
+            rtx_otu *grafted = nullptr;
+            const rtx_graft_params gp{o.fastidious_boundary, 0, 0, 0, 0};
+            trc = rtx_otu_graft(o.devices[0], sum, otu, &gp, &grafted);
+            if (trc == RTX_OK) {
+                rtx_otu_destroy(otu);
+                otu = grafted;
+                trc = rtx_otu_graft_view(otu, &gv);
+            }
+            if (trc == RTX_OK) trc = format_two_pass(grafts, [&](char *buf, uint64_t cap) { return rtx_otu_format_grafts(otu, buf, cap); });
+        }
         if (trc == RTX_OK) trc = format_two_pass(otu_fasta, [&](char *buf, uint64_t cap) { return rtx_otu_format_fasta(otu, sum, o.otus_minsize, buf, cap); });
         if (trc == RTX_OK) trc = format_two_pass(otu_map, [&](char *buf, uint64_t cap) { return rtx_otu_format_map(otu, buf, cap); });
         if (trc == RTX_OK && p.tags_on) trc = format_two_pass(otu_table, [&](char *buf, uint64_t cap) { return rtx_otu_format_table(otu, names.data(), o.otus_minsize, buf, cap); });
@@ -1396,6 +1421,11 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
         if (ov.long_rows) fprintf(stderr, "[INFO ] --otus: %llu distinct reads are longer than %d bases and stand alone\n", (ull)ov.long_rows, RTX_OTU_MAX_LEN);
         if (!write_whole(o.prefix + "/raxtax.otus", otu_fasta) || !write_whole(o.prefix + "/raxtax.otus.map", otu_map)) return 74;
         if (p.tags_on && !write_whole(o.prefix + "/raxtax.otus.tsv", otu_table)) return 74;
+        if (o.fastidious) {
+            fprintf(stderr, "[INFO ] --fastidious: boundary %llu, %llu heavy and %llu light OTUs, %llu grafts, %llu OTUs left\n", (ull)gv.boundary, (ull)gv.heavy_otus, (ull)gv.light_otus,
+                    (ull)gv.n_grafts, (ull)gv.n_otus);
+            if (!write_whole(o.prefix + "/raxtax.otus.grafts", grafts)) return 74;
+        }
         if (o.denovo) {  // the OTUs against the more abundant OTUs of the run
             rtx_denovo *&dn = own.dn;
             rtx_denovo_view_t dv{};

@@ -25,6 +25,7 @@
 
 #include "host_otu.hpp"
 #include "rtx_derep_dev.hpp"
+#include "rtx_otu_dev.hpp"  // plain, wave_incl_scan_u64, shifted_word, block_scan_incl_u32: shared with rtx_graft.hip
 #include "rtx_stage.hpp"
 #include "rtx_wave.hpp"
 
@@ -56,22 +57,6 @@ struct OtuParams {
     uint32_t *members;       // [n] (the first n_otus in use)
     uint32_t *n_otus;        // [1]
 };
-
-__device__ __forceinline__ bool plain(uint32_t c) { return c == 1u || c == 2u || c == 4u || c == 8u; }
-
-__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d, 64);
-        if (lane >= (uint32_t)d) v += o;
-    }
-    return v;
-}
-
-// word j of the row X (nw words, zero-padded) shifted down by one byte: what word j holds once a code in front of it is deleted
-__device__ __forceinline__ uint64_t shifted_word(const uint64_t *X, uint32_t nw, uint32_t j) {
-    return (X[j] >> 8) | (j + 1u < nw ? X[j + 1u] << 56 : 0ull);
-}
 
 __global__ __launch_bounds__(256) void otu_insert_kernel(OtuParams p) {
     const uint32_t lane = threadIdx.x & 63u;
@@ -192,24 +177,6 @@ __global__ __launch_bounds__(256) void otu_label_kernel(OtuParams p, uint64_t n_
         atomicMin(p.label + e.x, lb);
         p.changed[round] = 1u;
     }
-}
-
-// Inclusive scan of v over the 256 threads of the block (every thread calls); *total = the block's sum.  lds: 4 words.
-__device__ __forceinline__ uint32_t block_scan_incl_u32(uint32_t v, uint32_t *lds, uint32_t *total) {
-    const uint32_t w = threadIdx.x >> 6;
-    v = wave_incl_scan_u32(v);
-    if ((threadIdx.x & 63u) == 63u) lds[w] = v;
-    __syncthreads();
-    uint32_t add = 0, tot = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; k++) {
-        const uint32_t s = lds[k];
-        if (k < w) add += s;
-        tot += s;
-    }
-    __syncthreads();  // (lds may be written again)
-    *total = tot;
-    return v + add;
 }
 
 // (no thread leaves early in the three kernels of the scan: the block scans as a whole)
@@ -421,6 +388,7 @@ int cluster(OtuStage *st, const rtx_tally_view &v, const rtx_otu_params &prm, rt
 
 namespace rtxi {
 void set_otu_hash_mask(uint64_t mask) { g_otu_hash_mask.store(mask); }
+uint64_t otu_hash_mask() { return g_otu_hash_mask.load(); }  // (rtx_graft.hip hashes under the same mask)
 }  // namespace rtxi
 
 extern "C" int rtx_otu_cluster(int device, rtx_tally_table *table, const rtx_otu_params *params, rtx_otu **out) {
