@@ -54,7 +54,8 @@ extern "C" {
                                 rtx_index_profile_begin_samples / _read_samples / rtx_batch_prefetch_samples / rtx_sample_profile_merge /
                                 rtx_sample_table_format: the same; and with the contaminant screen, rtx_screen_* / rtx_index_set_screen /
                                 rtx_index_screen / rtx_raxtax_last_screen / rtx_raxtax_multi_ex8: the same; and with the de novo chimera check of a
-                                run, rtx_denovo_*: exports only) */
+                                run, rtx_denovo_*: exports only; and with the consensus taxonomy of the OTUs, rtx_otu_taxonomy* /
+                                rtx_result_best_lineages: exports only) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -824,6 +825,91 @@ int rtx_otu_graft(int device, rtx_tally_table *table, rtx_otu *otu, const rtx_gr
 int rtx_otu_graft_host(rtx_tally_table *table, rtx_otu *otu, const rtx_graft_params *params, rtx_otu **out);
 int rtx_otu_graft_view(rtx_otu *grafted, rtx_graft_view_t *view);
 int64_t rtx_otu_format_grafts(rtx_otu *grafted, char *buf, uint64_t cap);
+
+/* ---- Consensus taxonomy of the OTUs (rtx_otutax.hip, host_otutax.cpp) ------------------------------------------------------------------------
+ * Which taxon an OTU is: the deepest taxon that an agreed share of the OTU's reads reaches with confidence, with the support at every level.
+ * Exact, integers only, independent of scheduling.
+ *   record       of a row r: what the taxon profile takes of a query (rtx_index_profile_begin) under a cutoff c -- kind[r], RTX_LIN_*; L[r], the
+ *                leading levels of its best lineage whose confidence reaches c; node[r] = a_{L-1}; hund[r][0 .. L), their hundredths.  The
+ *                path a_0 .. a_{L-1} follows from node[r] over node_parent, a_0 a child of the root; L == 0 for the kinds that are not
+ *                classified (node and hund are then not read).  rtx_result_best_lineages makes the records of a batch from its download.
+ *   weight       w_r, the reads a row stands for (rtx_tally_view.sizes), at least 1.
+ *   size         S_k = the sum of w_r over ALL rows with otu[r] == k, whatever their kind (rtx_otu_view_t.sizes[k]); members[k] counts them.
+ *   clade        clade_k[n] = the sum of w_r over the members of k whose path contains node n; conf_k[n] = the sum of w_r x hund[r][d] over
+ *                the same members, d the level of n.
+ *   consensus    under an agreement percentage P, 51 <= P <= 100: start at the root; descend to the child n with clade_k[n] x 100 >= P x S_k;
+ *                stop where no child qualifies.  P > 50: at most one child qualifies, there are no ties and no tie rule.
+ *   result       per OTU: depth[k] (may be 0); node[k], the last node of the walk, 0 (the root) at depth 0; clade[k][d] and conf[k][d] for
+ *                d < depth[k] (0 from there to `stride`, the deepest L of the call, at least 1); classified[k] = the sum of w_r over the
+ *                members of kind RTX_LIN_CLASSIFIED; seed_rel[k], how the path of row seed[k] relates to the consensus path: 0 equal, 1 the
+ *                consensus is a proper prefix of the seed's path, 2 the seed's path is a proper prefix of the consensus, 3 they diverge.
+ *                Nothing is said about the level where the walk stops: without a majority there is no well-defined runner-up.
+ *   refused      RTX_ERR_INVALID, on the host, before anything is uploaded: a null array; P outside 51 .. 100; flags != 0; 2^32 - 1 rows or
+ *                more; an OTU number >= n_otus; an OTU without a row (its S_k would be 0); a seed >= n_rows; a weight of 0; 100 x the sum of all weights >= 2^64; a kind above 2; L != 0
+ *                on a row that is not classified, or L == 0 on one that is; L above RTX_MAX_DEPTH or hund_stride; a node id >= n_nodes; an L
+ *                that is not the depth of its node (above it there is no such path, below it the node is not a_{L-1}); a hundredths value
+ *                above 100; a node_parent that is not below its node (the nodes come breadth first, the root is node 0).  Of the
+ *                rtx_nodes_view only n_nodes and node_parent are read.
+ *   rtx_otu_taxonomy       on GPU `device` (RTX_ERR_NO_DEVICE without a gfx950).  A kernel writes every row's path; the host lays the members
+ *                out per OTU (rank order) and packs consecutive OTUs of at most 64 members into one wave while their members total at most
+ *                64 (packed_waves); every larger OTU takes a workgroup of its own (big_otus).  Level by level the members still on the
+ *                consensus path name their node; a one-counter majority summary picks the candidate, the candidate's clade and conf are
+ *                summed exactly in 64 bits, and the test above decides.  No atomics: one lane writes an OTU's result.
+ *   rtx_otu_taxonomy_host  the definition restated: per OTU a map node -> (clade, conf) over all members' paths, then the descent.  Equal to
+ *                the device's result field by field, except packed_waves and big_otus (0) and the times.
+ *   rtx_otu_taxonomy_view  valid until the object is destroyed.  rtx_otu_taxonomy_times: seconds of checks, plan and upload, the path kernel,
+ *                the consensus kernels, the download; all 0 for a host result.
+ *   rtx_otu_taxonomy_format  "#otu<TAB>size<TAB>members<TAB>classified<TAB>depth<TAB>taxon<TAB>lineage<TAB>support<TAB>mean_conf<TAB>seed", then one line
+ *                per OTU whose size reaches minsize, `otu{k}` counted from 1 as rtx_otu_format_fasta counts: lineage = the first `depth`
+ *                levels of lineages[node_begin[node]], taxon = the last of them (as rtx_profile_format prints them); support = per level
+ *                (clade x 10000 + S / 2) / S with two decimals, comma-separated; mean_conf = per level (conf + clade / 2) / clade hundredths
+ *                likewise; seed = one of `= < > x` for seed_rel 0 .. 3; a depth of 0 prints `-` in the four taxonomy columns.  Every line
+ *                ends in '\n'.  `tree` must be the tree of the nodes (RTX_ERR_INVALID when the node counts differ).  Buffer protocol of
+ *                rtx_profile_format.
+ *   rtx_result_best_lineages  the records of the n_queries of a download, by the per-query step of the taxon profile itself: cutoff 1 .. 100,
+ *                flags RTX_SKIP_EXACT_MATCHES | RTX_RAW_CONFIDENCE (either one: no override), exact_ids / exact_off the exact matches of the
+ *                batch (rtx_batch_exact_matches) or NULL / NULL: no query has one.  kind, L, node: [n_queries]; hund: [n_queries][hund_stride],
+ *                zero from L on; hund_stride at least the deepest lineage of the tree.  A view without the byte arrays (hand-made) has its
+ *                confidences converted as rtx_result_pack converts them.  No device involved. */
+#define RTX_LIN_UNCLASSIFIABLE 0u
+#define RTX_LIN_UNCLASSIFIED 1u
+#define RTX_LIN_CLASSIFIED 2u
+typedef struct rtx_otutax rtx_otutax;
+typedef struct rtx_lineage_records {
+    const uint8_t *kind;  /* [n_rows] RTX_LIN_* */
+    const uint8_t *L;     /* [n_rows] */
+    const uint32_t *node; /* [n_rows] a_{L-1} */
+    const uint8_t *hund;  /* [n_rows][hund_stride] */
+    uint32_t hund_stride;
+} rtx_lineage_records;
+typedef struct rtx_otu_taxonomy_params {
+    uint32_t agree_pct; /* 51 .. 100; 0: 51 */
+    uint32_t flags;     /* 0 */
+} rtx_otu_taxonomy_params;
+typedef struct rtx_otu_taxonomy_view_t {
+    uint64_t n_rows, n_otus;
+    uint32_t n_nodes, agree_pct;
+    uint32_t stride;            /* levels per OTU in clade and conf */
+    const uint64_t *sizes;      /* [n_otus] S_k */
+    const uint64_t *members;    /* [n_otus] rows */
+    const uint64_t *classified; /* [n_otus] */
+    const uint32_t *depth;      /* [n_otus] */
+    const uint32_t *node;       /* [n_otus] */
+    const uint8_t *seed_rel;    /* [n_otus] 0 .. 3 */
+    const uint64_t *clade;      /* [n_otus x stride] */
+    const uint64_t *conf;       /* [n_otus x stride] */
+    uint64_t packed_waves, big_otus; /* the device's plan; host: 0 */
+} rtx_otu_taxonomy_view_t;
+int rtx_otu_taxonomy(int device, uint64_t n_rows, const uint32_t *otu, const uint64_t *weight, uint64_t n_otus, const uint32_t *seed,
+                     const rtx_lineage_records *records, const rtx_nodes_view *nodes, const rtx_otu_taxonomy_params *params, rtx_otutax **out);
+int rtx_otu_taxonomy_host(uint64_t n_rows, const uint32_t *otu, const uint64_t *weight, uint64_t n_otus, const uint32_t *seed,
+                          const rtx_lineage_records *records, const rtx_nodes_view *nodes, const rtx_otu_taxonomy_params *params, rtx_otutax **out);
+int rtx_otu_taxonomy_view(rtx_otutax *tax, rtx_otu_taxonomy_view_t *view);
+int rtx_otu_taxonomy_times(const rtx_otutax *tax, double seconds[4]);
+void rtx_otu_taxonomy_destroy(rtx_otutax *tax);
+int64_t rtx_otu_taxonomy_format(rtx_otutax *tax, const rtx_tree *tree, uint64_t minsize, char *buf, uint64_t cap);
+int rtx_result_best_lineages(const rtx_tree *tree, const rtx_result_view *res, const uint32_t *exact_ids, const uint64_t *exact_off, uint32_t cutoff_hundredths,
+                             uint32_t flags, uint8_t *kind, uint8_t *L, uint32_t *node, uint8_t *hund, uint32_t hund_stride);
 
 /* ---- primer trimming (rtx_trim.hip; rtx_index_set_primers is the host mirror's use of it) ---------------------------------------------------
  * Amplicon reads come with their PCR primers attached, the references without: what `cutadapt` is run for in front of a classifier, on the

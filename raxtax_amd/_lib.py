@@ -27,6 +27,7 @@ RTX_DEFAULT_TALLY_HASH_MASK = 4    # rtx_set_default_option: the hash of rtx_tal
 RTX_DEFAULT_OTU_HASH_MASK = 5      # rtx_set_default_option: the hashes of rtx_otu_cluster ANDed with a mask (tests)
 RTX_DEFAULT_CHIMERA_SLICE = 6      # rtx_set_default_option: a cap on the reads / entries of a slice of rtx_chimera_run / rtx_denovo_check (tests)
 RTX_OTU_MAX_LEN = 4096
+RTX_LIN_UNCLASSIFIABLE, RTX_LIN_UNCLASSIFIED, RTX_LIN_CLASSIFIED = 0, 1, 2   # rtx_lineage_records.kind
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
 
 RTX_TRIM_5P, RTX_TRIM_3P = 0, 1      # rtx_trim_pattern.end
@@ -112,6 +113,19 @@ class ScreenParams(C.Structure):   # rtx_screen_params
 
 class TallyParams(C.Structure):   # rtx_tally_params
     _fields_ = [("n_samples", C.c_uint32), ("max_entries", C.c_uint64), ("max_bytes", C.c_uint64), ("initial_entries", C.c_uint64), ("initial_bytes", C.c_uint64)]
+
+
+class LineageRecords(C.Structure):   # rtx_lineage_records
+    _fields_ = [("kind", u8p), ("L", u8p), ("node", u32p), ("hund", u8p), ("hund_stride", C.c_uint32)]
+
+
+class OtuTaxonomyParams(C.Structure):   # rtx_otu_taxonomy_params
+    _fields_ = [("agree_pct", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class OtuTaxonomyView(C.Structure):   # rtx_otu_taxonomy_view_t
+    _fields_ = [("n_rows", C.c_uint64), ("n_otus", C.c_uint64), ("n_nodes", C.c_uint32), ("agree_pct", C.c_uint32), ("stride", C.c_uint32), ("sizes", u64p), ("members", u64p),
+                ("classified", u64p), ("depth", u32p), ("node", u32p), ("seed_rel", u8p), ("clade", u64p), ("conf", u64p), ("packed_waves", C.c_uint64), ("big_otus", C.c_uint64)]
 
 
 class TallyView(C.Structure):   # rtx_tally_view
@@ -350,6 +364,13 @@ _SIGNATURES = {
     "rtx_otu_graft_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraftParams), C.POINTER(C.c_void_p)]),
     "rtx_otu_graft_view": (C.c_int, [C.c_void_p, C.POINTER(GraftView)]),
     "rtx_otu_format_grafts": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "rtx_otu_taxonomy": (C.c_int, [C.c_int, C.c_uint64, u32p, u64p, C.c_uint64, u32p, C.POINTER(LineageRecords), C.POINTER(NodesView), C.POINTER(OtuTaxonomyParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_taxonomy_host": (C.c_int, [C.c_uint64, u32p, u64p, C.c_uint64, u32p, C.POINTER(LineageRecords), C.POINTER(NodesView), C.POINTER(OtuTaxonomyParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_taxonomy_view": (C.c_int, [C.c_void_p, C.POINTER(OtuTaxonomyView)]),
+    "rtx_otu_taxonomy_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "rtx_otu_taxonomy_destroy": (None, [C.c_void_p]),
+    "rtx_otu_taxonomy_format": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_char_p, C.c_uint64]),
+    "rtx_result_best_lineages": (C.c_int, [C.c_void_p, C.POINTER(ResultView), u32p, u64p, C.c_uint32, C.c_uint32, u8p, u8p, u32p, u8p, C.c_uint32]),
     "rtx_denovo_check": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.POINTER(DenovoParams), C.POINTER(C.c_void_p)]),
     "rtx_denovo_check_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(DenovoParams), C.POINTER(C.c_void_p)]),
     "rtx_denovo_view": (C.c_int, [C.c_void_p, C.POINTER(DenovoView)]),

@@ -2052,6 +2052,141 @@ def otu_grafts_text(otus: Otus) -> str:
     return _otu_text(_lib.load().rtx_otu_format_grafts, otus)
 
 
+@dataclass
+class Lineages:
+    """The records of a batch (rtx_lineage_records): per query what the taxon profile takes of it under a cutoff -- kind (_lib.RTX_LIN_*),
+    L (the leading levels of its best lineage that reach the cutoff), node (a_{L-1}) and hund [n, stride] (their hundredths, 0 from L on)."""
+    kind: np.ndarray
+    L: np.ndarray
+    node: np.ndarray
+    hund: np.ndarray
+
+    def __len__(self) -> int:
+        return len(self.kind)
+
+    def _c(self) -> "_lib.LineageRecords":
+        self.kind = np.ascontiguousarray(self.kind, dtype=np.uint8)
+        self.L = np.ascontiguousarray(self.L, dtype=np.uint8)
+        self.node = np.ascontiguousarray(self.node, dtype=np.uint32)
+        h = np.ascontiguousarray(self.hund, dtype=np.uint8)
+        self.hund = h.reshape(len(self.kind), -1) if len(self.kind) else h.reshape(0, max(1, h.shape[-1]))
+        return _lib.LineageRecords(ptr(self.kind, u8p), ptr(self.L, u8p), ptr(self.node, u32p), ptr(self.hund, u8p), int(self.hund.shape[1]))
+
+    @staticmethod
+    def concat(parts: Sequence["Lineages"]) -> "Lineages":
+        return Lineages(*(np.concatenate([getattr(p, f) for p in parts]) for f in ("kind", "L", "node", "hund")))
+
+
+def best_lineages(tree: Tree, result: Result, cutoff: int = 80, skip_exact_matches: bool = False, raw_confidence: bool = False, exact=None) -> Lineages:
+    """rtx_result_best_lineages: the records of a classified batch, by the per-query step of the taxon profile.  cutoff in hundredths (1 .. 100);
+    exact = (ids, off), the exact matches of the batch (Index.exact_matches), or None: no query has one."""
+    nq, nr = int(result.n_queries), len(result.row_node)
+    stride = int(result.row_conf.shape[1]) if result.row_conf.ndim == 2 else RTX_MAX_DEPTH
+    keep = dict(t=np.ascontiguousarray(result.t, np.uint32), status=np.ascontiguousarray(result.status, np.uint8),
+                gs=np.ascontiguousarray(result.global_signal, np.float64), begin=np.ascontiguousarray(result.row_off[:-1], np.uint64),
+                count=np.ascontiguousarray(np.diff(result.row_off.astype(np.int64)), np.uint32), lin=np.ascontiguousarray(result.row_lineage, np.uint32),
+                node=np.ascontiguousarray(result.row_node, np.uint32), depth=np.ascontiguousarray(result.row_depth, np.uint32),
+                conf=np.ascontiguousarray(result.row_conf, np.float64), local=np.ascontiguousarray(result.row_local_signal, np.float64),
+                depth8=np.ascontiguousarray(result.row_depth, np.uint8), hund=np.ascontiguousarray(result.row_conf_hundredths, np.uint8))
+    view = ResultView(nq, nr, ptr(keep["t"], u32p), ptr(keep["status"], u8p), ptr(keep["gs"], f64p), ptr(keep["begin"], u64p), ptr(keep["count"], u32p),
+                      ptr(keep["lin"], u32p), ptr(keep["node"], u32p), ptr(keep["depth"], u32p), ptr(keep["conf"], f64p), ptr(keep["local"], f64p),
+                      stride, ptr(keep["depth8"], u8p), ptr(keep["hund"], u8p))
+    ids = off = None
+    if exact is not None:
+        ids = np.ascontiguousarray(exact[0], np.uint32)
+        off = np.ascontiguousarray(exact[1], np.uint64)
+        if len(ids) == 0:
+            ids = np.zeros(1, np.uint32)
+    flags = (RTX_SKIP_EXACT_MATCHES if skip_exact_matches else 0) | (RTX_RAW_CONFIDENCE if raw_confidence else 0)
+    hs = max(stride, 1)
+    out = Lineages(np.zeros(nq, np.uint8), np.zeros(nq, np.uint8), np.zeros(nq, np.uint32), np.zeros((nq, hs), np.uint8))
+    check(_lib.load().rtx_result_best_lineages(tree._h, C.byref(view), None if ids is None else ptr(ids, u32p), None if off is None else ptr(off, u64p),
+                                               int(cutoff), flags, ptr(out.kind, u8p), ptr(out.L, u8p), ptr(out.node, u32p), ptr(out.hund, u8p), hs))
+    return out
+
+
+class OtuTaxonomy:
+    """The consensus taxonomy of the OTUs (rtx_otu_taxonomy / rtx_otu_taxonomy_host): per OTU sizes, members, classified, depth, node, seed_rel
+    (0 equal, 1 the consensus is a prefix of the seed's path, 2 the other way round, 3 they diverge) and clade, conf [otus, stride]; agree_pct;
+    packed_waves, big_otus (the device's plan) and seconds (checks, plan and upload; path kernel; consensus kernels; download)."""
+
+    def __init__(self, handle):
+        self._lib = _lib.load()
+        self._h = handle
+        v = _lib.OtuTaxonomyView()
+        check(self._lib.rtx_otu_taxonomy_view(self._h, C.byref(v)))
+        no, st = int(v.n_otus), int(v.stride)
+
+        def arr(p, n, dtype, shape=None):
+            if n == 0:
+                return np.zeros(shape if shape else (0,), dtype)
+            return np.ctypeslib.as_array(p, shape=(n,)).copy().reshape(shape if shape else (n,))
+
+        self.n_rows, self.n_otus, self.n_nodes, self.agree_pct, self.stride = int(v.n_rows), no, int(v.n_nodes), int(v.agree_pct), st
+        self.sizes = arr(v.sizes, no, np.uint64)
+        self.members = arr(v.members, no, np.uint64)
+        self.classified = arr(v.classified, no, np.uint64)
+        self.depth = arr(v.depth, no, np.uint32)
+        self.node = arr(v.node, no, np.uint32)
+        self.seed_rel = arr(v.seed_rel, no, np.uint8)
+        self.clade = arr(v.clade, no * st, np.uint64, (no, st))
+        self.conf = arr(v.conf, no * st, np.uint64, (no, st))
+        self.packed_waves, self.big_otus = int(v.packed_waves), int(v.big_otus)
+        t = (C.c_double * 4)()
+        check(self._lib.rtx_otu_taxonomy_times(self._h, t))
+        self.seconds = tuple(float(x) for x in t)
+
+    def text(self, tree: Tree, minsize: int = 0) -> str:
+        """rtx_otu_taxonomy_format: a header line and one line per OTU whose size reaches minsize (PREFIX/raxtax.otus.tax of raxtax-hip --otus-tax)."""
+        fn = self._lib.rtx_otu_taxonomy_format
+        n = check(fn(self._h, tree._h, int(minsize), None, 0))
+        buf = C.create_string_buffer(max(n, 1))
+        check(fn(self._h, tree._h, int(minsize), buf, n))
+        return buf.raw[:n].decode()
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._lib.rtx_otu_taxonomy_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+def _otutax_args(tree, otus, lineages, agree):
+    """otus: an Otus object, or (otu [rows], weight [rows], seed [otus]); tree: a Tree, or the parent array of its nodes"""
+    if isinstance(otus, Otus):
+        otu, weight, seed = otus.otu, otus.table.sizes, otus.seed
+    else:
+        otu, weight, seed = otus
+    otu = np.ascontiguousarray(otu, np.uint32)
+    weight = np.ascontiguousarray(weight, np.uint64)
+    seed = np.ascontiguousarray(seed, np.uint32)
+    if len(weight) != len(otu) or len(lineages) != len(otu):
+        raise ValueError(f"{len(otu)} rows, {len(weight)} weights, {len(lineages)} records")
+    parent = np.ascontiguousarray(tree.nodes()["parent"] if isinstance(tree, Tree) else tree, np.uint32)
+    nodes = NodesView(len(parent), None, None, None, None, ptr(parent, u32p), None)
+    keep = (otu, weight, seed, parent, lineages)
+    return keep, (len(otu), ptr(otu, u32p), ptr(weight, u64p), len(seed), ptr(seed, u32p), C.byref(lineages._c()), C.byref(nodes),
+                  C.byref(_lib.OtuTaxonomyParams(int(agree), 0)))
+
+
+def otu_taxonomy(tree, otus, lineages: Lineages, device: int = 0, agree: int = 51) -> OtuTaxonomy:
+    """rtx_otu_taxonomy on GPU `device`: per OTU the deepest taxon that `agree` percent (51 .. 100) of its reads reach, with the support of every level."""
+    keep, args = _otutax_args(tree, otus, lineages, agree)
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_taxonomy(int(device), *args, C.byref(h)))
+    return OtuTaxonomy(h)
+
+
+def otu_taxonomy_host(tree, otus, lineages: Lineages, agree: int = 51) -> OtuTaxonomy:
+    """rtx_otu_taxonomy_host: the same from the definition, on the host."""
+    keep, args = _otutax_args(tree, otus, lineages, agree)
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_taxonomy_host(*args, C.byref(h)))
+    return OtuTaxonomy(h)
+
+
 class DenovoParams:
     """rtx_denovo_params: segments S (2 .. 32) and mindelta as ChimeraParams, abskew (an integer >= 1: a parent is at least abskew times as
     abundant as the entry), max_parents (0: the default, 262 144, which is also the most), flags (0)."""

@@ -28,6 +28,12 @@
 //    OTUs on the first device (rtx_denovo.hip), right after the clustering: is an OTU's seed the head of one more abundant OTU of the run joined to the tail
 //    of another?  A header line and one line per OTU (rtx_denovo_format_records); PREFIX/raxtax.otus.clean, the lines of raxtax.otus of the OTUs that
 //    are not flagged (under --otus-minsize); with --tags also PREFIX/raxtax.otus.clean.tsv.  raxtax.otus, .map and .tsv are what they are without it.
+//   PREFIX/raxtax.otus.tax (--uniques --otus --otus-tax CUTOFF [--otus-tax-agree P]) the consensus taxonomy of the OTUs (rtx_otutax.hip): after the clustering, and after
+//    the grafting under --fastidious, every distinct read of the table is classified once more through the first handle -- in chunks, in table order, with
+//    the run's --skip-exact-matches / --raw-confidence / --strand and no front stage: the rows went through the front already -- its best lineage cut where the
+//    confidence falls below CUTOFF (rtx_result_best_lineages, as --profile cuts it), and an OTU takes the deepest taxon that P percent (51 .. 100, default 51)
+//    of its reads reach.  A header line and one line per OTU under --otus-minsize (rtx_otu_taxonomy_format), the numbers those of raxtax.otus.  The second
+//    pass costs one classification per distinct read.
 //   (--derep: each distinct read of a chunk is classified once, RTX_OPT_DEREP; the files are byte for byte the same, "N queries, U distinct" goes to the log)
 //   PREFIX/raxtax.demux (--tags SHEET) and PREFIX/raxtax.samples (with --profile as well): below
 //   (--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]: every read is assigned to a sample by the inline tags at
@@ -260,6 +266,9 @@ struct Options {
     bool denovo = false;          // --denovo: the OTUs checked for chimeras of more abundant OTUs (rtx_denovo.hip), PREFIX/raxtax.otus.denovo, raxtax.otus.clean (and .clean.tsv with --tags)
     rtx_denovo_params denovo_params{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA, RTX_DENOVO_DEFAULT_ABSKEW, 0, 0};  // --denovo-segments S, --denovo-mindelta N, --denovo-abskew N
     std::string denovo_opts;      // those three, likewise
+    uint32_t otus_tax_cutoff = 0; // --otus-tax CUTOFF, in hundredths (0: off): the consensus taxonomy of the OTUs (rtx_otutax.hip), PREFIX/raxtax.otus.tax
+    uint32_t otus_tax_agree = 51; // --otus-tax-agree P
+    std::string otus_tax_opts;    // that one, likewise
     uint32_t profile_cutoff = 0;  // --profile CUTOFF, in hundredths (0: no profile): a taxon profile open on every handle, PREFIX/raxtax.profile
     size_t chunk = 0;             // --batch: queries per chunk of rtx_raxtax; 0 = chosen per block of the query file (classify_blocks)
     size_t block_bytes = (size_t)256 << 20;  // query file read and parsed in blocks of this size
@@ -295,6 +304,7 @@ int parse_args(int argc, char **argv, Options &o) {
         {"--uniques-max-bytes", 'p', 1, LLONG_MAX, &o.uniques_max_bytes, &o.uniques_opts},
         {"--otus-minsize", 'p', 1, LLONG_MAX, &o.otus_minsize, &o.otus_opts},
         {"--fastidious-boundary", 'p', 1, LLONG_MAX, &o.fastidious_boundary, &o.fastidious_opts},
+        {"--otus-tax-agree", 'u', 51, 100, &o.otus_tax_agree, &o.otus_tax_opts},
         {"--denovo-abskew", 'u', 1, 0x7FFFFFFF, &o.denovo_params.abskew, &o.denovo_opts},
         {"--denovo-mindelta", 'u', 0, RTX_CHIMERA_MAX_QUERY, &o.denovo_params.mindelta, &o.denovo_opts},
         {"--denovo-segments", 'u', 2, RTX_CHIMERA_MAX_SEGMENTS, &o.denovo_params.segments, &o.denovo_opts},
@@ -395,13 +405,13 @@ int parse_args(int argc, char **argv, Options &o) {
         else if (a == "--contaminants") o.contam_file = val();
         else if (a == "--tags") o.tags_file = val();
         else if (a == "--tags-both-orientations") { o.tags_both = true; o.tag_opts += (o.tag_opts.empty() ? "" : " ") + a; }
-        else if (a == "--profile") {
+        else if (a == "--profile" || a == "--otus-tax") {
             char *end = nullptr;
             const char *v = val();
             const double x = strtod(v, &end);
             const long c = end != v && *end == '\0' && x > 0.0 && x <= 1.0 ? lround(x * 100.0) : 0;
-            if (c < 1 || c > 100) { fprintf(stderr, "raxtax-hip: --profile takes a confidence cutoff in (0, 1], such as 0.8\n"); return 64; }
-            o.profile_cutoff = (uint32_t)c;
+            if (c < 1 || c > 100) { fprintf(stderr, "raxtax-hip: %s takes a confidence cutoff in (0, 1], such as 0.8\n", a.c_str()); return 64; }
+            (a == "--profile" ? o.profile_cutoff : o.otus_tax_cutoff) = (uint32_t)c;
         }
         else if (a == "--uniques") o.uniques = true;
         else if (a == "--otus") o.otus = true;
@@ -411,8 +421,9 @@ int parse_args(int argc, char **argv, Options &o) {
         else if (a == "--block-bytes") o.block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--fastidious [--fastidious-boundary N]] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
-                            "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n");
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--fastidious [--fastidious-boundary N]] [--otus-tax CUTOFF [--otus-tax-agree P]] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
+                            "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n"
+                            "       (--otus-tax classifies every distinct read of the run once more, after the clustering: one classification per distinct read on top of the run)\n");
             return 64;
         }
     }
@@ -446,6 +457,7 @@ struct Identity {
         {"otus", true, ""},           // --otus with its setting: its files are the run's
         {"fastidious", true, ""},     // --fastidious with its boundary: the OTU files are the grafted ones
         {"denovo", true, ""},         // --denovo with its three settings, likewise
+        {"otus_tax", true, ""},       // --otus-tax with its cutoff and agreement, likewise
     };
     std::string &operator[](const std::string &key) {
         for (Entry &e : entries)
@@ -696,6 +708,9 @@ int validate(Options &o, Plan &p) {
     if (orphan(o.denovo ? "--denovo" : "", o.otus, "checks the OTUs of the run for chimeras and needs --otus")) return 64;
     if (o.denovo)
         id["denovo"] = "abskew=" + std::to_string(o.denovo_params.abskew) + ";mindelta=" + std::to_string(o.denovo_params.mindelta) + ";segments=" + std::to_string(o.denovo_params.segments);
+    if (orphan(o.otus_tax_opts.empty() ? "" : "--otus-tax-agree", o.otus_tax_cutoff != 0, "sets the share of an OTU's reads that must agree and needs --otus-tax CUTOFF")) return 64;
+    if (orphan(o.otus_tax_cutoff ? "--otus-tax" : "", o.otus, "names the taxon of every OTU of the run and needs --otus")) return 64;
+    if (o.otus_tax_cutoff) id["otus_tax"] = "cutoff=" + std::to_string(o.otus_tax_cutoff) + ";agree=" + std::to_string(o.otus_tax_agree);
     const char *const on_host = o.derep ? "--derep" : (o.both_strands ? "--strand both" : nullptr);
     if (o.device_format && on_host) {
         fprintf(stderr, "[INFO ] %s: the result lines are formatted on the host (--device-format has no effect)\n", on_host);
@@ -738,9 +753,9 @@ std::vector<Report> report_table(const Options &o, const Plan &p, Sink &s) {
             {"raxtax.screen", p.screen_on, "label\tlength\twindows\thits\tfirst\tsource\tverdict\n", &s.screen}};
 }
 
-// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --fastidious, --denovo): a run that starts over removes them
+// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --fastidious, --denovo, --otus-tax): a run that starts over removes them
 const char *const kEndOfRunFiles[] = {"raxtax.profile", "raxtax.samples", "raxtax.uniques", "raxtax.uniques.tsv", "raxtax.otus", "raxtax.otus.map", "raxtax.otus.tsv",
-                                      "raxtax.otus.grafts", "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv"};
+                                      "raxtax.otus.grafts", "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv", "raxtax.otus.tax"};
 
 // check_incomplete_output (io.rs:156-187): keep only the lines whose first field is a finished query
 void purge_incomplete(const std::string &path, const std::set<std::string> &done, bool keep_header = false) {
@@ -1359,9 +1374,64 @@ int write_sample_table(const Options &o, const Plan &p, const std::vector<rtx_in
     return write_whole(o.prefix + "/raxtax.samples", text) ? 0 : 74;
 }
 
+// --otus-tax: the rows of the table classified once more through the first handle, in chunks, in table order (no front stage: the rows went through
+// the front already); every chunk turned into records; then the consensus of every OTU on the first device
+int write_otu_taxonomy(const Options &o, rtx_index *ix, const rtx_tree *tree, const rtx_tally_view &view, const rtx_otu_view_t &ov) {
+    const auto t0 = std::chrono::steady_clock::now();
+    rtx_nodes_view nodes{};
+    int trc = rtx_tree_nodes(tree, &nodes);
+    uint32_t stride = 0;  // the deepest lineage of the tree: the nodes come breadth first, so the last one is among the deepest
+    for (uint32_t u = trc == RTX_OK && nodes.n_nodes ? nodes.n_nodes - 1u : 0u; u != 0 && stride < RTX_MAX_DEPTH; u = nodes.node_parent[u]) stride++;
+    stride = std::max(stride, 1u);
+    const uint64_t n = view.n_entries, step = o.chunk ? o.chunk : 65536;
+    const uint32_t flags = (o.skip_exact ? RTX_SKIP_EXACT_MATCHES : 0u) | (o.raw ? RTX_RAW_CONFIDENCE : 0u);
+    std::vector<uint8_t> kind(n), depth(n), hund(n * stride);
+    std::vector<uint32_t> node(n);
+    const bool lookup = rtx_index_has_exact_lookup(ix) != 0;
+    std::vector<uint64_t> x_off;
+    std::vector<uint32_t> x_ids;
+    if (trc == RTX_OK && o.profile_cutoff) trc = rtx_index_profile_end(ix);  // (the profile of the run is written: the second pass is not part of it)
+    for (uint64_t a = 0; a < n && trc == RTX_OK; a += step) {
+        const uint64_t m = std::min(step, n - a);
+        const uint64_t *xo = nullptr;
+        const uint32_t *xi = nullptr;
+        if (!lookup) {  // Tree.sequences.get on the host, as the run itself does for such a handle
+            x_off.assign(m + 1, 0);
+            x_ids.assign(16, 0);
+            const uint64_t tot = rtx_tree_exact_matches_batch(tree, m, view.bases, view.base_off + a, x_off.data(), x_ids.data(), x_ids.size());
+            if (tot > x_ids.size()) {
+                x_ids.assign(tot, 0);
+                rtx_tree_exact_matches_batch(tree, m, view.bases, view.base_off + a, x_off.data(), x_ids.data(), x_ids.size());
+            }
+            xo = x_off.data();
+            xi = x_ids.data();
+        }
+        rtx_result_view res{};
+        trc = rtx_classify_batch(ix, m, view.bases, view.base_off + a, xi, xo, flags, &res);
+        if (trc == RTX_OK && lookup) trc = rtx_batch_exact_matches(ix, &xo, &xi);
+        if (trc == RTX_OK)
+            trc = rtx_result_best_lineages(tree, &res, xi, xo, o.otus_tax_cutoff, flags, kind.data() + a, depth.data() + a, node.data() + a, hund.data() + a * stride, stride);
+    }
+    const rtx_lineage_records rec{kind.data(), depth.data(), node.data(), hund.data(), stride};
+    const rtx_otu_taxonomy_params prm{o.otus_tax_agree, 0};
+    rtx_otutax *tax = nullptr;
+    if (trc == RTX_OK) trc = rtx_otu_taxonomy(o.devices[0], n, ov.otu, view.sizes, ov.n_otus, ov.seed, &rec, &nodes, &prm, &tax);
+    rtx_otu_taxonomy_view_t tv{};
+    std::string text;
+    if (trc == RTX_OK) trc = rtx_otu_taxonomy_view(tax, &tv);
+    if (trc == RTX_OK) trc = format_two_pass(text, [&](char *buf, uint64_t cap) { return rtx_otu_taxonomy_format(tax, tree, o.otus_minsize, buf, cap); });
+    uint64_t named = 0;
+    for (uint64_t k = 0; trc == RTX_OK && k < tv.n_otus; k++) named += tv.depth[k] != 0;
+    rtx_otu_taxonomy_destroy(tax);
+    if (trc != RTX_OK) { fprintf(stderr, "[ERROR] OTU taxonomy: %s\n", rtx_last_error()); return 70; }
+    fprintf(stderr, "[INFO ] --otus-tax: %llu OTUs, %llu with a taxon, %.3f s for the second pass over %llu distinct reads\n", (ull)tv.n_otus, (ull)named,
+            std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), (ull)n);
+    return write_whole(o.prefix + "/raxtax.otus.tax", text) ? 0 : 74;
+}
+
 // --uniques: the distinct reads of the whole run: the tables of the handles' objects read, summed and written once;
 // --otus: the summed table, whole, clustered on the first device
-int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rtx_tally *> &tallies) {
+int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rtx_tally *> &tallies, rtx_index *first, const rtx_tree *tree) {
     struct Owned {  // what the function makes, released on every way out
         std::vector<rtx_tally_table *> tables;
         rtx_tally_table *sum = nullptr;
@@ -1425,6 +1495,11 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
             fprintf(stderr, "[INFO ] --fastidious: boundary %llu, %llu heavy and %llu light OTUs, %llu grafts, %llu OTUs left\n", (ull)gv.boundary, (ull)gv.heavy_otus, (ull)gv.light_otus,
                     (ull)gv.n_grafts, (ull)gv.n_otus);
             if (!write_whole(o.prefix + "/raxtax.otus.grafts", grafts)) return 74;
+        }
+        if (o.otus_tax_cutoff) {  // which taxon every OTU is (of the grafted OTUs under --fastidious)
+            rtx_otu_view_t cur{};
+            if (rtx_otu_view(otu, &cur) != RTX_OK) { fprintf(stderr, "[ERROR] OTU taxonomy: %s\n", rtx_last_error()); return 70; }
+            if (const int wrc = write_otu_taxonomy(o, first, tree, view, cur)) return wrc;
         }
         if (o.denovo) {  // the OTUs against the more abundant OTUs of the run
             rtx_denovo *&dn = own.dn;
@@ -1536,8 +1611,10 @@ int main(int argc, char **argv) {
         if (const int wrc = write_profile(o, indices, tree)) return wrc;
     if (o.profile_cutoff && plan.tags_on)
         if (const int wrc = write_sample_table(o, plan, indices, tree)) return wrc;
+    // (behind the two profile files, and it must stay there: under --otus-tax the second pass ends the first handle's profile, so that the rows it
+    //  classifies once more are not counted as reads of the run)
     if (o.uniques)
-        if (const int wrc = write_uniques_and_otus(o, plan, tallies)) return wrc;
+        if (const int wrc = write_uniques_and_otus(o, plan, tallies, indices[0], tree)) return wrc;
 
     if (o.clean) {  // Checkpoint::cleanup (io.rs:80-89)
         remove((o.prefix + "/raxtax.json").c_str());
