@@ -55,7 +55,8 @@ extern "C" {
                                 rtx_sample_table_format: the same; and with the contaminant screen, rtx_screen_* / rtx_index_set_screen /
                                 rtx_index_screen / rtx_raxtax_last_screen / rtx_raxtax_multi_ex8: the same; and with the de novo chimera check of a
                                 run, rtx_denovo_*: exports only; and with the consensus taxonomy of the OTUs, rtx_otu_taxonomy* /
-                                rtx_result_best_lineages: exports only) */
+                                rtx_result_best_lineages: exports only; and with denoising, rtx_otu_unoise* / rtx_otu_format_unoise: exports
+                                only) */
 #define RTX_NUM_KMERS 65536u /* 2 << 15 posting lists, src/tree.rs:52 */
 #define RTX_MAX_DEPTH 32u    /* deepest lineage (comma-separated levels) the device walk carries */
 
@@ -825,6 +826,75 @@ int rtx_otu_graft(int device, rtx_tally_table *table, rtx_otu *otu, const rtx_gr
 int rtx_otu_graft_host(rtx_tally_table *table, rtx_otu *otu, const rtx_graft_params *params, rtx_otu **out);
 int rtx_otu_graft_view(rtx_otu *grafted, rtx_graft_view_t *view);
 int64_t rtx_otu_format_grafts(rtx_otu *grafted, char *buf, uint64_t cap);
+
+/* ---- Denoising (UNOISE) (rtx_unoise.hip, host_unoise.cpp) ------------------------------------------------------------------------------------
+ * The distinct reads of a run denoised into ZOTUs by the UNOISE rule (Edgar 2016): a read is an error of a more abundant read d differences
+ * away when size(child) / size(parent) <= 1 / 2^(alpha d + 1).  Exact, integers only, independent of scheduling.
+ *   input        an rtx_tally_table (rows by total size descending, then bytes ascending; the row index is the rank; w[r] is the total of a
+ *                row; one code per byte) and minsize (default 8, at least 1), alpha (default 2, an integer in 1 .. 8), max_diffs (0: the
+ *                default RTX_UNOISE_MAX_DIFFS = 16, at most 16), flags (0).
+ *   distance     d(x, y) is the Levenshtein distance of the two rows as byte strings: global, both ends anchored, unit costs, two codes
+ *                match iff the bytes are equal (an ambiguity code matches itself and nothing else).  A row longer than RTX_OTU_MAX_LEN has
+ *                no distance to anything.
+ *   allowed      for rows p < e, k(e, p) is the largest d in 0 .. max_diffs with (w[p] >> (alpha d + 1)) >= w[e]; a shift of 64 or more
+ *                gives 0.  k = 0: not a candidate.  Weights never increase along the table, so lim(e) = #{p : (w[p] >> (alpha + 1)) >= w[e]}
+ *                is a prefix of the table, and only p < lim(e) can have k >= 1.
+ *   recursion    over e = 0, 1, ...: p is a live parent iff its status is ZOTU.  e is ABSORBED iff some live p < lim(e) has
+ *                d(e, p) <= k(e, p); its parent is the such p with the smallest (d, p), dist that d.  Otherwise e is a ZOTU if
+ *                w[e] >= minsize, else LEFT (small, without a parent; never a parent).  A row longer than RTX_OTU_MAX_LEN is LONG: never
+ *                compared, never a parent.  The status of e depends only on statuses below lim(e) <= e: exactly one solution.  An absorbed
+ *                read is no parent (UNOISE's greedy rule), parents are ZOTUs: no chains.
+ *   result       a new rtx_otu over the same table.  Every row that is not absorbed seeds an OTU of its own, numbered from 0 in the order
+ *                of the seeds' ranks; otu[r] is its own OTU or its parent's; members, sizes and counts are the sums; n_links, rounds and
+ *                link_passes are 0; long_rows as rtx_otu_cluster sets it.  rtx_otu_view, the three rtx_otu_format_* functions,
+ *                rtx_denovo_check(table, otu) and rtx_otu_taxonomy take the object as any other.
+ *   rtx_otu_unoise        on GPU `device` (RTX_ERR_NO_DEVICE without a gfx950).  The table is cut into tiers [s0, s1), s1 the first row
+ *                with (w[s0] >> (alpha + 1)) >= w[s1]: no row of a tier can be the parent of another, so a tier's statuses depend on
+ *                earlier tiers only, and there are at most 64 / (alpha + 1) + 1 tiers.  Per tier a pair kernel takes every (row of the
+ *                tier, live centroid below lim(row)) -- the row is a wave's pattern, one centroid per lane the text; k from the two
+ *                weights; a pair whose lengths differ by more than k is dropped; the others run Hyyro's bit-vector step on a band of 64
+ *                rows that slides down the diagonal, which gives the exact d whenever d <= k, and stop at the first column where the cell
+ *                on the final diagonal exceeds k -- and folds (d << 32 | p) per row with a 64-bit atomicMin; a decide kernel writes the
+ *                statuses; a scan appends the tier's new ZOTUs to the centroid list in rank order.  Rows travel as 4-bit codes, sixteen to
+ *                a 64-bit word: a table with a byte above 15 is refused (RTX_ERR_INVALID) by this entry.
+ *   rtx_otu_unoise_host   the definition restated literally: e ascending, an explicit list of live parents, a plain two-row dynamic
+ *                programme over the bytes.  Equal to the device's result field by field, except the device's counters and the times (0).
+ *                RTX_ERR_INVALID: alpha outside 1 .. 8, minsize 0 (in a params that is given), max_diffs above 16, flags != 0, more than
+ *                2^31 - 2 rows.  params NULL: the defaults.  The table is laid out (rtx_tally_table_view) and otherwise unchanged.
+ *   rtx_otu_unoise_view   of a denoising result (RTX_ERR_INVALID on any other rtx_otu); valid until the object is destroyed.
+ *   rtx_otu_format_unoise `#read\tsize\tstatus\tparent\tdiffs\totu\n`, then `uniq{rank}\t{size}\t{zotu|absorbed|left|long}\t{uniq{rank}|*}\t
+ *                {d|*}\totu{k}\n` per row, counted from 1.  Buffer protocol of rtx_tally_format_fasta.
+ *   RTX_DEFAULT_UNOISE_SLICE (rtx_set_default_option; default and 0: no cap): a cap on the rows of one launch of the pair kernel and on the
+ *                centroids of one launch, read at every call.  For tests: the result does not depend on it. */
+#define RTX_DEFAULT_UNOISE_SLICE 8 /* (7 stays unknown: the suite of the de novo check pins it as the first id that is refused) */
+#define RTX_UNOISE_MAX_DIFFS 16
+#define RTX_UNOISE_ZOTU 0
+#define RTX_UNOISE_ABSORBED 1
+#define RTX_UNOISE_LEFT 2
+#define RTX_UNOISE_LONG 3
+typedef struct rtx_unoise_params {
+    uint64_t minsize;   /* at least 1 (8 when params is NULL) */
+    uint32_t alpha;     /* 1 .. 8 (2 when params is NULL) */
+    uint32_t max_diffs; /* 0: RTX_UNOISE_MAX_DIFFS; at most 16 */
+    uint32_t flags;     /* 0 */
+} rtx_unoise_params;
+typedef struct rtx_unoise_view_t {
+    uint64_t n_rows;
+    const uint8_t *status;   /* [n_rows] RTX_UNOISE_* */
+    const uint32_t *parent;  /* [n_rows] a row, or RTX_NO_REF */
+    const uint32_t *dist;    /* [n_rows] d(row, parent), or RTX_NO_DIST */
+    const uint32_t *lim;     /* [n_rows] */
+    uint64_t n_zotu, n_absorbed, n_left, n_long;
+    uint64_t minsize;        /* the parameters as used */
+    uint32_t alpha, max_diffs;
+    uint32_t tiers, launches;                       /* device only from here on; 0 for a host result */
+    uint64_t pairs, pairs_length, pairs_finished;   /* pairs handed to the kernel, dropped by the length test, that reached the last column */
+    double seconds[4];                              /* upload, pair kernels (events around them), bookkeeping, download */
+} rtx_unoise_view_t;
+int rtx_otu_unoise(int device, rtx_tally_table *table, const rtx_unoise_params *params, rtx_otu **out);
+int rtx_otu_unoise_host(rtx_tally_table *table, const rtx_unoise_params *params, rtx_otu **out);
+int rtx_otu_unoise_view(rtx_otu *denoised, rtx_unoise_view_t *view);
+int64_t rtx_otu_format_unoise(rtx_otu *denoised, char *buf, uint64_t cap);
 
 /* ---- Consensus taxonomy of the OTUs (rtx_otutax.hip, host_otutax.cpp) ------------------------------------------------------------------------
  * Which taxon an OTU is: the deepest taxon that an agreed share of the OTU's reads reaches with confidence, with the support at every level.

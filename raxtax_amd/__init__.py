@@ -8,7 +8,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 from .api import (EvaluationResult, Index, Result, Tree, parse_query_fasta_str, parse_reference_fasta_str,  # noqa: F401
                   raxtax, raxtax_last_timing, NO_REF, NO_DIST, semiglobal_distance, Profile, profile_merge, profile_text, SampleProfile, sample_profile_merge, sample_table_text, Derep, derep_plan, raxtax_last_derep,
-                  Tally, TallyTable, tally_reads, tally_merge, tally_fasta, tally_table_text, raxtax_last_tally, Otus, otu_cluster, otu_cluster_host, otu_fasta, otu_table_text, otu_map_text, otu_graft, otu_graft_host, otu_grafts_text, DenovoParams, Denovo, denovo_check, denovo_check_host, denovo_records_text, denovo_fasta, denovo_table_text, Lineages, best_lineages, OtuTaxonomy, otu_taxonomy, otu_taxonomy_host,
+                  Tally, TallyTable, tally_reads, tally_merge, tally_fasta, tally_table_text, raxtax_last_tally, Otus, otu_cluster, otu_cluster_host, otu_fasta, otu_table_text, otu_map_text, otu_graft, otu_graft_host, otu_grafts_text, UnoiseParams, otu_unoise, otu_unoise_host, unoise_text, DenovoParams, Denovo, denovo_check, denovo_check_host, denovo_records_text, denovo_fasta, denovo_table_text, Lineages, best_lineages, OtuTaxonomy, otu_taxonomy, otu_taxonomy_host,
                   Trim, TrimPrimer, primer_patterns, primer_search, trim_apply, trim_hit, encode_iupac, raxtax_last_trim, TRIM_5P, TRIM_3P, TRIM_NO_PATTERN,
                   Demux, DemuxTag, DemuxParams, demux_read, demux_hit, demux_verdict_names, sample_sheet, raxtax_last_demux, DEMUX_NO_TAG, DEMUX_NONE,
                   DEMUX_OK, DEMUX_NO_TAG5, DEMUX_NO_TAG3, DEMUX_AMBIGUOUS, DEMUX_UNKNOWN_PAIR,
@@ -23,7 +23,7 @@ from ._lib import (RTX_RAW_CONFIDENCE, RTX_SKIP_EXACT_MATCHES, RtxError)  # noqa
 __all__ = ["Tree", "Index", "Result", "EvaluationResult", "raxtax", "raxtax_last_timing", "parse_reference_fasta_str",
            "parse_query_fasta_str", "RtxError", "RTX_SKIP_EXACT_MATCHES", "RTX_RAW_CONFIDENCE", "NO_REF", "NO_DIST", "semiglobal_distance",
            "Profile", "profile_merge", "profile_text", "SampleProfile", "sample_profile_merge", "sample_table_text", "Derep", "derep_plan", "raxtax_last_derep",
-           "Tally", "TallyTable", "tally_reads", "tally_merge", "tally_fasta", "tally_table_text", "raxtax_last_tally", "Otus", "otu_cluster", "otu_cluster_host", "otu_fasta", "otu_table_text", "otu_map_text", "otu_graft", "otu_graft_host", "otu_grafts_text", "DenovoParams", "Denovo", "denovo_check", "denovo_check_host", "denovo_records_text", "denovo_fasta", "denovo_table_text", "Lineages", "best_lineages", "OtuTaxonomy", "otu_taxonomy", "otu_taxonomy_host",
+           "Tally", "TallyTable", "tally_reads", "tally_merge", "tally_fasta", "tally_table_text", "raxtax_last_tally", "Otus", "otu_cluster", "otu_cluster_host", "otu_fasta", "otu_table_text", "otu_map_text", "otu_graft", "otu_graft_host", "otu_grafts_text", "UnoiseParams", "otu_unoise", "otu_unoise_host", "unoise_text", "DenovoParams", "Denovo", "denovo_check", "denovo_check_host", "denovo_records_text", "denovo_fasta", "denovo_table_text", "Lineages", "best_lineages", "OtuTaxonomy", "otu_taxonomy", "otu_taxonomy_host",
            "Trim", "TrimPrimer", "primer_patterns", "primer_search", "trim_apply", "trim_hit", "encode_iupac", "raxtax_last_trim", "TRIM_5P", "TRIM_3P",
            "TRIM_NO_PATTERN", "Demux", "DemuxTag", "DemuxParams", "demux_read", "demux_hit", "demux_verdict_names", "sample_sheet", "raxtax_last_demux", "DEMUX_NO_TAG",
            "DEMUX_NONE", "DEMUX_OK", "DEMUX_NO_TAG5", "DEMUX_NO_TAG3", "DEMUX_AMBIGUOUS", "DEMUX_UNKNOWN_PAIR", "parse_query_fastq_str", "Qual", "QualParams", "qual_read", "qual_error_table", "qual_verdict_names", "raxtax_last_qual",

@@ -14,8 +14,8 @@ PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
 CSRC = PKG / "csrc"
 LIB = PKG / "libraxtax_hip.so"
-SOURCES = ["rtx_kernels.hip", "rtx_hit_pair.hip", "rtx_prob_tables.hip", "rtx_cluster.hip", "rtx_segments.hip", "rtx_prune.hip", "rtx_bounds2.hip", "rtx_records.hip", "rtx_finalise.hip", "rtx_text.hip", "rtx_exact.hip", "rtx_strand.hip", "rtx_nearest.hip", "rtx_identity.hip", "rtx_profile.hip", "rtx_ingest.hip", "rtx_derep.hip", "rtx_tally.hip", "rtx_trim.hip", "rtx_demux.hip", "rtx_qual.hip", "rtx_screen.hip", "rtx_merge.hip", "rtx_chimera.hip", "rtx_api_index.hip", "rtx_api_batch.hip", "rtx_api_download.hip", "rtx_api_shard.hip", "rtx_api_debug.hip", "host_tree.cpp", "host_format.cpp", "host_align.cpp", "host_trim.cpp", "host_demux.cpp", "host_front.cpp", "host_qual.cpp", "host_screen.cpp", "host_merge.cpp", "host_chimera.cpp", "host_tally.cpp", "host_raxtax.cpp", "host_bin.cpp", "host_threads.cpp", "rtx_otu.hip", "rtx_graft.hip", "host_otu.cpp", "rtx_denovo.hip", "host_denovo.cpp", "rtx_otutax.hip", "host_otutax.cpp"]
-HEADERS = ["rtx_index.hpp", "rtx_stage.hpp", "rtx_derep_dev.hpp", "rtx_otu_dev.hpp", "host_tally.hpp", "host_otu.hpp", "host_denovo.hpp", "host_otutax.hpp", "host_stage.hpp", "rtx_kernels.hpp", "rtx_hit_common.hpp", "rtx_internal.hpp", "rtx_math.hpp", "rtx_wave.hpp", "rtx_walk.hpp", "host_raxtax.hpp", "host_front.hpp", "host_qual.hpp", "host_screen.hpp", "host_merge.hpp", "host_demux.hpp"]
+SOURCES = ["rtx_kernels.hip", "rtx_hit_pair.hip", "rtx_prob_tables.hip", "rtx_cluster.hip", "rtx_segments.hip", "rtx_prune.hip", "rtx_bounds2.hip", "rtx_records.hip", "rtx_finalise.hip", "rtx_text.hip", "rtx_exact.hip", "rtx_strand.hip", "rtx_nearest.hip", "rtx_identity.hip", "rtx_profile.hip", "rtx_ingest.hip", "rtx_derep.hip", "rtx_tally.hip", "rtx_trim.hip", "rtx_demux.hip", "rtx_qual.hip", "rtx_screen.hip", "rtx_merge.hip", "rtx_chimera.hip", "rtx_api_index.hip", "rtx_api_batch.hip", "rtx_api_download.hip", "rtx_api_shard.hip", "rtx_api_debug.hip", "host_tree.cpp", "host_format.cpp", "host_align.cpp", "host_trim.cpp", "host_demux.cpp", "host_front.cpp", "host_qual.cpp", "host_screen.cpp", "host_merge.cpp", "host_chimera.cpp", "host_tally.cpp", "host_raxtax.cpp", "host_bin.cpp", "host_threads.cpp", "rtx_otu.hip", "rtx_graft.hip", "host_otu.cpp", "rtx_denovo.hip", "host_denovo.cpp", "rtx_otutax.hip", "host_otutax.cpp", "rtx_unoise.hip", "host_unoise.cpp"]
+HEADERS = ["rtx_index.hpp", "rtx_stage.hpp", "rtx_derep_dev.hpp", "rtx_otu_dev.hpp", "host_tally.hpp", "host_otu.hpp", "host_denovo.hpp", "host_otutax.hpp", "host_unoise.hpp", "host_stage.hpp", "rtx_kernels.hpp", "rtx_hit_common.hpp", "rtx_internal.hpp", "rtx_math.hpp", "rtx_wave.hpp", "rtx_walk.hpp", "host_raxtax.hpp", "host_front.hpp", "host_qual.hpp", "host_screen.hpp", "host_merge.hpp", "host_demux.hpp"]
 CLI = PKG / "raxtax-hip"
 SYNTH = PKG / "raxtax-synth"   # the generator of the synthetic inputs as a host program: csrc/synth_main.cpp
 

@@ -26,6 +26,9 @@ RTX_DEFAULT_DEREP_HASH_MASK = 3    # rtx_set_default_option: the hash of rtx_der
 RTX_DEFAULT_TALLY_HASH_MASK = 4    # rtx_set_default_option: the hash of rtx_tally_add ANDed with a mask (tests)
 RTX_DEFAULT_OTU_HASH_MASK = 5      # rtx_set_default_option: the hashes of rtx_otu_cluster ANDed with a mask (tests)
 RTX_DEFAULT_CHIMERA_SLICE = 6      # rtx_set_default_option: a cap on the reads / entries of a slice of rtx_chimera_run / rtx_denovo_check (tests)
+RTX_DEFAULT_UNOISE_SLICE = 8       # rtx_set_default_option: a cap on the rows and on the centroids of one launch of rtx_otu_unoise (tests)
+RTX_UNOISE_MAX_DIFFS = 16          # rtx_otu_unoise: the most differences a read may have to its parent
+RTX_UNOISE_ZOTU, RTX_UNOISE_ABSORBED, RTX_UNOISE_LEFT, RTX_UNOISE_LONG = 0, 1, 2, 3   # rtx_unoise_view_t.status
 RTX_OTU_MAX_LEN = 4096
 RTX_LIN_UNCLASSIFIABLE, RTX_LIN_UNCLASSIFIED, RTX_LIN_CLASSIFIED = 0, 1, 2   # rtx_lineage_records.kind
 STAGES = ("kmer_extract", "hit_count", "prob_table", "taxon_prefix", "lineage_walk", "tile_bounds", "tile_prune", "exact_match", "order", "pair_union")
@@ -144,6 +147,16 @@ class OtuView(C.Structure):   # rtx_otu_view_t
 
 class GraftParams(C.Structure):   # rtx_graft_params
     _fields_ = [("boundary", C.c_uint64), ("bloom_log2", C.c_uint32), ("flags", C.c_uint32), ("max_bloom_bytes", C.c_uint64), ("initial_candidates", C.c_uint64)]
+
+
+class UnoiseParams(C.Structure):   # rtx_unoise_params
+    _fields_ = [("minsize", C.c_uint64), ("alpha", C.c_uint32), ("max_diffs", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class UnoiseView(C.Structure):   # rtx_unoise_view_t
+    _fields_ = [("n_rows", C.c_uint64), ("status", C.POINTER(C.c_uint8)), ("parent", u32p), ("dist", u32p), ("lim", u32p), ("n_zotu", C.c_uint64), ("n_absorbed", C.c_uint64),
+                ("n_left", C.c_uint64), ("n_long", C.c_uint64), ("minsize", C.c_uint64), ("alpha", C.c_uint32), ("max_diffs", C.c_uint32), ("tiers", C.c_uint32),
+                ("launches", C.c_uint32), ("pairs", C.c_uint64), ("pairs_length", C.c_uint64), ("pairs_finished", C.c_uint64), ("seconds", C.c_double * 4)]
 
 
 class GraftView(C.Structure):   # rtx_graft_view_t
@@ -364,6 +377,10 @@ _SIGNATURES = {
     "rtx_otu_graft_host": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GraftParams), C.POINTER(C.c_void_p)]),
     "rtx_otu_graft_view": (C.c_int, [C.c_void_p, C.POINTER(GraftView)]),
     "rtx_otu_format_grafts": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
+    "rtx_otu_unoise": (C.c_int, [C.c_int, C.c_void_p, C.POINTER(UnoiseParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_unoise_host": (C.c_int, [C.c_void_p, C.POINTER(UnoiseParams), C.POINTER(C.c_void_p)]),
+    "rtx_otu_unoise_view": (C.c_int, [C.c_void_p, C.POINTER(UnoiseView)]),
+    "rtx_otu_format_unoise": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_uint64]),
     "rtx_otu_taxonomy": (C.c_int, [C.c_int, C.c_uint64, u32p, u64p, C.c_uint64, u32p, C.POINTER(LineageRecords), C.POINTER(NodesView), C.POINTER(OtuTaxonomyParams), C.POINTER(C.c_void_p)]),
     "rtx_otu_taxonomy_host": (C.c_int, [C.c_uint64, u32p, u64p, C.c_uint64, u32p, C.POINTER(LineageRecords), C.POINTER(NodesView), C.POINTER(OtuTaxonomyParams), C.POINTER(C.c_void_p)]),
     "rtx_otu_taxonomy_view": (C.c_int, [C.c_void_p, C.POINTER(OtuTaxonomyView)]),

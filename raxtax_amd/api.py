@@ -1975,6 +1975,23 @@ class Otus:
         self.graft_info["seconds"] = tuple(float(x) for x in g.seconds)
         return self
 
+    def _read_unoise(self):
+        """what a denoising result carries beside its clustering (otu_unoise, otu_unoise_host): .unoise, the view as numpy arrays -- status
+        (_lib.RTX_UNOISE_*), parent (NO_REF: none), dist (NO_DIST: none) and lim per row, the four status counts, the parameters as used, the
+        device's counters (0 from the host) and the seconds of upload, pair kernels, bookkeeping and download"""
+        g = _lib.UnoiseView()
+        check(self._lib.rtx_otu_unoise_view(self._h, C.byref(g)))
+        n = int(g.n_rows)
+
+        def arr(p, dtype):
+            return np.ctypeslib.as_array(p, shape=(n,)).copy() if n else np.zeros(0, dtype)
+
+        self.unoise = {"status": arr(g.status, np.uint8), "parent": arr(g.parent, np.uint32), "dist": arr(g.dist, np.uint32), "lim": arr(g.lim, np.uint32)}
+        self.unoise.update({k: int(getattr(g, k)) for k in ("n_zotu", "n_absorbed", "n_left", "n_long", "minsize", "alpha", "max_diffs", "tiers", "launches", "pairs",
+                                                            "pairs_length", "pairs_finished")})
+        self.unoise["seconds"] = tuple(float(x) for x in g.seconds)
+        return self
+
     def __del__(self):
         try:
             if self._h:
@@ -2050,6 +2067,38 @@ def otu_graft_host(otus: Otus, **params) -> Otus:
 def otu_grafts_text(otus: Otus) -> str:
     """rtx_otu_format_grafts: `otu{k}\t{size}\tuniq{child}\tuniq{parent}\totu{heavy}\totu{new}` per graft (PREFIX/raxtax.otus.grafts)."""
     return _otu_text(_lib.load().rtx_otu_format_grafts, otus)
+
+
+@dataclass
+class UnoiseParams:
+    """rtx_unoise_params: minsize (a ZOTU holds at least that many reads), alpha (the skew exponent, 1 .. 8), max_diffs (0: 16), flags (0)."""
+    minsize: int = 8
+    alpha: int = 2
+    max_diffs: int = 0
+    flags: int = 0
+
+    def _c(self):
+        return C.byref(_lib.UnoiseParams(int(self.minsize), int(self.alpha), int(self.max_diffs), int(self.flags)))
+
+
+def otu_unoise(table: TallyTable, device: int = 0, **params) -> Otus:
+    """rtx_otu_unoise: the table's rows denoised into ZOTUs by the UNOISE rule, on GPU `device`.  An Otus over the table -- every row that is not
+    absorbed seeds an OTU -- with .unoise.  params: the fields of UnoiseParams."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_unoise(int(device), table._h, UnoiseParams(**params)._c(), C.byref(h)))
+    return Otus(h, table)._read_unoise()
+
+
+def otu_unoise_host(table: TallyTable, **params) -> Otus:
+    """rtx_otu_unoise_host: the same from the definition, on the host (the device's counters stay 0)."""
+    h = C.c_void_p()
+    check(_lib.load().rtx_otu_unoise_host(table._h, UnoiseParams(**params)._c(), C.byref(h)))
+    return Otus(h, table)._read_unoise()
+
+
+def unoise_text(otus: Otus) -> str:
+    """rtx_otu_format_unoise: `uniq{rank}\t{size}\t{status}\t{parent}\t{diffs}\totu{k}` per row (PREFIX/raxtax.otus.unoise)."""
+    return _otu_text(_lib.load().rtx_otu_format_unoise, otus)
 
 
 @dataclass

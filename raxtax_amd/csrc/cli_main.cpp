@@ -24,6 +24,11 @@
 //   PREFIX/raxtax.otus.grafts (--uniques --otus --fastidious [--fastidious-boundary N]) Swarm's fastidious pass on the first device (rtx_graft.hip), right after the
 //    clustering: an OTU below N reads (default 3) is grafted onto an OTU of at least N that holds a distinct read at most two differences away.  One line per
 //    graft (rtx_otu_format_grafts); raxtax.otus, .map and .tsv are then those of the grafted OTUs, and --denovo checks those.
+//   PREFIX/raxtax.otus.unoise (--uniques --otus --unoise [--unoise-minsize N] [--unoise-alpha A] [--unoise-maxdiffs D]) the distinct reads denoised into ZOTUs
+//    by the UNOISE rule on the first device (rtx_unoise.hip) INSTEAD of the clustering: a read is an error of a more abundant read d differences away when
+//    it is at most 1 / 2^(A d + 1) as abundant (A default 2, d at most D, default 16); what is left and holds at least N reads (default 8) is a ZOTU.  A header
+//    line and one line per distinct read (rtx_otu_format_unoise); raxtax.otus, .map, .tsv, --denovo and --otus-tax are then those of the ZOTUs, written
+//    under the larger of --otus-minsize and --unoise-minsize.  Not with --fastidious.
 //   PREFIX/raxtax.otus.denovo (--uniques --otus --denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]) the de novo chimera check of the
 //    OTUs on the first device (rtx_denovo.hip), right after the clustering: is an OTU's seed the head of one more abundant OTU of the run joined to the tail
 //    of another?  A header line and one line per OTU (rtx_denovo_format_records); PREFIX/raxtax.otus.clean, the lines of raxtax.otus of the OTUs that
@@ -263,6 +268,9 @@ struct Options {
     bool fastidious = false;      // --fastidious: the small OTUs grafted onto large ones two differences away (rtx_graft.hip), PREFIX/raxtax.otus.grafts; the OTU files are the grafted ones
     uint64_t fastidious_boundary = 0;  // --fastidious-boundary N (0: the library's default, 3)
     std::string fastidious_opts;  // that one, likewise
+    bool unoise = false;          // --unoise: the OTU object is made by the denoiser (rtx_unoise.hip) instead of the clustering, PREFIX/raxtax.otus.unoise; the OTU files are the ZOTUs
+    rtx_unoise_params unoise_params{8, 2, 0, 0};  // --unoise-minsize N, --unoise-alpha A, --unoise-maxdiffs D
+    std::string unoise_opts;      // those three, likewise
     bool denovo = false;          // --denovo: the OTUs checked for chimeras of more abundant OTUs (rtx_denovo.hip), PREFIX/raxtax.otus.denovo, raxtax.otus.clean (and .clean.tsv with --tags)
     rtx_denovo_params denovo_params{RTX_CHIMERA_DEFAULT_SEGMENTS, RTX_CHIMERA_DEFAULT_MINDELTA, RTX_DENOVO_DEFAULT_ABSKEW, 0, 0};  // --denovo-segments S, --denovo-mindelta N, --denovo-abskew N
     std::string denovo_opts;      // those three, likewise
@@ -304,6 +312,9 @@ int parse_args(int argc, char **argv, Options &o) {
         {"--uniques-max-bytes", 'p', 1, LLONG_MAX, &o.uniques_max_bytes, &o.uniques_opts},
         {"--otus-minsize", 'p', 1, LLONG_MAX, &o.otus_minsize, &o.otus_opts},
         {"--fastidious-boundary", 'p', 1, LLONG_MAX, &o.fastidious_boundary, &o.fastidious_opts},
+        {"--unoise-minsize", 'p', 1, LLONG_MAX, &o.unoise_params.minsize, &o.unoise_opts},
+        {"--unoise-alpha", 'u', 1, 8, &o.unoise_params.alpha, &o.unoise_opts},
+        {"--unoise-maxdiffs", 'u', 1, RTX_UNOISE_MAX_DIFFS, &o.unoise_params.max_diffs, &o.unoise_opts},
         {"--otus-tax-agree", 'u', 51, 100, &o.otus_tax_agree, &o.otus_tax_opts},
         {"--denovo-abskew", 'u', 1, 0x7FFFFFFF, &o.denovo_params.abskew, &o.denovo_opts},
         {"--denovo-mindelta", 'u', 0, RTX_CHIMERA_MAX_QUERY, &o.denovo_params.mindelta, &o.denovo_opts},
@@ -416,12 +427,13 @@ int parse_args(int argc, char **argv, Options &o) {
         else if (a == "--uniques") o.uniques = true;
         else if (a == "--otus") o.otus = true;
         else if (a == "--fastidious") o.fastidious = true;
+        else if (a == "--unoise") o.unoise = true;
         else if (a == "--denovo") o.denovo = true;
         else if (a == "--batch") o.chunk = (size_t)atoll(val());
         else if (a == "--block-bytes") o.block_bytes = std::max<size_t>(1, (size_t)atoll(val()));
         else {
             fprintf(stderr, "usage: raxtax-hip -d DB.(fasta|bin) [-i QUERIES.(fasta|fastq)] [-o PREFIX] [--skip-exact-matches] [--raw-confidence] "
-                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--fastidious [--fastidious-boundary N]] [--otus-tax CUTOFF [--otus-tax-agree P]] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
+                            "[--tsv] [--only-db] [--skip-db] [-c] [--redo] [--device N | --gpus N | --devices a,b,..] [--batch N] [--block-bytes N] [--device-format] [--strand plus|both] [--hits] [--identity] [--profile CUTOFF] [--derep] [--primers FWD:REV [--primer-errors PCT] [--primer-window N]] [--fastq-ascii 33|64] [--trunclen N] [--truncq Q] [--truncee E] [--minlen N] [--maxlen N] [--maxns N] [--maxee E] [--maxee-rate R] [--reverse R2.fastq [--merge-minovlen N] [--merge-maxdiffs N] [--merge-maxdiffpct N] [--merge-qcap N]] [--chimera [--chimera-mindelta N] [--chimera-segments S]] [--tags SHEET [--tag-mismatches N] [--tag-offset N] [--tags-both-orientations]] [--contaminants FILE [--contam-minhits N] [--contam-minpct P]] [--uniques [--uniques-minsize N] [--uniques-max-entries N] [--uniques-max-bytes N] [--otus [--otus-minsize N] [--fastidious [--fastidious-boundary N]] [--unoise [--unoise-minsize N] [--unoise-alpha A] [--unoise-maxdiffs D]] [--otus-tax CUTOFF [--otus-tax-agree P]] [--denovo [--denovo-abskew N] [--denovo-mindelta N] [--denovo-segments S]]]]\n"
                             "       (-t/--threads N, --pin, -v, -q of the reference are accepted and ignored)\n"
                             "       (--otus-tax classifies every distinct read of the run once more, after the clustering: one classification per distinct read on top of the run)\n");
             return 64;
@@ -456,6 +468,7 @@ struct Identity {
         {"uniques", true, ""},        // --uniques with its settings: the table is the run's, a resumed run would miss reads
         {"otus", true, ""},           // --otus with its setting: its files are the run's
         {"fastidious", true, ""},     // --fastidious with its boundary: the OTU files are the grafted ones
+        {"unoise", true, ""},         // --unoise with its three settings: the OTU files are the ZOTUs
         {"denovo", true, ""},         // --denovo with its three settings, likewise
         {"otus_tax", true, ""},       // --otus-tax with its cutoff and agreement, likewise
     };
@@ -704,6 +717,12 @@ int validate(Options &o, Plan &p) {
     if (orphan(o.fastidious_opts, o.fastidious, "sets which OTUs are grafted and needs --fastidious")) return 64;
     if (orphan(o.fastidious ? "--fastidious" : "", o.otus, "grafts the small OTUs of the run onto the large ones and needs --otus")) return 64;
     if (o.fastidious) id["fastidious"] = "boundary=" + std::to_string(o.fastidious_boundary ? o.fastidious_boundary : 3);
+    if (orphan(o.unoise_opts, o.unoise, "sets how the distinct reads are denoised and needs --unoise")) return 64;
+    if (orphan(o.unoise ? "--unoise" : "", o.otus, "denoises the distinct reads of the run into the OTUs and needs --otus")) return 64;
+    if (o.unoise && o.fastidious) { fprintf(stderr, "raxtax-hip: --unoise and --fastidious exclude each other (grafting is a pass over a d = 1 clustering)\n"); return 64; }
+    if (o.unoise)
+        id["unoise"] = "minsize=" + std::to_string(o.unoise_params.minsize) + ";alpha=" + std::to_string(o.unoise_params.alpha) +
+                       ";maxdiffs=" + std::to_string(o.unoise_params.max_diffs ? o.unoise_params.max_diffs : RTX_UNOISE_MAX_DIFFS);
     if (orphan(o.denovo_opts, o.denovo, "sets how the OTUs are checked for chimeras and needs --denovo")) return 64;
     if (orphan(o.denovo ? "--denovo" : "", o.otus, "checks the OTUs of the run for chimeras and needs --otus")) return 64;
     if (o.denovo)
@@ -753,9 +772,9 @@ std::vector<Report> report_table(const Options &o, const Plan &p, Sink &s) {
             {"raxtax.screen", p.screen_on, "label\tlength\twindows\thits\tfirst\tsource\tverdict\n", &s.screen}};
 }
 
-// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --fastidious, --denovo, --otus-tax): a run that starts over removes them
+// The files written once, at the end of a run (--profile, --tags with --profile, --uniques, --otus, --fastidious, --unoise, --denovo, --otus-tax): a run that starts over removes them
 const char *const kEndOfRunFiles[] = {"raxtax.profile", "raxtax.samples", "raxtax.uniques", "raxtax.uniques.tsv", "raxtax.otus", "raxtax.otus.map", "raxtax.otus.tsv",
-                                      "raxtax.otus.grafts", "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv", "raxtax.otus.tax"};
+                                      "raxtax.otus.grafts", "raxtax.otus.unoise", "raxtax.otus.denovo", "raxtax.otus.clean", "raxtax.otus.clean.tsv", "raxtax.otus.tax"};
 
 // check_incomplete_output (io.rs:156-187): keep only the lines whose first field is a finished query
 void purge_incomplete(const std::string &path, const std::set<std::string> &done, bool keep_header = false) {
@@ -1376,7 +1395,7 @@ int write_sample_table(const Options &o, const Plan &p, const std::vector<rtx_in
 
 // --otus-tax: the rows of the table classified once more through the first handle, in chunks, in table order (no front stage: the rows went through
 // the front already); every chunk turned into records; then the consensus of every OTU on the first device
-int write_otu_taxonomy(const Options &o, rtx_index *ix, const rtx_tree *tree, const rtx_tally_view &view, const rtx_otu_view_t &ov) {
+int write_otu_taxonomy(const Options &o, rtx_index *ix, const rtx_tree *tree, const rtx_tally_view &view, const rtx_otu_view_t &ov, uint64_t minsize) {
     const auto t0 = std::chrono::steady_clock::now();
     rtx_nodes_view nodes{};
     int trc = rtx_tree_nodes(tree, &nodes);
@@ -1419,7 +1438,7 @@ int write_otu_taxonomy(const Options &o, rtx_index *ix, const rtx_tree *tree, co
     rtx_otu_taxonomy_view_t tv{};
     std::string text;
     if (trc == RTX_OK) trc = rtx_otu_taxonomy_view(tax, &tv);
-    if (trc == RTX_OK) trc = format_two_pass(text, [&](char *buf, uint64_t cap) { return rtx_otu_taxonomy_format(tax, tree, o.otus_minsize, buf, cap); });
+    if (trc == RTX_OK) trc = format_two_pass(text, [&](char *buf, uint64_t cap) { return rtx_otu_taxonomy_format(tax, tree, minsize, buf, cap); });
     uint64_t named = 0;
     for (uint64_t k = 0; trc == RTX_OK && k < tv.n_otus; k++) named += tv.depth[k] != 0;
     rtx_otu_taxonomy_destroy(tax);
@@ -1468,8 +1487,14 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
         rtx_otu *&otu = own.otu;
         rtx_otu_view_t ov{};
         std::string otu_fasta, otu_map, otu_table;
-        trc = rtx_otu_cluster(o.devices[0], sum, nullptr, &otu);
+        // under --unoise the object is the denoiser's: everything below runs on it as on any other, under the larger of the two minsizes
+        const uint64_t otus_minsize = o.unoise ? std::max(o.otus_minsize, o.unoise_params.minsize) : o.otus_minsize;
+        rtx_unoise_view_t uv{};
+        std::string unoise_text;
+        trc = o.unoise ? rtx_otu_unoise(o.devices[0], sum, &o.unoise_params, &otu) : rtx_otu_cluster(o.devices[0], sum, nullptr, &otu);
         if (trc == RTX_OK) trc = rtx_otu_view(otu, &ov);
+        if (trc == RTX_OK && o.unoise) trc = rtx_otu_unoise_view(otu, &uv);
+        if (trc == RTX_OK && o.unoise) trc = format_two_pass(unoise_text, [&](char *buf, uint64_t cap) { return rtx_otu_format_unoise(otu, buf, cap); });
         rtx_graft_view_t gv{};
         std::string grafts;
         if (trc == RTX_OK && o.fastidious) {  // the small OTUs onto the large ones: everything below is written of the grafted object (ov keeps the numbers of the clustering)
@@ -1483,14 +1508,19 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
             }
             if (trc == RTX_OK) trc = format_two_pass(grafts, [&](char *buf, uint64_t cap) { return rtx_otu_format_grafts(otu, buf, cap); });
         }
-        if (trc == RTX_OK) trc = format_two_pass(otu_fasta, [&](char *buf, uint64_t cap) { return rtx_otu_format_fasta(otu, sum, o.otus_minsize, buf, cap); });
+        if (trc == RTX_OK) trc = format_two_pass(otu_fasta, [&](char *buf, uint64_t cap) { return rtx_otu_format_fasta(otu, sum, otus_minsize, buf, cap); });
         if (trc == RTX_OK) trc = format_two_pass(otu_map, [&](char *buf, uint64_t cap) { return rtx_otu_format_map(otu, buf, cap); });
-        if (trc == RTX_OK && p.tags_on) trc = format_two_pass(otu_table, [&](char *buf, uint64_t cap) { return rtx_otu_format_table(otu, names.data(), o.otus_minsize, buf, cap); });
+        if (trc == RTX_OK && p.tags_on) trc = format_two_pass(otu_table, [&](char *buf, uint64_t cap) { return rtx_otu_format_table(otu, names.data(), otus_minsize, buf, cap); });
         if (trc != RTX_OK) { fprintf(stderr, "[ERROR] OTUs: %s\n", rtx_last_error()); return 70; }
-        fprintf(stderr, "[INFO ] --otus: %llu distinct reads, %llu links, %llu OTUs, %u rounds\n", (ull)ov.n_rows, (ull)ov.n_links, (ull)ov.n_otus, ov.rounds);
+        if (o.unoise)
+            fprintf(stderr, "[INFO ] --unoise: %llu distinct reads, %llu ZOTUs, %llu absorbed, %llu left, %llu long, %u tiers\n", (ull)ov.n_rows, (ull)uv.n_zotu, (ull)uv.n_absorbed,
+                    (ull)uv.n_left, (ull)uv.n_long, uv.tiers);
+        else
+            fprintf(stderr, "[INFO ] --otus: %llu distinct reads, %llu links, %llu OTUs, %u rounds\n", (ull)ov.n_rows, (ull)ov.n_links, (ull)ov.n_otus, ov.rounds);
         if (ov.long_rows) fprintf(stderr, "[INFO ] --otus: %llu distinct reads are longer than %d bases and stand alone\n", (ull)ov.long_rows, RTX_OTU_MAX_LEN);
         if (!write_whole(o.prefix + "/raxtax.otus", otu_fasta) || !write_whole(o.prefix + "/raxtax.otus.map", otu_map)) return 74;
         if (p.tags_on && !write_whole(o.prefix + "/raxtax.otus.tsv", otu_table)) return 74;
+        if (o.unoise && !write_whole(o.prefix + "/raxtax.otus.unoise", unoise_text)) return 74;
         if (o.fastidious) {
             fprintf(stderr, "[INFO ] --fastidious: boundary %llu, %llu heavy and %llu light OTUs, %llu grafts, %llu OTUs left\n", (ull)gv.boundary, (ull)gv.heavy_otus, (ull)gv.light_otus,
                     (ull)gv.n_grafts, (ull)gv.n_otus);
@@ -1499,7 +1529,7 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
         if (o.otus_tax_cutoff) {  // which taxon every OTU is (of the grafted OTUs under --fastidious)
             rtx_otu_view_t cur{};
             if (rtx_otu_view(otu, &cur) != RTX_OK) { fprintf(stderr, "[ERROR] OTU taxonomy: %s\n", rtx_last_error()); return 70; }
-            if (const int wrc = write_otu_taxonomy(o, first, tree, view, cur)) return wrc;
+            if (const int wrc = write_otu_taxonomy(o, first, tree, view, cur, otus_minsize)) return wrc;
         }
         if (o.denovo) {  // the OTUs against the more abundant OTUs of the run
             rtx_denovo *&dn = own.dn;
@@ -1508,9 +1538,9 @@ int write_uniques_and_otus(const Options &o, const Plan &p, const std::vector<rt
             trc = rtx_denovo_check(o.devices[0], sum, otu, &o.denovo_params, &dn);
             if (trc == RTX_OK) trc = rtx_denovo_view(dn, &dv);
             if (trc == RTX_OK) trc = format_two_pass(records, [&](char *buf, uint64_t cap) { return rtx_denovo_format_records(dn, buf, cap); });
-            if (trc == RTX_OK) trc = format_two_pass(clean, [&](char *buf, uint64_t cap) { return rtx_denovo_format_fasta(dn, sum, otu, o.otus_minsize, buf, cap); });
+            if (trc == RTX_OK) trc = format_two_pass(clean, [&](char *buf, uint64_t cap) { return rtx_denovo_format_fasta(dn, sum, otu, otus_minsize, buf, cap); });
             if (trc == RTX_OK && p.tags_on)
-                trc = format_two_pass(clean_table, [&](char *buf, uint64_t cap) { return rtx_denovo_format_table(dn, sum, otu, names.data(), o.otus_minsize, buf, cap); });
+                trc = format_two_pass(clean_table, [&](char *buf, uint64_t cap) { return rtx_denovo_format_table(dn, sum, otu, names.data(), otus_minsize, buf, cap); });
             if (trc != RTX_OK) { fprintf(stderr, "[ERROR] de novo chimera check: %s\n", rtx_last_error()); return 70; }
             fprintf(stderr, "[INFO ] --denovo: %llu OTUs, %llu checked, %llu flagged, %u rounds\n", (ull)dv.n_entries, (ull)dv.n_checked, (ull)dv.n_flagged, dv.rounds);
             if (!write_whole(o.prefix + "/raxtax.otus.denovo", records) || !write_whole(o.prefix + "/raxtax.otus.clean", clean)) return 74;

@@ -20,8 +20,21 @@ struct rtx_graft_info {
     double seconds[5] = {0, 0, 0, 0, 0};                   // upload, Bloom, test, verify, resolve and download
 };
 
+// What a denoising result (rtx_otu_unoise, rtx_otu_unoise_host; raxtax_hip.h, "Denoising (UNOISE)") carries beside its clustering
+struct rtx_unoise_info {
+    rtx_unoise_params params{};                    // as used (max_diffs filled in)
+    std::vector<uint8_t> status;                   // [n_rows] RTX_UNOISE_*
+    std::vector<uint32_t> parent, dist, lim;       // [n_rows]
+    std::vector<uint64_t> weight;                  // [n_rows] w[r], for the text
+    uint64_t n_status[4] = {0, 0, 0, 0};
+    uint32_t tiers = 0, launches = 0;              // the device's: 0 for a host result
+    uint64_t pairs = 0, pairs_length = 0, pairs_finished = 0;
+    double seconds[4] = {0, 0, 0, 0};              // upload, pair kernels, bookkeeping, download
+};
+
 struct rtx_otu {
     std::unique_ptr<rtx_graft_info> graft;         // a graft result has one
+    std::unique_ptr<rtx_unoise_info> unoise;       // a denoising result has one
     uint64_t n_rows = 0, n_otus = 0;
     uint32_t columns = 1;
     std::vector<uint32_t> otu, seed;               // [n_rows], [n_otus]

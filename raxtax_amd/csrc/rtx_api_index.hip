@@ -781,6 +781,7 @@ int rtx_set_default_option(int option, uint64_t value) {
     if (option == RTX_DEFAULT_TALLY_HASH_MASK) { set_tally_hash_mask(value ? value : ~0ull); return RTX_OK; }
     if (option == RTX_DEFAULT_OTU_HASH_MASK) { set_otu_hash_mask(value ? value : ~0ull); return RTX_OK; }
     if (option == RTX_DEFAULT_CHIMERA_SLICE) { set_chimera_slice(value ? value : ~0ull); return RTX_OK; }
+    if (option == RTX_DEFAULT_UNOISE_SLICE) { set_unoise_slice(value ? value : ~0ull); return RTX_OK; }
     set_error("rtx_set_default_option: unknown option %d", option);
     return RTX_ERR_INVALID;
 }

@@ -1103,6 +1103,24 @@ uint32_t emul_denovo_allow(uint32_t n_parents, uint32_t tile, uint32_t lim, uint
     for (uint32_t lane = 0; lane < 64u; lane++) denovo_allow(lane, L, tile, lim, out + lane * 4u);
     return L;
 }
+// ---- denoising (rtx_unoise.hip) ----------------------------------------------------------------------------------------------------------
+// One lane of unoise_pair_kernel: x is the pattern (the bit rows of its codes laid out as the wave lays them out in LDS), y the text as
+// packed words.  d(x, y) if it is at most k, else 0xFFFFFFFF -- also when the lengths differ by more than k (the kernel's length test)
+// or k is above 16.  Codes are the low four bits of a byte.
+uint32_t emul_unoise_distance(const uint8_t *x, uint32_t nx, const uint8_t *y, uint32_t ny, uint32_t k) {
+    if (k > kUnoiseMaxDiffs || (nx > ny ? nx - ny : ny - nx) > k) return kUnoiseNoDist;
+    const uint32_t nw = unoise_peq_words(nx);
+    std::vector<uint64_t> peq((size_t)16 * nw, 0), text((ny + 15u) / 16u + 1u, 0);
+    for (uint32_t i = 0; i < nx; i++) {
+        const uint32_t b = unoise_peq_bit(i);
+        peq[(size_t)(x[i] & 15u) * nw + (b >> 6)] |= 1ull << (b & 63u);
+    }
+    unoise_pack(y, ny, text.data());
+    bool finished = false;
+    return unoise_distance(nx, ny, k, [&](uint32_t c, uint32_t j) { return unoise_eq(peq.data() + (size_t)c * nw, j); }, [&](uint32_t t) { return text[t]; }, finished);
+}
+uint32_t emul_unoise_allowed(uint64_t wp, uint64_t we, uint32_t alpha, uint32_t max_diffs) { return unoise_allowed(wp, we, alpha, max_diffs); }
+
 // A checkpoint of denovo_scan_kernel on one tile: emul_chimera_checkpoint with the planes masked by live[8192] (0 / 1 per local entry, laid
 // into the lanes by ref_slot as the live row is) AND the prefix mask of lim.
 int emul_denovo_checkpoint(const uint16_t *counts, const uint8_t *live, int planes, uint32_t n_parents, uint32_t tile, uint32_t lim, uint32_t *count, uint32_t *ref) {

@@ -599,6 +599,7 @@ void set_derep_hash_mask(uint64_t mask);  // RTX_DEFAULT_DEREP_HASH_MASK (rtx_se
 void set_tally_hash_mask(uint64_t mask);  // RTX_DEFAULT_TALLY_HASH_MASK, rtx_tally.hip
 void set_otu_hash_mask(uint64_t mask);    // RTX_DEFAULT_OTU_HASH_MASK, rtx_otu.hip
 void set_chimera_slice(uint64_t cap);     // RTX_DEFAULT_CHIMERA_SLICE, rtx_chimera.hip
+void set_unoise_slice(uint64_t cap);      // RTX_DEFAULT_UNOISE_SLICE, rtx_unoise.hip
 uint64_t chimera_slice_cap();             // the reads or entries a slice of rtx_chimera_run / rtx_denovo_check may hold at most (all ones: no cap)
 // ---- rtx_text.hip
 int enqueue_text(rtx_index *ix, const rtx_index::ResultSet &r);  // the text of the batch being downloaded (synchronous)

@@ -1590,4 +1590,84 @@ RTX_HD void denovo_lane_best(const uint32_t (&pl)[4][NP], const uint32_t (&allow
     }
 }
 
+// ---------------------------------------------------------------------------
+// Denoising (unoise_pair_kernel, rtx_unoise.hip; emul_unoise_distance on x86): the global (Levenshtein) distance of a pattern x of m codes
+// and a text y of n codes under a threshold k <= 16, by Hyyro's bit-vector step on a band of 64 rows that slides down the diagonal.
+//   band     column j (1 .. n; column 0 is the boundary) holds the rows i = j - 31 + b, b = 0 .. 63: every cell with |i - j| <= 16 and more.
+//            Rows i <= 0 are virtual, D[i][j] = j - i (column 0 is V-shaped: vn below bit 32, vp from it), which leaves D[0][j] = j; rows
+//            above m match nothing and nothing above them depends on them.  The top cell of a column ignores the cell above it and the
+//            cell that enters at the bottom ignores the cell to its left: the band computes the minimum over the paths that stay inside
+//            it, which is >= D and equal to D wherever D <= 16 (such a path never leaves |i - j| <= 16).
+//   match    the pattern's match vectors are bit rows, one per code: bit i + 31 of row c is set iff x_i == c (i from 1), so that Eq of
+//            column j is the 64 bits from bit j on (unoise_eq): no shift by a negative amount, no mask at either end.
+//   cut-off  the cell on the final diagonal, S_j = D[j + m - n][j], never decreases with j and ends as D[m][n]: the pair stops at the first
+//            column where S_j > k.  (S_j is at least the band's minimum, so this stops no later than Ukkonen's rule.)  A computed
+//            S_j > k proves D > k, a computed S_n <= k is D.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kUnoiseMaxDiffs = 16;
+constexpr uint32_t kUnoiseNoDist = 0xFFFFFFFFu;
+// k(e, p) of the definition: the largest d in 0 .. max_diffs with (wp >> (alpha d + 1)) >= we
+RTX_HD uint32_t unoise_allowed(uint64_t wp, uint64_t we, uint32_t alpha, uint32_t max_diffs) {
+    uint32_t k = 0;
+    for (uint32_t d = 1; d <= max_diffs; d++) {
+        const uint32_t sh = alpha * d + 1u;
+        if (sh >= 64u || (wp >> sh) < we) break;  // (the left side never grows with d)
+        k = d;
+    }
+    return k;
+}
+// 64-bit words of one code's bit row for a pattern of m codes: bits up to m + 31 are the pattern's, and Eq of column n <= m + 16 reads two words
+RTX_HD uint32_t unoise_peq_words(uint32_t m) { return ((m + kUnoiseMaxDiffs) >> 6) + 2u; }
+RTX_HD uint32_t unoise_peq_bit(uint32_t i0) { return i0 + 32u; }  // of code i0 of the pattern, from 0
+RTX_HD uint64_t unoise_eq(const uint64_t *row, uint32_t j) {
+    const uint32_t w = j >> 6, s = j & 63u;
+    return (row[w] >> s) | ((row[w + 1u] << 1) << (63u - s));
+}
+// len codes (one per byte, below 16) as sixteen to a word, the first in the low bits; words: (len + 15) / 16, the last one zero-padded
+RTX_HD void unoise_pack(const uint8_t *x, uint32_t len, uint64_t *words) {
+    for (uint32_t t = 0; t * 16u < len; t++) {
+        uint64_t w = 0;
+        for (uint32_t i = 0; i < 16u && t * 16u + i < len; i++) w |= (uint64_t)(x[t * 16u + i] & 15u) << (4u * i);
+        words[t] = w;
+    }
+}
+struct UnoiseBand {
+    uint64_t vp, vn;  // vertical deltas +1 / -1 of the band's rows in the column last processed, in that column's frame
+};
+RTX_HD void unoise_band_init(UnoiseBand &b) {
+    b.vp = 0xFFFFFFFF00000000ull;
+    b.vn = 0x00000000FFFFFFFFull;
+}
+// One column: the band moves down by one row (the deltas move one bit down), then Hyyro's step.  Returns D0: bit b set iff the cell of
+// row b equals its diagonal predecessor.
+RTX_HD uint64_t unoise_step(UnoiseBand &b, uint64_t eq) {
+    const uint64_t vp = b.vp >> 1, vn = b.vn >> 1;
+    const uint64_t d0 = (((eq & vp) + vp) ^ vp) | eq | vn;  // (the only carry chain)
+    const uint64_t hp = (vn | ~(d0 | vp)) << 1;
+    const uint64_t hn = (vp & d0) << 1;
+    b.vp = hn | ~(d0 | hp);
+    b.vn = d0 & hp;
+    return d0;
+}
+// d(x, y) if it is at most k, else kUnoiseNoDist.  m, n: the lengths, |m - n| <= k <= 16 (the caller's length test); eq(c, j): Eq of code c
+// in column j (unoise_eq of the row of c); text_word(t): codes 16 t .. 16 t + 15 of the text.  *finished: the last column was reached.
+template <class EQ, class TW>
+RTX_HD uint32_t unoise_distance(uint32_t m, uint32_t n, uint32_t k, const EQ &eq, const TW &text_word, bool &finished) {
+    UnoiseBand b;
+    unoise_band_init(b);
+    const uint64_t diag = 1ull << (m + 31u - n);  // the final diagonal in the band (a mask: no 64-bit shift by a register per column)
+    uint32_t s = m > n ? m - n : n - m;           // S_0
+    uint64_t word = 0;
+    finished = false;
+    for (uint32_t j = 1; j <= n; j++) {
+        if (((j - 1u) & 15u) == 0u) word = text_word((j - 1u) >> 4);
+        const uint64_t d0 = unoise_step(b, eq((uint32_t)word & 15u, j));
+        word >>= 4;
+        s += (d0 & diag) ? 0u : 1u;
+        if (s > k) return kUnoiseNoDist;
+    }
+    finished = true;
+    return s;
+}
+
 }  // namespace rtx
