@@ -648,9 +648,10 @@ int order_batch(rtx_index *ix, bool cluster) {
         }
         if (ix->d_sort_tmp.n < tmp && (rc = ix->d_sort_tmp.alloc(tmp + 256))) return rc;
         if (sketch) {
-            launch_sketch(ix->stream, ix->d_bases.p, ix->in[ix->cur_in].d_base_off.p, n, ix->d_skey_in.p, ix->d_sidx.p);
-            if (ix->d_loc_table.p && ix->locator_opt)
-                launch_locator(ix->stream, ix->d_bases.p, ix->in[ix->cur_in].d_base_off.p, n, ix->d_loc_table.p, ix->n_total, ix->d_skey_in.p);
+            if (ix->d_loc_table.p && ix->locator_opt)  // (takes the min-hashes its key holds itself)
+                launch_locator(ix->stream, ix->d_bases.p, ix->in[ix->cur_in].d_base_off.p, n, ix->d_loc_table.p, ix->n_total, ix->d_skey_in.p, ix->d_sidx.p);
+            else
+                launch_sketch(ix->stream, ix->d_bases.p, ix->in[ix->cur_in].d_base_off.p, n, ix->d_skey_in.p, ix->d_sidx.p);
         }
         if (multi) launch_class_keys(ix->stream, ix->d_skey_in.p, ix->in[ix->cur_in].d_base_off.p, n, ix->key_lim, !sketch, ix->d_sidx.p);
         tmp = ix->d_sort_tmp.n;

@@ -8,7 +8,8 @@
 //
 //   sketch_kernel : per query three min-hashes over its 12-mers (bottom-1 sketches, 21 bits each)
 //                   -> 63-bit key; related sequences agree on a min-hash with probability = their
-//                   12-mer Jaccard similarity, so sorting by the key puts most of them side by side
+//                   12-mer Jaccard similarity, so sorting by the key puts most of them side by side.
+//                   Launched only on handles without a locator: locator_kernel takes the min-hashes of its key itself
 //   locator       : (only when the index was built from the reference sequences) where in the lineage-ordered database
 //                   the relatives of a query sit.  At index build every 12-mer of every reference is entered into a
 //                   direct-mapped table (2^24 entries: lowest reference position holding it, number of occurrences);
@@ -34,53 +35,68 @@ namespace rtx {
 static constexpr int kSketchK = 12;
 static constexpr uint32_t kSketchBits = 21;
 
+// Sixteen windows of a read from p on (nw of them count): their 27 bases come in as four unaligned 8-byte words (one round trip instead of
+// 27 dependent byte loads; the batch buffer is padded by 64 bytes behind its end) and the code rolls over them in registers, as in
+// kmer_extract_kernel.  f(j, code, valid) per window j < nw; valid: no base of the window is an N.
+template <class F>
+__device__ __forceinline__ void roll_windows16(const uint8_t *p, uint32_t nw, F f) {
+    unsigned long long v[4];
+    __builtin_memcpy(v, p, 32);
+    uint32_t code = 0, run = 0;
+#pragma unroll
+    for (int b = 0; b < 16 + kSketchK - 1; b++) {
+        const uint32_t c = (uint32_t)(v[b >> 3] >> ((b & 7) * 8)) & 0xFFu;
+        const bool ok = c == 1u || c == 2u || c == 4u || c == 8u;
+        code = ((code << 2) | (((uint32_t)__ffs((int)c) - 1u) & 3u)) & 0xFFFFFFu;
+        run = ok ? run + 1u : 0u;
+        if (b >= kSketchK - 1 && (uint32_t)(b - (kSketchK - 1)) < nw) f((uint32_t)(b - (kSketchK - 1)), code, run >= (uint32_t)kSketchK);
+    }
+}
+
+// The first kHashes multiplicative hashes of one 12-mer into a lane's minima: three for the min-hash key, two for a key led by the locator
+template <int kHashes>
+__device__ __forceinline__ void minhash_add(uint32_t code, uint32_t (&m)[kHashes]) {
+    constexpr uint64_t mult[3] = {0x9E3779B97F4A7C15ull, 0xC2B2AE3D27D4EB4Full, 0x165667B19E3779F9ull};
+    static_assert(kHashes >= 1 && kHashes <= 3, "three hashes are defined");
+#pragma unroll
+    for (int i = 0; i < kHashes; i++) {
+        const uint32_t h = (uint32_t)(((uint64_t)code * mult[i]) >> (64 - kSketchBits));
+        m[i] = h < m[i] ? h : m[i];
+    }
+}
+
+// The windows [lo, hi) of a read over the wave: lane l rolls over [lo + l * wpl, lo + (l + 1) * wpl), sixteen at a time
+template <int kHashes>
+__device__ __forceinline__ void minhash_span(const uint8_t *seq, uint64_t lo, uint64_t hi, uint32_t lane, uint32_t (&m)[kHashes]) {
+    const uint64_t wpl = (hi - lo + 63) / 64;
+    const uint64_t w0 = lo + (uint64_t)lane * wpl;
+    const uint64_t w1 = w0 + wpl < hi ? w0 + wpl : hi;
+    for (uint64_t i = w0; i < w1; i += 16)
+        roll_windows16(seq + i, w1 - i < 16 ? (uint32_t)(w1 - i) : 16u, [&](uint32_t, uint32_t code, bool valid) {
+            if (valid) minhash_add(code, m);
+        });
+}
+
+static constexpr uint32_t kSketchNone = (1u << kSketchBits) - 1u;  // the min-hash of a read without a 12-mer
+
+__device__ __forceinline__ uint64_t sketch_key(uint32_t m1, uint32_t m2, uint32_t m3) {
+    return ((uint64_t)m1 << (2 * kSketchBits)) | ((uint64_t)m2 << kSketchBits) | m3;
+}
+
+// The whole min-hash key of a read, in every lane (sketch_kernel; locator_kernel for the reads it cannot place)
+__device__ __forceinline__ uint64_t sketch_key_of(const uint8_t *seq, uint64_t len, uint32_t lane) {
+    uint32_t m[3] = {kSketchNone, kSketchNone, kSketchNone};
+    if (len >= (uint64_t)kSketchK) minhash_span(seq, 0, len - kSketchK + 1, lane, m);
+    return sketch_key(wave_min_u32(m[0]), wave_min_u32(m[1]), wave_min_u32(m[2]));
+}
+
 __global__ __launch_bounds__(64) void sketch_kernel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ off,
                                                     uint64_t *__restrict__ keys, uint32_t *__restrict__ idx) {
     const uint32_t q = blockIdx.x, lane = threadIdx.x;
     const uint64_t b0 = off[q], len = off[q + 1] - b0;
-    const uint8_t *seq = bases + b0;
-    const uint32_t none = (1u << kSketchBits) - 1u;
-    uint32_t m1 = none, m2 = none, m3 = none;
-    if (len >= (uint64_t)kSketchK) {
-        // lane l rolls over the windows [l*wpl, (l+1)*wpl), sixteen at a time: their 27 bases come in as four unaligned 8-byte words
-        // (one round trip instead of 27 dependent byte loads; the batch buffer is padded by 64 bytes behind its end) and the
-        // code rolls over them in registers, as in kmer_extract_kernel
-        const uint64_t nwin = len - kSketchK + 1;
-        const uint64_t wpl = (nwin + 63) / 64;
-        const uint64_t w0 = (uint64_t)lane * wpl;
-        const uint64_t w1 = w0 + wpl < nwin ? w0 + wpl : nwin;
-        for (uint64_t i = w0; i < w1; i += 16) {
-            unsigned long long v[4];
-            __builtin_memcpy(v, seq + i, 32);
-            const uint32_t nw = w1 - i < 16 ? (uint32_t)(w1 - i) : 16u;
-            uint32_t code = 0, run = 0;
-#pragma unroll
-            for (int b = 0; b < 16 + kSketchK - 1; b++) {
-                const uint32_t c = (uint32_t)(v[b >> 3] >> ((b & 7) * 8)) & 0xFFu;
-                const bool ok = c == 1u || c == 2u || c == 4u || c == 8u;
-                code = ((code << 2) | (((uint32_t)__ffs((int)c) - 1u) & 3u)) & 0xFFFFFFu;
-                run = ok ? run + 1u : 0u;
-                if (b >= kSketchK - 1 && (uint32_t)(b - (kSketchK - 1)) < nw && run >= (uint32_t)kSketchK) {
-                    const uint64_t x = code;
-                    const uint32_t h1 = (uint32_t)((x * 0x9E3779B97F4A7C15ull) >> (64 - kSketchBits));
-                    const uint32_t h2 = (uint32_t)((x * 0xC2B2AE3D27D4EB4Full) >> (64 - kSketchBits));
-                    const uint32_t h3 = (uint32_t)((x * 0x165667B19E3779F9ull) >> (64 - kSketchBits));
-                    m1 = h1 < m1 ? h1 : m1;
-                    m2 = h2 < m2 ? h2 : m2;
-                    m3 = h3 < m3 ? h3 : m3;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o1 = __shfl_xor(m1, d, 64), o2 = __shfl_xor(m2, d, 64), o3 = __shfl_xor(m3, d, 64);
-        m1 = o1 < m1 ? o1 : m1;
-        m2 = o2 < m2 ? o2 : m2;
-        m3 = o3 < m3 ? o3 : m3;
-    }
+    const uint64_t key = sketch_key_of(bases + b0, len, lane);
     if (lane == 0) {
-        keys[q] = ((uint64_t)m1 << (2 * kSketchBits)) | ((uint64_t)m2 << kSketchBits) | m3;
+        keys[q] = key;
         idx[q] = q;
     }
 }
@@ -130,9 +146,11 @@ __global__ __launch_bounds__(256) void loc_finish_kernel(uint32_t *__restrict__ 
 }
 
 // ---------------------------------------------------------------------------
-// Locator of a query: one wave per query.
+// Locator of a query: one wave per query.  On a handle with a locator table this kernel is the whole key stage: it takes the min-hashes
+// the key holds itself, so the bases are read once and no second grid of single-wave workgroups runs in front of it.
 //   1. lane l rolls over the windows [l * wpl, (l + 1) * wpl) of the first kLocWin windows (their wpl + 11 bases in one round trip,
-//      as sketch_kernel) and leaves their 12-mer codes in LDS;
+//      roll_windows16), leaves their 12-mer codes in LDS and takes the first two min-hashes of them; the windows beyond kLocWin
+//      only add to the min-hashes (minhash_span);
 //   2. lane l looks up the windows 2 l, 2 (l + 64), ... (kLocStride; four table loads in flight), keeps the positions in
 //      LDS and votes for coarse bins of 2^bin_shift references.  Most lanes vote for the SAME bin -- that is the point --
 //      and LDS atomics on one address are served lane by lane (about 100 cycles for 64 of them): the lanes that agree
@@ -140,7 +158,9 @@ __global__ __launch_bounds__(256) void loc_finish_kernel(uint32_t *__restrict__ 
 //   3. the best pair of neighbouring coarse bins wins, then bins of a sixteenth inside it.
 // Votes are u16 pairs in u32 words (a bin gets at most kLocWin of them).  Queries longer than kLocWin + 11 bases are
 // located by their first kLocWin windows.  keys[q] = loc << 39 | (min-hash key >> 24): 24 bits of position, m1 and the
-// high 18 bits of m2.
+// high 18 bits of m2 -- the third min-hash is not in the key and is not taken.  A query that ends without a vote (shorter than a
+// 12-mer, or none of its 12-mers in the table) gets the whole min-hash key, as sketch_kernel computes it (sketch_key_of: rare, so
+// it simply starts over).
 // ---------------------------------------------------------------------------
 static constexpr uint32_t kLocMaxBins = 8192;    // coarse bins (LDS: 16 KiB)
 static constexpr uint32_t kLocFineDiv = 16;      // fine bins per coarse bin
@@ -169,40 +189,35 @@ __device__ __forceinline__ void vote_bins(uint32_t *h, uint32_t b, bool valid, u
 
 __global__ __launch_bounds__(64) void locator_kernel(const uint8_t *__restrict__ bases, const uint64_t *__restrict__ off,
                                                      const uint32_t *__restrict__ table, uint32_t bin_shift, uint32_t n_bins,
-                                                     uint64_t *__restrict__ keys) {
+                                                     uint64_t *__restrict__ keys, uint32_t *__restrict__ idx) {
     extern __shared__ __attribute__((aligned(16))) uint32_t h[];  // n_bins / 2 + 2 words (rounded up to four): the coarse bins as u16 pairs
     __shared__ uint32_t lcode[kLocWin / kLocStride];  // 12-mer codes of the windows that vote, then the positions found for them
     __shared__ uint32_t hf[kLocFineDiv + 2];   // 2 * kLocFineDiv + 1 fine bins as u16 pairs
     const uint32_t q = blockIdx.x, lane = threadIdx.x;
     const uint64_t b0 = off[q], len = off[q + 1] - b0;
-    if (len < (uint64_t)kSketchK) return;  // wave-uniform: the min-hash key stays
-    const uint64_t old_key = keys[q];
+    if (lane == 0) idx[q] = q;
     const uint8_t *seq = bases + b0;
+    if (len < (uint64_t)kSketchK) {  // wave-uniform: the min-hash key of a read without a 12-mer
+        if (lane == 0) keys[q] = sketch_key(kSketchNone, kSketchNone, kSketchNone);
+        return;
+    }
+    uint32_t m[2] = {kSketchNone, kSketchNone};  // the two min-hashes a key led by the position holds
     const uint32_t nwin = (uint32_t)(len - kSketchK + 1 < (uint64_t)kLocWin ? len - kSketchK + 1 : kLocWin);
     const uint32_t words = n_bins / 2 + 2;
     for (uint32_t i = lane; i < (words + 3u) / 4u; i += 64) reinterpret_cast<uint4 *>(h)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (lane < kLocFineDiv + 2) hf[lane] = 0;
-    {   // 1. codes of this lane's run of windows (at most 16: nwin <= kLocWin): its 27 bases as four unaligned 8-byte words, as sketch_kernel
+    {   // 1. codes of this lane's run of windows (at most 16: nwin <= kLocWin): one piece of roll_windows16
         const uint32_t wpl = (nwin + 63u) / 64u;
         const uint32_t w0 = lane * wpl, w1 = w0 + wpl < nwin ? w0 + wpl : nwin;
         static_assert(kLocWin <= 1024u && kLocWin % kLocStride == 0u, "a lane's run of windows fits one piece of 16");
-        if (w0 < w1) {
-            unsigned long long v[4];
-            __builtin_memcpy(v, seq + w0, 32);
-            const uint32_t nw = w1 - w0;
-            uint32_t code = 0, run = 0;
-#pragma unroll
-            for (int b = 0; b < 16 + kSketchK - 1; b++) {
-                uint32_t two;
-                const bool ok = base_code((uint32_t)(v[b >> 3] >> ((b & 7) * 8)) & 0xFFu, two);
-                code = ((code << 2) | two) & 0xFFFFFFu;
-                run = ok ? run + 1u : 0u;
-                if (b >= kSketchK - 1 && (uint32_t)(b - (kSketchK - 1)) < nw) {
-                    const uint32_t w = w0 + (uint32_t)(b - (kSketchK - 1));
-                    if (w % kLocStride == 0u) lcode[w / kLocStride] = run >= (uint32_t)kSketchK ? code : kLocNone;
-                }
-            }
-        }
+        if (w0 < w1)
+            roll_windows16(seq + w0, w1 - w0, [&](uint32_t j, uint32_t code, bool valid) {
+                const uint32_t w = w0 + j;
+                if (w % kLocStride == 0u) lcode[w / kLocStride] = valid ? code : kLocNone;
+                if (valid) minhash_add(code, m);
+            });
+        const uint64_t total = len - kSketchK + 1;
+        if (total > (uint64_t)kLocWin) minhash_span(seq, kLocWin, total, lane, m);  // wave-uniform
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -229,7 +244,11 @@ __global__ __launch_bounds__(64) void locator_kernel(const uint8_t *__restrict__
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    if (!__ballot(any != 0u)) return;  // no vote: the min-hash key stays
+    if (!__ballot(any != 0u)) {  // no vote: the whole min-hash key
+        const uint64_t key = sketch_key_of(seq, len, lane);
+        if (lane == 0) keys[q] = key;
+        return;
+    }
     // 3. best pair of neighbouring coarse bins (B, B + 1): value << 16 | (0xFFFF - B), the lowest B among equals
     auto bin = [&](uint32_t b) { return (h[b >> 1] >> ((b & 1u) * 16u)) & 0xFFFFu; };
     uint32_t best = 0;
@@ -263,7 +282,8 @@ __global__ __launch_bounds__(64) void locator_kernel(const uint8_t *__restrict__
         fine = 0xFFFFu - (fb & 0xFFFFu);
     }
     const uint64_t loc = ((uint64_t)B * kLocFineDiv + fine) & 0xFFFFFFull;
-    if (lane == 0) keys[q] = (loc << 39) | (old_key >> 24);
+    const uint32_t m1 = wave_min_u32(m[0]), m2 = wave_min_u32(m[1]);
+    if (lane == 0) keys[q] = (loc << 39) | (sketch_key(m1, m2, 0u) >> 24);
 }
 
 // Length classes (rtx_index.hpp: BatchClass): the class of a query -- the number of the limits its length exceeds -- leads the sort key, so
@@ -308,10 +328,10 @@ uint32_t loc_bin_shift(uint64_t n_refs) {
     return sh;
 }
 void launch_locator(hipStream_t s, const uint8_t *bases, const uint64_t *off, uint32_t n_q, const uint32_t *table, uint64_t n_refs,
-                    uint64_t *keys) {
+                    uint64_t *keys, uint32_t *idx) {
     const uint32_t sh = loc_bin_shift(n_refs);
     const uint32_t n_bins = (uint32_t)((n_refs + (1ull << sh) - 1) >> sh);
-    hipLaunchKernelGGL(locator_kernel, dim3(n_q), dim3(64), ((n_bins / 2 + 2 + 3) & ~3u) * 4, s, bases, off, table, sh, n_bins, keys);
+    hipLaunchKernelGGL(locator_kernel, dim3(n_q), dim3(64), ((n_bins / 2 + 2 + 3) & ~3u) * 4, s, bases, off, table, sh, n_bins, keys, idx);
 }
 void launch_invert_perm(hipStream_t s, const uint32_t *perm, uint32_t n, uint32_t *inv) {
     hipLaunchKernelGGL(invert_perm_kernel, dim3((n + 255) / 256), dim3(256), 0, s, perm, n, inv);

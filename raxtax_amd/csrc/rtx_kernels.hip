@@ -139,6 +139,14 @@ __device__ __forceinline__ unsigned long long transpose64(unsigned long long x, 
     return x;
 }
 
+// Where k-mer k sits in the 65 536-bit set of kmer_extract_kernel.  The read-out gives lane l the sixteen 64-bit words 16 l .. 16 l + 15;
+// read in their natural places, the lanes of a 32-lane group would meet on two bank pairs (32 l + 2 j dwords: sixteen addresses per bank).
+// The low four bits of the word index are therefore XORed with l >> 1: in read j the lanes l and l + 1 take opposite halves of the 64
+// banks and the sixteen pairs of lanes sixteen different bank pairs -- no conflicts for ds_read_b64, whose groups are the two 32-lane halves.
+// The atomicOr of the window phase lands on scattered words either way.
+__device__ __forceinline__ uint32_t kmer_set_slot(uint32_t k) { return k ^ ((k >> 5) & 0x3C0u); }
+static constexpr uint32_t kKmerStage = 4096;  // k-mers of a read staged in the set's 8 KB after the read-out (u16); a multiple of 256
+
 // kTilesOnly: the launch behind tile pruning (mode 2) -- without the 8 KB k-mer set of the extraction in LDS twice as many of its waves fit a CU
 // (a chain of gathers per query: the waves in flight are what hides them)
 template <bool kTilesOnly>
@@ -194,33 +202,50 @@ __global__ __launch_bounds__(64) void kmer_extract_kernel(KmerParams p) {
                 const bool ok = c == 1u || c == 2u || c == 4u || c == 8u;
                 k = ((k << 2) | (((uint32_t)__ffs((int)c) - 1u) & 3u)) & 0xFFFFu;  // first base of the window in bits 15:14
                 run = ok ? run + 1u : 0u;
-                if (b >= 7 && (uint32_t)(b - 7) < nw && run >= 8u) atomicOr(&bm[k >> 5], 1u << (k & 31u));
+                if (b >= 7 && (uint32_t)(b - 7) < nw && run >= 8u) {
+                    const uint32_t ks = kmer_set_slot(k);
+                    atomicOr(&bm[ks >> 5], 1u << (ks & 31u));
+                }
             }
         }
     }
     __syncthreads();
 
-    // ascending read-out: round r covers the 64-bit words r*64 .. r*64+63 of the set (conflict-free LDS reads); sixteen
-    // scans instead of thirty-two with 32-bit words
+    // ascending read-out: lane l owns the sixteen consecutive 64-bit words 16 l .. 16 l + 15 of the set (the codes 1024 l .. 1024 l + 1023),
+    // reads them into registers (kmer_set_slot: conflict-free) and counts them: ONE scan over the wave gives every lane the position of its
+    // first k-mer.  With the whole set in registers its 8 KB are free: the k-mers are staged there as u16 (the first kKmerStage of a read;
+    // what lies beyond goes to kout directly), the row translation below reads them from LDS instead of from kout behind a round trip of
+    // stores and loads, and kout is written with 64 consecutive values per store.
     uint16_t *kout = p.kmers + (size_t)q * p.kstride;
-    const unsigned long long *bm64 = reinterpret_cast<const unsigned long long *>(bm);
-    uint32_t base = 0;
-    for (uint32_t r = 0; r < 16; r++) {
-        unsigned long long word = bm64[r * 64 + lane];
-        const uint32_t cnt = (uint32_t)__popcll(word);
-        const uint32_t incl = wave_incl_scan_u32(cnt);
-        uint32_t pos = base + incl - cnt;
-        const uint32_t kbase = (r * 64 + lane) * 64;
-        while (word) {
-            const uint32_t bit = (uint32_t)__builtin_ctzll(word);
-            word &= word - 1;
-            if (pos < p.kstride) kout[pos] = (uint16_t)(kbase + bit);
-            pos++;
+    uint16_t *stage = reinterpret_cast<uint16_t *>(bm);
+    {
+        const unsigned long long *bm64 = reinterpret_cast<const unsigned long long *>(bm);
+        const uint32_t sw = (lane >> 1) & 15u;
+        unsigned long long w[16];
+        uint32_t cnt = 0;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            w[j] = bm64[lane * 16u + ((uint32_t)j ^ sw)];
+            cnt += (uint32_t)__popcll(w[j]);
         }
-        base += (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        const uint32_t incl = wave_incl_scan_u32(cnt);
+        t = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+        uint32_t pos = incl - cnt;
+        __syncthreads();  // every word of the set is in registers: the staging may overwrite it
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            unsigned long long word = w[j];
+            const uint32_t kbase = (lane * 16u + (uint32_t)j) * 64u;
+            while (word) {
+                const uint32_t bit = (uint32_t)__builtin_ctzll(word);
+                word &= word - 1;
+                if (pos < kKmerStage) stage[pos] = (uint16_t)(kbase + bit);
+                else if (pos < p.kstride) kout[pos] = (uint16_t)(kbase + bit);
+                pos++;
+            }
+        }
     }
-    t = base;
-    __syncthreads();  // kout visible to the whole wave
+    __syncthreads();  // the staged k-mers (and what went to kout) visible to the whole wave
     // A read that holds EVERY 8-mer (t = 65 536; only reads of 65 543 bases or more can): the reference asserts that t fits a u16
     // (raxtax.rs:56) and aborts.  Here the query is reported (RTX_Q_ALL_KMERS, set by finalise_kernel from t_all) and counted as one
     // without k-mers; the other queries of the batch are not affected.
@@ -233,10 +258,12 @@ __global__ __launch_bounds__(64) void kmer_extract_kernel(KmerParams p) {
     // (load, gather, store) pays two full round trips per chunk.
     for (uint32_t i0 = 0; i0 < tt; i0 += 256) {
         uint32_t kk[4], row[4], ll[4];
+        const bool staged = i0 < kKmerStage;  // wave-uniform: a turn lies on one side (kKmerStage is a multiple of 256)
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const uint32_t i = i0 + u * 64 + lane;
-            kk[u] = i < tt ? (uint32_t)kout[i] : 0xFFFFFFFFu;
+            kk[u] = 0xFFFFFFFFu;
+            if (i < tt) kk[u] = staged ? (uint32_t)stage[i] : (uint32_t)kout[i];
         }
 #pragma unroll
         for (int u = 0; u < 4; u++) {
@@ -255,6 +282,10 @@ __global__ __launch_bounds__(64) void kmer_extract_kernel(KmerParams p) {
             if (row[u] != kEmptyRow) rout[nrows + __popcll(m & lt_mask)] = row[u];
             nrows += (uint32_t)__popcll(m);
         }
+    }
+    {  // the staged k-mers to kout (a read that holds every 8-mer included: its first k-mers are stored as any other read's)
+        const uint32_t ns = t < p.kstride ? (t < kKmerStage ? t : kKmerStage) : (p.kstride < kKmerStage ? p.kstride : kKmerStage);
+        for (uint32_t i = lane; i < ns; i += 64) kout[i] = stage[i];
     }
     for (uint32_t i = nrows + lane; i < ((nrows + 63u) & ~63u); i += 64) rout[i] = p.zero_row;
     __syncthreads();  // rout visible to the whole wave

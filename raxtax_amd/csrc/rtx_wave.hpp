@@ -60,6 +60,15 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
     return ab > cd ? ab : cd;
 }
 
+// Minimum over the 64 lanes, in every lane
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+    v = row16_min_u32(v);
+    const uint32_t a = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), b = (uint32_t)__builtin_amdgcn_readlane((int)v, 16),
+                   c = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), d = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
+    const uint32_t ab = a < b ? a : b, cd = c < d ? c : d;
+    return ab < cd ? ab : cd;
+}
+
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
